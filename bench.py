@@ -35,7 +35,18 @@ Multi-GPU (--scaling):
   --emulate-world W (one GPU): the W ranks' strong-scaling steps one after the other on this GPU, no collective: per-rank step
   times for the scaling estimate in DESIGN.md section 6.
 
-The JSON line also carries:
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs (--dump-outputs DIR) and the
+JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, config, kernel_ms: the per-phase event times of the timed
+steps).  Everything that needs work after the timed steps runs with --full only: the roofline block and its extra pass (except
+c2b, whose byte model needs no pass), the CPU baseline and its parity gate (exit code 3 when it fails), the c2a extras and the
+host-pointer call, the plan timing of strong scaling and the check of the gathered scores against a single pass.
+
+--dump-outputs DIR: rank 0 writes what the timed path returned in its last step, before anything else runs on the device, as
+DIR/scores.npy (float64; c4: [frames][anchors]; strong c2a / c5: in anchor-pair order; c3 and weak runs at N > 1: rank 0's own
+pairs).  Inputs are seeded, so the same arguments give the same inputs in every run.  Above 64 MB a fixed, seeded sample of the
+scores is written instead, with its flat positions in DIR/scores_index.npy.
+
+The JSON line of --full also carries:
   roofline      dominant kernel's ALGORITHMIC bytes per launch (B_pair = (n_A+n_B)*28 + 16) / its average
                 launch duration (HIP events on the launch stream, recorded by the C library) against the 8 TB/s HBM peak
                 (`frac`, as section 8d defines it), plus what actually binds the kernel: `fabric_measured_frac` (fabric-side
@@ -62,6 +73,25 @@ sys.path.insert(0, str(ROOT))
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 PROFILE_ROUND = "r06"
 PRIME_STEPS = 6  # untimed set-up passes in front of the warm-up steps (Harness.run)
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirpath: str, **arrays) -> None:
+    """--dump-outputs: every array as DIR/<name>.npy in float64.  An array that would not fit into what is left of the limit is
+    replaced by a fixed, seeded sample of its elements (flattened) and DIR/<name>_index.npy holds their positions."""
+    out = Path(dirpath)
+    out.mkdir(parents=True, exist_ok=True)
+    left = DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes + 128 > left:  # (128: the .npy header)
+            k = max(0, (left - 256) // 16)  # sample + positions, 8 B each
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=min(k, a.size), replace=False))
+            np.save(out / f"{name}_index.npy", idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+            left -= idx.size * 8 + 128
+        np.save(out / f"{name}.npy", a)
+        left -= a.nbytes + 128
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -422,11 +452,14 @@ def run_c4(args, torch, dist, dev, rank, world, use_dist):
     elapsed = Harness(args, torch, dist, dev, use_dist).run(step, on_timed_start=start_collect)
     collect[0] = False
     phase = {k: v / max(args.steps, 1) for k, v in phase.items()}
-    for f0 in starts:  # environment points of the whole job (outside the timed region)
-        nf = min(chunk, n_frames - f0)
-        sess.load_atom_frames_dev(buf, frames[f0:f0 + nf])
-        sess.from_primitives(ref, buf, anchors[: nf * len(la)], 10.0, out=out[f0 * len(la):(f0 + nf) * len(la)])
-        env_points[0] += sess.last_env_points()
+    if rank == 0 and args.dump_outputs:  # the last timed step's scores
+        dump_outputs(args.dump_outputs, scores=out.cpu().numpy().reshape(n_frames, len(la)))
+    if args.full:
+        for f0 in starts:  # environment points of the whole job (outside the timed region)
+            nf = min(chunk, n_frames - f0)
+            sess.load_atom_frames_dev(buf, frames[f0:f0 + nf])
+            sess.from_primitives(ref, buf, anchors[: nf * len(la)], 10.0, out=out[f0 * len(la):(f0 + nf) * len(la)])
+            env_points[0] += sess.last_env_points()
     scores = out.cpu().numpy().reshape(n_frames, len(la))
     result = None
     if rank == 0:
@@ -436,13 +469,15 @@ def run_c4(args, torch, dist, dev, rank, world, use_dist):
         label = (f"C4: 1 reference vs {n_frames} frames/GPU of a {n_prim}-primitive-atom system ({n_src} float32 source atoms/frame, "
                  f"converted on the device), {len(la)} per-residue anchors/frame, accept_same=False, uniform[3,10], thr 10 A, "
                  f"chunks of {chunk} frames")
-        result = base_result(args, world, p * world, elapsed, label, {"pairs_per_gpu": p, "mean_env_points_per_pair": env_points[0] / p,
+        result = base_result(args, world, p * world, elapsed, label, {"pairs_per_gpu": p,
                                                                       "sharding": "frames across ranks, no exchange step, scores stay on their rank",
                                                                       "sessions": n_sess})
-        result["roofline"] = roofline_block("c4" if dom == "sweep" else "c4_env",
-                                            {"env": "k_env_group<false, 320, 6> (four environments per wavefront; side B: one environment per pair, no de-duplication)",
-                                             "sweep": "k_sweep_duo<8, 16 lanes, 240 events> (four pairs per wavefront)"}[dom], algo / len(starts),
-                                            phase[dom] / len(starts), len(starts), step_ms=result["ms_per_step"])
+        if args.full:
+            result["config"]["mean_env_points_per_pair"] = env_points[0] / p
+            result["roofline"] = roofline_block("c4" if dom == "sweep" else "c4_env",
+                                                {"env": "k_env_group<false, 320, 6> (four environments per wavefront; side B: one environment per pair, no de-duplication)",
+                                                 "sweep": "k_sweep_duo<8, 16 lanes, 240 events> (four pairs per wavefront)"}[dom], algo / len(starts),
+                                                phase[dom] / len(starts), len(starts), step_ms=result["ms_per_step"])
         result["kernel_ms"] = phase
         result["extras"] = {"k_frames_centroids": {"ms_per_step": phase["convert"], "algorithmic_bytes_per_step": conv_bytes,
                                                    "GB_per_s": conv_bytes / max(phase["convert"], 1e-9) / 1e6,
@@ -578,19 +613,24 @@ def run_c3(args, torch, dist, dev, rank, world, use_dist):
     out, pairs, p, batch, n_touched = out_holder["main"]
     phase_ms = phases_holder["main"]
     total_pairs = len(w["spairs"]) * len(la) * (1 if args.scaling == "strong" else world)
+    if rank == 0 and args.dump_outputs:  # the last timed step's scores (this rank's decoy pairs)
+        dump_outputs(args.dump_outputs, scores=out.cpu().numpy())
     result = None
     if rank == 0:
-        if p:
+        if p and args.full:
             sess.from_primitives(batch, batch, torch.from_numpy(np.ascontiguousarray(pairs)).to(dev), w["thr"], out=out)
         env_points = sess.last_env_points() if p else 0
         algo = env_points * 32 + 16 * p
         dom = max(("env", "sweep"), key=lambda k: phase_ms[k])
         result = base_result(args, world, total_pairs, elapsed, w["label"],
-                             {"pairs_this_rank": p, "mean_env_points_per_pair": env_points / max(p, 1),
+                             {"pairs_this_rank": p,
                               "sharding": (f"tiles of the 50 x 50 decoy-pair matrix, one set per rank; a rank holds the decoys its tiles touch ({n_touched} here)"
                                            if args.scaling == "strong" else "every rank scores its own all-vs-all job"),
                               **collective_note(args, world, use_dist)})
-        result["roofline"] = roofline_block("c3", {"env": "k_env_group", "sweep": "k_sweep_duo<8, 16 lanes, 240 events> (four pairs per wavefront)"}[dom], algo, phase_ms[dom], step_ms=result["ms_per_step"])
+        if args.full:
+            result["config"]["mean_env_points_per_pair"] = env_points / max(p, 1)
+            result["roofline"] = roofline_block("c3", {"env": "k_env_group", "sweep": "k_sweep_duo<8, 16 lanes, 240 events> (four pairs per wavefront)"}[dom], algo,
+                                                phase_ms[dom], step_ms=result["ms_per_step"])
         result["kernel_ms"] = phase_ms
         if emulated:
             emulated["single_gpu_ms"] = elapsed / args.steps * 1e3
@@ -654,6 +694,8 @@ def run_c2b(args, torch, dist, dev, rank, world, use_dist):
 
     elapsed = Harness(args, torch, dist, dev, use_dist).run(step, on_timed_start=start_collect)
     phase_ms = {k: v / max(args.steps, 1) for k, v in phase_ms.items()}
+    if rank == 0 and args.dump_outputs:  # the last timed step's scores
+        dump_outputs(args.dump_outputs, scores=out.cpu().numpy())
     result = None
     if rank == 0:
         algo = n * (2 * n * 28 + 16)  # every pair reads both whole structures: B_pair = (n_A + n_B) * 28 + 16
@@ -837,6 +879,16 @@ def run_pairs(args, torch, dist, dev, rank, world, use_dist):
     st = state["main"]
     phase_ms = st["phase_ms"]
     total_pairs = p if strong else p * world
+    if rank == 0 and args.dump_outputs:  # the last timed step's scores, in anchor-pair order
+        if not strong:
+            last = st["out"].cpu().numpy()
+        elif world == 1:  # the one share is the whole list: scores and their positions in the list, as the step left them
+            share = st["out"][:, :state["main_n_mine"]].cpu().numpy()
+            last = np.full(p, np.nan)
+            last[share[1].view(np.int64)] = share[0]
+        else:  # restored by rank 0 from the per-step gather (main() refuses --gather end here)
+            last = st["full"].cpu().numpy()
+        dump_outputs(args.dump_outputs, scores=last)
 
     # Outside the timed region: the same clouds with every anchor used ONCE (pairs (i, i), i < N) -- no environment is
     # shared between pairs, so this is the per-call cost of a plain from_primitives(i, i) call with device-resident inputs.
@@ -847,6 +899,20 @@ def run_pairs(args, torch, dist, dev, rank, world, use_dist):
         emulated["estimated_speedup_median_rank"] = emulated["single_gpu_ms"] / float(np.median(emulated["per_rank_ms"]))
         emulated["note"] = "the W ranks' shares timed one after the other on ONE GPU, no collective: an estimate, not a measurement on W GPUs"
         extras["emulated_strong_scaling"] = emulated
+    if not args.full:  # a plain run: the headline, nothing that needs another pass
+        line = None
+        if rank == 0:
+            line = base_result(args, world, total_pairs, elapsed, w["label"],
+                               {"pairs_total" if strong else "pairs_per_gpu": p,
+                                "sharding": ("pairs binned by their side-A anchor (library kernels, every rank the same rule), every rank holds both structures"
+                                             if strong else "every rank scores its own pair list of the same two structures"),
+                                **collective_note(args, world, use_dist)})
+            line["kernel_ms"] = phase_ms
+            if extras:
+                line["extras"] = extras
+        for s_ in sessions:
+            s_.close()
+        return line
     if rank == 0 and args.workload == "c2a" and not args.no_cpu_baseline and not strong:  # profiling runs launch only the timed steps
         n_atoms = w["n"]
         uniq = anchors[:n_atoms].contiguous()
@@ -1068,8 +1134,17 @@ def main():
     ap.add_argument("--streams", type=int, default=None, choices=[1, 2],
                     help="c2a / c5 / c3: HIP streams the two alternating sessions enqueue on (default: 1 at N = 1 -- clean per-kernel times --, "
                          "2 for N > 1 and --emulate-world: consecutive steps overlap)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle leg, the parity gate and the extras (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU oracle leg, the parity gate and the extras (profiling runs); a plain run has none of them")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline block, CPU baseline + parity gate, extras, plan timing, gather check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores of the last timed step to DIR/scores.npy (rank 0; at most 64 MB, else a seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.no_cpu_baseline = True
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (a CHILD process, before this one has
         # imported torch or touched a GPU -- never an exec), relay their output and exit with the launcher's code
@@ -1089,6 +1164,8 @@ def main():
         args.streams = 2 if (args.gpus > 1 or args.emulate_world > 1) else 1
     if args.scaling is None:  # c2b has no sharding (one from_coords call): replicas only
         args.scaling = "strong" if (args.gpus > 1 or args.emulate_world > 1) and args.workload != "c2b" else "weak"
+    if args.dump_outputs and world > 1 and args.scaling == "strong" and args.gather == "end" and args.workload in ("c2a", "c5"):
+        raise SystemExit("--dump-outputs with --scaling strong on N > 1 ranks needs --gather step (rank 0 holds the whole list only then)")
 
     import torch
     import torch.distributed as dist

@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for W in $WLS; do
   STEPS=10; [ $W = c4 ] && STEPS=3
-  BENCH="python3 $REPO/bench.py --no-cpu-baseline --workload $W"
+  BENCH="python3 $REPO/bench.py --full --no-cpu-baseline --workload $W"
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$W" -- $BENCH --steps $STEPS --warmup 2 > "$OUT/${W}_stats.log" 2>&1 || exit 1
   cp "$(find "$OUT/stats_$W" -name '*kernel_stats.csv' | head -1)" "$OUT/${W}_kernel_stats.csv"
   rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_$W" -- $BENCH --steps 2 --warmup 1 > "$OUT/${W}_pmc_fetch.log" 2>&1 || exit 1
@@ -26,6 +26,6 @@ done
 cd "$REPO"
 for W in $WLS; do
   STEPS=10; [ $W = c4 ] && STEPS=5
-  python3 bench.py --workload $W --steps $STEPS --warmup 3 > "$OUT/${W}_bench.log" 2>&1; tail -1 "$OUT/${W}_bench.log" > "$OUT/${W}_bench.json"
+  python3 bench.py --full --workload $W --steps $STEPS --warmup 3 > "$OUT/${W}_bench.log" 2>&1; tail -1 "$OUT/${W}_bench.log" > "$OUT/${W}_bench.json"
 done
 ls -la "$OUT"

@@ -13,7 +13,7 @@ if [ $PART = a ]; then
   bash profiles/collect.sh $ROUND f > $F/collect.log 2>&1 < /dev/null || echo "collect failed" | tee -a $F/summary_a.txt
 else
   bash profiles/collect_extra.sh $ROUND f > $F/collect_extra.log 2>&1 < /dev/null || echo "collect_extra failed" | tee $F/summary_b.txt
-  python3 bench.py > $F/default_bench_line.json 2> $F/default_bench_line.err < /dev/null
+  python3 bench.py --full > $F/default_bench_line.json 2> $F/default_bench_line.err < /dev/null
   tail -c 600 $F/default_bench_line.json
   python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee -a $F/summary_b.txt
 fi

@@ -5,7 +5,7 @@ mkdir -p $OUT
 R=$PWD
 cd /tmp && export TMPDIR=/tmp
 for W in ${WLS:-c5 c2a}; do
-  BENCH="python3 $R/bench.py --no-cpu-baseline --workload $W --steps 2 --warmup 1"
+  BENCH="python3 $R/bench.py --full --no-cpu-baseline --workload $W --steps 2 --warmup 1"
   i=0
   for SET in "SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE" "SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_LDS_MEM_VIOLATIONS SQ_LDS_ATOMIC_RETURN" "SQ_INST_CYCLES_VMEM SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY"; do
     i=$((i+1))

@@ -15,7 +15,8 @@ from loco_hd_amd.pdb_reader import PDBParser
 from oracle import atom_converter_oracle as aco
 from tests import pdb_util
 
-REF_SCHEMES = sorted(Path("/root/reference/primitive_typings").glob("*.config.json"))
+# the reference's four typing schemes (primitive_typings/*.config.json), stored as data fixtures
+REF_SCHEMES = sorted((Path(__file__).resolve().parent / "golden" / "primitive_typings").glob("*.config.json"))
 
 
 def _as_tuples(model):
@@ -97,10 +98,14 @@ def test_assign_matches_oracle_on_test_scheme(tmp_path, seed):
     assert "Never" not in {g.primitive_type for g in got} and "Wat" in {g.primitive_type for g in got}
 
 
-@pytest.mark.skipif(not REF_SCHEMES, reason="the reference's typing schemes are only present in the build container")
+def test_all_reference_schemes_are_stored():
+    assert [p.name for p in REF_SCHEMES] == ["all_atom.config.json", "all_atom_with_centroid.config.json", "coarse_grained.config.json",
+                                             "coarse_grained_with_centroid.config.json"]
+
+
 @pytest.mark.parametrize("scheme", REF_SCHEMES, ids=lambda p: p.name)
 def test_assign_matches_oracle_on_reference_schemes(scheme):
-    """The four typing schemes the reference ships (primitive_typings/*.config.json), read in place as data."""
+    """The four typing schemes the reference ships (primitive_typings/*.config.json), stored under tests/golden/."""
     pa, got, _ = _check_assign(scheme, pdb_util.synthetic_pdb(seed=11, n_res=80, hetero=False))
     assert set(pa.all_primitive_types) >= {g.primitive_type for g in got}
 

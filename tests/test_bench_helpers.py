@@ -66,6 +66,27 @@ def test_roofline_block_arithmetic(tmp_path, monkeypatch):
     assert blk["traffic"] is None
 
 
+def test_dump_outputs_writes_float64_and_samples_above_the_limit(tmp_path, monkeypatch):
+    small = np.arange(12, dtype=np.float64).reshape(3, 4)
+    bench.dump_outputs(str(tmp_path / "a"), scores=small)
+    got = np.load(tmp_path / "a" / "scores.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small) and not (tmp_path / "a" / "scores_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8_000)
+    big = np.random.default_rng(3).uniform(0, 1, 5_000)
+    for d in ("b", "c"):  # a fixed sample: the same positions in every run
+        bench.dump_outputs(str(tmp_path / d), scores=big)
+    idx, vals = np.load(tmp_path / "b" / "scores_index.npy"), np.load(tmp_path / "b" / "scores.npy")
+    assert idx.dtype == np.float64 and vals.dtype == np.float64 and 0 < len(vals) == len(idx) < len(big)
+    assert np.array_equal(vals, big[idx.astype(np.int64)]) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "scores_index.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 8_000
+
+
+def test_bench_rejects_zero_timed_steps():
+    p = _run_bench({}, "--steps", "0", timeout=60)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr
+
+
 def _run_bench(extra_env, *argv, timeout=180):
     import os
     import subprocess

@@ -169,7 +169,7 @@ def test_bench_strong_scaling_line_under_a_forced_process_group(workload, extra)
     env = dict(os.environ, LCHD_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29800 + os.getpid() % 150),
                WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     cmd = [sys.executable, str(root / "bench.py"), "--workload", workload, "--scaling", "strong", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", *extra]
+           "--full", "--no-cpu-baseline", *extra]
     run = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-3000:]
     line = json.loads(run.stdout.strip().splitlines()[-1])
@@ -203,7 +203,7 @@ def test_bench_with_two_real_ranks_started_by_bench_itself(workload, extra):
     import json
 
     run = _bench_without_launcher({"LCHD_BENCH_SHARE_GPU": "1"}, "--gpus", "2", "--workload", workload, "--steps", "2", "--warmup", "1",
-                                  "--no-cpu-baseline", *extra)
+                                  "--full", "--no-cpu-baseline", *extra)
     assert run.returncode == 0, run.stderr[-3000:]
     assert "rank 0 of 2 up" in run.stderr and "rank 1 of 2 up" in run.stderr
     line = json.loads(run.stdout.strip().splitlines()[-1])
