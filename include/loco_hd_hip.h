@@ -246,10 +246,17 @@ int32_t lchd_ctx_last_dense_fused(lchd_ctx *ctx);
  * on != 0 pins ONE sweep family (one pair per wavefront, global-memory tables; dense rows through the row sort + that sweep) and
  * switches every history-dependent choice off: a pair's score is then a function of the pair and the configuration alone --
  * bitwise equal across batch composition, call order, sharding and second passes -- at roughly half the default throughput.
- * on == 0 returns to the default selection.  Not allowed while an asynchronous call is pending.
- * (In every mode: points of DIFFERENT categories at EXACTLY the same distance from an anchor -- lattice coordinates -- enter an
- * environment in the order the cell list's atomics produced, which may differ from run to run; they span zero-width intervals, so only
- * the rounding of the running sums differs: a few 1e-16 in a handful of pairs.  Inputs without such ties are bit-reproducible.) */
+ * Ties: with on != 0 the categories inside every run of EXACTLY equal keys of an environment are put in ascending order, so an
+ * environment's stored (distance, category) sequence depends on the multiset of (distance, category) of its points alone (the
+ * first point included: several points at distance 0 are ordered like any other tie).  Scores are then invariant under any permutation of the
+ * points (from_primitives: with the anchor pairs renumbered; from_coords: out[k] follows point k; from_dmxs: rows and columns
+ * permuted together), on lattices, duplicated coordinates, extra zeros and +inf entries of distance matrices included
+ * (tests/test_gpu_deterministic.py).  With on == 0 points of DIFFERENT categories at exactly the same distance enter an environment in
+ * the order the cell lists' and row sorts' atomics produced, which may differ from run to run; they span zero-width intervals, so only
+ * the rounding of the running sums differs: a few 1e-16 in a handful of pairs.  Inputs without such ties are bit-reproducible in
+ * both modes.  The one exception to the one-family rule: environments of more than 65 535 points take the 64-bit-count sweep in
+ * both modes (their scores are still a function of the pair and the configuration).
+ * on == 0 returns to the default selection.  Not allowed while an asynchronous call is pending. */
 int lchd_ctx_set_deterministic(lchd_ctx *ctx, int32_t on);
 int32_t lchd_ctx_get_deterministic(lchd_ctx *ctx);
 /* from_primitives passes the context has enqueued since it was created.  A call is one pass in the steady state; a pass is

@@ -473,37 +473,42 @@ void launch_env_key_sets(hipStream_t s, const DevConfig* cfg, const EnvStore& ea
 // input.  The environment kernels here break ties by the position a point happened to get in a cell list or a bucket (global / LDS
 // atomics: another order in another run), and although a zero-width interval never counts, the O(1) Bhattacharyya update sees the
 // categories in that order: scores moved by a few 1e-16 from run to run on lattice inputs.  Under lchd_ctx_set_deterministic one wavefront
-// per environment sorts the CATEGORIES of every run of equal keys (positions >= 1: the first point is the anchor) -- two points of one
-// key and one category are interchangeable, so the stored (key, category) sequence is then a function of the input alone.  Environments
-// without ties (every random cloud) cost one read of their keys.
+// per environment sorts the CATEGORIES of every run of equal keys -- two points of one key and one category are interchangeable, so the
+// stored (key, category) sequence is then a function of the multiset of (key, category) of the environment's points alone.  Position 0
+// takes part: nothing puts the anchor there, it is whichever point at distance 0 sorted first (the anchor, a point with the anchor's
+// coordinates, another zero of a matrix row), and its category is the sweep's starting state (k_pair_meta; k_env_group's cat0 header is
+// rewritten with it).  Environments without ties (every random cloud) cost one read of their keys.  Runs of at most 64 points: an insertion sort by one lane.  Longer runs (thousands of +inf entries of a distance matrix, the
+// F = 1 tail of a uniform weight function): the wavefront counts the run's categories and writes them out in ascending order -- no
+// lane ever walks a long run alone.
 __global__ __launch_bounds__(256) void k_env_canon(EnvStore ea, EnvStore eb, int64_t n_a, int64_t n_b, const DeviceStatus* st) {
     __shared__ uint32_t cnt_s[4][256];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t nu_a = st ? (int64_t)st->n_unique[0] : n_a, nu_b = st ? (int64_t)st->n_unique[1] : n_b;
+    // (n_a / n_b bound the environments in use: one store given for both sides comes with n_b = 0 -- no environment is canonicalised twice)
+    const int64_t nu_a = st ? min((int64_t)st->n_unique[0], n_a) : n_a, nu_b = st ? min((int64_t)st->n_unique[1], n_b) : n_b;
     for (int64_t e = (int64_t)blockIdx.x * 4 + wave; e < nu_a + nu_b; e += (int64_t)gridDim.x * 4) {
         const bool on_b = e >= nu_a;
         const EnvStore& es = on_b ? eb : ea;
         const int64_t slot = on_b ? e - nu_a : e;
         const int len = es.len[slot];
-        if (len < 3) continue;
-        const uint64_t* __restrict__ key = es.key + slot * es.stride;
+        if (len < 2) continue;
+        uint64_t* const key = es.key + slot * es.stride;
         uint8_t* const c8 = es.cat + slot * es.stride * (es.cat16 ? 2 : 1);
         uint16_t* const c16 = reinterpret_cast<uint16_t*>(c8);
         const bool wide = es.cat16 != 0;
         bool any = false;
-        for (int i0 = 2; i0 < len; i0 += 64) {
+        for (int i0 = 1; i0 < len; i0 += 64) {
             const int i = i0 + lane;
             any |= __ballot(i < len && key[i] == key[i - 1]) != 0ull;
         }
         if (!any) continue;
-        for (int i0 = 1; i0 < len; i0 += 64) {
+        for (int i0 = 0; i0 < len; i0 += 64) {
             const int i = i0 + lane;
-            const bool head = i + 1 < len && (i == 1 || key[i] != key[i - 1]) && key[i + 1] == key[i];
+            const bool head = i + 1 < len && (i == 0 || key[i] != key[i - 1]) && key[i + 1] == key[i];
             int end = i + 1;
-            if (head) {
+            if (head) {  // (a lane looks at most 65 entries ahead: a longer run is the wavefront's)
                 const uint64_t k0 = key[i];
-                while (end < len && key[end] == k0) ++end;
-                if (end - i <= 64 || wide) {  // a short run (every lattice): insertion sort by this lane
+                while (end < len && end - i <= 64 && key[end] == k0) ++end;
+                if (end - i <= 64) {  // a short run (every lattice): insertion sort by this lane
                     for (int p = i + 1; p < end; ++p) {
                         const uint32_t v = wide ? (uint32_t)c16[p] : (uint32_t)c8[p];
                         int q = p - 1;
@@ -515,27 +520,87 @@ __global__ __launch_bounds__(256) void k_env_canon(EnvStore ea, EnvStore eb, int
                     }
                 }
             }
-            // long runs (thousands of +inf entries of a distance matrix): the wavefront counts the run's categories and writes them out in order
-            unsigned long long longs = __ballot(head && end - i > 64 && !wide);
+            // long runs: (at most one per chunk of 64 heads -- it reaches past the chunk) the wavefront finds the run's end ...
+            unsigned long long longs = __ballot(head && end - i > 64);
             while (longs) {
                 const int src = __ffsll((long long)longs) - 1;
                 longs &= longs - 1;
-                const int s0 = __shfl(i, src), s1 = __shfl(end, src);
+                const int s0 = __shfl(i, src);
+                const uint64_t k0 = key[s0];
+                int s1 = __shfl(end, src);  // (= s0 + 65: the head lane saw that many equal keys)
+                for (;;) {
+                    const int p = s1 + lane;
+                    const unsigned long long stop = __ballot(!(p < len && key[p] == k0));
+                    if (stop) { s1 += __ffsll((long long)stop) - 1; break; }
+                    s1 += 64;
+                }
+                // ... then counts its categories (8-bit ids: one histogram; 16-bit ids: one of the high bytes, then one of the low bytes per
+                // high byte that occurs) and writes them out in ascending order
 #pragma unroll
                 for (int k = 0; k < 4; ++k) cnt_s[wave][4 * lane + k] = 0u;
                 wave_sync_lds();
-                for (int p = s0 + lane; p < s1; p += 64) atomicAdd(&cnt_s[wave][c8[p]], 1u);
+                if (wide) {  // the run's key slots all hold k0: they keep a copy of its categories while c16 is rewritten, and get k0 back
+                    for (int p = s0 + lane; p < s1; p += 64) {
+                        const uint32_t v = c16[p];
+                        key[p] = v;
+                        atomicAdd(&cnt_s[wave][v >> 8], 1u);
+                    }
+                } else {
+                    for (int p = s0 + lane; p < s1; p += 64) atomicAdd(&cnt_s[wave][c8[p]], 1u);
+                }
+                __threadfence_block();
                 wave_sync_lds();
                 uint32_t c[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) c[k] = cnt_s[wave][4 * lane + k];
                 const uint32_t mine = c[0] + c[1] + c[2] + c[3];
                 uint32_t at = (uint32_t)s0 + wave_incl_scan_u32(mine) - mine;
+                if (!wide) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    for (uint32_t r = 0; r < c[k]; ++r) c8[at++] = (uint8_t)(4 * lane + k);
+                    for (int k = 0; k < 4; ++k)
+                        for (uint32_t r = 0; r < c[k]; ++r) c8[at++] = (uint8_t)(4 * lane + k);
+                    wave_sync_lds();
+                    continue;
+                }
+                uint32_t hb[4];  // where the ids of high byte 4 * lane + k start
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { hb[k] = at; at += c[k]; }
+                wave_sync_lds();
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    unsigned long long highs = __ballot(c[k] != 0u);
+                    while (highs) {  // (every high byte writes its own range: any order will do)
+                        const int hl = __ffsll((long long)highs) - 1;
+                        highs &= highs - 1;
+                        const uint32_t h = 4u * (uint32_t)hl + (uint32_t)k, base = (uint32_t)__shfl((int)hb[k], hl);
+#pragma unroll
+                        for (int kk = 0; kk < 4; ++kk) cnt_s[wave][4 * lane + kk] = 0u;
+                        wave_sync_lds();
+                        for (int p = s0 + lane; p < s1; p += 64) {
+                            const uint32_t v = (uint32_t)key[p];
+                            if ((v >> 8) == h) atomicAdd(&cnt_s[wave][v & 255u], 1u);
+                        }
+                        wave_sync_lds();
+                        uint32_t d[4];
+#pragma unroll
+                        for (int kk = 0; kk < 4; ++kk) d[kk] = cnt_s[wave][4 * lane + kk];
+                        const uint32_t own = d[0] + d[1] + d[2] + d[3];
+                        uint32_t w = base + wave_incl_scan_u32(own) - own;
+#pragma unroll
+                        for (int kk = 0; kk < 4; ++kk)
+                            for (uint32_t r = 0; r < d[kk]; ++r) c16[w++] = (uint16_t)((h << 8) | (4u * (uint32_t)lane + (uint32_t)kk));
+                        wave_sync_lds();
+                    }
+                }
+                __threadfence_block();
+                for (int p = s0 + lane; p < s1; p += 64) key[p] = k0;
+                __threadfence_block();  // (the next chunks' lanes read these keys)
                 wave_sync_lds();
             }
+        }
+        if (es.cat0 && !wide) {  // (the grouped environment kernel's copy of the first category)
+            __threadfence_block();
+            if (lane == 0) es.cat0[slot] = c8[0];
         }
     }
 }

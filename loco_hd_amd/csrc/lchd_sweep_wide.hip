@@ -337,7 +337,10 @@ __global__ __launch_bounds__(64 * WPB) void k_sweep_wide(SweepArgs args) {
 template <int MODE>
 static void launch_sweep_wide_m(hipStream_t s, int n_cat, int64_t n_pairs, int fmode, const SweepArgs& a) {
     // dynamic LDS = WPB * C * 64 * 4 bytes of per-lane count columns
-    if (a.env_a.stride > 65535 || a.env_b.stride > 65535) {  // environments of more than 65 535 points: 64-bit count words (<= 255 categories: the host checks)
+    // environments of more than 65 535 points: 64-bit count words (<= 255 categories: the host checks).  16-bit ids never come here: their
+    // environments hold at most 65 535 points, but a dense row of 32 769 .. 65 535 points has a store stride of 65 536, and this form reads
+    // one-byte ids and 24-bit lengths from the pair records (a 16-bit id above the length: reads far beyond the environment)
+    if (!a.env_a.cat16 && (a.env_a.stride > 65535 || a.env_b.stride > 65535)) {
         const unsigned grid = (unsigned)(n_pairs < 8192 ? n_pairs : 8192);
         const size_t dyn = (size_t)n_cat * 512;
         if (fmode == F_KEY) k_sweep_wide<MODE, F_KEY, 1, false, true><<<grid, 64, dyn, s>>>(a);
