@@ -138,6 +138,8 @@ int lchd_cloud_create_batch(lchd_ctx *ctx, const double *xyz, const int32_t *cat
                             int64_t n, int32_t n_struct, lchd_cloud **out);
 /* Atoms a cloud / batch / frames buffer currently holds (-1 for a null handle). */
 int64_t lchd_cloud_size(const lchd_cloud *cloud);
+/* Structures a cloud (1), batch or frames buffer (the frames loaded last) currently holds (-1 for a null handle). */
+int32_t lchd_cloud_structures(const lchd_cloud *cloud);
 /* Replace the coordinates of an existing cloud (MD frames: same atoms, new positions). Host pointer [n][3]. */
 int lchd_cloud_set_coords(lchd_ctx *ctx, lchd_cloud *cloud, const double *xyz);
 void lchd_cloud_destroy(lchd_ctx *ctx, lchd_cloud *cloud);
@@ -153,6 +155,29 @@ int lchd_from_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const 
  * b), every environment is the whole structure (no threshold, no tag rule).  d_wf_index: DEVICE [n] int32 or NULL, d_out:
  * DEVICE [n] double, complete on return.  Uses the configuration set by lchd_ctx_set_config. */
 int lchd_from_coords_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, double *d_out);
+
+/* Dense ensembles (python_codes/ensembles/compare_ensembles.py:277-296: from_dmxs(seq, seq, dmx[i], dmx[j]) for every pair i < j of M
+ * structures of one topology), additive.  out[p][r] = from_coords(seq, seq, X[i_p], X[j_p])[r] for structure pair p = (i_p, j_p);
+ * each structure's n dense rows are sorted once and reused by all of its pairs.
+ *   cloud     a regular batch (lchd_cloud_create_batch of equal-sized structures stored one after the other, or a frames
+ *             buffer): M = its structures, n = atoms per structure; the categories of structure 0 are the topology's
+ *   d_pairs   DEVICE int32 [n_pairs][2] structure indices ((i, i), (j, i) and repeats allowed), or NULL: every i < j, i outer
+ *             (n_pairs must then be M (M - 1) / 2)
+ *   d_excl_start [n + 1], d_excl_idx [d_excl_start[n]]: DEVICE CSR of excluded columns per row, or both NULL; an excluded entry
+ *             (r, c) counts as distance +inf in every structure (directional: list (c, r) as well for a symmetric ban)
+ *   d_wf_index DEVICE int32 [n] (one weight function per row, as from_dmxs's w_func_keys) or NULL; d_out DEVICE double [n_pairs][n]
+ * Uses the configuration of lchd_ctx_set_config; d_out is complete on return.  The environment store holds as many structures
+ * as the free device memory allows; beyond that the structures are processed in blocks (rows of a block rebuilt per block pair). */
+int lchd_ensemble_from_coords_dev(lchd_ctx *ctx, lchd_cloud *cloud, const int32_t *d_pairs, int64_t n_pairs,
+                                  const int32_t *d_excl_start, const int32_t *d_excl_idx, const int32_t *d_wf_index, double *d_out);
+/* The same from host arrays: xyz [n_struct][n][3], pairs [n_pairs][2] or NULL, excl_start / excl_idx or NULL, wf_index [n] or
+ * NULL, out [n_pairs][n].  Uploads a temporary batch and calls the _dev form. */
+int lchd_ensemble_from_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq, int64_t n, const double *xyz, int64_t n_struct,
+                              const int32_t *pairs, int64_t n_pairs, const int32_t *excl_start, const int32_t *excl_idx,
+                              const int32_t *wf_index, double *out);
+/* Given square distance matrices dmx [n_struct][n][n] (+inf allowed), out[p][r] = from_dmxs(seq, seq, dmx[i_p], dmx[j_p])[r]. */
+int lchd_ensemble_from_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq, int64_t n, const double *dmx, int64_t n_struct,
+                            const int32_t *pairs, int64_t n_pairs, const int32_t *wf_index, double *out);
 
 /* Split form of lchd_from_primitives_dev: _async enqueues the whole pass on the context's stream and returns without
  * waiting; lchd_ctx_finish waits, re-runs the pass with a larger environment capacity if one overflowed, and returns

@@ -446,6 +446,79 @@ class LoCoHD:
                                          N.dp(xb), len(xb), N.ip(idx), N.dp(out)))
         return out.tolist()
 
+    # ---- dense ensembles (additive) ----------------------------------------------------------------------
+    def from_coords_ensemble(self, seq, coords, structure_pairs=None, w_func_keys: Optional[Sequence[str]] = None,
+                             excluded_pairs=None) -> np.ndarray:
+        """Additive: `from_coords(seq, seq, coords[i], coords[j])` for every structure pair (i, j) of M structures of one
+        topology, in one call -- python_codes/ensembles/compare_ensembles.py:277-296, where each structure's dense rows are
+        sorted once.  `coords`: (M, n, 3) or a list of (n, 3); `structure_pairs`: (i, j) pairs, default every i < j (i outer);
+        `excluded_pairs`: (r, c) atom-index pairs whose distance counts as +inf in every structure (directional: give both
+        orders, as the script's homo-residue ban does).  Returns a float64 array (P, n)."""
+        xs = [self._coords(x) for x in coords]
+        n = len(xs[0]) if xs else 0
+        for x in xs[1:]:
+            if len(x) != n:
+                raise ValueError(f"Expected matrices with the same length, got lengths {n} and {len(x)}!")
+        xyz = np.ascontiguousarray(np.stack(xs) if xs else np.zeros((0, 0, 3)), dtype=np.float64)
+        pairs = self._structure_pairs(structure_pairs, len(xs))
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], n)
+        cs = self._cats(list(seq))
+        if len(cs) < n:
+            raise N.PanicException("index out of bounds: a distance row is longer than its seq")
+        xstart, xidx = self._exclusion_csr(excluded_pairs, n)
+        cfg, keep = self._config()
+        p = len(pairs) if pairs is not None else len(xs) * (len(xs) - 1) // 2
+        out = np.empty((p, n))
+        N.check(N.lib().lchd_ensemble_from_coords(self._context(), C.byref(cfg), N.ip(cs), n, N.dp(xyz), len(xs),
+                                                  N.ip(pairs), p, N.ip(xstart), N.ip(xidx), N.ip(idx), N.dp(out)))
+        return out
+
+    def from_dmxs_ensemble(self, seq, dmxs, structure_pairs=None, w_func_keys: Optional[Sequence[str]] = None) -> np.ndarray:
+        """Additive: `from_dmxs(seq, seq, dmxs[i], dmxs[j])` for every structure pair (i, j), in one call (the exact call of
+        python_codes/ensembles/compare_ensembles.py:277-296).  `dmxs`: (M, n, n) square matrices, +inf allowed.  Returns a
+        float64 array (P, n)."""
+        ms = [self._matrix(m)[0] for m in dmxs]
+        n = ms[0].shape[0] if ms else 0
+        for m in ms:
+            if m.shape[0] != n:
+                raise ValueError(f"Expected matrices with the same length, got lengths {n} and {m.shape[0]}!")
+            if m.shape[1] != m.shape[0]:
+                raise ValueError(f"from_dmxs_ensemble takes square distance matrices, got {m.shape[0]} x {m.shape[1]}")
+        dmx = np.ascontiguousarray(np.stack(ms) if ms else np.zeros((0, 0, 0)), dtype=np.float64)
+        pairs = self._structure_pairs(structure_pairs, len(ms))
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], n)
+        cs = self._cats(list(seq))
+        if len(cs) < n:
+            raise N.PanicException("index out of bounds: a distance row is longer than its seq")
+        cfg, keep = self._config()
+        p = len(pairs) if pairs is not None else len(ms) * (len(ms) - 1) // 2
+        out = np.empty((p, n))
+        N.check(N.lib().lchd_ensemble_from_dmxs(self._context(), C.byref(cfg), N.ip(cs), n, N.dp(dmx), len(ms), N.ip(pairs), p,
+                                                N.ip(idx), N.dp(out)))
+        return out
+
+    @staticmethod
+    def _structure_pairs(structure_pairs, m: int) -> Optional[np.ndarray]:
+        if structure_pairs is None:
+            return None
+        pairs = np.ascontiguousarray(np.asarray(list(structure_pairs), dtype=np.int64).reshape(-1, 2))
+        if len(pairs) and (pairs.min() < 0 or pairs.max() >= m):
+            raise ValueError(f"a structure pair refers to a structure outside [0, {m})")
+        return pairs.astype(np.int32)
+
+    @staticmethod
+    def _exclusion_csr(excluded_pairs, n: int) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+        """(r, c) pairs -> CSR (row starts [n + 1], columns) of the excluded entries, or (None, None)."""
+        if excluded_pairs is None:
+            return None, None
+        ex = np.asarray(list(excluded_pairs), dtype=np.int64).reshape(-1, 2)
+        if len(ex) and (ex.min() < 0 or ex.max() >= n):
+            raise ValueError(f"an excluded pair refers to an atom outside [0, {n})")
+        ex = ex[np.lexsort((ex[:, 1], ex[:, 0]))]
+        start = np.zeros(n + 1, dtype=np.int32)
+        np.cumsum(np.bincount(ex[:, 0], minlength=n), out=start[1:])
+        return start, np.ascontiguousarray(ex[:, 1], dtype=np.int32)
+
     def from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
                         threshold_distance: float) -> List[float]:
         """src/locohd.rs:479-567."""
@@ -530,8 +603,12 @@ class LoCoHD:
         PrimitiveAtoms; a job `(a, b, anchor_pairs)` asks for `from_primitives(structures[a], structures[b],
         anchor_pairs, threshold_distance)`.  Returns one score list per job, each bit-identical to the single call.
         Replaces loops such as python_codes/casp14/casp14_extend_with_locohd.py:42-88 (every decoy against the native
-        structure) or python_codes/ensembles/compare_ensembles.py:277-296: all structures are uploaded once as one batch
-        object, the anchor pairs of all jobs are scored by one kernel sequence."""
+        structure): all structures are uploaded once as one batch
+        object, the anchor pairs of all jobs are scored by one kernel sequence.
+
+        It does NOT reproduce the dense numbers of python_codes/ensembles/compare_ensembles.py:277-296: that script scores
+        whole-structure rows (from_dmxs), this call thresholded from_primitives environments.  The script's call is
+        `from_dmxs_ensemble` / `from_coords_ensemble`."""
         from .device import DeviceSession  # torch is only needed on this path
 
         if isinstance(self._w_func, dict):

@@ -312,6 +312,7 @@ static Tuning tuning_from_env() {  // the ONLY place that reads LCHD_* hooks (te
     t.force_cmax = env_int("LCHD_FORCE_CMAX", 0);
     t.per_pair = env_int("LCHD_PER_PAIR", 0);
     t.pre_rows = env_int("LCHD_PRE_ROWS", 0);
+    t.ensemble_block = env_int("LCHD_ENSEMBLE_BLOCK", 0);
     return t;
 }
 
@@ -728,6 +729,7 @@ extern "C" int lchd_cloud_create_batch(lchd_ctx* c, const double* xyz, const int
 }
 
 extern "C" int64_t lchd_cloud_size(const lchd_cloud* cl) { return cl ? cl->n : -1; }
+extern "C" int32_t lchd_cloud_structures(const lchd_cloud* cl) { return cl ? cl->n_struct : -1; }
 
 extern "C" int lchd_cloud_set_coords(lchd_ctx* c, lchd_cloud* cl, const double* xyz) {
     if (!c || !cl || !xyz) return fail(LCHD_EVALUE, "null argument");
@@ -2531,4 +2533,374 @@ extern "C" int lchd_from_anchors(lchd_ctx* c, const lchd_config* cfg, const int3
                         reinterpret_cast<int4*>(c->d_io + o_meta), DRV_ANCHORS);
     if (!rc) *out = *h_out;
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// dense ensembles (python_codes/ensembles/compare_ensembles.py:277-296: from_dmxs(seq, seq, dmx[i], dmx[j]) for every pair i < j
+// of M structures of one topology).  The n dense rows of a structure are the same in all M - 1 of its comparisons: they are
+// sorted ONCE into an environment store of resident structures (slot s: rows [s * n, (s + 1) * n)), and a structure pair is n
+// sweep records over that store (lchd_ensemble.hip).  The row sort is the one from_dmxs uses (k_env_rows2 / k_env_rows on
+// distance rows materialised by k_ens_dist), the sweep the launch_sweep family of the context's mode, so a record's score is
+// the one from_coords / from_dmxs computes for that row (bit for bit in deterministic mode).
+// Blocking: when the store of all M structures does not fit the free HBM, B slots are split into two halves of B / 2
+// structures; block bi is built into the first half, every block bj > bi in turn into the second, and the pairs between the
+// two resident blocks are swept -- block bi's rows are built once, block bj's once per bi < bj.
+// ------------------------------------------------------------------------------------------------
+constexpr int64_t kEnsRecords = (int64_t)1 << 22;   // sweep records per pass (anchors, weight-function index, pair record, score: 44 B each)
+constexpr int64_t kEnsDistBytes = (int64_t)1 << 30; // distance rows materialised for one row-sort launch
+
+struct EnsSrc {
+    CloudView cats;             // the topology's categories (n atoms; coordinates unused)
+    const lchd_cloud* coords;   // regular batch of M structures of n atoms, or null (given rows)
+    const double* h_dmx;        // given rows: HOST [M][n][n], or null
+    const int32_t *excl_start, *excl_idx;  // DEVICE CSR of excluded columns per row, or null
+};
+
+static int ens_sweep(lchd_ctx* c, const EnvStore& st, const int64_t* anchors, const uint32_t* slots, int64_t n_slots, const int32_t* wf_rec,
+                     int64_t q, double* out, int4* meta) {
+    SweepArgs sw{};
+    fill_sweep_args(c, sw);
+    sw.env_a = sw.env_b = st;
+    sw.anchors = anchors;
+    sw.slot_a = sw.slot_b = slots;
+    sw.n_slot_a = sw.n_slot_b = n_slots;
+    sw.wf_index = wf_rec;
+    sw.n_pairs = q;
+    sw.out = out;
+    sw.meta = meta;
+    (void)launch_sweep(c->stream, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, 0, sw);
+    HIP_TRY(hipGetLastError());
+    c->status_dirty = false;  // the record pass resets the device status
+    uint32_t f = 0;
+    if (int rc = wait_pass(c, &f)) return rc;
+    return status_to_rc(f, DRV_DMXS);
+}
+
+// pairs: host [P][2] structure indices (validated); d_wf: DEVICE [n] or null; d_out: DEVICE [P][n]
+static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, const std::vector<int32_t>& pairs, const int32_t* d_wf,
+                         double* d_out) {
+    const int64_t P = (int64_t)pairs.size() / 2;
+    c->last_valid = false;
+    c->last_dense_fused = false;
+    if (P == 0 || n == 0) return LCHD_OK;
+    const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
+    if (n > 65535 && (cat16 || n > (1 << 23)))
+        return fail(LCHD_EUNSUPPORTED, "dense rows of more than 65535 points are supported with at most %d categories and 2^23 points (got %lld)",
+                    kMaxCategories, (long long)n);
+    const int64_t cap = next_pow2_host(n);
+    const size_t cat_bytes = cat16 ? 2 : 1;
+    const bool rows2 = !cat16 && !c->tune.old_rows && n <= 16384;  // (longer rows: k_env_rows, which needs no segmented-sort retry)
+    const int64_t dist_structs = std::max<int64_t>(1, std::min<int64_t>(M, kEnsDistBytes / (8 * n * n)));
+    const int64_t pass_pairs = std::max<int64_t>(1, std::min<int64_t>(P, kEnsRecords / n));
+    const int64_t q_cap = pass_pairs * n;
+    const size_t slot_bytes = (size_t)n * cap * (8 + cat_bytes) + (size_t)n * 8 + 1024;  // keys, categories, length, identity map, alignment
+    const size_t fixed = (size_t)(dist_structs * n + 1) * n * 8 + (size_t)q_cap * (16 + 4 + 16 + 8) + (size_t)P * 16 + slot_bytes + (16 << 20);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const size_t budget = free_b / 10 * 8;
+    int64_t fit = budget > fixed ? (int64_t)((budget - fixed) / slot_bytes) : 0;
+    if (c->tune.ensemble_block > 0) fit = std::min<int64_t>(fit, c->tune.ensemble_block);
+    int64_t slots, half;  // store slots; structures per block (== M: one block)
+    if (fit >= M) {
+        slots = half = M;
+    } else {
+        half = fit / 2;
+        if (half < 1)
+            return fail(LCHD_EUNSUPPORTED, "the ensemble call needs the sorted rows of two structures (%zu bytes) resident, but only %zu of %zu bytes "
+                                           "of device memory are free", fixed + 2 * slot_bytes, free_b, total_b);
+        slots = 2 * half;
+    }
+    if (slots * n >= ((int64_t)1 << 31)) return fail(LCHD_EUNSUPPORTED, "%lld resident rows exceed the 2^31 environment slots of a pass", (long long)(slots * n));
+    // one device block for the call, released on every path out
+    EnvStore st{};
+    double *dmx = nullptr, *tmp = nullptr;
+    int64_t* anchors = nullptr;
+    int32_t* wf_rec = nullptr;
+    int4 *meta = nullptr, *plan = nullptr;
+    uint32_t* iota = nullptr;
+    char* blk = nullptr;
+    size_t blk_bytes = 0;
+    for (int dry = 1; dry >= 0; --dry) {
+        Arena ar(blk, blk_bytes, dry != 0);
+        st.key = ar.take<uint64_t>((size_t)(slots * n + 1) * cap);  // (+1 row: the odd row of a row-sort launch, below)
+        st.cat = ar.take<uint8_t>((size_t)(slots * n + 1) * cap * cat_bytes);
+        st.len = ar.take<int32_t>((size_t)(slots * n + 1));
+        iota = ar.take<uint32_t>((size_t)(slots * n));
+        dmx = ar.take<double>((size_t)(dist_structs * n) * n);
+        anchors = ar.take<int64_t>((size_t)q_cap * 2);
+        wf_rec = d_wf ? ar.take<int32_t>((size_t)q_cap) : nullptr;
+        meta = ar.take<int4>((size_t)q_cap);
+        tmp = ar.take<double>((size_t)q_cap);
+        plan = ar.take<int4>((size_t)P);
+        if (dry) {
+            blk_bytes = ar.off + 256;
+            if (hipMalloc(&blk, blk_bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(LCHD_EUNSUPPORTED, "the ensemble call needs %zu bytes of device memory; %zu of %zu are free", blk_bytes, free_b, total_b);
+            }
+        }
+    }
+    struct Release {
+        lchd_ctx* c;
+        char* p;
+        ~Release() { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); }
+    } release{c, blk};
+    st.stride = cap;
+    st.cat16 = cat16 ? 1 : 0;
+    st.cdf_keys = (c->h_cfg.n_wf == 1 && !c->tune.no_cdf_keys) ? 1 : 0;
+    hipStream_t s = c->stream;
+    launch_ens_iota(s, iota, slots * n);
+    auto rows_of = [&](int64_t slot) {  // the store seen from row slot * n on
+        EnvStore e = st;
+        e.key += slot * n * cap;
+        e.cat += slot * n * cap * (int64_t)cat_bytes;
+        e.len += slot * n;
+        return e;
+    };
+    // structures [s0, s0 + cnt) into slots [slot0, slot0 + cnt)
+    auto build = [&](int64_t slot0, int64_t s0, int64_t cnt) -> int {
+        for (int64_t k0 = 0; k0 < cnt; k0 += dist_structs) {
+            const int64_t kc = std::min(dist_structs, cnt - k0), rows = kc * n;
+            if (src.coords) {
+                launch_ens_dist(s, src.coords->view(cat16), (s0 + k0) * n, (int32_t)n, rows, src.excl_start, src.excl_idx, dmx);
+            } else {
+                HIP_TRY(hipMemcpyAsync(dmx, src.h_dmx + (size_t)(s0 + k0) * n * n, sizeof(double) * (size_t)rows * n, hipMemcpyHostToDevice, s));
+            }
+            const EnvStore e0 = rows_of(slot0 + k0);
+            bool ok;
+            if (rows2) {  // both halves of the launch: rows [0, h) and [h, 2h); an odd last row goes with the store's spare row
+                const int64_t h = rows / 2;
+                EnvStore e1 = e0;
+                e1.key += h * cap; e1.cat += h * cap; e1.len += h;
+                ok = launch_env_rows2(s, c->d_cfg, RowSide{src.cats, dmx, n, n, 0.0, e0, nullptr}, RowSide{src.cats, dmx + h * n, n, n, 0.0, e1, nullptr}, h,
+                                      c->d_status);
+                if (ok && (rows & 1)) {
+                    EnvStore el = e0, spare = st;
+                    el.key += (rows - 1) * cap; el.cat += (rows - 1) * cap; el.len += rows - 1;
+                    spare.key += slots * n * cap; spare.cat += slots * n * cap; spare.len += slots * n;
+                    const double* last = dmx + (rows - 1) * n;
+                    ok = launch_env_rows2(s, c->d_cfg, RowSide{src.cats, last, n, n, 0.0, el, nullptr}, RowSide{src.cats, last, n, n, 0.0, spare, nullptr}, 1,
+                                          c->d_status);
+                }
+            } else {
+                ok = launch_env_rows(s, (int)cap, c->d_cfg, src.cats, dmx, n, rows, n, 0.0, e0, c->d_status);
+            }
+            if (!ok) return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for rows of %lld points", (long long)n);
+        }
+        if (c->deterministic) {  // one order among equal keys, as deterministic from_coords / from_dmxs
+            const EnvStore e = rows_of(slot0);
+            launch_env_canon(s, e, e, cnt * n, 0, nullptr);
+        }
+        HIP_TRY(hipGetLastError());
+        return LCHD_OK;
+    };
+    // pairs grouped by the (lower, upper) block pair they need resident
+    const int64_t n_blk = (M + half - 1) / half;
+    std::vector<int64_t> order((size_t)P);
+    for (int64_t p = 0; p < P; ++p) order[(size_t)p] = p;
+    auto key_of = [&](int64_t p) {
+        const int64_t bi = pairs[2 * p] / half, bj = pairs[2 * p + 1] / half;
+        return std::min(bi, bj) * n_blk + std::max(bi, bj);
+    };
+    if (n_blk > 1) std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return key_of(x) < key_of(y); });
+    std::vector<int4> h_plan((size_t)P);
+    int64_t held[2] = {-1, -1};  // block resident in each half
+    for (int64_t g0 = 0; g0 < P;) {
+        const int64_t key = key_of(order[(size_t)g0]);
+        int64_t g1 = g0;
+        while (g1 < P && key_of(order[(size_t)g1]) == key) ++g1;
+        const int64_t bi = key / n_blk, bj = key % n_blk;
+        auto slot_of = [&](int32_t sidx) -> int32_t {
+            const int64_t b = sidx / half;
+            return (int32_t)((b == bi ? 0 : half) + (sidx - b * half));
+        };
+        for (int64_t g = g0; g < g1; ++g) {
+            const int64_t p = order[(size_t)g];
+            h_plan[(size_t)g] = make_int4(slot_of(pairs[2 * p]), slot_of(pairs[2 * p + 1]), (int)p, 0);
+        }
+        if (int rc = begin_pass(c)) return rc;
+        c->status_dirty = true;  // until the record pass has been enqueued (ens_sweep)
+        if (held[0] != bi) {
+            if (int rc = build(0, bi * half, std::min(half, M - bi * half))) return rc;
+            held[0] = bi;
+        }
+        if (bj != bi && held[1] != bj) {
+            if (int rc = build(half, bj * half, std::min(half, M - bj * half))) return rc;
+            held[1] = bj;
+        }
+        HIP_TRY(hipMemcpyAsync(plan + g0, h_plan.data() + g0, sizeof(int4) * (size_t)(g1 - g0), hipMemcpyHostToDevice, s));
+        for (int64_t k0 = g0; k0 < g1; k0 += pass_pairs) {
+            const int64_t kc = std::min(pass_pairs, g1 - k0);
+            if (k0 != g0) {
+                if (int rc = begin_pass(c)) return rc;
+                c->status_dirty = true;
+            }
+            launch_ens_records(s, plan + k0, kc, (int32_t)n, d_wf, anchors, wf_rec);
+            if (int rc = ens_sweep(c, st, anchors, iota, slots * n, wf_rec, kc * n, tmp, meta)) return rc;
+            launch_ens_scatter(s, tmp, plan + k0, kc, (int32_t)n, d_out);
+        }
+        g0 = g1;
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    return LCHD_OK;
+}
+
+// d_pairs: DEVICE [n_pairs][2] or null (every i < j, i outer); excluded columns: DEVICE CSR or null.  Copies the (small) pair and
+// exclusion lists to the host to validate them and to plan the blocks; the P * n records are made on the device.
+extern "C" int lchd_ensemble_from_coords_dev(lchd_ctx* c, lchd_cloud* cl, const int32_t* d_pairs, int64_t n_pairs, const int32_t* d_excl_start,
+                                             const int32_t* d_excl_idx, const int32_t* d_wf_index, double* d_out) {
+    if (!c || !cl) return fail(LCHD_EVALUE, "null argument");
+    if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (!cl->sid || cl->struct_size <= 0 || cl->n != (int64_t)cl->n_struct * cl->struct_size)
+        return fail(LCHD_EVALUE, "the ensemble call takes a regular batch (structures of equal size stored one after the other: "
+                                 "lchd_cloud_create_batch or a frames buffer)");
+    if (n_pairs < 0) return fail(LCHD_EVALUE, "negative number of structure pairs");
+    CTX_GUARD(c);
+    const int64_t n = cl->struct_size, M = cl->n_struct;
+    if (!d_pairs && n_pairs != M * (M - 1) / 2)
+        return fail(LCHD_EVALUE, "without a pair list the call scores all %lld pairs i < j of %lld structures (got n_pairs = %lld)",
+                    (long long)(M * (M - 1) / 2), (long long)M, (long long)n_pairs);
+    if (n_pairs > 0 && !d_out) return fail(LCHD_EVALUE, "null score pointer");
+    if (int rc = resolve_bbox(c, cl)) return rc;  // (a frames buffer: waits for its upload, rejects non-finite coordinates)
+    std::vector<int32_t> pairs((size_t)n_pairs * 2);
+    if (d_pairs) {
+        if (n_pairs) HIP_TRY(hipMemcpyAsync(pairs.data(), d_pairs, sizeof(int32_t) * pairs.size(), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (int64_t p = 0; p < n_pairs; ++p)
+            for (int k = 0; k < 2; ++k)
+                if (pairs[2 * p + k] < 0 || pairs[2 * p + k] >= M)
+                    return fail(LCHD_EVALUE, "structure pair %lld refers to structure %d of %lld", (long long)p, pairs[2 * p + k], (long long)M);
+    } else {
+        size_t k = 0;
+        for (int32_t i = 0; i < M; ++i)
+            for (int32_t j = i + 1; j < M; ++j) { pairs[k++] = i; pairs[k++] = j; }
+    }
+    if (d_excl_start || d_excl_idx) {
+        if (!d_excl_start || !d_excl_idx) return fail(LCHD_EVALUE, "the exclusion list needs both its row starts and its column indices");
+        std::vector<int32_t> xs((size_t)n + 1);
+        HIP_TRY(hipMemcpyAsync(xs.data(), d_excl_start, sizeof(int32_t) * xs.size(), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (xs[0] != 0) return fail(LCHD_EVALUE, "the exclusion list's row starts must begin with 0");
+        for (int64_t r = 0; r < n; ++r)
+            if (xs[(size_t)r + 1] < xs[(size_t)r]) return fail(LCHD_EVALUE, "the exclusion list's row starts must not decrease");
+        std::vector<int32_t> xi((size_t)xs[(size_t)n]);
+        if (!xi.empty()) {
+            HIP_TRY(hipMemcpyAsync(xi.data(), d_excl_idx, sizeof(int32_t) * xi.size(), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        for (size_t e = 0; e < xi.size(); ++e)
+            if (xi[e] < 0 || xi[e] >= n) return fail(LCHD_EVALUE, "excluded column %d is outside [0, %lld)", xi[e], (long long)n);
+    }
+    CloudView cats = cl->view(c->h_cfg.n_categories > kMaxCategories);  // (every structure carries the topology's categories: structure 0's are read)
+    cats.n = (int32_t)n;
+    cats.sid = nullptr;
+    cats.n_struct = 1;
+    cats.struct_size = 0;
+    return ensemble_core(c, EnsSrc{cats, cl, nullptr, d_excl_start, d_excl_idx}, n, M, pairs, d_wf_index, d_out);
+}
+
+static int ens_check_pairs(const int32_t* pairs, int64_t n_pairs, int64_t M) {
+    if (n_pairs < 0) return fail(LCHD_EVALUE, "negative number of structure pairs");
+    if (n_pairs > 0 && !pairs) return LCHD_OK;
+    for (int64_t p = 0; pairs && p < n_pairs; ++p)
+        for (int k = 0; k < 2; ++k)
+            if (pairs[2 * p + k] < 0 || pairs[2 * p + k] >= M)
+                return fail(LCHD_EVALUE, "structure pair %lld refers to structure %d of %lld", (long long)p, pairs[2 * p + k], (long long)M);
+    return LCHD_OK;
+}
+
+// device copies of a host call's arrays, released on every path out
+struct EnsDevBufs {
+    std::vector<void*> p;
+    ~EnsDevBufs() { for (void* q : p) (void)hipFree(q); }
+    template <class T>
+    int put(const T* h, size_t count, T** d) {
+        *d = nullptr;
+        if (!count) return LCHD_OK;
+        void* q = nullptr;
+        HIP_TRY(hipMalloc(&q, sizeof(T) * count));
+        p.push_back(q);
+        if (h) HIP_TRY(hipMemcpy(q, h, sizeof(T) * count, hipMemcpyHostToDevice));
+        *d = static_cast<T*>(q);
+        return LCHD_OK;
+    }
+};
+
+extern "C" int lchd_ensemble_from_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t n, const double* xyz, int64_t n_struct,
+                                         const int32_t* pairs, int64_t n_pairs, const int32_t* excl_start, const int32_t* excl_idx,
+                                         const int32_t* wf_index, double* out) {
+    if (!c) return fail(LCHD_EVALUE, "null context");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (n < 0 || n_struct < 0) return fail(LCHD_EVALUE, "negative size");
+    if (n_struct * n > ((int64_t)1 << 30)) return fail(LCHD_EUNSUPPORTED, "%lld atoms in all exceed a batch", (long long)(n_struct * n));
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    if (int rc = check_wf_index(cfg, wf_index, n)) return rc;
+    if (int rc = ens_check_pairs(pairs, n_pairs, n_struct)) return rc;
+    const int64_t P = pairs ? n_pairs : n_struct * (n_struct - 1) / 2;
+    if (!pairs && n_pairs != P)
+        return fail(LCHD_EVALUE, "without a pair list the call scores all %lld pairs i < j of %lld structures (got n_pairs = %lld)", (long long)P,
+                    (long long)n_struct, (long long)n_pairs);
+    c->last_valid = false;
+    if (P == 0 || n == 0) return LCHD_OK;
+    if (!(excl_start == nullptr) != !(excl_idx == nullptr)) return fail(LCHD_EVALUE, "the exclusion list needs both its row starts and its column indices");
+    std::vector<int32_t> cat((size_t)(n_struct * n)), sid((size_t)(n_struct * n));
+    for (int64_t k = 0; k < n_struct; ++k)
+        for (int64_t i = 0; i < n; ++i) { cat[(size_t)(k * n + i)] = seq[i]; sid[(size_t)(k * n + i)] = (int32_t)k; }
+    lchd_cloud* cl = nullptr;
+    if (int rc = lchd_cloud_create_batch(c, xyz, cat.data(), nullptr, sid.data(), n_struct * n, (int32_t)n_struct, &cl)) return rc;
+    struct Drop { lchd_ctx* c; lchd_cloud* cl; ~Drop() { lchd_cloud_destroy(c, cl); } } drop{c, cl};
+    EnsDevBufs bufs;
+    int32_t *d_pairs = nullptr, *d_xs = nullptr, *d_xi = nullptr, *d_wf = nullptr;
+    double* d_out = nullptr;
+    if (int rc = bufs.put(pairs, (size_t)(pairs ? 2 * n_pairs : 0), &d_pairs)) return rc;
+    if (excl_start) {
+        if (excl_start[0] != 0 || excl_start[n] < excl_start[0]) return fail(LCHD_EVALUE, "the exclusion list's row starts must begin with 0 and not decrease");
+        if (int rc = bufs.put(excl_start, (size_t)n + 1, &d_xs)) return rc;
+        if (int rc = bufs.put(excl_start[n] ? excl_idx : nullptr, (size_t)std::max<int32_t>(excl_start[n], 1), &d_xi)) return rc;
+    }
+    if (int rc = bufs.put(wf_index, (size_t)(wf_index ? n : 0), &d_wf)) return rc;
+    if (int rc = bufs.put<double>(nullptr, (size_t)(P * n), &d_out)) return rc;
+    if (int rc = lchd_ensemble_from_coords_dev(c, cl, d_pairs, P, d_xs, d_xi, d_wf, d_out)) return rc;
+    HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * (size_t)(P * n), hipMemcpyDeviceToHost));
+    return LCHD_OK;
+}
+
+extern "C" int lchd_ensemble_from_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t n, const double* dmx, int64_t n_struct,
+                                       const int32_t* pairs, int64_t n_pairs, const int32_t* wf_index, double* out) {
+    if (!c) return fail(LCHD_EVALUE, "null context");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (n < 0 || n_struct < 0) return fail(LCHD_EVALUE, "negative size");
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    if (int rc = check_wf_index(cfg, wf_index, n)) return rc;
+    if (int rc = ens_check_pairs(pairs, n_pairs, n_struct)) return rc;
+    const int64_t P = pairs ? n_pairs : n_struct * (n_struct - 1) / 2;
+    if (!pairs && n_pairs != P)
+        return fail(LCHD_EVALUE, "without a pair list the call scores all %lld pairs i < j of %lld structures (got n_pairs = %lld)", (long long)P,
+                    (long long)n_struct, (long long)n_pairs);
+    c->last_valid = false;
+    if (P == 0 || n == 0) return LCHD_OK;
+    std::vector<int32_t> hp((size_t)P * 2);
+    if (pairs) {
+        std::copy(pairs, pairs + 2 * P, hp.begin());
+    } else {
+        size_t k = 0;
+        for (int32_t i = 0; i < n_struct; ++i)
+            for (int32_t j = i + 1; j < n_struct; ++j) { hp[k++] = i; hp[k++] = j; }
+    }
+    lchd_cloud* cl = nullptr;  // the topology's categories (no coordinates: the rows are given)
+    if (int rc = lchd_cloud_create(c, nullptr, seq, nullptr, n, &cl)) return rc;
+    struct Drop { lchd_ctx* c; lchd_cloud* cl; ~Drop() { lchd_cloud_destroy(c, cl); } } drop{c, cl};
+    EnsDevBufs bufs;
+    int32_t* d_wf = nullptr;
+    double* d_out = nullptr;
+    if (int rc = bufs.put(wf_index, (size_t)(wf_index ? n : 0), &d_wf)) return rc;
+    if (int rc = bufs.put<double>(nullptr, (size_t)(P * n), &d_out)) return rc;
+    const CloudView cats = cl->view(cfg->n_categories > kMaxCategories);
+    if (int rc = ensemble_core(c, EnsSrc{cats, nullptr, dmx, nullptr, nullptr}, n, n_struct, hp, d_wf, d_out)) return rc;
+    HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * (size_t)(P * n), hipMemcpyDeviceToHost));
+    return LCHD_OK;
 }

@@ -88,6 +88,7 @@ struct Tuning {
     int force_cmax = 0;             // LCHD_FORCE_CMAX: at least this many category slots
     int per_pair = 0;               // LCHD_PER_PAIR: -1 never a side B without de-duplication, 1 whenever it applies, 0: from the previous pass (side-B anchors (almost) all unique)
     int pre_rows = 0;               // LCHD_PRE_ROWS: -1 never prefix-count rows next to the environments (the team sweeps build their chunk-start counts per tile), 1 also for small calls, 0: by the rule of prims_enqueue
+    int ensemble_block = 0;         // LCHD_ENSEMBLE_BLOCK: at most this many structures resident in the dense ensemble call's environment store (0: as many as the free HBM holds)
 };
 
 struct WfEntry {
@@ -417,6 +418,15 @@ void launch_scatter_scores(hipStream_t s, const double* scores, const int64_t* i
 void launch_unshard_scores(hipStream_t s, const double* gathered, const ShardCounts& counts, int world, int64_t stride, double* out,
                            int64_t n_pairs, uint32_t* bad);
 void launch_env_points(hipStream_t s, const SweepArgs& a, unsigned long long* out);
+// Dense ensemble call (lchd_ensemble.hip).  Distance rows [n_rows][n] of the consecutive n-atom structures that start at atom
+// atom0 of c (row k * n + r: atom r of structure k), the excluded entries (CSR over the n rows of a structure, or null) +inf.
+void launch_ens_dist(hipStream_t s, const CloudView& c, int64_t atom0, int32_t n, int64_t n_rows, const int32_t* excl_start,
+                     const int32_t* excl_idx, double* dmx);
+void launch_ens_iota(hipStream_t s, uint32_t* slot, int64_t n);
+// plan[k] = {slot of structure i, slot of structure j, output pair, 0}: record k * n + r = (slot_i * n + r, slot_j * n + r),
+// weight function wf[r] (wf / wf_rec null: all 0); the scatter puts score k * n + r at out[plan[k].z * n + r]
+void launch_ens_records(hipStream_t s, const int4* plan, int64_t n_plan, int32_t n, const int32_t* wf, int64_t* anchors, int32_t* wf_rec);
+void launch_ens_scatter(hipStream_t s, const double* scores, const int4* plan, int64_t n_plan, int32_t n, double* out);
 // from_anchors on lists whose distances do not ascend: the reference's loop walked literally by one lane (lchd_sweep.hip)
 void launch_anchors_literal(hipStream_t s, const DevConfig* cfg, int n_categories, const EnvStore& ea, const EnvStore& eb, int nA, int nB, int wfi,
                             double* out);

@@ -128,6 +128,41 @@ class DeviceSession:
         N.check(N.lib().lchd_from_coords_dev(self._ctx, cloud_a, cloud_b, wf_ptr, C.c_void_p(out.data_ptr())))
         return out
 
+    def from_coords_ensemble(self, batch, pairs=None, out=None, wf_index=None, excluded=None):
+        """LoCoHD.from_coords_ensemble on a batch from `upload_batch` (structures of equal size) or a frames buffer: row r of
+        structure pair p = from_coords(seq, seq, X[i_p], X[j_p])[r].  pairs: torch int32 CUDA tensor [P][2] or None (every
+        i < j); wf_index: torch int32 CUDA tensor [n] or None; excluded: iterable of (r, c) atom pairs counted as +inf.
+        Returns (or fills) a torch float64 CUDA tensor [P][n]."""
+        torch = self.torch
+        dev = torch.device("cuda", self.device)
+        total = int(N.lib().lchd_cloud_size(batch))
+        m = self._n_structures(batch)
+        n = total // m if m else 0
+        pairs_ptr, p = None, m * (m - 1) // 2
+        if pairs is not None:
+            assert pairs.is_cuda and pairs.dtype == torch.int32 and pairs.is_contiguous() and pairs.dim() == 2 and pairs.shape[1] == 2
+            pairs_ptr, p = C.c_void_p(pairs.data_ptr()), pairs.shape[0]
+        if out is None:
+            out = torch.empty((p, n), dtype=torch.float64, device=dev)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= p * n
+        wf_ptr = None
+        if wf_index is not None:
+            assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= n
+            wf_ptr = C.c_void_p(wf_index.data_ptr())
+        xs_ptr = xi_ptr = None
+        keep = []
+        if excluded is not None:
+            xs, xi = LoCoHD._exclusion_csr(excluded, n)
+            xs_t, xi_t = torch.from_numpy(xs).to(dev), torch.from_numpy(xi if len(xi) else np.zeros(1, dtype=np.int32)).to(dev)
+            keep += [xs_t, xi_t]
+            xs_ptr, xi_ptr = C.c_void_p(xs_t.data_ptr()), C.c_void_p(xi_t.data_ptr())
+        N.check(N.lib().lchd_ensemble_from_coords_dev(self._ctx, batch, pairs_ptr, p, xs_ptr, xi_ptr, wf_ptr, C.c_void_p(out.data_ptr())))
+        return out
+
+    def _n_structures(self, cloud) -> int:
+        """Structures a cloud / batch / frames buffer currently holds (lchd_cloud_structures)."""
+        return int(N.lib().lchd_cloud_structures(cloud))
+
     # ---- asynchronous form + trajectory streaming ----------------------------------------------------------------
     def from_primitives_async(self, cloud_a, cloud_b, anchors, threshold_distance: float, out, wf_index=None):
         """Enqueue one pass and return immediately; `finish()` waits for it and raises on errors."""
