@@ -16,6 +16,14 @@
  * integer (equal strings <=> equal integers; only equality is ever used,
  * src/locohd/tag_pairing_rule.rs:49-75).  The caller owns every buffer; the library never frees or
  * retains caller memory beyond the call (mirrors the reference's copy-in / copy-out ownership).
+ *
+ * Threads: calls on one context are serialised.  Every entry point that takes an lchd_ctx holds the context for the whole call
+ * (lchd_ctx_destroy excepted: no call may be in flight when it is called), so threads may share a context and each gets the
+ * result, the status and the lchd_last_error() text of its own call; they simply run one after the other.  Between
+ * lchd_from_primitives_dev_async and lchd_ctx_finish the context stays with the thread that enqueued the pass: that thread may
+ * go on calling (a second async call is LCHD_EVALUE as before), a call from any other thread waits until the pass is finished
+ * (any thread may call lchd_ctx_finish).  lchd_group_from_primitives and lchd_group_last_counts are serialised per group in the
+ * same way.  For parallel throughput use one context (one LoCoHD instance) per thread.
  */
 #ifndef LOCO_HD_HIP_H
 #define LOCO_HD_HIP_H

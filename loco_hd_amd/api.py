@@ -16,6 +16,7 @@ methods raise DeviceError.
 from __future__ import annotations
 
 import ctypes as C
+import threading
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -78,7 +79,8 @@ class WeightFunction:
 
 
 # Bumped by every PrimitiveAtom SETTER (not by construction): LoCoHD caches the packed form of the lists it is given and a
-# cached list is only valid while none of its atoms has been changed (see LoCoHD._packed_lists).
+# cached list is only valid while none of its atoms has been changed (see LoCoHD._packed_lists).  A setter bumps it AFTER it has
+# changed the atom, and a pack reads it BEFORE it reads the atoms: a pack that overlaps a setter is then stored under an older stamp.
 _ATOM_MUTATIONS = [0]
 
 
@@ -87,27 +89,44 @@ _ATOM_MUTATIONS = [0]
 # atom in native code (_fastpack.pack_atoms), whatever list object the atoms arrive in.  The reference's PyO3 extraction clones
 # both Strings of every atom on every call instead (primitive_atom.rs:4-16, src/locohd.rs:479-485).  Ids are never re-used; the
 # tables grow with the number of DISTINCT strings the process has seen (residue tags, primitive type names).
+# New entries (and the mutation stamp) are written under _INTERN_LOCK: two threads interning new names at once would otherwise
+# read the same next id.  A name is entered in _TYPE_NAMES before its id is published in _TYPE_IDS.  (Re-entrant: hashing a str
+# subclass runs Python code, which may pack a list while the lock is held.)
 _TYPE_IDS: Dict[Any, int] = {}
 _TYPE_NAMES: List[Any] = []
 _TAG_IDS: Dict[Any, int] = {}
+_INTERN_LOCK = threading.RLock()
 
 
 def _type_id(value) -> int:
     try:
         i = _TYPE_IDS.get(value)
+        if i is None:
+            with _INTERN_LOCK:
+                i = _TYPE_IDS.get(value)
+                if i is None:
+                    i = len(_TYPE_NAMES)
+                    _TYPE_NAMES.append(value)
+                    _TYPE_IDS[value] = i
     except TypeError:  # unhashable: no id (the general packing path looks str(value) up)
         return -1
-    if i is None:
-        i = _TYPE_IDS[value] = len(_TYPE_NAMES)
-        _TYPE_NAMES.append(value)
     return i
 
 
 def _tag_id(value) -> int:
     try:
-        return _TAG_IDS.setdefault(value, len(_TAG_IDS))
+        i = _TAG_IDS.get(value)
+        if i is None:
+            with _INTERN_LOCK:
+                i = _TAG_IDS.setdefault(value, len(_TAG_IDS))
     except TypeError:
         return -1
+    return i
+
+
+def _bump_mutations() -> None:
+    with _INTERN_LOCK:
+        _ATOM_MUTATIONS[0] += 1
 
 
 class PrimitiveAtom:
@@ -131,9 +150,9 @@ class PrimitiveAtom:
 
     @primitive_type.setter
     def primitive_type(self, value: str) -> None:
-        _ATOM_MUTATIONS[0] += 1
         self._primitive_type = value
         self._pid = _type_id(value)
+        _bump_mutations()
 
     @property
     def tag(self) -> str:
@@ -141,9 +160,9 @@ class PrimitiveAtom:
 
     @tag.setter
     def tag(self, value: str) -> None:
-        _ATOM_MUTATIONS[0] += 1
         self._tag = value
         self._tid = _tag_id(value)
+        _bump_mutations()
 
     @property
     def coordinates(self) -> List[float]:
@@ -154,8 +173,8 @@ class PrimitiveAtom:
         v = [float(x) for x in value]
         if len(v) != 3:
             raise ValueError(f"expected a sequence of length 3 (got {len(v)})")
-        _ATOM_MUTATIONS[0] += 1
         self._coordinates = v
+        _bump_mutations()
 
     def __getstate__(self):
         return (self._primitive_type, self._tag, self._coordinates)
@@ -288,6 +307,8 @@ class LoCoHD:
             raise ValueError("deterministic=True applies to one device (the device group picks kernels per share)")
         self._ctx = None
         self._group = None
+        self._handle_lock = threading.Lock()  # the context / device group is created once, whichever threads ask first
+        self._cache_lock = threading.Lock()   # _pack_cache is reordered and trimmed by every thread that uses the instance
         self._pack_cache: List[Any] = []   # most recent first: (list, its items, mutation stamp, None, packed, interner)
         self._pid_map = np.empty(0, dtype=np.int32)  # PrimitiveAtom type id -> category index (_type_map)
         self._anchor_cache = None
@@ -311,22 +332,35 @@ class LoCoHD:
         return self._tpr
 
     # ---- plumbing -----------------------------------------------------------------------------------
+    # Threads may share an instance: the C library serialises the calls on one context / device group (include/loco_hd_hip.h,
+    # "Threads"); for parallel throughput give every thread a LoCoHD of its own.
     def _context(self):
-        if self._ctx is None:
-            h = C.c_void_p()
-            N.check(N.lib().lchd_ctx_create(self._device, C.byref(h)))
-            self._ctx = h
-            if self._deterministic:
-                N.check(N.lib().lchd_ctx_set_deterministic(h, 1))
-        return self._ctx
+        ctx = self._ctx
+        if ctx is None:
+            with self._handle_lock:
+                if self._ctx is None:
+                    h = C.c_void_p()
+                    N.check(N.lib().lchd_ctx_create(self._device, C.byref(h)))
+                    if self._deterministic:
+                        rc = N.lib().lchd_ctx_set_deterministic(h, 1)
+                        if rc:
+                            N.lib().lchd_ctx_destroy(h)
+                            N.check(rc)
+                    self._ctx = h  # published once it is fully set up
+                ctx = self._ctx
+        return ctx
 
     def _device_group(self):
-        if self._group is None:
-            h = C.c_void_p()
-            devs = np.asarray(self._devices, dtype=np.int32)
-            N.check(N.lib().lchd_group_create(N.ip(devs), len(devs), C.byref(h)))
-            self._group = h
-        return self._group
+        grp = self._group
+        if grp is None:
+            with self._handle_lock:
+                if self._group is None:
+                    h = C.c_void_p()
+                    devs = np.asarray(self._devices, dtype=np.int32)
+                    N.check(N.lib().lchd_group_create(N.ip(devs), len(devs), C.byref(h)))
+                    self._group = h
+                grp = self._group
+        return grp
 
     def last_group_counts(self) -> List[int]:
         """Anchor pairs each device of ``devices`` scored in the most recent from_primitives / from_packed call."""
@@ -374,8 +408,12 @@ class LoCoHD:
         cfg.tag_mode, cfg.tag_accept_same = t._mode, int(t._accept_same)
         cfg.tag_accepted_pairs, cfg.tag_ordered = int(t._accepted_pairs), int(t._ordered)
         interner = {} if interner is None else interner
-        pairs = np.asarray([[interner.setdefault(a, len(interner)), interner.setdefault(b, len(interner))]
-                            for a, b in sorted(t._pairs)], dtype=np.int32).reshape(-1, 2)
+        if interner is _TAG_IDS:  # the process-wide table: ids are handed out under its lock
+            intern = _tag_id
+        else:
+            def intern(s):
+                return interner.setdefault(s, len(interner))
+        pairs = np.asarray([[intern(a), intern(b)] for a, b in sorted(t._pairs)], dtype=np.int32).reshape(-1, 2)
         keep.append(pairs)
         cfg.tag_pairs = N.ip(pairs) if len(pairs) else None
         cfg.n_tag_pairs = len(pairs)
@@ -535,11 +573,12 @@ class LoCoHD:
     _CACHE_ENTRIES = 8
 
     def _cache_lookup(self, prims, parent):
-        for k, e in enumerate(self._pack_cache):
-            if e[0] is prims and e[3] is parent and e[2] == _ATOM_MUTATIONS[0] and _fastpack.same_items(prims, e[1]):
-                if k:
-                    self._pack_cache.insert(0, self._pack_cache.pop(k))
-                return e
+        with self._cache_lock:
+            for k, e in enumerate(self._pack_cache):
+                if e[0] is prims and e[3] is parent and e[2] == _ATOM_MUTATIONS[0] and _fastpack.same_items(prims, e[1]):
+                    if k:
+                        self._pack_cache.insert(0, self._pack_cache.pop(k))
+                    return e
         return None
 
     def _type_map(self) -> np.ndarray:
@@ -559,23 +598,27 @@ class LoCoHD:
             xyz, cat, tag = np.empty((n, 3), dtype=np.float64), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
             if _fastpack.pack_atoms(prims, PrimitiveAtom, self._type_map(), xyz, cat, tag):
                 return _Packed(xyz, cat, tag)
-        return self.pack(prims, _TAG_IDS)
+        with _INTERN_LOCK:  # (new tags enter the process-wide table)
+            return self.pack(prims, _TAG_IDS)
 
     def _packed_lists(self, prim_a, prim_b):
         """(packed A, packed B, interner): tags of both lists (and of the tag rule, _config) are ids of ONE table, the process-wide
         one of PrimitiveAtom -- only their equality matters (tag_pairing_rule.rs:49-75)."""
         if _fastpack is None or not hasattr(_fastpack, "same_items"):
-            return self.pack(prim_a, _TAG_IDS), self.pack(prim_b, _TAG_IDS), _TAG_IDS
+            with _INTERN_LOCK:
+                return self.pack(prim_a, _TAG_IDS), self.pack(prim_b, _TAG_IDS), _TAG_IDS
         entries = []
         for prims in (prim_a, prim_b):
             e = self._cache_lookup(prims, None)
             if e is None:
-                packed = self._pack_global(prims)
+                stamp = _ATOM_MUTATIONS[0]  # before the atoms are read (see _ATOM_MUTATIONS)
                 items = _fastpack.items_tuple(prims, PrimitiveAtom)
-                e = (prims, items, _ATOM_MUTATIONS[0], None, packed, _TAG_IDS)
+                packed = self._pack_global(prims)
+                e = (prims, items, stamp, None, packed, _TAG_IDS)
                 if items is not None:
-                    self._pack_cache.insert(0, e)
-                    del self._pack_cache[self._CACHE_ENTRIES:]
+                    with self._cache_lock:
+                        self._pack_cache.insert(0, e)
+                        del self._pack_cache[self._CACHE_ENTRIES:]
             entries.append(e)
         return entries[0][4], entries[1][4], _TAG_IDS
 
@@ -584,6 +627,8 @@ class LoCoHD:
         c = self._anchor_cache
         if c is not None and c[0] is anchor_pairs and _fastpack is not None and hasattr(_fastpack, "same_items") and _fastpack.same_items(anchor_pairs, c[1]):
             return c[2], c[3]
+        # (the items are taken BEFORE the conversion: a list changed in between then fails same_items rather than hit a stale entry)
+        items = _fastpack.items_tuple(anchor_pairs, tuple) if (_fastpack is not None and hasattr(_fastpack, "items_tuple")) else None
         if _fastpack is not None and hasattr(_fastpack, "pairs_into") and hasattr(anchor_pairs, "__len__"):
             arr = np.empty((len(anchor_pairs), 2), dtype=np.int64)
             keys = _fastpack.pairs_into(anchor_pairs, arr)  # (AnchorPairSpecifier in native code, like the PyO3 derive)
@@ -592,7 +637,6 @@ class LoCoHD:
             pairs, keys = self._split_anchor_pairs(anchor_pairs)
             idx = self._wf_indices(keys, len(pairs))
             arr = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
-        items = _fastpack.items_tuple(anchor_pairs, tuple) if (_fastpack is not None and hasattr(_fastpack, "items_tuple")) else None
         self._anchor_cache = (anchor_pairs, items, arr, idx) if items is not None else None
         return arr, idx
 

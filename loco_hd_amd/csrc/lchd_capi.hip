@@ -9,9 +9,11 @@
 
 #include <algorithm>
 #include <cmath>
+#include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -161,7 +163,22 @@ struct lchd_cloud {
 
 enum { PH_CELLS = 0, PH_ANCHORS = 1, PH_ENV = 2, PH_SWEEP = 3, PH_N = 4 };
 
+// Calls on one context are serialised (include/loco_hd_hip.h, "Threads"): every entry point that takes a context holds it for its
+// whole duration (CtxLock below).  The owner may re-enter (lchd_from_primitives_dev is lchd_from_primitives_dev_async +
+// lchd_ctx_finish).  Between lchd_from_primitives_dev_async and lchd_ctx_finish the context stays with the thread that enqueued the
+// pass: that thread may go on calling (and gets today's errors, e.g. LCHD_EVALUE for a second async call), a call from any other
+// thread waits until the pass has been finished -- lchd_ctx_finish itself excepted, which any thread may make.
+struct CtxMutex {
+    std::mutex m;
+    std::condition_variable cv;
+    std::thread::id owner{};        // the thread inside an entry point (depth > 0)
+    int depth = 0;
+    bool async_open = false;        // an asynchronous pass is pending ...
+    std::thread::id async_owner{};  // ... enqueued by this thread
+};
+
 struct lchd_ctx {
+    CtxMutex mu;
     int device = 0;
     hipStream_t stream = nullptr;
     Tuning tune{};  // LCHD_* test / tuning hooks, read once in lchd_ctx_create
@@ -285,6 +302,37 @@ struct DeviceGuard {
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 #define CTX_GUARD(c) DeviceGuard device_guard_((c)->device)
+
+struct CtxLock {
+    lchd_ctx* c;
+    CtxLock(lchd_ctx* ctx, bool finishing) : c(ctx) {  // ctx == nullptr: nothing to lock (the entry point fails on it)
+        if (!c) return;
+        CtxMutex& mu = c->mu;
+        const std::thread::id me = std::this_thread::get_id();
+        std::unique_lock<std::mutex> lk(mu.m);
+        if (mu.depth > 0 && mu.owner == me) {
+            ++mu.depth;
+            return;
+        }
+        mu.cv.wait(lk, [&] { return mu.depth == 0 && (!mu.async_open || mu.async_owner == me || finishing); });
+        mu.owner = me;
+        mu.depth = 1;
+    }
+    ~CtxLock() {
+        if (!c) return;
+        CtxMutex& mu = c->mu;
+        std::lock_guard<std::mutex> lk(mu.m);
+        if (--mu.depth > 0) return;
+        mu.async_open = c->pend.active;  // (written by the owner only: stable here)
+        mu.async_owner = mu.owner;
+        mu.owner = std::thread::id();
+        mu.cv.notify_all();
+    }
+    CtxLock(const CtxLock&) = delete;
+    CtxLock& operator=(const CtxLock&) = delete;
+};
+#define CTX_LOCK(c) CtxLock ctx_lock_((c), false)
+#define CTX_LOCK_FINISH(c) CtxLock ctx_lock_((c), true)
 
 static int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -414,6 +462,7 @@ extern "C" void lchd_ctx_destroy(lchd_ctx* c) {
 }
 
 extern "C" int lchd_ctx_set_stream(lchd_ctx* c, void* s) {
+    CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     CTX_GUARD(c);
@@ -423,11 +472,13 @@ extern "C" int lchd_ctx_set_stream(lchd_ctx* c, void* s) {
 }
 
 extern "C" int lchd_ctx_enable_timing(lchd_ctx* c, int32_t on) {
+    CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
     c->timing = on != 0;
     return LCHD_OK;
 }
 extern "C" double lchd_ctx_last_ms(lchd_ctx* c, const char* phase) {
+    CTX_LOCK(c);
     static const char* names[PH_N] = {"cells", "anchors", "env", "sweep"};
     if (!c || !phase) return -1.0;
     for (int i = 0; i < PH_N; ++i)
@@ -435,6 +486,7 @@ extern "C" double lchd_ctx_last_ms(lchd_ctx* c, const char* phase) {
     return -1.0;
 }
 extern "C" int64_t lchd_ctx_last_env_points(lchd_ctx* c) {
+    CTX_LOCK(c);
     if (!c || !c->last_valid || c->pend.active) return -1;
     CTX_GUARD(c);
     launch_env_points(c->stream, c->last, c->d_points);
@@ -451,6 +503,7 @@ extern "C" int64_t lchd_ctx_last_env_points(lchd_ctx* c) {
 // context scored before, or on whether the pair was reached through a second pass.  (Environments of more than 65 535 points
 // still take the 64-bit-count sweep, whatever the mode.)
 extern "C" int lchd_ctx_set_deterministic(lchd_ctx* c, int32_t on) {
+    CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     c->deterministic = on != 0;
@@ -462,12 +515,13 @@ extern "C" int lchd_ctx_set_deterministic(lchd_ctx* c, int32_t on) {
     c->sweep_hint = 0;
     return LCHD_OK;
 }
-extern "C" int32_t lchd_ctx_get_deterministic(lchd_ctx* c) { return (c && c->deterministic) ? 1 : 0; }
+extern "C" int32_t lchd_ctx_get_deterministic(lchd_ctx* c) { CTX_LOCK(c); return (c && c->deterministic) ? 1 : 0; }
 
-extern "C" int32_t lchd_ctx_last_dense_fused(lchd_ctx* c) { return (c && c->last_dense_fused) ? 1 : 0; }
-extern "C" int64_t lchd_ctx_pass_count(lchd_ctx* c) { return c ? c->n_passes : -1; }
+extern "C" int32_t lchd_ctx_last_dense_fused(lchd_ctx* c) { CTX_LOCK(c); return (c && c->last_dense_fused) ? 1 : 0; }
+extern "C" int64_t lchd_ctx_pass_count(lchd_ctx* c) { CTX_LOCK(c); return c ? c->n_passes : -1; }
 
 extern "C" int lchd_ctx_set_config(lchd_ctx* c, const lchd_config* cfg) {
+    CTX_LOCK(c);
     if (!c || !cfg) return fail(LCHD_EVALUE, "null context/config");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     CTX_GUARD(c);
@@ -655,6 +709,7 @@ static void cats_encode(const int32_t* cat, int64_t n, uint8_t* lo, uint8_t* hi 
 }
 
 extern "C" int lchd_cloud_create(lchd_ctx* c, const double* xyz, const int32_t* cat, const int32_t* tag, int64_t n, lchd_cloud** out) {
+    CTX_LOCK(c);
     if (!c || !out) return fail(LCHD_EVALUE, "null context");
     *out = nullptr;
     if (n < 0 || n > (int64_t)1 << 30) return fail(LCHD_EUNSUPPORTED, "cloud size %lld out of range", (long long)n);
@@ -705,6 +760,7 @@ extern "C" int lchd_cloud_create(lchd_ctx* c, const double* xyz, const int32_t* 
 
 extern "C" int lchd_cloud_create_batch(lchd_ctx* c, const double* xyz, const int32_t* cat, const int32_t* tag, const int32_t* sid,
                                        int64_t n, int32_t n_struct, lchd_cloud** out) {
+    CTX_LOCK(c);
     if (!c || !out) return fail(LCHD_EVALUE, "null context");
     if (n_struct < 1 || !sid) return fail(LCHD_EVALUE, "a batch needs n_struct >= 1 and a structure id per atom");
     for (int64_t i = 0; i < n; ++i)
@@ -732,6 +788,7 @@ extern "C" int64_t lchd_cloud_size(const lchd_cloud* cl) { return cl ? cl->n : -
 extern "C" int32_t lchd_cloud_structures(const lchd_cloud* cl) { return cl ? cl->n_struct : -1; }
 
 extern "C" int lchd_cloud_set_coords(lchd_ctx* c, lchd_cloud* cl, const double* xyz) {
+    CTX_LOCK(c);
     if (!c || !cl || !xyz) return fail(LCHD_EVALUE, "null argument");
     if (c->pend.active && (c->pend.a == cl || c->pend.b == cl))
         return fail(LCHD_EVALUE, "this structure is in use by an unfinished asynchronous call");
@@ -740,6 +797,7 @@ extern "C" int lchd_cloud_set_coords(lchd_ctx* c, lchd_cloud* cl, const double* 
 }
 
 extern "C" void lchd_cloud_destroy(lchd_ctx* c, lchd_cloud* cl) {
+    CTX_LOCK(c);
     if (!cl) return;
     DeviceGuard device_guard_(c ? c->device : -1);
     if (c) (void)hipStreamSynchronize(c->stream);
@@ -1147,6 +1205,7 @@ static int prims_enqueue(lchd_ctx* c) {
 
 extern "C" int lchd_from_primitives_dev_async(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors,
                                               const int32_t* d_wf_index, int64_t n_pairs, double thr, double* d_out) {
+    CTX_LOCK(c);
     if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
     if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
     if (c->pend.active) return fail(LCHD_EVALUE, "a previous asynchronous call has not been finished (lchd_ctx_finish)");
@@ -1357,6 +1416,7 @@ static int finish_passes(lchd_ctx* c, uint32_t* flags_out) {
 }
 
 extern "C" int lchd_ctx_finish(lchd_ctx* c) {
+    CTX_LOCK_FINISH(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
     auto& P = c->pend;
     if (!P.active) return LCHD_OK;
@@ -1367,12 +1427,13 @@ extern "C" int lchd_ctx_finish(lchd_ctx* c) {
     return status_to_rc(f, DRV_PRIMS);
 }
 
-extern "C" int64_t lchd_ctx_subset_pass_count(lchd_ctx* c) { return c ? c->n_subset_passes : -1; }
-extern "C" int64_t lchd_ctx_per_pair_pass_count(lchd_ctx* c) { return c ? c->n_per_pair_passes : -1; }
-extern "C" int64_t lchd_ctx_last_store_bytes(lchd_ctx* c) { return c ? (int64_t)c->last_store_bytes : -1; }
+extern "C" int64_t lchd_ctx_subset_pass_count(lchd_ctx* c) { CTX_LOCK(c); return c ? c->n_subset_passes : -1; }
+extern "C" int64_t lchd_ctx_per_pair_pass_count(lchd_ctx* c) { CTX_LOCK(c); return c ? c->n_per_pair_passes : -1; }
+extern "C" int64_t lchd_ctx_last_store_bytes(lchd_ctx* c) { CTX_LOCK(c); return c ? (int64_t)c->last_store_bytes : -1; }
 
 extern "C" int lchd_from_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors,
                                         const int32_t* d_wf_index, int64_t n_pairs, double thr, double* d_out) {
+    CTX_LOCK(c);
     if (int rc = lchd_from_primitives_dev_async(c, a, b, d_anchors, d_wf_index, n_pairs, thr, d_out)) return rc;
     return lchd_ctx_finish(c);
 }
@@ -1381,6 +1442,7 @@ extern "C" int lchd_from_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* 
 // trajectory frames: a batch cloud whose structures are frames of one template structure
 // ------------------------------------------------------------------------------------------------
 extern "C" int lchd_frames_create(lchd_ctx* c, const lchd_cloud* tmpl, int32_t capacity_frames, lchd_cloud** out) {
+    CTX_LOCK(c);
     if (!c || !tmpl || !out || capacity_frames < 1) return fail(LCHD_EVALUE, "bad argument");
     CTX_GUARD(c);
     if (tmpl->sid) return fail(LCHD_EVALUE, "the template of a frames buffer must be a single structure");
@@ -1421,6 +1483,7 @@ extern "C" int lchd_frames_create(lchd_ctx* c, const lchd_cloud* tmpl, int32_t c
 }
 
 extern "C" int lchd_frames_load(lchd_ctx* c, lchd_cloud* fr, const double* xyz, int32_t n_frames, void* hip_stream) {
+    CTX_LOCK(c);
     if (!c || !fr || !xyz || !fr->cap_frames) return fail(LCHD_EVALUE, "not a frames buffer");
     if (n_frames < 1 || n_frames > fr->cap_frames) return fail(LCHD_EVALUE, "%d frames do not fit a buffer of %d", n_frames, fr->cap_frames);
     if (c->pend.active && (c->pend.a == fr || c->pend.b == fr))
@@ -1444,6 +1507,7 @@ extern "C" int lchd_frames_load(lchd_ctx* c, lchd_cloud* fr, const double* xyz, 
 
 extern "C" int lchd_frames_set_sources(lchd_ctx* c, lchd_cloud* fr, const int32_t* src_start, const int32_t* src_idx,
                                        int64_t n_src_atoms) {
+    CTX_LOCK(c);
     if (!c || !fr || !fr->cap_frames || !src_start || !src_idx) return fail(LCHD_EVALUE, "not a frames buffer / null map");
     if (c->pend.active && (c->pend.a == fr || c->pend.b == fr))
         return fail(LCHD_EVALUE, "this frames buffer is in use by an unfinished asynchronous call");
@@ -1557,12 +1621,15 @@ static int frames_load_atoms(lchd_ctx* c, lchd_cloud* fr, const float* atom_xyz,
 }
 
 extern "C" int lchd_frames_load_atoms(lchd_ctx* c, lchd_cloud* fr, const float* atom_xyz, int32_t n_frames, void* hip_stream) {
+    CTX_LOCK(c);
     return frames_load_atoms(c, fr, atom_xyz, n_frames, hip_stream, true);
 }
 extern "C" int lchd_frames_load_atoms_dev(lchd_ctx* c, lchd_cloud* fr, const float* d_atom_xyz, int32_t n_frames, void* hip_stream) {
+    CTX_LOCK(c);
     return frames_load_atoms(c, fr, d_atom_xyz, n_frames, hip_stream, false);
 }
 extern "C" double lchd_frames_last_convert_ms(lchd_ctx* c, lchd_cloud* fr) {
+    CTX_LOCK(c);
     if (!c || !fr || !fr->t_valid) return -1.0;
     CTX_GUARD(c);
     float t = -1.f;
@@ -1573,6 +1640,7 @@ extern "C" double lchd_frames_last_convert_ms(lchd_ctx* c, lchd_cloud* fr) {
 /* Read back the primitive-atom coordinates of a frames buffer (or any cloud) as [n][3] f64: lets a caller check the device
  * centroids against its own np.mean, and feeds generate_primitive_pdb for a frame. */
 extern "C" int lchd_cloud_get_coords(lchd_ctx* c, lchd_cloud* cl, double* xyz_out, int64_t n) {
+    CTX_LOCK(c);
     if (!c || !cl || !xyz_out) return fail(LCHD_EVALUE, "null argument");
     if (n != cl->n) return fail(LCHD_EVALUE, "the cloud holds %lld atoms, not %lld", (long long)cl->n, (long long)n);
     CTX_GUARD(c);
@@ -1803,6 +1871,7 @@ extern "C" int lchd_from_primitives(lchd_ctx* c, const lchd_config* cfg, const d
                                     const int32_t* tag_a, int64_t n_a, const double* xyz_b, const int32_t* cat_b,
                                     const int32_t* tag_b, int64_t n_b, const int64_t* anchors, const int32_t* wf_index,
                                     int64_t n_pairs, double thr, double* out) {
+    CTX_LOCK(c);
     if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
     if (int rc = check_wf_index(cfg, wf_index, n_pairs)) return rc;
     if (n_a < 0 || n_b < 0 || n_a > ((int64_t)1 << 30) || n_b > ((int64_t)1 << 30)) return fail(LCHD_EUNSUPPORTED, "structure size out of range");
@@ -1845,6 +1914,7 @@ static int shard_plan_enqueue(lchd_ctx* c, const int64_t* d_anchors, const int64
 static int shard_plan_wait(lchd_ctx* c, int64_t n_pairs, int64_t n_atoms_a, int64_t n_atoms_b, int32_t world, int64_t* counts_out);
 
 struct lchd_group {
+    mutable std::mutex mu;  // lchd_group_from_primitives / lchd_group_last_counts are serialised per group
     std::vector<lchd_ctx*> ctx;
     std::vector<int64_t> last_counts;
     // the caller's pair list and the scores in the caller's order: pinned, visible to every device of the group (grow-only)
@@ -2003,6 +2073,7 @@ static int group_call_device_partition(lchd_group* g, const lchd_config* cfg, co
 extern "C" int32_t lchd_group_size(const lchd_group* g) { return g ? (int32_t)g->ctx.size() : 0; }
 extern "C" int lchd_group_last_counts(const lchd_group* g, int64_t* counts_out) {
     if (!g || !counts_out) return fail(LCHD_EVALUE, "null argument");
+    std::lock_guard<std::mutex> lk(g->mu);
     for (size_t k = 0; k < g->ctx.size(); ++k) counts_out[k] = g->last_counts[k];
     return LCHD_OK;
 }
@@ -2012,6 +2083,7 @@ extern "C" int lchd_group_from_primitives(lchd_group* g, const lchd_config* cfg,
                                           const int32_t* tag_b, int64_t n_b, const int64_t* anchors, const int32_t* wf_index,
                                           int64_t n_pairs, double thr, double* out) {
     if (!g || !cfg || g->ctx.empty()) return fail(LCHD_EVALUE, "null group / configuration");
+    std::lock_guard<std::mutex> lk(g->mu);
     if (int rc = check_wf_index(cfg, wf_index, n_pairs)) return rc;
     if (n_a < 0 || n_b < 0 || n_a > ((int64_t)1 << 30) || n_b > ((int64_t)1 << 30)) return fail(LCHD_EUNSUPPORTED, "structure size out of range");
     const int world = (int)g->ctx.size();
@@ -2110,6 +2182,7 @@ static int shard_plan_wait(lchd_ctx* c, int64_t n_pairs, int64_t n_atoms_a, int6
 }
 extern "C" int lchd_shard_plan_dev(lchd_ctx* c, const int64_t* d_anchors, int64_t n_pairs, int64_t n_atoms_a, int64_t n_atoms_b, int32_t world,
                                    int64_t* counts_out) {
+    CTX_LOCK(c);
     if (!c || !counts_out) return fail(LCHD_EVALUE, "null argument");
     if (world < 1 || world > kShardMaxWorld) return fail(LCHD_EVALUE, "world size %d outside [1, %d]", world, kShardMaxWorld);
     if (n_pairs < 0 || n_atoms_a < 1) return fail(LCHD_EVALUE, "bad pair / atom count");
@@ -2123,6 +2196,7 @@ extern "C" int lchd_shard_plan_dev(lchd_ctx* c, const int64_t* d_anchors, int64_
 }
 extern "C" int lchd_shard_select_dev(lchd_ctx* c, const int64_t* d_anchors, int64_t n_pairs, int64_t n_atoms_a, int64_t n_atoms_b, int32_t rank,
                                      int64_t* d_sel_anchors, int64_t* d_sel_index) {
+    CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
     if (c->shard_world < 1 || n_pairs != c->shard_pairs || n_atoms_a != c->shard_atoms || n_atoms_b != c->shard_atoms_b)
         return fail(LCHD_EVALUE, "lchd_shard_plan_dev has not been called for this pair list");
@@ -2139,6 +2213,7 @@ extern "C" int lchd_shard_select_dev(lchd_ctx* c, const int64_t* d_anchors, int6
 }
 extern "C" int lchd_unshard_scores_dev(lchd_ctx* c, const double* d_gathered, const int64_t* counts, int32_t world, int64_t stride,
                                        double* d_out, int64_t n_pairs) {
+    CTX_LOCK(c);
     if (!c || !counts) return fail(LCHD_EVALUE, "null argument");
     if (world < 1 || world > kShardMaxWorld) return fail(LCHD_EVALUE, "world size %d outside [1, %d]", world, kShardMaxWorld);
     ShardCounts sc{};
@@ -2384,6 +2459,7 @@ static int dense_driver(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_
  * atom r of b), the environments are the whole structures.  d_wf_index / d_out are device pointers ([n] int32 or NULL,
  * [n] double).  Uses the configuration of lchd_ctx_set_config; d_out is complete on return. */
 extern "C" int lchd_from_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, double* d_out) {
+    CTX_LOCK(c);
     if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
     if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
@@ -2410,6 +2486,7 @@ extern "C" int lchd_from_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, c
 extern "C" int lchd_from_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
                                 int64_t len_seq_b, const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b,
                                 const int32_t* wf_index, double* out) {
+    CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
     if (n_a != n_b)  // src/locohd.rs:420-428 via :472-475
         return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)n_a, (long long)n_b);
@@ -2419,6 +2496,7 @@ extern "C" int lchd_from_coords(lchd_ctx* c, const lchd_config* cfg, const int32
 extern "C" int lchd_from_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
                               int64_t len_seq_b, const double* dmx_a, int64_t rows_a, int64_t cols_a, const double* dmx_b,
                               int64_t rows_b, int64_t cols_b, const int32_t* wf_index, double* out) {
+    CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
     if (rows_a != rows_b)  // src/locohd.rs:420-428
         return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)rows_a, (long long)rows_b);
@@ -2432,6 +2510,7 @@ extern "C" int lchd_from_dmxs_ragged(lchd_ctx* c, const lchd_config* cfg, const 
                                      int64_t len_seq_b, const double* dmx_a, int64_t rows_a, int64_t cols_a, const int32_t* row_len_a,
                                      const double* dmx_b, int64_t rows_b, int64_t cols_b, const int32_t* row_len_b, const int32_t* wf_index,
                                      double* out) {
+    CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
     if (rows_a != rows_b)  // src/locohd.rs:420-428
         return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)rows_a, (long long)rows_b);
@@ -2443,6 +2522,7 @@ extern "C" int lchd_from_dmxs_ragged(lchd_ctx* c, const lchd_config* cfg, const 
 extern "C" int lchd_from_anchors(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const double* dists_a,
                                  int64_t len_dists_a, const int32_t* seq_b, int64_t len_seq_b, const double* dists_b,
                                  int64_t len_dists_b, int32_t wf_index, double* out) {
+    CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     CTX_GUARD(c);
@@ -2750,6 +2830,7 @@ static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, c
 // exclusion lists to the host to validate them and to plan the blocks; the P * n records are made on the device.
 extern "C" int lchd_ensemble_from_coords_dev(lchd_ctx* c, lchd_cloud* cl, const int32_t* d_pairs, int64_t n_pairs, const int32_t* d_excl_start,
                                              const int32_t* d_excl_idx, const int32_t* d_wf_index, double* d_out) {
+    CTX_LOCK(c);
     if (!c || !cl) return fail(LCHD_EVALUE, "null argument");
     if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
@@ -2831,6 +2912,7 @@ struct EnsDevBufs {
 extern "C" int lchd_ensemble_from_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t n, const double* xyz, int64_t n_struct,
                                          const int32_t* pairs, int64_t n_pairs, const int32_t* excl_start, const int32_t* excl_idx,
                                          const int32_t* wf_index, double* out) {
+    CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     if (n < 0 || n_struct < 0) return fail(LCHD_EVALUE, "negative size");
@@ -2870,6 +2952,7 @@ extern "C" int lchd_ensemble_from_coords(lchd_ctx* c, const lchd_config* cfg, co
 
 extern "C" int lchd_ensemble_from_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t n, const double* dmx, int64_t n_struct,
                                        const int32_t* pairs, int64_t n_pairs, const int32_t* wf_index, double* out) {
+    CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     if (n < 0 || n_struct < 0) return fail(LCHD_EVALUE, "negative size");
