@@ -92,7 +92,36 @@ int lchd_config_validate(int64_t n_categories_given, int64_t n_categories_map, c
 /* device < 0 => current HIP device.  Fails with LCHD_EDEVICE when no GPU is usable. */
 int lchd_ctx_create(int32_t device, lchd_ctx **out);
 void lchd_ctx_destroy(lchd_ctx *ctx);
-/* Launch everything on this hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL = default stream. */
+/* Launch everything on this hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL = default stream.
+ *
+ * Streams (tests/test_gpu_streams.py and tests/cabi_streams.c are the executable form of this paragraph, except where it says
+ * "not observable").  The stream may be a
+ * non-blocking one.  lchd_ctx_set_stream first waits, on the host, for everything the context has queued on the stream it leaves,
+ * so work of one context never runs on two streams at once; it is LCHD_EVALUE while an asynchronous pass is pending (the pass stays
+ * intact).  DEVICE pointers passed to a *_dev / _async call (d_anchors, d_wf_index, d_pairs, d_excl_*, d_gathered, and d_out /
+ * d_sel_* as outputs) are read and written IN STREAM ORDER on the context's stream: work queued on that stream in front of the
+ * call (a kernel or hipMemcpyAsync that fills the pair list, a fill of d_out) is complete before the library touches them, and no
+ * host synchronise is needed in between.  Two things must be COMPLETE AT CALL TIME instead: every HOST pointer (it is read before
+ * the call returns; the caller may reuse it at once), and the pair list of lchd_shard_plan_dev, which is read on a side stream of
+ * the context that is not ordered behind the context's stream.  "Complete on return" (lchd_from_primitives_dev,
+ * lchd_from_coords_dev, lchd_ensemble_from_coords_dev, lchd_ctx_finish, lchd_unshard_scores_dev): the host has waited for the
+ * context's stream, so d_out may be read from ANY stream or copied to the host without a further wait.
+ * lchd_from_primitives_dev_async and lchd_shard_select_dev return with their work only queued: their outputs are ready in stream
+ * order on the context's stream (the pass's: for everybody after lchd_ctx_finish).  Structures and configurations come from host
+ * pointers (lchd_cloud_create*, lchd_cloud_set_coords, lchd_ctx_set_config): they are ordered behind what the context's stream
+ * holds -- a pass queued earlier still sees the old contents -- and are complete on return.  A load into a frames buffer
+ * (lchd_frames_load*) runs on ITS `hip_stream` (NULL = the context's stream) and is ordered (a) behind the work queued on that
+ * stream before it, the producer of d_atom_xyz included, (b) behind the last pass that read the buffer, and (c) behind the previous
+ * load of the same buffer (the host waits until the pinned staging block is free); it is refused (LCHD_EVALUE) while an unfinished
+ * asynchronous pass uses the buffer.  Every later call that reads the buffer (a pass, the ensemble call, lchd_cloud_get_coords)
+ * waits for the load, whatever stream it ran on -- on the host, because the frames' bounding box and non-finite flag are needed to
+ * plan the pass --, and reports a non-finite coordinate of the loaded frames as LCHD_EVALUE.
+ * What a caller can rely on, and what is belt and braces: of the load's orderings, (a) and (c) can be observed and are tested (for
+ * (c): the previous load is complete when the next load's call returns).  (b) is not observable through this API: a load is refused
+ * while a pass is pending, and lchd_ctx_finish has waited for the pass on the host before a load is accepted, so the load's stream
+ * wait for the pass's event never has anything left to wait for.  The same holds for the stream wait a pass makes for the load's
+ * event: the host wait in front of it has already covered it.  Both stream waits are kept for a later version in which the host
+ * wait is dropped for passes that need no new grid; the guarantee callers get today is the host-side one. */
 int lchd_ctx_set_stream(lchd_ctx *ctx, void *hip_stream);
 /* Upload a LoCoHD configuration; later *_dev calls use it. (The host-pointer drivers below do this themselves.) */
 int lchd_ctx_set_config(lchd_ctx *ctx, const lchd_config *cfg);

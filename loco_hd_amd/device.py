@@ -36,6 +36,19 @@ class DeviceSession:
         self._clouds = []
 
     def use_current_stream(self):
+        """Move the session to torch's current stream on its device (lchd_ctx_set_stream; non-blocking side streams are fine).
+
+        The call first waits for everything the session has queued on the stream it leaves, and raises ValueError while an
+        asynchronous pass is pending (the pass stays intact).  Afterwards every CUDA tensor handed to a scoring call (anchors,
+        wf_index, pairs, out) is read and written in the order of THAT stream: torch kernels queued on it before the call may
+        still be filling them, and no synchronise is needed in between.  from_primitives / from_coords / from_coords_ensemble /
+        finish return with `out` complete (the host has waited), so it may be read from any stream; from_primitives_async only
+        queues the pass.  Host arrays (upload, set_coords, load_frames, load_atom_frames) are read before the call returns.  A
+        frames load runs on the `stream=` it is given, behind what that stream holds (the producer of a load_atom_frames_dev
+        tensor included) and behind the last pass that read the buffer; whatever reads the buffer later waits for the load.
+        The one input that must be complete when it is passed is the pair list of the sharding plan (dist.select_shard /
+        score_sharded).  tests/test_gpu_streams.py enforces this with delayed producers (include/loco_hd_hip.h, "Streams", names the two
+        internal stream waits that the host-side waits make unobservable)."""
         s = self.torch.cuda.current_stream(self.device).cuda_stream
         N.check(N.lib().lchd_ctx_set_stream(self._ctx, C.c_void_p(s)))
 
