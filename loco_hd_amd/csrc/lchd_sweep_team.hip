@@ -47,6 +47,8 @@ __global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8
     // one buffer per team: list A's points, then list B's (at most TILE together; + the spare entries the head re-reads may touch)
     __shared__ uint64_t s_[WPB][TEAMS][TILE + 2];
     __shared__ uint8_t c_[WPB][TEAMS][TILE + 8];
+    // (TeamTile's PRE branch reads up to kPreStep - 1 category bytes behind a chunk's start without a clamp: at most byte TILE + 1 + kPreStep - 1 of a team's row)
+    static_assert(!PRE || TILE + 1 + (kPreStep - 1) < TILE + 8, "spare category bytes behind list B for the unclamped reads of the prefix-count rows");
     __shared__ uint64_t lc_[LCNT ? WPB : 1][LCNT ? LW * 64 : 1];  // (TeamTile::LCNT: per-lane count rows of the event loop)
     __shared__ double w_s[WGT ? 32 : 1];
     if (!args.forced && rule_in_force(args) != RULE) return;  // another rule's pairs are the majority, or none's: k_sweep sweeps everything

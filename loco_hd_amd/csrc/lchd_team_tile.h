@@ -163,20 +163,53 @@ struct TeamTile {
         if constexpr (PRE) {
             // the rows at or below the two chunk starts (i0 / j0 non-anchor points of A / B lie before this lane's first event), and the
             // one-hot fields of the up to kPreStep - 1 points between a row and its chunk start
-            const int ra_ = i0 / kPreStep, rb_ = j0 / kPreStep;
+            // All of it in 32-bit arithmetic: a point touches ONE count byte of its side.  The up to three points of a side are first
+            // counted in 2-bit fields of one register (field c at bit 2 c: no field exceeds 3), the fields are spread to bytes once, and
+            // the bytes are added to the row's halves (no count exceeds 255: no carry crosses a byte).
+            static_assert(kPreStep >= 1 && kPreStep <= 4 && (kPreStep & (kPreStep - 1)) == 0 && CMAX <= 16, "2-bit fields: at most three points, 16 slots");
+            constexpr int NW32 = (CMAX + 3) / 4;  // 32-bit words of four count bytes per side
+            const unsigned ui0 = (unsigned)i0, uj0 = (unsigned)j0;  // (both >= 0: unsigned division is a shift)
+            const unsigned ra_ = ui0 / kPreStep, rb_ = uj0 / kPreStep, qa_ = ui0 % kPreStep, qb_ = uj0 % kPreStep;
 #pragma unroll
             for (int k = 0; k < NW; ++k) {
                 exA[k] = preA[(size_t)ra_ * NW + k];
                 exB[k] = preB[(size_t)rb_ * NW + k];
             }
+            // Bytes ra_ * kPreStep + m, m < kPreStep - 1, are read without a clamp.  The byte is a point of the list iff m < qa_ (then
+            // ra_ * kPreStep + m < i0 <= mA); every other byte is multiplied by 0 below, and it lies inside the team's buffer whatever
+            // it holds: ra_ * kPreStep + m <= i0 + 2 <= mA + 2, list B's bytes end at most at TILE + 1 + 2, the buffer has TILE + 8.
+            const uint8_t* pa_ = cA + ra_ * kPreStep;
+            const uint8_t* pb_ = cB + rb_ * kPreStep;
+            uint32_t ta_ = 0u, tb_ = 0u;
 #pragma unroll
             for (int m = 0; m < kPreStep - 1; ++m) {
-                const unsigned ca_ = cA[min(ra_ * kPreStep + m, max(mA - 1, 0))], cb_ = cB[min(rb_ * kPreStep + m, max(mB - 1, 0))];
-                const uint64_t oa_ = m < (i0 % kPreStep) ? (1ull << ((ca_ % FPW) * FB)) : 0ull, ob_ = m < (j0 % kPreStep) ? (1ull << ((cb_ % FPW) * FB)) : 0ull;
-                if constexpr (NW == 1) { exA[0] += oa_; exB[0] += ob_; }
-                else {
+                // 1 where point m lies before the chunk's start (m < q), else 0 -- without a compare for rows of four points
+                uint32_t va_, vb_;
+                if (kPreStep == 4 && m == 0) { va_ = min(qa_, 1u); vb_ = min(qb_, 1u); }
+                else if (kPreStep == 4 && m == 1) { va_ = qa_ >> 1; vb_ = qb_ >> 1; }
+                else if (kPreStep == 4 && m == 2) { va_ = qa_ & (qa_ >> 1); vb_ = qb_ & (qb_ >> 1); }
+                else { va_ = (unsigned)m < qa_ ? 1u : 0u; vb_ = (unsigned)m < qb_ ? 1u : 0u; }
+                const unsigned ca_ = pa_[m], cb_ = pb_[m];
+                ta_ += va_ << ((2u * ca_) & 31u);  // (a point's category is below CMAX <= 16; a byte that is no point may hold anything)
+                tb_ += vb_ << ((2u * cb_) & 31u);
+            }
+            if constexpr (kPreStep > 1) {
+                // the four 2-bit fields of the low eight bits of h -> four bytes
+                auto spread2 = [](uint32_t h) -> uint32_t {
+                    const uint32_t t = (h & 0x0000000Fu) | ((h << 12) & 0x000F0000u);
+                    return (t | (t << 6)) & 0x03030303u;
+                };
 #pragma unroll
-                    for (int k = 0; k < NW; ++k) { exA[k] += (int)(ca_ / FPW) == k ? oa_ : 0ull; exB[k] += (int)(cb_ / FPW) == k ? ob_ : 0ull; }
+                for (int k = 0; k < NW; ++k) {
+                    uint32_t la_ = (uint32_t)exA[k], ha_ = (uint32_t)(exA[k] >> 32), lb_ = (uint32_t)exB[k], hb_ = (uint32_t)(exB[k] >> 32);
+                    la_ += spread2(ta_ >> (16 * k));
+                    lb_ += spread2(tb_ >> (16 * k));
+                    if (2 * k + 1 < NW32) {  // (the side's last count word may hold four categories only: its upper half stays as the row has it)
+                        ha_ += spread2(ta_ >> (16 * k + 8));
+                        hb_ += spread2(tb_ >> (16 * k + 8));
+                    }
+                    exA[k] = ((uint64_t)ha_ << 32) | la_;
+                    exB[k] = ((uint64_t)hb_ << 32) | lb_;
                 }
             }
         } else {
@@ -305,7 +338,7 @@ struct TeamTile {
         int i = i0, j = j0;
 #if LCHD_CAT_HEADS
         uint64_t ka = sA[i], kb = sB[j];
-        int cta = cA[i], ctb = cB[j];
+        unsigned cta = cA[i], ctb = cB[j];  // (unsigned from the byte load: no mask is emitted)
 #else
         uint64_t ka = (i < i1) ? sA[i] : kPadKey, kb = (j < j1) ? sB[j] : kPadKey;
 #endif
@@ -326,14 +359,21 @@ struct TeamTile {
 #if LCHD_CAT_HEADS
                 // both heads and their categories are re-read after every event (see k_sweep); run ends are tested on the indices
                 const bool takeA = (i < i1) & ((j >= j1) | (ka <= kb));
-                const uint64_t key = takeA ? ka : kb;
-                const int ct = takeA ? cta : ctb;
+                uint64_t key = takeA ? ka : kb;
+                const unsigned ct = takeA ? cta : ctb;
+                // (the event's key is selected HERE, before the next heads are loaded: the old heads are dead when the loads issue, so the
+                // loads land in the loop-carried registers -- left to itself the compiler sinks the select behind the literal-form
+                // branch and pays two v_mov_b64 per event to rotate the new heads in; no instruction is emitted for this)
+                asm volatile("" : "+v"(key));
                 i += takeA ? 1 : 0;
                 j += takeA ? 0 : 1;
                 ka = sA[i];  // (one past the run's end at most: the buffers have spare entries)
                 kb = sB[j];
                 cta = cA[i];
                 ctb = cB[j];
+                // (opaque to the optimiser: it would otherwise carry the two heads as BYTES around the loop and widen them again with a
+                // v_and_b32 0xff each per event -- ds_read_u8 has already zero-extended them; no instruction is emitted for this)
+                asm("" : "+v"(cta), "+v"(ctb));
 #else
                 const bool takeA = (ka <= kb);
                 const uint64_t key = takeA ? ka : kb;
@@ -358,7 +398,7 @@ struct TeamTile {
 #endif
                 // (unsigned: a signed `% 8` is five instructions; with one count word the category is below 8 -- checked where the
                 // environments were built, foreign ones stored as 0)
-                const unsigned uct = (unsigned)ct;
+                const unsigned uct = ct;
                 const int sh = (int)((NW == 1 ? uct : (uct % FPW)) * FB), sh4 = (int)((uct & 15u) * 4u);
                 int cntA_, cntB_;  // counts of category ct before the update
                 if constexpr (LCNT) {
