@@ -1335,7 +1335,7 @@ static int finish_passes(lchd_ctx* c, uint32_t* flags_out) {
                                                "categories and 2^23 points (the 64-bit-count sweep)", (long long)biggest, kMaxCategories);
             if (P.group && P.group_small && biggest <= kEnvGroupCap) {
                 c->group_small = false;  // the small instantiation of k_env_group overflowed: the same capacity with the regular one
-                c->last_biggest = std::max<int64_t>(biggest, kEnvGroupCapSmall + 1);  // (also when LCHD_ENV_GROUP_SMALL=1 forces the small one)
+                c->last_biggest = std::max<int64_t>(biggest, kEnvGroupCapSmall + 1);
             } else {
                 // The companion sweep for the larger pairs was left out (the previous pass of this context had none): if this pass has
                 // some, their scores were never written -- the whole pass again with the full launch set BEFORE the second pass over

@@ -61,36 +61,19 @@ __device__ __forceinline__ const LCHD_AS4 T* df_const(const T* p) {  // memory t
     return (const LCHD_AS4 T*)(unsigned long long)p;
 }
 
-#ifndef LCHD_DF_NT
-#define LCHD_DF_NT 512     // threads per workgroup (tuning builds: 1024 with LCHD_DF_CAP 14336 and LCHD_DF_BUCKETS 8192 = one workgroup per CU)
-#endif
-#ifndef LCHD_DF_CAP
-#define LCHD_DF_CAP 6144
-#endif
-#ifndef LCHD_DF_BUCKETS
-#define LCHD_DF_BUCKETS 8192
-#endif
-constexpr int kNT = LCHD_DF_NT, kWaves = kNT / 64;
-constexpr int kCap = LCHD_DF_CAP;     // events of one distance segment (keys + values in LDS)
+constexpr int kNT = 512, kWaves = kNT / 64;  // threads per workgroup (1024 with segments of 14336 events -- one workgroup per CU -- was slower: DESIGN.md)
+constexpr int kCap = 6144;            // events of one distance segment (keys + values in LDS)
 constexpr int kEpt = kCap / kNT;      // 14 events per thread in the sort and in the sweep (<= 15: 4-bit chunk-local counters)
-#ifndef LCHD_DF_SAMPLE
-#define LCHD_DF_SAMPLE 4
-#endif
-constexpr int kSample = LCHD_DF_SAMPLE;  // the coarse CDF of a row pair is estimated from every kSample-th point of either row
+constexpr int kSample = 4;            // the coarse CDF of a row pair is estimated from every kSample-th point of either row
 constexpr int kCoarse = 512;          // uniform bins of the distance image; bin kCoarse holds +inf entries of a distance matrix
-#ifndef LCHD_DF_GRID
-#define LCHD_DF_GRID 512              // workgroups of a launch (two per CU): each owns one scratch region and takes rows blockIdx, + grid, ...
-#endif
+constexpr int kGrid = 512;            // workgroups of a launch (two per CU): each owns one scratch region and takes rows blockIdx, + grid, ...
 // events a segment may be PLANNED to hold: the plan sees a sample, the segment must hold the real thing (six standard deviations of the
 // count that a sample of one in kSample predicts, and a coarse bin's worth)
 __host__ __device__ inline int df_seg_margin(int est) { return 6 * (int)sqrtf((float)(est * kSample)) + 70; }
-constexpr int kBuckets = LCHD_DF_BUCKETS;  // buckets of a segment's sort, two 16-bit counters per LDS word
+constexpr int kBuckets = 8192;        // buckets of a segment's sort, two 16-bit counters per LDS word
 constexpr int kBucketLimit = 64;      // a fuller bucket sends the call to the two-kernel path
 constexpr int kPart = kBuckets / 4;   // sqrt(k) for k < kPart from LDS (the histogram's bytes), larger counts are computed
-#ifndef LCHD_DF_MAXSEG
-#define LCHD_DF_MAXSEG 16
-#endif
-constexpr int kMaxSeg = LCHD_DF_MAXSEG;  // (<= 64: the plan gives every boundary a lane)
+constexpr int kMaxSeg = 16;           // (<= 64: the plan gives every boundary a lane)
 constexpr double kExactBelow = 1e-6;  // as lchd_team_tile.h (kExactH2Below): below this H^2 the literal difference-of-roots form
 static_assert(kEpt <= 15 && kCap % kNT == 0, "chunk-local counters are 4-bit fields");
 static_assert((kBuckets / 2) % (4 * kNT) == 0 && kBuckets <= 8192, "the bucket scan gives every thread whole 16-byte groups of histogram words; 13-bit bucket ids");
@@ -861,7 +844,7 @@ size_t dense_fused_scratch(int64_t n_rows, int64_t len_a, int64_t len_b, int32_t
     int S = (int)std::max<int64_t>(1, (total + kCap - 1) / kCap);
     while (S < kMaxSeg && (int)(total / S) + df_seg_margin((int)(total / S)) > kCap) ++S;
     const int segs = std::min(kMaxSeg, S + 2);
-    const int grid = (int)std::min<int64_t>(n_rows, LCHD_DF_GRID);
+    const int grid = (int)std::min<int64_t>(n_rows, kGrid);
     if (grid_out) *grid_out = grid;
     if (segs_out) *segs_out = segs;
     return (size_t)std::max(grid, 1) * (size_t)segs * (size_t)kCap;

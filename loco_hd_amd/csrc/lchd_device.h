@@ -13,10 +13,7 @@ inline size_t wide_scratch_bytes_per_wave(int C) { return (((size_t)C * 65 * 4 +
 constexpr int kWideCategories = 512;  // ... or, for 256 .. 512 categories, as u16 (CloudView::cat_hi, EnvStore::cat16): from_primitives and
                                       // from_anchors only, through k_env_cells<.., uint16_t> and k_sweep_wide<.., CAT16> (its per-lane
                                       // category counts, 256 bytes per category, must fit the LDS)
-#ifndef LCHD_SWEEP_EPL
-#define LCHD_SWEEP_EPL 6
-#endif
-constexpr int kSweepEPL = LCHD_SWEEP_EPL;  // merged events per lane per tile in the sweep kernel (16-bit counts, LDS tables, <= 16 category slots; the generic distances)
+constexpr int kSweepEPL = 6;  // merged events per lane per tile in the sweep kernel (16-bit counts, LDS tables, <= 16 category slots; the generic distances)
 constexpr int kSweepTile = 64 * kSweepEPL;
 constexpr int kMetaPartials = 4096;   // most workgroups of k_pair_meta
 constexpr uint64_t kPadKey = ~0ull;   // sorts after every valid (non-negative, non-NaN) f64 bit pattern
@@ -174,10 +171,7 @@ struct EnvStore {
     uint8_t* cat0;       // [slots] category of every environment's first (sorted) point, or null: what k_pair_meta puts into the pair records -- one
                          // gather into a small array instead of one into the store itself (k_env_group writes it; the other environment kernels do not)
 };
-#ifndef LCHD_PRE_STEP
-#define LCHD_PRE_STEP 4
-#endif
-constexpr int kPreStep = LCHD_PRE_STEP;  // points per prefix-count row (round 6: every row of round 5's store cost the sweeps one 128-byte line per lane)
+constexpr int kPreStep = 4;  // points per prefix-count row (round 6: every row of round 5's store cost the sweeps one 128-byte line per lane)
 // u64 words of a prefix-count row that the team sweep of `cmax` category slots reads: TeamTile<CM>::NW of the instantiation launch_team
 // picks (8, 12 / 16 slots); 0: no instantiation reads rows (k_env_group's writer handles up to four words)
 inline int team_pre_words(int cmax) { return cmax <= 8 ? 1 : (cmax <= 16 ? 2 : 0); }

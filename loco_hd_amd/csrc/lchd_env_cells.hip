@@ -4,10 +4,6 @@
 
 #include "lchd_env_sort.h"
 
-#ifndef LCHD_ENV_FLAT
-#define LCHD_ENV_FLAT 4   // steps of 64 candidates whose record loads are issued together in the radius search
-#endif
-
 namespace lchd {
 // ------------------------------------------------------------------------------------------------
 // K1 (thresholded): one wavefront builds the sorted environment of one unique anchor.
@@ -24,12 +20,7 @@ __device__ unsigned long long g_env_stamps[8];
 #endif
 // VT: the category type of the LDS buffer and of the store (uint16_t: more than 255 categories, EnvStore::cat16; no O(n) bucket sort)
 template <int NT, bool TAGLIST, class VT = uint8_t>  // TAGLIST: the tag rule is a pair list (binary searches); otherwise one comparison, no branch
-#ifdef ENV_W8
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 64 ? 8 : 1, NT == 64 ? 8 : 8))) void k_env_cells(
-#else
-__global__ __launch_bounds__(NT) void k_env_cells(
-#endif
-const DevConfig* __restrict__ cfgp, EnvSides sides, double thr, int cap, DeviceStatus* st) {
+__global__ __launch_bounds__(NT) void k_env_cells(const DevConfig* __restrict__ cfgp, EnvSides sides, double thr, int cap, DeviceStatus* st) {
     // both structures in one launch: workgroups [0, sides.s[0].max_envs) build side A, the rest side B; the side's block of
     // kernel arguments is read with a wave-uniform index (scalar loads from the kernarg segment, no per-field selects)
     const int side = (int64_t)blockIdx.x >= sides.s[0].max_envs ? 1 : 0;
@@ -111,7 +102,7 @@ const DevConfig* __restrict__ cfgp, EnvSides sides, double thr, int cap, DeviceS
         const int total = __builtin_amdgcn_readlane((int)incl, 8);
         ESTAMP(0);
         const double2* __restrict__ rec2 = reinterpret_cast<const double2*>(g.rec);
-        constexpr int U = LCHD_ENV_FLAT;
+        constexpr int U = 4;  // steps of 64 candidates whose record loads are issued together in the radius search
         for (int c0 = 0; c0 < total; c0 += 64 * U) {
             int idx[U];
             double2 R0[U], R1[U];

@@ -21,10 +21,6 @@
 // instantiation or with k_env_cells.
 #include "lchd_kcommon.h"
 
-#ifndef LCHD_GROUP_U
-#define LCHD_GROUP_U 4   // search steps (64 candidates each) whose record loads are issued together
-#endif
-
 namespace lchd {
 
 #define LCHD_AS4 __attribute__((address_space(4)))  // the constant address space: kernel arguments, the configuration blob
@@ -87,18 +83,7 @@ __device__ __forceinline__ const LCHD_AS4 T* as_const(const T* p) {  // memory t
 // overflow list; the slot itself receives the anchor alone -- a valid one-point environment, so that the sweeps of this pass run
 // cleanly over the pairs of this anchor (the host scores those pairs again with larger slots: lchd_ctx_finish).
 // bound != 0: the anchor's candidate table overflowed before anything was counted; `bound` candidates are an upper bound of the environment.
-#ifndef LCHD_OVF_VARIANT
-#define LCHD_OVF_VARIANT 1
-#endif
-#if LCHD_OVF_VARIANT == 2
-__device__ __attribute__((noinline))
-#else
-__device__ __forceinline__
-#endif
-void env_group_overflow(const LCHD_AS4 EnvSide* p, DeviceStatus* st, int side, int e, uint32_t count, uint32_t bound, uint32_t apos32, int n_cat) {
-#if LCHD_OVF_VARIANT == 0
-    atomicOr(&st->flags, ST_ENV_OVERFLOW); atomicMax(&st->max_env, count); p->env.len[e] = 0; return;
-#endif
+__device__ __forceinline__ void env_group_overflow(const LCHD_AS4 EnvSide* p, DeviceStatus* st, int side, int e, uint32_t count, uint32_t bound, uint32_t apos32, int n_cat) {
     atomicOr(&st->flags, ST_ENV_OVERFLOW);
     atomicMax(&st->max_env, count);
     if (bound) atomicMax(&st->max_bound, bound);
@@ -117,20 +102,17 @@ void env_group_overflow(const LCHD_AS4 EnvSide* p, DeviceStatus* st, int side, i
     }
 }
 
-#ifndef LCHD_CAT0_STORE
-#define LCHD_CAT0_STORE 1
-#endif
-#ifndef LCHD_GROUP_WPB
-#define LCHD_GROUP_WPB 1   // independent wavefronts per workgroup (each with its own LDS block; no workgroup barrier anywhere)
-#endif
+// One wavefront per workgroup: no workgroup barrier anywhere.
 template <bool TAGLIST, int kGCap, int WAVES>
-__global__ __launch_bounds__(64 * LCHD_GROUP_WPB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_env_group(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_env_group(
     const DevConfig* __restrict__ cfgp, EnvSides sides, double thr, int apw, int nwa, DeviceStatus* st) {
     static_assert(kGCap % 64 == 0 && kGCap <= kEnvGroupCap, "whole wavefronts; environment slots hold kEnvGroupCap points");
-    __shared__ __attribute__((aligned(16))) GroupLds<kGCap> lds_all[LCHD_GROUP_WPB];
+    // (The wave index is always 0, but the compiler does not derive that from the launch bounds: folding it away by hand -- no array of
+    // one, wid = blockIdx.x -- changes the generated code (the kernel's scalar spills), so that is a change of its own.)
+    __shared__ __attribute__((aligned(16))) GroupLds<kGCap> lds_all[1];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     GroupLds<kGCap>& lds = lds_all[wave];
-    const int wid = (int)blockIdx.x * LCHD_GROUP_WPB + wave;  // nwa wavefronts build side A, the rest side B
+    const int wid = (int)blockIdx.x + wave;  // nwa wavefronts build side A, the rest side B
     const int side = wid >= nwa ? 1 : 0;
     const int lane = threadIdx.x & 63;
 #ifdef LCHD_SWEEP_STAMPS
@@ -263,7 +245,7 @@ __global__ __launch_bounds__(64 * LCHD_GROUP_WPB) __attribute__((amdgpu_waves_pe
                     else return (atag == t_other) == accept_same;
                 };
                 int count = 0;
-                constexpr int U = LCHD_GROUP_U;
+                constexpr int U = 4;  // search steps (64 candidates each) whose record loads are issued together
                 static_assert(8 * U <= 32, "table padding covers one round of 8 U groups");
                 for (int g0 = 0; g0 < NG; g0 += 8 * U) {
                     uint32_t off[U], ent[U];
@@ -530,10 +512,8 @@ __global__ __launch_bounds__(64 * LCHD_GROUP_WPB) __attribute__((amdgpu_waves_pe
             }
             if (lf < G) {
                 p->env.len[e_first + lf] = (int32_t)lds.gcount[lf];
-#if LCHD_CAT0_STORE
                 const uint32_t c0 = (uint32_t)lds.val[lds.gstart[lf]] & 0xFFu;  // (the sorted first point's category, as it was stored)
                 if (p->env.cat0) p->env.cat0[e_first + lf] = (int)c0 < n_cat ? (uint8_t)c0 : (uint8_t)0;
-#endif
             }
         }
         wave_sync_lds();  // (gstart / gcount / key are rewritten by the next group)
@@ -554,14 +534,13 @@ bool launch_env_group(hipStream_t s, const DevConfig* cfg, bool tag_list, bool s
     sides.s[0] = a;
     sides.s[1] = b;
     const int64_t nwa = (a.max_envs + anchors_per_wave - 1) / anchors_per_wave, nwb = (b.max_envs + anchors_per_wave - 1) / anchors_per_wave;
-    constexpr int WPB = LCHD_GROUP_WPB;
-    const dim3 grid((unsigned)((nwa + nwb + WPB - 1) / WPB));
+    const dim3 grid((unsigned)(nwa + nwb));
     if (small_cap) {
-        if (tag_list) k_env_group<true, kEnvGroupCapSmall, 6><<<grid, 64 * WPB, 0, s>>>(cfg, sides, thr, anchors_per_wave, (int)nwa, st);
-        else k_env_group<false, kEnvGroupCapSmall, 6><<<grid, 64 * WPB, 0, s>>>(cfg, sides, thr, anchors_per_wave, (int)nwa, st);
+        if (tag_list) k_env_group<true, kEnvGroupCapSmall, 6><<<grid, 64, 0, s>>>(cfg, sides, thr, anchors_per_wave, (int)nwa, st);
+        else k_env_group<false, kEnvGroupCapSmall, 6><<<grid, 64, 0, s>>>(cfg, sides, thr, anchors_per_wave, (int)nwa, st);
     } else {
-        if (tag_list) k_env_group<true, kEnvGroupCap, 5><<<grid, 64 * WPB, 0, s>>>(cfg, sides, thr, anchors_per_wave, (int)nwa, st);
-        else k_env_group<false, kEnvGroupCap, 5><<<grid, 64 * WPB, 0, s>>>(cfg, sides, thr, anchors_per_wave, (int)nwa, st);
+        if (tag_list) k_env_group<true, kEnvGroupCap, 5><<<grid, 64, 0, s>>>(cfg, sides, thr, anchors_per_wave, (int)nwa, st);
+        else k_env_group<false, kEnvGroupCap, 5><<<grid, 64, 0, s>>>(cfg, sides, thr, anchors_per_wave, (int)nwa, st);
     }
     return true;
 }

@@ -673,9 +673,6 @@ bool launch_env_rows2(hipStream_t s, const DevConfig* cfg, const RowSide& a, con
     else if (n2 <= 1024) k_env_rows2<64, 16, 1><<<grid, 64, lds, s>>>(cfg, sides, n2, st);
     else if (n2 <= 4096) k_env_rows2<256, 16, 1><<<grid, 256, lds, s>>>(cfg, sides, n2, st);
     else if (n2 <= 8192) k_env_rows2<1024, 8, 1><<<grid, 1024, lds, s>>>(cfg, sides, n2, st);
-#ifdef LCHD_ROWS_NT512
-    else if (longest <= 10240) k_env_rows2<512, 20, 1><<<grid, 512, lds, s>>>(cfg, sides, n2, st);
-#endif
     else if (longest <= 10240) k_env_rows2<1024, 10, 1><<<grid, 1024, lds, s>>>(cfg, sides, n2, st);
     else k_env_rows2<1024, 16, 1><<<grid, 1024, lds, s>>>(cfg, sides, n2, st);
     return true;
@@ -729,9 +726,6 @@ void init_env_rows_kernels() {
     raise(reinterpret_cast<const void*>(&k_env_rows<1024, false, uint16_t>), 8192 * 10 + 16 + (kRowBucketsSmall + 1) * 4);
     raise(reinterpret_cast<const void*>(&k_env_rows2<1024, 16, 1>), 16384 * 9 + 16 + (kRowBucketsSmall + 1) * 4);
     raise(reinterpret_cast<const void*>(&k_env_rows2<1024, 10, 1>), 16384 * 9 + 16 + (kRowBucketsSmall + 1) * 4);
-#ifdef LCHD_ROWS_NT512
-    raise(reinterpret_cast<const void*>(&k_env_rows2<512, 20, 1>), 16384 * 9 + 16 + (kRowBucketsSmall + 1) * 4);
-#endif
     raise(reinterpret_cast<const void*>(&k_env_rows2<1024, 12, 2>), (int)kRowSegLds);
     raise(reinterpret_cast<const void*>(&k_env_rows2<1024, 8, 1>), 8192 * 9 + 16 + (kRowBucketsSmall + 1) * 4);
     (void)hipGetLastError();

@@ -511,9 +511,7 @@ static bool fits_struct_path(const PrepSide& P, const Tuning& t, CloudView& cs) 
            (int64_t)cs.n_struct * cs.struct_size == P.c.n && (cs.n_struct >= 8 || cs.struct_size <= 4096);
 }
 
-#ifndef LCHD_STRUCT_NT
-#define LCHD_STRUCT_NT 512   // (measured, C4 cell lists: 128 0.506, 256 0.466, 512 0.445 ms per step) threads of the per-structure cell-list workgroups of a batch of more than 16 structures
-#endif
+constexpr int kStructNT = 512;   // (measured, C4 cell lists: 128 0.506, 256 0.466, 512 0.445 ms per step) threads of the per-structure cell-list workgroups of a batch of more than 16 structures
 int launch_prologue(hipStream_t s, const Tuning& t, const int64_t* anchors, int64_t n_pairs, const PrepSide& a_in, const PrepSide& b_in,
                     void* zero_base, size_t zero_bytes, DeviceStatus* st, bool same) {
     PrepSide a = a_in, b = b_in;
@@ -550,7 +548,7 @@ int launch_prologue(hipStream_t s, const Tuning& t, const int64_t* anchors, int6
             k_cells_struct2<1024><<<nsa + nsb + nz, 1024, lds, s>>>(sa_, sb_, nsa, nsb, zb, zw);
         } else {
             const int nz = fold_zero ? (int)std::min<int64_t>(1024, (zw + 1023) / 1024) : 0;
-            k_cells_struct2<LCHD_STRUCT_NT><<<nsa + nsb + nz, LCHD_STRUCT_NT, lds, s>>>(sa_, sb_, nsa, nsb, zb, zw);
+            k_cells_struct2<kStructNT><<<nsa + nsb + nz, kStructNT, lds, s>>>(sa_, sb_, nsa, nsb, zb, zw);
         }
         ++ops;
     }
@@ -583,7 +581,7 @@ void init_prologue_kernels() {
     auto raise = [](const void* fn, int bytes) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
     raise(reinterpret_cast<const void*>(&k_prologue_fused), kStructCellsMax * 4 + kStructAtomsMax * 4);  // + ~3 KB static: above 64 KB in total
     raise(reinterpret_cast<const void*>(&k_cells_struct2<1024>), kStructCellsMax * 4 + kStructAtomsMax * 4);
-    raise(reinterpret_cast<const void*>(&k_cells_struct2<LCHD_STRUCT_NT>), kStructCellsMax * 4 + kStructAtomsMax * 4);
+    raise(reinterpret_cast<const void*>(&k_cells_struct2<kStructNT>), kStructCellsMax * 4 + kStructAtomsMax * 4);
     (void)hipGetLastError();
 }
 static_assert(kPrepScanAtoms == 1 << 18, "k_prep_scatter: chunk of atom i = i >> 18");

@@ -99,9 +99,10 @@ __device__ unsigned long long g_sweep_stamps[8];
 // counts are 8-bit fields, eight per word instead of four -- half the words to scan across the wavefront, to unpack at every
 // tile and to keep per lane, and 3 KB less LDS per wavefront, which lets the many-slot variants run at 3 waves per SIMD
 // instead of 2.  Pairs with a larger environment are left to the INDIRECT instantiation of the 16-bit kernel.
-#ifndef LCHD_C8S_WAVES
-#define LCHD_C8S_WAVES 4   // waves per SIMD the 8-bit-count sweep with at most 12 category slots is compiled for
-#endif
+constexpr int kC8SWaves = 4;     // waves per SIMD the 8-bit-count sweep with at most 12 category slots is compiled for
+constexpr int kC8Waves = 3;      // waves per SIMD the 8-bit-count sweep with more than 16 category slots is compiled for
+constexpr int kSweepW3Max = 16;  // largest category-slot count that is compiled for 3 waves per SIMD (above: 2)
+constexpr int kGenW3Max = 0;     // generic-distance sweeps (MODE_GEN) with at most this many category slots are compiled for 3 waves/SIMD
 // Waves per SIMD an instantiation is COMPILED for (the register budget: 512 / waves).  The default configurations (Hellinger-2, unit
 // weights, CDF keys, LDS tables) are register-bound: 4 up to 12 slots, 3 up to 16, 2 beyond.  The others are bound by their LDS
 // footprint -- 576-event tiles without the LDS tables (deterministic mode, environments beyond 512 points), the weighted sweeps'
@@ -110,31 +111,32 @@ __device__ unsigned long long g_sweep_stamps[8];
 // allocator may use the registers that occupancy leaves.
 template <int CMAX, int MODE, int FMODE, bool LDSTAB, bool CNT8>
 constexpr int sweep_waves_per_simd() {
-    if (MODE == MODE_GEN) return CMAX <= LCHD_GEN_W3MAX ? 3 : 2;
+    if (MODE == MODE_GEN) return CMAX <= kGenW3Max ? 3 : 2;
     if (CMAX <= 12) {
-        if (CNT8) return LCHD_C8S_WAVES;
+        if (CNT8) return kC8SWaves;
         if (!LDSTAB) return ((CMAX > 8 && (FMODE == 2 || MODE == MODE_H2W)) || (MODE == MODE_H2W && FMODE == 2)) ? 2 : 3;
         return MODE == MODE_H2W ? 3 : 4;
     }
-    if (CMAX <= LCHD_SWEEP_W3MAX) return (MODE == MODE_H2W && LDSTAB) ? 2 : 3;
-    return CNT8 ? LCHD_C8_WAVES : 2;
+    if (CMAX <= kSweepW3Max) return (MODE == MODE_H2W && LDSTAB) ? 2 : 3;
+    return CNT8 ? kC8Waves : 2;
 }
+// Merged events per lane per tile (kSweepEPL, lchd_device.h: 16-bit counts, LDS tables, <= 16 category slots; the generic distances) ...
+constexpr int kEplBig = 8;    // ... of the many-slot Hellinger-2 sweep (k_sweep<20..32>): tiles of 512
+constexpr int kEplDense = 9;  // ... of the sweeps without LDS tables (environments beyond 512 points: dense rows, thousands of events per pair)
+constexpr int kEplWGen = 7;   // ... of the sweeps with category weights and of the generic distances, CDF-keyed environments (measured on C2a: weights 2.86 -> 2.54 ms, KS 4.62 -> 4.29 ms; the plain 16-bit Hellinger sweep and the sweeps that evaluate the CDF themselves are faster with 6: their LDS tables + tiles of 448 leave 3 workgroups per CU)
+constexpr int kEplC8 = 8;     // ... of the 8-bit-count sweep: tiles of 512 -- two environments of <= 255 points never merge to more, so every pair is ONE tile (a list is staged whole: 256 entries; C5: 448-event tiles + tile-sized staging 3.08 ms, whole-list staging 2.88 ms, 512-event tiles 2.80 ms)
+constexpr int kEplC8S = 8;    // ... of the 8-bit-count sweep with at most 16 category slots: see kEplC8 (C2a: 343 events per pair on average; tiles of 384: 1.77 ms, 448: 1.61 ms, 512 with whole-list staging: 1.585 ms)
+constexpr int kPartTab = 1024;  // entries of the partial sqrt table of the Hellinger-2 sweeps without full LDS tables
 template <int CMAX, int MODE, int FMODE, bool LDSTAB, bool INDIRECT = false, bool INLINE_META = false, bool CNT8 = false>
-#ifndef LCHD_DENSE_PARTTAB
-#define LCHD_DENSE_PARTTAB 1024   // entries of the partial sqrt table of the sweeps without full LDS tables (0: none)
-#endif
-#ifndef LCHD_EXACT_H2_LOOP
-#define LCHD_EXACT_H2_LOOP 1
-#endif
 __global__ __launch_bounds__(64 * kSweepWaves, (sweep_waves_per_simd<CMAX, MODE, FMODE, LDSTAB, CNT8>())) void k_sweep(SweepArgs args) {
     static_assert(!(INDIRECT && INLINE_META), "the indirect instantiation reads the records of k_pair_meta");
     static_assert(!CNT8 || (MODE == MODE_H2U && FMODE == F_KEY && LDSTAB && !INDIRECT && !INLINE_META), "8-bit counts: default configuration only");
     // Merged events per lane per tile.  The per-tile prologue (staging, merge path, scan of the packed counts, state reload)
     // costs about as many instructions as the events of a 384-event tile themselves, and it grows with the category slots:
-    // the variants with many slots (25 categories at 0.05 atoms/A^3: ~416 events per pair) take tiles of 64 x LCHD_EPL_BIG so
+    // the variants with many slots (25 categories at 0.05 atoms/A^3: ~416 events per pair) take tiles of 64 x kEplBig so
     // that such a pair is ONE tile instead of a full one plus a nearly empty one.
     constexpr bool H2_ = (MODE != MODE_GEN);
-    constexpr int EPL = (CNT8 && CMAX > 16) ? LCHD_EPL_C8 : (CNT8 && CMAX <= 16) ? LCHD_EPL_C8S : ((H2_ && LDSTAB && CMAX > 16) ? LCHD_EPL_BIG : ((H2_ && !LDSTAB) ? LCHD_EPL_DENSE : ((MODE != MODE_H2U && FMODE == F_KEY) ? LCHD_EPL_WGEN : kSweepEPL))),
+    constexpr int EPL = (CNT8 && CMAX > 16) ? kEplC8 : (CNT8 && CMAX <= 16) ? kEplC8S : ((H2_ && LDSTAB && CMAX > 16) ? kEplBig : ((H2_ && !LDSTAB) ? kEplDense : ((MODE != MODE_H2U && FMODE == F_KEY) ? kEplWGen : kSweepEPL))),
                   TILE = 64 * EPL, WPB = kSweepWaves;
     // entries staged per list and tile: a tile's worth -- but the pairs of the 8-bit-count sweep have at most 254 non-anchor
     // points per environment, so 256 entries hold a whole list (4 KB of keys per wave instead of 7) and a tile of 512 events
@@ -149,10 +151,9 @@ __global__ __launch_bounds__(64 * kSweepWaves, (sweep_waves_per_simd<CMAX, MODE,
     constexpr int NH = (CMAX + 15) / 16;  // u64 words of 4-bit histogram fields per side
     constexpr bool H2 = (MODE != MODE_GEN);
     constexpr int NV = H2 ? 1 : CMAX;     // only the generic path keeps per-category values in registers
-    constexpr int NT = LDSTAB ? (CNT8 ? 256 + 8 : kSqrtTab + 8) : 1;  // sqrt(k), 1/sqrt(k) for k <= 512 (255) in LDS; otherwise read from the global tables
+    constexpr int NT = LDSTAB ? (CNT8 ? 256 + 8 : kSqrtTab + 8) : 1;  // sqrt(k), 1/sqrt(k) for k <= 512 (255) in LDS; otherwise computed (sqrt_cnt below)
     __shared__ double t_sqrt[NT], t_rsqrt[NT];
-    constexpr bool PARTTAB = !LDSTAB && H2_ && (LCHD_DENSE_PARTTAB != 0);
-    constexpr int kPartTab = LCHD_DENSE_PARTTAB > 0 ? LCHD_DENSE_PARTTAB : 1;
+    constexpr bool PARTTAB = !LDSTAB && H2_;
     __shared__ double t_part[PARTTAB ? kPartTab : 1];
     __shared__ double w_s[32], sw_s[32];
     // MODE_GEN, Hellinger with a general exponent, environments of at most kSqrtTab points: k^(1/e) and k^(-1/e) for k <= 512 in
@@ -162,15 +163,11 @@ __global__ __launch_bounds__(64 * kSweepWaves, (sweep_waves_per_simd<CMAX, MODE,
     __shared__ uint64_t sA_[WPB][LT], sB_[WPB][LT];
     __shared__ uint8_t cA_[WPB][LT], cB_[WPB][LT];
     // per-lane category counts of the event loop: [side][word][lane] u64 of four 16-bit fields (a lane only ever touches its own)
-    // (13 and more category slots only: up to 12 the register form runs at 4 waves/SIMD, which the extra 3 KB of LDS per wave
-    // would cut to 3 -- measured 2-6 % slower -- while from 13 on the LDS form is 4-13 % faster at unchanged occupancy)
-#ifndef LCHD_C8_REGCNT
-#define LCHD_C8_REGCNT 0
-#endif
-#ifndef LCHD_C8_LDSCNT_ALL
-#define LCHD_C8_LDSCNT_ALL 1   // the 8-bit-count sweeps keep their per-lane counts in LDS for every slot count (<= 12 slots: their 2 KB per wave do not cost a wave of occupancy, and the byte read-modify-write replaces the word select + 4-bit counter chains: C2a sweep 1.577 -> 1.523 ms)
-#endif
-    constexpr bool LDSCNT = H2 && LDSTAB && (NW > 3 || (CNT8 && LCHD_C8_LDSCNT_ALL)) && (LCHD_LDS_COUNTS != 0) && !(CNT8 && LCHD_C8_REGCNT);  // (16-bit fields: from 13 category slots on)
+    // (16-bit fields: 13 and more category slots only: up to 12 the register form runs at 4 waves/SIMD, which the extra 3 KB of LDS
+    // per wave would cut to 3 -- measured 2-6 % slower -- while from 13 on the LDS form is 4-13 % faster at unchanged occupancy;
+    // the 8-bit-count sweeps keep them there for every slot count: <= 12 slots: their 2 KB per wave do not cost a wave of occupancy,
+    // and the byte read-modify-write replaces the word select + 4-bit counter chains: C2a sweep 1.577 -> 1.523 ms)
+    constexpr bool LDSCNT = H2 && LDSTAB && (NW > 3 || CNT8);
     __shared__ uint64_t lc_[LDSCNT ? WPB : 1][LDSCNT ? 2 * NW * 64 : 1];
     // When pairs with at most kDuoTile merged events are the majority of a launch, k_sweep_duo sweeps them two per wavefront
     // and the INDIRECT instantiation of this kernel picks the remaining ones out of the pair records; otherwise the plain
@@ -216,7 +213,6 @@ __global__ __launch_bounds__(64 * kSweepWaves, (sweep_waves_per_simd<CMAX, MODE,
     unsigned char* lcl = reinterpret_cast<unsigned char*>(lc_[LDSCNT ? wv : 0]) + lane * 8;  // this lane's slot of word 0, side A
     constexpr int kLcSide = NW * 512;  // bytes from a side-A field to the same field of side B
 
-#if LCHD_BIG_SQRT_COMPUTE
     // environments beyond the LDS tables: sqrt(count) is computed (rsq seed + Goldschmidt, <= 1 ulp from the table value)
     // instead of being fetched from the 65536-entry global tables -- four dependent L2 round trips per event otherwise
     // (dense rows: counts below kPartTab -- per-category counts of a 10^4-point row with ten categories stay there until the row's
@@ -236,10 +232,6 @@ __global__ __launch_bounds__(64 * kSweepWaves, (sweep_waves_per_simd<CMAX, MODE,
             return y;
         }
     };
-#else
-    auto sqrt_cnt = [&](int cnt) -> double { if constexpr (LDSTAB) return t_sqrt[cnt]; else return g_sqrt[cnt]; };
-    auto rsqrt_cnt = [&](int cnt) -> double { if constexpr (LDSTAB) return t_rsqrt[cnt]; else return g_rsqrt[cnt]; };
-#endif
     // sqrt of the weighted count of category c (c may be dynamic)
     auto root_of = [&](int c, int cnt) -> double {
         if constexpr (MODE == MODE_H2W) return sqrt_cnt(cnt) * sw_s[c & 31];
@@ -447,7 +439,7 @@ __global__ __launch_bounds__(64 * kSweepWaves, (sweep_waves_per_simd<CMAX, MODE,
         // exact squared Hellinger distance in the literal difference-of-roots form (statistical_distances.rs:4-10)
         auto exact_h2 = [&]() -> double {
             double acc2 = 0.0;
-            if constexpr (LDSCNT && CMAX > 16 && (LCHD_EXACT_H2_LOOP != 0)) {
+            if constexpr (LDSCNT && CMAX > 16) {
                 // many slots, counts in LDS: a runtime loop over the count words (one copy of the eight-field body): the rarely
                 // taken path no longer sizes the kernel's register allocation
 #pragma unroll 1
@@ -628,7 +620,6 @@ __global__ __launch_bounds__(64 * kSweepWaves, (sweep_waves_per_simd<CMAX, MODE,
             uint64_t hA[NH], hB[NH];
 #pragma unroll
             for (int k = 0; k < NH; ++k) hA[k] = hB[k] = 0;
-#if LCHD_PASS1_FUSED
             if constexpr (NH == 1) {
                 // one fixed-trip loop over the chunk's (at most EPL) points, A's run first, then B's: the two data-dependent
                 // loops it replaces each ran for the longest run of any lane.  hT counts every point, hA only A's.
@@ -647,19 +638,17 @@ __global__ __launch_bounds__(64 * kSweepWaves, (sweep_waves_per_simd<CMAX, MODE,
                     }
                 }
                 hB[0] = hT - hA[0];
-            } else
-#endif
-            {
-            for (int i = i0; i < i1; ++i) {
-                const int ct = cA[i];
+            } else {
+                for (int i = i0; i < i1; ++i) {
+                    const int ct = cA[i];
 #pragma unroll
-                for (int k = 0; k < NH; ++k) hA[k] += ((ct >> 4) == k) ? (1ull << ((ct & 15) * 4)) : 0ull;
-            }
-            for (int j = j0; j < j1; ++j) {
-                const int ct = cB[j];
+                    for (int k = 0; k < NH; ++k) hA[k] += ((ct >> 4) == k) ? (1ull << ((ct & 15) * 4)) : 0ull;
+                }
+                for (int j = j0; j < j1; ++j) {
+                    const int ct = cB[j];
 #pragma unroll
-                for (int k = 0; k < NH; ++k) hB[k] += ((ct >> 4) == k) ? (1ull << ((ct & 15) * 4)) : 0ull;
-            }
+                    for (int k = 0; k < NH; ++k) hB[k] += ((ct >> 4) == k) ? (1ull << ((ct & 15) * 4)) : 0ull;
+                }
             }
             STAMP(3);
             // widen to 16-bit fields and exclusive-scan across the wavefront
@@ -686,60 +675,28 @@ __global__ __launch_bounds__(64 * kSweepWaves, (sweep_waves_per_simd<CMAX, MODE,
             }
             STAMP(5);
 
-            // pass 2: sequential sweep of this lane's events.  Branch-free: both list heads stay in registers and the one
-            // that was consumed is refilled with a single (address-selected) LDS read.  The packed counts exA/exB stay
-            // fixed at their chunk-start values; what the chunk itself adds (<= 6 per category) is kept in 4-bit fields.
+            // pass 2: sequential sweep of this lane's events.  Branch-free: both list heads stay in registers and both are
+            // re-read from LDS after every event (the single address-selected refill this replaced: DESIGN.md section 4).  The packed
+            // counts exA/exB stay fixed at their chunk-start values; what the chunk itself adds (<= 6 per category) is kept in 4-bit fields.
             int i = i0, j = j0;
-#if LCHD_HEADS_REREAD
             uint64_t ka = sA[i], kb = sB[j];  // both heads are re-read after every event; run ends are tested on the indices
-#if LCHD_CAT_HEADS
             int cta = cA[i], ctb = cB[j];     // ... and so are their categories: the event's category is a select, not an LDS round trip behind takeA
-#endif
-#else
-            uint64_t ka = (i < i1) ? sA[i] : kPadKey, kb = (j < j1) ? sB[j] : kPadKey;
-#endif
 #pragma unroll
             for (int k = 0; k < NH; ++k) dA[k] = dB[k] = 0;
             double Fp = 0.0, Hp = 0.0, firstF = 0.0, local = 0.0;
             for (int e = 0; e < epl; ++e) {
                 if (d0 + e < d1) {
-#if LCHD_HEADS_REREAD
                     // A-first on ties; an exhausted run cannot be taken.  Two LDS reads per event instead of one, but none of
                     // the selects that steer a single refill into the right head register (the kernel is VALU-issue bound).
                     const bool takeA = (i < i1) & ((j >= j1) | (ka <= kb));
                     const uint64_t key = takeA ? ka : kb;
-#if LCHD_CAT_HEADS
                     const int ct = takeA ? cta : ctb;
-#else
-                    const int ct = (takeA ? cA : cB)[takeA ? i : j];
-#endif
                     i += takeA ? 1 : 0;
                     j += takeA ? 0 : 1;
                     ka = sA[i];  // (one past the run's end at most: inside the tile buffers, never used)
                     kb = sB[j];
-#if LCHD_CAT_HEADS
                     cta = cA[i];
                     ctb = cB[j];
-#endif
-#else
-                    const bool takeA = (ka <= kb);  // an exhausted list shows the pad key (> every real key)
-                    const uint64_t key = takeA ? ka : kb;
-#if LCHD_BRANCHFREE_HEADS
-                    const int ct = (takeA ? cA : cB)[takeA ? i : j];
-                    i += takeA ? 1 : 0;
-                    j += takeA ? 0 : 1;
-                    {
-                        const int nidx = takeA ? i : j, nend = takeA ? i1 : j1;
-                        const uint64_t nk = (takeA ? sA : sB)[min(nidx, LT - 1)];
-                        const uint64_t nh = nidx < nend ? nk : kPadKey;
-                        ka = takeA ? nh : ka;
-                        kb = takeA ? kb : nh;
-                    }
-#else
-                    const int ct = takeA ? cA[i] : cB[j];
-                    if (takeA) { ++i; ka = (i < i1) ? sA[i] : kPadKey; } else { ++j; kb = (j < j1) ? sB[j] : kPadKey; }
-#endif
-#endif
                     const double F = cdf_of_key(key);
                     if (e == 0) firstF = F; else local += (F - Fp) * Hp;
                     totA += takeA ? 1 : 0;

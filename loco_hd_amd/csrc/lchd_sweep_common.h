@@ -1,5 +1,5 @@
 // lchd_sweep_common.h -- what the sweep kernel families share (lchd_sweep.hip, lchd_sweep_team.hip, lchd_sweep_wide.hip, the record pass
-// and the launch logic in lchd_kernels.hip): distance / key modes, tuning macros, the pass's small-pair rule, the status hand-over
+// and the launch logic in lchd_kernels.hip): distance / key modes, tuning constants, the pass's small-pair rule, the status hand-over
 // without a fence, the generic statistical distances and the per-pair weight-function registers.
 #pragma once
 #include <algorithm>
@@ -35,54 +35,6 @@ namespace lchd {
 enum { MODE_H2U = 0, MODE_H2W = 1, MODE_GEN = 2 };
 // where F(t) comes from: the environment keys already are F values / inline CDFs only / any CDF
 enum { F_KEY = 0, F_FAST = 1, F_ANY = 2 };
-#ifndef LCHD_PASS1_FUSED
-#define LCHD_PASS1_FUSED 1  // k_sweep: the chunk histogram is one fixed-trip loop over the lane's points
-#endif
-#ifndef LCHD_LDS_COUNTS
-#define LCHD_LDS_COUNTS 1   // k_sweep (Hellinger-2, LDS tables, > 12 category slots): per-lane category counts live in LDS during the event loop
-#endif
-#ifndef LCHD_HEADS_REREAD
-#define LCHD_HEADS_REREAD 1   // k_sweep: both list heads are re-read from LDS after every event
-#endif
-#ifndef LCHD_CAT_HEADS
-#define LCHD_CAT_HEADS 1      // k_sweep / k_sweep_duo: the categories of both list heads are read together with their keys
-#endif
-#ifndef LCHD_BRANCHFREE_HEADS
-#define LCHD_BRANCHFREE_HEADS 1
-#endif
-#ifndef LCHD_SWEEP_WAVES
-#define LCHD_SWEEP_WAVES 4
-#endif
-#ifndef LCHD_BIG_SQRT_COMPUTE
-#define LCHD_BIG_SQRT_COMPUTE 1
-#endif
-#ifndef LCHD_SWEEP_W3MAX
-#define LCHD_SWEEP_W3MAX 16   // largest category-slot count that is compiled for 3 waves per SIMD (above: 2)
-#endif
-#ifndef LCHD_SWEEP_MINW
-#define LCHD_SWEEP_MINW 2
-#endif
-#ifndef LCHD_GEN_W3MAX
-#define LCHD_GEN_W3MAX 0   // generic-distance sweeps (MODE_GEN) with at most this many category slots are compiled for 3 waves/SIMD
-#endif
-#ifndef LCHD_EPL_WGEN
-#define LCHD_EPL_WGEN 7  // ... of the sweeps with category weights and of the generic distances, CDF-keyed environments (measured on C2a: weights 2.86 -> 2.54 ms, KS 4.62 -> 4.29 ms; the plain 16-bit Hellinger sweep and the sweeps that evaluate the CDF themselves are faster with 6: their LDS tables + tiles of 448 leave 3 workgroups per CU)
-#endif
-#ifndef LCHD_EPL_C8S
-#define LCHD_EPL_C8S 8   // ... of the 8-bit-count sweep with at most 16 category slots: see LCHD_EPL_C8 (C2a: 343 events per pair on average; tiles of 384: 1.77 ms, 448: 1.61 ms, 512 with whole-list staging: 1.585 ms)
-#endif
-#ifndef LCHD_EPL_C8
-#define LCHD_EPL_C8 8    // ... of the 8-bit-count sweep: tiles of 512 -- two environments of <= 255 points never merge to more, so every pair is ONE tile (a list is staged whole: 256 entries; C5: 448-event tiles + tile-sized staging 3.08 ms, whole-list staging 2.88 ms, 512-event tiles 2.80 ms)
-#endif
-#ifndef LCHD_C8_WAVES
-#define LCHD_C8_WAVES 3  // waves per SIMD the 8-bit-count sweep with more than 16 category slots is compiled for
-#endif
-#ifndef LCHD_EPL_DENSE
-#define LCHD_EPL_DENSE 9   // ... of the sweeps without LDS tables (environments beyond 512 points: dense rows, thousands of events per pair)
-#endif
-#ifndef LCHD_EPL_BIG
-#define LCHD_EPL_BIG 8   // merged events per lane per tile of the many-slot Hellinger-2 sweep (k_sweep<20..32>): tiles of 512
-#endif
 constexpr int kDuoTileFwd = kDuoTile;  // (lchd_team_tile.h)
 // The small rule in force in this pass, or -1 (the plain sweep takes every pair).  With a hint the host launched exactly the
 // kernels that have to run (forced); without one every candidate kernel is launched and all of them decide here, from the
@@ -95,12 +47,9 @@ __device__ __forceinline__ int rule_in_force(const SweepArgs& args) {
     if (args.second_rule && 2 * args.st->n_c8 >= P) return args.second_rule;
     return -1;
 }
-#ifndef LCHD_INLINE_META_PAIRS
-#define LCHD_INLINE_META_PAIRS 4096
-#endif
-constexpr int64_t kInlineMetaPairs = LCHD_INLINE_META_PAIRS;   // calls of at most this many pairs: the sweep works out the pair records itself (one launch)
+constexpr int64_t kInlineMetaPairs = 4096;   // calls of at most this many pairs: the sweep works out the pair records itself (one launch)
 constexpr int kSqrtTab = 512;  // LDSTAB kernels: environments of at most 512 points, sqrt tables entirely in LDS
-constexpr int kSweepWaves = LCHD_SWEEP_WAVES;  // anchor pairs (wavefronts) per workgroup
+constexpr int kSweepWaves = 4;  // anchor pairs (wavefronts) per workgroup
 
 // A sweep kernel reports a (rare) condition: plain store of 1 into the condition's word of the host-mapped mirror (every
 // writer stores the same value; no atomics on host memory, no device-to-host copy afterwards).
@@ -276,10 +225,7 @@ static __device__ __noinline__ double sd_generic(int kind, double p0, double p1,
     return sd_eval<0>(kind, p0, p1, [&](int c) { return p[c]; }, [&](int c) { return q[c]; }, C);
 }
 
-#define LCHD_DUO_TL 16   // lanes per pair of k_sweep_duo's <= 240-event form: four pairs per wavefront (round 1 / 2: 32 lanes, two pairs, 224 events)
-#ifndef LCHD_COMPANION_GRID
-#define LCHD_COMPANION_GRID 2048u   // (measured: 1024 -> 2048: C2a 19.4 -> 16.6 us, C4 47.3 -> 37.3 us per pass; 4096: no further gain) workgroups of the INDIRECT companion sweep (it walks every pair record and sweeps the few the team kernel left)
-#endif
+constexpr int kDuoTL = 16;   // lanes per pair of k_sweep_duo's <= 240-event form: four pairs per wavefront (round 1 / 2: 32 lanes, two pairs, 224 events)
 
 // ---- launchers of the kernel families (one translation unit each) ---------------------------------------------------
 // lchd_sweep.hip: one pair per wavefront

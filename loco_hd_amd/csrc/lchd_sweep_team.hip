@@ -15,9 +15,7 @@ namespace lchd {
 // host launches this kernel AND k_sweep; k_pair_meta counts the qualifying pairs (DeviceStatus::n_small): when they are
 // the majority this kernel sweeps them and k_sweep only the rest, otherwise this kernel returns at once.
 // ------------------------------------------------------------------------------------------------
-#ifndef LCHD_TEAM_BIG_WAVES
-#define LCHD_TEAM_BIG_WAVES 3   // waves per SIMD k_sweep_duo is compiled for with more than 16 category slots
-#endif
+constexpr int kTeamBigWaves = 3;   // waves per SIMD k_sweep_duo is compiled for with more than 16 category slots, and with category weights and 9 .. 16 (their counts in LDS bytes, TeamTile::LCNT); 4 otherwise
 // (the name is historic: round 1 swept TWO pairs per wavefront; with TL = 16 a wavefront sweeps FOUR -- the per-tile prologue, which
 // is two thirds of this kernel's instructions at ~150 events per pair, is shared by twice as many pairs, the event loop costs the
 // same per pair: C3 459 -> see DESIGN section 4)
@@ -30,14 +28,8 @@ namespace lchd {
 // KSM: the Kolmogorov-Smirnov distance max_c |a_c / N_a - b_c / N_b| (statistical_distances.rs:12-21) with unit weights instead of
 // Hellinger-2: every event needs all categories, but as INTEGERS -- max_c |a_c N_b - b_c N_a| over the 8-bit count fields (two 24-bit
 // multiplies, one v_sad_u32, one max per category), scaled once by 1 / (N_a N_b) from the reciprocal-root table; no square root.
-#ifndef LCHD_STAGE_PAIRS
-#define LCHD_STAGE_PAIRS 1   // the team sweeps stage two buffer entries per lane and round (0: one)
-#endif
-#ifndef LCHD_WGT_W3
-#define LCHD_WGT_W3 0       // 1: ... are compiled for 3 waves per SIMD (170 registers: no spills)
-#endif
-template <int CMAX, int TL = LCHD_DUO_TL, int TILE_ = kDuoTile, bool WGT = false, bool KSM = false, bool PRE = false>
-__global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8 && (LCHD_WGT_LDSCNT || LCHD_WGT_W3))) ? 4 : LCHD_TEAM_BIG_WAVES)) void k_sweep_duo(SweepArgs args) {
+template <int CMAX, int TL = kDuoTL, int TILE_ = kDuoTile, bool WGT = false, bool KSM = false, bool PRE = false>
+__global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8)) ? 4 : kTeamBigWaves)) void k_sweep_duo(SweepArgs args) {
     // (the tile itself -- merge path, chunk histogram, count scans, event loop, stitching -- is lchd_team_tile.h)
     using TT = TeamTile<CMAX, TL, TILE_, WGT, KSM, PRE>;
     constexpr int TEAMS = TT::TEAMS, EPL = TT::EPL, TILE = TT::TILE, WPB = kSweepWaves, NT = TT::NT, LW = TT::LW;
@@ -92,16 +84,11 @@ __global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8
         const uint8_t* __restrict__ tA = args.env_a.cat + offA;
         const uint8_t* __restrict__ tB = args.env_b.cat + offB;
         const double F0 = valid ? u2d(kA[0]) : 0.0;            // F(0): both anchors sit at distance 0
-#if LCHD_STAGE_PAIRS
         // list B starts at an EVEN entry of the buffer (one unused entry behind an odd list A): the staging below moves two entries per
         // lane and round -- one 16-byte key load, one 16-byte LDS write -- and no pair of entries straddles the two lists
         const int mAe = (mA + 1) & ~1, Tb = mAe + mB;  // <= TILE + 1: the buffers hold TILE + 2 entries
         uint64_t* sB = sA + mAe;
         uint8_t* cB = cA + mAe;
-#else
-        uint64_t* sB = sA + mA;
-        uint8_t* cB = cA + mA;
-#endif
 
         // lane tl of a team owns merged events [d0, d1) of its pair
         const int epl = (T + TL - 1) / TL;  // <= EPL
@@ -110,7 +97,6 @@ __global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8
         for (int k = 1; k < TEAMS; ++k) epl_w = max(epl_w, __builtin_amdgcn_readlane(epl, k * TL));
 
         wave_sync_lds();  // the previous pairs' tiles are fully consumed
-#if LCHD_STAGE_PAIRS
         {   // stage [A's points | pad | B's points]: entries 2 q and 2 q + 1 of the buffer by lane q % TL in round q / TL; all loads before
             // the first LDS write.  A pair's second entry may lie one past its list's last point (still inside the environment's slot or,
             // for the last slot, the workspace's slack): it lands in the pad entry or behind the buffer's used part and is never read.
@@ -152,37 +138,6 @@ __global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8
                 }
             }
         }
-#else
-        {   // stage [A's points | B's points]: entry t of the buffer is A[1 + t] or B[1 + t - mA]; all loads before the first LDS write.
-            // One predicate for the whole team (the pair is swept here), none per entry: an entry beyond T re-reads the pair's last
-            // point (index clamped: inside the row) and lands in the buffer's unused tail (t < TILE).
-            uint64_t rk[EPL];
-            uint8_t rc[EPL];
-            const uint64_t* kBs = kB - mA;
-            const uint8_t* tBs = tB - mA;
-#pragma unroll
-            for (int u = 0; u < EPL; ++u) { rk[u] = 0ull; rc[u] = 0; }
-            if (valid) {
-#pragma unroll
-                for (int u = 0; u < EPL; ++u) {
-                    if (u < epl_w) {  // (wave-uniform: rounds no team of this wavefront needs are skipped)
-                        const int t = min(tl + TL * u, T - 1);  // (T = 0: entry 0 of list A's row, the anchor)
-                        const bool isA = t < mA;
-                        rk[u] = (isA ? kA : kBs)[1 + t];
-                        rc[u] = (isA ? tA : tBs)[1 + t];
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < EPL; ++u) {
-                if (u < epl_w) {
-                    const int t = tl + TL * u;
-                    sA[t] = rk[u];
-                    cA[t] = rc[u];
-                }
-            }
-        }
-#endif
         wave_sync_lds();
 
         // (PRE: the prefix-count rows of the two environments; an unusable pair's records may name slots that do not exist: row 0 of slot 0)
@@ -197,7 +152,7 @@ template <int CM, int TM, bool PRE>
 static void launch_team_c(hipStream_t s, bool tile240, unsigned grid, const SweepArgs& a) {
     constexpr int NTH = 64 * kSweepWaves;
     constexpr bool WGT = TM == 1, KSM = TM == 2;
-    if (tile240) k_sweep_duo<CM, LCHD_DUO_TL, kDuoTile, WGT, KSM, PRE><<<grid, NTH, 0, s>>>(a);
+    if (tile240) k_sweep_duo<CM, kDuoTL, kDuoTile, WGT, KSM, PRE><<<grid, NTH, 0, s>>>(a);
     else k_sweep_duo<CM, 32, kTeam8Tile, WGT, KSM, PRE><<<grid, NTH, 0, s>>>(a);
 }
 template <int TM>

@@ -9,25 +9,6 @@
 
 #include "lchd_kcommon.h"
 
-#ifndef LCHD_CAT_HEADS
-#define LCHD_CAT_HEADS 1      // k_sweep / k_sweep_duo: the categories of both list heads are read together with their keys
-#endif
-#ifndef LCHD_TEAM_EXACT_UNROLL_MAX
-#define LCHD_TEAM_EXACT_UNROLL_MAX 8    // category slots up to which the (rare) literal Hellinger form of k_sweep_duo is unrolled (above: a rolled loop -- the unrolled look-ups of 12+ slots cost registers in the event loop)
-#endif
-#ifndef LCHD_TEAM_LOOP_UNROLL
-#define LCHD_TEAM_LOOP_UNROLL 1
-#endif
-#ifndef LCHD_TEAM_LDSCNT
-#define LCHD_TEAM_LDSCNT 1   // k_sweep_duo with 20 .. 28 category slots: per-lane counts of the event loop in LDS bytes (0: packed registers)
-#endif
-#ifndef LCHD_LCNT_HIST
-#define LCHD_LCNT_HIST 1     // the instantiations with per-lane counts in LDS bytes build the chunk histogram there too (LDS adds) when that takes two 4-bit words (17 and more slots; with one word the register form is as fast); 0: always in registers
-#endif
-#ifndef LCHD_WGT_LDSCNT
-#define LCHD_WGT_LDSCNT 1   // 1: the weighted instantiations with 9 .. 16 slots keep their per-lane counts in LDS bytes too
-#endif
-
 namespace lchd {
 
 constexpr int kDuoTile = 240;  // merged events per pair: 16 lanes x 15, the most the 4-bit chunk fields take (224 = 16 x 14 until late in round 3: at ~95 points per environment 8.7 % of C4's pairs were longer than that, 2.3 % are longer than 240 -- C4 sweep 3.27 -> 3.19 ms, C3 0.867 -> 0.837)
@@ -45,6 +26,7 @@ __device__ __forceinline__ bool pair_is_small(int rule, int nA, int nB) {
 // form is still good to ~2e-13.  (It used to be 1e-3: large random clouds -- dense from_coords rows -- sit at H^2 ~ 1e-4 and
 // paid the O(C) literal form with 2C square roots on nearly every event.)
 constexpr double kExactH2Below = 1e-6;
+constexpr int kTeamExactUnrollMax = 8;  // category slots up to which the (rare) literal Hellinger form of k_sweep_duo is unrolled (above: a rolled loop -- the unrolled look-ups of 12+ slots cost registers in the event loop)
 
 __device__ __forceinline__ int merge_path(const uint64_t* A, int nA, const uint64_t* B, int nB, int d) {
     int lo = max(0, d - nB), hi = min(d, nA);
@@ -136,7 +118,8 @@ struct TeamTile {
     // write replace the word-select chains over the count words and the 4-bit chunk fields (C5, 28 slots: 25 of the event's 88
     // vector instructions were v_cndmask_b32_e64).  The rows cost (2 CMAX / 8) x 512 bytes per wavefront: three workgroups per CU
     // -- what these instantiations are compiled for -- still fit up to 28 slots; with 32 they would not (registers there).
-    static constexpr bool LCNT = (((CMAX > 16) && (CMAX <= 28)) || (WGT && (LCHD_WGT_LDSCNT != 0) && CMAX > 8 && CMAX <= 16)) && (LCHD_TEAM_LDSCNT != 0);
+    // The weighted instantiations with 9 .. 16 slots keep their per-lane counts there too.
+    static constexpr bool LCNT = ((CMAX > 16) && (CMAX <= 28)) || (WGT && CMAX > 8 && CMAX <= 16);
     static constexpr int LW = LCNT ? (2 * CMAX + 7) / 8 : 1;  // u64 words of a lane's LDS count row ([LW][64] per wavefront)
     static_assert(!PRE || (!LCNT && !WGT && CMAX <= 16), "prefix-count rows: the register-resident forms of up to two count words per side");
 
@@ -166,7 +149,7 @@ struct TeamTile {
             // All of it in 32-bit arithmetic: a point touches ONE count byte of its side.  The up to three points of a side are first
             // counted in 2-bit fields of one register (field c at bit 2 c: no field exceeds 3), the fields are spread to bytes once, and
             // the bytes are added to the row's halves (no count exceeds 255: no carry crosses a byte).
-            static_assert(kPreStep >= 1 && kPreStep <= 4 && (kPreStep & (kPreStep - 1)) == 0 && CMAX <= 16, "2-bit fields: at most three points, 16 slots");
+            static_assert(kPreStep == 4 && CMAX <= 16, "2-bit fields: at most three points, 16 slots");
             constexpr int NW32 = (CMAX + 3) / 4;  // 32-bit words of four count bytes per side
             const unsigned ui0 = (unsigned)i0, uj0 = (unsigned)j0;  // (both >= 0: unsigned division is a shift)
             const unsigned ra_ = ui0 / kPreStep, rb_ = uj0 / kPreStep, qa_ = ui0 % kPreStep, qb_ = uj0 % kPreStep;
@@ -183,46 +166,46 @@ struct TeamTile {
             uint32_t ta_ = 0u, tb_ = 0u;
 #pragma unroll
             for (int m = 0; m < kPreStep - 1; ++m) {
-                // 1 where point m lies before the chunk's start (m < q), else 0 -- without a compare for rows of four points
+                // 1 where point m lies before the chunk's start (m < q, q <= 3), else 0 -- without a compare
+                // (the last arm is never reached, m < 3: without it the same instructions come out with other registers, and this
+                // file's clean-up was held to byte-identical code objects -- drop it with the next change that moves the code anyway)
                 uint32_t va_, vb_;
-                if (kPreStep == 4 && m == 0) { va_ = min(qa_, 1u); vb_ = min(qb_, 1u); }
-                else if (kPreStep == 4 && m == 1) { va_ = qa_ >> 1; vb_ = qb_ >> 1; }
-                else if (kPreStep == 4 && m == 2) { va_ = qa_ & (qa_ >> 1); vb_ = qb_ & (qb_ >> 1); }
+                if (m == 0) { va_ = min(qa_, 1u); vb_ = min(qb_, 1u); }
+                else if (m == 1) { va_ = qa_ >> 1; vb_ = qb_ >> 1; }
+                else if (m == 2) { va_ = qa_ & (qa_ >> 1); vb_ = qb_ & (qb_ >> 1); }
                 else { va_ = (unsigned)m < qa_ ? 1u : 0u; vb_ = (unsigned)m < qb_ ? 1u : 0u; }
                 const unsigned ca_ = pa_[m], cb_ = pb_[m];
                 ta_ += va_ << ((2u * ca_) & 31u);  // (a point's category is below CMAX <= 16; a byte that is no point may hold anything)
                 tb_ += vb_ << ((2u * cb_) & 31u);
             }
-            if constexpr (kPreStep > 1) {
-                // the four 2-bit fields of the low eight bits of h -> four bytes
-                auto spread2 = [](uint32_t h) -> uint32_t {
-                    const uint32_t t = (h & 0x0000000Fu) | ((h << 12) & 0x000F0000u);
-                    return (t | (t << 6)) & 0x03030303u;
-                };
+            // the four 2-bit fields of the low eight bits of h -> four bytes
+            auto spread2 = [](uint32_t h) -> uint32_t {
+                const uint32_t t = (h & 0x0000000Fu) | ((h << 12) & 0x000F0000u);
+                return (t | (t << 6)) & 0x03030303u;
+            };
 #pragma unroll
-                for (int k = 0; k < NW; ++k) {
-                    uint32_t la_ = (uint32_t)exA[k], ha_ = (uint32_t)(exA[k] >> 32), lb_ = (uint32_t)exB[k], hb_ = (uint32_t)(exB[k] >> 32);
-                    la_ += spread2(ta_ >> (16 * k));
-                    lb_ += spread2(tb_ >> (16 * k));
-                    if (2 * k + 1 < NW32) {  // (the side's last count word may hold four categories only: its upper half stays as the row has it)
-                        ha_ += spread2(ta_ >> (16 * k + 8));
-                        hb_ += spread2(tb_ >> (16 * k + 8));
-                    }
-                    exA[k] = ((uint64_t)ha_ << 32) | la_;
-                    exB[k] = ((uint64_t)hb_ << 32) | lb_;
+            for (int k = 0; k < NW; ++k) {
+                uint32_t la_ = (uint32_t)exA[k], ha_ = (uint32_t)(exA[k] >> 32), lb_ = (uint32_t)exB[k], hb_ = (uint32_t)(exB[k] >> 32);
+                la_ += spread2(ta_ >> (16 * k));
+                lb_ += spread2(tb_ >> (16 * k));
+                if (2 * k + 1 < NW32) {  // (the side's last count word may hold four categories only: its upper half stays as the row has it)
+                    ha_ += spread2(ta_ >> (16 * k + 8));
+                    hb_ += spread2(tb_ >> (16 * k + 8));
                 }
+                exA[k] = ((uint64_t)ha_ << 32) | la_;
+                exB[k] = ((uint64_t)hb_ << 32) | lb_;
             }
         } else {
         // pass 1: 4-bit-per-category histogram of the lane's chunk
         H4 hA[NH], hB[NH];
 #pragma unroll
         for (int w = 0; w < NH; ++w) hA[w] = hB[w] = 0;
-        // ... LCNT: in the lane's LDS row instead -- the row the event loop keeps its running counts in is zeroed, every point of the chunk
-        // is ONE non-returning 32-bit LDS add of 1 << (8 x byte) (a chunk holds at most 15 points: no byte overflows into its neighbour),
+        // ... LCNT with two 4-bit words (17 and more slots; with one word the register form is as fast): in the lane's LDS row instead --
+        // the row the event loop keeps its running counts in is zeroed, every point of the chunk is ONE non-returning 32-bit LDS add of 1 << (8 x byte) (a chunk holds at most 15 points: no byte overflows into its neighbour),
         // and the row read back IS the chunk's counts as 8-bit fields, A's CMAX bytes then B's: five instructions per point instead of the
         // 24 of the two-word 4-bit form, and no 4-bit -> 8-bit spreading afterwards
         uint64_t hw[LW];
-        if constexpr (LCNT && NH > 1 && (LCHD_LCNT_HIST != 0)) {
+        if constexpr (LCNT && NH > 1) {
 #pragma unroll
             for (int k = 0; k < LW; ++k) *reinterpret_cast<uint64_t*>(lcl + k * 512) = 0ull;
             const int nAl = i1 - i0, nl = d1 - d0;
@@ -239,8 +222,7 @@ struct TeamTile {
             }
 #pragma unroll
             for (int k = 0; k < LW; ++k) hw[k] = *reinterpret_cast<const uint64_t*>(lcl + k * 512);
-        } else
-        {   // one fixed-trip loop over the chunk's points, A's run first (see k_sweep)
+        } else {  // one fixed-trip loop over the chunk's points, A's run first (see k_sweep)
             const int nAl = i1 - i0, nl = d1 - d0;
             const uint8_t* pa_ = cA + i0;
             const uint8_t* pb_ = cB + (j0 - nAl);
@@ -272,7 +254,7 @@ struct TeamTile {
 #pragma unroll
         for (int k = 0; k < NW; ++k) {
             uint64_t va_, vb_;
-            if constexpr (LCNT && NH > 1 && (LCHD_LCNT_HIST != 0)) {
+            if constexpr (LCNT && NH > 1) {
                 // count word k of a side = its bytes [8 k, 8 k + 8) in the row (A's CMAX bytes | B's CMAX bytes, CMAX a multiple of 4)
                 va_ = hw[k];
                 if (8 * k + 8 > CMAX) va_ &= 0xFFFFFFFFull;  // (A's last four categories; the upper half is B's first)
@@ -336,27 +318,18 @@ struct TeamTile {
 
         // pass 2 (same scheme as k_sweep): both list heads in registers, chunk-local additions in 4-bit fields
         int i = i0, j = j0;
-#if LCHD_CAT_HEADS
         uint64_t ka = sA[i], kb = sB[j];
         unsigned cta = cA[i], ctb = cB[j];  // (unsigned from the byte load: no mask is emitted)
-#else
-        uint64_t ka = (i < i1) ? sA[i] : kPadKey, kb = (j < j1) ? sB[j] : kPadKey;
-#endif
         H4 dA[NH], dB[NH];
 #pragma unroll
         for (int w = 0; w < NH; ++w) dA[w] = dB[w] = 0;
         double Fp = 0.0, Hp = 0.0, local = 0.0;
-#if LCHD_CAT_HEADS
         // F of the chunk's first event, for the stitching below: known from the heads.  Inside the loop the first event adds
         // (F - 0) * 0 = 0 like any other -- no "first event" selects per event.
         const double firstF = u2d(((i < i1) & ((j >= j1) | (ka <= kb))) ? ka : kb);
-#else
-        double firstF = 0.0;
-#endif
-#pragma unroll LCHD_TEAM_LOOP_UNROLL
+#pragma unroll 1
         for (int e = 0; e < epl_w; ++e) {
             if (d0 + e < d1) {
-#if LCHD_CAT_HEADS
                 // both heads and their categories are re-read after every event (see k_sweep); run ends are tested on the indices
                 const bool takeA = (i < i1) & ((j >= j1) | (ka <= kb));
                 uint64_t key = takeA ? ka : kb;
@@ -374,28 +347,10 @@ struct TeamTile {
                 // (opaque to the optimiser: it would otherwise carry the two heads as BYTES around the loop and widen them again with a
                 // v_and_b32 0xff each per event -- ds_read_u8 has already zero-extended them; no instruction is emitted for this)
                 asm("" : "+v"(cta), "+v"(ctb));
-#else
-                const bool takeA = (ka <= kb);
-                const uint64_t key = takeA ? ka : kb;
-                const int ct = (takeA ? cA : cB)[takeA ? i : j];
-                i += takeA ? 1 : 0;
-                j += takeA ? 0 : 1;
-                {
-                    const int nidx = takeA ? i : j, nend = takeA ? i1 : j1;
-                    const uint64_t nk = (takeA ? sA : sB)[nidx];
-                    const uint64_t nh = nidx < nend ? nk : kPadKey;
-                    ka = takeA ? nh : ka;
-                    kb = takeA ? kb : nh;
-                }
-#endif
                 const double F = u2d(key);
-#if LCHD_CAT_HEADS
                 local = fma(F - Fp, Hp, local);  // (fused on purpose, like the two updates below: one rounding less and one instruction less per
                                                  //  event; the translation unit's -ffp-contract=off is there for the DISTANCES, whose roundings decide
                                                  //  ties and the strict threshold)
-#else
-                if (e == 0) firstF = F; else local += (F - Fp) * Hp;
-#endif
                 // (unsigned: a signed `% 8` is five instructions; with one count word the category is below 8 -- checked where the
                 // environments were built, foreign ones stored as 0)
                 const unsigned uct = ct;
@@ -493,7 +448,7 @@ struct TeamTile {
                             const double dd = t_sqrt[ca] * ra - t_sqrt[cb] * rb;
                             acc2 = WGT ? fma(w_s[c & 31] * dd, dd, acc2) : fma(dd, dd, acc2);
                         }
-                    } else if constexpr (CMAX <= LCHD_TEAM_EXACT_UNROLL_MAX) {
+                    } else if constexpr (CMAX <= kTeamExactUnrollMax) {
 #pragma unroll
                         for (int k = 0; k < NW; ++k) {
 #pragma unroll
