@@ -297,6 +297,17 @@ int lchd_ctx_enable_timing(lchd_ctx *ctx, int32_t on);
 double lchd_ctx_last_ms(lchd_ctx *ctx, const char *phase);
 /* Environment statistics of the most recent call: sum over anchor pairs of (n_A + n_B) (points incl. anchors). */
 int64_t lchd_ctx_last_env_points(lchd_ctx *ctx);
+/* The uniform grid a thresholded pass buckets one side's atoms into, as a pure function (no context, no device): cells are at
+ * least (1 + 1e-9) thr / reach wide (reach 1: the one-environment-per-workgroup kernels, reach 2: the grouped kernel), at most 1024
+ * per axis, and the largest axis is halved until n_struct * dims[0] * dims[1] * dims[2] <= 2^23.  cell_out: the cell edges
+ * (1.0 on an axis of extent 0); *n_cells_out: cells of all structures together.  Returns LCHD_OK or LCHD_EVALUE. */
+int lchd_plan_grid(const double bbmin[3], const double bbmax[3], int32_t n_struct, double thr, int32_t reach,
+                   int32_t dims_out[3], double cell_out[3], int64_t *n_cells_out);
+/* Grid and cell-list build of side `side` (0: A, 1: B) of the most recent thresholded pass.  *build_out: 0 no list built for this
+ * side (one object on both sides: shared with side A), 1 fused prologue, 2 one workgroup per structure, 3 general build with the
+ * one-workgroup scan, 4 general build with the multi-block scan.  Any output pointer may be null.  Returns 0, or -1 under the
+ * conditions under which lchd_ctx_last_env_points returns -1 (and for a side other than 0 / 1). */
+int lchd_ctx_last_grid(lchd_ctx *ctx, int32_t side, int32_t dims_out[3], int64_t *n_cells_out, int32_t *build_out);
 /* 1 if the most recent from_coords / from_dmxs call of the context ran the fused sort + sweep kernel (one launch per
  * call, nothing but the scores written: Hellinger-2, unit category weights, at most 16 categories, rows of 1 025 .. 20 480
  * points), 0 if it ran the row sort followed by the sweep (src/locohd.rs:410-476 either way). */

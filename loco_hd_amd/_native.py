@@ -100,6 +100,8 @@ _PROTOS = {
     "lchd_ctx_enable_timing": (C.c_int, [_VP, _i32]),
     "lchd_ctx_last_ms": (C.c_double, [_VP, C.c_char_p]),
     "lchd_ctx_last_env_points": (C.c_int64, [_VP]),
+    "lchd_plan_grid": (C.c_int, [_DP, _DP, _i32, _f64, _i32, _IP, _DP, _LP]),
+    "lchd_ctx_last_grid": (C.c_int, [_VP, _i32, _IP, _LP, _IP]),
     "lchd_ctx_last_dense_fused": (C.c_int32, [_VP]),
     "lchd_ctx_set_deterministic": (C.c_int, [_VP, _i32]),
     "lchd_ctx_get_deterministic": (C.c_int32, [_VP]),

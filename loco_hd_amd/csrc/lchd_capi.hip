@@ -163,6 +163,13 @@ struct lchd_cloud {
 
 enum { PH_CELLS = 0, PH_ANCHORS = 1, PH_ENV = 2, PH_SWEEP = 3, PH_N = 4 };
 
+// What lchd_ctx_last_grid reports about one side of a pass: the planned grid and which cell-list build launch_prologue picked.
+struct GridRecord {
+    int32_t dim[3] = {0, 0, 0};
+    int64_t n_cells = 0;
+    int32_t build = 0;
+};
+
 // Calls on one context are serialised (include/loco_hd_hip.h, "Threads"): every entry point that takes a context holds it for its
 // whole duration (CtxLock below).  The owner may re-enter (lchd_from_primitives_dev is lchd_from_primitives_dev_async +
 // lchd_ctx_finish).  Between lchd_from_primitives_dev_async and lchd_ctx_finish the context stays with the thread that enqueued the
@@ -255,6 +262,7 @@ struct lchd_ctx {
         int64_t n_slots_a = 0, n_slots_b = 0;               // environment slots per side
         bool subset = false;                                // the enqueued pass IS a second pass over the pairs of overflowed environments
         bool per_pair = false;                              // the enqueued pass did not de-duplicate side B (slot p = pair p)
+        GridRecord grid[2];                                 // grids and cell-list builds of the enqueued pass
     } pend;
     // multi-GPU sharding helpers (lchd_shard_*): device state, host-mapped counts, the plan they belong to
     ShardState* d_shard = nullptr;
@@ -269,6 +277,7 @@ struct lchd_ctx {
     // most recent sweep (for lchd_ctx_last_env_points)
     SweepArgs last{};
     bool last_valid = false;
+    GridRecord last_grid[2];  // ... and its grids and cell-list builds (for lchd_ctx_last_grid)
 };
 
 struct Arena {
@@ -494,6 +503,17 @@ extern "C" int64_t lchd_ctx_last_env_points(lchd_ctx* c) {
     if (hipMemcpyAsync(&v, c->d_points, sizeof v, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return -1;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
     return (int64_t)v;
+}
+
+extern "C" int lchd_ctx_last_grid(lchd_ctx* c, int32_t side, int32_t dims_out[3], int64_t* n_cells_out, int32_t* build_out) {
+    CTX_LOCK(c);
+    if (!c || !c->last_valid || c->pend.active || side < 0 || side > 1) return -1;
+    const GridRecord& g = c->last_grid[side];
+    for (int k = 0; k < 3; ++k)
+        if (dims_out) dims_out[k] = g.dim[k];
+    if (n_cells_out) *n_cells_out = g.n_cells;
+    if (build_out) *build_out = g.build;
+    return 0;
 }
 
 // One sweep family for every pair: the one-pair-per-wavefront k_sweep that reads its square-root tables from global memory (tiles
@@ -906,35 +926,54 @@ struct GridPlan {
     int n_cells;
 };
 
-static GridPlan plan_grid(const lchd_cloud* cl, double thr, int reach) {
-    GridPlan g{};
+// The grid of one side of a thresholded pass: a pure function of the bounding box, the structure count, the threshold and the
+// neighbourhood reach of the environment kernel (no context, no device).
+extern "C" int lchd_plan_grid(const double bbmin[3], const double bbmax[3], int32_t n_struct, double thr, int32_t reach,
+                              int32_t dims_out[3], double cell_out[3], int64_t* n_cells_out) {
+    if (!bbmin || !bbmax || !dims_out || !cell_out || !n_cells_out) return fail(LCHD_EVALUE, "null argument");
+    if (n_struct < 1 || reach < 1 || !(thr > 0.0)) return fail(LCHD_EVALUE, "lchd_plan_grid: n_struct >= 1, reach >= 1 and thr > 0 are required");
     // cells are at least (1 + 1e-9) * thr / reach wide so that |dx| < thr can never leave the (2 reach + 1)^3 neighbourhood of
     // the anchor's cell through rounding (reach 1: k_env_cells / k_env_collect; reach 2: k_env_group)
     const double cell0 = thr / reach * (1.0 + 1e-9);
+    int dim[3];
     long long total = 1;
     for (int k = 0; k < 3; ++k) {
-        const double ext = cl->bbmax[k] - cl->bbmin[k];
+        const double ext = bbmax[k] - bbmin[k];
         double nd = std::floor(ext / cell0);
         if (!(nd >= 1.0)) nd = 1.0;
         if (nd > 1024.0) nd = 1024.0;
-        g.dim[k] = (int)nd;
-        total *= g.dim[k];
+        dim[k] = (int)nd;
+        total *= dim[k];
     }
-    total *= cl->n_struct;
+    total *= n_struct;
     while (total > (1ll << 23)) {  // bound the cell arrays (8M cells): coarsen the largest axis
-        int k = (g.dim[0] >= g.dim[1] && g.dim[0] >= g.dim[2]) ? 0 : (g.dim[1] >= g.dim[2] ? 1 : 2);
-        if (g.dim[k] == 1) break;
-        total /= g.dim[k];
-        g.dim[k] = (g.dim[k] + 1) / 2;
-        total *= g.dim[k];
+        int k = (dim[0] >= dim[1] && dim[0] >= dim[2]) ? 0 : (dim[1] >= dim[2] ? 1 : 2);
+        if (dim[k] == 1) break;
+        total /= dim[k];
+        dim[k] = (dim[k] + 1) / 2;
+        total *= dim[k];
     }
     for (int k = 0; k < 3; ++k) {
-        const double ext = cl->bbmax[k] - cl->bbmin[k];
-        g.min[k] = cl->bbmin[k];
-        const double cell = ext > 0.0 ? ext / g.dim[k] : 1.0;
-        g.inv[k] = 1.0 / (cell * (1.0 + 1e-12));
+        const double ext = bbmax[k] - bbmin[k];
+        dims_out[k] = dim[k];
+        cell_out[k] = ext > 0.0 ? ext / dim[k] : 1.0;
     }
-    g.n_cells = cl->n_struct * g.dim[0] * g.dim[1] * g.dim[2];
+    *n_cells_out = (int64_t)n_struct * dim[0] * dim[1] * dim[2];
+    return LCHD_OK;
+}
+
+static GridPlan plan_grid(const lchd_cloud* cl, double thr, int reach) {
+    GridPlan g{};
+    int32_t dim[3];
+    double cell[3];
+    int64_t n_cells = 0;
+    (void)lchd_plan_grid(cl->bbmin, cl->bbmax, cl->n_struct, thr, reach, dim, cell, &n_cells);
+    for (int k = 0; k < 3; ++k) {
+        g.min[k] = cl->bbmin[k];
+        g.dim[k] = dim[k];
+        g.inv[k] = 1.0 / (cell[k] * (1.0 + 1e-12));
+    }
+    g.n_cells = (int)n_cells;
     return g;
 }
 
@@ -1135,7 +1174,12 @@ static int prims_enqueue(lchd_ctx* c) {
     {
         PrepSide psa = prep_side(cva, gva, sa), psb = prep_side(cvb, gvb, sb);
         psb.no_anchors = per_pair ? 1 : 0;  // (side B without de-duplication: no flags, no slots -- one environment per pair)
-        (void)launch_prologue(s, c->tune, P.anchors, n_pairs, psa, psb, pb.zero_base, pb.zero_bytes, c->d_status, same);
+        int builds[2] = {0, 0};
+        (void)launch_prologue(s, c->tune, P.anchors, n_pairs, psa, psb, pb.zero_base, pb.zero_bytes, c->d_status, same, builds);
+        for (int side = 0; side < 2; ++side) {
+            const GridPlan& g = side ? gb : ga;
+            P.grid[side] = GridRecord{{g.dim[0], g.dim[1], g.dim[2]}, g.n_cells, builds[side]};
+        }
         if (per_pair) launch_pair_anchor_recs(s, P.anchors, n_pairs, psb, c->d_status);
     }
     mark(c, 1);
@@ -1408,6 +1452,8 @@ static int finish_passes(lchd_ctx* c, uint32_t* flags_out) {
                             (2 * c->h_status->n_c8 >= (unsigned long long)P.n_pairs ? 2 : 0) |
                             (c->h_status->n_duo == (unsigned long long)P.n_pairs ? 8 : 0) | (c->h_status->n_c8 == (unsigned long long)P.n_pairs ? 16 : 0);
         c->last = P.sw;
+        c->last_grid[0] = P.grid[0];
+        c->last_grid[1] = P.grid[1];
         c->last_valid = true;
         *flags_out = f;
         return LCHD_OK;

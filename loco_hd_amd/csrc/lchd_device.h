@@ -200,8 +200,10 @@ struct PrepSide {
 // zeroes what its launch tier needs with at most one operation.  Returns the number of stream operations enqueued.
 // `same`: both sides are one device object -- side B's cell list and slots are not built, the anchors of both columns are
 // de-duplicated together into side A's flags / slots / records and n_unique[1] = 0.
+// builds_out (optional, two entries): which cell-list build each side took -- 0 none (side B of `same`), 1 fused prologue, 2 one
+// workgroup per structure, 3 general build with the one-workgroup scan, 4 general build with the multi-block scan.
 int launch_prologue(hipStream_t s, const Tuning& t, const int64_t* anchors, int64_t n_pairs, const PrepSide& a, const PrepSide& b,
-                    void* zero_base, size_t zero_bytes, DeviceStatus* st, bool same = false);
+                    void* zero_base, size_t zero_bytes, DeviceStatus* st, bool same = false, int* builds_out = nullptr);
 // Anchor records of a side without de-duplication (PrepSide::no_anchors), one per PAIR: record p = the side-B anchor of pair p; sets
 // DeviceStatus::n_unique[1] = n_pairs.  Behind launch_prologue (reads the side's atom -> position map).
 void launch_pair_anchor_recs(hipStream_t s, const int64_t* anchors, int64_t n_pairs, const PrepSide& b, DeviceStatus* st);

@@ -513,7 +513,7 @@ static bool fits_struct_path(const PrepSide& P, const Tuning& t, CloudView& cs) 
 
 constexpr int kStructNT = 512;   // (measured, C4 cell lists: 128 0.506, 256 0.466, 512 0.445 ms per step) threads of the per-structure cell-list workgroups of a batch of more than 16 structures
 int launch_prologue(hipStream_t s, const Tuning& t, const int64_t* anchors, int64_t n_pairs, const PrepSide& a_in, const PrepSide& b_in,
-                    void* zero_base, size_t zero_bytes, DeviceStatus* st, bool same) {
+                    void* zero_base, size_t zero_bytes, DeviceStatus* st, bool same, int* builds_out) {
     PrepSide a = a_in, b = b_in;
     CloudView csa, csb;
     bool fa = fits_struct_path(a, t, csa), fb = fits_struct_path(b, t, csb);
@@ -529,6 +529,7 @@ int launch_prologue(hipStream_t s, const Tuning& t, const int64_t* anchors, int6
     if (!same && fa && fb && csa.n_struct == 1 && csb.n_struct == 1 && n_pairs <= kFusedPairsMax && a.c.n > 0 && b.c.n > 0) {
         const size_t lds = std::max((size_t)cps_a * 4 + (size_t)a.c.n * 4, (size_t)cps_b * 4 + (size_t)b.c.n * 4);
         k_prologue_fused<<<2, 1024, lds, s>>>(anchors, n_pairs, a, b, st);
+        if (builds_out) builds_out[0] = builds_out[1] = 1;
         return 1;
     }
     // the anchor flags (and, for the general cell list, its counters) must be zero: folded into the struct launch when both
@@ -553,6 +554,10 @@ int launch_prologue(hipStream_t s, const Tuning& t, const int64_t* anchors, int6
         ++ops;
     }
     const int cells_a = fa ? 0 : a.g.n_cells, cells_b = fb ? 0 : b.g.n_cells;  // 0: the struct path has built that side's cell list
+    if (builds_out) {
+        builds_out[0] = fa ? 2 : (cells_a > kPrepScanCells ? 4 : 3);
+        builds_out[1] = same ? 0 : (fb ? 2 : (cells_b > kPrepScanCells ? 4 : 3));
+    }
     const int64_t work = std::max<int64_t>((cells_a ? a.c.n : 0) + (int64_t)(cells_b ? b.c.n : 0), n_pairs);
     const int64_t nbk = (work + 255) / 256;
     k_prep_count<<<(unsigned)std::max<int64_t>(1, std::min<int64_t>(nbk, 8192)), 256, 0, s>>>(anchors, n_pairs, a, b, cells_a, cells_b, st);

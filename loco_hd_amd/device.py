@@ -66,6 +66,17 @@ class DeviceSession:
     def last_env_points(self) -> int:
         return int(N.lib().lchd_ctx_last_env_points(self._ctx))
 
+    def last_grid(self):
+        """Grid and cell-list build of both sides of the most recent thresholded pass (lchd_ctx_last_grid): a list of two dicts
+        {"dims": (d0, d1, d2), "n_cells": int, "build": 0 .. 4}, or None where last_env_points() would return -1."""
+        sides = []
+        for side in (0, 1):
+            dims, n_cells, build = (C.c_int32 * 3)(), C.c_int64(), C.c_int32()
+            if N.lib().lchd_ctx_last_grid(self._ctx, side, dims, C.byref(n_cells), C.byref(build)) != 0:
+                return None
+            sides.append({"dims": tuple(dims), "n_cells": int(n_cells.value), "build": int(build.value)})
+        return sides
+
     def last_dense_fused(self) -> bool:
         """True if the most recent from_coords call ran the fused sort + sweep kernel (lchd_ctx_last_dense_fused)."""
         return bool(N.lib().lchd_ctx_last_dense_fused(self._ctx))

@@ -544,7 +544,8 @@ def test_leftover_list_of_hinted_passes_follows_a_changing_pair_list(lh, oracle,
 
 def test_regular_batch_of_large_structures_uses_the_per_structure_cell_build(lh, oracle):
     """64 frames of an 11 000-atom structure: the one-workgroup-per-structure cell list at (almost) its LDS limit, against
-    the oracle on a sample of frames and against the generic cell-list path."""
+    the oracle on a sample of frames and against the generic cell-list path.  The frames' box (side 54.6 + the jitter's tails: 56.5) holds
+    16 cells of 3.5 per axis: the per-structure build takes grids of at most 4096 cells, and last_grid() says which build ran."""
     import os
 
     import torch
@@ -552,7 +553,7 @@ def test_regular_batch_of_large_structures_uses_the_per_structure_cell_build(lh,
 
     rng = np.random.default_rng(31)
     n, nf = 11_000, 64
-    side = (n / 0.05) ** (1 / 3)
+    side = (n / 0.0676) ** (1 / 3)
     base = rng.uniform(0, side, (n, 3))
     cat = rng.integers(0, 6, n).astype(np.int32)
     cats = [f"c{i}" for i in range(6)]
@@ -567,6 +568,9 @@ def test_regular_batch_of_large_structures_uses_the_per_structure_cell_build(lh,
             sess = DeviceSession(lchd)
             ref = sess.upload(base, cat)
             outs[mode] = sess.score_trajectory(ref, frames, np.stack([la, la], 1), 7.0, chunk=nf)
+            grid = sess.last_grid()  # side B: the 64 frames
+            assert grid is not None and grid[1]["n_cells"] == nf * int(np.prod(grid[1]["dims"]))
+            assert grid[1]["build"] == 2 if mode == "struct" else grid[1]["build"] in (3, 4), (mode, grid)
             sess.close()
         finally:
             os.environ.pop("LCHD_NO_STRUCT_CELLS", None)
