@@ -308,6 +308,79 @@ int lchd_plan_grid(const double bbmin[3], const double bbmax[3], int32_t n_struc
  * one-workgroup scan, 4 general build with the multi-block scan.  Any output pointer may be null.  Returns 0, or -1 under the
  * conditions under which lchd_ctx_last_env_points returns -1 (and for a side other than 0 / 1). */
 int lchd_ctx_last_grid(lchd_ctx *ctx, int32_t side, int32_t dims_out[3], int64_t *n_cells_out, int32_t *build_out);
+/* The sweep kernel families of a from_primitives pass, one bit each (lchd_sweep_plan::families). */
+typedef enum {
+    LCHD_SWEEP_INLINE = 1,    /* one launch for a small call: the sweep works out the pair records itself */
+    LCHD_SWEEP_TEAM240 = 2,   /* four pairs of at most 240 merged events per wavefront (rule 0) */
+    LCHD_SWEEP_TEAM480 = 4,   /* two pairs per wavefront: both environments <= 255 points, at most 480 merged events (rule 2) */
+    LCHD_SWEEP_C8 = 8,        /* one pair per wavefront, 8-bit counts: both environments <= 255 points (rule 1) */
+    LCHD_SWEEP_INDIRECT = 16, /* the companion: the usable pairs the rule in force leaves over */
+    LCHD_SWEEP_PLAIN = 32,    /* one pair per wavefront, every size and distance */
+    LCHD_SWEEP_INC = 64,      /* Kullback-Leibler / Renyi in O(1) per event */
+    LCHD_SWEEP_WIDE = 128     /* more than 32 category slots, environments beyond 65535 points */
+} lchd_sweep_family;
+/* The test hooks (LCHD_* environment variables, deterministic mode) the choice depends on, one bit each (lchd_sweep_query::hooks). */
+typedef enum {
+    LCHD_HOOK_NO_DUO = 1, LCHD_HOOK_NO_COUNT8 = 2, LCHD_HOOK_NO_C8_TEAM = 4, LCHD_HOOK_NO_INLINE_META = 8, LCHD_HOOK_FORCE_WIDE = 16,
+    LCHD_HOOK_FORCE_GENERIC = 32, LCHD_HOOK_FORCE_BIGENV = 64, LCHD_HOOK_NO_SWEEP_HINT = 128
+} lchd_sweep_hook;
+/* Everything the choice of sweep kernels depends on. */
+typedef struct lchd_sweep_query {
+    int64_t n_pairs;
+    int32_t n_categories;
+    int32_t force_cmax;        /* LCHD_FORCE_CMAX: at least this many category slots (0: none) */
+    int32_t hellinger2;        /* the distance is Hellinger with exponent 2 */
+    int32_t unit_weights;      /* every category weight is 1 */
+    int32_t wf_pow;            /* a weight function needs pow() (matters only without CDF keys) */
+    int32_t sd_fast;           /* 0, 1 Kullback-Leibler / 2 Renyi with parameters the O(1) sweep takes, 3 Kolmogorov-Smirnov */
+    int32_t has_wf_index;      /* the call names a weight function per pair */
+    int32_t has_left_list;     /* the pass has leftover-list buffers (not in deterministic mode) */
+    int64_t stride_a, stride_b; /* points per environment slot */
+    int32_t cdf_keys_a, cdf_keys_b; /* key sets of F values in the stores (0: distance keys) */
+    int32_t pre_rows;          /* both stores carry prefix-count rows of the width this slot count reads */
+    int32_t hint_bits;         /* 0 unknown, else 4 | 1 (pairs of <= 240 events were the previous pass's majority) | 2 (pairs of the
+                                  8-bit-count rule were) | 8 (EVERY pair had <= 240 events) | 16 (... was of the 8-bit-count rule) */
+    uint32_t hooks;            /* lchd_sweep_hook bits */
+} lchd_sweep_query;
+/* What a pass launches.  Without a hint (forced == 0) every candidate family is launched and the kernels decide on the device which
+ * rule is in force: small_rule if 2 * (pairs of small_rule) >= n_pairs, else second_rule (when not 0) if 2 * (pairs of rule 2) >=
+ * n_pairs, else none (-1: the plain family takes every pair).  With a hint (forced == 1) small_rule is in force.  A pair with an
+ * unusable anchor or environment (its score is NaN) belongs to the team / 8-bit family of the rule in force, to the plain / incremental
+ * family under rule -1. */
+typedef struct lchd_sweep_plan {
+    uint32_t families;         /* lchd_sweep_family bits: exactly what is launched */
+    int32_t slots;             /* category-slot instantiation: 8 / 12 / 16 / 20 / 24 / 28 / 32 (8 / 12 / 16 / 24 / 32 for the incremental
+                                  family), 0 for the wide family */
+    int32_t pre;               /* the team kernels read prefix-count rows (PRE instantiations) */
+    int32_t small_rule;        /* 0: a + b - 2 <= 240; 1: max(a, b) <= 255; 2: max(a, b) <= 255 and a + b - 2 <= 480 (a, b: points of
+                                  the two environments); without a team / 8-bit family in `families` it is only what n_small counts */
+    int32_t second_rule;       /* 0, or 2: the second team kernel of a pass without a hint */
+    int32_t c8_rule;           /* the rule (1 or 2) the pass's n_c8 is counted under */
+    int32_t forced;            /* the host picked the kernels: no decision on the device */
+    int32_t left_listing;      /* the record pass lists the leftover pairs for the companion */
+    int32_t companion_left_out; /* the previous pass had no pair for the companion: it is not launched, and the caller repeats the
+                                  pass if this one has such a pair after all */
+    int32_t team_mode;         /* team / companion form: 0 Hellinger-2 with unit weights, 1 with category weights, 2 Kolmogorov-Smirnov */
+    int32_t plain_mode;        /* plain / wide form: 0 Hellinger-2 unit weights, 1 Hellinger-2 category weights, 2 generic distance */
+    int32_t ldstab;            /* the plain family keeps its square-root tables in LDS (environments of at most 512 points) */
+    int32_t fmode;             /* 0 the keys are F values, 1 inline CDFs only, 2 any CDF */
+    int32_t wide_long;         /* wide family: a stride beyond 65535 points asks for its 64-bit-count form */
+} lchd_sweep_plan;
+/* Which sweep kernels a from_primitives pass launches, as a pure function (no context, no device).  Returns LCHD_OK, or LCHD_EVALUE
+ * (null argument, n_pairs < 1, n_categories < 1).  The planner checks its own answer: a launch set that would not give every pair
+ * exactly one kernel is LCHD_EDEVICE (an internal error; no input is known to produce it). */
+int lchd_plan_sweep(const lchd_sweep_query *query, lchd_sweep_plan *plan_out);
+/* What the sweep of the most recent from_primitives call did, for its last pass (the one whose scores stand).  *plan_out: what
+ * lchd_plan_sweep answered for it.  stats_out[0 .. 3]: pairs of at most 240 merged events (unusable pairs included), pairs of c8_rule
+ * (likewise), the largest environment (points) -- as the record pass published them -- and the usable pairs the rule in force leaves
+ * to the companion (n_pairs minus the count of that rule; -1 without a rule in force); all -1 where no record pass ran (the inline
+ * family).  *rule_out: the rule in force (-1, 0, 1, 2) worked out from those counts by the inequalities the kernels evaluate; -1 where
+ * the plan has no team / 8-bit family.  *repeated_out: 1 if the pass repeated one whose companion had been left out.  Any output
+ * pointer may be null.  Returns 0, or -1 where lchd_ctx_last_grid returns -1: before the first call, while an asynchronous pass is pending,
+ * after a from_primitives call that failed or re-scored overflowed environments in a second pass, after a call of another entry point
+ * (from_coords, from_dmxs, from_anchors, the ensembles).  One difference: the record is host data, so a host-pointer
+ * lchd_from_primitives / lchd_group_from_primitives call (after which the grid is no longer reported) keeps it. */
+int lchd_ctx_last_sweep(lchd_ctx *ctx, lchd_sweep_plan *plan_out, int64_t stats_out[4], int32_t *rule_out, int32_t *repeated_out);
 /* 1 if the most recent from_coords / from_dmxs call of the context ran the fused sort + sweep kernel (one launch per
  * call, nothing but the scores written: Hellinger-2, unit category weights, at most 16 categories, rows of 1 025 .. 20 480
  * points), 0 if it ran the row sort followed by the sweep (src/locohd.rs:410-476 either way). */

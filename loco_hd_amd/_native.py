@@ -49,6 +49,29 @@ class ConfigC(C.Structure):
     ]
 
 
+class SweepQueryC(C.Structure):
+    """lchd_sweep_query: what the choice of sweep kernels depends on (include/loco_hd_hip.h)."""
+    _fields_ = [("n_pairs", C.c_int64), ("n_categories", C.c_int32), ("force_cmax", C.c_int32), ("hellinger2", C.c_int32),
+                ("unit_weights", C.c_int32), ("wf_pow", C.c_int32), ("sd_fast", C.c_int32), ("has_wf_index", C.c_int32),
+                ("has_left_list", C.c_int32), ("stride_a", C.c_int64), ("stride_b", C.c_int64), ("cdf_keys_a", C.c_int32),
+                ("cdf_keys_b", C.c_int32), ("pre_rows", C.c_int32), ("hint_bits", C.c_int32), ("hooks", C.c_uint32)]
+
+
+class SweepPlanC(C.Structure):
+    """lchd_sweep_plan: what a pass launches."""
+    _fields_ = [("families", C.c_uint32), ("slots", C.c_int32), ("pre", C.c_int32), ("small_rule", C.c_int32), ("second_rule", C.c_int32),
+                ("c8_rule", C.c_int32), ("forced", C.c_int32), ("left_listing", C.c_int32), ("companion_left_out", C.c_int32),
+                ("team_mode", C.c_int32), ("plain_mode", C.c_int32), ("ldstab", C.c_int32), ("fmode", C.c_int32), ("wide_long", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+# lchd_sweep_family / lchd_sweep_hook bits
+SWEEP_INLINE, SWEEP_TEAM240, SWEEP_TEAM480, SWEEP_C8, SWEEP_INDIRECT, SWEEP_PLAIN, SWEEP_INC, SWEEP_WIDE = (1 << k for k in range(8))
+HOOK_NO_DUO, HOOK_NO_COUNT8, HOOK_NO_C8_TEAM, HOOK_NO_INLINE_META, HOOK_FORCE_WIDE, HOOK_FORCE_GENERIC, HOOK_FORCE_BIGENV, HOOK_NO_SWEEP_HINT = (
+    1 << k for k in range(8))
+
 _DP, _IP, _LP, _VP = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_void_p
 _i32, _i64, _f64 = C.c_int32, C.c_int64, C.c_double
 
@@ -102,6 +125,8 @@ _PROTOS = {
     "lchd_ctx_last_env_points": (C.c_int64, [_VP]),
     "lchd_plan_grid": (C.c_int, [_DP, _DP, _i32, _f64, _i32, _IP, _DP, _LP]),
     "lchd_ctx_last_grid": (C.c_int, [_VP, _i32, _IP, _LP, _IP]),
+    "lchd_plan_sweep": (C.c_int, [C.POINTER(SweepQueryC), C.POINTER(SweepPlanC)]),
+    "lchd_ctx_last_sweep": (C.c_int, [_VP, C.POINTER(SweepPlanC), _LP, _IP, _IP]),
     "lchd_ctx_last_dense_fused": (C.c_int32, [_VP]),
     "lchd_ctx_set_deterministic": (C.c_int, [_VP, _i32]),
     "lchd_ctx_get_deterministic": (C.c_int32, [_VP]),

@@ -169,6 +169,13 @@ struct GridRecord {
     int64_t n_cells = 0;
     int32_t build = 0;
 };
+// What lchd_ctx_last_sweep reports: the plan launch_sweep followed, what k_pair_meta published about the pass's pairs, the rule in force.
+struct SweepRecord {
+    lchd_sweep_plan plan{};
+    int64_t stats[4] = {-1, -1, -1, -1};  // n_duo, n_c8, largest environment, pairs left to the companion
+    int32_t rule = -1;
+    int32_t repeated = 0;
+};
 
 // Calls on one context are serialised (include/loco_hd_hip.h, "Threads"): every entry point that takes a context holds it for its
 // whole duration (CtxLock below).  The owner may re-enter (lchd_from_primitives_dev is lchd_from_primitives_dev_async +
@@ -263,6 +270,8 @@ struct lchd_ctx {
         bool subset = false;                                // the enqueued pass IS a second pass over the pairs of overflowed environments
         bool per_pair = false;                              // the enqueued pass did not de-duplicate side B (slot p = pair p)
         GridRecord grid[2];                                 // grids and cell-list builds of the enqueued pass
+        lchd_sweep_plan plan{};                             // what launch_sweep launched for it
+        bool repeated = false;                              // the enqueued pass repeats one whose companion sweep had been left out
     } pend;
     // multi-GPU sharding helpers (lchd_shard_*): device state, host-mapped counts, the plan they belong to
     ShardState* d_shard = nullptr;
@@ -278,6 +287,8 @@ struct lchd_ctx {
     SweepArgs last{};
     bool last_valid = false;
     GridRecord last_grid[2];  // ... and its grids and cell-list builds (for lchd_ctx_last_grid)
+    SweepRecord last_sweep;   // ... and its sweep kernels (for lchd_ctx_last_sweep)
+    bool last_sweep_valid = false;  // (host data only: it outlives the I/O block of a host-pointer call, which last_valid does not)
 };
 
 struct Arena {
@@ -379,7 +390,7 @@ static int ensure_ws(lchd_ctx* ctx, size_t need) {
     if (ctx->ws) HIP_TRY(hipFree(ctx->ws));
     ctx->ws = nullptr;
     ctx->ws_cap = 0;
-    ctx->last_valid = false;
+    ctx->last_valid = ctx->last_sweep_valid = false;
     size_t got = need + need / 8 + (1 << 20);
     hipError_t e = hipMalloc(&ctx->ws, got);
     if (e != hipSuccess) {  // without the growth margin
@@ -513,6 +524,18 @@ extern "C" int lchd_ctx_last_grid(lchd_ctx* c, int32_t side, int32_t dims_out[3]
         if (dims_out) dims_out[k] = g.dim[k];
     if (n_cells_out) *n_cells_out = g.n_cells;
     if (build_out) *build_out = g.build;
+    return 0;
+}
+
+extern "C" int lchd_ctx_last_sweep(lchd_ctx* c, lchd_sweep_plan* plan_out, int64_t stats_out[4], int32_t* rule_out, int32_t* repeated_out) {
+    CTX_LOCK(c);
+    if (!c || !c->last_sweep_valid || c->pend.active) return -1;
+    const SweepRecord& r = c->last_sweep;
+    if (plan_out) *plan_out = r.plan;
+    for (int k = 0; k < 4; ++k)
+        if (stats_out) stats_out[k] = r.stats[k];
+    if (rule_out) *rule_out = r.rule;
+    if (repeated_out) *repeated_out = r.repeated;
     return 0;
 }
 
@@ -962,6 +985,14 @@ extern "C" int lchd_plan_grid(const double bbmin[3], const double bbmax[3], int3
     return LCHD_OK;
 }
 
+// Which sweep kernels a pass launches: plan_sweep (lchd_kernels.hip), the decision launch_sweep follows.
+extern "C" int lchd_plan_sweep(const lchd_sweep_query* query, lchd_sweep_plan* plan_out) {
+    if (!query || !plan_out) return fail(LCHD_EVALUE, "null argument");
+    if (query->n_pairs < 1 || query->n_categories < 1) return fail(LCHD_EVALUE, "lchd_plan_sweep: n_pairs >= 1 and n_categories >= 1 are required");
+    if (!plan_sweep(*query, *plan_out)) return fail(LCHD_EDEVICE, "lchd_plan_sweep: internal error: the launch set %u would not give every pair exactly one kernel", plan_out->families);
+    return LCHD_OK;
+}
+
 static GridPlan plan_grid(const lchd_cloud* cl, double thr, int reach) {
     GridPlan g{};
     int32_t dim[3];
@@ -1236,7 +1267,8 @@ static int prims_enqueue(lchd_ctx* c) {
         sw.left_zero = c->d_left + 32 * (c->left_slot ^ 1);
         sw.left_expected = P.subset ? n_pairs : c->last_left;
     }
-    P.sweep_info = launch_sweep(s, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, c->sweep_hint, sw);
+    P.sweep_info = launch_sweep(s, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, c->sweep_hint, sw, &P.plan);
+    if (P.sweep_info < 0) return fail(LCHD_EDEVICE, "internal error: the sweep launch set %u would not give every pair exactly one kernel", P.plan.families);
     if (P.sweep_info & 4) c->left_slot ^= 1;  // (the record pass ran and zeroed the other slot)
     mark(c, 4);
     if (a->ev_used) { HIP_TRY(hipEventRecord(a->ev_used, s)); a->used_valid = true; }
@@ -1253,7 +1285,7 @@ extern "C" int lchd_from_primitives_dev_async(lchd_ctx* c, lchd_cloud* a, lchd_c
     if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
     if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
     if (c->pend.active) return fail(LCHD_EVALUE, "a previous asynchronous call has not been finished (lchd_ctx_finish)");
-    c->last_valid = false;
+    c->last_valid = c->last_sweep_valid = false;
     if (n_pairs <= 0) return LCHD_OK;
     if (!d_anchors || !d_out) return fail(LCHD_EVALUE, "null anchor / score pointer");
     if (n_pairs > (int64_t)0x7FFFFFFF) return fail(LCHD_EUNSUPPORTED, "more than 2^31 - 1 anchor pairs in one call (%lld): split the list", (long long)n_pairs);
@@ -1268,6 +1300,7 @@ extern "C" int lchd_from_primitives_dev_async(lchd_ctx* c, lchd_cloud* a, lchd_c
     P.a = a; P.b = b; P.anchors = d_anchors; P.wf = d_wf_index; P.n_pairs = n_pairs; P.thr = thr; P.out = d_out;
     P.cap = c->cap_hint;
     P.subset = false;
+    P.repeated = false;
     c->last_store_bytes = 0;
     if (int rc = prims_enqueue(c)) return rc;
     P.active = true;
@@ -1358,9 +1391,30 @@ static int rescore_overflow_pairs(lchd_ctx* c, uint32_t f1, int64_t biggest, boo
     launch_scatter_scores(s, sub_out, sel.sel_index, (int64_t)n_sub, saved.out);
     HIP_TRY(hipStreamSynchronize(s));
     c->last_valid = false;  // (c->last would describe the first pass, whose arena the second one has reused)
+    c->last_sweep_valid = false;  // (... and the sweep record the second pass's selection)
     *flags_out = (f1 & ~ST_ENV_OVERFLOW) | f2;
     *handled = true;
     return LCHD_OK;
+}
+
+// The record of a finished pass: the counts are the words k_pair_meta published into the host-mapped mirror, the rule in force is
+// rule_in_force (lchd_sweep_common.h) evaluated here from the same counts.
+static SweepRecord sweep_record(const lchd_sweep_plan& plan, const HostStatus& h, int64_t n_pairs, bool repeated) {
+    SweepRecord r;
+    r.plan = plan;
+    r.repeated = repeated ? 1 : 0;
+    if (h.n_small == ~0ull) return r;  // (no record pass: the inline sweep counts nothing)
+    const unsigned long long P = (unsigned long long)n_pairs, n_duo = h.n_duo, n_c8 = h.n_c8;
+    if (plan.families & (LCHD_SWEEP_TEAM240 | LCHD_SWEEP_TEAM480 | LCHD_SWEEP_C8)) {
+        const unsigned long long n_small = plan.small_rule ? n_c8 : n_duo;
+        if (plan.forced || 2 * n_small >= P) r.rule = plan.small_rule;
+        else if (plan.second_rule && 2 * n_c8 >= P) r.rule = plan.second_rule;
+    }
+    r.stats[0] = (int64_t)n_duo;
+    r.stats[1] = (int64_t)n_c8;
+    r.stats[2] = (int64_t)h.max_env;
+    r.stats[3] = r.rule < 0 ? -1 : n_pairs - (int64_t)std::min(r.rule == 0 ? n_duo : n_c8, P);
+    return r;
 }
 
 // Waits for the enqueued pass and repeats it while the device asks for it (larger slots, the full launch set); *flags_out = the
@@ -1388,6 +1442,7 @@ static int finish_passes(lchd_ctx* c, uint32_t* flags_out) {
                     const unsigned long long taken = (P.sweep_info & 1) ? c->h_status->n_c8 : c->h_status->n_duo;
                     if (taken < (unsigned long long)P.n_pairs) {
                         c->sweep_hint &= ~(8 | 16);
+                        P.repeated = true;
                         if (int rc = prims_enqueue(c)) return rc;
                         continue;
                     }
@@ -1425,6 +1480,7 @@ static int finish_passes(lchd_ctx* c, uint32_t* flags_out) {
             const unsigned long long taken = (P.sweep_info & 1) ? c->h_status->n_c8 : c->h_status->n_duo;
             if (taken < (unsigned long long)P.n_pairs) {
                 c->sweep_hint &= ~(8 | 16);
+                P.repeated = true;
                 if (int rc = prims_enqueue(c)) return rc;
                 continue;
             }
@@ -1454,6 +1510,8 @@ static int finish_passes(lchd_ctx* c, uint32_t* flags_out) {
         c->last = P.sw;
         c->last_grid[0] = P.grid[0];
         c->last_grid[1] = P.grid[1];
+        c->last_sweep = sweep_record(P.plan, *c->h_status, P.n_pairs, P.repeated);
+        c->last_sweep_valid = true;
         c->last_valid = true;
         *flags_out = f;
         return LCHD_OK;
@@ -2298,7 +2356,8 @@ static int sweep_rows(lchd_ctx* c, const EnvStore& ea, const EnvStore& eb, const
     sw.n_pairs = rows;
     sw.out = d_out;
     sw.meta = d_meta;
-    (void)launch_sweep(c->stream, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, 0, sw);
+    if (launch_sweep(c->stream, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, 0, sw) < 0)
+        return fail(LCHD_EDEVICE, "internal error: the sweep launch set would not give every pair exactly one kernel");
     mark(c, 4);
     HIP_TRY(hipGetLastError());
     c->status_dirty = false;  // the record pass of this sequence resets the device status
@@ -2439,7 +2498,7 @@ static int dense_driver(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_
     CTX_GUARD(c);
     if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
     if (int rc = check_wf_index(cfg, wf_index, rows)) return rc;
-    c->last_valid = false;
+    c->last_valid = c->last_sweep_valid = false;
     if (rows == 0) return LCHD_OK;
     // utils.rs:25-39: the sort mask has row-length entries and indexes seq => a row longer than seq panics
     if (cols_a > len_seq_a || cols_b > len_seq_b) return fail(LCHD_EPANIC, "index out of bounds: a distance row is longer than its seq");
@@ -2512,7 +2571,7 @@ extern "C" int lchd_from_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, c
     if (a->sid || b->sid) return fail(LCHD_EVALUE, "from_coords takes single structures, not batches");
     if (a->n != b->n)  // src/locohd.rs:420-428 via :472-475
         return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)a->n, (long long)b->n);
-    c->last_valid = false;
+    c->last_valid = c->last_sweep_valid = false;
     if (a->n == 0) return LCHD_OK;
     if (!d_out) return fail(LCHD_EVALUE, "null score pointer");
     if (a->n > 65535 && (c->h_cfg.n_categories > kMaxCategories || a->n > (1 << 23)))
@@ -2574,7 +2633,7 @@ extern "C" int lchd_from_anchors(lchd_ctx* c, const lchd_config* cfg, const int3
     CTX_GUARD(c);
     if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
     if (wf_index < 0 || wf_index >= cfg->n_weight_functions) return fail(LCHD_EVALUE, "weight-function index out of range");
-    c->last_valid = false;
+    c->last_valid = c->last_sweep_valid = false;
     // src/locohd.rs:70-77
     if (len_seq_a != len_dists_a || len_seq_b != len_dists_b) return fail(LCHD_EVALUE, "Lists seq and dists must have equal lengths!");
     if (len_seq_a == 0 || len_seq_b == 0) return fail(LCHD_EPANIC, "index out of bounds: the len is 0 but the index is 0");
@@ -2694,7 +2753,8 @@ static int ens_sweep(lchd_ctx* c, const EnvStore& st, const int64_t* anchors, co
     sw.n_pairs = q;
     sw.out = out;
     sw.meta = meta;
-    (void)launch_sweep(c->stream, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, 0, sw);
+    if (launch_sweep(c->stream, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, 0, sw) < 0)
+        return fail(LCHD_EDEVICE, "internal error: the sweep launch set would not give every pair exactly one kernel");
     HIP_TRY(hipGetLastError());
     c->status_dirty = false;  // the record pass resets the device status
     uint32_t f = 0;
@@ -2706,7 +2766,7 @@ static int ens_sweep(lchd_ctx* c, const EnvStore& st, const int64_t* anchors, co
 static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, const std::vector<int32_t>& pairs, const int32_t* d_wf,
                          double* d_out) {
     const int64_t P = (int64_t)pairs.size() / 2;
-    c->last_valid = false;
+    c->last_valid = c->last_sweep_valid = false;
     c->last_dense_fused = false;
     if (P == 0 || n == 0) return LCHD_OK;
     const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
@@ -2971,7 +3031,7 @@ extern "C" int lchd_ensemble_from_coords(lchd_ctx* c, const lchd_config* cfg, co
     if (!pairs && n_pairs != P)
         return fail(LCHD_EVALUE, "without a pair list the call scores all %lld pairs i < j of %lld structures (got n_pairs = %lld)", (long long)P,
                     (long long)n_struct, (long long)n_pairs);
-    c->last_valid = false;
+    c->last_valid = c->last_sweep_valid = false;
     if (P == 0 || n == 0) return LCHD_OK;
     if (!(excl_start == nullptr) != !(excl_idx == nullptr)) return fail(LCHD_EVALUE, "the exclusion list needs both its row starts and its column indices");
     std::vector<int32_t> cat((size_t)(n_struct * n)), sid((size_t)(n_struct * n));
@@ -3010,7 +3070,7 @@ extern "C" int lchd_ensemble_from_dmxs(lchd_ctx* c, const lchd_config* cfg, cons
     if (!pairs && n_pairs != P)
         return fail(LCHD_EVALUE, "without a pair list the call scores all %lld pairs i < j of %lld structures (got n_pairs = %lld)", (long long)P,
                     (long long)n_struct, (long long)n_pairs);
-    c->last_valid = false;
+    c->last_valid = c->last_sweep_valid = false;
     if (P == 0 || n == 0) return LCHD_OK;
     std::vector<int32_t> hp((size_t)P * 2);
     if (pairs) {

@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct lchd_sweep_query;  // include/loco_hd_hip.h
+struct lchd_sweep_plan;
+
 namespace lchd {
 
 constexpr int kMaxCategories = 255;   // categories travel as u8 on the device ...
@@ -350,8 +353,10 @@ struct SweepArgs {
 // launch for the larger pairs is left out.  Returns 1 (the "small" rule of this pass was the 8-bit-count one) | 2 (the companion
 // launch was left out: the caller must check this pass's counts, HostStatus::n_duo / n_c8 against the number of pairs) | 4 (k_pair_meta
 // ran with the leftover-list counters of `a`: the caller swaps the two counter slots for the next pass).
+// plan_sweep is the decision alone (lchd_plan_sweep); launch_sweep launches what it returns and, if asked, hands the plan back.
+bool plan_sweep(const lchd_sweep_query& q, lchd_sweep_plan& p);  // false: the set would not give every pair exactly one kernel (unreachable); launch_sweep then launches nothing and returns -1
 int launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinger2, bool unit_weights, bool wf_pow, int sweep_hint,
-                 const SweepArgs& a);
+                 const SweepArgs& a, lchd_sweep_plan* plan_out = nullptr);
 // Kullback-Leibler / Renyi in O(1) per event (lchd_sweep_inc.hip): unit weights, CDF-keyed environments of at most 512 points, tiny eps;
 // reads the pair records of k_pair_meta.  kind: SweepArgs::sd_fast.
 void launch_sweep_inc(hipStream_t s, int kind, int cmax, const SweepArgs& a);

@@ -22,6 +22,7 @@
 #include <type_traits>
 #include <cstdlib>
 
+#include "../../include/loco_hd_hip.h"
 #include "lchd_sweep_common.h"
 
 namespace lchd {
@@ -115,26 +116,168 @@ __global__ void k_pair_meta(SweepArgs args) {
     }
 }
 
+// Which sweep kernels take a pass: a pure function of the configuration, the call's size and the previous pass's pair statistics
+// (lchd_plan_sweep, include/loco_hd_hip.h).  launch_sweep below launches exactly what this returns.
+static int slots_of(int cmax) { return cmax <= 8 ? 8 : cmax <= 12 ? 12 : cmax <= 16 ? 16 : cmax <= 20 ? 20 : cmax <= 24 ? 24 : cmax <= 28 ? 28 : 32; }
+static void plan_sweep_families(const lchd_sweep_query& q, lchd_sweep_plan& p) {
+    p = lchd_sweep_plan{};
+    const bool no_duo = q.hooks & LCHD_HOOK_NO_DUO, no_count8 = q.hooks & LCHD_HOOK_NO_COUNT8, no_c8_team = q.hooks & LCHD_HOOK_NO_C8_TEAM,
+               no_inline_meta = q.hooks & LCHD_HOOK_NO_INLINE_META, force_wide = q.hooks & LCHD_HOOK_FORCE_WIDE,
+               force_generic = q.hooks & LCHD_HOOK_FORCE_GENERIC, force_bigenv = q.hooks & LCHD_HOOK_FORCE_BIGENV,
+               no_sweep_hint = q.hooks & LCHD_HOOK_NO_SWEEP_HINT;
+    const bool unit_weights = q.unit_weights != 0, wf_pow = q.wf_pow != 0;
+    const bool hellinger2 = q.hellinger2 != 0 && !force_generic;  // (force_generic: test hook)
+    const int n_categories = q.n_categories;
+    const int cmax = std::max(n_categories, q.force_cmax);  // (force_cmax: test hook)
+    const bool small = q.stride_a <= kSqrtTab && q.stride_b <= kSqrtTab && !force_bigenv;  // every count fits the LDS tables
+    const bool keyed = q.cdf_keys_a && q.cdf_keys_b;
+    p.slots = slots_of(cmax);
+    p.c8_rule = 2;
+    p.plain_mode = !hellinger2 ? MODE_GEN : (unit_weights ? MODE_H2U : MODE_H2W);
+    p.fmode = keyed ? F_KEY : (wf_pow ? F_ANY : F_FAST);
+    if (q.n_pairs <= kInlineMetaPairs && !no_inline_meta && hellinger2 && unit_weights && n_categories <= 32 && !force_wide && keyed && small) {
+        // small call, default configuration: one launch (records worked out by the sweep itself, one pair per wavefront)
+        p.families = LCHD_SWEEP_INLINE;
+        p.ldstab = 1;
+        return;
+    }
+    const bool wide = n_categories > 32 || force_wide || q.stride_a > 65535 || q.stride_b > 65535;  // (long environments: the 64-bit-count form of the wide sweep)
+    // Two kernels for "small" pairs exist for the default configuration (Hellinger-2, unit weights, CDF-keyed environments):
+    // k_sweep_duo (two pairs of <= 240 merged events per wavefront, <= 16 category slots) and the 8-bit-count k_sweep (both
+    // environments <= 255 points, more than 16 slots); the INDIRECT 16-bit k_sweep takes what they leave over.
+    // ... and, up to 16 slots, for category weights other than 1 (the WGT instantiations of the team kernels; the one-pair-per-wavefront
+    // 8-bit-count sweep has no weighted form, so both team rules must be available)
+    const bool weighted_team = !unit_weights && cmax <= 16 && !no_duo && !no_c8_team && !no_count8;
+    // ... and for the Kolmogorov-Smirnov distance with unit weights (sd_fast == 3: the KSM instantiations)
+    const bool ks_team = !hellinger2 && q.sd_fast == 3 && unit_weights && cmax <= 16 && !no_duo && !no_c8_team && !no_count8 && !force_generic;
+    const bool fast_cfg = !wide && ((hellinger2 && (unit_weights || weighted_team)) || ks_team) && small && p.fmode == F_KEY;  // (F_KEY with a weight-function dictionary: the store holds one key set per function)
+    // hint_bits (what k_pair_meta counted in the previous pass of this configuration): 0 = nothing known, else
+    // 4 | (pairs of <= 240 events were the majority ? 1 : 0) | (pairs with both environments <= 255 points were ? 2 : 0).
+    // Up to 16 slots k_sweep_duo is the first choice and the 8-bit-count sweep the second (C2a: environments of ~170 points,
+    // pairs of ~340 events -- too long for a 32-lane tile, but their counts fit 8 bits: 2 count words per side instead of 3);
+    // above 16 slots only the 8-bit-count sweep exists.
+    const int hint_bits = no_sweep_hint ? 0 : q.hint_bits;
+    const bool known = (hint_bits & 4) != 0, duo_major = (hint_bits & 1) != 0, c8_major = (hint_bits & 2) != 0;
+    const bool c8_small_slots = fast_cfg && cmax <= 16 && !no_count8 && known && !(duo_major && !no_duo) && c8_major;
+    const bool use_duo = fast_cfg && cmax <= 16 && !no_duo && !c8_small_slots;
+    const bool use_c8 = fast_cfg && !no_count8 && (cmax > 16 || c8_small_slots);
+    // up to 16 slots the 8-bit-count pairs are swept two per wavefront (rule 2: and at most 480 merged events)
+    const bool team_ok = !no_c8_team && cmax <= 32;
+    const bool c8_team = use_c8 && team_ok;
+    p.c8_rule = team_ok ? 2 : 1;  // (what k_pair_meta counts as n_c8 -- whichever small-pair kernel this pass uses)
+    p.small_rule = use_c8 ? p.c8_rule : 0;
+    // no hint and up to 16 slots: k_sweep_duo's rule first, the two-pairs-per-wavefront 8-bit-count rule second
+    p.second_rule = (!known && use_duo && fast_cfg && !no_count8 && !no_c8_team) ? 2 : 0;
+    const int hint = !known ? 0 : ((use_c8 ? c8_major : duo_major) ? 1 : 2);
+    // ... | 8 (EVERY pair of the previous pass had at most 240 events) | 16 (... both environments <= 255 points): the companion
+    // launch for the larger pairs would find nothing to do and is left out; the host checks the counts of THIS pass afterwards
+    // and repeats it with the full launch set if a larger pair turned up after all
+    const bool team_cfg = !wide && (use_duo || use_c8);
+    const bool no_others = team_cfg && hint == 1 && (hint_bits & (use_c8 ? 16 : 8)) != 0;
+    // the leftover list: only where the rule is known at launch and a companion will read it (otherwise the device decides the rule
+    // from this very record pass and the companion scans the records)
+    p.left_listing = (q.has_left_list && team_cfg && hint == 1 && !no_others) ? 1 : 0;
+    p.companion_left_out = no_others ? 1 : 0;
+    if (wide) {
+        p.families = LCHD_SWEEP_WIDE;
+        p.slots = 0;
+        p.fmode = keyed ? F_KEY : F_ANY;
+        p.wide_long = (q.stride_a > 65535 || q.stride_b > 65535) ? 1 : 0;
+        return;
+    }
+    // (team mode: 0 Hellinger-2 with unit weights, 1 with category weights, 2 Kolmogorov-Smirnov with unit weights)
+    p.team_mode = ks_team ? 2 : (unit_weights ? 0 : 1);
+    if (team_cfg) {
+        // Without a hint the small-pair kernel, its companion and the plain sweep are all launched and the number of small
+        // pairs (k_pair_meta) decides on the device which of them do the work; with the hint of the previous pass only the
+        // kernels that will work are launched.
+        p.forced = hint != 0;
+        if (hint != 2) {
+            // the four-pairs team kernel, the INDIRECT companion for the pairs its rule leaves over and -- a pass without a hint --
+            // the second team rule's kernel; or the 8-bit-count rule's kernel (two pairs per wavefront, else one) and its companion
+            p.families |= use_duo ? LCHD_SWEEP_TEAM240 : (c8_team ? LCHD_SWEEP_TEAM480 : LCHD_SWEEP_C8);
+            if (use_duo && p.second_rule) p.families |= LCHD_SWEEP_TEAM480;
+            if (!no_others) p.families |= LCHD_SWEEP_INDIRECT;
+            // both stores carry prefix-count rows of the width this slot count reads (k_env_group wrote them): the PRE instantiations
+            p.pre = ((use_duo || c8_team) && p.team_mode != 1 && cmax <= 16 && q.pre_rows) ? 1 : 0;
+            if (hint == 1) { p.ldstab = 1; return; }
+        }
+    }
+    if (!hellinger2 && (q.sd_fast == 1 || q.sd_fast == 2) && unit_weights && small && p.fmode == F_KEY && !q.has_wf_index && cmax <= 32) {
+        p.families |= LCHD_SWEEP_INC;
+        p.slots = cmax <= 8 ? 8 : cmax <= 12 ? 12 : cmax <= 16 ? 16 : cmax <= 24 ? 24 : 32;  // (launch_sweep_inc's ladder)
+    } else {
+        p.families |= LCHD_SWEEP_PLAIN;
+    }
+    p.ldstab = (hellinger2 && small) ? 1 : 0;
+}
+bool plan_sweep(const lchd_sweep_query& q, lchd_sweep_plan& p) {
+    plan_sweep_families(q, p);
+    // Every pair must have exactly one taker.  Inline and wide stand alone.  The families that answer to a rule (at most two, one per
+    // rule) come with the companion -- or with the caller's promise to repeat the pass --; a pass the host picked has them or an
+    // all-pairs family, never both; a pass the device decides has them, the companion and the plain family (the only all-pairs
+    // family that steps back when a rule is in force).
+    const uint32_t f = p.families, ruled = f & (LCHD_SWEEP_TEAM240 | LCHD_SWEEP_TEAM480 | LCHD_SWEEP_C8),
+                   all_pairs = f & (LCHD_SWEEP_INLINE | LCHD_SWEEP_WIDE | LCHD_SWEEP_PLAIN | LCHD_SWEEP_INC);
+    const bool companion = (f & LCHD_SWEEP_INDIRECT) != 0, one_all = all_pairs != 0 && (all_pairs & (all_pairs - 1)) == 0;
+    const uint32_t of_small = p.small_rule == 0 ? LCHD_SWEEP_TEAM240 : (p.small_rule == 2 ? LCHD_SWEEP_TEAM480 : LCHD_SWEEP_C8);
+    bool ok;
+    if (!ruled) ok = one_all && !companion && !p.companion_left_out;
+    else if (p.forced) ok = !all_pairs && ruled == of_small && companion != (p.companion_left_out != 0);
+    else ok = all_pairs == LCHD_SWEEP_PLAIN && companion && !p.companion_left_out && (p.second_rule == 0 || (p.second_rule == 2 && p.small_rule != 2)) &&
+              ruled == (of_small | (p.second_rule ? (uint32_t)LCHD_SWEEP_TEAM480 : 0u));
+    return ok;  // (false: unreachable -- tests/test_sweep_plan.py enumerates the planner's inputs; the callers report an internal error)
+}
+
 // workgroups of the INDIRECT companion sweep (it walks every pair record and sweeps the few the team kernel left)
 // (measured: 1024 -> 2048: C2a 19.4 -> 16.6 us, C4 47.3 -> 37.3 us per pass; 4096: no further gain)
 constexpr unsigned kCompanionGrid = 2048u;
 int launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinger2, bool unit_weights, bool wf_pow, int sweep_hint,
-                 const SweepArgs& a_in) {
+                 const SweepArgs& a_in, lchd_sweep_plan* plan_out) {
+    if (plan_out) *plan_out = lchd_sweep_plan{};
     if (a_in.n_pairs <= 0) return 0;
     SweepArgs a = a_in;
-    a.duo_enabled = 0;
-    a.forced = 0;
+    lchd_sweep_query q{};
+    q.n_pairs = a.n_pairs;
+    q.n_categories = n_categories;
+    q.force_cmax = t.force_cmax;
+    q.hellinger2 = hellinger2;
+    q.unit_weights = unit_weights;
+    q.wf_pow = wf_pow;
+    q.sd_fast = a.sd_fast;
+    q.has_wf_index = a.wf_index != nullptr;
+    q.has_left_list = a.left_list && a.left_count;
+    q.stride_a = a.env_a.stride;
+    q.stride_b = a.env_b.stride;
+    q.cdf_keys_a = a.env_a.cdf_keys;
+    q.cdf_keys_b = a.env_b.cdf_keys;
+    const int cmax = std::max(n_categories, t.force_cmax);
+    {
+        const int nw = team_pre_words(cmax);
+        q.pre_rows = cmax <= 16 && a.env_a.pre && a.env_b.pre && a.env_a.pre_words == nw && a.env_b.pre_words == nw;
+    }
+    q.hint_bits = sweep_hint;
+    q.hooks = (t.no_duo ? LCHD_HOOK_NO_DUO : 0) | (t.no_count8 ? LCHD_HOOK_NO_COUNT8 : 0) | (t.no_c8_team ? LCHD_HOOK_NO_C8_TEAM : 0) |
+              (t.no_inline_meta ? LCHD_HOOK_NO_INLINE_META : 0) | (t.force_wide ? LCHD_HOOK_FORCE_WIDE : 0) |
+              (t.force_generic ? LCHD_HOOK_FORCE_GENERIC : 0) | (t.force_bigenv ? LCHD_HOOK_FORCE_BIGENV : 0) |
+              (t.no_sweep_hint ? LCHD_HOOK_NO_SWEEP_HINT : 0);
+    lchd_sweep_plan p;
+    const bool covered = plan_sweep(q, p);
+    if (plan_out) *plan_out = p;
+    if (!covered) return -1;  // (nothing launched)
+    const uint32_t fam = p.families;
+    a.duo_enabled = (fam & (LCHD_SWEEP_TEAM240 | LCHD_SWEEP_TEAM480 | LCHD_SWEEP_C8)) ? 1 : 0;
+    a.forced = p.forced;
     a.gen_tab = unit_weights ? 1 : 0;  // (MODE_GEN, Hellinger with a general exponent: the configuration's power tables apply)
-    if (t.force_generic) hellinger2 = false;  // test hook
-    if (a.n_pairs <= kInlineMetaPairs && !t.no_inline_meta && hellinger2 && unit_weights && n_categories <= 32 && !t.force_wide &&
-        a.env_a.cdf_keys && a.env_b.cdf_keys && a.env_a.stride <= kSqrtTab && a.env_b.stride <= kSqrtTab && !t.force_bigenv) {
-        // small call, default configuration: one launch (records worked out by the sweep itself, one pair per wavefront)
-        const int cm = std::max(n_categories, t.force_cmax);
+    a.c8_rule = p.c8_rule;
+    a.small_rule = p.small_rule;
+    a.second_rule = p.second_rule;
+    a.left_listing = p.left_listing;
+    if (fam & LCHD_SWEEP_INLINE) {
         const unsigned g = (unsigned)((a.n_pairs + kSweepWaves - 1) / kSweepWaves);
-        launch_sweep_inline(s, cm, g, a);
+        launch_sweep_inline(s, cmax, g, a);
         return 0;
     }
-    const bool wide = n_categories > 32 || t.force_wide || a.env_a.stride > 65535 || a.env_b.stride > 65535;  // (long environments: the 64-bit-count form of the wide sweep)
     const int64_t blocks = (a.n_pairs + kSweepWaves - 1) / kSweepWaves;
     // grid-stride: LDS tables are built once per block.  8192 workgroups = 8 rounds of the 1024 that are resident at a time: finer
     // than that the table loads show, coarser the last round's imbalance does (measured on C2a: 4096 +2.8 %, 16384 +0.5 %)
@@ -145,102 +288,44 @@ int launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinge
     // 0.214 -> 0.200 ms; the same cap on the 10^6-pair launches costs 1-5 %: C4 sweep 2.69 -> 2.83 ms)
     const int64_t tcap_big = 16384, tcap_small = 4096, tcap_switch = 32768;
     const unsigned grid = (unsigned)(blocks < gcap ? blocks : gcap);
-    const int cmax = std::max(n_categories, t.force_cmax);  // (force_cmax: test hook)
-    const bool small = a.env_a.stride <= kSqrtTab && a.env_b.stride <= kSqrtTab && !t.force_bigenv;  // every count fits the LDS tables
-    const int fmode = (a.env_a.cdf_keys && a.env_b.cdf_keys) ? F_KEY : (wf_pow ? F_ANY : F_FAST);
-    // Two kernels for "small" pairs exist for the default configuration (Hellinger-2, unit weights, CDF-keyed environments):
-    // k_sweep_duo (two pairs of <= 240 merged events per wavefront, <= 16 category slots) and the 8-bit-count k_sweep (both
-    // environments <= 255 points, more than 16 slots); the INDIRECT 16-bit k_sweep takes what they leave over.
-    // ... and, up to 16 slots, for category weights other than 1 (the WGT instantiations of the team kernels; the one-pair-per-wavefront
-    // 8-bit-count sweep has no weighted form, so both team rules must be available)
-    const bool weighted_team = !unit_weights && cmax <= 16 && !t.no_duo && !t.no_c8_team && !t.no_count8;
-    // ... and for the Kolmogorov-Smirnov distance with unit weights (SweepArgs::sd_fast == 3: the KSM instantiations)
-    const bool ks_team = !hellinger2 && a.sd_fast == 3 && unit_weights && cmax <= 16 && !t.no_duo && !t.no_c8_team && !t.no_count8 && !t.force_generic;
-    const bool fast_cfg = !wide && ((hellinger2 && (unit_weights || weighted_team)) || ks_team) && small && fmode == F_KEY;  // (F_KEY with a weight-function dictionary: the store holds one key set per function)
-    // sweep_hint (what k_pair_meta counted in the previous pass of this configuration): 0 = nothing known, else
-    // 4 | (pairs of <= 240 events were the majority ? 1 : 0) | (pairs with both environments <= 255 points were ? 2 : 0).
-    // Up to 16 slots k_sweep_duo is the first choice and the 8-bit-count sweep the second (C2a: environments of ~170 points,
-    // pairs of ~340 events -- too long for a 32-lane tile, but their counts fit 8 bits: 2 count words per side instead of 3);
-    // above 16 slots only the 8-bit-count sweep exists.
-    const int hint_bits = t.no_sweep_hint ? 0 : sweep_hint;
-    const bool known = (hint_bits & 4) != 0, duo_major = (hint_bits & 1) != 0, c8_major = (hint_bits & 2) != 0;
-    const bool c8_small_slots = fast_cfg && cmax <= 16 && !t.no_count8 && known && !(duo_major && !t.no_duo) && c8_major;
-    const bool use_duo = fast_cfg && cmax <= 16 && !t.no_duo && !c8_small_slots;
-    const bool use_c8 = fast_cfg && !t.no_count8 && (cmax > 16 || c8_small_slots);
-    // up to 16 slots the 8-bit-count pairs are swept two per wavefront (rule 2: and at most 480 merged events)
-    const bool team_ok = !t.no_c8_team && cmax <= 32;
-    const bool c8_team = use_c8 && team_ok;
-    a.c8_rule = team_ok ? 2 : 1;  // (what k_pair_meta counts as n_c8 -- whichever small-pair kernel this pass uses)
-    a.small_rule = use_c8 ? a.c8_rule : 0;
-    // no hint and up to 16 slots: k_sweep_duo's rule first, the two-pairs-per-wavefront 8-bit-count rule second
-    a.second_rule = (!known && use_duo && fast_cfg && !t.no_count8 && !t.no_c8_team) ? 2 : 0;
-    const int hint = !known ? 0 : ((use_c8 ? c8_major : duo_major) ? 1 : 2);
-    // ... | 8 (EVERY pair of the previous pass had at most 240 events) | 16 (... both environments <= 255 points): the companion
-    // launch for the larger pairs would find nothing to do and is left out; the host checks the counts of THIS pass afterwards
-    // and repeats it with the full launch set if a larger pair turned up after all (the returned bit 2 says the launch was left out)
-    const bool no_others = hint == 1 && (hint_bits & (use_c8 ? 16 : 8)) != 0;
-    // the leftover list: only where the rule is known at launch and a companion will read it (otherwise the device decides the rule
-    // from this very record pass and the companion scans the records)
-    a.left_listing = (a.left_list && a.left_count && !wide && (use_duo || use_c8) && hint == 1 && !no_others) ? 1 : 0;
-    const int info = (use_c8 ? 1 : 0) | (no_others ? 2 : 0) | (a.left_zero ? 4 : 0);
+    // returned: 1 (the "small" rule of this pass was the 8-bit-count one) | 2 (the companion launch was left out) | 4 (the record pass ran
+    // with the leftover-list counters)
+    const int info = (p.small_rule ? 1 : 0) | (p.companion_left_out ? 2 : 0) | (a.left_zero ? 4 : 0);
     {
         const int64_t nb = (a.n_pairs + 255) / 256;
         const int mgrid = (int)(nb < kMetaPartials ? nb : kMetaPartials);
         k_pair_meta<<<mgrid, 256, 0, s>>>(a);
     }
-    if (wide) {
-        const int fm = (a.env_a.cdf_keys && a.env_b.cdf_keys) ? F_KEY : F_ANY;
-        launch_sweep_wide(s, !hellinger2 ? MODE_GEN : (unit_weights ? MODE_H2U : MODE_H2W), n_categories, a.n_pairs, fm, a);
+    if (fam & LCHD_SWEEP_WIDE) {
+        launch_sweep_wide(s, p.plain_mode, n_categories, a.n_pairs, p.fmode, a);
         return info & 4;
     }
-    if (use_duo || use_c8) {
-        // Without a hint the small-pair kernel, its companion and the plain sweep are all launched and the number of small
-        // pairs (k_pair_meta) decides on the device which of them do the work; with the hint of the previous pass only the
-        // kernels that will work are launched.
-        a.forced = hint != 0;
-        if (hint != 2) {
-            a.duo_enabled = 1;
-            unsigned bgrid = grid < kCompanionGrid ? grid : kCompanionGrid;  // the listed (larger) pairs are a minority whenever this launch does anything
-            if (a.left_listing) {  // one wavefront per listed pair, sized from what the previous pass left over (a grid-stride loop: any grid is correct)
-                const int64_t want = (a.left_expected + a.left_expected / 4 + kSweepWaves - 1) / kSweepWaves + 8;
-                bgrid = (unsigned)std::min<int64_t>(bgrid, std::max<int64_t>(want, 16));
-            }
-            // (team mode: 0 Hellinger-2 with unit weights, 1 with category weights, 2 Kolmogorov-Smirnov with unit weights)
-            const int tm = ks_team ? 2 : (unit_weights ? 0 : 1);
-            if (use_duo) {
-                constexpr int kTeamPairs = (64 / kDuoTL) * kSweepWaves;  // pairs per workgroup and round
-                const int64_t dblocks = (a.n_pairs + kTeamPairs - 1) / kTeamPairs;
-                const int64_t tcap = dblocks <= tcap_switch ? tcap_small : tcap_big;
-                const unsigned dgrid = (unsigned)(dblocks < tcap ? dblocks : tcap);
-                const int64_t tblocks = (a.n_pairs + 2 * kSweepWaves - 1) / (2 * kSweepWaves);
-                const int64_t tcap2 = tblocks <= tcap_switch ? tcap_small : tcap_big;
-                const unsigned tgrid = (unsigned)(tblocks < tcap2 ? tblocks : tcap2);
-                // the four-pairs team kernel, the INDIRECT companion for the pairs its rule leaves over and -- a pass without a hint --
-                // the second team rule's kernel
-                launch_team(s, cmax, tm, true, dgrid, a);
-                if (!no_others) launch_sweep_indirect(s, cmax, tm, bgrid, a);
-                if (a.second_rule) launch_team(s, cmax, tm, false, tgrid, a);
-            } else if (c8_team) {
-                constexpr int kTeamPairs = 2 * kSweepWaves;
-                const int64_t dblocks = (a.n_pairs + kTeamPairs - 1) / kTeamPairs;
-                const int64_t tcap = dblocks <= tcap_switch ? tcap_small : tcap_big;
-                const unsigned dgrid = (unsigned)(dblocks < tcap ? dblocks : tcap);
-                launch_team(s, cmax, tm, false, dgrid, a);
-                if (!no_others) launch_sweep_indirect(s, cmax, tm, bgrid, a);
-            } else {
-                launch_sweep_c8(s, cmax, grid, a);
-                if (!no_others) launch_sweep_indirect(s, cmax, 0, bgrid, a);
-            }
-            if (hint == 1) return info;
-        }
+    const int tm = p.team_mode;
+    unsigned bgrid = grid < kCompanionGrid ? grid : kCompanionGrid;  // the listed (larger) pairs are a minority whenever this launch does anything
+    if (a.left_listing) {  // one wavefront per listed pair, sized from what the previous pass left over (a grid-stride loop: any grid is correct)
+        const int64_t want = (a.left_expected + a.left_expected / 4 + kSweepWaves - 1) / kSweepWaves + 8;
+        bgrid = (unsigned)std::min<int64_t>(bgrid, std::max<int64_t>(want, 16));
     }
-    if (!hellinger2) {
-        if ((a.sd_fast == 1 || a.sd_fast == 2) && unit_weights && small && fmode == F_KEY && !a.wf_index && cmax <= 32) launch_sweep_inc(s, a.sd_fast, cmax, a);
-        else launch_sweep_plain(s, MODE_GEN, false, cmax, grid, fmode, a);
-    } else {
-        launch_sweep_plain(s, unit_weights ? MODE_H2U : MODE_H2W, small, cmax, grid, fmode, a);
+    const int64_t tblocks = (a.n_pairs + 2 * kSweepWaves - 1) / (2 * kSweepWaves);  // (two pairs per wavefront)
+    const int64_t tcap2 = tblocks <= tcap_switch ? tcap_small : tcap_big;
+    const unsigned tgrid = (unsigned)(tblocks < tcap2 ? tblocks : tcap2);
+    // launch order: the first rule's kernel, the companion, the second rule's kernel, the all-pairs kernel
+    if (fam & LCHD_SWEEP_TEAM240) {
+        constexpr int kTeamPairs = (64 / kDuoTL) * kSweepWaves;  // pairs per workgroup and round
+        const int64_t dblocks = (a.n_pairs + kTeamPairs - 1) / kTeamPairs;
+        const int64_t tcap = dblocks <= tcap_switch ? tcap_small : tcap_big;
+        const unsigned dgrid = (unsigned)(dblocks < tcap ? dblocks : tcap);
+        launch_team(s, cmax, tm, true, p.pre != 0, dgrid, a);
+    } else if (fam & LCHD_SWEEP_TEAM480) {
+        launch_team(s, cmax, tm, false, p.pre != 0, tgrid, a);
+    } else if (fam & LCHD_SWEEP_C8) {
+        launch_sweep_c8(s, cmax, grid, a);
     }
-    return info & 5;
+    if (fam & LCHD_SWEEP_INDIRECT) launch_sweep_indirect(s, cmax, (fam & LCHD_SWEEP_C8) ? 0 : tm, bgrid, a);
+    if ((fam & LCHD_SWEEP_TEAM240) && (fam & LCHD_SWEEP_TEAM480)) launch_team(s, cmax, tm, false, p.pre != 0, tgrid, a);
+    if (fam & LCHD_SWEEP_INC) launch_sweep_inc(s, a.sd_fast, cmax, a);
+    else if (fam & LCHD_SWEEP_PLAIN) launch_sweep_plain(s, p.plain_mode, p.ldstab != 0, cmax, grid, p.fmode, a);
+    return (fam & (LCHD_SWEEP_PLAIN | LCHD_SWEEP_INC)) ? (info & 5) : info;
 }
 
 // Kernels that may be launched with more than 64 KB of dynamic LDS need the limit raised per DEVICE: lchd_ctx_create calls this

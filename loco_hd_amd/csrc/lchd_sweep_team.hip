@@ -156,11 +156,10 @@ static void launch_team_c(hipStream_t s, bool tile240, unsigned grid, const Swee
     else k_sweep_duo<CM, 32, kTeam8Tile, WGT, KSM, PRE><<<grid, NTH, 0, s>>>(a);
 }
 template <int TM>
-static void launch_team_t(hipStream_t s, int cmax, bool tile240, unsigned grid, const SweepArgs& a) {
+static void launch_team_t(hipStream_t s, int cmax, bool tile240, bool pre, unsigned grid, const SweepArgs& a) {
     // both stores carry prefix-count rows of the width this slot count reads (k_env_group wrote them): the PRE instantiations
     if constexpr (TM != 1) {
-        const int nw = team_pre_words(cmax);
-        if (cmax <= 16 && a.env_a.pre && a.env_b.pre && a.env_a.pre_words == nw && a.env_b.pre_words == nw) {
+        if (pre && cmax <= 16) {
             if (cmax <= 8) launch_team_c<8, TM, true>(s, tile240, grid, a);
             else if (cmax <= 12) launch_team_c<12, TM, true>(s, tile240, grid, a);
             else launch_team_c<16, TM, true>(s, tile240, grid, a);
@@ -169,7 +168,7 @@ static void launch_team_t(hipStream_t s, int cmax, bool tile240, unsigned grid, 
     }
     if (cmax <= 8) launch_team_c<8, TM, false>(s, tile240, grid, a);
     else if (cmax <= 12) launch_team_c<12, TM, false>(s, tile240, grid, a);
-    else if (cmax <= 16 || TM != 0) launch_team_c<16, TM, false>(s, tile240, grid, a);  // (weights / Kolmogorov-Smirnov: at most 16 slots, checked by launch_sweep)
+    else if (cmax <= 16 || TM != 0) launch_team_c<16, TM, false>(s, tile240, grid, a);  // (weights / Kolmogorov-Smirnov: at most 16 slots, checked by plan_sweep)
     else if constexpr (TM == 0) {
         if (cmax <= 20) launch_team_c<20, 0, false>(s, tile240, grid, a);
         else if (cmax <= 24) launch_team_c<24, 0, false>(s, tile240, grid, a);
@@ -177,10 +176,10 @@ static void launch_team_t(hipStream_t s, int cmax, bool tile240, unsigned grid, 
         else launch_team_c<32, 0, false>(s, tile240, grid, a);
     }
 }
-void launch_team(hipStream_t s, int cmax, int tm, bool tile240, unsigned grid, const SweepArgs& a) {
-    if (tm == 2) launch_team_t<2>(s, cmax, tile240, grid, a);
-    else if (tm == 1) launch_team_t<1>(s, cmax, tile240, grid, a);
-    else launch_team_t<0>(s, cmax, tile240, grid, a);
+void launch_team(hipStream_t s, int cmax, int tm, bool tile240, bool pre, unsigned grid, const SweepArgs& a) {
+    if (tm == 2) launch_team_t<2>(s, cmax, tile240, pre, grid, a);
+    else if (tm == 1) launch_team_t<1>(s, cmax, tile240, pre, grid, a);
+    else launch_team_t<0>(s, cmax, tile240, pre, grid, a);
 }
 
 }  // namespace lchd

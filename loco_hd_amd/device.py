@@ -16,6 +16,17 @@ from . import _native as N
 from .api import LoCoHD
 
 
+def last_sweep_of(ctx):
+    """lchd_ctx_last_sweep of a context handle as a dict (DeviceSession.last_sweep), or None."""
+    plan, stats, rule, repeated = N.SweepPlanC(), (C.c_int64 * 4)(), C.c_int32(), C.c_int32()
+    if N.lib().lchd_ctx_last_sweep(ctx, C.byref(plan), stats, C.byref(rule), C.byref(repeated)) != 0:
+        return None
+    rec = plan.as_dict()
+    rec.update(n_duo=int(stats[0]), n_c8=int(stats[1]), max_env=int(stats[2]), left=int(stats[3]), rule=int(rule.value),
+               repeated=bool(repeated.value))
+    return rec
+
+
 class DeviceSession:
     def __init__(self, lchd: LoCoHD, device: Optional[int] = None, interner: Optional[dict] = None):
         import torch
@@ -76,6 +87,13 @@ class DeviceSession:
                 return None
             sides.append({"dims": tuple(dims), "n_cells": int(n_cells.value), "build": int(build.value)})
         return sides
+
+    def last_sweep(self):
+        """Sweep kernels of the most recent from_primitives call's last pass (lchd_ctx_last_sweep): the fields of lchd_sweep_plan
+        ("families" is a mask of the _native.SWEEP_* bits) plus "n_duo", "n_c8", "max_env", "left" (what the record pass counted; -1
+        where none ran), "rule" (the rule in force: -1, 0, 1, 2) and "repeated" (the pass repeated one whose companion sweep had been
+        left out); None where last_grid() returns None."""
+        return last_sweep_of(self._ctx)
 
     def last_dense_fused(self) -> bool:
         """True if the most recent from_coords call ran the fused sort + sweep kernel (lchd_ctx_last_dense_fused)."""

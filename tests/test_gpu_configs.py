@@ -8,6 +8,25 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 TIGHT = 1e-11
+
+# sweep families as DeviceSession.last_sweep() / lchd_ctx_last_sweep report them (include/loco_hd_hip.h: lchd_sweep_family)
+S_INLINE, S_TEAM240, S_TEAM480, S_C8, S_INDIRECT, S_PLAIN, S_INC, S_WIDE = (1 << k for k in range(8))
+S_NO_HINT_16 = S_TEAM240 | S_INDIRECT | S_TEAM480 | S_PLAIN  # up to 16 slots, no hint: every candidate, the device decides
+S_NO_HINT_32 = S_TEAM480 | S_INDIRECT | S_PLAIN              # 17 .. 32 slots
+
+
+def swept_by(lchd):
+    """what the sweep of a LoCoHD instance's most recent from_primitives / from_packed call did (lchd_ctx_last_sweep), or None"""
+    from loco_hd_amd.device import last_sweep_of
+
+    return last_sweep_of(lchd._ctx)
+
+
+def pair_counts(sizes):
+    """(pairs of at most 240 merged events, pairs with both environments <= 255 points, ... and at most 480 events, pairs)"""
+    sizes = np.asarray(sizes)
+    c8 = sizes.max(axis=1) <= 255
+    return int(np.sum(sizes.sum(axis=1) - 2 <= 240)), int(np.sum(c8)), int(np.sum(c8 & (sizes.sum(axis=1) - 2 <= 480))), len(sizes)
 CG_TYPES = ["Cent", "AmideC", "OH", "Pos", "Neg", "Aro", "Ali", "Sulf"]  # primitive_typings/coarse_grained_with_centroid.config.json
 
 
@@ -342,18 +361,21 @@ def test_from_primitives_batch_matches_single_calls(lh, oracle):
 def test_small_pair_kernel_with_a_minority_of_large_pairs(lh, oracle, monkeypatch):
     """k_sweep_duo (two pairs per wavefront) takes the pairs with <= 240 merged events when they are the majority; the
     INDIRECT instantiation of k_sweep picks the larger ones out of the pair records.  A sparse cloud with one dense blob gives
-    both kinds in one call; a second cloud (mostly dense) makes the small pairs a minority, where the plain kernel must do
-    everything.  Checked against the oracle and against the same call with the small-pair kernel disabled."""
+    both kinds in one call; a second cloud (a sparse halo around a box at three times protein density: environments of up to ~380
+    points, inside the default 512-point slots, so every candidate kernel is still launched) makes the small pairs of either rule a
+    minority, where the plain kernel must do everything.  last_sweep() says which kernels were launched and which rule was in force.
+    Checked against the oracle and against the same call with the small-pair kernel disabled."""
     rng = np.random.default_rng(21)
     cats = ["a", "b", "c", "d", "e", "f"]
 
-    def cloud(n_sparse, n_dense):
-        pts = np.concatenate([rng.uniform(0, 60, (n_sparse, 3)), rng.normal(30, 3.0, (n_dense, 3))])
+    def cloud(n_sparse, n_dense, half):  # half: None -- a Gaussian blob; else the dense part fills a box of that half width
+        dense = rng.normal(30, 3.0, (n_dense, 3)) if half is None else rng.uniform(30 - half, 30 + half, (n_dense, 3))
+        pts = np.concatenate([rng.uniform(0, 60, (n_sparse, 3)), dense])
         return [cats[i] for i in rng.integers(0, 6, len(pts))], pts
 
-    for n_sparse, n_dense, expect_small_majority in ((3000, 260, True), (300, 900, False)):
-        sa, xa = cloud(n_sparse, n_dense)
-        sb, xb = cloud(n_sparse, n_dense)
+    for n_sparse, n_dense, half, expect_small_majority in ((3000, 260, None, True), (300, 3000, 13.5, False)):
+        sa, xa = cloud(n_sparse, n_dense, half)
+        sb, xb = cloud(n_sparse, n_dense, half)
         n = len(xa)
         anchors = [(i, int(j)) for i, j in zip(range(n), rng.permutation(n))] + [(5, 5), (n - 1, n - 1)]
 
@@ -364,20 +386,31 @@ def test_small_pair_kernel_with_a_minority_of_large_pairs(lh, oracle, monkeypatc
             if mod is oracle:
                 out, sizes = lchd.from_primitives(pa, pb, anchors, 8.0, return_env_sizes=True)
                 return np.asarray(out), np.asarray(sizes)
-            return np.asarray(lchd.from_primitives(pa, pb, anchors, 8.0)), None
+            return np.asarray(lchd.from_primitives(pa, pb, anchors, 8.0)), swept_by(lchd)
 
         want, sizes = run(oracle)
         events = sizes.sum(axis=1) - 2 if sizes.ndim == 2 else None
         if events is not None:  # the intended mix of pair sizes
             small = np.mean(events <= 240)
             assert (small >= 0.5) == expect_small_majority and 0.02 < small < 0.98, small
-        inline, _ = run(lh)  # a call this small: the one-launch sweep (records inline, one pair per wavefront)
+        inline, rec = run(lh)  # a call this small: the one-launch sweep (records inline, one pair per wavefront)
         assert np.max(np.abs(inline - want)) < TIGHT
+        assert int(sizes.max()) <= 512 and len(anchors) <= 4096  # (default slots, one pass)
+        assert rec["families"] == S_INLINE, rec
         monkeypatch.setenv("LCHD_NO_INLINE_META", "1")  # the regular pipeline: k_pair_meta, then the device picks the kernels
-        got, _ = run(lh)
+        got, rec = run(lh)
         assert np.max(np.abs(got - want)) < TIGHT
+        n_duo, _, n_team, n_pairs = pair_counts(sizes)
+        assert (rec["n_duo"], rec["n_c8"], rec["max_env"]) == (n_duo, n_team, int(sizes.max())), rec
+        assert rec["families"] == S_NO_HINT_16 and rec["forced"] == 0, rec  # every candidate launched, the device decides
+        if expect_small_majority:  # k_sweep_duo's rule in force: it and the companion share the pairs
+            assert rec["rule"] == 0 and rec["left"] == n_pairs - n_duo > 0, rec
+        else:                      # neither rule has a majority: the plain kernel does everything
+            assert 2 * n_duo < n_pairs and 2 * n_team < n_pairs
+            assert rec["rule"] == -1 and rec["left"] == -1 and rec["ldstab"] == 1, rec
         monkeypatch.setenv("LCHD_NO_DUO", "1")
-        plain, _ = run(lh)
+        plain, rec = run(lh)
+        assert rec["families"] == S_PLAIN and rec["rule"] == -1, rec
         monkeypatch.delenv("LCHD_NO_DUO")
         monkeypatch.delenv("LCHD_NO_INLINE_META")
         assert np.max(np.abs(got - plain)) < 1e-13 and np.max(np.abs(inline - plain)) < 1e-13
@@ -385,16 +418,19 @@ def test_small_pair_kernel_with_a_minority_of_large_pairs(lh, oracle, monkeypatc
 
 def test_eight_bit_count_sweep_with_a_minority_of_large_environments(lh, oracle, monkeypatch):
     """More than 16 category slots: pairs whose environments both have <= 255 points go to the 8-bit-count k_sweep, the
-    others to the INDIRECT 16-bit instantiation.  A cloud at protein-like density with one dense blob gives both kinds in one
-    call (and environments of exactly 255 / 256 points sit on the boundary); a mostly dense cloud makes the large pairs the
-    majority, where the plain kernel does everything.  Against the oracle and against the call with the 8-bit kernel disabled."""
+    others to the INDIRECT 16-bit instantiation (by default two such pairs of at most 480 events per wavefront: rule 2).  A cloud at
+    protein-like density with one dense blob gives both kinds in one call (and environments of exactly 255 / 256 points sit on the
+    boundary); a cloud at one and a half times that density makes the large pairs the majority, where the plain kernel does everything.
+    Every environment stays within the default 512-point slots (the blob has 250 points at sigma 4: at most ~470 per environment):
+    beyond them the pass is repeated with larger slots and only the plain sweep is launched.  last_sweep() says which kernels ran.
+    Against the oracle and against the call with the 8-bit kernel disabled."""
     monkeypatch.setenv("LCHD_NO_INLINE_META", "1")
     rng = np.random.default_rng(27)
     for ncat in (17, 25, 32):
         cats = [f"k{i}" for i in range(ncat)]
-        for n_sparse, n_dense, expect_small_majority in ((4000, 500, True), (300, 1200, False)):
+        for n_sparse, n_dense, box, expect_small_majority in ((4000, 250, 43, True), (4500, 0, 40, False)):
             def cloud():
-                pts = np.concatenate([rng.uniform(0, 43, (n_sparse, 3)), rng.normal(21, 2.6, (n_dense, 3))])
+                pts = np.concatenate([rng.uniform(0, box, (n_sparse, 3)), rng.normal(21, 4.0, (n_dense, 3))])
                 return rng.integers(0, ncat, len(pts)).astype(np.int32), pts
 
             (ca, xa), (cb, xb) = cloud(), cloud()
@@ -406,11 +442,25 @@ def test_eight_bit_count_sweep_with_a_minority_of_large_environments(lh, oracle,
             want, sizes = np.asarray(want), np.asarray(sizes)
             small = np.mean(sizes.max(axis=1) <= 255)
             assert (small >= 0.5) == expect_small_majority and 0.02 < small < 0.98, small
+            assert int(sizes.max()) <= 512 and 255 in sizes and 256 in sizes
             pk = lambda x, c: lh.api._Packed(x, c, tag)
-            got = lh.LoCoHD(cats, lh.WeightFunction("hyper_exp", [1.0, 0.2])).from_packed(pk(xa, ca), pk(xb, cb), pairs, 10.0)
+            lchd = lh.LoCoHD(cats, lh.WeightFunction("hyper_exp", [1.0, 0.2]))
+            got = lchd.from_packed(pk(xa, ca), pk(xb, cb), pairs, 10.0)
             assert np.max(np.abs(got - want)) < TIGHT, (ncat, n_dense)
+            rec = swept_by(lchd)
+            n_duo, _, n_team, n_pairs = pair_counts(sizes)
+            slots = 20 if ncat == 17 else 28 if ncat == 25 else 32
+            assert (rec["families"], rec["forced"], rec["slots"], rec["small_rule"]) == (S_NO_HINT_32, 0, slots, 2), rec
+            assert (rec["n_duo"], rec["n_c8"], rec["max_env"]) == (n_duo, n_team, int(sizes.max())), rec
+            if expect_small_majority:  # rule 2 in force: the 480-event team kernel and the companion share the pairs
+                assert rec["rule"] == 2 and rec["left"] == n_pairs - n_team > 0, rec
+            else:                      # the plain kernel does everything
+                assert 2 * n_team < n_pairs and rec["rule"] == -1 and rec["left"] == -1, rec
             monkeypatch.setenv("LCHD_NO_COUNT8", "1")
-            plain = lh.LoCoHD(cats, lh.WeightFunction("hyper_exp", [1.0, 0.2])).from_packed(pk(xa, ca), pk(xb, cb), pairs, 10.0)
+            lchd = lh.LoCoHD(cats, lh.WeightFunction("hyper_exp", [1.0, 0.2]))
+            plain = lchd.from_packed(pk(xa, ca), pk(xb, cb), pairs, 10.0)
+            rec = swept_by(lchd)
+            assert rec["families"] == S_PLAIN and rec["rule"] == -1 and rec["ldstab"] == 1, rec
             monkeypatch.delenv("LCHD_NO_COUNT8")
             assert np.max(np.abs(got - plain)) < 1e-13
 
@@ -439,14 +489,52 @@ def test_sweep_hint_follows_the_workload(lh, oracle, monkeypatch, ncat):
         ca, cb = rng.integers(0, ncat, n).astype(np.int32), rng.integers(0, ncat, n).astype(np.int32)
         pairs = np.stack([rng.integers(0, n, 3000), rng.integers(0, n, 3000)], 1).astype(np.int64)
         tag = np.zeros(n, dtype=np.int32)
-        want = np.asarray(lo.from_arrays(xa, ca, tag, xb, cb, tag, pairs, 10.0))
-        clouds[name] = (sess.upload(xa, ca), sess.upload(xb, cb), torch.from_numpy(pairs).cuda(), want)
+        want, sizes = lo.from_arrays(xa, ca, tag, xb, cb, tag, pairs, 10.0, return_env_sizes=True)
+        clouds[name] = (sess.upload(xa, ca), sess.upload(xb, cb), torch.from_numpy(pairs).cuda(), np.asarray(want), pair_counts(sizes))
+    # the three workloads are what their names say: every sparse pair has at most 240 events (the NEXT pass leaves the companion out),
+    # dense pairs are of the 8-bit-count rule but mostly longer than 240 events, packed pairs are mostly of neither rule
+    (sd, _, st, sp), (dd, _, dt, dp), (pd, _, pt, pp) = (clouds[k][4] for k in ("sparse", "dense", "packed"))
+    assert sd == st == sp and 2 * dd < dp <= 2 * dt and dd > 0 and 2 * pd < pp and 2 * pt < pp
     order = ("sparse", "sparse", "dense", "dense", "sparse", "dense", "packed", "packed", "dense", "packed", "sparse", "packed", "dense", "dense")
-    for name in order:  # every hint transition
-        a, b, anchors, want = clouds[name]
+    prev, seen, repeats, repeated_at = None, set(), 0, []
+    for step, name in enumerate(order):  # every hint transition
+        a, b, anchors, want, (n_duo, _, n_team, n_pairs) = clouds[name]
+        before = sess.pass_counts()["passes"]
         got = sess.from_primitives(a, b, anchors, 10.0).cpu().numpy()
         assert np.max(np.abs(got - want)) < TIGHT, name
+        rec = sess.last_sweep()
+        assert (rec["n_duo"], rec["n_c8"], rec["slots"]) == (n_duo, n_team, 8 if ncat == 7 else 12 if ncat == 11 else 16), (name, rec)
+        if prev is None:  # no hint: every candidate, the device decides by this list's counts
+            want_fam, want_rule = S_NO_HINT_16, (0 if 2 * n_duo >= n_pairs else 2 if 2 * n_team >= n_pairs else -1)
+            repeated = False
+        else:             # what the PREVIOUS list's counts name
+            p_duo, _, p_team, p_pairs = clouds[prev][4]
+            if 2 * p_duo >= p_pairs:
+                want_fam, want_rule, all_small, taken = S_TEAM240 | S_INDIRECT, 0, p_duo == p_pairs, n_duo
+            elif 2 * p_team >= p_pairs:
+                want_fam, want_rule, all_small, taken = S_TEAM480 | S_INDIRECT, 2, p_team == p_pairs, n_team
+            else:
+                want_fam, want_rule, all_small, taken = S_PLAIN, -1, False, n_pairs
+            repeated = all_small and taken < n_pairs  # the companion was left out and this list needs it: the pass is run again with it
+            if all_small and not repeated:
+                want_fam &= ~S_INDIRECT
+        assert (rec["families"], rec["rule"], rec["repeated"], rec["forced"]) == (want_fam, want_rule, repeated, int(prev is not None)), (prev, name, rec)
+        assert rec["companion_left_out"] == (0 if want_fam & (S_INDIRECT | S_PLAIN) else 1), (prev, name, rec)
+        # (at least: the packed list after a smaller one also repeats a pass whose environments outgrew the small environment kernel)
+        assert sess.pass_counts()["passes"] - before >= (2 if repeated else 1), (prev, name)
+        seen.add(want_fam)
+        repeats += repeated
+        if repeated:
+            repeated_at.append(step)
+        prev = name
     sess.close()
+    # the order reaches every launch set of a hinted pass, the left-out companion and its repetition included
+    # (at 11 and 15 categories EVERY dense pair is of rule 2: dense after dense leaves the companion out as well)
+    want_seen = {S_NO_HINT_16, S_TEAM240, S_TEAM240 | S_INDIRECT, S_TEAM480 | S_INDIRECT, S_PLAIN}
+    assert want_seen <= seen <= want_seen | {S_TEAM480} and repeats >= 2, (seen, repeats)
+    # the steps that run twice: dense or packed after sparse (the companion of the 240-event rule was left out), and at 11 / 15
+    # categories packed after dense as well (every dense pair is of rule 2; at 7 categories one is not)
+    assert repeated_at == ([2, 5, 11] if ncat == 7 else [2, 5, 6, 9, 11]), repeated_at
 
 
 @pytest.mark.parametrize("ncat,density", [(7, 0.060), (7, 0.065), (8, 0.0575), (11, 0.0575), (12, 0.061), (15, 0.0575), (16, 0.060),
@@ -486,10 +574,27 @@ def test_two_pairs_per_wavefront_eight_bit_sweep_around_its_limits(lh, oracle, m
             monkeypatch.setenv("LCHD_NO_C8_TEAM", "1")
         sess = DeviceSession(lh.LoCoHD(cats, lh.WeightFunction(*wf)))
         a, b, d_pairs = sess.upload(xa, ca), sess.upload(xb, cb), torch.from_numpy(pairs).cuda()
-        first = sess.from_primitives(a, b, d_pairs, 10.0).cpu().numpy()
-        second = sess.from_primitives(a, b, d_pairs, 10.0).cpu().numpy()
-        third = sess.from_primitives(a, b, d_pairs, 10.0).cpu().numpy()
+        first, rec1 = sess.from_primitives(a, b, d_pairs, 10.0).cpu().numpy(), sess.last_sweep()
+        second, rec2 = sess.from_primitives(a, b, d_pairs, 10.0).cpu().numpy(), sess.last_sweep()
+        third, rec3 = sess.from_primitives(a, b, d_pairs, 10.0).cpu().numpy(), sess.last_sweep()
         sess.close()
+        n_duo, n_c8, n_team, n_pairs = pair_counts(sizes)
+        assert 2 * n_duo < n_pairs  # (no case is one of k_sweep_duo's 240-event rule)
+        slots = 8 if ncat <= 8 else 12 if ncat <= 12 else 16 if ncat <= 16 else 20 if ncat <= 20 else 24 if ncat <= 24 else 28 if ncat <= 28 else 32
+        if mode == "team":  # rule 2 on every pass when its pairs are the majority: the two-pairs-per-wavefront kernel and the companion
+            rule = 2 if 2 * n_team >= n_pairs else -1
+            assert (rec1["families"], rec1["rule"]) == (S_NO_HINT_16 if ncat <= 16 else S_NO_HINT_32, rule), rec1
+            hinted = S_TEAM480 | S_INDIRECT if rule == 2 else S_PLAIN
+            count, left = n_team, n_pairs - n_team
+        else:  # the hook: rule 1, the one-pair-per-wavefront 8-bit kernel -- up to 16 slots only from the second pass on
+            rule = 1 if 2 * n_c8 >= n_pairs else -1
+            assert (rec1["families"], rec1["rule"]) == ((S_TEAM240 | S_INDIRECT | S_PLAIN, -1) if ncat <= 16 else (S_C8 | S_INDIRECT | S_PLAIN, rule)), rec1
+            hinted = S_C8 | S_INDIRECT if rule == 1 else S_PLAIN
+            count, left = n_c8, n_pairs - n_c8
+        for rec in (rec1, rec2, rec3):
+            assert (rec["n_duo"], rec["n_c8"], rec["slots"]) == (n_duo, count, slots), (mode, rec)
+        for rec in (rec2, rec3):
+            assert (rec["families"], rec["rule"], rec["forced"], rec["left"]) == (hinted, rule, 1, left if rule >= 0 else -1), (mode, rec)
         assert np.max(np.abs(first - want)) < TIGHT, (mode, np.mean(team))
         if mode == "team":
             assert np.array_equal(first, second) and np.array_equal(second, third)
@@ -533,9 +638,18 @@ def test_leftover_list_of_hinted_passes_follows_a_changing_pair_list(lh, oracle,
         left.append(int(np.sum(~((sizes.max(axis=1) <= 255) & (sizes.sum(axis=1) - 2 <= 480)))))
         got = sess.from_primitives(a, b, torch.from_numpy(pairs).cuda(), 10.0).cpu().numpy()
         assert np.max(np.abs(got - want)) < TIGHT, (k, left)
+        # rule 2 is in force in every call (asserted: its pairs are the majority, those of at most 240 events are not); from the second call
+        # on the host picks the 480-event team kernel and the companion, and the companion walks the list
+        n_duo, _, n_team, n_pairs = pair_counts(sizes)
+        assert 2 * n_duo < n_pairs <= 2 * n_team
+        rec = sess.last_sweep()
+        assert (rec["rule"], rec["left"], rec["n_c8"], rec["repeated"]) == (2, left[k], n_team, False), (k, rec)
+        assert (rec["families"], rec["forced"], rec["left_listing"]) == ((S_NO_HINT_16, 0, 0) if k == 0 else (S_TEAM480 | S_INDIRECT, 1, 1)), (k, rec)
         fresh = DeviceSession(lh.LoCoHD(cats, lh.WeightFunction(*wf)))
         fa, fb = fresh.upload(xa, ca), fresh.upload(xb, cb)
         first = fresh.from_primitives(fa, fb, torch.from_numpy(pairs).cuda(), 10.0).cpu().numpy()
+        rec = fresh.last_sweep()  # the scanning pass: every candidate launched, no list
+        assert (rec["families"], rec["forced"], rec["left_listing"], rec["rule"], rec["left"]) == (S_NO_HINT_16, 0, 0, 2, left[k]), (k, rec)
         fresh.close()
         assert np.array_equal(got, first), (k, left)
     sess.close()

@@ -102,7 +102,8 @@ PRIM_CASES = {"lattice": (("hyper_exp", [1.0, 0.3]), 3.2, 10, 400), "f1_tail": (
 @pytest.mark.parametrize("n_cat", CATS)
 def test_from_primitives_is_invariant_under_point_permutation(lh, oracle, n_cat, api, case):
     import torch
-    from loco_hd_amd.device import DeviceSession
+    from loco_hd_amd import _native as N
+    from loco_hd_amd.device import DeviceSession, last_sweep_of
 
     wf, thr, m, n_pairs = PRIM_CASES[case]
     rng = np.random.default_rng(7000 + n_cat + (1 if api == "host" else 0) + (2 if case == "f1_tail" else 0))
@@ -117,11 +118,17 @@ def test_from_primitives_is_invariant_under_point_permutation(lh, oracle, n_cat,
         lchd = lh.LoCoHD(cats, lh.WeightFunction(*wf), deterministic=det)
         if api == "host":
             prim = lambda x, c: [lh.PrimitiveAtom(cats[k], "", p) for k, p in zip(c, x)]
-            return np.asarray(lchd.from_primitives(prim(xa, ca), prim(xb, cb), [tuple(p) for p in pairs.tolist()], thr))
-        sess = DeviceSession(lchd)
-        a, b = sess.upload(xa, ca), sess.upload(xb, cb)
-        out = sess.from_primitives(a, b, torch.from_numpy(pairs).cuda(), thr).cpu().numpy()
-        sess.close()
+            out = np.asarray(lchd.from_primitives(prim(xa, ca), prim(xb, cb), [tuple(p) for p in pairs.tolist()], thr))
+            swept = last_sweep_of(lchd._ctx)
+        else:
+            sess = DeviceSession(lchd)
+            a, b = sess.upload(xa, ca), sess.upload(xb, cb)
+            out = sess.from_primitives(a, b, torch.from_numpy(pairs).cuda(), thr).cpu().numpy()
+            swept = sess.last_sweep()
+            sess.close()
+        if det:  # ONE family whatever the call looks like: the plain sweep with global-memory tables (beyond 32 categories: the wide one)
+            assert swept is not None and swept["families"] == (N.SWEEP_PLAIN if n_cat <= 32 else N.SWEEP_WIDE), swept
+            assert swept["forced"] == 0 and swept["rule"] == -1 and (n_cat > 32 or swept["ldstab"] == 0), swept
         return out
 
     got = run(True, xa, ca, xb, cb, pairs)

@@ -4,6 +4,8 @@ loco_hd_amd/csrc/lchd_sweep_inc.hip) instead of the generic per-category evaluat
 import numpy as np
 import pytest
 
+from loco_hd_amd import _native as N
+
 pytestmark = pytest.mark.gpu
 
 TIGHT = 1e-11
@@ -15,6 +17,19 @@ def lh():
     import loco_hd_amd
 
     return loco_hd_amd
+
+
+def swept_by(lchd):
+    """sweep families of the instance's most recent from_primitives call (lchd_ctx_last_sweep)"""
+    from loco_hd_amd.device import last_sweep_of
+
+    rec = last_sweep_of(lchd._ctx)
+    assert rec is not None
+    return rec["families"]
+
+
+# the parameters k_sweep_inc takes (lchd_ctx_set_config): eps <= 1e-9 and, for Renyi, an order of 0.01 .. 20
+FAST = lambda sd: (sd[0] == "Kullback-Leibler" and sd[1][0] <= 1e-9) or (sd[0] == "Renyi" and 0.01 <= sd[1][0] <= 20.0 and sd[1][1] <= 1e-9)
 
 
 def prims(mod, seq, xyz, tags=None):
@@ -42,16 +57,26 @@ def test_fast_divergences_match_the_oracle(lh, oracle, sd, monkeypatch):
 
             def run(mod):
                 lchd = mod.LoCoHD(cats, mod.WeightFunction("hyper_exp", [1.0, 0.12]), statistical_distance=mod.StatisticalDistance(*sd))
-                return [np.asarray(lchd.from_primitives(prims(mod, qa, ya), prims(mod, qb, yb), anchors, thr)) for _ in range(2)]
+                outs = []
+                for _ in range(2):
+                    outs.append(np.asarray(lchd.from_primitives(prims(mod, qa, ya), prims(mod, qb, yb), anchors, thr)))
+                    if mod is lh:
+                        families.append(swept_by(lchd))
+                return outs
 
+            families = []
             got, want = run(lh), run(oracle)[0]
+            # the incremental sweep ran where the parameters qualify, the generic one where they do not
+            assert families == [N.SWEEP_INC if FAST(sd) else N.SWEEP_PLAIN] * 2, (sd, families)
             scale = max(1.0, float(np.max(np.abs(want[np.isfinite(want)]))) if np.isfinite(want).any() else 1.0)
             for g in got:
                 assert np.array_equal(np.isfinite(g), np.isfinite(want))
                 ok = np.isfinite(want)
                 assert np.max(np.abs(g[ok] - want[ok])) < TIGHT * scale, (sd, n)
             monkeypatch.setenv("LCHD_NO_SD_INC", "1")
+            families = []
             slow = run(lh)[0]
+            assert families == [N.SWEEP_PLAIN] * 2, (sd, families)
             monkeypatch.delenv("LCHD_NO_SD_INC")
             ok = np.isfinite(want)
             assert np.max(np.abs(slow[ok] - got[0][ok])) < TIGHT * scale, (sd, n)
@@ -59,7 +84,9 @@ def test_fast_divergences_match_the_oracle(lh, oracle, sd, monkeypatch):
 
 def test_fast_divergences_fall_back_where_they_must(lh, oracle):
     """Category weights, a weight-function dictionary, environments beyond 512 points and a tag rule: the first three leave the
-    fast path's conditions (generic sweep), the tag rule stays on it."""
+    fast path's conditions (generic sweep), the tag rule stays on it.  Only the tag-rule variant carries tags: under the default rule
+    a tagged atom's environment holds the atoms of its own tag alone (four here), which kept the threshold-40 variant far below 512
+    points and on the incremental sweep; untagged, every atom has all 700 within 40."""
     rng = np.random.default_rng(82)
     n = 700
     sa, xa = rng.choice(CATS, n).tolist(), rng.uniform(0, 24.0, (n, 3))
@@ -82,7 +109,11 @@ def test_fast_divergences_fall_back_where_they_must(lh, oracle):
                 keyed = [(i, j, "u" if i % 2 else "h") for i, j in anchors]
             rule = mod.TagPairingRule(v["rule"]) if "rule" in v else None
             lchd = mod.LoCoHD(CATS, wf, rule, **kw)
-            return np.asarray(lchd.from_primitives(prims(mod, sa, xa, tags), prims(mod, sb, xb, tags), keyed, v.get("thr", 9.0)))
+            tg = tags if "rule" in v else None
+            out = np.asarray(lchd.from_primitives(prims(mod, sa, xa, tg), prims(mod, sb, xb, tg), keyed, v.get("thr", 9.0)))
+            if mod is lh:  # only the tag rule stays on the incremental sweep
+                assert swept_by(lchd) == (N.SWEEP_INC if "rule" in v else N.SWEEP_PLAIN), v
+            return out
 
         got, want = run(lh), run(oracle)
         scale = max(1.0, float(np.max(np.abs(want))))

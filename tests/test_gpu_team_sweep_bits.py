@@ -12,9 +12,11 @@ weights (WGT) and with the Kolmogorov-Smirnov distance (KSM):
   h2_16   0.05 atoms/A^3, 16 categories: 16 slots, 480-event tiles
   wgt_12, ksm_12   the clouds of h2_12 (the weighted form has no prefix-count-row instantiation: wgt_12 covers the event loop only)
 
-Which kernel sweeps a pair is decided inside the library from the previous pass's pair statistics and is not exposed to Python, so this
-test cannot assert it; it asserts the pair statistics that decide (most pairs fit the shape's tile, and for the 480-event shapes most do
-not fit the 240-event one).  profiles/r10/kernel_stats_team_sweep_bits.csv is a kernel trace of these five cases.
+Which kernels sweep a pass is decided inside the library from the previous pass's pair statistics; DeviceSession.last_sweep() reports it,
+and the test asserts it: the hinted passes ran the team kernel of the case's tile and nothing else but the companion -- which is left out
+where every pair of the list fits the tile (all cases but h2_16) --, at the case's slot count, reading prefix-count rows (PRE) in the h2 and ksm cases and building the chunk-start counts per tile in the weighted one.  It also
+asserts the pair statistics that decide (most pairs fit the shape's tile, and for the 480-event shapes most do not fit the 240-event
+one).  profiles/r10/kernel_stats_team_sweep_bits.csv is a kernel trace of these five cases.
 
 Behind the 20 000 random pairs every list carries pairs built for the ends of the chunk-start reads: small clusters far outside the box
 give environments of 1, 2 and 3 points on either side (a lane's chunk then starts 0 .. 2 points behind a prefix-count row that is the
@@ -106,9 +108,12 @@ def gpu_scores(lh, case, passes=3):
     sess = DeviceSession(build(lh, case))
     a, b = sess.upload(case["xa"], case["ca"]), sess.upload(case["xb"], case["cb"])
     d_pairs = torch.from_numpy(case["pairs"]).cuda()
-    outs = [sess.from_primitives(a, b, d_pairs, THR).cpu().numpy() for _ in range(passes)]
+    outs, swept = [], []
+    for _ in range(passes):
+        outs.append(sess.from_primitives(a, b, d_pairs, THR).cpu().numpy())
+        swept.append(sess.last_sweep())
     sess.close()
-    return outs
+    return outs, swept
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -130,7 +135,21 @@ def test_team_sweep_scores_keep_their_bits(name, oracle):
 
     tag = np.zeros(len(case["xa"]), dtype=np.int32)
     want = np.asarray(build(oracle, case).from_arrays(case["xa"], case["ca"], tag, case["xb"], case["cb"], tag, case["pairs"], THR))
-    outs = gpu_scores(lh, case)
+    from loco_hd_amd import _native as N
+
+    outs, swept = gpu_scores(lh, case)
+    form = CASES[name][3]
+    team, rule = (N.SWEEP_TEAM480, 2) if tile == 480 else (N.SWEEP_TEAM240, 0)
+    assert swept[0]["families"] == N.SWEEP_TEAM240 | N.SWEEP_INDIRECT | N.SWEEP_TEAM480 | N.SWEEP_PLAIN and swept[0]["forced"] == 0, swept[0]
+    for rec in swept:  # (pass 1: every candidate launched, the device decides for the same rule)
+        assert rec["rule"] == rule and rec["slots"] == {8: 8, 10: 12, 16: 16}[case["n_cat"]], rec
+        assert rec["team_mode"] == {"h2": 0, "wgt": 1, "ksm": 2}[form] and rec["pre"] == (0 if form == "wgt" else 1), rec
+    for rec in swept[1:]:
+        left = int(np.count_nonzero(~small))  # pairs beyond the tile: with none in the previous pass the companion is not launched
+        assert rec["families"] == (team | N.SWEEP_INDIRECT if left else team) and rec["forced"] == 1 and rec["small_rule"] == rule, rec
+        assert rec["left"] == left and rec["left_listing"] == (1 if left else 0) and rec["companion_left_out"] == (0 if left else 1), rec
+        assert not rec["repeated"], rec
+    assert (name == "h2_16") == bool(np.count_nonzero(~small))
     golden = np.load(GOLDEN / f"{name}.npy")
     for k, got in enumerate(outs):
         err = float(np.max(np.abs(got - want)))
