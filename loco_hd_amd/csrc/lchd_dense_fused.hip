@@ -84,12 +84,6 @@ constexpr size_t kValOff = (size_t)(kCap + kKeyPad) * 8, kHistOff = kValOff + (s
 static_assert(kHistOff % 16 == 0, "the bucket scan reads 16-byte groups");
 constexpr size_t kDynLds = kHistOff + (size_t)kBuckets * 2 + 16;  // (+ the histogram's end word)
 
-__device__ __forceinline__ uint64_t df_spread4(uint64_t x) {  // four 4-bit fields -> four 16-bit fields
-    const uint32_t v = (uint32_t)x;
-    const uint32_t lo = (v & 0xFu) | ((v & 0xF0u) << 12);
-    const uint32_t hi = ((v >> 8) & 0xFu) | ((v & 0xF000u) << 4);
-    return ((uint64_t)hi << 32) | lo;
-}
 // sqrt for moderate x (counts, H^2): v_rsq_f64 seed + Goldschmidt, within 1 ulp; sqrt(0) = 0
 __device__ __forceinline__ double df_sqrt(double x) {
     const double y = __builtin_amdgcn_rsq(x);
@@ -658,7 +652,7 @@ __global__ __launch_bounds__(kNT, 4) void k_dense_fused(DenseArgs a) {
             uint64_t exA[NW], exB[NW];  // packed 16-bit category counts before this lane's first event
 #pragma unroll
             for (int k = 0; k < NW; ++k) {
-                const uint64_t va_ = df_spread4(hA >> (16 * k)), vb_ = df_spread4(hB >> (16 * k));
+                const uint64_t va_ = spread4(hA >> (16 * k)), vb_ = spread4(hB >> (16 * k));
                 const uint64_t sa_ = wave_incl_scan_fields(va_), sb_ = wave_incl_scan_fields(vb_);
                 exA[k] = sa_ - va_;
                 exB[k] = sb_ - vb_;

@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <iterator>
+#include <type_traits>
+
 struct lchd_sweep_query;  // include/loco_hd_hip.h
 struct lchd_sweep_plan;
 
@@ -19,6 +22,16 @@ constexpr int kWideCategories = 512;  // ... or, for 256 .. 512 categories, as u
 constexpr int kSweepEPL = 6;  // merged events per lane per tile in the sweep kernel (16-bit counts, LDS tables, <= 16 category slots; the generic distances)
 constexpr int kSweepTile = 64 * kSweepEPL;
 constexpr int kMetaPartials = 4096;   // most workgroups of k_pair_meta
+// Category slots the register-resident sweeps are instantiated for.  A configuration runs the smallest entry that holds its categories
+// (the last one beyond it); the launchers and plan_sweep (lchd_sweep_plan::slots) both go through with_slots.
+inline constexpr int kSweepSlots[] = {8, 12, 16, 20, 24, 28, 32};  // k_sweep, k_sweep_duo
+inline constexpr int kIncSlots[] = {8, 12, 16, 24, 32};            // k_sweep_inc
+// f(std::integral_constant<int, S>) for the entry S of TAB that `cmax` categories round up to
+template <const auto& TAB, size_t I = 0, class F>
+inline void with_slots(int cmax, F&& f) {
+    if (cmax <= TAB[I] || I + 1 == std::size(TAB)) f(std::integral_constant<int, TAB[I]>{});
+    else if constexpr (I + 1 < std::size(TAB)) with_slots<TAB, I + 1>(cmax, f);
+}
 constexpr uint64_t kPadKey = ~0ull;   // sorts after every valid (non-negative, non-NaN) f64 bit pattern
 
 // status word written by kernels (device memory, zeroed per call)

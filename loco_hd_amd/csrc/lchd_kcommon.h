@@ -1,5 +1,6 @@
 // lchd_kcommon.h -- device helpers shared by every kernel translation unit (lchd_prologue / _env_* / _sweep* / _dense_fused / _kernels .hip):
-// lane shuffles / DPP scans, the table-driven exp / log / pow, the lean CDF evaluation and the tag pairing rule.
+// lane shuffles / DPP scans, the merge-path search and the count-field spreads of the sweeps, the table-driven exp / log / pow, the
+// lean CDF evaluation and the tag pairing rule.
 #pragma once
 #include "lchd_device.h"
 #include "lchd_math.h"
@@ -87,6 +88,34 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {  // l wave-uni
 __device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int l) {
     const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, l), hi = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
     return ((uint64_t)hi << 32) | lo;
+}
+
+// merge path of two ascending lists: how many of the first d merged entries come from A (A first on ties)
+__device__ __forceinline__ int merge_path(const uint64_t* A, int nA, const uint64_t* B, int nB, int d) {
+    int lo = max(0, d - nB), hi = min(d, nA);
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (A[mid] <= B[d - 1 - mid]) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// spread the four 4-bit fields of the low 16 bits of x into four 16-bit fields
+__device__ __forceinline__ uint64_t spread4(uint64_t x) {
+    // two 32-bit halves, three operations each (and, and / bfe, shift-or); the 64-bit shift-or-mask form is compiled to
+    // quarter-rate 32x32 multiplies
+    const uint32_t v = (uint32_t)x;
+    const uint32_t lo = (v & 0xFu) | ((v & 0xF0u) << 12);
+    const uint32_t hi = ((v >> 8) & 0xFu) | ((v & 0xF000u) << 4);
+    return ((uint64_t)hi << 32) | lo;
+}
+// spread the eight 4-bit fields of the low 32 bits of x into eight 8-bit fields
+__device__ __forceinline__ uint64_t spread8(uint64_t x) {
+    const uint32_t v = (uint32_t)x;
+    auto half = [](uint32_t h) -> uint32_t {  // four nibbles (16 bits) -> four bytes
+        const uint32_t t = (h | (h << 8)) & 0x00FF00FFu;
+        return (t | (t << 4)) & 0x0F0F0F0Fu;
+    };
+    return ((uint64_t)half(v >> 16) << 32) | half(v & 0xFFFFu);
 }
 
 // hyper_exp and uniform are the common weight functions and stay inline; the pow-based CDFs are called.

@@ -72,7 +72,7 @@ __global__ void k_pair_meta(SweepArgs args) {
         // pairs k_sweep_duo takes: everything that fits its tile, and the unusable ones (it writes their NaN); pairs the
         // 8-bit-count sweep takes: both environments of at most 255 points.  Both are counted whichever rule this pass uses:
         // the host picks the next pass's kernels from them.
-        n_duo += (nA + nB - 2 <= kDuoTileFwd) ? 1 : 0;
+        n_duo += (nA + nB - 2 <= kDuoTile) ? 1 : 0;
         n_c8 += pair_is_small(args.c8_rule, nA, nB) ? 1 : 0;
         if (args.left_listing) {  // (uniform) the pairs the team kernel of this pass leaves to the INDIRECT companion: the test of its scan
             const bool left = nA > 0 && !pair_is_small(args.small_rule, nA, nB);
@@ -118,7 +118,6 @@ __global__ void k_pair_meta(SweepArgs args) {
 
 // Which sweep kernels take a pass: a pure function of the configuration, the call's size and the previous pass's pair statistics
 // (lchd_plan_sweep, include/loco_hd_hip.h).  launch_sweep below launches exactly what this returns.
-static int slots_of(int cmax) { return cmax <= 8 ? 8 : cmax <= 12 ? 12 : cmax <= 16 ? 16 : cmax <= 20 ? 20 : cmax <= 24 ? 24 : cmax <= 28 ? 28 : 32; }
 static void plan_sweep_families(const lchd_sweep_query& q, lchd_sweep_plan& p) {
     p = lchd_sweep_plan{};
     const bool no_duo = q.hooks & LCHD_HOOK_NO_DUO, no_count8 = q.hooks & LCHD_HOOK_NO_COUNT8, no_c8_team = q.hooks & LCHD_HOOK_NO_C8_TEAM,
@@ -131,7 +130,7 @@ static void plan_sweep_families(const lchd_sweep_query& q, lchd_sweep_plan& p) {
     const int cmax = std::max(n_categories, q.force_cmax);  // (force_cmax: test hook)
     const bool small = q.stride_a <= kSqrtTab && q.stride_b <= kSqrtTab && !force_bigenv;  // every count fits the LDS tables
     const bool keyed = q.cdf_keys_a && q.cdf_keys_b;
-    p.slots = slots_of(cmax);
+    with_slots<kSweepSlots>(cmax, [&](auto S) { p.slots = S; });
     p.c8_rule = 2;
     p.plain_mode = !hellinger2 ? MODE_GEN : (unit_weights ? MODE_H2U : MODE_H2W);
     p.fmode = keyed ? F_KEY : (wf_pow ? F_ANY : F_FAST);
@@ -205,7 +204,7 @@ static void plan_sweep_families(const lchd_sweep_query& q, lchd_sweep_plan& p) {
     }
     if (!hellinger2 && (q.sd_fast == 1 || q.sd_fast == 2) && unit_weights && small && p.fmode == F_KEY && !q.has_wf_index && cmax <= 32) {
         p.families |= LCHD_SWEEP_INC;
-        p.slots = cmax <= 8 ? 8 : cmax <= 12 ? 12 : cmax <= 16 ? 16 : cmax <= 24 ? 24 : 32;  // (launch_sweep_inc's ladder)
+        with_slots<kIncSlots>(cmax, [&](auto S) { p.slots = S; });
     } else {
         p.families |= LCHD_SWEEP_PLAIN;
     }

@@ -1,5 +1,5 @@
 // lchd_sweep.hip -- K2, one anchor pair per wavefront: k_sweep<CMAX, MODE, FMODE, LDSTAB, INDIRECT, INLINE_META, CNT8>
-// (LoCoHD::stat_dist_integral, /root/reference/src/locohd.rs:61-226; PMFSystem, pmf.rs; statistical_distances.rs; cdfs.rs) and
+// (LoCoHD::stat_dist_integral, src/locohd.rs:61-226; PMFSystem, pmf.rs; statistical_distances.rs; cdfs.rs) and
 // k_anchors_literal (from_anchors on lists that do not ascend).
 #include "lchd_sweep_common.h"
 
@@ -828,16 +828,10 @@ __global__ __launch_bounds__(64 * kSweepWaves, (sweep_waves_per_simd<CMAX, MODE,
     }
 }
 
+constexpr int kSweepThreads = 64 * kSweepWaves;
 template <int MODE, int FMODE, bool LDSTAB>
 static void launch_sweep_mode(hipStream_t s, int cmax, unsigned grid, const SweepArgs& a) {
-    constexpr int NTH = 64 * kSweepWaves;
-    if (cmax <= 8) k_sweep<8, MODE, FMODE, LDSTAB><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 12) k_sweep<12, MODE, FMODE, LDSTAB><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 16) k_sweep<16, MODE, FMODE, LDSTAB><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 20) k_sweep<20, MODE, FMODE, LDSTAB><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 24) k_sweep<24, MODE, FMODE, LDSTAB><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 28) k_sweep<28, MODE, FMODE, LDSTAB><<<grid, NTH, 0, s>>>(a);
-    else k_sweep<32, MODE, FMODE, LDSTAB><<<grid, NTH, 0, s>>>(a);
+    with_slots<kSweepSlots>(cmax, [&](auto S) { k_sweep<S, MODE, FMODE, LDSTAB><<<grid, kSweepThreads, 0, s>>>(a); });
 }
 template <int MODE, bool LDSTAB>
 static void launch_sweep_f(hipStream_t s, int cmax, unsigned grid, int fmode, const SweepArgs& a) {
@@ -858,29 +852,15 @@ void launch_sweep_plain(hipStream_t s, int mode, bool ldstab, int cmax, unsigned
         else launch_sweep_f<MODE_H2W, false>(s, cmax, grid, fmode, a);
     }
 }
-void launch_sweep_inline(hipStream_t s, int cm, unsigned g, const SweepArgs& a) {
-    constexpr int NTH = 64 * kSweepWaves;
-    if (cm <= 8) k_sweep<8, MODE_H2U, F_KEY, true, false, true><<<g, NTH, 0, s>>>(a);
-    else if (cm <= 12) k_sweep<12, MODE_H2U, F_KEY, true, false, true><<<g, NTH, 0, s>>>(a);
-    else if (cm <= 16) k_sweep<16, MODE_H2U, F_KEY, true, false, true><<<g, NTH, 0, s>>>(a);
-    else if (cm <= 20) k_sweep<20, MODE_H2U, F_KEY, true, false, true><<<g, NTH, 0, s>>>(a);
-    else if (cm <= 24) k_sweep<24, MODE_H2U, F_KEY, true, false, true><<<g, NTH, 0, s>>>(a);
-    else if (cm <= 28) k_sweep<28, MODE_H2U, F_KEY, true, false, true><<<g, NTH, 0, s>>>(a);
-    else k_sweep<32, MODE_H2U, F_KEY, true, false, true><<<g, NTH, 0, s>>>(a);
+void launch_sweep_inline(hipStream_t s, int cmax, unsigned grid, const SweepArgs& a) {
+    with_slots<kSweepSlots>(cmax, [&](auto S) { k_sweep<S, MODE_H2U, F_KEY, true, false, true><<<grid, kSweepThreads, 0, s>>>(a); });
 }
 void launch_sweep_c8(hipStream_t s, int cmax, unsigned grid, const SweepArgs& a) {
-    constexpr int NTH = 64 * kSweepWaves;
-    if (cmax <= 8) k_sweep<8, MODE_H2U, F_KEY, true, false, false, true><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 12) k_sweep<12, MODE_H2U, F_KEY, true, false, false, true><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 16) k_sweep<16, MODE_H2U, F_KEY, true, false, false, true><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 20) k_sweep<20, MODE_H2U, F_KEY, true, false, false, true><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 24) k_sweep<24, MODE_H2U, F_KEY, true, false, false, true><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 28) k_sweep<28, MODE_H2U, F_KEY, true, false, false, true><<<grid, NTH, 0, s>>>(a);
-    else k_sweep<32, MODE_H2U, F_KEY, true, false, false, true><<<grid, NTH, 0, s>>>(a);
+    with_slots<kSweepSlots>(cmax, [&](auto S) { k_sweep<S, MODE_H2U, F_KEY, true, false, false, true><<<grid, kSweepThreads, 0, s>>>(a); });
 }
 template <int CM>
 static void launch_indirect_c(hipStream_t s, int tm, unsigned grid, const SweepArgs& a) {
-    constexpr int NTH = 64 * kSweepWaves;
+    constexpr int NTH = kSweepThreads;
     if constexpr (CM <= 16) {
         if (tm == 2) { k_sweep<CM, MODE_GEN, F_KEY, false, true><<<grid, NTH, 0, s>>>(a); return; }
         if (tm == 1) { k_sweep<CM, MODE_H2W, F_KEY, true, true><<<grid, NTH, 0, s>>>(a); return; }
@@ -888,13 +868,7 @@ static void launch_indirect_c(hipStream_t s, int tm, unsigned grid, const SweepA
     k_sweep<CM, MODE_H2U, F_KEY, true, true><<<grid, NTH, 0, s>>>(a);
 }
 void launch_sweep_indirect(hipStream_t s, int cmax, int tm, unsigned grid, const SweepArgs& a) {
-    if (cmax <= 8) launch_indirect_c<8>(s, tm, grid, a);
-    else if (cmax <= 12) launch_indirect_c<12>(s, tm, grid, a);
-    else if (cmax <= 16) launch_indirect_c<16>(s, tm, grid, a);
-    else if (cmax <= 20) launch_indirect_c<20>(s, tm, grid, a);
-    else if (cmax <= 24) launch_indirect_c<24>(s, tm, grid, a);
-    else if (cmax <= 28) launch_indirect_c<28>(s, tm, grid, a);
-    else launch_indirect_c<32>(s, tm, grid, a);
+    with_slots<kSweepSlots>(cmax, [&](auto S) { launch_indirect_c<S>(s, tm, grid, a); });
 }
 
 }  // namespace lchd

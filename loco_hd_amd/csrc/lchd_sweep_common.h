@@ -1,6 +1,7 @@
-// lchd_sweep_common.h -- what the sweep kernel families share (lchd_sweep.hip, lchd_sweep_team.hip, lchd_sweep_wide.hip, the record pass
-// and the launch logic in lchd_kernels.hip): distance / key modes, tuning constants, the pass's small-pair rule, the status hand-over
-// without a fence, the generic statistical distances and the per-pair weight-function registers.
+// lchd_sweep_common.h -- what the sweep kernel families share (lchd_sweep.hip, lchd_sweep_team.hip, lchd_sweep_wide.hip, lchd_sweep_inc.hip,
+// the record pass and the launch logic in lchd_kernels.hip): distance / key modes, tuning constants, the pass's small-pair rule, the
+// status hand-over without a fence, the generic statistical distances and the per-pair weight-function registers.  (The merge-path
+// search and the count-field spreads are in lchd_kcommon.h, the category-slot tables of the launchers and the planner in lchd_device.h.)
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -35,7 +36,6 @@ namespace lchd {
 enum { MODE_H2U = 0, MODE_H2W = 1, MODE_GEN = 2 };
 // where F(t) comes from: the environment keys already are F values / inline CDFs only / any CDF
 enum { F_KEY = 0, F_FAST = 1, F_ANY = 2 };
-constexpr int kDuoTileFwd = kDuoTile;  // (lchd_team_tile.h)
 // The small rule in force in this pass, or -1 (the plain sweep takes every pair).  With a hint the host launched exactly the
 // kernels that have to run (forced); without one every candidate kernel is launched and all of them decide here, from the
 // counts of k_pair_meta: the first-choice rule if its pairs are the majority, else the second-choice rule if ITS pairs are --
@@ -110,17 +110,6 @@ __device__ __forceinline__ void publish_status(const SweepArgs& args, unsigned l
     st->n_overflow[1] = 0u;
     st->max_bound = 0u;
     st->n_dup_b = 0u;
-}
-
-
-// spread the four 4-bit fields of the low 16 bits of x into four 16-bit fields
-__device__ __forceinline__ uint64_t spread4(uint64_t x) {
-    // two 32-bit halves, three operations each (and, and / bfe, shift-or); the 64-bit shift-or-mask form is compiled to
-    // quarter-rate 32x32 multiplies
-    const uint32_t v = (uint32_t)x;
-    const uint32_t lo = (v & 0xFu) | ((v & 0xF0u) << 12);
-    const uint32_t hi = ((v >> 8) & 0xFu) | ((v & 0xF000u) << 4);
-    return ((uint64_t)hi << 32) | lo;
 }
 
 // StatisticalDistance::run for Hellinger with a general exponent (statistical_distances.rs:4-10) and Renyi (:31-78) on the

@@ -25,7 +25,7 @@
 // routines).  Sums are rebuilt from the exact integer counts at every lane chunk (<= 6 events), and -- Renyi -- whenever an
 // event moves a category out of the b = 0 class (Z loses its possibly dominant term: a subtraction that must not leave
 // rounding debris).  Everything else (tiles, merge path, packed 16-bit count scan, stitching) is the scheme of k_sweep.
-#include "lchd_kcommon.h"
+#include "lchd_sweep_common.h"
 
 namespace lchd {
 
@@ -33,20 +33,6 @@ enum { INC_KL = 1, INC_RENYI = 2 };
 constexpr int kIncTab = 520;              // counts 0 .. 512 (+ padding)
 constexpr int kIncEPL = 6, kIncTile = 64 * kIncEPL, kIncWaves = 4;
 
-__device__ __forceinline__ int inc_merge_path(const uint64_t* A, int nA, const uint64_t* B, int nB, int d) {
-    int lo = max(0, d - nB), hi = min(d, nA);
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (A[mid] <= B[d - 1 - mid]) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ uint64_t inc_spread4(uint64_t x) {  // four 4-bit fields -> four 16-bit fields
-    const uint32_t v = (uint32_t)x;
-    const uint32_t lo = (v & 0xFu) | ((v & 0xF0u) << 12);
-    const uint32_t hi = ((v >> 8) & 0xFu) | ((v & 0xF000u) << 4);
-    return ((uint64_t)hi << 32) | lo;
-}
 static __device__ __noinline__ double inc_log(double x) { return log(x); }
 static __device__ __noinline__ double inc_pow(double x, double y) { return pow(x, y); }
 
@@ -199,7 +185,7 @@ __global__ __launch_bounds__(64 * kIncWaves, 2) void k_sweep_inc(SweepArgs args)
             wave_sync_lds();
             const int epl = (T + 63) >> 6;
             const int d0 = min(lane * epl, T), d1 = min(d0 + epl, T);
-            const int i1 = inc_merge_path(sA, nAt, sB, nBt, d1);
+            const int i1 = merge_path(sA, nAt, sB, nBt, d1);
             int i0 = __shfl_up(i1, 1);
             if (lane == 0) i0 = 0;
             const int iend = __builtin_amdgcn_readlane(i1, 63);
@@ -220,7 +206,7 @@ __global__ __launch_bounds__(64 * kIncWaves, 2) void k_sweep_inc(SweepArgs args)
             }
 #pragma unroll
             for (int k = 0; k < NW; ++k) {
-                const uint64_t va_ = inc_spread4(hA[(k * 4) / 16] >> (((k * 4) % 16) * 4)), vb_ = inc_spread4(hB[(k * 4) / 16] >> (((k * 4) % 16) * 4));
+                const uint64_t va_ = spread4(hA[(k * 4) / 16] >> (((k * 4) % 16) * 4)), vb_ = spread4(hB[(k * 4) / 16] >> (((k * 4) % 16) * 4));
                 const uint64_t sa_ = wave_incl_scan_fields(va_), sb_ = wave_incl_scan_fields(vb_);
                 exA[k] = cntA[k] + sa_ - va_;
                 exB[k] = cntB[k] + sb_ - vb_;
@@ -309,12 +295,7 @@ __global__ __launch_bounds__(64 * kIncWaves, 2) void k_sweep_inc(SweepArgs args)
 
 template <int KIND>
 static void launch_inc_kind(hipStream_t s, int cmax, unsigned grid, const SweepArgs& a) {
-    constexpr int NTH = 64 * kIncWaves;
-    if (cmax <= 8) k_sweep_inc<8, KIND><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 12) k_sweep_inc<12, KIND><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 16) k_sweep_inc<16, KIND><<<grid, NTH, 0, s>>>(a);
-    else if (cmax <= 24) k_sweep_inc<24, KIND><<<grid, NTH, 0, s>>>(a);
-    else k_sweep_inc<32, KIND><<<grid, NTH, 0, s>>>(a);
+    with_slots<kIncSlots>(cmax, [&](auto S) { k_sweep_inc<S, KIND><<<grid, 64 * kIncWaves, 0, s>>>(a); });
 }
 void launch_sweep_inc(hipStream_t s, int kind, int cmax, const SweepArgs& a) {
     const int64_t blocks = (a.n_pairs + kIncWaves - 1) / kIncWaves;

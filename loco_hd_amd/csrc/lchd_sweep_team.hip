@@ -157,24 +157,14 @@ static void launch_team_c(hipStream_t s, bool tile240, unsigned grid, const Swee
 }
 template <int TM>
 static void launch_team_t(hipStream_t s, int cmax, bool tile240, bool pre, unsigned grid, const SweepArgs& a) {
-    // both stores carry prefix-count rows of the width this slot count reads (k_env_group wrote them): the PRE instantiations
-    if constexpr (TM != 1) {
-        if (pre && cmax <= 16) {
-            if (cmax <= 8) launch_team_c<8, TM, true>(s, tile240, grid, a);
-            else if (cmax <= 12) launch_team_c<12, TM, true>(s, tile240, grid, a);
-            else launch_team_c<16, TM, true>(s, tile240, grid, a);
-            return;
+    with_slots<kSweepSlots>(cmax, [&](auto S) {
+        constexpr int CM = (TM != 0 && S > 16) ? 16 : S;  // (weights / Kolmogorov-Smirnov: at most 16 slots, checked by plan_sweep)
+        // both stores carry prefix-count rows of the width this slot count reads (k_env_group wrote them): the PRE instantiations
+        if constexpr (TM != 1 && CM <= 16) {
+            if (pre && cmax <= 16) return launch_team_c<CM, TM, true>(s, tile240, grid, a);
         }
-    }
-    if (cmax <= 8) launch_team_c<8, TM, false>(s, tile240, grid, a);
-    else if (cmax <= 12) launch_team_c<12, TM, false>(s, tile240, grid, a);
-    else if (cmax <= 16 || TM != 0) launch_team_c<16, TM, false>(s, tile240, grid, a);  // (weights / Kolmogorov-Smirnov: at most 16 slots, checked by plan_sweep)
-    else if constexpr (TM == 0) {
-        if (cmax <= 20) launch_team_c<20, 0, false>(s, tile240, grid, a);
-        else if (cmax <= 24) launch_team_c<24, 0, false>(s, tile240, grid, a);
-        else if (cmax <= 28) launch_team_c<28, 0, false>(s, tile240, grid, a);
-        else launch_team_c<32, 0, false>(s, tile240, grid, a);
-    }
+        launch_team_c<CM, TM, false>(s, tile240, grid, a);
+    });
 }
 void launch_team(hipStream_t s, int cmax, int tm, bool tile240, bool pre, unsigned grid, const SweepArgs& a) {
     if (tm == 2) launch_team_t<2>(s, cmax, tile240, pre, grid, a);

@@ -25,13 +25,10 @@ __global__ __launch_bounds__(64 * WPB) void k_sweep_wide(SweepArgs args) {
     constexpr int SH = BIG ? 32 : 16;
     constexpr W kOneA = (W)1, kOneB = (W)1 << SH, kMaskA = kOneB - 1;
     constexpr int TILE = kSweepTile;
-    constexpr bool LDSTAB = false;
     constexpr bool H2 = (MODE != MODE_GEN);
-    constexpr int NT = LDSTAB ? kSqrtTab + 8 : 1;  // sqrt(k), 1/sqrt(k) for k <= 512 in LDS; otherwise read from the global tables
     // Dynamic LDS: per-lane category counts, cnt[wave][category][lane] = count_A | count_B << 16.  A lane only
     // ever touches its own column, and column-major placement makes every access conflict-free.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_dyn[];
-    __shared__ double t_sqrt[NT], t_rsqrt[NT];
     __shared__ double w_s[kLdsCat], sw_s[kLdsCat];
     __shared__ W carry_[WPB][BIG ? 256 : kLdsCat];  // per category: counts before the current tile (A | B << SH)
     __shared__ uint64_t sA_[WPB][TILE], sB_[WPB][TILE];
@@ -42,11 +39,6 @@ __global__ __launch_bounds__(64 * WPB) void k_sweep_wide(SweepArgs args) {
     const int C = cfgp->n_categories;
     const double* __restrict__ g_sqrt = args.sqrt_tab;    // [65536] sqrt(k)
     const double* __restrict__ g_rsqrt = args.rsqrt_tab;  // [65536] 1/sqrt(k)
-    if constexpr (LDSTAB)
-        for (int k = tid; k < NT; k += 64 * WPB) {
-            t_sqrt[k] = g_sqrt[k];
-            t_rsqrt[k] = g_rsqrt[k];
-        }
     for (int c = tid; c < kLdsCat; c += 64 * WPB) {
         const double wv_ = (!HUGE && c < C) ? cfgp->cat_w[c] : 0.0;
         w_s[c] = wv_;
@@ -72,14 +64,12 @@ __global__ __launch_bounds__(64 * WPB) void k_sweep_wide(SweepArgs args) {
     // (HUGE: the carry row goes from lane 63 to lane 0 through global memory)
     auto wsync = [&]() { if constexpr (HUGE) { __threadfence(); __builtin_amdgcn_wave_barrier(); } wave_sync_lds(); };
 
-    auto sqrt_cnt = [&](int k) -> double {
-        if constexpr (LDSTAB) return t_sqrt[k];
-        else if constexpr (BIG) return k < 65536 ? g_sqrt[k] : sqrt((double)k);  // (k_fill_sqrt_tables: the same expressions)
+    auto sqrt_cnt = [&](int k) -> double {  // (the sqrt tables are read from global memory)
+        if constexpr (BIG) return k < 65536 ? g_sqrt[k] : sqrt((double)k);  // (k_fill_sqrt_tables: the same expressions)
         else return g_sqrt[k];
     };
     auto rsqrt_cnt = [&](int k) -> double {
-        if constexpr (LDSTAB) return t_rsqrt[k];
-        else if constexpr (BIG) return k < 65536 ? g_rsqrt[k] : 1.0 / sqrt((double)k);
+        if constexpr (BIG) return k < 65536 ? g_rsqrt[k] : 1.0 / sqrt((double)k);
         else return g_rsqrt[k];
     };
     auto scan_counts = [&](W x) -> W {  // inclusive wave scan of both halves at once (no half overflows: counts stay below 2^SH)
@@ -333,36 +323,29 @@ __global__ __launch_bounds__(64 * WPB) void k_sweep_wide(SweepArgs args) {
     }
 }
 
-
+template <int MODE, int WPB, bool CAT16 = false, bool BIG = false, bool HUGE = false>
+static void launch_wide_f(hipStream_t s, int fmode, unsigned grid, size_t dyn, const SweepArgs& a) {
+    if (fmode == F_KEY) k_sweep_wide<MODE, F_KEY, WPB, CAT16, BIG, HUGE><<<grid, 64 * WPB, dyn, s>>>(a);
+    else k_sweep_wide<MODE, F_ANY, WPB, CAT16, BIG, HUGE><<<grid, 64 * WPB, dyn, s>>>(a);
+}
 template <int MODE>
 static void launch_sweep_wide_m(hipStream_t s, int n_cat, int64_t n_pairs, int fmode, const SweepArgs& a) {
     // dynamic LDS = WPB * C * 64 * 4 bytes of per-lane count columns
     // environments of more than 65 535 points: 64-bit count words (<= 255 categories: the host checks).  16-bit ids never come here: their
     // environments hold at most 65 535 points, but a dense row of 32 769 .. 65 535 points has a store stride of 65 536, and this form reads
     // one-byte ids and 24-bit lengths from the pair records (a 16-bit id above the length: reads far beyond the environment)
+    const unsigned grid1 = (unsigned)(n_pairs < 8192 ? n_pairs : 8192);  // one pair per workgroup
     if (!a.env_a.cat16 && (a.env_a.stride > 65535 || a.env_b.stride > 65535)) {
-        const unsigned grid = (unsigned)(n_pairs < 8192 ? n_pairs : 8192);
-        const size_t dyn = (size_t)n_cat * 512;
-        if (fmode == F_KEY) k_sweep_wide<MODE, F_KEY, 1, false, true><<<grid, 64, dyn, s>>>(a);
-        else k_sweep_wide<MODE, F_ANY, 1, false, true><<<grid, 64, dyn, s>>>(a);
+        launch_wide_f<MODE, 1, false, true>(s, fmode, grid1, (size_t)n_cat * 512, a);
     } else if (n_cat <= 64) {
         const int64_t blocks = (n_pairs + 3) / 4;
-        const unsigned grid = (unsigned)(blocks < 4096 ? blocks : 4096);
-        const size_t dyn = (size_t)4 * n_cat * 256;
-        if (fmode == F_KEY) k_sweep_wide<MODE, F_KEY, 4><<<grid, 256, dyn, s>>>(a);
-        else k_sweep_wide<MODE, F_ANY, 4><<<grid, 256, dyn, s>>>(a);
+        launch_wide_f<MODE, 4>(s, fmode, (unsigned)(blocks < 4096 ? blocks : 4096), (size_t)4 * n_cat * 256, a);
     } else if (n_cat > kWideCategories) {  // the global-memory form (the caller has checked that the scratch block exists)
-        const unsigned grid = (unsigned)std::min<int64_t>(n_pairs, a.wide_scratch_waves);
-        if (fmode == F_KEY) k_sweep_wide<MODE, F_KEY, 1, true, false, true><<<grid, 64, 0, s>>>(a);
-        else k_sweep_wide<MODE, F_ANY, 1, true, false, true><<<grid, 64, 0, s>>>(a);
+        launch_wide_f<MODE, 1, true, false, true>(s, fmode, (unsigned)std::min<int64_t>(n_pairs, a.wide_scratch_waves), 0, a);
     } else {
-        const unsigned grid = (unsigned)(n_pairs < 8192 ? n_pairs : 8192);
         const size_t dyn = (size_t)n_cat * 256;  // (> 64 KB from 257 categories' worth on: init_device_kernels raised the limit)
-        if (a.env_a.cat16) {  // more than 255 categories: 16-bit ids in the store
-            if (fmode == F_KEY) k_sweep_wide<MODE, F_KEY, 1, true><<<grid, 64, dyn, s>>>(a);
-            else k_sweep_wide<MODE, F_ANY, 1, true><<<grid, 64, dyn, s>>>(a);
-        } else if (fmode == F_KEY) k_sweep_wide<MODE, F_KEY, 1><<<grid, 64, dyn, s>>>(a);
-        else k_sweep_wide<MODE, F_ANY, 1><<<grid, 64, dyn, s>>>(a);
+        if (a.env_a.cat16) launch_wide_f<MODE, 1, true>(s, fmode, grid1, dyn, a);  // more than 255 categories: 16-bit ids in the store
+        else launch_wide_f<MODE, 1>(s, fmode, grid1, dyn, a);
     }
 }
 
@@ -371,26 +354,18 @@ void launch_sweep_wide(hipStream_t s, int mode, int n_cat, int64_t n_pairs, int 
     else if (mode == MODE_H2U) launch_sweep_wide_m<MODE_H2U>(s, n_cat, n_pairs, fmode, a);
     else launch_sweep_wide_m<MODE_H2W>(s, n_cat, n_pairs, fmode, a);
 }
+// the one-pair-per-workgroup instantiations whose count columns may exceed 64 KB of dynamic LDS: 8-bit ids, 64-bit counts, 16-bit ids
+template <int MODE, int FMODE>
+static void raise_wide_lds() {
+    const struct { const void* fn; int bytes; } list[] = {{reinterpret_cast<const void*>(&k_sweep_wide<MODE, FMODE, 1>), 256 * 256},
+                                                          {reinterpret_cast<const void*>(&k_sweep_wide<MODE, FMODE, 1, false, true>), 256 * 512},
+                                                          {reinterpret_cast<const void*>(&k_sweep_wide<MODE, FMODE, 1, true>), kWideCategories * 256}};
+    for (const auto& e : list) (void)hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, e.bytes);
+}
+template <int... MODE>
+static void raise_wide_lds_modes() { (..., (raise_wide_lds<MODE, F_KEY>(), raise_wide_lds<MODE, F_ANY>())); }
 void init_sweep_wide_kernels() {
-    auto raise = [](const void* fn, int bytes) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_GEN, F_KEY, 1>), 256 * 256);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_GEN, F_ANY, 1>), 256 * 256);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_H2U, F_KEY, 1>), 256 * 256);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_H2U, F_ANY, 1>), 256 * 256);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_H2W, F_KEY, 1>), 256 * 256);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_H2W, F_ANY, 1>), 256 * 256);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_GEN, F_KEY, 1, false, true>), 256 * 512);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_GEN, F_ANY, 1, false, true>), 256 * 512);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_H2U, F_KEY, 1, false, true>), 256 * 512);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_H2U, F_ANY, 1, false, true>), 256 * 512);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_H2W, F_KEY, 1, false, true>), 256 * 512);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_H2W, F_ANY, 1, false, true>), 256 * 512);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_GEN, F_KEY, 1, true>), kWideCategories * 256);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_GEN, F_ANY, 1, true>), kWideCategories * 256);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_H2U, F_KEY, 1, true>), kWideCategories * 256);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_H2U, F_ANY, 1, true>), kWideCategories * 256);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_H2W, F_KEY, 1, true>), kWideCategories * 256);
-    raise(reinterpret_cast<const void*>(&k_sweep_wide<MODE_H2W, F_ANY, 1, true>), kWideCategories * 256);
+    raise_wide_lds_modes<MODE_GEN, MODE_H2U, MODE_H2W>();
     (void)hipGetLastError();
 }
 

@@ -28,25 +28,6 @@ __device__ __forceinline__ bool pair_is_small(int rule, int nA, int nB) {
 constexpr double kExactH2Below = 1e-6;
 constexpr int kTeamExactUnrollMax = 8;  // category slots up to which the (rare) literal Hellinger form of k_sweep_duo is unrolled (above: a rolled loop -- the unrolled look-ups of 12+ slots cost registers in the event loop)
 
-__device__ __forceinline__ int merge_path(const uint64_t* A, int nA, const uint64_t* B, int nB, int d) {
-    int lo = max(0, d - nB), hi = min(d, nA);
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (A[mid] <= B[d - 1 - mid]) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// spread the eight 4-bit fields of the low 32 bits of x into eight 8-bit fields
-__device__ __forceinline__ uint64_t spread8(uint64_t x) {
-    const uint32_t v = (uint32_t)x;
-    auto half = [](uint32_t h) -> uint32_t {  // four nibbles (16 bits) -> four bytes
-        const uint32_t t = (h | (h << 8)) & 0x00FF00FFu;
-        return (t | (t << 4)) & 0x0F0F0F0Fu;
-    };
-    return ((uint64_t)half(v >> 16) << 32) | half(v & 0xFFFFu);
-}
-
 // sqrt for x in [0, ~1]: v_rsq_f64 seed + Goldschmidt refinement (the same scheme the compiler's IEEE sqrt uses, minus
 // its range scaling and special-case fix-ups, which H^2 in [0, 1] never needs).  Result within 1 ulp; sqrt(0) = 0.
 __device__ __forceinline__ double sqrt_unit(double x) {

@@ -337,3 +337,65 @@ def test_unusable_pair_has_one_nan_writer(name, oracle, monkeypatch):
     assert float(np.max(np.abs(np.delete(got, at) - want))) <= TIGHT
     assert sess.last_sweep() is None
     sess.close()
+
+
+# The slot count of a pass -- which instantiation of the register-resident sweeps runs -- comes from one table per family (kSweepSlots /
+# kIncSlots, lchd_device.h), read by the launchers and by the planner alike: for every category count of 1 .. 32 the slots the session
+# records after a real call equal the slots lchd_plan_sweep returns for the same query, and the scores are the oracle's.  Two random clouds
+# of 1500 atoms in a box of 20 units, threshold 8, anchors next to the centre: environments of a few hundred points (more than 255: no
+# small-pair rule applies; at most 512: the LDS-table forms), so every pair spans more than one tile of 384 events and every lane's chunk
+# holds several events.  64 pairs: the one-launch form of the default configuration, the regular pipeline with LCHD_NO_INLINE_META (the
+# plain sweep does the work, both team forms and the companion are launched next to it) and the incremental sweep of Kullback-Leibler.
+SLOT_FAMILIES = {
+    "inline": (INLINE, {}, {}, 0),
+    "plain": (PLAIN, {"LCHD_NO_INLINE_META": "1"}, {}, N.HOOK_NO_INLINE_META),
+    "inc": (INC, {}, KL, 0),
+}
+SLOT_THR, SLOT_BOX, SLOT_ATOMS, SLOT_PAIRS = 8.0, 20.0, 1500, 64
+
+
+@pytest.mark.parametrize("family", list(SLOT_FAMILIES))
+def test_recorded_slots_are_the_planned_slots(family, oracle, monkeypatch):
+    import ctypes as C
+
+    import torch
+
+    import loco_hd_amd as lh
+    from loco_hd_amd.device import DeviceSession
+
+    fam, env, cfg, hooks = SLOT_FAMILIES[family]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    rng = np.random.default_rng(7300)
+    xa, xb = rng.uniform(0.0, SLOT_BOX, (SLOT_ATOMS, 3)), rng.uniform(0.0, SLOT_BOX, (SLOT_ATOMS, 3))
+    near = [np.argsort(np.linalg.norm(x - SLOT_BOX / 2, axis=1))[:SLOT_PAIRS] for x in (xa, xb)]
+    pairs = np.stack([near[0], near[1][::-1]], 1).astype(np.int64)
+    ra, rb = rng.integers(0, 1 << 20, SLOT_ATOMS), rng.integers(0, 1 << 20, SLOT_ATOMS)
+    tag = np.zeros(SLOT_ATOMS, dtype=np.int32)
+    bad = []
+    for ncat in range(1, 33):
+        c = dict(ncat=ncat, cfg=cfg)
+        ca, cb = (ra % ncat).astype(np.int32), (rb % ncat).astype(np.int32)
+        lo = build(oracle, c)
+        lo.n_threads = 8
+        want, sizes = lo.from_arrays(xa, ca, tag, xb, cb, tag, pairs, SLOT_THR, return_env_sizes=True)
+        want, sizes = np.asarray(want), np.asarray(sizes)
+        assert sizes.min() > 255 and sizes.max() <= 512 and (sizes.sum(axis=1) - 2 > 384).all(), (sizes.min(), sizes.max())
+        sess = DeviceSession(build(lh, c))
+        out = torch.full((SLOT_PAIRS,), SENTINEL, dtype=torch.float64, device="cuda")
+        sess.from_primitives(sess.upload(xa, ca), sess.upload(xb, cb), torch.from_numpy(pairs).cuda(), SLOT_THR, out=out)
+        got, seen = out.cpu().numpy(), sess.last_sweep()
+        sess.close()
+        q = N.SweepQueryC(n_pairs=SLOT_PAIRS, n_categories=ncat, force_cmax=0, hellinger2=0 if cfg else 1, unit_weights=1, wf_pow=0,
+                          sd_fast=1 if cfg else 0, has_wf_index=0, has_left_list=1, stride_a=512, stride_b=512, cdf_keys_a=1, cdf_keys_b=1,
+                          pre_rows=0, hint_bits=0, hooks=hooks)
+        plan = N.SweepPlanC()
+        assert N.lib().lchd_plan_sweep(C.byref(q), C.byref(plan)) == 0
+        err = float(np.max(np.abs(got - want)))
+        print(f"{family} {ncat} categories: families {seen['families']:#x} (planned {plan.families:#x}) slots {seen['slots']} (planned {plan.slots}) "
+              f"environments {sizes.min()} .. {sizes.max()} points; max |gpu - oracle| = {err:.3e}")
+        ok = (seen["families"] & fam and seen["families"] == plan.families and seen["slots"] == plan.slots and seen["rule"] == -1
+              and not np.isnan(got).any() and not (got == SENTINEL).any() and err <= TIGHT)
+        if not ok:
+            bad.append((ncat, seen["families"], plan.families, seen["slots"], plan.slots, err))
+    assert not bad, bad
