@@ -251,6 +251,44 @@ double lchd_frames_last_convert_ms(lchd_ctx *ctx, lchd_cloud *frames);
 /* Coordinates of a cloud / frames buffer back on the host as [n][3] f64 (n must equal the atoms it holds). */
 int lchd_cloud_get_coords(lchd_ctx *ctx, lchd_cloud *cloud, double *xyz_out, int64_t n);
 
+/* ---- periodic boundaries (additive) ---------------------------------------------------------------
+ * The reference searches an open system: KdTree::within_radius over the structure's own atoms (src/locohd.rs:504-528).  MD boxes are
+ * periodic; the calls below extend that search to an ORTHORHOMBIC box (Lx, Ly, Lz), all edges finite and > 0.  With a box, the
+ * environment of an anchor holds every periodic image of every atom of its structure whose distance to the anchor is < the
+ * threshold (the same strict comparison of squared distances), the anchor itself always; an image passes or fails the tag rule as
+ * its atom would (an image is a different atom with the same category and tag).  For a threshold <= L / 2 this is the minimum-image
+ * convention; for L / 2 < threshold <= L an atom may enter through two images, as it would for a kd-tree over the replicated system.
+ * Periodicity is resolved in front of the search: an IMAGE CLOUD holds the wrapped atoms of its source at their indices 0 .. n - 1
+ * (anchor lists stay valid) and, behind them, the images ("ghosts") that lie within `reach` of the box; the cell lists, environment
+ * and sweep kernels then run on it as on any other cloud.
+ *   wrap    w = x - floor(x / L) * L per axis, and w = 0 if that rounds to L
+ *   images  w + L is emitted iff w < reach, w - L iff w >= L - reach, each computed as that single f64 addition; a ghost is any
+ *           combination of per-axis choices other than "all original" (up to 26 per atom), written in ascending image code
+ *           cx + 3 cy + 9 cz (c = 0 original, 1 +L, 2 -L) behind the ghosts of the atoms in front: the cloud is a function of its input
+ *   reach   threshold_distance <= reach <= min(Lx, Ly, Lz): one layer of images suffices and an anchor never meets its own image
+ * Triclinic cells, the dense from_coords / from_dmxs paths and device groups are out of scope. */
+/* Host only, no device: LCHD_EVALUE for a non-finite or non-positive edge or reach, or reach > the smallest edge of a box. */
+int lchd_box_validate(const double *boxes /* [n_boxes][3] */, int32_t n_boxes, double reach);
+/* The image cloud of `src` -- a single structure, a batch (ragged included) or a frames buffer (the frames loaded last).  boxes: HOST
+ * [n_boxes][3], n_boxes = 1 (one box for every structure) or the number of structures.  The work runs on the context's stream, behind
+ * the source's pending upload (the events lchd_from_primitives_dev uses); the call reads ONE total back to size the output -- a small
+ * synchronising copy -- and the ghosts are queued behind it.  The result is an ordinary lchd_cloud (its structures and structure ids
+ * are the source's; destroy it with lchd_cloud_destroy) with two differences: lchd_from_primitives_dev / _async return LCHD_EVALUE for
+ * a threshold_distance beyond its reach, and lchd_cloud_set_coords / lchd_frames_load* on it are LCHD_EVALUE.  A non-finite source
+ * coordinate is LCHD_EVALUE. */
+int lchd_cloud_create_images(lchd_ctx *ctx, lchd_cloud *src, const double *boxes, int32_t n_boxes, double reach, lchd_cloud **out);
+/* Rebuild an image cloud in place from the current coordinates of `src` (trajectories: once per chunk).  Its arrays only grow.  Waits
+ * for the context's stream (the last pass over the image cloud) and, like the call above, for the one total. */
+int lchd_cloud_update_images(lchd_ctx *ctx, lchd_cloud *images, lchd_cloud *src, const double *boxes, int32_t n_boxes);
+/* Atoms one workgroup of the image kernels covers: beyond it the exclusive scan of the ghost counts takes its two-level form. */
+int32_t lchd_images_scan_span(void);
+/* lchd_from_primitives in periodic boxes: box_a / box_b are HOST (Lx, Ly, Lz) of the two structures, NULL for a non-periodic side.
+ * Uploads both structures, builds the image cloud of every side that has a box with reach = threshold_distance, and scores. */
+int lchd_from_primitives_periodic(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a,
+                                  const int32_t *tag_a, int64_t n_a, const double *xyz_b, const int32_t *cat_b,
+                                  const int32_t *tag_b, int64_t n_b, const int64_t *anchors, const int32_t *wf_index,
+                                  int64_t n_pairs, double threshold_distance, const double *box_a, const double *box_b, double *out);
+
 /* ---- multi-GPU ------------------------------------------------------------------------------------
  * The reference's parallelism lives INSIDE the core call: a thread pool that is a field of `LoCoHD` (src/locohd.rs:53,
  * 373-383) runs the anchor pairs of one call (:545-557, order-preserving collect).  The counterpart here is a GROUP of

@@ -63,10 +63,21 @@ def parse_cli_args(argv: Optional[Sequence[str]] = None) -> Namespace:
     parser = ArgumentParser(prog="python -m loco_hd_amd", description="LoCoHD scores of anchor pairs of two PDB structures (MI355X)")
     for short, long_, kind, default, required, text in _FLAGS:
         parser.add_argument(short, long_, type=kind, default=default, required=required, help=text)
+    parser.add_argument("--periodic", action="store_true",
+                        help="periodic boundaries: each structure in the orthorhombic box of its CRYST1 record (additive)")
     ns = parser.parse_args(argv)
     for key in ("tag_pairing_rule_args", "weight_function_args"):
         setattr(ns, key, json.loads(getattr(ns, key)))
     return ns
+
+
+def orthorhombic_box(cell, path) -> Tuple[float, float, float]:
+    """(a, b, c) of a CRYST1 cell; SystemExit with a message where --periodic cannot use the structure."""
+    if cell is None:
+        raise SystemExit(f"--periodic: {path} has no CRYST1 record, so its periodic box is unknown")
+    if any(abs(angle - 90.0) > 1e-3 for angle in cell[3:]):
+        raise SystemExit(f"--periodic: the cell of {path} has angles {cell[3:]}; only orthorhombic boxes (90, 90, 90) are supported")
+    return cell[:3]
 
 
 def run(args: Namespace) -> List[str]:
@@ -75,8 +86,12 @@ def run(args: Namespace) -> List[str]:
         pair_strs = f.read().replace("\n", "").split(";")
     anchor_pairing = parse_anchor_pairing(pair_strs)
 
-    structure1 = PDBParser(QUIET=True).get_structure("s1", args.structure1)[args.model_number]
-    structure2 = PDBParser(QUIET=True).get_structure("s2", args.structure2)[args.model_number]
+    parsed1 = PDBParser(QUIET=True).get_structure("s1", args.structure1)
+    parsed2 = PDBParser(QUIET=True).get_structure("s2", args.structure2)
+    boxes = {}
+    if getattr(args, "periodic", False):
+        boxes = {"box_a": orthorhombic_box(parsed1.cell, args.structure1), "box_b": orthorhombic_box(parsed2.cell, args.structure2)}
+    structure1, structure2 = parsed1[args.model_number], parsed2[args.model_number]
     assigner = PrimitiveAssigner(Path(args.primitive_typing_scheme))
     templates1 = assigner.assign_primitive_structure(structure1)
     templates2 = assigner.assign_primitive_structure(structure2)
@@ -86,7 +101,7 @@ def run(args: Namespace) -> List[str]:
     lchd = LoCoHD(assigner.all_primitive_types, WeightFunction(**args.weight_function_args),
                   TagPairingRule(args.tag_pairing_rule_args), args.number_of_threads)
     scores = lchd.from_primitives(list(map(prat_to_pra, templates1)), list(map(prat_to_pra, templates2)), anchor_pairs,
-                                  args.upper_distance_cutoff)
+                                  args.upper_distance_cutoff, **boxes)
     return [f"LoCoHD({s}) = {score}" for s, score in zip(pair_strs, scores)]
 
 

@@ -92,6 +92,11 @@ _PROTOS = {
     "lchd_from_dmxs_ragged": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _i64, _i64, _IP, _DP, _i64, _i64, _IP, _IP, _DP]),
     "lchd_from_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _i64, _DP, _i64, _IP, _DP]),
     "lchd_from_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _DP]),
+    "lchd_from_primitives_periodic": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _DP, _DP, _DP]),
+    "lchd_box_validate": (C.c_int, [_DP, _i32, _f64]),
+    "lchd_cloud_create_images": (C.c_int, [_VP, _VP, _DP, _i32, _f64, C.POINTER(_VP)]),
+    "lchd_cloud_update_images": (C.c_int, [_VP, _VP, _VP, _DP, _i32]),
+    "lchd_images_scan_span": (_i32, []),
     "lchd_cloud_create": (C.c_int, [_VP, _DP, _IP, _IP, _i64, C.POINTER(_VP)]),
     "lchd_cloud_create_batch": (C.c_int, [_VP, _DP, _IP, _IP, _IP, _i64, _i32, C.POINTER(_VP)]),
     "lchd_cloud_size": (C.c_int64, [_VP]),
@@ -192,7 +197,7 @@ def check(rc: int) -> None:
 
 
 def dp(a):
-    return a.ctypes.data_as(_DP)
+    return None if a is None else a.ctypes.data_as(_DP)
 
 
 def ip(a):

@@ -36,6 +36,24 @@ def _f64(x) -> np.ndarray:
     return np.ascontiguousarray(x, dtype=np.float64)
 
 
+def periodic_boxes(box, n_structures: int, reach: float, what: str = "box") -> np.ndarray:
+    """An orthorhombic box (Lx, Ly, Lz), or one per structure, as a float64 array [n_boxes][3] (n_boxes is 1 or `n_structures`).
+    ValueError for another shape and for what lchd_box_validate rejects (an edge or `reach` that is not finite and > 0, `reach`
+    beyond the smallest edge).  No device is touched."""
+    try:
+        arr = _f64(box)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be three edge lengths (Lx, Ly, Lz)") from None
+    if arr.shape == (3,):
+        arr = arr.reshape(1, 3)
+    elif arr.ndim != 2 or arr.shape[1] != 3:
+        raise ValueError(f"{what} must be three edge lengths (Lx, Ly, Lz), got an array of shape {arr.shape}")
+    if len(arr) not in (1, int(n_structures)):
+        raise ValueError(f"{what}: {len(arr)} boxes given for {n_structures} structures (pass one box, or one per structure)")
+    N.check(N.lib().lchd_box_validate(N.dp(arr), len(arr), float(reach)))
+    return arr
+
+
 class WeightFunction:
     """weight_function.rs:6-120.  ``parameters`` and ``function_name`` are read-only like the pyo3 getters."""
 
@@ -558,11 +576,39 @@ class LoCoHD:
         return start, np.ascontiguousarray(ex[:, 1], dtype=np.int32)
 
     def from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
-                        threshold_distance: float) -> List[float]:
-        """src/locohd.rs:479-567."""
+                        threshold_distance: float, *, box_a=None, box_b=None) -> List[float]:
+        """src/locohd.rs:479-567.
+
+        ``box_a`` / ``box_b`` (keyword-only, additive): an orthorhombic periodic box (Lx, Ly, Lz) of the structure.  Its environments
+        then hold every periodic image of every atom closer than ``threshold_distance`` (<= the smallest edge) to the anchor: the
+        minimum-image convention up to half an edge, beyond it an atom may enter through two images."""
+        if box_a is not None or box_b is not None:
+            return self._from_primitives_periodic(prim_a, prim_b, anchor_pairs, threshold_distance, box_a, box_b)
         pairs, idx = self._anchor_arrays(anchor_pairs)
         pa, pb, interner = self._packed_lists(prim_a, prim_b)
         return self.from_packed(pa, pb, pairs, threshold_distance, wf_index=idx, interner=interner).tolist()
+
+    def _no_device_group_with_box(self) -> None:
+        if self._devices is not None:
+            raise ValueError("a periodic box applies to one device (a device group has no image clouds): drop devices=[...]")
+
+    def _from_primitives_periodic(self, prim_a, prim_b, anchor_pairs, threshold_distance, box_a, box_b) -> List[float]:
+        self._no_device_group_with_box()
+        thr = float(threshold_distance)
+        ba = None if box_a is None else periodic_boxes(box_a, 1, thr, "box_a")
+        bb = None if box_b is None else periodic_boxes(box_b, 1, thr, "box_b")
+        pairs, idx = self._anchor_arrays(anchor_pairs)
+        pa, pb, interner = self._packed_lists(prim_a, prim_b)
+        anchors = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        cfg, keep = self._config(interner)
+        out = np.empty(len(anchors))
+        if len(anchors) == 0:
+            return []
+        xa, xb = _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3)
+        N.check(N.lib().lchd_from_primitives_periodic(self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa),
+                                                      N.dp(xb), N.ip(pb.cat), N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx),
+                                                      len(anchors), thr, N.dp(ba), N.dp(bb), N.dp(out)))
+        return out.tolist()
 
     # The reference's callers score the same structures over and over (one native structure against every decoy,
     # python_codes/casp14/casp14_extend_with_locohd.py:72-79; one reference frame against a trajectory,
@@ -642,7 +688,7 @@ class LoCoHD:
 
     def from_primitives_batch(self, structures: Sequence[Sequence[PrimitiveAtom]],
                               jobs: Sequence[Tuple[int, int, Sequence[Tuple[int, int]]]],
-                              threshold_distance: float) -> List[List[float]]:
+                              threshold_distance: float, *, boxes=None) -> List[List[float]]:
         """Additive: many `from_primitives` calls in one device pass.  `structures` are lists of
         PrimitiveAtoms; a job `(a, b, anchor_pairs)` asks for `from_primitives(structures[a], structures[b],
         anchor_pairs, threshold_distance)`.  Returns one score list per job, each bit-identical to the single call.
@@ -652,7 +698,13 @@ class LoCoHD:
 
         It does NOT reproduce the dense numbers of python_codes/ensembles/compare_ensembles.py:277-296: that script scores
         whole-structure rows (from_dmxs), this call thresholded from_primitives environments.  The script's call is
-        `from_dmxs_ensemble` / `from_coords_ensemble`."""
+        `from_dmxs_ensemble` / `from_coords_ensemble`.
+
+        ``boxes`` (keyword-only, additive): one orthorhombic periodic box (Lx, Ly, Lz) for all structures, or one per structure;
+        every environment then holds the periodic images within ``threshold_distance`` as in ``from_primitives(..., box_a=...)``."""
+        if boxes is not None:  # (checked before anything touches a device)
+            self._no_device_group_with_box()
+            boxes = periodic_boxes(boxes, len(structures), float(threshold_distance), "boxes")
         from .device import DeviceSession  # torch is only needed on this path
 
         if isinstance(self._w_func, dict):
@@ -677,6 +729,8 @@ class LoCoHD:
         try:
             torch = sess.torch
             batch, _ = sess.upload_batch([(pk.xyz, pk.cat, pk.tag) for pk in packed])
+            if boxes is not None:
+                batch = sess.periodic_images(batch, boxes, float(threshold_distance))
             anchors = torch.from_numpy(np.concatenate(flat)).to(torch.device("cuda", sess.device))
             scores = sess.from_primitives(batch, batch, anchors, float(threshold_distance)).cpu().numpy()
         finally:

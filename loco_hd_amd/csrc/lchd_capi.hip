@@ -154,6 +154,15 @@ struct lchd_cloud {
     hipEvent_t ev_ready = nullptr, ev_used = nullptr;
     bool bbox_pending = false, used_valid = false;
     double bbmin[3] = {0, 0, 0}, bbmax[3] = {0, 0, 0};
+    // image cloud (lchd_cloud_create_images): the periodic images of another cloud; d_bbox holds 8 words (the ghost total last)
+    double reach = INFINITY;   // the largest threshold a pass may search this cloud with (+inf: every cloud that is not an image cloud)
+    bool images = false;
+    int64_t img_cap = 0;       // atoms the arrays hold (they only grow)
+    uint32_t *d_img_count = nullptr, *d_img_offset = nullptr;  // [img_scan_cap] ghosts per source atom / their exclusive scan per span
+    unsigned long long* d_img_spans = nullptr;                 // [img_scan_cap / kImgScanSpan + 1]
+    int64_t img_scan_cap = 0;
+    double* d_boxes = nullptr; // [boxes_cap][3]
+    int32_t boxes_cap = 0;
     // wide: the configuration has more than 255 categories (two-byte ids where the structure carries them)
     CloudView view(bool wide) const {
         const bool two = wide && cat_hi;
@@ -835,6 +844,7 @@ extern "C" int lchd_cloud_set_coords(lchd_ctx* c, lchd_cloud* cl, const double* 
     if (!c || !cl || !xyz) return fail(LCHD_EVALUE, "null argument");
     if (c->pend.active && (c->pend.a == cl || c->pend.b == cl))
         return fail(LCHD_EVALUE, "this structure is in use by an unfinished asynchronous call");
+    if (cl->images) return fail(LCHD_EVALUE, "an image cloud takes its coordinates from its source (lchd_cloud_update_images)");
     CTX_GUARD(c);
     return upload_coords(c, cl, xyz);
 }
@@ -859,6 +869,10 @@ extern "C" void lchd_cloud_destroy(lchd_ctx* c, lchd_cloud* cl) {
     (void)hipFree(cl->d_src_idx);
     (void)hipFree(cl->d_tiles);
     (void)hipFree(cl->d_raw32);
+    (void)hipFree(cl->d_img_count);
+    (void)hipFree(cl->d_img_offset);
+    (void)hipFree(cl->d_img_spans);
+    (void)hipFree(cl->d_boxes);
     if (cl->h_pinned32) (void)hipHostFree(cl->h_pinned32);
     if (cl->h_pinned) (void)hipHostFree(cl->h_pinned);
     if (cl->ev_ready) (void)hipEventDestroy(cl->ev_ready);
@@ -1292,6 +1306,8 @@ extern "C" int lchd_from_primitives_dev_async(lchd_ctx* c, lchd_cloud* a, lchd_c
     if (!(thr > 0.0))  // within_radius returns nothing => dists[0] panics (src/locohd.rs:74)
         return fail(LCHD_EPANIC, "index out of bounds: threshold_distance = %g leaves every environment empty", thr);
     if (a->n == 0 || b->n == 0) return fail(LCHD_EPANIC, "index out of bounds: anchor pairs given for an empty structure");
+    if (thr > a->reach || thr > b->reach)  // (an image cloud holds the images within its reach of the box, no others)
+        return fail(LCHD_EVALUE, "threshold_distance = %g is beyond the reach %g the periodic images were built with", thr, std::min(a->reach, b->reach));
     if (!std::isfinite(thr)) thr = 1.7e308;
     CTX_GUARD(c);
     if (int rc = resolve_bbox(c, a)) return rc;
@@ -1549,7 +1565,7 @@ extern "C" int lchd_frames_create(lchd_ctx* c, const lchd_cloud* tmpl, int32_t c
     CTX_LOCK(c);
     if (!c || !tmpl || !out || capacity_frames < 1) return fail(LCHD_EVALUE, "bad argument");
     CTX_GUARD(c);
-    if (tmpl->sid) return fail(LCHD_EVALUE, "the template of a frames buffer must be a single structure");
+    if (tmpl->sid || tmpl->images) return fail(LCHD_EVALUE, "the template of a frames buffer must be a single structure");
     const int64_t nt = tmpl->n, total = nt * capacity_frames;
     if (nt < 1 || total > ((int64_t)1 << 30)) return fail(LCHD_EUNSUPPORTED, "frames buffer of %lld atoms is out of range", (long long)total);
     lchd_cloud* cl = new lchd_cloud();
@@ -1759,6 +1775,154 @@ extern "C" int lchd_cloud_get_coords(lchd_ctx* c, lchd_cloud* cl, double* xyz_ou
     for (int64_t i = 0; i < n; ++i)
         for (int k = 0; k < 3; ++k) xyz_out[3 * i + k] = soa[(size_t)k * n + i];
     return LCHD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// periodic boundaries: the periodic images of a cloud as a cloud (kernels: lchd_images.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int32_t lchd_images_scan_span(void) { return kImgScanSpan; }
+
+extern "C" int lchd_box_validate(const double* boxes, int32_t n_boxes, double reach) {
+    if (!boxes || n_boxes < 1) return fail(LCHD_EVALUE, "a periodic box is three edge lengths (Lx, Ly, Lz); none given");
+    if (!std::isfinite(reach) || !(reach > 0.0)) return fail(LCHD_EVALUE, "the reach of the periodic images must be finite and > 0, got %g", reach);
+    for (int32_t b = 0; b < n_boxes; ++b)
+        for (int k = 0; k < 3; ++k) {
+            const double L = boxes[3 * (size_t)b + k];
+            if (!std::isfinite(L) || !(L > 0.0)) return fail(LCHD_EVALUE, "box %d: edge %d is %g; every edge must be finite and > 0", b, k, L);
+            if (reach > L)
+                return fail(LCHD_EVALUE, "box %d: the reach %g exceeds the edge %g; one layer of periodic images covers a threshold up to the smallest edge", b, reach, L);
+        }
+    return LCHD_OK;
+}
+
+template <class T>
+static int grow_array(T*& p, size_t n) {
+    (void)hipFree(p);
+    p = nullptr;
+    HIP_TRY(hipMalloc(&p, sizeof(T) * std::max<size_t>(n, 1)));
+    return LCHD_OK;
+}
+static int images_reserve(lchd_cloud* img, const lchd_cloud* src, int64_t cap) {  // (the stream is idle: nothing reads the arrays)
+    if (cap <= img->img_cap && (!src->cat_hi || img->cat_hi) && (!src->sid || img->sid)) return LCHD_OK;
+    cap = std::max(cap, img->img_cap);
+    img->img_cap = 0;
+    if (int rc = grow_array(img->x, (size_t)cap)) return rc;
+    if (int rc = grow_array(img->y, (size_t)cap)) return rc;
+    if (int rc = grow_array(img->z, (size_t)cap)) return rc;
+    if (int rc = grow_array(img->cat, (size_t)cap)) return rc;
+    if (int rc = grow_array(img->tag, (size_t)cap)) return rc;
+    if (src->cat_hi) {
+        if (int rc = grow_array(img->cat_hi, (size_t)cap)) return rc;
+        if (int rc = grow_array(img->cat_narrow, (size_t)cap)) return rc;
+    }
+    if (src->sid)
+        if (int rc = grow_array(img->sid, (size_t)cap)) return rc;
+    img->img_cap = cap;
+    return LCHD_OK;
+}
+
+// count -> scan -> (read the total back, size the arrays) -> emit, on the context's stream behind the source's pending upload
+static int images_build(lchd_ctx* c, lchd_cloud* img, lchd_cloud* src, const double* boxes, int32_t n_boxes) {
+    if (n_boxes != 1 && n_boxes != src->n_struct)
+        return fail(LCHD_EVALUE, "%d boxes given for %d structures: pass one box, or one per structure", n_boxes, src->n_struct);
+    if (int rc = lchd_box_validate(boxes, n_boxes, img->reach)) return rc;
+    if (src->images) return fail(LCHD_EVALUE, "the source of an image cloud must not be an image cloud");
+    if (c->pend.active && (c->pend.a == img || c->pend.b == img))
+        return fail(LCHD_EVALUE, "this image cloud is in use by an unfinished asynchronous call");
+    const int64_t n = src->n;
+    if (n > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "periodic images of %lld atoms: at most 2^27", (long long)n);
+    hipStream_t s = c->stream;
+    img->n = 0;  // (until the build has succeeded)
+    img->n_struct = src->n_struct;
+    img->struct_size = 0;
+    HIP_TRY(hipStreamSynchronize(s));  // the last pass over the image cloud has read its arrays; they may move now
+    if (n > img->img_scan_cap) {
+        const int64_t cap = n + n / 4;
+        img->img_scan_cap = 0;
+        if (int rc = grow_array(img->d_img_count, (size_t)cap)) return rc;
+        if (int rc = grow_array(img->d_img_offset, (size_t)cap)) return rc;
+        if (int rc = grow_array(img->d_img_spans, (size_t)(cap / kImgScanSpan + 1))) return rc;
+        img->img_scan_cap = cap;
+    }
+    if (n_boxes > img->boxes_cap) {
+        img->boxes_cap = 0;
+        if (int rc = grow_array(img->d_boxes, (size_t)3 * n_boxes)) return rc;
+        img->boxes_cap = n_boxes;
+    }
+    if (!img->d_bbox) HIP_TRY(hipMalloc(&img->d_bbox, sizeof(unsigned long long) * 8));
+    if (int rc = images_reserve(img, src, 2 * n + 64)) return rc;
+    if (n == 0) { for (int k = 0; k < 3; ++k) img->bbmin[k] = img->bbmax[k] = 0.0; return LCHD_OK; }
+    HIP_TRY(hipMemcpyAsync(img->d_boxes, boxes, sizeof(double) * 3 * (size_t)n_boxes, hipMemcpyHostToDevice, s));
+    if (src->ev_ready && src->cap_frames) HIP_TRY(hipStreamWaitEvent(s, src->ev_ready, 0));  // (a frames buffer is filled on another stream)
+    ImageArgs ia{};
+    ia.src = CloudView{src->x, src->y, src->z, src->cat, src->cat_hi, src->tag, (int32_t)n, src->sid, src->n_struct, 0};
+    ia.src_narrow = src->cat_narrow;
+    ia.boxes = img->d_boxes;
+    ia.n_boxes = n_boxes;
+    ia.reach = img->reach;
+    ia.count = img->d_img_count;
+    ia.offset = img->d_img_offset;
+    ia.span_sum = n > kImgScanSpan ? img->d_img_spans : nullptr;
+    ia.bbox = img->d_bbox;
+    auto point_at_arrays = [&] {
+        ia.x = img->x; ia.y = img->y; ia.z = img->z;
+        ia.cat = img->cat;
+        ia.cat_hi = src->cat_hi ? img->cat_hi : nullptr;
+        ia.cat_narrow = src->cat_hi ? img->cat_narrow : nullptr;
+        ia.tag = img->tag;
+        ia.sid = src->sid ? img->sid : nullptr;
+        ia.capacity = img->img_cap;
+    };
+    point_at_arrays();
+    launch_img_count(s, ia);
+    launch_img_scan(s, ia);
+    unsigned long long k[8];
+    HIP_TRY(hipMemcpyAsync(k, img->d_bbox, sizeof k, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (k[6]) return fail(LCHD_EVALUE, src->cap_frames ? "non-finite coordinate in a trajectory frame" : "non-finite coordinate in the source of the periodic images");
+    const int64_t total = n + (int64_t)k[7];
+    if (total > ((int64_t)1 << 30)) return fail(LCHD_EUNSUPPORTED, "%lld atoms and periodic images exceed a cloud", (long long)total);
+    if (total > img->img_cap) {  // grow (with a margin: the rim population of a trajectory drifts) and wrap into the new arrays
+        if (int rc = images_reserve(img, src, total + total / 4)) return rc;
+        point_at_arrays();
+        launch_img_count(s, ia);
+    }
+    launch_img_emit(s, ia);
+    if (src->ev_used) { HIP_TRY(hipEventRecord(src->ev_used, s)); src->used_valid = true; }  // (a later load into the source waits for the emit)
+    HIP_TRY(hipGetLastError());
+    auto dec = [](unsigned long long u) { u = (u >> 63) ? (u ^ 0x8000000000000000ull) : ~u; double d; memcpy(&d, &u, 8); return d; };
+    for (int q = 0; q < 3; ++q) { img->bbmin[q] = dec(k[q]); img->bbmax[q] = dec(k[3 + q]); }
+    if (!src->cat_hi && img->cat_hi) {  // (the arrays outlive a source with wide ids: this source has none)
+        (void)hipFree(img->cat_hi); (void)hipFree(img->cat_narrow);
+        img->cat_hi = img->cat_narrow = nullptr;
+    }
+    if (!src->sid && img->sid) { (void)hipFree(img->sid); img->sid = nullptr; }
+    img->n = total;
+    return LCHD_OK;
+}
+
+extern "C" int lchd_cloud_create_images(lchd_ctx* c, lchd_cloud* src, const double* boxes, int32_t n_boxes, double reach, lchd_cloud** out) {
+    CTX_LOCK(c);
+    if (!c || !src || !out) return fail(LCHD_EVALUE, "null argument");
+    *out = nullptr;
+    CTX_GUARD(c);
+    lchd_cloud* img = new lchd_cloud();
+    img->images = true;
+    img->reach = reach;
+    if (int rc = images_build(c, img, src, boxes, n_boxes)) {
+        lchd_cloud_destroy(c, img);
+        return rc;
+    }
+    *out = img;
+    return LCHD_OK;
+}
+
+extern "C" int lchd_cloud_update_images(lchd_ctx* c, lchd_cloud* img, lchd_cloud* src, const double* boxes, int32_t n_boxes) {
+    CTX_LOCK(c);
+    if (!c || !img || !src) return fail(LCHD_EVALUE, "null argument");
+    if (!img->images) return fail(LCHD_EVALUE, "not an image cloud (lchd_cloud_create_images)");
+    CTX_GUARD(c);
+    return images_build(c, img, src, boxes, n_boxes);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1982,6 +2146,54 @@ extern "C" int lchd_from_primitives(lchd_ctx* c, const lchd_config* cfg, const d
     HostCall hc;
     if (int rc = host_call_enqueue(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, nullptr, n_pairs, thr, hc)) return rc;
     return host_call_finish(c, hc, nullptr, out);
+}
+
+// from_primitives in a periodic box: both structures go to the device as clouds of their own, a side with a box is replaced by its
+// image cloud (reach = the threshold) and the pass runs as for any two clouds.  lchd_from_primitives above is untouched.
+extern "C" int lchd_from_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a,
+                                             const int32_t* tag_a, int64_t n_a, const double* xyz_b, const int32_t* cat_b,
+                                             const int32_t* tag_b, int64_t n_b, const int64_t* anchors, const int32_t* wf_index,
+                                             int64_t n_pairs, double thr, const double* box_a, const double* box_b, double* out) {
+    CTX_LOCK(c);
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = check_wf_index(cfg, wf_index, n_pairs)) return rc;
+    if (n_a < 0 || n_b < 0 || n_a > ((int64_t)1 << 27) || n_b > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "structure size out of range");
+    if (box_a) if (int rc = lchd_box_validate(box_a, 1, thr)) return rc;
+    if (box_b) if (int rc = lchd_box_validate(box_b, 1, thr)) return rc;
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (n_pairs > 0 && (!anchors || !out)) return fail(LCHD_EVALUE, "null anchor / score pointer");
+    for (int64_t p = 0; p < n_pairs; ++p)  // (an index beyond the structure would name a ghost atom of the image cloud)
+        if (anchors[2 * p] < 0 || anchors[2 * p] >= n_a || anchors[2 * p + 1] < 0 || anchors[2 * p + 1] >= n_b)
+            return fail(LCHD_EPANIC, "index out of bounds: an anchor index is outside its structure (src/locohd.rs:521)");
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    if (n_pairs <= 0) return LCHD_OK;
+    lchd_cloud *ca = nullptr, *cb = nullptr, *ia = nullptr, *ib = nullptr;
+    char* d_blk = nullptr;
+    const size_t o_wf = sizeof(int64_t) * 2 * (size_t)n_pairs, o_out = (o_wf + sizeof(int32_t) * (size_t)n_pairs + 255) & ~size_t(255);
+    auto run = [&]() -> int {
+        if (int rc = lchd_cloud_create(c, xyz_a, cat_a, tag_a, n_a, &ca)) return rc;
+        if (int rc = lchd_cloud_create(c, xyz_b, cat_b, tag_b, n_b, &cb)) return rc;
+        if (box_a) if (int rc = lchd_cloud_create_images(c, ca, box_a, 1, thr, &ia)) return rc;
+        if (box_b) if (int rc = lchd_cloud_create_images(c, cb, box_b, 1, thr, &ib)) return rc;
+        HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)n_pairs));
+        HIP_TRY(hipMemcpy(d_blk, anchors, o_wf, hipMemcpyHostToDevice));
+        if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice));
+        if (int rc = lchd_from_primitives_dev(c, ia ? ia : ca, ib ? ib : cb, reinterpret_cast<const int64_t*>(d_blk),
+                                              wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, n_pairs, thr,
+                                              reinterpret_cast<double*>(d_blk + o_out)))
+            return rc;
+        HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost));
+        return LCHD_OK;
+    };
+    const int rc = run();
+    const std::string msg = g_err;  // (the clean-up below makes calls of its own)
+    c->last_valid = false;  // the anchors and the clouds of this call go away
+    c->pend.a = c->pend.b = nullptr;
+    for (lchd_cloud* cl : {ia, ib, ca, cb}) lchd_cloud_destroy(c, cl);
+    (void)hipFree(d_blk);
+    if (rc) snprintf(g_err, sizeof g_err, "%s", msg.c_str());
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -386,6 +386,26 @@ void launch_frames_centroids(hipStream_t s, const float* raw, int64_t n_src, con
                              unsigned long long* bbox7, unsigned long long* bbox_part /* [bbox_parts_capacity()][7] */);
 int centroid_tile_span();
 int bbox_parts_capacity();
+// Periodic images of a cloud as a cloud (lchd_images.hip): the wrapped originals in slots 0 .. n - 1, their ghosts behind them.
+constexpr int kImgScanSpan = 256;  // atoms per workgroup of the three steps = items one workgroup of the scan covers
+struct ImageArgs {
+    CloudView src;              // the source (cat: the low bytes, cat_hi: the high bytes or null)
+    const uint8_t* src_narrow;  // with cat_hi: the source's one-byte view
+    const double* boxes;        // DEVICE [n_boxes][3] box edges; n_boxes == 1: one box for every structure, else box[sid]
+    int32_t n_boxes;
+    double reach;               // an image within `reach` of the box is materialised (threshold <= reach <= smallest edge)
+    double *x, *y, *z;          // the image cloud's arrays, `capacity` atoms each
+    uint8_t *cat, *cat_hi, *cat_narrow;
+    int32_t *tag, *sid;         // (sid null: one structure)
+    int64_t capacity;
+    uint32_t* count;            // [n] ghosts per atom
+    uint32_t* offset;           // [n] ghosts of the atom's span in front of the atom
+    unsigned long long* span_sum;  // [spans] ghosts in front of each span of kImgScanSpan atoms, or null: n <= kImgScanSpan
+    unsigned long long* bbox;   // [8]: the seven bounding-box words of a frames buffer (ordered keys, non-finite flag), then the ghost total
+};
+void launch_img_count(hipStream_t s, const ImageArgs& a);  // wrapped originals, counts, bounding box (of originals and ghosts)
+void launch_img_scan(hipStream_t s, const ImageArgs& a);   // offsets, span sums, total
+void launch_img_emit(hipStream_t s, const ImageArgs& a);   // the ghosts
 void launch_fill_sqrt_tables(hipStream_t s, double* sqrt_tab, double* rsqrt_tab);  // 65536 entries each
 void launch_fill_pow_tables(hipStream_t s, double* tab /* [2][65536] */, double exponent);  // k^(1/e), k^(-1/e)
 

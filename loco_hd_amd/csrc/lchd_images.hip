@@ -1,0 +1,155 @@
+// lchd_images.hip -- periodic boundaries for from_primitives: the periodic images of a structure, materialised as an ordinary cloud.
+//
+// The reference searches an open system (KdTree::within_radius over the structure's own atoms, src/locohd.rs:504-528 of the reference).
+// With an orthorhombic box (Lx, Ly, Lz) the environment of an anchor holds every periodic image of every atom of its structure that
+// lies closer than the threshold.  Nothing of that search changes here: the images are resolved BEFORE it, into a cloud that holds the
+// wrapped originals at their indices 0 .. n - 1 followed by the ghost atoms, and the cell lists, environment and sweep kernels run on
+// that cloud as on any other (the cell build keys cells by the per-atom structure id, so ghosts need not follow their structure).
+//
+//   wrap      w = x - floor(x / L) * L, and 0 where that rounds to L                       (per axis, box of the atom's structure)
+//   images    w + L exists iff w < reach, w - L exists iff w >= L - reach; both are that single f64 addition
+//   ghosts    every combination of per-axis choices {original, +L, -L} except "all original": at most 26 per atom
+//   order     the ghosts of atom i occupy n + offset[i] ... in ascending image code cx + 3 cy + 9 cz (c: 0 original, 1 +L, 2 -L)
+//
+// reach <= min(L) (lchd_box_validate), so one layer of images is all there is, and threshold <= reach is checked by the pass.
+// Three steps, one launch each (the scan of more than kImgScanSpan atoms: two): k_img_count, the exclusive scan, k_img_emit.
+#include "lchd_kcommon.h"
+
+namespace lchd {
+
+__device__ __forceinline__ double img_wrap(double x, double L) {
+    const double w = x - floor(x / L) * L;
+    return w == L ? 0.0 : w;
+}
+// per-axis choices of one wrapped coordinate: bit 0 the image w + L exists, bit 1 the image w - L
+__device__ __forceinline__ int img_choices(double w, double L, double reach) { return (w < reach ? 1 : 0) | (w >= L - reach ? 2 : 0); }
+__device__ __forceinline__ int img_ways(int ch) { return 1 + (ch & 1) + (ch >> 1); }
+__device__ __forceinline__ const double* img_box(const ImageArgs& a, int64_t i) {
+    return a.boxes + 3 * (size_t)((a.n_boxes > 1 && a.src.sid) ? a.src.sid[i] : 0);
+}
+
+// One lane per atom: the wrapped original into slot i (coordinates and labels), its ghost count into count[i], the bounding box of the
+// atom and its ghosts into the seven ordered-key words (k_frames_unpack's reduction: one atomic per word and wavefront).
+__global__ __launch_bounds__(kImgScanSpan) void k_img_count(ImageArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * kImgScanSpan + threadIdx.x;
+    double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool bad = false;
+    if (i < a.src.n) {
+        const double* L = img_box(a, i);
+        const double v[3] = {a.src.x[i], a.src.y[i], a.src.z[i]};
+        double w[3];
+        int ways = 1;
+        for (int k = 0; k < 3; ++k) {
+            w[k] = img_wrap(v[k], L[k]);
+            bad = bad || !(fabs(w[k]) < INFINITY);
+            const int ch = img_choices(w[k], L[k], a.reach);
+            ways *= img_ways(ch);
+            mn[k] = (ch & 2) ? w[k] - L[k] : w[k];
+            mx[k] = (ch & 1) ? w[k] + L[k] : w[k];
+        }
+        a.x[i] = w[0]; a.y[i] = w[1]; a.z[i] = w[2];
+        a.cat[i] = a.src.cat[i];
+        if (a.cat_hi) { a.cat_hi[i] = a.src.cat_hi[i]; a.cat_narrow[i] = a.src_narrow[i]; }
+        a.tag[i] = a.src.tag[i];
+        if (a.sid) a.sid[i] = a.src.sid[i];
+        a.count[i] = (uint32_t)(ways - 1);
+    }
+    for (int m = 32; m > 0; m >>= 1)
+        for (int k = 0; k < 3; ++k) { mn[k] = fmin(mn[k], shfl_xor_f64(mn[k], m)); mx[k] = fmax(mx[k], shfl_xor_f64(mx[k], m)); }
+    const unsigned long long anybad = __ballot(bad);
+    if ((threadIdx.x & 63) == 0 && (int64_t)blockIdx.x * kImgScanSpan + (threadIdx.x & ~63) < a.src.n) {
+        for (int k = 0; k < 3; ++k) { atomicMin(&a.bbox[k], ordered_key(mn[k])); atomicMax(&a.bbox[3 + k], ordered_key(mx[k])); }
+        if (anybad) atomicOr(&a.bbox[6], 1ull);
+    }
+}
+
+// Exclusive scan of one block span: DPP scan per wavefront, the wavefronts' totals through LDS.  Returns the lane's exclusive prefix
+// inside the span; *span_total (all lanes) = the span's sum.
+__device__ __forceinline__ uint32_t img_span_scan(uint32_t v, uint32_t* span_total) {
+    constexpr int kWaves = kImgScanSpan / 64;
+    __shared__ uint32_t wave_sum[kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t incl = wave_incl_scan_u32(v);
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+    for (int w = 0; w < kWaves; ++w) { before += w < wave ? wave_sum[w] : 0u; all += wave_sum[w]; }
+    __syncthreads();  // (the caller may scan again: wave_sum is free from here on)
+    *span_total = all;
+    return before + incl - v;
+}
+// offset[i] = ghosts of the atoms of i's span before i; span_sum[b] = ghosts of span b (one workgroup per span).  With a single span
+// (n <= kImgScanSpan) this is the whole scan: the total goes straight to *total.
+__global__ __launch_bounds__(kImgScanSpan) void k_img_scan_spans(const uint32_t* __restrict__ count, int64_t n, uint32_t* __restrict__ offset,
+                                                                 unsigned long long* __restrict__ span_sum, unsigned long long* total) {
+    const int64_t i = (int64_t)blockIdx.x * kImgScanSpan + threadIdx.x;
+    uint32_t all;
+    const uint32_t ex = img_span_scan(i < n ? count[i] : 0u, &all);
+    if (i < n) offset[i] = ex;
+    if (threadIdx.x == 0) {
+        if (span_sum) span_sum[blockIdx.x] = all;
+        if (total) *total = all;
+    }
+}
+// span_sum[b] -> ghosts of all spans before b (in place), by one workgroup that carries the running sum from chunk to chunk
+__global__ __launch_bounds__(kImgScanSpan) void k_img_scan_sums(unsigned long long* span_sum, int64_t n_spans, unsigned long long* total) {
+    unsigned long long carry = 0;
+    for (int64_t base = 0; base < n_spans; base += kImgScanSpan) {
+        const int64_t b = base + threadIdx.x;
+        const uint32_t v = b < n_spans ? (uint32_t)span_sum[b] : 0u;  // (a span holds at most 26 * kImgScanSpan ghosts)
+        uint32_t all;
+        const uint32_t ex = img_span_scan(v, &all);
+        if (b < n_spans) span_sum[b] = carry + ex;
+        carry += all;
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+// One lane per atom: its ghosts at n + offset in ascending image code, x fastest; every ghost carries its atom's labels.
+// Reads the wrapped coordinates k_img_count left in slot i, so the choices are the ones that were counted.
+__global__ __launch_bounds__(kImgScanSpan) void k_img_emit(ImageArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * kImgScanSpan + threadIdx.x;
+    if (i >= a.src.n) return;
+    const double* L = img_box(a, i);
+    const double w[3] = {a.x[i], a.y[i], a.z[i]};
+    double im[3][3];
+    int ch[3];
+    for (int k = 0; k < 3; ++k) {
+        ch[k] = img_choices(w[k], L[k], a.reach) << 1 | 1;  // bit c: choice c of this axis exists (0 original, 1 +L, 2 -L)
+        im[k][0] = w[k]; im[k][1] = w[k] + L[k]; im[k][2] = w[k] - L[k];
+    }
+    int64_t o = (int64_t)a.src.n + (int64_t)((a.span_sum ? a.span_sum[i / kImgScanSpan] : 0ull) + a.offset[i]);
+    const uint8_t cat = a.cat[i];
+    const int32_t tag = a.tag[i];
+    for (int cz = 0; cz < 3; ++cz)
+        for (int cy = 0; cy < 3; ++cy)
+            for (int cx = 0; cx < 3; ++cx) {
+                if (!((ch[0] >> cx) & (ch[1] >> cy) & (ch[2] >> cz) & 1) || (cx | cy | cz) == 0) continue;
+                if (o >= a.capacity) return;  // (never: the host sized the arrays from the scan's total)
+                a.x[o] = im[0][cx]; a.y[o] = im[1][cy]; a.z[o] = im[2][cz];
+                a.cat[o] = cat;
+                if (a.cat_hi) { a.cat_hi[o] = a.cat_hi[i]; a.cat_narrow[o] = a.cat_narrow[i]; }
+                a.tag[o] = tag;
+                if (a.sid) a.sid[o] = a.sid[i];
+                ++o;
+            }
+}
+
+static unsigned img_blocks(int64_t n) { return (unsigned)((n + kImgScanSpan - 1) / kImgScanSpan); }
+void launch_img_count(hipStream_t s, const ImageArgs& a) {
+    static const unsigned long long init[7] = {~0ull, ~0ull, ~0ull, 0ull, 0ull, 0ull, 0ull};
+    (void)hipMemcpyAsync(a.bbox, init, sizeof init, hipMemcpyHostToDevice, s);
+    k_img_count<<<img_blocks(a.src.n), kImgScanSpan, 0, s>>>(a);
+}
+void launch_img_scan(hipStream_t s, const ImageArgs& a) {
+    const unsigned spans = img_blocks(a.src.n);
+    if (!a.span_sum) {
+        k_img_scan_spans<<<1, kImgScanSpan, 0, s>>>(a.count, a.src.n, a.offset, nullptr, a.bbox + 7);
+    } else {
+        k_img_scan_spans<<<spans, kImgScanSpan, 0, s>>>(a.count, a.src.n, a.offset, a.span_sum, nullptr);
+        k_img_scan_sums<<<1, kImgScanSpan, 0, s>>>(a.span_sum, spans, a.bbox + 7);
+    }
+}
+void launch_img_emit(hipStream_t s, const ImageArgs& a) { k_img_emit<<<img_blocks(a.src.n), kImgScanSpan, 0, s>>>(a); }
+
+}  // namespace lchd

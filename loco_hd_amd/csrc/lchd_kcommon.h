@@ -16,6 +16,11 @@ __device__ __forceinline__ int cell_coord(double p, double mn, double inv, int d
 }
 __device__ __forceinline__ uint64_t d2u(double d) { return (uint64_t)__double_as_longlong(d); }
 __device__ __forceinline__ double u2d(uint64_t u) { return __longlong_as_double((long long)u); }
+// order-preserving map double -> u64 (so that atomicMin / atomicMax on integers order like the doubles)
+__device__ __forceinline__ unsigned long long ordered_key(double d) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(d);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
 
 __device__ __forceinline__ double shfl_f64(double v, int src) {
     int lo = __shfl(__double2loint(v), src), hi = __shfl(__double2hiint(v), src);

@@ -831,11 +831,6 @@ void launch_frames_labels(hipStream_t s, const uint8_t* tcat, const int32_t* tta
     k_frames_labels<<<2048, 256, 0, s>>>(tcat, ttag, n_tmpl, n_tmpl * n_frames, cat, tag, sid);
 }
 
-// order-preserving map double -> u64 (so that atomicMin / atomicMax on integers order like the doubles)
-__device__ __forceinline__ unsigned long long ordered_key(double d) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(d);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
 __global__ void k_frames_unpack(const double* __restrict__ raw, int64_t n, double* __restrict__ x, double* __restrict__ y,
                                 double* __restrict__ z, unsigned long long* bbox7) {
     double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};

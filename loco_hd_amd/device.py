@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .api import LoCoHD
+from .api import LoCoHD, periodic_boxes
 
 
 def last_sweep_of(ctx):
@@ -138,6 +138,25 @@ class DeviceSession:
     def set_coords(self, cloud, xyz: np.ndarray):
         xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
         N.check(N.lib().lchd_cloud_set_coords(self._ctx, cloud, N.dp(xyz)))
+
+    def periodic_images(self, cloud, box, reach: float):
+        """The periodic images of an uploaded structure / batch / frames buffer as a cloud of its own (lchd_cloud_create_images):
+        the wrapped atoms at their indices, then every image within `reach` of the orthorhombic `box` (Lx, Ly, Lz; one, or one
+        per structure).  Use it in place of `cloud` in from_primitives with threshold_distance <= reach <= the smallest edge;
+        the session owns it like any other cloud."""
+        arr = periodic_boxes(box, self._n_structures(cloud), reach)
+        h = C.c_void_p()
+        N.check(N.lib().lchd_cloud_create_images(self._ctx, cloud, N.dp(arr), len(arr), float(reach), C.byref(h)))
+        self._clouds.append(h)
+        return h
+
+    def update_images(self, images, cloud, box):
+        """Rebuild an image cloud in place from the current coordinates of `cloud` (lchd_cloud_update_images); its reach stays."""
+        arr = np.ascontiguousarray(box, dtype=np.float64)
+        arr = arr.reshape(1, 3) if arr.shape == (3,) else arr
+        if arr.ndim != 2 or arr.shape[1] != 3:
+            raise ValueError(f"box must be three edge lengths (Lx, Ly, Lz), got an array of shape {arr.shape}")
+        N.check(N.lib().lchd_cloud_update_images(self._ctx, images, cloud, N.dp(arr), len(arr)))
 
     def from_primitives(self, cloud_a, cloud_b, anchors, threshold_distance: float, out=None, wf_index=None):
         """anchors: torch int64 CUDA tensor [P][2]; returns (or fills) a torch float64 CUDA tensor [P]."""
@@ -265,7 +284,7 @@ class DeviceSession:
         return out
 
     def score_trajectory(self, ref_cloud, frames_xyz: np.ndarray, local_pairs, threshold_distance: float, chunk: int = 1024,
-                         topology=None):
+                         topology=None, ref_box=None, boxes=None):
         """MD-trajectory mode (python_codes/trajectory_analyzer.py:97-119): score every frame of `frames_xyz`
         [n_frames][n_atoms][3] against the reference structure for the anchor pairs `local_pairs` [(atom in reference,
         atom in frame)].  Frames are streamed in chunks: while chunk k is scored, chunk k+1 is copied on a second
@@ -273,7 +292,11 @@ class DeviceSession:
 
         With `topology` (PrimitiveAssigner.compile_topology of the trajectory's structure) `frames_xyz` holds the float32
         coordinates of the SOURCE atoms, [n_frames][topology.n_atoms][3], and the per-frame structure -> primitive-atom
-        conversion (trajectory_analyzer.py:37-74) runs on the device as well."""
+        conversion (trajectory_analyzer.py:37-74) runs on the device as well.
+
+        `ref_box` / `boxes` (additive): orthorhombic periodic boxes (Lx, Ly, Lz) of the reference structure and of the frames
+        ([n_frames][3], or [3] for a constant box); environments then hold the periodic images within `threshold_distance`.
+        The reference's image cloud is built once, a chunk's is rebuilt on the scoring stream behind the chunk's upload."""
         torch = self.torch
         if topology is not None:
             frames_xyz = np.ascontiguousarray(frames_xyz, dtype=np.float32)
@@ -285,6 +308,10 @@ class DeviceSession:
             frames_xyz = np.ascontiguousarray(frames_xyz, dtype=np.float64)
             n_frames, n_atoms = frames_xyz.shape[0], frames_xyz.shape[1]
             load = self.load_frames
+        thr = float(threshold_distance)
+        if boxes is not None:
+            boxes = periodic_boxes(boxes, n_frames, thr, "boxes")
+        ref_side = ref_cloud if ref_box is None else self.periodic_images(ref_cloud, ref_box, thr)
         lp = np.ascontiguousarray(local_pairs, dtype=np.int64).reshape(-1, 2)
         chunk = max(1, min(int(chunk), n_frames))
         dev = torch.device("cuda", self.device)
@@ -294,6 +321,7 @@ class DeviceSession:
         anchors = anchors.contiguous()
         out = torch.empty(n_frames * len(lp), dtype=torch.float64, device=dev)
         bufs = [self.frames_buffer(ref_cloud, chunk), self.frames_buffer(ref_cloud, chunk)]
+        images = [None, None]  # one image cloud per buffer, made by the first chunk that uses the buffer
         if topology is not None:
             for b in bufs:
                 self.set_frame_sources(b, topology)
@@ -303,7 +331,15 @@ class DeviceSession:
             load(bufs[0], frames_xyz[starts[0]:starts[0] + chunk], copy_stream)
             for k, f0 in enumerate(starts):
                 nf = min(chunk, n_frames - f0)
-                self.from_primitives_async(ref_cloud, bufs[k % 2], anchors[: nf * len(lp)], threshold_distance,
+                side_b = bufs[k % 2]
+                if boxes is not None:
+                    bx = boxes if len(boxes) == 1 else boxes[f0:f0 + nf]
+                    if images[k % 2] is None:
+                        images[k % 2] = self.periodic_images(side_b, bx, thr)
+                    else:
+                        self.update_images(images[k % 2], side_b, bx)
+                    side_b = images[k % 2]
+                self.from_primitives_async(ref_side, side_b, anchors[: nf * len(lp)], threshold_distance,
                                            out[f0 * len(lp):(f0 + nf) * len(lp)])
                 if k + 1 < len(starts):
                     f1 = starts[k + 1]
@@ -315,7 +351,7 @@ class DeviceSession:
                 self.finish()
             except Exception:
                 pass
-            for b in bufs:
+            for b in bufs + [h for h in images if h is not None] + ([ref_side] if ref_side is not ref_cloud else []):
                 N.lib().lchd_cloud_destroy(self._ctx, b)
                 self._clouds.remove(b)
 

@@ -279,6 +279,7 @@ class Structure:
     def __init__(self, structure_id: str):
         self.id = structure_id
         self._models: List[Model] = []
+        self.cell: Optional[Tuple[float, float, float, float, float, float]] = None  # (a, b, c, alpha, beta, gamma) of a CRYST1 record
 
     def get_models(self) -> Iterator[Model]:
         return iter(self._models)
@@ -327,6 +328,8 @@ class PDBParser:
         for start, line in enumerate(lines):
             if line[0:6] in ("ATOM  ", "HETATM", "MODEL "):
                 break
+            if line[0:6] == "CRYST1" and st.cell is None:
+                st.cell = self._cryst1(line)
         else:
             return st
         model: Optional[Model] = None
@@ -392,6 +395,14 @@ class PDBParser:
                 model = None
                 cur_chain_id = cur_res_id = None
         return st
+
+    @staticmethod
+    def _cryst1(line: str):
+        """CRYST1 in fixed columns: a, b, c (7-15, 16-24, 25-33), alpha, beta, gamma (34-40, 41-47, 48-54); None if unreadable."""
+        try:
+            return (float(line[6:15]), float(line[15:24]), float(line[24:33]), float(line[33:40]), float(line[40:47]), float(line[47:54]))
+        except ValueError:
+            return None
 
     @staticmethod
     def _new_model(st: Structure, model_id: int, serial_num: Optional[int]) -> Model:
