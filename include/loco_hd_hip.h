@@ -346,6 +346,16 @@ int lchd_plan_grid(const double bbmin[3], const double bbmax[3], int32_t n_struc
  * one-workgroup scan, 4 general build with the multi-block scan.  Any output pointer may be null.  Returns 0, or -1 under the
  * conditions under which lchd_ctx_last_env_points returns -1 (and for a side other than 0 / 1). */
 int lchd_ctx_last_grid(lchd_ctx *ctx, int32_t side, int32_t dims_out[3], int64_t *n_cells_out, int32_t *build_out);
+/* The anchor de-duplication of side `side` (0: A, 1: B) of the same pass: which atoms are anchors, which environment slot each gets.
+ * *mode_out: 0 with side A's anchors (one object on both sides: both columns share side A's slots), 1 fused prologue (one workgroup per
+ * side, the flags as a bit set in LDS: single structures of at most 4096 atoms and 4096 cells, at most 65 536 pairs), 2 byte flags and
+ * the one-workgroup scan (at most 2^18 atoms per side), 3 byte flags and one workgroup per chunk of 2^18 atoms (either side larger),
+ * 4 none: every PAIR gets a slot of its own (side B only: its anchors were (almost) all used once in the last regular pass, or
+ * LCHD_PER_PAIR=1).  *n_unique_out: the environments the pass built for the side, as the device counted them -- the distinct anchors of
+ * the side's column (mode 0: 0, and side A's count covers both columns; mode 4: the number of pairs).  *n_repeated_out: -1, or in
+ * mode 4 the pairs whose side-B anchor an earlier pair of the list had used (exact up to 2^17 pairs; longer lists count every 16th
+ * pair and report 16 times that).  Any output pointer may be null.  Returns 0, or -1 where lchd_ctx_last_grid returns -1. */
+int lchd_ctx_last_anchors(lchd_ctx *ctx, int32_t side, int64_t *n_unique_out, int32_t *mode_out, int64_t *n_repeated_out);
 /* The sweep kernel families of a from_primitives pass, one bit each (lchd_sweep_plan::families). */
 typedef enum {
     LCHD_SWEEP_INLINE = 1,    /* one launch for a small call: the sweep works out the pair records itself */

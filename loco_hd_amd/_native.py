@@ -130,6 +130,7 @@ _PROTOS = {
     "lchd_ctx_last_env_points": (C.c_int64, [_VP]),
     "lchd_plan_grid": (C.c_int, [_DP, _DP, _i32, _f64, _i32, _IP, _DP, _LP]),
     "lchd_ctx_last_grid": (C.c_int, [_VP, _i32, _IP, _LP, _IP]),
+    "lchd_ctx_last_anchors": (C.c_int, [_VP, _i32, _LP, _IP, _LP]),
     "lchd_plan_sweep": (C.c_int, [C.POINTER(SweepQueryC), C.POINTER(SweepPlanC)]),
     "lchd_ctx_last_sweep": (C.c_int, [_VP, C.POINTER(SweepPlanC), _LP, _IP, _IP]),
     "lchd_ctx_last_dense_fused": (C.c_int32, [_VP]),

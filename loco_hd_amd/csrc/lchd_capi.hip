@@ -178,6 +178,13 @@ struct GridRecord {
     int64_t n_cells = 0;
     int32_t build = 0;
 };
+// What lchd_ctx_last_anchors reports about one side of a pass: which de-duplication launch_prologue picked and what the pass's kernels
+// counted (the host status mirror's n_unique / n_dup_b).
+struct AnchorRecord {
+    int32_t mode = 0;
+    int64_t n_unique = 0;
+    int64_t n_repeated = -1;  // mode 4 only
+};
 // What lchd_ctx_last_sweep reports: the plan launch_sweep followed, what k_pair_meta published about the pass's pairs, the rule in force.
 struct SweepRecord {
     lchd_sweep_plan plan{};
@@ -279,6 +286,7 @@ struct lchd_ctx {
         bool subset = false;                                // the enqueued pass IS a second pass over the pairs of overflowed environments
         bool per_pair = false;                              // the enqueued pass did not de-duplicate side B (slot p = pair p)
         GridRecord grid[2];                                 // grids and cell-list builds of the enqueued pass
+        int dedup[2] = {0, 0};                              // ... and its de-duplication modes (launch_prologue's dedup_out)
         lchd_sweep_plan plan{};                             // what launch_sweep launched for it
         bool repeated = false;                              // the enqueued pass repeats one whose companion sweep had been left out
     } pend;
@@ -296,6 +304,7 @@ struct lchd_ctx {
     SweepArgs last{};
     bool last_valid = false;
     GridRecord last_grid[2];  // ... and its grids and cell-list builds (for lchd_ctx_last_grid)
+    AnchorRecord last_anchors[2];  // ... and its anchor de-duplication (for lchd_ctx_last_anchors)
     SweepRecord last_sweep;   // ... and its sweep kernels (for lchd_ctx_last_sweep)
     bool last_sweep_valid = false;  // (host data only: it outlives the I/O block of a host-pointer call, which last_valid does not)
 };
@@ -533,6 +542,16 @@ extern "C" int lchd_ctx_last_grid(lchd_ctx* c, int32_t side, int32_t dims_out[3]
         if (dims_out) dims_out[k] = g.dim[k];
     if (n_cells_out) *n_cells_out = g.n_cells;
     if (build_out) *build_out = g.build;
+    return 0;
+}
+
+extern "C" int lchd_ctx_last_anchors(lchd_ctx* c, int32_t side, int64_t* n_unique_out, int32_t* mode_out, int64_t* n_repeated_out) {
+    CTX_LOCK(c);
+    if (!c || !c->last_valid || c->pend.active || side < 0 || side > 1) return -1;
+    const AnchorRecord& r = c->last_anchors[side];
+    if (n_unique_out) *n_unique_out = r.n_unique;
+    if (mode_out) *mode_out = r.mode;
+    if (n_repeated_out) *n_repeated_out = r.n_repeated;
     return 0;
 }
 
@@ -1035,7 +1054,12 @@ struct SideBufs {
 
 // Workspace layout of one pass.  Everything that must be zero when the prologue starts -- the general cell list's counters
 // and the anchor flags of both sides -- is carved as ONE contiguous region (flags_a, flags_b last), so at most one memset
-// (or none: the fused / per-structure prologue launches zero what they need themselves) precedes the kernels.
+// precedes the kernels.  Who zeroes it (launch_prologue):
+//   fused            nobody: the flags are an LDS bit set and the general counters are not used.  One exception: a side B without
+//                    de-duplication keeps its repeat bit set in flags_b (k_pair_anchor_recs), and side B's workgroup of
+//                    k_prologue_fused clears those (n_b + 31) / 32 words
+//   per structure    (both sides) the spare workgroups of k_cells_struct2 zero flags_a .. the end of the region
+//   anything else    one memset over the whole region
 struct PassBufs {
     SideBufs a, b;
     int4* pair_meta;
@@ -1220,7 +1244,7 @@ static int prims_enqueue(lchd_ctx* c) {
         PrepSide psa = prep_side(cva, gva, sa), psb = prep_side(cvb, gvb, sb);
         psb.no_anchors = per_pair ? 1 : 0;  // (side B without de-duplication: no flags, no slots -- one environment per pair)
         int builds[2] = {0, 0};
-        (void)launch_prologue(s, c->tune, P.anchors, n_pairs, psa, psb, pb.zero_base, pb.zero_bytes, c->d_status, same, builds);
+        (void)launch_prologue(s, c->tune, P.anchors, n_pairs, psa, psb, pb.zero_base, pb.zero_bytes, c->d_status, same, builds, P.dedup);
         for (int side = 0; side < 2; ++side) {
             const GridPlan& g = side ? gb : ga;
             P.grid[side] = GridRecord{{g.dim[0], g.dim[1], g.dim[2]}, g.n_cells, builds[side]};
@@ -1526,6 +1550,9 @@ static int finish_passes(lchd_ctx* c, uint32_t* flags_out) {
         c->last = P.sw;
         c->last_grid[0] = P.grid[0];
         c->last_grid[1] = P.grid[1];
+        for (int side = 0; side < 2; ++side)
+            c->last_anchors[side] = AnchorRecord{P.dedup[side], (int64_t)c->h_status->n_unique[side],
+                                                 P.dedup[side] == 4 ? (int64_t)c->h_status->n_dup_b : (int64_t)-1};
         c->last_sweep = sweep_record(P.plan, *c->h_status, P.n_pairs, P.repeated);
         c->last_sweep_valid = true;
         c->last_valid = true;

@@ -218,8 +218,12 @@ struct PrepSide {
 // de-duplicated together into side A's flags / slots / records and n_unique[1] = 0.
 // builds_out (optional, two entries): which cell-list build each side took -- 0 none (side B of `same`), 1 fused prologue, 2 one
 // workgroup per structure, 3 general build with the one-workgroup scan, 4 general build with the multi-block scan.
+// dedup_out (optional, two entries): how each side's anchors get their environment slots -- 0 with side A's (side B of `same`),
+// 1 fused prologue (LDS bit set), 2 byte flags + the one-workgroup scan, 3 byte flags + one workgroup per chunk of 2^18 atoms,
+// 4 not at all (PrepSide::no_anchors: launch_pair_anchor_recs gives every PAIR a slot).
 int launch_prologue(hipStream_t s, const Tuning& t, const int64_t* anchors, int64_t n_pairs, const PrepSide& a, const PrepSide& b,
-                    void* zero_base, size_t zero_bytes, DeviceStatus* st, bool same = false, int* builds_out = nullptr);
+                    void* zero_base, size_t zero_bytes, DeviceStatus* st, bool same = false, int* builds_out = nullptr,
+                    int* dedup_out = nullptr);
 // Anchor records of a side without de-duplication (PrepSide::no_anchors), one per PAIR: record p = the side-B anchor of pair p; sets
 // DeviceStatus::n_unique[1] = n_pairs.  Behind launch_prologue (reads the side's atom -> position map).
 void launch_pair_anchor_recs(hipStream_t s, const int64_t* anchors, int64_t n_pairs, const PrepSide& b, DeviceStatus* st);

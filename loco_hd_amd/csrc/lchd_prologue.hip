@@ -236,6 +236,10 @@ __global__ __launch_bounds__(1024) void k_prologue_fused(const int64_t* __restri
     for (int w = tid; w <= kBitWordsMax; w += 1024) bits[w] = 0u;
     cell_build_wg<1024>(c, P.g, cps, 0, n, 0, true, P.rec, P.pos_of, P.cell_start, smem_pf, wsum);  // (its barriers order the clear above)
     if (P.no_anchors) {  // (side B without de-duplication: k_pair_anchor_recs validates this side's anchor indices)
+        // ... and counts the repeated ones in a bit set over the side's flag region: this launch uses no global flags and is preceded
+        // by no memset, so the words are cleared here (k_pair_anchor_recs runs behind this kernel on the same stream)
+        uint32_t* seen = reinterpret_cast<uint32_t*>(P.flag8);
+        for (int w = tid; w < nw; w += 1024) seen[w] = 0u;
         if (tid == 0) st->n_unique[side] = 0u;
         return;
     }
@@ -475,8 +479,9 @@ __global__ void k_pair_anchor_recs(const int64_t* __restrict__ anchors, int64_t 
             atomicOr(&st->flags, ST_BAD_ANCHOR);  // (the one-workgroup prologue does not look at this side's anchors in this mode)
             i = 0;
         }
-        // how many pairs share their side-B anchor with an earlier one?  The side's flag region (zeroed by the prologue, otherwise unused
-        // in this mode) as a bit set, one returning atomic per pair: the count tells the host when this side has stopped being "used
+        // how many pairs share their side-B anchor with an earlier one?  The side's flag region (otherwise unused in this mode) as a bit
+        // set over the atoms -- zero when this kernel starts: by the prologue's memset, by the spare workgroups of k_cells_struct2 when
+        // both sides take the per-structure build, by side B's workgroup of k_prologue_fused -- one returning atomic per pair: the count tells the host when this side has stopped being "used
         // once" (a pass per pair is then a waste).  (Plain loads and stores do not work: a small list's threads all load before any stores.)
         // Large lists: every 16th pair only (1.7 10^6 returning atomics cost 0.19 ms per C4 pass; the host scales the count).
         if (n_pairs <= kDupSampleAbove || (p & 15) == 0) {
@@ -513,7 +518,7 @@ static bool fits_struct_path(const PrepSide& P, const Tuning& t, CloudView& cs) 
 
 constexpr int kStructNT = 512;   // (measured, C4 cell lists: 128 0.506, 256 0.466, 512 0.445 ms per step) threads of the per-structure cell-list workgroups of a batch of more than 16 structures
 int launch_prologue(hipStream_t s, const Tuning& t, const int64_t* anchors, int64_t n_pairs, const PrepSide& a_in, const PrepSide& b_in,
-                    void* zero_base, size_t zero_bytes, DeviceStatus* st, bool same, int* builds_out) {
+                    void* zero_base, size_t zero_bytes, DeviceStatus* st, bool same, int* builds_out, int* dedup_out) {
     PrepSide a = a_in, b = b_in;
     CloudView csa, csb;
     bool fa = fits_struct_path(a, t, csa), fb = fits_struct_path(b, t, csb);
@@ -530,6 +535,7 @@ int launch_prologue(hipStream_t s, const Tuning& t, const int64_t* anchors, int6
         const size_t lds = std::max((size_t)cps_a * 4 + (size_t)a.c.n * 4, (size_t)cps_b * 4 + (size_t)b.c.n * 4);
         k_prologue_fused<<<2, 1024, lds, s>>>(anchors, n_pairs, a, b, st);
         if (builds_out) builds_out[0] = builds_out[1] = 1;
+        if (dedup_out) { dedup_out[0] = 1; dedup_out[1] = b.no_anchors ? 4 : 1; }
         return 1;
     }
     // the anchor flags (and, for the general cell list, its counters) must be zero: folded into the struct launch when both
@@ -569,6 +575,10 @@ int launch_prologue(hipStream_t s, const Tuning& t, const int64_t* anchors, int6
         if (cells > kPrepScanCells) { launch_exclusive_scan(s, P.cell_count, P.cell_start, cells, nullptr, P.scan_tmp); ops += 3; }
     }
     const bool big = a.c.n > kPrepScanAtoms || (!b.no_anchors && b.c.n > kPrepScanAtoms);
+    if (dedup_out) {  // (`big` is decided by either side: a small side next to a large one goes through k_prep_bits too)
+        dedup_out[0] = big ? 3 : 2;
+        dedup_out[1] = same ? 0 : (b.no_anchors ? 4 : (big ? 3 : 2));
+    }
     if (big) {
         const int ca = (int)((((int64_t)a.c.n + 31) / 32 + kChunkWords - 1) / kChunkWords),
                   cb = b.no_anchors ? 0 : (int)((((int64_t)b.c.n + 31) / 32 + kChunkWords - 1) / kChunkWords);

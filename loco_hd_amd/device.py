@@ -27,6 +27,17 @@ def last_sweep_of(ctx):
     return rec
 
 
+def last_anchors_of(ctx):
+    """lchd_ctx_last_anchors of a context handle as a list of two dicts (DeviceSession.last_anchors), or None."""
+    sides = []
+    for side in (0, 1):
+        n_unique, mode, n_repeated = C.c_int64(), C.c_int32(), C.c_int64()
+        if N.lib().lchd_ctx_last_anchors(ctx, side, C.byref(n_unique), C.byref(mode), C.byref(n_repeated)) != 0:
+            return None
+        sides.append({"mode": int(mode.value), "n_unique": int(n_unique.value), "n_repeated": int(n_repeated.value)})
+    return sides
+
+
 class DeviceSession:
     def __init__(self, lchd: LoCoHD, device: Optional[int] = None, interner: Optional[dict] = None):
         import torch
@@ -87,6 +98,13 @@ class DeviceSession:
                 return None
             sides.append({"dims": tuple(dims), "n_cells": int(n_cells.value), "build": int(build.value)})
         return sides
+
+    def last_anchors(self):
+        """Anchor de-duplication of both sides of the same pass (lchd_ctx_last_anchors): a list of two dicts {"mode": 0 shared with
+        side A / 1 fused / 2 one-workgroup scan / 3 chunked / 4 per pair, "n_unique": environments built for the side as the device
+        counted them, "n_repeated": -1, or in mode 4 the pairs whose side-B anchor an earlier pair had used}; None where last_grid()
+        returns None."""
+        return last_anchors_of(self._ctx)
 
     def last_sweep(self):
         """Sweep kernels of the most recent from_primitives call's last pass (lchd_ctx_last_sweep): the fields of lchd_sweep_plan
