@@ -230,7 +230,6 @@ struct lchd_ctx {
     HostStatus* h_status = nullptr;    // pinned, device-visible: the kernels publish into it with plain stores (no D2H copy)
     bool status_dirty = false;         // a pass was abandoned half-way: memset d_status before the next one
     uint32_t seq = 0;                  // pass counter (HostStatus::snapshot_seq)
-    int sweep_hint = 0;                // 0 unknown, else 4 | 1 (pairs of <= 240 events were the majority of the last pass) | 2 (pairs with both environments <= 255 points were): launch_sweep
     unsigned long long* d_points = nullptr;
     double* d_tabs = nullptr;  // sqrt(k) | 1/sqrt(k), 65536 entries each
     unsigned char* d_wide_scratch = nullptr;  // more than kWideCategories categories: per-workgroup state of k_sweep_wide<.., HUGE> (lchd_ctx_set_config)
@@ -241,23 +240,13 @@ struct lchd_ctx {
     DoneState* d_done = nullptr;     // 'last workgroup' counters / accumulators of k_pair_meta (zero between kernels)
     uint32_t* d_left = nullptr;      // two counter slots of the leftover list (SweepArgs::left_count / left_zero), 128 B apart
     int left_slot = 0;               // the slot the next record pass appends to (zero by then: the previous one zeroed it)
-    int64_t last_left = 0;           // pairs the last pass left to the INDIRECT companion
     // host-pointer calls: one grow-only device block + pinned staging block per context (no allocation in the steady state)
     char *d_io = nullptr, *h_io = nullptr;
     size_t io_cap = 0;
     std::vector<char> cfg_blob_host;  // last configuration blob uploaded (identical configurations are not uploaded again)
-    int cap_hint = 512;
-    bool group_small = false;  // the last pass had no environment beyond kEnvGroupSmallUpTo points: k_env_group's small instantiation
-    int64_t last_biggest = 0;  // largest environment of the last pass (0: unknown): anchors per wavefront of k_env_group
-    int shrink_votes = 0;  // consecutive passes whose largest environment would fit half of cap_hint
+    PassHints hints{};  // what the thresholded passes of this context looked like so far (lchd_pass_plan.h): plan_pass and launch_sweep read it
     bool last_dense_fused = false;  // the most recent dense pass ran the fused sort + sweep kernel (lchd_dense_fused.hip)
-    // side B without de-duplication (one environment slot per PAIR) for side-B environments that are used once: taken when the last
-    // REGULAR pass of the configuration found (almost) every side-B anchor unique; every 64th pass is a regular one again
-    // (such a pass does not count side B's unique anchors, so it cannot see the anchors becoming shared)
-    bool b_use_once = false;        // the last regular pass: n_unique[1] >= 0.8 n_pairs
-    int64_t use_once_pairs = 0, use_once_nb = 0;  // ... its pair count and the size of its side B (the hint holds for lists like it)
-    int per_pair_streak = 0;        // passes without side-B de-duplication since the last regular one
-    int64_t n_per_pair_passes = 0;  // passes whose side B was not de-duplicated
+    int64_t n_per_pair_passes = 0;  // passes whose side B was not de-duplicated (PassPlan::per_pair)
     // second pass over the pairs of overflowed environments (lchd_ctx_finish): grow-only device blocks outside the arena
     char *d_ovf_bits = nullptr, *d_ovf_lists = nullptr;
     size_t ovf_bits_cap = 0, ovf_lists_cap = 0;
@@ -269,8 +258,7 @@ struct lchd_ctx {
     hipEvent_t ev[PH_N + 1] = {};
     float ms[PH_N] = {-1, -1, -1, -1};
     // a from_primitives call that has been enqueued but not finished (lchd_from_primitives_dev_async)
-    struct {
-        bool active = false;
+    struct PassRequest {  // what the caller (or rescore_overflow_pairs) asked for
         lchd_cloud *a = nullptr, *b = nullptr;
         const int64_t* anchors = nullptr;
         const int32_t* wf = nullptr;
@@ -278,17 +266,23 @@ struct lchd_ctx {
         double thr = 0.0;
         double* out = nullptr;
         int cap = 0;
-        bool group = false, group_small = false;  // which environment kernel the enqueued pass uses
-        int sweep_info = 0;                        // launch_sweep's return value
+        bool subset = false;    // the pass IS a second pass over the pairs of overflowed environments
+        bool repeated = false;  // the pass repeats one whose companion sweep had been left out
+    };
+    struct PassLaunched {  // what prims_enqueue put on the stream for it
         SweepArgs sw{};
         const uint32_t *ovf_a = nullptr, *ovf_b = nullptr;  // overflow lists of the enqueued pass (null: its kernels keep none)
         int64_t n_slots_a = 0, n_slots_b = 0;               // environment slots per side
-        bool subset = false;                                // the enqueued pass IS a second pass over the pairs of overflowed environments
-        bool per_pair = false;                              // the enqueued pass did not de-duplicate side B (slot p = pair p)
         GridRecord grid[2];                                 // grids and cell-list builds of the enqueued pass
         int dedup[2] = {0, 0};                              // ... and its de-duplication modes (launch_prologue's dedup_out)
         lchd_sweep_plan plan{};                             // what launch_sweep launched for it
-        bool repeated = false;                              // the enqueued pass repeats one whose companion sweep had been left out
+        SweepLaunched sweep{};                              // ... and reported back
+    };
+    struct {
+        bool active = false;
+        PassRequest req;
+        PassPlan plan;  // plan_pass's decisions for the enqueued pass
+        PassLaunched run;
     } pend;
     // multi-GPU sharding helpers (lchd_shard_*): device state, host-mapped counts, the plan they belong to
     ShardState* d_shard = nullptr;
@@ -583,7 +577,7 @@ extern "C" int lchd_ctx_set_deterministic(lchd_ctx* c, int32_t on) {
         Tuning& t = c->tune;
         t.no_duo = t.no_count8 = t.no_c8_team = t.no_inline_meta = t.force_bigenv = t.no_dense_fused = t.no_sd_inc = t.no_sweep_hint = true;
     }
-    c->sweep_hint = 0;
+    c->hints.sweep_hint = 0;
     return LCHD_OK;
 }
 extern "C" int32_t lchd_ctx_get_deterministic(lchd_ctx* c) { CTX_LOCK(c); return (c && c->deterministic) ? 1 : 0; }
@@ -678,8 +672,8 @@ extern "C" int lchd_ctx_set_config(lchd_ctx* c, const lchd_config* cfg) {
     }
     HIP_TRY(hipMemcpy(c->d_blob, blob.data(), total, hipMemcpyHostToDevice));
     c->cfg_set = false;
-    c->sweep_hint = 0;  // another configuration: what the last pass looked like says nothing about the next
-    c->b_use_once = false;
+    c->hints.sweep_hint = 0;  // another configuration: what the last pass looked like says nothing about the next
+    c->hints.b_use_once = false;
     c->cfg_blob_host.swap(sig);
     DevConfig h{};
     h.n_categories = C;
@@ -861,7 +855,7 @@ extern "C" int32_t lchd_cloud_structures(const lchd_cloud* cl) { return cl ? cl-
 extern "C" int lchd_cloud_set_coords(lchd_ctx* c, lchd_cloud* cl, const double* xyz) {
     CTX_LOCK(c);
     if (!c || !cl || !xyz) return fail(LCHD_EVALUE, "null argument");
-    if (c->pend.active && (c->pend.a == cl || c->pend.b == cl))
+    if (c->pend.active && (c->pend.req.a == cl || c->pend.req.b == cl))
         return fail(LCHD_EVALUE, "this structure is in use by an unfinished asynchronous call");
     if (cl->images) return fail(LCHD_EVALUE, "an image cloud takes its coordinates from its source (lchd_cloud_update_images)");
     CTX_GUARD(c);
@@ -1067,9 +1061,10 @@ struct PassBufs {
     char* zero_base;
     size_t zero_bytes;
 };
-static void carve_pass(Arena& ar, int64_t n_a, int cells_a, int64_t envs_a, int64_t n_b, int cells_b, int64_t envs_b, int cap, int64_t n_pairs,
-                       PassBufs& pb, bool cat16 = false, int key_sets = 1, int pre_words_a = 0, int pre_words_b = 0) {
-    const size_t ma = (size_t)std::max<int64_t>(n_a, 1), mb = (size_t)std::max<int64_t>(n_b, 1);
+static void carve_pass(Arena& ar, const PassQuery& q, const PassPlan& plan, int cells_a, int cells_b, PassBufs& pb) {
+    const int cap = q.cap;
+    const bool cat16 = plan.cat16;
+    const size_t ma = (size_t)std::max<int64_t>(q.n_a, 1), mb = (size_t)std::max<int64_t>(q.n_b, 1);
     ar.off = (ar.off + 255) & ~size_t(255);
     const size_t z0 = ar.off;
     pb.a.cell_count = ar.take<uint32_t>((size_t)cells_a + 1);
@@ -1082,7 +1077,7 @@ static void carve_pass(Arena& ar, int64_t n_a, int cells_a, int64_t envs_a, int6
         SideBufs& b = side ? pb.b : pb.a;
         const size_t m = side ? mb : ma;
         const int n_cells = side ? cells_b : cells_a;
-        const size_t ne = (size_t)std::max<int64_t>(side ? envs_b : envs_a, 1);
+        const size_t ne = (size_t)std::max<int64_t>(side ? plan.max_env_b : plan.max_env_a, 1);
         b.cell_of = ar.take<uint32_t>(m);
         b.slot = ar.take<uint32_t>(m + 1);
         b.bits = ar.take<uint32_t>((m + 31) / 32 + 1);
@@ -1093,12 +1088,12 @@ static void carve_pass(Arena& ar, int64_t n_a, int cells_a, int64_t envs_a, int6
         b.pos_of = ar.take<uint32_t>(m);
         b.uniq = ar.take<AnchorRec>(ne);
         b.scan_tmp = ar.take<uint32_t>(std::max<size_t>(m, (size_t)n_cells) / 4096 + 4);
-        b.env.key = ar.take<uint64_t>(ne * (size_t)cap * (size_t)std::max(key_sets, 1));
+        b.env.key = ar.take<uint64_t>(ne * (size_t)cap * (size_t)std::max(plan.key_sets, 1));
         b.env.set_stride = (int64_t)(ne * (size_t)cap);
         b.env.cat = ar.take<uint8_t>(ne * (size_t)cap * (cat16 ? 2 : 1));
         b.env.len = ar.take<int32_t>(ne);
         b.env.cat0 = (cap == kEnvGroupCap && !cat16) ? ar.take<uint8_t>(ne) : nullptr;  // (written by k_env_group only: prims_enqueue drops it otherwise)
-        const int pw = side ? pre_words_b : pre_words_a;  // prefix-count rows (k_env_group, configurations of at most 16 categories)
+        const int pw = plan.pre_words;  // prefix-count rows (k_env_group, configurations of at most 16 categories)
         b.env.pre = pw > 0 ? ar.take<uint64_t>(ne * (size_t)(cap / kPreStep) * (size_t)pw) : nullptr;  // (one row per kPreStep points)
         b.env.pre_words = pw;
         b.env.stride = cap;
@@ -1108,14 +1103,8 @@ static void carve_pass(Arena& ar, int64_t n_a, int cells_a, int64_t envs_a, int6
         b.raw_cat = cap > 16384 ? ar.take<uint8_t>(ne * (size_t)cap) : nullptr;
         b.ovf_list = cap <= 16384 ? ar.take<uint32_t>(ne) : nullptr;
     }
-    pb.pair_meta = ar.take<int4>((size_t)n_pairs);
-    pb.left_list = ar.take<uint32_t>((size_t)n_pairs);
-}
-
-static int next_pow2_host(int64_t n) {
-    int p = 64;
-    while (p < n) p <<= 1;
-    return p;
+    pb.pair_meta = ar.take<int4>((size_t)q.n_pairs);
+    pb.left_list = ar.take<uint32_t>((size_t)q.n_pairs);
 }
 
 // A frames buffer computes its bounding box on the device while it is being filled; fetch it before planning a grid.
@@ -1145,74 +1134,47 @@ static void fill_sweep_args(lchd_ctx* c, SweepArgs& sw) {
     sw.wide_scratch_waves = c->wide_scratch_waves;
 }
 
-// Everything of one from_primitives pass; no host synchronisation (the workspace only grows between passes).
+// What plan_pass is asked about the pending request: its sizes, the configuration and the context's hooks and hints.
+static PassQuery pass_query(const lchd_ctx* c) {
+    const auto& R = c->pend.req;
+    PassQuery q;
+    q.n_a = R.a->n; q.n_b = R.b->n; q.n_pairs = R.n_pairs;
+    q.same_object = R.a == R.b;
+    q.has_wf_index = R.wf != nullptr;
+    q.cap = R.cap; q.subset = R.subset;
+    q.n_categories = c->h_cfg.n_categories; q.n_wf = c->h_cfg.n_wf;
+    q.hellinger2 = c->hellinger2; q.sd_fast = c->sd_fast; q.unit_weights = c->unit_weights; q.finf_differ = c->finf_differ;
+    q.deterministic = c->deterministic; q.tag_mode = c->h_cfg.tag_mode;
+    q.tune = c->tune; q.hints = c->hints;
+    return q;
+}
+
+// Everything of one from_primitives pass: plan -> grids -> workspace -> launches; no host synchronisation (the workspace only grows
+// between passes).
 static int prims_enqueue(lchd_ctx* c) {
-    auto& P = c->pend;
+    const auto& R = c->pend.req;
+    auto& L = c->pend.run;
     ++c->n_passes;
-    lchd_cloud *a = P.a, *b = P.b;
-    const int64_t n_pairs = P.n_pairs;
-    const double thr = P.thr;
-    const int cap = P.cap;
-    // environments of the default capacity: several per wavefront on a grid of half-threshold cells (lchd_env_group.hip)
-    // more than 255 categories: 16-bit ids in the environment store, k_env_cells<.., uint16_t> + k_sweep_wide<.., CAT16>
-    const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
-    // Both sides the SAME device object (all-vs-all over one batch of structures, a structure against itself): an anchor's
-    // environment does not depend on the side it is used on (src/locohd.rs:514-542 is one closure for both), so the cell
-    // list and every environment are built once -- the anchors of both columns share side A's flags, slots and store.
-    const bool same = (a == b) && !c->tune.no_share;
-    const int64_t max_env_a = same ? std::min<int64_t>(a->n, 2 * n_pairs) : std::min<int64_t>(a->n, n_pairs);
-    int64_t max_env_b = same ? 0 : std::min<int64_t>(b->n, n_pairs);  // (side B without de-duplication: one slot per PAIR, below)
-    // (the grouped kernel addresses environment slots and records with 32-bit offsets: the limits of launch_env_group; larger
-    //  calls take k_env_cells, which has none)
-    const bool group = cap == kEnvGroupCap && !c->tune.no_env_group && a->n < ((int64_t)1 << 27) && b->n < ((int64_t)1 << 27) &&
-                       max_env_a < ((int64_t)1 << 22) && max_env_b < ((int64_t)1 << 22) && !cat16;
-    P.group = group;
-    P.group_small = false;
-    // Side B used once -- (almost) every side-B anchor of the last regular pass of this context was unique: the frames of a trajectory,
-    // (i, i) lists, a rank's partners under strong scaling.  Such a side is not de-duplicated: environment slot p belongs to pair p
-    // and its anchor record comes straight from the pair list (launch_pair_anchor_recs) -- no flags, bit set, scan and scatter over
-    // the side's atoms.  Any choice is correct for any input: an anchor that occurs in several pairs is built once per pair, as the
-    // reference does (src/locohd.rs:514-554).  Every 64th pass is a regular one again (this mode does not count unique anchors).
-    const bool per_pair_ok = group && !same && !P.subset && !c->deterministic && c->tune.per_pair >= 0 && n_pairs < ((int64_t)1 << 22) && n_pairs > 0;
-    // (history alone is not enough: the hint must have come from a list of this size on a structure of this size, and a list with more
-    //  pairs than the side has atoms repeats anchors by counting -- C2a: 10^6 pairs over 10^4 atoms right after a list of (i, i) pairs)
-    const bool like_hinted = n_pairs <= b->n && b->n == c->use_once_nb && 2 * n_pairs >= c->use_once_pairs && n_pairs <= 2 * c->use_once_pairs;
-    const bool per_pair = per_pair_ok && (c->tune.per_pair > 0 || (c->b_use_once && like_hinted && n_pairs > 4096 && c->per_pair_streak < 64));
-    P.per_pair = per_pair;
-    if (per_pair) max_env_b = n_pairs;  // (one slot per PAIR)
-    const GridPlan ga = plan_grid(a, thr, group ? 2 : 1), gb = plan_grid(b, thr, group ? 2 : 1);
-    // Keys of the store: F(distance) whenever the sweep can use them without evaluating a CDF -- one weight function, or a
-    // dictionary of up to kMaxKeySets (src/locohd.rs:230-283: every pair names its function): k_env_group writes one key set per
-    // function (the sort is shared, the store's key part grows k-fold) and a pair reads the set of its function.
-    const int n_wf = c->h_cfg.n_wf;
-    // (dictionary: set 0 keeps the distances k_env_group writes, k_env_key_sets fills sets 1 .. n_wf; the sweeps' view starts at set 1)
-    const bool dict_sets = n_wf > 1 && group && n_wf <= kMaxKeySets && P.wf && !c->tune.no_key_sets && !c->tune.no_cdf_keys && !c->finf_differ;
-    const int key_sets = c->tune.no_cdf_keys ? 0 : (n_wf == 1 ? 1 : (dict_sets ? n_wf + 1 : 0));
-    // Prefix-count rows next to the environments (EnvStore::pre, 8 or 16 bytes per point): the team sweeps of up to 16 category slots
-    // read a chunk's start counts from them instead of building a histogram and a scan per tile.  Worth their write when environments
-    // are swept more than once: not for a side without de-duplication (one pair per environment), not for small calls (one pair per
-    // wavefront: the one-launch sweep), only where the team sweeps exist (Hellinger-2 / Kolmogorov-Smirnov on unit weights).
-    int pre_words = 0;
-    {
-        const int cm = std::max(c->h_cfg.n_categories, c->tune.force_cmax);
-        const bool team_cfg = (c->hellinger2 || c->sd_fast == 3) && c->unit_weights && key_sets >= 1 && !c->tune.no_duo && !c->tune.no_count8 &&
-                              !c->tune.no_c8_team && !c->tune.force_generic && !c->tune.force_wide && !c->tune.force_bigenv;
-        // (17 .. 28 slots -- three / four count words, the LDS-byte form of the team sweep -- were built and measured in round 6: C5's
-        //  k_sweep_duo<28, 32, 480> 1.690 ms with rows against 1.679 without, k_env_group 0.93 against 0.77 ms: no rows there)
-        if (group && team_cfg && cm <= 16 && !per_pair && !c->deterministic && c->tune.pre_rows >= 0 && (n_pairs > 4096 || c->tune.no_inline_meta || c->tune.pre_rows > 0))
-            pre_words = team_pre_words(cm);
-    }
+    lchd_cloud *a = R.a, *b = R.b;
+    const int64_t n_pairs = R.n_pairs;
+    const double thr = R.thr;
+    const int cap = R.cap;
+    const PassQuery q = pass_query(c);
+    const PassPlan plan = c->pend.plan = plan_pass(q);
+    const bool same = plan.same, per_pair = plan.per_pair;
+    const int64_t max_env_a = plan.max_env_a, max_env_b = plan.max_env_b;
+    const GridPlan ga = plan_grid(a, thr, plan.reach), gb = plan_grid(b, thr, plan.reach);
     PassBufs pb{};
     {
         Arena dry(nullptr, 0, true);
-        carve_pass(dry, a->n, ga.n_cells, max_env_a, b->n, gb.n_cells, max_env_b, cap, n_pairs, pb, cat16, key_sets, pre_words, pre_words);
+        carve_pass(dry, q, plan, ga.n_cells, gb.n_cells, pb);
         if (int rc = ensure_ws(c, dry.off + 4096)) return rc;
     }
     Arena ar(c->ws, c->ws_cap, false);
-    carve_pass(ar, a->n, ga.n_cells, max_env_a, b->n, gb.n_cells, max_env_b, cap, n_pairs, pb, cat16, key_sets, pre_words, pre_words);
+    carve_pass(ar, q, plan, ga.n_cells, gb.n_cells, pb);
     SideBufs &sa = pb.a, &sb = pb.b;
-    sa.env.cdf_keys = sb.env.cdf_keys = dict_sets ? 0 : key_sets;  // (what the environment kernels write into set 0)
-    if (!group) sa.env.cat0 = sb.env.cat0 = nullptr;
+    sa.env.cdf_keys = sb.env.cdf_keys = plan.dict_sets ? 0 : plan.key_sets;  // (what the environment kernels write into set 0)
+    if (!plan.group) sa.env.cat0 = sb.env.cat0 = nullptr;
 
     auto grid_view = [](const GridPlan& g, const SideBufs& s) {
         GridView v{};
@@ -1224,7 +1186,7 @@ static int prims_enqueue(lchd_ctx* c) {
         return v;
     };
     const GridView gva = grid_view(ga, sa), gvb = grid_view(gb, sb);
-    const CloudView cva = a->view(cat16), cvb = b->view(cat16);
+    const CloudView cva = a->view(plan.cat16), cvb = b->view(plan.cat16);
     hipStream_t s = c->stream;
     // frames buffers are filled on another stream: order this pass behind their upload
     if (a->ev_ready && a->cap_frames) HIP_TRY(hipStreamWaitEvent(s, a->ev_ready, 0));
@@ -1244,41 +1206,32 @@ static int prims_enqueue(lchd_ctx* c) {
         PrepSide psa = prep_side(cva, gva, sa), psb = prep_side(cvb, gvb, sb);
         psb.no_anchors = per_pair ? 1 : 0;  // (side B without de-duplication: no flags, no slots -- one environment per pair)
         int builds[2] = {0, 0};
-        (void)launch_prologue(s, c->tune, P.anchors, n_pairs, psa, psb, pb.zero_base, pb.zero_bytes, c->d_status, same, builds, P.dedup);
+        (void)launch_prologue(s, c->tune, R.anchors, n_pairs, psa, psb, pb.zero_base, pb.zero_bytes, c->d_status, same, builds, L.dedup);
         for (int side = 0; side < 2; ++side) {
             const GridPlan& g = side ? gb : ga;
-            P.grid[side] = GridRecord{{g.dim[0], g.dim[1], g.dim[2]}, g.n_cells, builds[side]};
+            L.grid[side] = GridRecord{{g.dim[0], g.dim[1], g.dim[2]}, g.n_cells, builds[side]};
         }
-        if (per_pair) launch_pair_anchor_recs(s, P.anchors, n_pairs, psb, c->d_status);
+        if (per_pair) launch_pair_anchor_recs(s, R.anchors, n_pairs, psb, c->d_status);
     }
     mark(c, 1);
     mark(c, 2);  // (cell lists and anchor de-duplication are one phase now; "anchors" reads 0)
-    const bool tag_list = c->h_cfg.tag_mode != 0;
     const EnvSide esa{cva, gva, sa.uniq, sa.env, max_env_a, sa.raw_key, sa.raw_cat, sa.ovf_list},
                   esb{cvb, gvb, sb.uniq, sb.env, max_env_b, sb.raw_key, sb.raw_cat, sb.ovf_list};
-    P.ovf_a = sa.ovf_list;
-    P.ovf_b = sb.ovf_list;
-    P.n_slots_a = max_env_a;
-    P.n_slots_b = max_env_b;
-    c->last_store_bytes += (size_t)(std::max<int64_t>(max_env_a, 1) + std::max<int64_t>(max_env_b, 1)) * (size_t)cap * ((cat16 ? 2 : 1) + 8 * (size_t)std::max(key_sets, 1));
-    if (group) {
-        // anchors per wavefront: as many as fit ONE group of the kernel's LDS buffer (measured, env phase in ms for 1 / 2 / 4 / 8 /
-        // 16 anchors: C4, ~96-point environments 3.87 / 2.88 / 2.68 / 2.69 / 2.96; C5, ~200 points 0.81 / 0.75 / 0.75 / 0.78 / 0.81 --
-        // more anchors per wavefront only lengthen the tail of the launch)
-        // A call with few anchors is bound by the latency of one wavefront's chain, not by throughput: one anchor per wavefront
-        // until there are enough of them to fill the chip twice (3000-atom structure pair: 19.9 -> 11.7 us).
-        const int by_size = c->last_biggest > 0 && c->last_biggest <= 140 ? 4 : (c->last_biggest > kEnvGroupSmallUpTo ? 1 : 2);
-        const int apw = c->tune.env_apw > 0 ? c->tune.env_apw
-                                            : (int)std::max<int64_t>(1, std::min<int64_t>(by_size, (max_env_a + max_env_b) / 8192));
-        P.group_small = c->group_small;
-        if (!launch_env_group(s, c->d_cfg, tag_list, P.group_small, esa, esb, thr, apw, c->d_status))
+    L.ovf_a = sa.ovf_list;
+    L.ovf_b = sb.ovf_list;
+    L.n_slots_a = max_env_a;
+    L.n_slots_b = max_env_b;
+    c->last_store_bytes += (size_t)(std::max<int64_t>(max_env_a, 1) + std::max<int64_t>(max_env_b, 1)) * (size_t)cap * ((plan.cat16 ? 2 : 1) + 8 * (size_t)std::max(plan.key_sets, 1));
+    if (plan.group) {
+        if (!launch_env_group(s, c->d_cfg, plan.tag_list, plan.group_small, esa, esb, thr, plan.apw, c->d_status))
             return fail(LCHD_EDEVICE, "the grouped environment kernel rejected its launch configuration");
-    } else if (!launch_env_cells(s, cap, c->d_cfg, tag_list, esa, esb, thr, c->d_status))
-        return fail(LCHD_EUNSUPPORTED, cat16 ? "with more than 255 categories an environment may hold at most 8192 points (capacity %d asked for)"
-                                             : "no environment kernel variant with capacity %d", cap);
+    } else if (!launch_env_cells(s, cap, c->d_cfg, plan.tag_list, esa, esb, thr, c->d_status))
+        return fail(LCHD_EUNSUPPORTED, plan.cat16 ? "with more than 255 categories an environment may hold at most 8192 points (capacity %d asked for)"
+                                                  : "no environment kernel variant with capacity %d", cap);
     if (c->deterministic)  // one order among equal keys, whatever order the cell lists' and the buckets' atomics produced (utils.rs:25-39: a stable sort)
         launch_env_canon(s, sa.env, same ? sa.env : sb.env, max_env_a, same ? 0 : max_env_b, c->d_status);
-    if (dict_sets) {
+    if (plan.dict_sets) {
+        const int n_wf = c->h_cfg.n_wf;
         launch_env_key_sets(s, c->d_cfg, sa.env, sb.env, n_wf, max_env_a + max_env_b, c->d_status);
         for (SideBufs* sb_ : {&sa, &sb}) {  // the sweeps' view of the store: the F sets
             sb_->env.key += sb_->env.set_stride;
@@ -1290,30 +1243,30 @@ static int prims_enqueue(lchd_ctx* c) {
     fill_sweep_args(c, sw);
     sw.env_a = sa.env;
     sw.env_b = same ? sa.env : sb.env;
-    sw.anchors = P.anchors;
+    sw.anchors = R.anchors;
     sw.slot_a = sa.slot;
     sw.slot_b = same ? sa.slot : (per_pair ? nullptr : sb.slot);  // (nullptr: side B's slot of pair p is p)
     sw.n_slot_a = a->n;
     sw.n_slot_b = b->n;
-    sw.wf_index = P.wf;
+    sw.wf_index = R.wf;
     sw.n_pairs = n_pairs;
-    sw.out = P.out;
+    sw.out = R.out;
     sw.meta = pb.pair_meta;
     if (!c->deterministic) {  // (deterministic mode: no team kernels, no companion)
         sw.left_list = pb.left_list;
         sw.left_count = c->d_left + 32 * c->left_slot;
         sw.left_zero = c->d_left + 32 * (c->left_slot ^ 1);
-        sw.left_expected = P.subset ? n_pairs : c->last_left;
+        sw.left_expected = R.subset ? n_pairs : c->hints.last_left;
     }
-    P.sweep_info = launch_sweep(s, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, c->sweep_hint, sw, &P.plan);
-    if (P.sweep_info < 0) return fail(LCHD_EDEVICE, "internal error: the sweep launch set %u would not give every pair exactly one kernel", P.plan.families);
-    if (P.sweep_info & 4) c->left_slot ^= 1;  // (the record pass ran and zeroed the other slot)
+    L.sweep = launch_sweep(s, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, c->hints.sweep_hint, sw, &L.plan);
+    if (!L.sweep.ok) return fail(LCHD_EDEVICE, "internal error: the sweep launch set %u would not give every pair exactly one kernel", L.plan.families);
+    if (L.sweep.left_counters_used) c->left_slot ^= 1;  // (the record pass ran and zeroed the other slot)
     mark(c, 4);
     if (a->ev_used) { HIP_TRY(hipEventRecord(a->ev_used, s)); a->used_valid = true; }
     if (b->ev_used) { HIP_TRY(hipEventRecord(b->ev_used, s)); b->used_valid = true; }
     HIP_TRY(hipGetLastError());
     c->status_dirty = false;  // the record pass of this sequence leaves the device status clean
-    P.sw = sw;
+    L.sw = sw;
     return LCHD_OK;
 }
 
@@ -1336,14 +1289,14 @@ extern "C" int lchd_from_primitives_dev_async(lchd_ctx* c, lchd_cloud* a, lchd_c
     CTX_GUARD(c);
     if (int rc = resolve_bbox(c, a)) return rc;
     if (int rc = resolve_bbox(c, b)) return rc;
-    auto& P = c->pend;
-    P.a = a; P.b = b; P.anchors = d_anchors; P.wf = d_wf_index; P.n_pairs = n_pairs; P.thr = thr; P.out = d_out;
-    P.cap = c->cap_hint;
-    P.subset = false;
-    P.repeated = false;
+    auto& R = c->pend.req;
+    R.a = a; R.b = b; R.anchors = d_anchors; R.wf = d_wf_index; R.n_pairs = n_pairs; R.thr = thr; R.out = d_out;
+    R.cap = c->hints.cap_hint;
+    R.subset = false;
+    R.repeated = false;
     c->last_store_bytes = 0;
     if (int rc = prims_enqueue(c)) return rc;
-    P.active = true;
+    c->pend.active = true;
     return LCHD_OK;
 }
 
@@ -1373,22 +1326,23 @@ static int finish_passes(lchd_ctx* c, uint32_t* flags_out);
 static int rescore_overflow_pairs(lchd_ctx* c, uint32_t f1, int64_t biggest, bool* handled, uint32_t* flags_out) {
     *handled = false;
     auto& P = c->pend;
+    const auto& L = P.run;
     const HostStatus* h = c->h_status;
     const uint32_t na = h->n_overflow[0], nb = h->n_overflow[1];
     const uint64_t n_uniq = (uint64_t)h->n_unique[0] + h->n_unique[1];
-    if (P.subset || P.per_pair || c->tune.no_overflow_subset || !P.ovf_a || na + nb == 0 || (f1 & ST_EMPTY_ENV)) return LCHD_OK;  // (per_pair: the selection kernels read side B's slot map)
+    if (P.req.subset || P.plan.per_pair || c->tune.no_overflow_subset || !L.ovf_a || na + nb == 0 || (f1 & ST_EMPTY_ENV)) return LCHD_OK;  // (per_pair: the selection kernels read side B's slot map)
     if ((uint64_t)(na + nb) * 8 > n_uniq) return LCHD_OK;  // not a minority: larger slots for everything
     hipStream_t s = c->stream;
-    const SweepArgs sw = P.sw;  // the finished pass's arrays (the arena stays as it is until the second pass is enqueued)
-    const bool same = sw.slot_a == sw.slot_b && sw.env_a.key == sw.env_b.key;
+    const SweepArgs sw = L.sw;  // the finished pass's arrays (the arena stays as it is until the second pass is enqueued)
+    const bool same = P.plan.same;
     // bit sets over the slots + the selection's scratch
-    const size_t wa = (size_t)(P.n_slots_a + 31) / 32 + 1, wb = same ? 0 : (size_t)(P.n_slots_b + 31) / 32 + 1;
+    const size_t wa = (size_t)(L.n_slots_a + 31) / 32 + 1, wb = same ? 0 : (size_t)(L.n_slots_b + 31) / 32 + 1;
     const size_t o_cnt = (wa + wb) * 4, o_tot = o_cnt + (size_t)kOverflowWaves * 8, bits_bytes = o_tot + 8;
     if (int rc = grow_block(c->d_ovf_bits, c->ovf_bits_cap, bits_bytes)) return rc;
     uint32_t* bits_a = reinterpret_cast<uint32_t*>(c->d_ovf_bits);
     uint32_t* bits_b = same ? bits_a : bits_a + wa;
     HIP_TRY(hipMemsetAsync(c->d_ovf_bits, 0, bits_bytes, s));
-    launch_mark_overflow(s, P.ovf_a, na, P.ovf_b, nb, bits_a, bits_b);
+    launch_mark_overflow(s, L.ovf_a, na, L.ovf_b, nb, bits_a, bits_b);
     OverflowSelect sel{};
     sel.anchors = sw.anchors; sel.n_pairs = sw.n_pairs; sel.slot_a = sw.slot_a; sel.slot_b = sw.slot_b;
     sel.bits_a = bits_a; sel.bits_b = bits_b; sel.wf = sw.wf_index;
@@ -1410,25 +1364,22 @@ static int rescore_overflow_pairs(lchd_ctx* c, uint32_t f1, int64_t biggest, boo
     HIP_TRY(hipGetLastError());
     // the second pass: the context's hints describe the caller's workload, not this selection -- saved and restored around it
     const auto saved = P;
-    const int cap_hint = c->cap_hint, sweep_hint = c->sweep_hint, shrink_votes = c->shrink_votes;
-    const bool group_small = c->group_small;
-    const int64_t last_biggest = c->last_biggest;
-    P.anchors = sel.sel_anchors; P.wf = sel.sel_wf; P.n_pairs = (int64_t)n_sub; P.out = sub_out;
+    const PassHints saved_hints = c->hints;
+    auto& R = P.req;
+    R.anchors = sel.sel_anchors; R.wf = sel.sel_wf; R.n_pairs = (int64_t)n_sub; R.out = sub_out;
     // (an anchor whose candidate table overflowed reported its candidates, an upper bound: a few large slots cost little here)
-    P.cap = next_pow2_host(std::max<int64_t>(std::max<int64_t>(biggest, h->max_bound), saved.cap + 1));
-    P.subset = true;
-    c->sweep_hint = 0;
-    c->last_biggest = biggest;
+    R.cap = next_pow2_host(std::max<int64_t>(std::max<int64_t>(biggest, h->max_bound), saved.req.cap + 1));
+    R.subset = true;
+    c->hints.sweep_hint = 0;
+    c->hints.last_biggest = biggest;
     ++c->n_subset_passes;
     uint32_t f2 = 0;
     int rc = prims_enqueue(c);
     if (!rc) rc = finish_passes(c, &f2);
-    const SweepArgs sub_sw = P.sw;
     P = saved;
-    c->cap_hint = cap_hint; c->sweep_hint = sweep_hint; c->shrink_votes = shrink_votes; c->group_small = group_small; c->last_biggest = last_biggest;
-    (void)sub_sw;
+    c->hints = saved_hints;
     if (rc) return rc;
-    launch_scatter_scores(s, sub_out, sel.sel_index, (int64_t)n_sub, saved.out);
+    launch_scatter_scores(s, sub_out, sel.sel_index, (int64_t)n_sub, saved.req.out);
     HIP_TRY(hipStreamSynchronize(s));
     c->last_valid = false;  // (c->last would describe the first pass, whose arena the second one has reused)
     c->last_sweep_valid = false;  // (... and the sweep record the second pass's selection)
@@ -1457,107 +1408,60 @@ static SweepRecord sweep_record(const lchd_sweep_plan& plan, const HostStatus& h
     return r;
 }
 
+// What the lchd_ctx_last_* read-backs report about the pass that stood.
+static void record_last_pass(lchd_ctx* c, const HostStatus& h) {
+    const auto& P = c->pend;
+    c->last = P.run.sw;
+    c->last_grid[0] = P.run.grid[0];
+    c->last_grid[1] = P.run.grid[1];
+    for (int side = 0; side < 2; ++side)
+        c->last_anchors[side] = AnchorRecord{P.run.dedup[side], (int64_t)h.n_unique[side], P.run.dedup[side] == 4 ? (int64_t)h.n_dup_b : (int64_t)-1};
+    c->last_sweep = sweep_record(P.run.plan, h, P.req.n_pairs, P.req.repeated);
+    c->last_sweep_valid = true;
+    c->last_valid = true;
+}
+
 // Waits for the enqueued pass and repeats it while the device asks for it (larger slots, the full launch set); *flags_out = the
-// status words of the pass that stood.
+// status words of the pass that stood.  Every decision is pass_verdict's and every hint hints_after_pass's / hints_for_repeat's
+// (lchd_pass_plan.h); this loop waits, asks, and enqueues.
 static int finish_passes(lchd_ctx* c, uint32_t* flags_out) {
     auto& P = c->pend;
+    auto& R = P.req;
     for (int attempt = 0; attempt < 6; ++attempt) {
         uint32_t f = 0;
         if (int rc = wait_pass(c, &f)) return rc;
         collect_times(c, 0, 4);
-        if (f & ST_BAD_ANCHOR) { *flags_out = f; return LCHD_OK; }
-        const int64_t biggest = c->h_status->max_env;  // largest environment of the pass (k_pair_meta), or what overflowed
-        if (f & ST_ENV_OVERFLOW) {  // an environment did not fit its slot: its pairs again with larger slots, or the whole pass
-            if (biggest > 65535 && (c->h_cfg.n_categories > kMaxCategories || biggest > (1 << 23)))
+        // what the pairs of THIS pass looked like (a second pass over overflowed environments overwrites the mirror with its selection's numbers)
+        const HostStatus h = *c->h_status;
+        const PassOutcome o = pass_verdict(f, h, P.plan, P.run.sweep, c->h_cfg.n_categories, R.n_pairs, R.cap, R.subset);
+        switch (o.verdict) {
+            case PassVerdict::BAD_ANCHOR:
+                *flags_out = f;
+                return LCHD_OK;
+            case PassVerdict::UNSUPPORTED:
                 return fail(LCHD_EUNSUPPORTED, "an environment holds %lld points; beyond 65535 per environment this build handles at most %d "
-                                               "categories and 2^23 points (the 64-bit-count sweep)", (long long)biggest, kMaxCategories);
-            if (P.group && P.group_small && biggest <= kEnvGroupCap) {
-                c->group_small = false;  // the small instantiation of k_env_group overflowed: the same capacity with the regular one
-                c->last_biggest = std::max<int64_t>(biggest, kEnvGroupCapSmall + 1);
-            } else {
-                // The companion sweep for the larger pairs was left out (the previous pass of this context had none): if this pass has
-                // some, their scores were never written -- the whole pass again with the full launch set BEFORE the second pass over
-                // the overflowed environments' pairs keeps the first pass's scores of everything else.
-                if ((P.sweep_info & 2) && c->h_status->n_small != ~0ull) {
-                    const unsigned long long taken = (P.sweep_info & 1) ? c->h_status->n_c8 : c->h_status->n_duo;
-                    if (taken < (unsigned long long)P.n_pairs) {
-                        c->sweep_hint &= ~(8 | 16);
-                        P.repeated = true;
-                        if (int rc = prims_enqueue(c)) return rc;
-                        continue;
-                    }
-                }
-                // what the pairs of THIS pass looked like (the second pass overwrites the mirror with its selection's numbers)
-                const HostStatus first = *c->h_status;
+                                               "categories and 2^23 points (the 64-bit-count sweep)", (long long)o.biggest, kMaxCategories);
+            case PassVerdict::STANDS:
+                if (P.plan.per_pair) ++c->n_per_pair_passes;
+                record_last_pass(c, h);
+                c->hints = hints_after_pass(c->hints, h, P.plan, P.run.sweep, R.n_pairs, R.b ? R.b->n : 0, R.subset);
+                *flags_out = f;
+                return LCHD_OK;
+            case PassVerdict::OVERFLOW: {
                 bool handled = false;
-                if (int rc = rescore_overflow_pairs(c, f, biggest, &handled, flags_out)) return rc;
-                if (handled) {
-                    if (!P.subset && first.n_small != ~0ull)  // the next call of this configuration starts from the first pass's launch set
-                        c->sweep_hint = 4 | (2 * first.n_duo >= (unsigned long long)P.n_pairs ? 1 : 0) |
-                                        (2 * first.n_c8 >= (unsigned long long)P.n_pairs ? 2 : 0);
+                if (int rc = rescore_overflow_pairs(c, f, o.biggest, &handled, flags_out)) return rc;
+                if (handled) {  // the next call of this configuration starts from the first pass's launch set
+                    if (h.n_small != ~0ull) c->hints.sweep_hint = sweep_hint_from_counts(h.n_duo, h.n_c8, R.n_pairs, false);
                     return LCHD_OK;
                 }
-                // (candidate-table overflows reported an upper bound -- candidates, ~2.4 environments' worth on a uniform cloud --: the whole
-                //  pass tries the slot size that would fit a typical share of them first; a subset's few slots take the bound itself)
-                const int64_t bound = c->h_status->max_bound;
-                P.cap = next_pow2_host(std::max<int64_t>(std::max<int64_t>(biggest, P.subset ? bound : bound / 3), P.cap + 1));
-                if (!P.subset) { c->cap_hint = P.cap; c->shrink_votes = 0; }
+                R.cap = o.grown_cap;
+                break;
             }
-            if (int rc = prims_enqueue(c)) return rc;
-            continue;
+            case PassVerdict::REPEAT_FULL_SET: R.repeated = true; break;
+            case PassVerdict::REPEAT_REGULAR: break;
         }
-        // The capacity hint decays: a single dense environment should not make every later call of this context pay for
-        // its slot size (slots are fixed-stride).  Eight passes in a row that would have fitted half the capacity halve it.
-        if (!P.subset) {
-            if (c->cap_hint > 512 && biggest > 0 && 2 * next_pow2_host(biggest) <= c->cap_hint) {
-                if (++c->shrink_votes >= 8) { c->cap_hint = std::max(512, c->cap_hint / 2); c->shrink_votes = 0; }
-            } else {
-                c->shrink_votes = 0;
-            }
-        }
-        if ((P.sweep_info & 2) && c->h_status->n_small != ~0ull) {
-            // the companion sweep for the larger pairs was left out because the previous pass had none: did this one?
-            const unsigned long long taken = (P.sweep_info & 1) ? c->h_status->n_c8 : c->h_status->n_duo;
-            if (taken < (unsigned long long)P.n_pairs) {
-                c->sweep_hint &= ~(8 | 16);
-                P.repeated = true;
-                if (int rc = prims_enqueue(c)) return rc;
-                continue;
-            }
-        }
-        if (biggest > 0) { c->group_small = biggest <= kEnvGroupSmallUpTo; c->last_biggest = biggest; }
-        if (!P.subset) {
-            if (P.per_pair) {
-                ++c->per_pair_streak;
-                ++c->n_per_pair_passes;
-                // (this pass did not count side B's unique anchors; its bit set counts the repeated ones: a list that shares
-                //  more than a fifth of them goes back to the regular pipeline with the next pass)
-                if ((unsigned long long)c->h_status->n_dup_b * 5ull > (unsigned long long)P.n_pairs) c->b_use_once = false;
-            } else {  // (almost) every side-B anchor unique: the next passes of this context on such lists do not de-duplicate side B
-                const bool same_obj = P.sw.slot_a == P.sw.slot_b;
-                c->b_use_once = !same_obj && (unsigned long long)c->h_status->n_unique[1] * 5ull >= (unsigned long long)P.n_pairs * 4ull;
-                c->use_once_pairs = P.n_pairs;
-                c->use_once_nb = P.b ? P.b->n : 0;
-                c->per_pair_streak = 0;
-            }
-        }
-        if (c->h_status->n_small != ~0ull && !P.subset)  // (sizes the next pass's companion launch when it walks the leftover list)
-            c->last_left = P.n_pairs - (int64_t)std::min<unsigned long long>((P.sweep_info & 1) ? c->h_status->n_c8 : c->h_status->n_duo, (unsigned long long)P.n_pairs);
-        if (c->h_status->n_small != ~0ull)  // what the pairs looked like this time picks the sweep kernels of the next pass of this configuration
-            c->sweep_hint = 4 | (2 * c->h_status->n_duo >= (unsigned long long)P.n_pairs ? 1 : 0) |
-                            (2 * c->h_status->n_c8 >= (unsigned long long)P.n_pairs ? 2 : 0) |
-                            (c->h_status->n_duo == (unsigned long long)P.n_pairs ? 8 : 0) | (c->h_status->n_c8 == (unsigned long long)P.n_pairs ? 16 : 0);
-        c->last = P.sw;
-        c->last_grid[0] = P.grid[0];
-        c->last_grid[1] = P.grid[1];
-        for (int side = 0; side < 2; ++side)
-            c->last_anchors[side] = AnchorRecord{P.dedup[side], (int64_t)c->h_status->n_unique[side],
-                                                 P.dedup[side] == 4 ? (int64_t)c->h_status->n_dup_b : (int64_t)-1};
-        c->last_sweep = sweep_record(P.plan, *c->h_status, P.n_pairs, P.repeated);
-        c->last_sweep_valid = true;
-        c->last_valid = true;
-        *flags_out = f;
-        return LCHD_OK;
+        c->hints = hints_for_repeat(c->hints, o, R.subset);
+        if (int rc = prims_enqueue(c)) return rc;
     }
     return fail(LCHD_EDEVICE, "environment capacity retry did not converge");
 }
@@ -1565,9 +1469,8 @@ static int finish_passes(lchd_ctx* c, uint32_t* flags_out) {
 extern "C" int lchd_ctx_finish(lchd_ctx* c) {
     CTX_LOCK_FINISH(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
-    auto& P = c->pend;
-    if (!P.active) return LCHD_OK;
-    P.active = false;
+    if (!c->pend.active) return LCHD_OK;
+    c->pend.active = false;
     CTX_GUARD(c);
     uint32_t f = 0;
     if (int rc = finish_passes(c, &f)) return rc;
@@ -1633,7 +1536,7 @@ extern "C" int lchd_frames_load(lchd_ctx* c, lchd_cloud* fr, const double* xyz, 
     CTX_LOCK(c);
     if (!c || !fr || !xyz || !fr->cap_frames) return fail(LCHD_EVALUE, "not a frames buffer");
     if (n_frames < 1 || n_frames > fr->cap_frames) return fail(LCHD_EVALUE, "%d frames do not fit a buffer of %d", n_frames, fr->cap_frames);
-    if (c->pend.active && (c->pend.a == fr || c->pend.b == fr))
+    if (c->pend.active && (c->pend.req.a == fr || c->pend.req.b == fr))
         return fail(LCHD_EVALUE, "this frames buffer is in use by an unfinished asynchronous call");
     CTX_GUARD(c);
     hipStream_t s = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->stream;
@@ -1656,7 +1559,7 @@ extern "C" int lchd_frames_set_sources(lchd_ctx* c, lchd_cloud* fr, const int32_
                                        int64_t n_src_atoms) {
     CTX_LOCK(c);
     if (!c || !fr || !fr->cap_frames || !src_start || !src_idx) return fail(LCHD_EVALUE, "not a frames buffer / null map");
-    if (c->pend.active && (c->pend.a == fr || c->pend.b == fr))
+    if (c->pend.active && (c->pend.req.a == fr || c->pend.req.b == fr))
         return fail(LCHD_EVALUE, "this frames buffer is in use by an unfinished asynchronous call");
     CTX_GUARD(c);
     const int64_t np = fr->n_tmpl;
@@ -1736,7 +1639,7 @@ static int frames_load_atoms(lchd_ctx* c, lchd_cloud* fr, const float* atom_xyz,
     if (!c || !fr || !atom_xyz || !fr->cap_frames) return fail(LCHD_EVALUE, "not a frames buffer");
     if (!fr->n_src) return fail(LCHD_EVALUE, "lchd_frames_set_sources has not been called on this frames buffer");
     if (n_frames < 1 || n_frames > fr->cap_frames) return fail(LCHD_EVALUE, "%d frames do not fit a buffer of %d", n_frames, fr->cap_frames);
-    if (c->pend.active && (c->pend.a == fr || c->pend.b == fr))
+    if (c->pend.active && (c->pend.req.a == fr || c->pend.req.b == fr))
         return fail(LCHD_EVALUE, "this frames buffer is in use by an unfinished asynchronous call");
     CTX_GUARD(c);
     hipStream_t s = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->stream;
@@ -1854,7 +1757,7 @@ static int images_build(lchd_ctx* c, lchd_cloud* img, lchd_cloud* src, const dou
         return fail(LCHD_EVALUE, "%d boxes given for %d structures: pass one box, or one per structure", n_boxes, src->n_struct);
     if (int rc = lchd_box_validate(boxes, n_boxes, img->reach)) return rc;
     if (src->images) return fail(LCHD_EVALUE, "the source of an image cloud must not be an image cloud");
-    if (c->pend.active && (c->pend.a == img || c->pend.b == img))
+    if (c->pend.active && (c->pend.req.a == img || c->pend.req.b == img))
         return fail(LCHD_EVALUE, "this image cloud is in use by an unfinished asynchronous call");
     const int64_t n = src->n;
     if (n > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "periodic images of %lld atoms: at most 2^27", (long long)n);
@@ -2144,7 +2047,7 @@ static int host_call_finish(lchd_ctx* c, HostCall& hc, const int64_t* subset, do
             if (ev[q]) (void)hipEventDestroy(ev[q]);
         if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); rc = fail(LCHD_EDEVICE, "HIP error %d in D2H scores", (int)e); }
         c->last_valid = false;
-        c->pend.a = c->pend.b = nullptr;
+        c->pend.req.a = c->pend.req.b = nullptr;
         return rc;
     }
     if (!rc && !hc.direct) {
@@ -2158,7 +2061,7 @@ static int host_call_finish(lchd_ctx* c, HostCall& hc, const int64_t* subset, do
         else for (int64_t k = 0; k < hc.n; ++k) out[subset[k]] = h[k];
     }
     c->last_valid = false;  // the anchors of this call live in the I/O block, which the next call overwrites
-    c->pend.a = c->pend.b = nullptr;  // the clouds of the call are gone
+    c->pend.req.a = c->pend.req.b = nullptr;  // the clouds of the call are gone
     return rc;
 }
 
@@ -2216,7 +2119,7 @@ extern "C" int lchd_from_primitives_periodic(lchd_ctx* c, const lchd_config* cfg
     const int rc = run();
     const std::string msg = g_err;  // (the clean-up below makes calls of its own)
     c->last_valid = false;  // the anchors and the clouds of this call go away
-    c->pend.a = c->pend.b = nullptr;
+    c->pend.req.a = c->pend.req.b = nullptr;
     for (lchd_cloud* cl : {ia, ib, ca, cb}) lchd_cloud_destroy(c, cl);
     (void)hipFree(d_blk);
     if (rc) snprintf(g_err, sizeof g_err, "%s", msg.c_str());
@@ -2404,7 +2307,7 @@ static int group_call_device_partition(lchd_group* g, const lchd_config* cfg, co
         lchd_ctx* c = g->ctx[(size_t)r];
         GroupDev& D = dev[(size_t)r];
         c->last_valid = false;
-        c->pend.a = c->pend.b = nullptr;  // the structures of the call live in the I/O block, which the next call overwrites
+        c->pend.req.a = c->pend.req.b = nullptr;  // the structures of the call live in the I/O block, which the next call overwrites
         if (!D.enqueued) continue;
         CTX_GUARD(c);
         if (hipStreamSynchronize(c->stream) != hipSuccess) note(fail(LCHD_EDEVICE, "HIP error while waiting for device %d of the group", r));
@@ -2595,7 +2498,7 @@ static int sweep_rows(lchd_ctx* c, const EnvStore& ea, const EnvStore& eb, const
     sw.n_pairs = rows;
     sw.out = d_out;
     sw.meta = d_meta;
-    if (launch_sweep(c->stream, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, 0, sw) < 0)
+    if (!launch_sweep(c->stream, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, 0, sw).ok)
         return fail(LCHD_EDEVICE, "internal error: the sweep launch set would not give every pair exactly one kernel");
     mark(c, 4);
     HIP_TRY(hipGetLastError());
@@ -2992,7 +2895,7 @@ static int ens_sweep(lchd_ctx* c, const EnvStore& st, const int64_t* anchors, co
     sw.n_pairs = q;
     sw.out = out;
     sw.meta = meta;
-    if (launch_sweep(c->stream, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, 0, sw) < 0)
+    if (!launch_sweep(c->stream, c->tune, c->h_cfg.n_categories, c->hellinger2, c->unit_weights, c->wf_pow, 0, sw).ok)
         return fail(LCHD_EDEVICE, "internal error: the sweep launch set would not give every pair exactly one kernel");
     HIP_TRY(hipGetLastError());
     c->status_dirty = false;  // the record pass resets the device status

@@ -7,12 +7,14 @@
 #include <iterator>
 #include <type_traits>
 
+#include "lchd_pass_plan.h"  // the host-only part: Tuning, HostStatus, the ST_* status bits, the pass planner
+
 struct lchd_sweep_query;  // include/loco_hd_hip.h
 struct lchd_sweep_plan;
 
 namespace lchd {
 
-constexpr int kMaxCategories = 255;   // categories travel as u8 on the device ...
+// (kMaxCategories = 255, lchd_pass_plan.h: categories travel as u8 on the device ...)
 constexpr int kHugeCategories = 65534;  // ... beyond kWideCategories: the same 16-bit ids (0xFFFF = not in the map), the sweep's per-category state in global memory
 // scratch of one workgroup of k_sweep_wide<.., HUGE>: [C][64] u32 count columns | [C] u32 carry row | 2 x [64][C] f64 normalised vectors
 inline size_t wide_scratch_bytes_per_wave(int C) { return (((size_t)C * 65 * 4 + 15) & ~(size_t)15) + (size_t)C * 64 * 16; }
@@ -34,18 +36,6 @@ inline void with_slots(int cmax, F&& f) {
 }
 constexpr uint64_t kPadKey = ~0ull;   // sorts after every valid (non-negative, non-NaN) f64 bit pattern
 
-// status word written by kernels (device memory, zeroed per call)
-enum : uint32_t {
-    ST_BAD_ANCHOR = 1u << 0,      // anchor index outside the cloud            (reference: panic, :521)
-    ST_EMPTY_ENV = 1u << 1,       // environment without any point              (reference: panic, :74)
-    ST_FIRST_NOT_ZERO = 1u << 2,  // sorted dists[0] != 0                       (reference: ValueError, :74-77)
-    ST_BAD_CATEGORY = 1u << 3,    // category id outside [0, C)                 (reference: ValueError, pmf.rs:38-42)
-    ST_ENV_OVERFLOW = 1u << 4,    // environment larger than the kernel variant's LDS capacity (retry bigger)
-    ST_ZERO_NORM = 1u << 5,       // PMF norm 0                                 (reference: ValueError, pmf.rs:70-76)
-    ST_BAD_DISTANCE = 1u << 6,    // negative / NaN distance in a matrix row    (reference: ValueError / panic)
-    ST_BAD_WF = 1u << 7,          // weight-function index outside the table
-    ST_ROW_RETRY = 1u << 8,       // a dense row of more than 16384 points defeated the segmented sort: repeat the call with k_env_rows
-};
 // Device-resident status of a pass.  Invariant between passes: flags == max_env == 0 -- the last workgroup of
 // k_pair_meta copies the words the host needs into the host-mapped HostStatus and resets them, so a pass needs neither a
 // memset in front of it nor a device-to-host copy behind it.  n_unique / n_small are plain-stored by every pass.
@@ -61,48 +51,7 @@ struct DeviceStatus {
     uint32_t n_dup_b;        // a pass without de-duplication of side B (k_pair_anchor_recs): pairs whose side-B anchor another pair of the list had
                              //  marked before (a bit set in the side's flag region, one returning atomic per pair); reset with the flags
 };
-// Host-mapped (pinned, device-visible) mirror: written with plain stores only -- the snapshot by one thread of k_pair_meta,
-// the error words by whichever sweep wavefront meets the (rare) condition; every writer of a word stores the same value.
-struct HostStatus {
-    uint32_t flags;          // DeviceStatus::flags at the end of the record pass (everything the kernels before the sweep reported)
-    uint32_t max_env;
-    uint32_t n_unique[2];
-    unsigned long long n_small;
-    uint32_t sweep_flags[8]; // word k != 0 <=> a sweep kernel reported status bit k (ST_* below)
-    uint32_t snapshot_seq;   // pass counter written with the snapshot (the host checks that the pass it waited for got this far)
-    uint32_t pad;
-    unsigned long long n_duo, n_c8;  // pairs of at most kDuoTile merged events / with both environments <= 255 points (both always counted)
-    uint32_t n_overflow[2];  // DeviceStatus::n_overflow at the end of the record pass
-    uint32_t max_bound;      // DeviceStatus::max_bound
-    uint32_t n_dup_b;        // DeviceStatus::n_dup_b
-};
 
-// Test / tuning hooks.  Read from the environment ONCE, when a context is created (lchd_ctx_create), and handed to the
-// launchers by value: nothing in the launch path calls getenv().
-struct Tuning {
-    bool no_struct_cells = false;   // LCHD_NO_STRUCT_CELLS: always the generic (multi-pass, global atomics) cell list
-    bool no_share = false;          // LCHD_NO_SHARED_ENVS: build both sides even when they are the same device object
-    bool no_key_sets = false;       // LCHD_NO_KEY_SETS: weight-function dictionaries keep distance keys (the CDF is evaluated by the sweep, per event)
-    bool no_cdf_keys = false;       // LCHD_NO_CDF_KEYS: environments keep distance keys even with a single weight function
-    bool no_duo = false;            // LCHD_NO_DUO: never two pairs per wavefront
-    bool force_wide = false;        // LCHD_FORCE_WIDE: k_sweep_wide for any category count
-    bool force_generic = false;     // LCHD_FORCE_GENERIC: MODE_GEN even for Hellinger-2
-    bool force_bigenv = false;      // LCHD_FORCE_BIGENV: the !LDSTAB sweep instantiations
-    bool no_sweep_hint = false;     // (deterministic mode only) always launch all three sweep kernels and let the device decide
-    bool no_inline_meta = false;    // LCHD_NO_INLINE_META: small calls also run k_pair_meta + the regular sweep kernels
-    bool old_rows = false;          // LCHD_OLD_ROWS: dense rows through k_env_rows (three distance passes) for every length
-    bool no_dense_fused = false;    // LCHD_NO_DENSE_FUSED: dense rows always through the two-kernel path (row sort, then sweep)
-    bool no_count8 = false;         // LCHD_NO_COUNT8: never the 8-bit-count sweep
-    bool no_c8_team = false;        // LCHD_NO_C8_TEAM: the 8-bit-count sweep always one pair per wavefront (k_sweep<.., CNT8>)
-    bool no_overflow_subset = false;  // LCHD_NO_OVERFLOW_SUBSET: an overflowing environment repeats the WHOLE pass with larger slots (never only its pairs)
-    bool no_env_group = false;      // LCHD_NO_ENV_GROUP: environments of the default capacity through k_env_cells (one per wavefront) too
-    bool no_sd_inc = false;         // LCHD_NO_SD_INC: Kullback-Leibler / Renyi through the generic sweep even where k_sweep_inc applies
-    int env_apw = 0;                // LCHD_ENV_APW: anchors per wavefront of k_env_group (0: chosen from the number of anchors)
-    int force_cmax = 0;             // LCHD_FORCE_CMAX: at least this many category slots
-    int per_pair = 0;               // LCHD_PER_PAIR: -1 never a side B without de-duplication, 1 whenever it applies, 0: from the previous pass (side-B anchors (almost) all unique)
-    int pre_rows = 0;               // LCHD_PRE_ROWS: -1 never prefix-count rows next to the environments (the team sweeps build their chunk-start counts per tile), 1 also for small calls, 0: by the rule of prims_enqueue
-    int ensemble_block = 0;         // LCHD_ENSEMBLE_BLOCK: at most this many structures resident in the dense ensemble call's environment store (0: as many as the free HBM holds)
-};
 
 struct WfEntry {
     int32_t kind, n_params, offset, pad;
@@ -188,10 +137,6 @@ struct EnvStore {
                          // gather into a small array instead of one into the store itself (k_env_group writes it; the other environment kernels do not)
 };
 constexpr int kPreStep = 4;  // points per prefix-count row (round 6: every row of round 5's store cost the sweeps one 128-byte line per lane)
-// u64 words of a prefix-count row that the team sweep of `cmax` category slots reads: TeamTile<CM>::NW of the instantiation launch_team
-// picks (8, 12 / 16 slots); 0: no instantiation reads rows (k_env_group's writer handles up to four words)
-inline int team_pre_words(int cmax) { return cmax <= 8 ? 1 : (cmax <= 16 ? 2 : 0); }
-constexpr int kMaxKeySets = 4;  // weight-function dictionaries of up to 4 entries get one key set each (k_env_group); larger ones keep distance keys
 
 // One structure (or batch of structures) of a from_primitives pass as the prologue sees it: the inputs, and the arrays the
 // prologue fills (cell list, anchor slots, anchor records).
@@ -254,7 +199,7 @@ bool launch_env_cells(hipStream_t s, int cap, const DevConfig* cfg, bool tag_lis
 // Needs a grid whose cells are at least thr / 2 wide (the search walks the 5 x 5 x 5 neighbourhood), record arrays padded by
 // kEnvGroupRecPad records, fewer than 2^29 records per side and environment slots of at least kEnvGroupCap points.
 // small_cap: the instantiation for environments of at most kEnvGroupCapSmall points (less LDS, one more wavefront per SIMD).
-constexpr int kEnvGroupCap = 512, kEnvGroupCapSmall = 320, kEnvGroupSmallUpTo = 288, kEnvGroupRecPad = 8;
+// (kEnvGroupCap, kEnvGroupCapSmall, kEnvGroupSmallUpTo, kEnvGroupRecPad: lchd_pass_plan.h)
 bool launch_env_group(hipStream_t s, const DevConfig* cfg, bool tag_list, bool small_cap, const EnvSide& a, const EnvSide& b, double thr,
                       int anchors_per_wave, DeviceStatus* st);
 
@@ -362,18 +307,12 @@ struct SweepArgs {
     int32_t left_listing;     // set by launch_sweep: k_pair_meta appends and the companion reads the list
     int64_t left_expected;    // pairs the previous pass of the context left over (sizes the companion's grid; any grid is correct)
 };
-// sweep_hint: 0 = unknown (launch every candidate kernel, the device decides from the pair records); otherwise what
-// k_pair_meta counted in the previous pass of this configuration: 4 | 1 (pairs of at most 240 merged events were the
-// majority: k_sweep_duo + the indirect k_sweep) | 2 (pairs with both environments <= 255 points were: the 8-bit-count k_sweep
-// + the indirect one); neither: the plain k_sweep only.  Any choice is correct for any input; the hint only picks the launch set.
-// ... | 8 (every pair of the previous pass had at most 240 events) | 16 (... both environments <= 255 points): the companion
-// launch for the larger pairs is left out.  Returns 1 (the "small" rule of this pass was the 8-bit-count one) | 2 (the companion
-// launch was left out: the caller must check this pass's counts, HostStatus::n_duo / n_c8 against the number of pairs) | 4 (k_pair_meta
-// ran with the leftover-list counters of `a`: the caller swaps the two counter slots for the next pass).
+// sweep_hint: SweepHintBits (lchd_pass_plan.h), what k_pair_meta counted in the previous pass of this configuration.  Returns what the
+// caller's bookkeeping needs (SweepLaunched); !ok: nothing was launched.
 // plan_sweep is the decision alone (lchd_plan_sweep); launch_sweep launches what it returns and, if asked, hands the plan back.
-bool plan_sweep(const lchd_sweep_query& q, lchd_sweep_plan& p);  // false: the set would not give every pair exactly one kernel (unreachable); launch_sweep then launches nothing and returns -1
-int launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinger2, bool unit_weights, bool wf_pow, int sweep_hint,
-                 const SweepArgs& a, lchd_sweep_plan* plan_out = nullptr);
+bool plan_sweep(const lchd_sweep_query& q, lchd_sweep_plan& p);  // false: the set would not give every pair exactly one kernel (unreachable); launch_sweep then launches nothing
+SweepLaunched launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinger2, bool unit_weights, bool wf_pow, int sweep_hint,
+                           const SweepArgs& a, lchd_sweep_plan* plan_out = nullptr);
 // Kullback-Leibler / Renyi in O(1) per event (lchd_sweep_inc.hip): unit weights, CDF-keyed environments of at most 512 points, tiny eps;
 // reads the pair records of k_pair_meta.  kind: SweepArgs::sd_fast.
 void launch_sweep_inc(hipStream_t s, int kind, int cmax, const SweepArgs& a);

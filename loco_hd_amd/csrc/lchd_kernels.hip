@@ -151,12 +151,12 @@ static void plan_sweep_families(const lchd_sweep_query& q, lchd_sweep_plan& p) {
     const bool ks_team = !hellinger2 && q.sd_fast == 3 && unit_weights && cmax <= 16 && !no_duo && !no_c8_team && !no_count8 && !force_generic;
     const bool fast_cfg = !wide && ((hellinger2 && (unit_weights || weighted_team)) || ks_team) && small && p.fmode == F_KEY;  // (F_KEY with a weight-function dictionary: the store holds one key set per function)
     // hint_bits (what k_pair_meta counted in the previous pass of this configuration): 0 = nothing known, else
-    // 4 | (pairs of <= 240 events were the majority ? 1 : 0) | (pairs with both environments <= 255 points were ? 2 : 0).
+    // HINT_KNOWN | (pairs of <= 240 events were the majority ? HINT_DUO_MAJOR : 0) | (pairs with both environments <= 255 points were ? HINT_C8_MAJOR : 0).
     // Up to 16 slots k_sweep_duo is the first choice and the 8-bit-count sweep the second (C2a: environments of ~170 points,
     // pairs of ~340 events -- too long for a 32-lane tile, but their counts fit 8 bits: 2 count words per side instead of 3);
     // above 16 slots only the 8-bit-count sweep exists.
     const int hint_bits = no_sweep_hint ? 0 : q.hint_bits;
-    const bool known = (hint_bits & 4) != 0, duo_major = (hint_bits & 1) != 0, c8_major = (hint_bits & 2) != 0;
+    const bool known = (hint_bits & HINT_KNOWN) != 0, duo_major = (hint_bits & HINT_DUO_MAJOR) != 0, c8_major = (hint_bits & HINT_C8_MAJOR) != 0;
     const bool c8_small_slots = fast_cfg && cmax <= 16 && !no_count8 && known && !(duo_major && !no_duo) && c8_major;
     const bool use_duo = fast_cfg && cmax <= 16 && !no_duo && !c8_small_slots;
     const bool use_c8 = fast_cfg && !no_count8 && (cmax > 16 || c8_small_slots);
@@ -168,11 +168,11 @@ static void plan_sweep_families(const lchd_sweep_query& q, lchd_sweep_plan& p) {
     // no hint and up to 16 slots: k_sweep_duo's rule first, the two-pairs-per-wavefront 8-bit-count rule second
     p.second_rule = (!known && use_duo && fast_cfg && !no_count8 && !no_c8_team) ? 2 : 0;
     const int hint = !known ? 0 : ((use_c8 ? c8_major : duo_major) ? 1 : 2);
-    // ... | 8 (EVERY pair of the previous pass had at most 240 events) | 16 (... both environments <= 255 points): the companion
+    // ... | HINT_ALL_DUO (EVERY pair of the previous pass had at most 240 events) | HINT_ALL_C8 (... both environments <= 255 points): the companion
     // launch for the larger pairs would find nothing to do and is left out; the host checks the counts of THIS pass afterwards
     // and repeats it with the full launch set if a larger pair turned up after all
     const bool team_cfg = !wide && (use_duo || use_c8);
-    const bool no_others = team_cfg && hint == 1 && (hint_bits & (use_c8 ? 16 : 8)) != 0;
+    const bool no_others = team_cfg && hint == 1 && (hint_bits & (use_c8 ? HINT_ALL_C8 : HINT_ALL_DUO)) != 0;
     // the leftover list: only where the rule is known at launch and a companion will read it (otherwise the device decides the rule
     // from this very record pass and the companion scans the records)
     p.left_listing = (q.has_left_list && team_cfg && hint == 1 && !no_others) ? 1 : 0;
@@ -231,10 +231,11 @@ bool plan_sweep(const lchd_sweep_query& q, lchd_sweep_plan& p) {
 // workgroups of the INDIRECT companion sweep (it walks every pair record and sweeps the few the team kernel left)
 // (measured: 1024 -> 2048: C2a 19.4 -> 16.6 us, C4 47.3 -> 37.3 us per pass; 4096: no further gain)
 constexpr unsigned kCompanionGrid = 2048u;
-int launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinger2, bool unit_weights, bool wf_pow, int sweep_hint,
-                 const SweepArgs& a_in, lchd_sweep_plan* plan_out) {
+SweepLaunched launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinger2, bool unit_weights, bool wf_pow, int sweep_hint,
+                           const SweepArgs& a_in, lchd_sweep_plan* plan_out) {
     if (plan_out) *plan_out = lchd_sweep_plan{};
-    if (a_in.n_pairs <= 0) return 0;
+    SweepLaunched done;  // (nothing to report: the inline sweep, or nothing launched)
+    if (a_in.n_pairs <= 0) return done;
     SweepArgs a = a_in;
     lchd_sweep_query q{};
     q.n_pairs = a.n_pairs;
@@ -263,7 +264,7 @@ int launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinge
     lchd_sweep_plan p;
     const bool covered = plan_sweep(q, p);
     if (plan_out) *plan_out = p;
-    if (!covered) return -1;  // (nothing launched)
+    if (!covered) { done.ok = false; return done; }  // (nothing launched)
     const uint32_t fam = p.families;
     a.duo_enabled = (fam & (LCHD_SWEEP_TEAM240 | LCHD_SWEEP_TEAM480 | LCHD_SWEEP_C8)) ? 1 : 0;
     a.forced = p.forced;
@@ -275,7 +276,7 @@ int launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinge
     if (fam & LCHD_SWEEP_INLINE) {
         const unsigned g = (unsigned)((a.n_pairs + kSweepWaves - 1) / kSweepWaves);
         launch_sweep_inline(s, cmax, g, a);
-        return 0;
+        return done;
     }
     const int64_t blocks = (a.n_pairs + kSweepWaves - 1) / kSweepWaves;
     // grid-stride: LDS tables are built once per block.  8192 workgroups = 8 rounds of the 1024 that are resident at a time: finer
@@ -287,9 +288,7 @@ int launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinge
     // 0.214 -> 0.200 ms; the same cap on the 10^6-pair launches costs 1-5 %: C4 sweep 2.69 -> 2.83 ms)
     const int64_t tcap_big = 16384, tcap_small = 4096, tcap_switch = 32768;
     const unsigned grid = (unsigned)(blocks < gcap ? blocks : gcap);
-    // returned: 1 (the "small" rule of this pass was the 8-bit-count one) | 2 (the companion launch was left out) | 4 (the record pass ran
-    // with the leftover-list counters)
-    const int info = (p.small_rule ? 1 : 0) | (p.companion_left_out ? 2 : 0) | (a.left_zero ? 4 : 0);
+    done.left_counters_used = a.left_zero != nullptr;  // (the record pass runs with the leftover-list counters)
     {
         const int64_t nb = (a.n_pairs + 255) / 256;
         const int mgrid = (int)(nb < kMetaPartials ? nb : kMetaPartials);
@@ -297,7 +296,7 @@ int launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinge
     }
     if (fam & LCHD_SWEEP_WIDE) {
         launch_sweep_wide(s, p.plain_mode, n_categories, a.n_pairs, p.fmode, a);
-        return info & 4;
+        return done;  // (no small rule, no companion)
     }
     const int tm = p.team_mode;
     unsigned bgrid = grid < kCompanionGrid ? grid : kCompanionGrid;  // the listed (larger) pairs are a minority whenever this launch does anything
@@ -324,7 +323,10 @@ int launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinge
     if ((fam & LCHD_SWEEP_TEAM240) && (fam & LCHD_SWEEP_TEAM480)) launch_team(s, cmax, tm, false, p.pre != 0, tgrid, a);
     if (fam & LCHD_SWEEP_INC) launch_sweep_inc(s, a.sd_fast, cmax, a);
     else if (fam & LCHD_SWEEP_PLAIN) launch_sweep_plain(s, p.plain_mode, p.ldstab != 0, cmax, grid, p.fmode, a);
-    return (fam & (LCHD_SWEEP_PLAIN | LCHD_SWEEP_INC)) ? (info & 5) : info;
+    done.small_is_c8 = p.small_rule != 0;
+    // (with an all-pairs family in the set every pair has a taker whatever the counts turn out to be: nothing for the caller to check)
+    done.companion_left_out = p.companion_left_out != 0 && !(fam & (LCHD_SWEEP_PLAIN | LCHD_SWEEP_INC));
+    return done;
 }
 
 // Kernels that may be launched with more than 64 KB of dynamic LDS need the limit raised per DEVICE: lchd_ctx_create calls this
