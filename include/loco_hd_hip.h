@@ -413,6 +413,10 @@ typedef struct lchd_sweep_plan {
     int32_t ldstab;            /* the plain family keeps its square-root tables in LDS (environments of at most 512 points) */
     int32_t fmode;             /* 0 the keys are F values, 1 inline CDFs only, 2 any CDF */
     int32_t wide_long;         /* wide family: a stride beyond 65535 points asks for its 64-bit-count form */
+    /* How the team families were launched (0 where the family is not in `families`, and from lchd_plan_sweep, which knows no launch):
+       consecutive pairs a wavefront takes at a time and co-schedules by chunk length, and workgroups of the launch. */
+    int32_t team_batch240, team_grid240;   /* the four-team form (pairs of at most 240 events) */
+    int32_t team_batch480, team_grid480;   /* the two-team form (at most 480 events) */
 } lchd_sweep_plan;
 /* Which sweep kernels a from_primitives pass launches, as a pure function (no context, no device).  Returns LCHD_OK, or LCHD_EVALUE
  * (null argument, n_pairs < 1, n_categories < 1).  The planner checks its own answer: a launch set that would not give every pair

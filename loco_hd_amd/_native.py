@@ -61,7 +61,8 @@ class SweepPlanC(C.Structure):
     """lchd_sweep_plan: what a pass launches."""
     _fields_ = [("families", C.c_uint32), ("slots", C.c_int32), ("pre", C.c_int32), ("small_rule", C.c_int32), ("second_rule", C.c_int32),
                 ("c8_rule", C.c_int32), ("forced", C.c_int32), ("left_listing", C.c_int32), ("companion_left_out", C.c_int32),
-                ("team_mode", C.c_int32), ("plain_mode", C.c_int32), ("ldstab", C.c_int32), ("fmode", C.c_int32), ("wide_long", C.c_int32)]
+                ("team_mode", C.c_int32), ("plain_mode", C.c_int32), ("ldstab", C.c_int32), ("fmode", C.c_int32), ("wide_long", C.c_int32),
+                ("team_batch240", C.c_int32), ("team_grid240", C.c_int32), ("team_batch480", C.c_int32), ("team_grid480", C.c_int32)]
 
     def as_dict(self) -> dict:
         return {name: int(getattr(self, name)) for name, _ in self._fields_}

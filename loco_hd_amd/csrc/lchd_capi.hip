@@ -392,6 +392,8 @@ static Tuning tuning_from_env() {  // the ONLY place that reads LCHD_* hooks (te
     t.force_cmax = env_int("LCHD_FORCE_CMAX", 0);
     t.per_pair = env_int("LCHD_PER_PAIR", 0);
     t.pre_rows = env_int("LCHD_PRE_ROWS", 0);
+    t.team_batch = env_int("LCHD_TEAM_BATCH", 0);
+    t.team_grid = env_int("LCHD_TEAM_GRID", 0);
     t.ensemble_block = env_int("LCHD_ENSEMBLE_BLOCK", 0);
     return t;
 }

@@ -231,6 +231,30 @@ bool plan_sweep(const lchd_sweep_query& q, lchd_sweep_plan& p) {
 // workgroups of the INDIRECT companion sweep (it walks every pair record and sweeps the few the team kernel left)
 // (measured: 1024 -> 2048: C2a 19.4 -> 16.6 us, C4 47.3 -> 37.3 us per pass; 4096: no further gain)
 constexpr unsigned kCompanionGrid = 2048u;
+// The team sweeps (k_sweep_duo) take kTeamBatch480 / kTeamBatch240 consecutive pairs per wavefront at a time and co-schedule, inside the batch, the pairs of
+// equal chunk length ("Batches").  A batch is swept by ONE wavefront, iteration after iteration, so batches make a
+// launch's work coarser; only LONG launches get them.
+// Long launches -- more than kTeamShortBlocks workgroups' worth of pairs at one iteration's pairs per wavefront (C2a: 262 144 pairs, C3:
+// 524 288), i.e. at least four rounds of batches over the wavefronts the device holds at a time.  Measured (one MI355X, bench lines,
+// parent 1.246 / 0.823 ms; batch / workgroup cap):
+//   C2a, two teams, 480 events    8 / 16384 1.235   16 / 4096 1.252   16 / 8192 1.219   16 / 16384 1.228   32 / 1024 1.328   32 / 2048 1.261
+//                                 32 / 4096 1.225   32 / 8192 1.233   64 / 1024 1.426   64 / 4096 1.285
+//   C3, four teams, 240 events    16 / 8192 0.785   32 / 2048 0.815   32 / 8192 0.776   64 / 2048 0.793   64 / 8192 0.779
+// A larger batch pairs better, but the last round of workgroups weighs more (the two-team form's iterations are twice as long, its
+// best batch half as large).  One cap serves both forms.
+// Short launches (a rank's 125 000-pair share of C2a under strong scaling) keep what they had before the batches: one iteration's pairs
+// per wavefront and trip (a "batch" of TEAMS pairs, nothing ranked) and at most kTeamShortCap workgroups, so that every workgroup
+// amortises its LDS table load over ~4 rounds (measured with --emulate-world 8, per-rank step median: 0.214 -> 0.200 ms against 16384
+// workgroups; the same cap on the 10^6-pair launches cost 1-5 %: C4 sweep 2.69 -> 2.83 ms).  With batches of 16 a list of 70 000 pairs
+// would be 1094 workgroups of 8 iterations each on a device that holds 1024: two rounds where 1.07 are needed.
+// Both are functions of the number of pairs alone: the same list always gets the same co-scheduling.
+constexpr int kTeamBatch480 = 16, kTeamBatch240 = 32;
+constexpr int64_t kTeamGridCap = 8192, kTeamShortCap = 4096, kTeamShortBlocks = 32768;
+static bool team_short(int teams, int64_t n_pairs) { return (n_pairs + teams * kSweepWaves - 1) / (teams * kSweepWaves) <= kTeamShortBlocks; }
+static int team_batch(int teams, int64_t n_pairs, int forced) {  // forced: LCHD_TEAM_BATCH
+    const int kb = forced > 0 ? std::min(forced, 64) : (team_short(teams, n_pairs) ? teams : (teams == 2 ? kTeamBatch480 : kTeamBatch240));
+    return std::max(teams, kb / teams * teams);
+}
 SweepLaunched launch_sweep(hipStream_t s, const Tuning& t, int n_categories, bool hellinger2, bool unit_weights, bool wf_pow, int sweep_hint,
                            const SweepArgs& a_in, lchd_sweep_plan* plan_out) {
     if (plan_out) *plan_out = lchd_sweep_plan{};
@@ -282,11 +306,8 @@ SweepLaunched launch_sweep(hipStream_t s, const Tuning& t, int n_categories, boo
     // grid-stride: LDS tables are built once per block.  8192 workgroups = 8 rounds of the 1024 that are resident at a time: finer
     // than that the table loads show, coarser the last round's imbalance does (measured on C2a: 4096 +2.8 %, 16384 +0.5 %)
     const int64_t gcap = 8192;
-    // ... the team sweeps (shorter iterations, a smaller table load per workgroup): 16384 (C2a 1.3648 -> 1.358 ms, C3 0.7835 -> 0.7769; 32768: no further gain)
-    // ... but a launch of at most 32768 team workgroups' worth of pairs (a rank's 125 000-pair share of C2a under strong scaling) is cut into
-    // 4096: every workgroup then amortises its LDS table load over ~4 rounds (measured with --emulate-world 8, per-rank step median:
-    // 0.214 -> 0.200 ms; the same cap on the 10^6-pair launches costs 1-5 %: C4 sweep 2.69 -> 2.83 ms)
-    const int64_t tcap_big = 16384, tcap_small = 4096, tcap_switch = 32768;
+    // ... the team sweeps: a wavefront takes a BATCH of consecutive pairs at a time (team_batch above); the grid is counted in batches
+    // and cut at kTeamGridCap / kTeamShortCap workgroups (LCHD_TEAM_GRID: tuning runs)
     const unsigned grid = (unsigned)(blocks < gcap ? blocks : gcap);
     done.left_counters_used = a.left_zero != nullptr;  // (the record pass runs with the leftover-list counters)
     {
@@ -304,23 +325,27 @@ SweepLaunched launch_sweep(hipStream_t s, const Tuning& t, int n_categories, boo
         const int64_t want = (a.left_expected + a.left_expected / 4 + kSweepWaves - 1) / kSweepWaves + 8;
         bgrid = (unsigned)std::min<int64_t>(bgrid, std::max<int64_t>(want, 16));
     }
-    const int64_t tblocks = (a.n_pairs + 2 * kSweepWaves - 1) / (2 * kSweepWaves);  // (two pairs per wavefront)
-    const int64_t tcap2 = tblocks <= tcap_switch ? tcap_small : tcap_big;
-    const unsigned tgrid = (unsigned)(tblocks < tcap2 ? tblocks : tcap2);
+    auto team_grid = [&](int teams, int batch) {  // one batch per wavefront, kSweepWaves wavefronts per workgroup
+        const int64_t tcap = t.team_grid > 0 ? t.team_grid : (team_short(teams, a.n_pairs) ? kTeamShortCap : kTeamGridCap);
+        const int64_t tblocks = ((a.n_pairs + batch - 1) / batch + kSweepWaves - 1) / kSweepWaves;
+        return (unsigned)(tblocks < tcap ? tblocks : tcap);
+    };
+    const int tbatch = team_batch(2, a.n_pairs, t.team_batch), dbatch = team_batch(64 / kDuoTL, a.n_pairs, t.team_batch);  // 480 / 240 events
+    const unsigned tgrid = team_grid(2, tbatch), dgrid = team_grid(64 / kDuoTL, dbatch);
+    if (plan_out) {  // (the record of the pass shows how its team kernels were launched)
+        if (fam & LCHD_SWEEP_TEAM240) { plan_out->team_batch240 = dbatch; plan_out->team_grid240 = (int32_t)dgrid; }
+        if (fam & LCHD_SWEEP_TEAM480) { plan_out->team_batch480 = tbatch; plan_out->team_grid480 = (int32_t)tgrid; }
+    }
     // launch order: the first rule's kernel, the companion, the second rule's kernel, the all-pairs kernel
     if (fam & LCHD_SWEEP_TEAM240) {
-        constexpr int kTeamPairs = (64 / kDuoTL) * kSweepWaves;  // pairs per workgroup and round
-        const int64_t dblocks = (a.n_pairs + kTeamPairs - 1) / kTeamPairs;
-        const int64_t tcap = dblocks <= tcap_switch ? tcap_small : tcap_big;
-        const unsigned dgrid = (unsigned)(dblocks < tcap ? dblocks : tcap);
-        launch_team(s, cmax, tm, true, p.pre != 0, dgrid, a);
+        launch_team(s, cmax, tm, true, p.pre != 0, dgrid, dbatch, a);
     } else if (fam & LCHD_SWEEP_TEAM480) {
-        launch_team(s, cmax, tm, false, p.pre != 0, tgrid, a);
+        launch_team(s, cmax, tm, false, p.pre != 0, tgrid, tbatch, a);
     } else if (fam & LCHD_SWEEP_C8) {
         launch_sweep_c8(s, cmax, grid, a);
     }
     if (fam & LCHD_SWEEP_INDIRECT) launch_sweep_indirect(s, cmax, (fam & LCHD_SWEEP_C8) ? 0 : tm, bgrid, a);
-    if ((fam & LCHD_SWEEP_TEAM240) && (fam & LCHD_SWEEP_TEAM480)) launch_team(s, cmax, tm, false, p.pre != 0, tgrid, a);
+    if ((fam & LCHD_SWEEP_TEAM240) && (fam & LCHD_SWEEP_TEAM480)) launch_team(s, cmax, tm, false, p.pre != 0, tgrid, tbatch, a);
     if (fam & LCHD_SWEEP_INC) launch_sweep_inc(s, a.sd_fast, cmax, a);
     else if (fam & LCHD_SWEEP_PLAIN) launch_sweep_plain(s, p.plain_mode, p.ldstab != 0, cmax, grid, p.fmode, a);
     done.small_is_c8 = p.small_rule != 0;

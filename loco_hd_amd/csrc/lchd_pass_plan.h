@@ -72,6 +72,8 @@ struct Tuning {
     int force_cmax = 0;             // LCHD_FORCE_CMAX: at least this many category slots
     int per_pair = 0;               // LCHD_PER_PAIR: -1 never a side B without de-duplication, 1 whenever it applies, 0: from the previous pass (side-B anchors (almost) all unique)
     int pre_rows = 0;               // LCHD_PRE_ROWS: -1 never prefix-count rows next to the environments (the team sweeps build their chunk-start counts per tile), 1 also for small calls, 0: by the rule of plan_pass
+    int team_batch = 0;             // LCHD_TEAM_BATCH: pairs per wavefront and batch of the team sweeps (0: team_batch() of lchd_kernels.hip; else rounded to a multiple of the teams, at most 64)
+    int team_grid = 0;              // LCHD_TEAM_GRID: at most this many workgroups per team-sweep launch (0: the measured caps of launch_sweep)
     int ensemble_block = 0;         // LCHD_ENSEMBLE_BLOCK: at most this many structures resident in the dense ensemble call's environment store (0: as many as the free HBM holds)
 };
 

@@ -225,7 +225,8 @@ void launch_sweep_indirect(hipStream_t s, int cmax, int tm, unsigned grid, const
 // lchd_sweep_team.hip: several pairs per wavefront (tile240: four pairs of <= 240 events, else two 8-bit-count pairs of <= 480);
 // tm: 0 Hellinger-2 with unit weights, 1 with category weights, 2 Kolmogorov-Smirnov with unit weights; pre: both stores carry
 // prefix-count rows of the width this slot count reads (tm 0 / 2, at most 16 slots: the PRE instantiations)
-void launch_team(hipStream_t s, int cmax, int tm, bool tile240, bool pre, unsigned grid, const SweepArgs& a);
+// batch: consecutive pairs a wavefront takes at a time and co-schedules by chunk length (team_batch, lchd_kernels.hip)
+void launch_team(hipStream_t s, int cmax, int tm, bool tile240, bool pre, unsigned grid, int batch, const SweepArgs& a);
 // lchd_sweep_wide.hip: 33 .. 65534 categories, environments beyond 65535 points
 void launch_sweep_wide(hipStream_t s, int mode, int n_cat, int64_t n_pairs, int fmode, const SweepArgs& a);
 // per-device attributes (dynamic LDS above 64 KB) of the families, called by init_device_kernels

@@ -4,8 +4,42 @@
 #include "lchd_sweep_common.h"
 
 namespace lchd {
+// What a pair record means to the team kernel of `rule` -- for the batch's sort key and for the iteration that sweeps the pair alike.
+struct TeamPair {
+    int nA, nB;   // points of the two environments, anchors included
+    bool mine;    // this kernel writes the pair's score: it sweeps it, or the pair is unusable (NaN); larger pairs belong to k_sweep
+    bool valid;   // this kernel sweeps it
+};
+__device__ __forceinline__ TeamPair team_pair(int rule, bool live, const int4& m) {
+    TeamPair k;
+    k.nA = m.z & 0xFFFFFF;
+    k.nB = m.w & 0xFFFFFF;
+    const bool usable = live && k.nA > 0 && k.nB > 0;
+    k.mine = !usable || pair_is_small(rule, k.nA, k.nB);
+    k.valid = usable && k.mine;
+    return k;
+}
+// The stable rank of a lane's key (0 .. 15) among the first kb lanes of the wavefront; a lane beyond them keeps its own number, so the
+// ranks are a permutation of 0 .. 63.  A 4-bit radix over ballots, most significant bit first: every lane keeps the set of lanes whose
+// key is smaller than its own (lt) and of those that agree with it in the bits seen so far (eq); its rank is |lt| + the lanes of eq
+// before it.  A pure function of the keys (no atomics): the same list always gets the same co-scheduling.  (Sixteen ballot + mbcnt
+// steps, one per key value, come out 13 vector instructions longer.)
+__device__ __forceinline__ int team_batch_rank(int key, int lane, int kb) {
+    const bool inb = lane < kb;
+    uint64_t lt = 0ull, eq = __ballot(inb);
+#pragma unroll
+    for (int bit = 3; bit >= 0; --bit) {
+        const bool one = (key >> bit) & 1;
+        const uint64_t b = __ballot(one);
+        lt |= one ? (eq & ~b) : 0ull;
+        eq &= one ? b : ~b;
+    }
+    const int r = __popcll(lt) + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(eq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)eq, 0u));
+    return inb ? r : lane;
+}
+
 // ------------------------------------------------------------------------------------------------
-// K2 for small environments: TWO anchor pairs per wavefront, 32 lanes each.
+// K2 for small environments: TWO (or four) anchor pairs per wavefront and iteration, 32 (16) lanes each.
 //
 // With environments of ~70-100 points per side (coarse-grained typing, the reference's main use) a pair has ~150 merged
 // events: one wavefront per pair spends most of its instructions on the per-tile prologue (staging, merge path, scan, state
@@ -14,6 +48,18 @@ namespace lchd {
 // configuration must be Hellinger-2 with unit category weights, CDF-keyed environments, at most 16 category slots.  The
 // host launches this kernel AND k_sweep; k_pair_meta counts the qualifying pairs (DeviceStatus::n_small): when they are
 // the majority this kernel sweeps them and k_sweep only the rest, otherwise this kernel returns at once.
+//
+// Batches.  The tile's loops run a wave-uniform number of trips, the longest chunk length epl = ceil(T / TL) among the wavefront's
+// teams; a team with a shorter chunk issues the other trips with its lanes masked off.  So a wavefront does not take TEAMS consecutive
+// pairs per iteration but a BATCH of `batch` consecutive pairs (a kernel argument, at most 64, a multiple of TEAMS; grid-stride over
+// batches): once per batch every lane loads ONE pair record (coalesced), works out its key -- epl if this kernel sweeps the pair, else
+// 0 -- and its stable rank among the batch's keys (team_batch_rank); one ds_permute sends the lane's number to the lane of its rank.
+// Iteration q sweeps the pairs of rank TEAMS q + team: a ds_bpermute fetches the pair's place in the batch, the record is read again
+// (from the cache) and everything per pair -- out[p], wf_index[p], offsets, anchors' categories -- follows that p.  Teams of equal
+// chunk length share a wavefront; the pairs of key 0 come first and an iteration without a pair to sweep is skipped (its unusable
+// pairs get their NaN).  Only the record's PLACE is kept in a register across the tile (one VGPR: the 28-slot form stands at its limit
+// of 168), and no LDS is added.  A pair's score does not depend on its partners: the trip counts only bound loops whose bodies are
+// guarded per lane.
 // ------------------------------------------------------------------------------------------------
 constexpr int kTeamBigWaves = 3;   // waves per SIMD k_sweep_duo is compiled for with more than 16 category slots, and with category weights and 9 .. 16 (their counts in LDS bytes, TeamTile::LCNT); 4 otherwise
 // (the name is historic: round 1 swept TWO pairs per wavefront; with TL = 16 a wavefront sweeps FOUR -- the per-tile prologue, which
@@ -29,7 +75,7 @@ constexpr int kTeamBigWaves = 3;   // waves per SIMD k_sweep_duo is compiled for
 // Hellinger-2: every event needs all categories, but as INTEGERS -- max_c |a_c N_b - b_c N_a| over the 8-bit count fields (two 24-bit
 // multiplies, one v_sad_u32, one max per category), scaled once by 1 / (N_a N_b) from the reciprocal-root table; no square root.
 template <int CMAX, int TL = kDuoTL, int TILE_ = kDuoTile, bool WGT = false, bool KSM = false, bool PRE = false>
-__global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8)) ? 4 : kTeamBigWaves)) void k_sweep_duo(SweepArgs args) {
+__global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8)) ? 4 : kTeamBigWaves)) void k_sweep_duo(SweepArgs args, int batch) {
     // (the tile itself -- merge path, chunk histogram, count scans, event loop, stitching -- is lchd_team_tile.h)
     using TT = TeamTile<CMAX, TL, TILE_, WGT, KSM, PRE>;
     constexpr int TEAMS = TT::TEAMS, EPL = TT::EPL, TILE = TT::TILE, WPB = kSweepWaves, NT = TT::NT, LW = TT::LW;
@@ -60,116 +106,144 @@ __global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8
     uint8_t* cA = c_[wv][team];
     unsigned char* lcl = reinterpret_cast<unsigned char*>(lc_[LCNT ? wv : 0]) + lane * 8;  // this lane's eight bytes of word 0
 
-    const int64_t pstride = (int64_t)gridDim.x * WPB * TEAMS;
-    for (int64_t pb = ((int64_t)blockIdx.x * WPB + wv) * TEAMS; pb < args.n_pairs; pb += pstride) {
-        const int64_t p = pb + team;
-        const bool live = p < args.n_pairs;
-        const int4 m = args.meta[live ? p : pb];
-        const bool usable = live && (m.z & 0xFFFFFF) > 0 && (m.w & 0xFFFFFF) > 0;
-        const bool mine = !usable || pair_is_small(RULE, m.z & 0xFFFFFF, m.w & 0xFFFFFF);  // larger pairs belong to k_sweep
-        const bool valid = usable && mine;
-        const int mA = valid ? (m.z & 0xFFFFFF) - 1 : 0, mB = valid ? (m.w & 0xFFFFFF) - 1 : 0, T = mA + mB;  // non-anchor events
-        const int c0a = (m.z >> 24) & 255, c0b = (m.w >> 24) & 255;
-        // (a dictionary's key sets: the set of this pair's weight function -- k_pair_meta has checked the index of every usable pair)
-        int64_t ksetA = 0, ksetB = 0;
-        if (args.wf_index) {  // (wave-uniform: configurations with one weight function never multiply)
-            const int64_t kset = valid ? args.wf_index[p] : 0;
-            ksetA = kset * args.env_a.set_stride;
-            ksetB = kset * args.env_b.set_stride;
+    // ---- batches: kb consecutive pairs per wavefront, one record per lane, co-scheduled by chunk length (see the header) ----
+    const int kb = __builtin_amdgcn_readfirstlane(batch);  // TEAMS <= kb <= 64, a multiple of TEAMS
+    const int64_t bstride = (int64_t)gridDim.x * WPB * kb;
+    for (int64_t base = ((int64_t)blockIdx.x * WPB + wv) * kb; base < args.n_pairs; base += bstride) {
+        int sl;  // lane r: the index in the batch of the pair of rank r (p = base + sl), -1 where the batch has no such pair
+        {
+            // (the lane number, worked out HERE from a zero the optimiser cannot see through: carried from the kernel's head it is one more
+            // register live across the tile, and the 28-slot forms, which stand at their limit of 168, spill it)
+            uint32_t zero = 0u;
+            asm volatile("" : "+v"(zero));
+            const int bl = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
+            const int nrec = (int)min((int64_t)kb, args.n_pairs - base);  // (wave-uniform) the last batch of the list may be short
+            const bool have = bl < nrec;
+            const int4 r = (args.meta + base)[have ? bl : 0];
+            const TeamPair tp = team_pair(RULE, have, r);
+            // the key: the pair's chunk length; 0 for every pair this kernel does not sweep -- they sort together and first
+            const int key = tp.valid ? (tp.nA + tp.nB - 2 + TL - 1) / TL : 0;
+            // (wave-uniform: a batch of one iteration's pairs -- what a short launch gets -- has nothing to rank)
+            const int rank = kb > TEAMS ? team_batch_rank(key, bl, kb) : bl;
+            sl = __builtin_amdgcn_ds_permute(rank * 4, have ? bl : -1);
         }
-        // (slot x stride as ONE 32 x 32 -> 64-bit multiply: slots and strides are below 2^31)
-        const uint64_t offA = (uint64_t)(uint32_t)m.x * (uint32_t)args.env_a.stride, offB = (uint64_t)(uint32_t)m.y * (uint32_t)args.env_b.stride;
-        const uint64_t* __restrict__ kA = args.env_a.key + offA + ksetA;
-        const uint64_t* __restrict__ kB = args.env_b.key + offB + ksetB;
-        const uint8_t* __restrict__ tA = args.env_a.cat + offA;
-        const uint8_t* __restrict__ tB = args.env_b.cat + offB;
-        const double F0 = valid ? u2d(kA[0]) : 0.0;            // F(0): both anchors sit at distance 0
-        // list B starts at an EVEN entry of the buffer (one unused entry behind an odd list A): the staging below moves two entries per
-        // lane and round -- one 16-byte key load, one 16-byte LDS write -- and no pair of entries straddles the two lists
-        const int mAe = (mA + 1) & ~1, Tb = mAe + mB;  // <= TILE + 1: the buffers hold TILE + 2 entries
-        uint64_t* sB = sA + mAe;
-        uint8_t* cB = cA + mAe;
+        const int nq = kb / TEAMS;
+#pragma unroll 1
+        for (int q = 0; q < nq; ++q) {
+            const int src = (q * TEAMS + team) * 4;  // this team's pair of the iteration: rank TEAMS q + team
+            const int pl = __builtin_amdgcn_ds_bpermute(src, sl);
+            const bool live = pl >= 0;
+            const int64_t p = base + (live ? pl : 0);
+            const int4 m = args.meta[p];  // (the batch's records are in the cache: every lane of the wavefront has just read one)
+            const TeamPair tp = team_pair(RULE, live, m);
+            const bool mine = tp.mine, valid = tp.valid;
+            if (__ballot(valid) == 0ull) {  // (wave-uniform) nothing to sweep: an unusable pair still gets its NaN
+                if (tl == TL - 1 && live && mine) args.out[p] = nan("");
+                continue;
+            }
+            const int mA = valid ? tp.nA - 1 : 0, mB = valid ? tp.nB - 1 : 0, T = mA + mB;  // non-anchor events
+            const int c0a = (m.z >> 24) & 255, c0b = (m.w >> 24) & 255;
+            // (a dictionary's key sets: the set of this pair's weight function -- k_pair_meta has checked the index of every usable pair)
+            int64_t ksetA = 0, ksetB = 0;
+            if (args.wf_index) {  // (wave-uniform: configurations with one weight function never multiply)
+                const int64_t kset = valid ? args.wf_index[p] : 0;
+                ksetA = kset * args.env_a.set_stride;
+                ksetB = kset * args.env_b.set_stride;
+            }
+            // (slot x stride as ONE 32 x 32 -> 64-bit multiply: slots and strides are below 2^31)
+            const uint64_t offA = (uint64_t)(uint32_t)m.x * (uint32_t)args.env_a.stride, offB = (uint64_t)(uint32_t)m.y * (uint32_t)args.env_b.stride;
+            const uint64_t* __restrict__ kA = args.env_a.key + offA + ksetA;
+            const uint64_t* __restrict__ kB = args.env_b.key + offB + ksetB;
+            const uint8_t* __restrict__ tA = args.env_a.cat + offA;
+            const uint8_t* __restrict__ tB = args.env_b.cat + offB;
+            const double F0 = valid ? u2d(kA[0]) : 0.0;            // F(0): both anchors sit at distance 0
+            // list B starts at an EVEN entry of the buffer (one unused entry behind an odd list A): the staging below moves two entries per
+            // lane and round -- one 16-byte key load, one 16-byte LDS write -- and no pair of entries straddles the two lists
+            const int mAe = (mA + 1) & ~1, Tb = mAe + mB;  // <= TILE + 1: the buffers hold TILE + 2 entries
+            uint64_t* sB = sA + mAe;
+            uint8_t* cB = cA + mAe;
 
-        // lane tl of a team owns merged events [d0, d1) of its pair
-        const int epl = (T + TL - 1) / TL;  // <= EPL
-        int epl_w = __builtin_amdgcn_readlane(epl, 0);  // wave-uniform trip count: the longest of the teams' chunks
+            // lane tl of a team owns merged events [d0, d1) of its pair
+            const int epl = (T + TL - 1) / TL;  // <= EPL
+            int epl_w = __builtin_amdgcn_readlane(epl, 0);  // wave-uniform trip count: the longest of the teams' chunks
 #pragma unroll
-        for (int k = 1; k < TEAMS; ++k) epl_w = max(epl_w, __builtin_amdgcn_readlane(epl, k * TL));
+            for (int k = 1; k < TEAMS; ++k) epl_w = max(epl_w, __builtin_amdgcn_readlane(epl, k * TL));
 
-        wave_sync_lds();  // the previous pairs' tiles are fully consumed
-        {   // stage [A's points | pad | B's points]: entries 2 q and 2 q + 1 of the buffer by lane q % TL in round q / TL; all loads before
-            // the first LDS write.  A pair's second entry may lie one past its list's last point (still inside the environment's slot or,
-            // for the last slot, the workspace's slack): it lands in the pad entry or behind the buffer's used part and is never read.
-            constexpr int EPL2 = (EPL + 1) / 2;
-            static_assert(2 * TL * EPL2 >= TILE_ + 1, "the rounds cover the buffer's used part (pad entry included)");
-            typedef unsigned long long __attribute__((ext_vector_type(2), aligned(8))) key2_t;
-            const int epl2 = (Tb + 2 * TL - 1) / (2 * TL);
-            int epl2_w = __builtin_amdgcn_readlane(epl2, 0);
+            wave_sync_lds();  // the previous pairs' tiles are fully consumed
+            {   // stage [A's points | pad | B's points]: entries 2 q and 2 q + 1 of the buffer by lane q % TL in round q / TL; all loads before
+                // the first LDS write.  A pair's second entry may lie one past its list's last point (still inside the environment's slot or,
+                // for the last slot, the workspace's slack): it lands in the pad entry or behind the buffer's used part and is never read.
+                constexpr int EPL2 = (EPL + 1) / 2;
+                static_assert(2 * TL * EPL2 >= TILE_ + 1, "the rounds cover the buffer's used part (pad entry included)");
+                typedef unsigned long long __attribute__((ext_vector_type(2), aligned(8))) key2_t;
+                const int epl2 = (Tb + 2 * TL - 1) / (2 * TL);
+                int epl2_w = __builtin_amdgcn_readlane(epl2, 0);
 #pragma unroll
-            for (int k = 1; k < TEAMS; ++k) epl2_w = max(epl2_w, __builtin_amdgcn_readlane(epl2, k * TL));
-            key2_t rk[EPL2];
-            uint32_t rc[EPL2];
-            const uint64_t* kBs = kB - mAe;
-            const uint8_t* tBs = tB - mAe;
+                for (int k = 1; k < TEAMS; ++k) epl2_w = max(epl2_w, __builtin_amdgcn_readlane(epl2, k * TL));
+                key2_t rk[EPL2];
+                uint32_t rc[EPL2];
+                const uint64_t* kBs = kB - mAe;
+                const uint8_t* tBs = tB - mAe;
 #pragma unroll
-            for (int u = 0; u < EPL2; ++u) { rk[u] = key2_t{0ull, 0ull}; rc[u] = 0u; }
-            if (valid) {
+                for (int u = 0; u < EPL2; ++u) { rk[u] = key2_t{0ull, 0ull}; rc[u] = 0u; }
+                if (valid) {
+#pragma unroll
+                    for (int u = 0; u < EPL2; ++u) {
+                        if (u < epl2_w) {  // (wave-uniform: rounds no team of this wavefront needs are skipped)
+                            const int t0 = 2 * (tl + TL * u);
+                            const int tt = t0 < Tb ? t0 : 0;  // (beyond the used part: re-read the row's first pair, nothing is written)
+                            const bool isA = tt < mAe;
+                            const uint64_t* src = (isA ? kA : kBs) + 1 + tt;
+                            const uint8_t* csrc = (isA ? tA : tBs) + 1 + tt;
+                            rk[u] = *reinterpret_cast<const key2_t*>(src);
+                            rc[u] = (uint32_t)csrc[0] | ((uint32_t)csrc[1] << 8);
+                        }
+                    }
+                }
 #pragma unroll
                 for (int u = 0; u < EPL2; ++u) {
-                    if (u < epl2_w) {  // (wave-uniform: rounds no team of this wavefront needs are skipped)
+                    if (u < epl2_w) {
                         const int t0 = 2 * (tl + TL * u);
-                        const int tt = t0 < Tb ? t0 : 0;  // (beyond the used part: re-read the row's first pair, nothing is written)
-                        const bool isA = tt < mAe;
-                        const uint64_t* src = (isA ? kA : kBs) + 1 + tt;
-                        const uint8_t* csrc = (isA ? tA : tBs) + 1 + tt;
-                        rk[u] = *reinterpret_cast<const key2_t*>(src);
-                        rc[u] = (uint32_t)csrc[0] | ((uint32_t)csrc[1] << 8);
+                        if (t0 < Tb) {
+                            *reinterpret_cast<ulonglong2*>(sA + t0) = ulonglong2{rk[u].x, rk[u].y};
+                            *reinterpret_cast<uint16_t*>(cA + t0) = (uint16_t)rc[u];
+                        }
                     }
                 }
             }
-#pragma unroll
-            for (int u = 0; u < EPL2; ++u) {
-                if (u < epl2_w) {
-                    const int t0 = 2 * (tl + TL * u);
-                    if (t0 < Tb) {
-                        *reinterpret_cast<ulonglong2*>(sA + t0) = ulonglong2{rk[u].x, rk[u].y};
-                        *reinterpret_cast<uint16_t*>(cA + t0) = (uint16_t)rc[u];
-                    }
-                }
-            }
-        }
-        wave_sync_lds();
+            wave_sync_lds();
 
-        // (PRE: the prefix-count rows of the two environments; an unusable pair's records may name slots that do not exist: row 0 of slot 0)
-        const uint64_t* preA = PRE ? args.env_a.pre + (valid ? offA / kPreStep * (uint64_t)TT::NW : 0ull) : nullptr;  // (slot strides are multiples of kPreStep)
-        const uint64_t* preB = PRE ? args.env_b.pre + (valid ? offB / kPreStep * (uint64_t)TT::NW : 0ull) : nullptr;
-        const double acc = TT::run(sA, cA, sB, cB, mA, mB, T, epl, epl_w, c0a, c0b, F0, Finf0, t_sqrt, t_rsqrt, w_s, lcl, tl, preA, preB);
-        if (tl == TL - 1 && live && mine) args.out[p] = valid ? acc : nan("");  // (categories were checked when the environments were built)
+            // (PRE: the prefix-count rows of the two environments; an unusable pair's records may name slots that do not exist: row 0 of slot 0)
+            const uint64_t* preA = PRE ? args.env_a.pre + (valid ? offA / kPreStep * (uint64_t)TT::NW : 0ull) : nullptr;  // (slot strides are multiples of kPreStep)
+            const uint64_t* preB = PRE ? args.env_b.pre + (valid ? offB / kPreStep * (uint64_t)TT::NW : 0ull) : nullptr;
+            const double acc = TT::run(sA, cA, sB, cB, mA, mB, T, epl, epl_w, c0a, c0b, F0, Finf0, t_sqrt, t_rsqrt, w_s, lcl, tl, preA, preB);
+            if (tl == TL - 1 && live && mine) args.out[p] = valid ? acc : nan("");  // (categories were checked when the environments were built)
+        }
     }
 }
 
 template <int CM, int TM, bool PRE>
-static void launch_team_c(hipStream_t s, bool tile240, unsigned grid, const SweepArgs& a) {
+static void launch_team_c(hipStream_t s, bool tile240, unsigned grid, int batch, const SweepArgs& a) {
     constexpr int NTH = 64 * kSweepWaves;
     constexpr bool WGT = TM == 1, KSM = TM == 2;
-    if (tile240) k_sweep_duo<CM, kDuoTL, kDuoTile, WGT, KSM, PRE><<<grid, NTH, 0, s>>>(a);
-    else k_sweep_duo<CM, 32, kTeam8Tile, WGT, KSM, PRE><<<grid, NTH, 0, s>>>(a);
+    if (tile240) k_sweep_duo<CM, kDuoTL, kDuoTile, WGT, KSM, PRE><<<grid, NTH, 0, s>>>(a, batch);
+    else k_sweep_duo<CM, 32, kTeam8Tile, WGT, KSM, PRE><<<grid, NTH, 0, s>>>(a, batch);
 }
 template <int TM>
-static void launch_team_t(hipStream_t s, int cmax, bool tile240, bool pre, unsigned grid, const SweepArgs& a) {
+static void launch_team_t(hipStream_t s, int cmax, bool tile240, bool pre, unsigned grid, int batch, const SweepArgs& a) {
     with_slots<kSweepSlots>(cmax, [&](auto S) {
         constexpr int CM = (TM != 0 && S > 16) ? 16 : S;  // (weights / Kolmogorov-Smirnov: at most 16 slots, checked by plan_sweep)
         // both stores carry prefix-count rows of the width this slot count reads (k_env_group wrote them): the PRE instantiations
         if constexpr (TM != 1 && CM <= 16) {
-            if (pre && cmax <= 16) return launch_team_c<CM, TM, true>(s, tile240, grid, a);
+            if (pre && cmax <= 16) return launch_team_c<CM, TM, true>(s, tile240, grid, batch, a);
         }
-        launch_team_c<CM, TM, false>(s, tile240, grid, a);
+        launch_team_c<CM, TM, false>(s, tile240, grid, batch, a);
     });
 }
-void launch_team(hipStream_t s, int cmax, int tm, bool tile240, bool pre, unsigned grid, const SweepArgs& a) {
-    if (tm == 2) launch_team_t<2>(s, cmax, tile240, pre, grid, a);
-    else if (tm == 1) launch_team_t<1>(s, cmax, tile240, pre, grid, a);
-    else launch_team_t<0>(s, cmax, tile240, pre, grid, a);
+void launch_team(hipStream_t s, int cmax, int tm, bool tile240, bool pre, unsigned grid, int batch, const SweepArgs& a) {
+    if (tm == 2) launch_team_t<2>(s, cmax, tile240, pre, grid, batch, a);
+    else if (tm == 1) launch_team_t<1>(s, cmax, tile240, pre, grid, batch, a);
+    else launch_team_t<0>(s, cmax, tile240, pre, grid, batch, a);
 }
 
 }  // namespace lchd
