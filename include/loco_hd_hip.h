@@ -266,7 +266,7 @@ int lchd_cloud_get_coords(lchd_ctx *ctx, lchd_cloud *cloud, double *xyz_out, int
  *           combination of per-axis choices other than "all original" (up to 26 per atom), written in ascending image code
  *           cx + 3 cy + 9 cz (c = 0 original, 1 +L, 2 -L) behind the ghosts of the atoms in front: the cloud is a function of its input
  *   reach   threshold_distance <= reach <= min(Lx, Ly, Lz): one layer of images suffices and an anchor never meets its own image
- * Triclinic cells, the dense from_coords / from_dmxs paths and device groups are out of scope. */
+ * Triclinic cells have calls of their own further down; the dense from_coords / from_dmxs paths and device groups are out of scope. */
 /* Host only, no device: LCHD_EVALUE for a non-finite or non-positive edge or reach, or reach > the smallest edge of a box. */
 int lchd_box_validate(const double *boxes /* [n_boxes][3] */, int32_t n_boxes, double reach);
 /* The image cloud of `src` -- a single structure, a batch (ragged included) or a frames buffer (the frames loaded last).  boxes: HOST
@@ -288,6 +288,40 @@ int lchd_from_primitives_periodic(lchd_ctx *ctx, const lchd_config *cfg, const d
                                   const int32_t *tag_a, int64_t n_a, const double *xyz_b, const int32_t *cat_b,
                                   const int32_t *tag_b, int64_t n_b, const int64_t *anchors, const int32_t *wf_index,
                                   int64_t n_pairs, double threshold_distance, const double *box_a, const double *box_b, double *out);
+
+/* ---- periodic boundaries in triclinic cells (additive) ---------------------------------------------
+ * The siblings of the box calls above for a CELL of three lattice vectors a, b, c: a 3 x 3 row-major f64 matrix, row 0 = a.  Any
+ * non-singular matrix is a cell: left-handed, not reduced, strongly skewed, not lower-triangular.  Lifetime, stream and error rules are
+ * those of the box calls; an image cloud is a box cloud or a cell cloud from its creation on.
+ *   widths  w_k = |det| / |cross product of the other two vectors|: the distance between the two faces of the cell that axis k joins.
+ *           det = a . (b x c); every cross component is u1 v2 - u2 v1 (cyclic), every sum runs left to right, every norm is
+ *           sqrt(x x + y y + z z): plain f64, nothing fused, so a caller can compute the very same numbers
+ *   reach   threshold_distance <= reach <= min(w_0, w_1, w_2): a shift of 2 along axis k moves an atom of the cell at least w_k away
+ *           from every point of the cell, so one layer of images (shifts in {-1, 0, 1}^3) is all there is, and an anchor never meets
+ *           its own image (a non-zero lattice vector is at least min w long)
+ *   wrap    f = x . cell^-1 (the inverse is computed on the host in f64), p = x - (floor(f_0) a + floor(f_1) b + floor(f_2) c); the
+ *           wrapped originals keep the slots 0 .. n - 1
+ *   images  with g = p . cell^-1: along axis k the image p + a_k exists iff g_k w_k < reach, the image p - a_k iff (1 - g_k) w_k <= reach.
+ *           This slab rule is a superset of the images within `reach` of any point of the cell; the search measures real distances.
+ *           A ghost is any combination of per-axis choices other than "all original" (up to 26 per atom), in ascending image code
+ *           c0 + 3 c1 + 9 c2 (c = 0 original, 1 plus, 2 minus), as in a box
+ *   ghosts  coordinate d of a ghost is p[d] + t[d], t[d] = (i a[d] + j b[d]) + k c[d] with i, j, k in {-1, 0, 1} held as doubles:
+ *           plain f64 products and sums in exactly that order, no fused multiply-add.  A host that reads the wrapped originals back
+ *           (lchd_cloud_get_coords) can therefore rebuild every ghost bit for bit. */
+/* Host only, no device: LCHD_EVALUE for a non-finite entry, a singular cell (|det| not > 0, or below 1e-12 |a| |b| |c|), a reach that is
+ * not finite and > 0, or a reach above the smallest width of a cell. */
+int lchd_cell_validate(const double *cells /* [n_cells][9] */, int32_t n_cells, double reach);
+/* lchd_cloud_create_images for cells: HOST [n_cells][9], n_cells = 1 (one cell for every structure) or the number of structures.
+ * What an image cloud refuses (lchd_cloud_set_coords, lchd_frames_load*, a threshold beyond its reach) a cell cloud refuses too. */
+int lchd_cloud_create_images_cell(lchd_ctx *ctx, lchd_cloud *src, const double *cells, int32_t n_cells, double reach, lchd_cloud **out);
+/* lchd_cloud_update_images for a cloud made by the call above.  Updating a box cloud through this call, or a cell cloud through
+ * lchd_cloud_update_images, is LCHD_EVALUE. */
+int lchd_cloud_update_images_cell(lchd_ctx *ctx, lchd_cloud *images, lchd_cloud *src, const double *cells, int32_t n_cells);
+/* lchd_from_primitives_periodic with cells: cell_a / cell_b are HOST [9] matrices of the two structures, NULL for a non-periodic side. */
+int lchd_from_primitives_periodic_cell(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a,
+                                       const int32_t *tag_a, int64_t n_a, const double *xyz_b, const int32_t *cat_b,
+                                       const int32_t *tag_b, int64_t n_b, const int64_t *anchors, const int32_t *wf_index,
+                                       int64_t n_pairs, double threshold_distance, const double *cell_a, const double *cell_b, double *out);
 
 /* ---- multi-GPU ------------------------------------------------------------------------------------
  * The reference's parallelism lives INSIDE the core call: a thread pool that is a field of `LoCoHD` (src/locohd.rs:53,

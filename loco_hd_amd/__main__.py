@@ -13,7 +13,7 @@ from argparse import ArgumentParser, Namespace
 from pathlib import Path
 from typing import Dict, FrozenSet, List, Optional, Sequence, Tuple
 
-from .api import LoCoHD, TagPairingRule, WeightFunction
+from .api import LoCoHD, TagPairingRule, WeightFunction, cell_from_lengths_angles
 from .atom_converter_utils import PrimitiveAssigner, PrimitiveAtomTemplate, prat_to_pra
 from .pdb_reader import PDBParser
 
@@ -63,8 +63,11 @@ def parse_cli_args(argv: Optional[Sequence[str]] = None) -> Namespace:
     parser = ArgumentParser(prog="python -m loco_hd_amd", description="LoCoHD scores of anchor pairs of two PDB structures (MI355X)")
     for short, long_, kind, default, required, text in _FLAGS:
         parser.add_argument(short, long_, type=kind, default=default, required=required, help=text)
-    parser.add_argument("--periodic", action="store_true",
-                        help="periodic boundaries: each structure in the orthorhombic box of its CRYST1 record (additive)")
+    periodic = parser.add_mutually_exclusive_group()
+    periodic.add_argument("--periodic", action="store_true",
+                          help="periodic boundaries: each structure in the orthorhombic box of its CRYST1 record (additive)")
+    periodic.add_argument("--periodic-cell", action="store_true",
+                          help="periodic boundaries: each structure in the cell of its CRYST1 record, triclinic or not (additive)")
     ns = parser.parse_args(argv)
     for key in ("tag_pairing_rule_args", "weight_function_args"):
         setattr(ns, key, json.loads(getattr(ns, key)))
@@ -80,6 +83,17 @@ def orthorhombic_box(cell, path) -> Tuple[float, float, float]:
     return cell[:3]
 
 
+def cryst1_cell(cell, path):
+    """The 3 x 3 cell of a CRYST1 record (a along x, b in the xy plane); SystemExit with a message where --periodic-cell cannot
+    use the structure."""
+    if cell is None:
+        raise SystemExit(f"--periodic-cell: {path} has no CRYST1 record, so its periodic cell is unknown")
+    try:
+        return cell_from_lengths_angles(*cell)
+    except ValueError as err:
+        raise SystemExit(f"--periodic-cell: the CRYST1 record of {path} is no cell: {err}") from None
+
+
 def run(args: Namespace) -> List[str]:
     """__main__.py:149-204; returns the output lines."""
     with open(args.anchor_pairing_file, "r") as f:
@@ -91,6 +105,8 @@ def run(args: Namespace) -> List[str]:
     boxes = {}
     if getattr(args, "periodic", False):
         boxes = {"box_a": orthorhombic_box(parsed1.cell, args.structure1), "box_b": orthorhombic_box(parsed2.cell, args.structure2)}
+    if getattr(args, "periodic_cell", False):
+        boxes = {"cell_a": cryst1_cell(parsed1.cell, args.structure1), "cell_b": cryst1_cell(parsed2.cell, args.structure2)}
     structure1, structure2 = parsed1[args.model_number], parsed2[args.model_number]
     assigner = PrimitiveAssigner(Path(args.primitive_typing_scheme))
     templates1 = assigner.assign_primitive_structure(structure1)

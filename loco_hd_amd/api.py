@@ -54,6 +54,46 @@ def periodic_boxes(box, n_structures: int, reach: float, what: str = "box") -> n
     return arr
 
 
+def periodic_cells(cell, n_structures: int, reach: float, what: str = "cell") -> np.ndarray:
+    """A triclinic cell (3 x 3, rows = the lattice vectors a, b, c), or one per structure, as a float64 array [n_cells][3][3] (n_cells
+    is 1 or `n_structures`).  ValueError for another shape and for what lchd_cell_validate rejects (a non-finite entry, a singular
+    cell, a `reach` that is not finite and > 0 or lies beyond the smallest perpendicular width).  No device is touched."""
+    try:
+        arr = _f64(cell)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a 3 x 3 matrix of lattice vectors (rows a, b, c)") from None
+    if arr.shape == (3, 3):
+        arr = arr.reshape(1, 3, 3)
+    elif arr.ndim != 3 or arr.shape[1:] != (3, 3):
+        raise ValueError(f"{what} must be a 3 x 3 matrix of lattice vectors (rows a, b, c), got an array of shape {arr.shape}")
+    if len(arr) not in (1, int(n_structures)):
+        raise ValueError(f"{what}: {len(arr)} cells given for {n_structures} structures (pass one cell, or one per structure)")
+    N.check(N.lib().lchd_cell_validate(N.dp(arr), len(arr), float(reach)))
+    return arr
+
+
+def cell_from_lengths_angles(a: float, b: float, c: float, alpha: float, beta: float, gamma: float) -> np.ndarray:
+    """The 3 x 3 cell (rows = lattice vectors) of the lengths a, b, c and the angles alpha = (b, c), beta = (a, c), gamma = (a, b) in
+    degrees, in the orientation of PDB / GROMACS / MDAnalysis: a along x, b in the xy plane.  An angle of exactly 90 gives exact
+    zeros, so (L, L, L, 90, 90, 90) is diag(L)."""
+    a, b, c = float(a), float(b), float(c)
+
+    def cos_sin(deg):
+        deg = float(deg)
+        if deg == 90.0:
+            return 0.0, 1.0
+        rad = np.deg2rad(deg)
+        return float(np.cos(rad)), float(np.sin(rad))
+    (ca, _), (cb, _), (cg, sg) = cos_sin(alpha), cos_sin(beta), cos_sin(gamma)
+    if not (a > 0.0 and b > 0.0 and c > 0.0 and sg > 0.0):
+        raise ValueError(f"no cell has the lengths ({a}, {b}, {c}) and the angle gamma = {gamma}")
+    cy = (ca - cb * cg) / sg
+    cz2 = 1.0 - cb * cb - cy * cy
+    if not cz2 > 0.0:
+        raise ValueError(f"no cell has the angles ({alpha}, {beta}, {gamma})")
+    return np.array([[a, 0.0, 0.0], [b * cg, b * sg, 0.0], [c * cb, c * cy, c * float(np.sqrt(cz2))]])
+
+
 class WeightFunction:
     """weight_function.rs:6-120.  ``parameters`` and ``function_name`` are read-only like the pyo3 getters."""
 
@@ -576,27 +616,36 @@ class LoCoHD:
         return start, np.ascontiguousarray(ex[:, 1], dtype=np.int32)
 
     def from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
-                        threshold_distance: float, *, box_a=None, box_b=None) -> List[float]:
+                        threshold_distance: float, *, box_a=None, box_b=None, cell_a=None, cell_b=None) -> List[float]:
         """src/locohd.rs:479-567.
 
         ``box_a`` / ``box_b`` (keyword-only, additive): an orthorhombic periodic box (Lx, Ly, Lz) of the structure.  Its environments
         then hold every periodic image of every atom closer than ``threshold_distance`` (<= the smallest edge) to the anchor: the
-        minimum-image convention up to half an edge, beyond it an atom may enter through two images."""
-        if box_a is not None or box_b is not None:
-            return self._from_primitives_periodic(prim_a, prim_b, anchor_pairs, threshold_distance, box_a, box_b)
+        minimum-image convention up to half an edge, beyond it an atom may enter through two images.
+
+        ``cell_a`` / ``cell_b`` (keyword-only, additive): a triclinic periodic cell instead, a 3 x 3 matrix whose rows are the lattice
+        vectors (``cell_from_lengths_angles`` makes one from a CRYST1 record); ``threshold_distance`` <= the smallest perpendicular
+        width.  A side takes a box or a cell, not both; the two sides are independent."""
+        if box_a is not None or box_b is not None or cell_a is not None or cell_b is not None:
+            return self._from_primitives_periodic(prim_a, prim_b, anchor_pairs, threshold_distance, box_a, box_b, cell_a, cell_b)
         pairs, idx = self._anchor_arrays(anchor_pairs)
         pa, pb, interner = self._packed_lists(prim_a, prim_b)
         return self.from_packed(pa, pb, pairs, threshold_distance, wf_index=idx, interner=interner).tolist()
 
     def _no_device_group_with_box(self) -> None:
         if self._devices is not None:
-            raise ValueError("a periodic box applies to one device (a device group has no image clouds): drop devices=[...]")
+            raise ValueError("a periodic box or cell applies to one device (a device group has no image clouds): drop devices=[...]")
 
-    def _from_primitives_periodic(self, prim_a, prim_b, anchor_pairs, threshold_distance, box_a, box_b) -> List[float]:
+    def _from_primitives_periodic(self, prim_a, prim_b, anchor_pairs, threshold_distance, box_a, box_b, cell_a=None, cell_b=None) -> List[float]:
+        for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+            if box is not None and cell is not None:
+                raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
         self._no_device_group_with_box()
         thr = float(threshold_distance)
         ba = None if box_a is None else periodic_boxes(box_a, 1, thr, "box_a")
         bb = None if box_b is None else periodic_boxes(box_b, 1, thr, "box_b")
+        ca = None if cell_a is None else periodic_cells(cell_a, 1, thr, "cell_a")
+        cb = None if cell_b is None else periodic_cells(cell_b, 1, thr, "cell_b")
         pairs, idx = self._anchor_arrays(anchor_pairs)
         pa, pb, interner = self._packed_lists(prim_a, prim_b)
         anchors = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
@@ -605,9 +654,33 @@ class LoCoHD:
         if len(anchors) == 0:
             return []
         xa, xb = _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3)
-        N.check(N.lib().lchd_from_primitives_periodic(self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa),
-                                                      N.dp(xb), N.ip(pb.cat), N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx),
-                                                      len(anchors), thr, N.dp(ba), N.dp(bb), N.dp(out)))
+        if ca is None and cb is None:
+            N.check(N.lib().lchd_from_primitives_periodic(self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa),
+                                                          N.dp(xb), N.ip(pb.cat), N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx),
+                                                          len(anchors), thr, N.dp(ba), N.dp(bb), N.dp(out)))
+        elif ba is None and bb is None:
+            N.check(N.lib().lchd_from_primitives_periodic_cell(self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa),
+                                                               N.dp(xb), N.ip(pb.cat), N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx),
+                                                               len(anchors), thr, N.dp(ca), N.dp(cb), N.dp(out)))
+        else:  # a box on one side, a cell on the other: no single C call takes both families, a session does
+            from .device import DeviceSession
+
+            # (as in the two C calls above: an index beyond the structure would name a ghost atom of the image cloud)
+            if anchors.min() < 0 or anchors[:, 0].max() >= len(xa) or anchors[:, 1].max() >= len(xb):
+                raise N.PanicException("index out of bounds: an anchor index is outside its structure (src/locohd.rs:521)")
+
+            sess = DeviceSession(self, device=None if self._device < 0 else self._device, interner=interner)
+            try:
+                torch = sess.torch
+                sides = []
+                for pk, x, box, cell in ((pa, xa, ba, ca), (pb, xb, bb, cb)):
+                    cl = sess.upload(x, pk.cat, pk.tag)
+                    sides.append(sess.periodic_images(cl, box, thr) if box is not None else sess.periodic_images(cl, reach=thr, cell=cell))
+                dev = torch.device("cuda", sess.device)
+                d_idx = None if idx is None else torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(dev)
+                out = sess.from_primitives(sides[0], sides[1], torch.from_numpy(anchors).to(dev), thr, wf_index=d_idx).cpu().numpy()
+            finally:
+                sess.close()
         return out.tolist()
 
     # The reference's callers score the same structures over and over (one native structure against every decoy,
@@ -688,7 +761,7 @@ class LoCoHD:
 
     def from_primitives_batch(self, structures: Sequence[Sequence[PrimitiveAtom]],
                               jobs: Sequence[Tuple[int, int, Sequence[Tuple[int, int]]]],
-                              threshold_distance: float, *, boxes=None) -> List[List[float]]:
+                              threshold_distance: float, *, boxes=None, cells=None) -> List[List[float]]:
         """Additive: many `from_primitives` calls in one device pass.  `structures` are lists of
         PrimitiveAtoms; a job `(a, b, anchor_pairs)` asks for `from_primitives(structures[a], structures[b],
         anchor_pairs, threshold_distance)`.  Returns one score list per job, each bit-identical to the single call.
@@ -701,10 +774,16 @@ class LoCoHD:
         `from_dmxs_ensemble` / `from_coords_ensemble`.
 
         ``boxes`` (keyword-only, additive): one orthorhombic periodic box (Lx, Ly, Lz) for all structures, or one per structure;
-        every environment then holds the periodic images within ``threshold_distance`` as in ``from_primitives(..., box_a=...)``."""
+        every environment then holds the periodic images within ``threshold_distance`` as in ``from_primitives(..., box_a=...)``.
+        ``cells`` (keyword-only, additive): the same with one triclinic cell (3 x 3) for all structures, or one per structure."""
+        if boxes is not None and cells is not None:
+            raise ValueError("boxes and cells were both given: a batch is periodic in boxes or in cells")
         if boxes is not None:  # (checked before anything touches a device)
             self._no_device_group_with_box()
             boxes = periodic_boxes(boxes, len(structures), float(threshold_distance), "boxes")
+        if cells is not None:
+            self._no_device_group_with_box()
+            cells = periodic_cells(cells, len(structures), float(threshold_distance), "cells")
         from .device import DeviceSession  # torch is only needed on this path
 
         if isinstance(self._w_func, dict):
@@ -731,6 +810,8 @@ class LoCoHD:
             batch, _ = sess.upload_batch([(pk.xyz, pk.cat, pk.tag) for pk in packed])
             if boxes is not None:
                 batch = sess.periodic_images(batch, boxes, float(threshold_distance))
+            if cells is not None:
+                batch = sess.periodic_images(batch, reach=float(threshold_distance), cell=cells)
             anchors = torch.from_numpy(np.concatenate(flat)).to(torch.device("cuda", sess.device))
             scores = sess.from_primitives(batch, batch, anchors, float(threshold_distance)).cpu().numpy()
         finally:

@@ -163,6 +163,10 @@ struct lchd_cloud {
     int64_t img_scan_cap = 0;
     double* d_boxes = nullptr; // [boxes_cap][3]
     int32_t boxes_cap = 0;
+    bool img_cell = false;     // built from triclinic cells (lchd_cloud_create_images_cell), not boxes: the family is fixed at creation
+    double* d_cells = nullptr; // [cells_cap][kImgCellRecord]
+    int32_t cells_cap = 0;
+    std::vector<double> h_cells;  // what the last build copied to d_cells (the copy is asynchronous)
     // wide: the configuration has more than 255 categories (two-byte ids where the structure carries them)
     CloudView view(bool wide) const {
         const bool two = wide && cat_hi;
@@ -888,6 +892,7 @@ extern "C" void lchd_cloud_destroy(lchd_ctx* c, lchd_cloud* cl) {
     (void)hipFree(cl->d_img_offset);
     (void)hipFree(cl->d_img_spans);
     (void)hipFree(cl->d_boxes);
+    (void)hipFree(cl->d_cells);
     if (cl->h_pinned32) (void)hipHostFree(cl->h_pinned32);
     if (cl->h_pinned) (void)hipHostFree(cl->h_pinned);
     if (cl->ev_ready) (void)hipEventDestroy(cl->ev_ready);
@@ -1727,6 +1732,45 @@ extern "C" int lchd_box_validate(const double* boxes, int32_t n_boxes, double re
     return LCHD_OK;
 }
 
+// A triclinic cell on the host: rec = cell (9), inverse (9), perpendicular widths (3).  The arithmetic is part of the contract of
+// lchd_cell_validate (include/loco_hd_hip.h): plain f64, left to right, nothing contracted (-ffp-contract=off, Makefile).
+static void cross3(const double* u, const double* v, double* o) {
+    o[0] = u[1] * v[2] - u[2] * v[1]; o[1] = u[2] * v[0] - u[0] * v[2]; o[2] = u[0] * v[1] - u[1] * v[0];
+}
+static double norm3(const double* u) { return std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]); }
+static int cell_record(const double* cell, int32_t index, double reach, double* rec /* [kImgCellRecord] or null */) {
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(cell[k])) return fail(LCHD_EVALUE, "cell %d: entry %d is %g; every entry of a cell must be finite", index, k, cell[k]);
+    const double *a = cell, *b = cell + 3, *c = cell + 6;
+    double x[3][3];  // x[k] = the cross product of the other two vectors, cyclic: a . x[0] = b . x[1] = c . x[2] = det
+    cross3(b, c, x[0]); cross3(c, a, x[1]); cross3(a, b, x[2]);
+    const double det = a[0] * x[0][0] + a[1] * x[0][1] + a[2] * x[0][2];
+    if (!(std::fabs(det) > 0.0) || !std::isfinite(det) || std::fabs(det) < 1e-12 * (norm3(a) * norm3(b) * norm3(c)))
+        return fail(LCHD_EVALUE, "cell %d is singular (determinant %g): its three vectors must span a volume", index, det);
+    for (int k = 0; k < 3; ++k) {
+        const double w = std::fabs(det) / norm3(x[k]);
+        if (!std::isfinite(w) || !(w > 0.0)) return fail(LCHD_EVALUE, "cell %d is singular (width %d is %g)", index, k, w);
+        if (reach > w)
+            return fail(LCHD_EVALUE, "cell %d: the reach %g exceeds the perpendicular width %g of axis %d; one layer of periodic images covers a threshold up to the smallest width",
+                        index, reach, w, k);
+        if (rec) rec[18 + k] = w;
+    }
+    if (rec)
+        for (int d = 0; d < 3; ++d)
+            for (int k = 0; k < 3; ++k) { rec[3 * d + k] = cell[3 * d + k]; rec[9 + 3 * d + k] = x[k][d] / det; }  // column k of the inverse = x[k] / det
+    return LCHD_OK;
+}
+
+// Every cell against the reach; with `recs` ([n_cells][kImgCellRecord]) their device records are filled on the way.
+static int cell_records(const double* cells, int32_t n_cells, double reach, double* recs) {
+    if (!cells || n_cells < 1) return fail(LCHD_EVALUE, "a periodic cell is three lattice vectors (a 3 x 3 matrix); none given");
+    if (!std::isfinite(reach) || !(reach > 0.0)) return fail(LCHD_EVALUE, "the reach of the periodic images must be finite and > 0, got %g", reach);
+    for (int32_t b = 0; b < n_cells; ++b)
+        if (int rc = cell_record(cells + 9 * (size_t)b, b, reach, recs ? recs + (size_t)kImgCellRecord * b : nullptr)) return rc;
+    return LCHD_OK;
+}
+extern "C" int lchd_cell_validate(const double* cells, int32_t n_cells, double reach) { return cell_records(cells, n_cells, reach, nullptr); }
+
 template <class T>
 static int grow_array(T*& p, size_t n) {
     (void)hipFree(p);
@@ -1754,10 +1798,18 @@ static int images_reserve(lchd_cloud* img, const lchd_cloud* src, int64_t cap) {
 }
 
 // count -> scan -> (read the total back, size the arrays) -> emit, on the context's stream behind the source's pending upload
+// (boxes: [n_boxes][3] edges, or for a cell cloud [n_boxes][9] cells)
 static int images_build(lchd_ctx* c, lchd_cloud* img, lchd_cloud* src, const double* boxes, int32_t n_boxes) {
+    const bool cell = img->img_cell;
     if (n_boxes != 1 && n_boxes != src->n_struct)
-        return fail(LCHD_EVALUE, "%d boxes given for %d structures: pass one box, or one per structure", n_boxes, src->n_struct);
-    if (int rc = lchd_box_validate(boxes, n_boxes, img->reach)) return rc;
+        return fail(LCHD_EVALUE, "%d %s given for %d structures: pass one %s, or one per structure", n_boxes, cell ? "cells" : "boxes",
+                    src->n_struct, cell ? "cell" : "box");
+    if (cell) {  // validated and turned into records in one go (the last build's copy out of h_cells was waited for in that build)
+        img->h_cells.resize((size_t)kImgCellRecord * std::max(n_boxes, 1));
+        if (int rc = cell_records(boxes, n_boxes, img->reach, img->h_cells.data())) return rc;
+    } else if (int rc = lchd_box_validate(boxes, n_boxes, img->reach)) {
+        return rc;
+    }
     if (src->images) return fail(LCHD_EVALUE, "the source of an image cloud must not be an image cloud");
     if (c->pend.active && (c->pend.req.a == img || c->pend.req.b == img))
         return fail(LCHD_EVALUE, "this image cloud is in use by an unfinished asynchronous call");
@@ -1776,20 +1828,30 @@ static int images_build(lchd_ctx* c, lchd_cloud* img, lchd_cloud* src, const dou
         if (int rc = grow_array(img->d_img_spans, (size_t)(cap / kImgScanSpan + 1))) return rc;
         img->img_scan_cap = cap;
     }
-    if (n_boxes > img->boxes_cap) {
+    if (!cell && n_boxes > img->boxes_cap) {
         img->boxes_cap = 0;
         if (int rc = grow_array(img->d_boxes, (size_t)3 * n_boxes)) return rc;
         img->boxes_cap = n_boxes;
     }
+    if (cell && n_boxes > img->cells_cap) {
+        img->cells_cap = 0;
+        if (int rc = grow_array(img->d_cells, (size_t)kImgCellRecord * n_boxes)) return rc;
+        img->cells_cap = n_boxes;
+    }
     if (!img->d_bbox) HIP_TRY(hipMalloc(&img->d_bbox, sizeof(unsigned long long) * 8));
     if (int rc = images_reserve(img, src, 2 * n + 64)) return rc;
     if (n == 0) { for (int k = 0; k < 3; ++k) img->bbmin[k] = img->bbmax[k] = 0.0; return LCHD_OK; }
-    HIP_TRY(hipMemcpyAsync(img->d_boxes, boxes, sizeof(double) * 3 * (size_t)n_boxes, hipMemcpyHostToDevice, s));
+    if (cell) {
+        HIP_TRY(hipMemcpyAsync(img->d_cells, img->h_cells.data(), sizeof(double) * img->h_cells.size(), hipMemcpyHostToDevice, s));
+    } else {
+        HIP_TRY(hipMemcpyAsync(img->d_boxes, boxes, sizeof(double) * 3 * (size_t)n_boxes, hipMemcpyHostToDevice, s));
+    }
     if (src->ev_ready && src->cap_frames) HIP_TRY(hipStreamWaitEvent(s, src->ev_ready, 0));  // (a frames buffer is filled on another stream)
     ImageArgs ia{};
     ia.src = CloudView{src->x, src->y, src->z, src->cat, src->cat_hi, src->tag, (int32_t)n, src->sid, src->n_struct, 0};
     ia.src_narrow = src->cat_narrow;
-    ia.boxes = img->d_boxes;
+    ia.boxes = cell ? nullptr : img->d_boxes;
+    ia.cells = cell ? img->d_cells : nullptr;
     ia.n_boxes = n_boxes;
     ia.reach = img->reach;
     ia.count = img->d_img_count;
@@ -1833,13 +1895,14 @@ static int images_build(lchd_ctx* c, lchd_cloud* img, lchd_cloud* src, const dou
     return LCHD_OK;
 }
 
-extern "C" int lchd_cloud_create_images(lchd_ctx* c, lchd_cloud* src, const double* boxes, int32_t n_boxes, double reach, lchd_cloud** out) {
+static int images_create(lchd_ctx* c, lchd_cloud* src, const double* boxes, int32_t n_boxes, double reach, bool cell, lchd_cloud** out) {
     CTX_LOCK(c);
     if (!c || !src || !out) return fail(LCHD_EVALUE, "null argument");
     *out = nullptr;
     CTX_GUARD(c);
     lchd_cloud* img = new lchd_cloud();
     img->images = true;
+    img->img_cell = cell;
     img->reach = reach;
     if (int rc = images_build(c, img, src, boxes, n_boxes)) {
         lchd_cloud_destroy(c, img);
@@ -1849,12 +1912,28 @@ extern "C" int lchd_cloud_create_images(lchd_ctx* c, lchd_cloud* src, const doub
     return LCHD_OK;
 }
 
-extern "C" int lchd_cloud_update_images(lchd_ctx* c, lchd_cloud* img, lchd_cloud* src, const double* boxes, int32_t n_boxes) {
+extern "C" int lchd_cloud_create_images(lchd_ctx* c, lchd_cloud* src, const double* boxes, int32_t n_boxes, double reach, lchd_cloud** out) {
+    return images_create(c, src, boxes, n_boxes, reach, false, out);
+}
+extern "C" int lchd_cloud_create_images_cell(lchd_ctx* c, lchd_cloud* src, const double* cells, int32_t n_cells, double reach, lchd_cloud** out) {
+    return images_create(c, src, cells, n_cells, reach, true, out);
+}
+
+static int images_update(lchd_ctx* c, lchd_cloud* img, lchd_cloud* src, const double* boxes, int32_t n_boxes, bool cell) {
     CTX_LOCK(c);
     if (!c || !img || !src) return fail(LCHD_EVALUE, "null argument");
     if (!img->images) return fail(LCHD_EVALUE, "not an image cloud (lchd_cloud_create_images)");
+    if (img->img_cell != cell)
+        return fail(LCHD_EVALUE, cell ? "this image cloud was built from boxes: update it with lchd_cloud_update_images"
+                                      : "this image cloud was built from cells: update it with lchd_cloud_update_images_cell");
     CTX_GUARD(c);
     return images_build(c, img, src, boxes, n_boxes);
+}
+extern "C" int lchd_cloud_update_images(lchd_ctx* c, lchd_cloud* img, lchd_cloud* src, const double* boxes, int32_t n_boxes) {
+    return images_update(c, img, src, boxes, n_boxes, false);
+}
+extern "C" int lchd_cloud_update_images_cell(lchd_ctx* c, lchd_cloud* img, lchd_cloud* src, const double* cells, int32_t n_cells) {
+    return images_update(c, img, src, cells, n_cells, true);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2082,16 +2161,19 @@ extern "C" int lchd_from_primitives(lchd_ctx* c, const lchd_config* cfg, const d
 
 // from_primitives in a periodic box: both structures go to the device as clouds of their own, a side with a box is replaced by its
 // image cloud (reach = the threshold) and the pass runs as for any two clouds.  lchd_from_primitives above is untouched.
-extern "C" int lchd_from_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a,
-                                             const int32_t* tag_a, int64_t n_a, const double* xyz_b, const int32_t* cat_b,
-                                             const int32_t* tag_b, int64_t n_b, const int64_t* anchors, const int32_t* wf_index,
-                                             int64_t n_pairs, double thr, const double* box_a, const double* box_b, double* out) {
+// (a side has at most one of box / cell; the public calls below pass one family each)
+static int from_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
+                                    int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
+                                    const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, const double* box_a,
+                                    const double* box_b, const double* cell_a, const double* cell_b, double* out) {
     CTX_LOCK(c);
     if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
     if (int rc = check_wf_index(cfg, wf_index, n_pairs)) return rc;
     if (n_a < 0 || n_b < 0 || n_a > ((int64_t)1 << 27) || n_b > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "structure size out of range");
     if (box_a) if (int rc = lchd_box_validate(box_a, 1, thr)) return rc;
     if (box_b) if (int rc = lchd_box_validate(box_b, 1, thr)) return rc;
+    if (cell_a) if (int rc = lchd_cell_validate(cell_a, 1, thr)) return rc;
+    if (cell_b) if (int rc = lchd_cell_validate(cell_b, 1, thr)) return rc;
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     if (n_pairs > 0 && (!anchors || !out)) return fail(LCHD_EVALUE, "null anchor / score pointer");
     for (int64_t p = 0; p < n_pairs; ++p)  // (an index beyond the structure would name a ghost atom of the image cloud)
@@ -2108,6 +2190,8 @@ extern "C" int lchd_from_primitives_periodic(lchd_ctx* c, const lchd_config* cfg
         if (int rc = lchd_cloud_create(c, xyz_b, cat_b, tag_b, n_b, &cb)) return rc;
         if (box_a) if (int rc = lchd_cloud_create_images(c, ca, box_a, 1, thr, &ia)) return rc;
         if (box_b) if (int rc = lchd_cloud_create_images(c, cb, box_b, 1, thr, &ib)) return rc;
+        if (cell_a) if (int rc = lchd_cloud_create_images_cell(c, ca, cell_a, 1, thr, &ia)) return rc;
+        if (cell_b) if (int rc = lchd_cloud_create_images_cell(c, cb, cell_b, 1, thr, &ib)) return rc;
         HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)n_pairs));
         HIP_TRY(hipMemcpy(d_blk, anchors, o_wf, hipMemcpyHostToDevice));
         if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice));
@@ -2126,6 +2210,21 @@ extern "C" int lchd_from_primitives_periodic(lchd_ctx* c, const lchd_config* cfg
     (void)hipFree(d_blk);
     if (rc) snprintf(g_err, sizeof g_err, "%s", msg.c_str());
     return rc;
+}
+extern "C" int lchd_from_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a,
+                                             const int32_t* tag_a, int64_t n_a, const double* xyz_b, const int32_t* cat_b,
+                                             const int32_t* tag_b, int64_t n_b, const int64_t* anchors, const int32_t* wf_index,
+                                             int64_t n_pairs, double thr, const double* box_a, const double* box_b, double* out) {
+    return from_primitives_periodic(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, box_a, box_b,
+                                    nullptr, nullptr, out);
+}
+// The same with triclinic cells (HOST [9], row 0 = a; NULL: an open side).
+extern "C" int lchd_from_primitives_periodic_cell(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a,
+                                                  const int32_t* tag_a, int64_t n_a, const double* xyz_b, const int32_t* cat_b,
+                                                  const int32_t* tag_b, int64_t n_b, const int64_t* anchors, const int32_t* wf_index,
+                                                  int64_t n_pairs, double thr, const double* cell_a, const double* cell_b, double* out) {
+    return from_primitives_periodic(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, nullptr, nullptr,
+                                    cell_a, cell_b, out);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -331,12 +331,15 @@ int centroid_tile_span();
 int bbox_parts_capacity();
 // Periodic images of a cloud as a cloud (lchd_images.hip): the wrapped originals in slots 0 .. n - 1, their ghosts behind them.
 constexpr int kImgScanSpan = 256;  // atoms per workgroup of the three steps = items one workgroup of the scan covers
+constexpr int kImgCellRecord = 21;  // doubles per triclinic cell on the device: cell, inverse, widths
 struct ImageArgs {
     CloudView src;              // the source (cat: the low bytes, cat_hi: the high bytes or null)
     const uint8_t* src_narrow;  // with cat_hi: the source's one-byte view
     const double* boxes;        // DEVICE [n_boxes][3] box edges; n_boxes == 1: one box for every structure, else box[sid]
     int32_t n_boxes;
-    double reach;               // an image within `reach` of the box is materialised (threshold <= reach <= smallest edge)
+    const double* cells;        // triclinic cells instead of boxes: DEVICE [n_boxes][kImgCellRecord] = cell (9, row-major, row 0 = a),
+                                // its inverse (9), the perpendicular widths (3); indexed like `boxes`.  Null: an orthorhombic box, `boxes` is set
+    double reach;               // an image within `reach` of the box is materialised (threshold <= reach <= smallest edge / width)
     double *x, *y, *z;          // the image cloud's arrays, `capacity` atoms each
     uint8_t *cat, *cat_hi, *cat_narrow;
     int32_t *tag, *sid;         // (sid null: one structure)
@@ -346,6 +349,7 @@ struct ImageArgs {
     unsigned long long* span_sum;  // [spans] ghosts in front of each span of kImgScanSpan atoms, or null: n <= kImgScanSpan
     unsigned long long* bbox;   // [8]: the seven bounding-box words of a frames buffer (ordered keys, non-finite flag), then the ghost total
 };
+// (count and emit pick the triclinic kernels when a.cells is set)
 void launch_img_count(hipStream_t s, const ImageArgs& a);  // wrapped originals, counts, bounding box (of originals and ghosts)
 void launch_img_scan(hipStream_t s, const ImageArgs& a);   // offsets, span sums, total
 void launch_img_emit(hipStream_t s, const ImageArgs& a);   // the ghosts

@@ -13,6 +13,20 @@
 //
 // reach <= min(L) (lchd_box_validate), so one layer of images is all there is, and threshold <= reach is checked by the pass.
 // Three steps, one launch each (the scan of more than kImgScanSpan atoms: two): k_img_count, the exclusive scan, k_img_emit.
+//
+// A triclinic cell (lattice vectors a, b, c = the rows of a 3 x 3 matrix, any non-singular one) takes the same three steps with
+// k_img_count_cell / k_img_emit_cell; the scan does not know the difference.  Per cell the host prepares the matrix, its inverse and
+// the perpendicular widths w_k = |det| / |cross of the other two vectors| (kImgCellRecord doubles, lchd_cell_validate's arithmetic).
+//
+//   wrap      f = x . inverse, p = x - (floor(f0) a + floor(f1) b + floor(f2) c); g = p . inverse are the fractional coordinates
+//   images    along axis k: p + a_k exists iff g_k w_k < reach, p - a_k iff (1 - g_k) w_k <= reach -- the slab within `reach` of the
+//             cell's faces, a superset of what any point of the cell can see; the search measures real distances and stays exact
+//   ghosts    p[d] + t[d] with t[d] = (i a[d] + j b[d]) + k c[d], i, j, k in {0, 1, -1} as doubles: plain f64 products and sums in
+//             that order, never contracted (-ffp-contract=off of the Makefile: the kernels below hold no fused multiply-add), so that a host
+//             can rebuild them bit for bit
+//   order     as above: ascending image code c0 + 3 c1 + 9 c2 (c: 0 original, 1 plus, 2 minus)
+//
+// reach <= min(w) (lchd_cell_validate): a shift of 2 along axis k is at least w_k away from every point of the cell.
 #include "lchd_kcommon.h"
 
 namespace lchd {
@@ -26,6 +40,17 @@ __device__ __forceinline__ int img_choices(double w, double L, double reach) { r
 __device__ __forceinline__ int img_ways(int ch) { return 1 + (ch & 1) + (ch >> 1); }
 __device__ __forceinline__ const double* img_box(const ImageArgs& a, int64_t i) {
     return a.boxes + 3 * (size_t)((a.n_boxes > 1 && a.src.sid) ? a.src.sid[i] : 0);
+}
+
+// The lanes' bounding boxes and non-finite flags into the seven ordered-key words: one atomic per word and wavefront.
+__device__ __forceinline__ void img_reduce_bbox(const ImageArgs& a, double (&mn)[3], double (&mx)[3], bool bad) {
+    for (int m = 32; m > 0; m >>= 1)
+        for (int k = 0; k < 3; ++k) { mn[k] = fmin(mn[k], shfl_xor_f64(mn[k], m)); mx[k] = fmax(mx[k], shfl_xor_f64(mx[k], m)); }
+    const unsigned long long anybad = __ballot(bad);
+    if ((threadIdx.x & 63) == 0 && (int64_t)blockIdx.x * kImgScanSpan + (threadIdx.x & ~63) < a.src.n) {
+        for (int k = 0; k < 3; ++k) { atomicMin(&a.bbox[k], ordered_key(mn[k])); atomicMax(&a.bbox[3 + k], ordered_key(mx[k])); }
+        if (anybad) atomicOr(&a.bbox[6], 1ull);
+    }
 }
 
 // One lane per atom: the wrapped original into slot i (coordinates and labels), its ghost count into count[i], the bounding box of the
@@ -54,13 +79,7 @@ __global__ __launch_bounds__(kImgScanSpan) void k_img_count(ImageArgs a) {
         if (a.sid) a.sid[i] = a.src.sid[i];
         a.count[i] = (uint32_t)(ways - 1);
     }
-    for (int m = 32; m > 0; m >>= 1)
-        for (int k = 0; k < 3; ++k) { mn[k] = fmin(mn[k], shfl_xor_f64(mn[k], m)); mx[k] = fmax(mx[k], shfl_xor_f64(mx[k], m)); }
-    const unsigned long long anybad = __ballot(bad);
-    if ((threadIdx.x & 63) == 0 && (int64_t)blockIdx.x * kImgScanSpan + (threadIdx.x & ~63) < a.src.n) {
-        for (int k = 0; k < 3; ++k) { atomicMin(&a.bbox[k], ordered_key(mn[k])); atomicMax(&a.bbox[3 + k], ordered_key(mx[k])); }
-        if (anybad) atomicOr(&a.bbox[6], 1ull);
-    }
+    img_reduce_bbox(a, mn, mx, bad);
 }
 
 // Exclusive scan of one block span: DPP scan per wavefront, the wavefronts' totals through LDS.  Returns the lane's exclusive prefix
@@ -135,11 +154,103 @@ __global__ __launch_bounds__(kImgScanSpan) void k_img_emit(ImageArgs a) {
             }
 }
 
+// ---- triclinic cells ----------------------------------------------------------------------------------------------------------
+// The record of the atom's cell: R[0..8] the cell (row 0 = a), R[9..17] its inverse, R[18..20] the perpendicular widths.
+__device__ __forceinline__ const double* img_cell(const ImageArgs& a, int64_t i) {
+    return a.cells + kImgCellRecord * (size_t)((a.n_boxes > 1 && a.src.sid) ? a.src.sid[i] : 0);
+}
+// row vector times the inverse: the fractional coordinates of a point
+__device__ __forceinline__ void img_frac(const double* R, const double (&v)[3], double (&f)[3]) {
+    for (int k = 0; k < 3; ++k) f[k] = (v[0] * R[9 + k] + v[1] * R[12 + k]) + v[2] * R[15 + k];
+}
+// per-axis choices of a fractional coordinate: bit 0 the image + a_k exists, bit 1 the image - a_k
+__device__ __forceinline__ int img_choices_cell(double g, double w, double reach) {
+    return (g * w < reach ? 1 : 0) | ((1.0 - g) * w <= reach ? 2 : 0);
+}
+// component d of the shift i a + j b + k c, the coefficients as doubles: THE expression of the contract
+__device__ __forceinline__ double img_shift(const double* R, int d, double i, double j, double k) {
+    return (i * R[d] + j * R[3 + d]) + k * R[6 + d];
+}
+__device__ __forceinline__ double img_coef(int choice) { return choice == 0 ? 0.0 : (choice == 1 ? 1.0 : -1.0); }
+
+// k_img_count for a triclinic cell.  The bounding box is taken over the very sums k_img_emit_cell will write (a ghost's coordinate
+// mixes all three lattice vectors, so there is no per-axis shortcut that rounds the same way).
+__global__ __launch_bounds__(kImgScanSpan) void k_img_count_cell(ImageArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * kImgScanSpan + threadIdx.x;
+    double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool bad = false;
+    if (i < a.src.n) {
+        const double* R = img_cell(a, i);
+        const double v[3] = {a.src.x[i], a.src.y[i], a.src.z[i]};
+        double f[3], p[3], g[3];
+        img_frac(R, v, f);
+        for (int k = 0; k < 3; ++k) f[k] = floor(f[k]);
+        for (int d = 0; d < 3; ++d) {
+            p[d] = v[d] - img_shift(R, d, f[0], f[1], f[2]);
+            bad = bad || !(fabs(p[d]) < INFINITY);
+        }
+        img_frac(R, p, g);
+        int ch[3];
+        for (int k = 0; k < 3; ++k) ch[k] = img_choices_cell(g[k], R[18 + k], a.reach) << 1 | 1;  // bit c: choice c of this axis exists
+        int ways = 0;
+        for (int c2 = 0; c2 < 3; ++c2)
+            for (int c1 = 0; c1 < 3; ++c1)
+                for (int c0 = 0; c0 < 3; ++c0) {
+                    if (!((ch[0] >> c0) & (ch[1] >> c1) & (ch[2] >> c2) & 1)) continue;
+                    ++ways;
+                    for (int d = 0; d < 3; ++d) {
+                        const double q = (c0 | c1 | c2) ? p[d] + img_shift(R, d, img_coef(c0), img_coef(c1), img_coef(c2)) : p[d];
+                        mn[d] = fmin(mn[d], q); mx[d] = fmax(mx[d], q);
+                    }
+                }
+        if (bad) ways = 1;  // (a NaN compares false everywhere; keep the count well defined, the build is refused anyway)
+        a.x[i] = p[0]; a.y[i] = p[1]; a.z[i] = p[2];
+        a.cat[i] = a.src.cat[i];
+        if (a.cat_hi) { a.cat_hi[i] = a.src.cat_hi[i]; a.cat_narrow[i] = a.src_narrow[i]; }
+        a.tag[i] = a.src.tag[i];
+        if (a.sid) a.sid[i] = a.src.sid[i];
+        a.count[i] = (uint32_t)(ways - 1);
+    }
+    img_reduce_bbox(a, mn, mx, bad);
+}
+
+// k_img_emit for a triclinic cell: the fractional coordinates are recomputed from the wrapped coordinates k_img_count_cell left in
+// slot i by the same expression, so the choices are the ones that were counted.
+__global__ __launch_bounds__(kImgScanSpan) void k_img_emit_cell(ImageArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * kImgScanSpan + threadIdx.x;
+    if (i >= a.src.n) return;
+    const double* R = img_cell(a, i);
+    const double p[3] = {a.x[i], a.y[i], a.z[i]};
+    double g[3];
+    img_frac(R, p, g);
+    int ch[3];
+    for (int k = 0; k < 3; ++k) ch[k] = img_choices_cell(g[k], R[18 + k], a.reach) << 1 | 1;
+    int64_t o = (int64_t)a.src.n + (int64_t)((a.span_sum ? a.span_sum[i / kImgScanSpan] : 0ull) + a.offset[i]);
+    const int64_t end = o + a.count[i];  // (what was counted, whatever a non-finite coordinate does to the comparisons)
+    const uint8_t cat = a.cat[i];
+    const int32_t tag = a.tag[i];
+    for (int c2 = 0; c2 < 3; ++c2)
+        for (int c1 = 0; c1 < 3; ++c1)
+            for (int c0 = 0; c0 < 3; ++c0) {
+                if (!((ch[0] >> c0) & (ch[1] >> c1) & (ch[2] >> c2) & 1) || (c0 | c1 | c2) == 0) continue;
+                if (o >= end || o >= a.capacity) return;  // (never: the host sized the arrays from the scan's total)
+                a.x[o] = p[0] + img_shift(R, 0, img_coef(c0), img_coef(c1), img_coef(c2));
+                a.y[o] = p[1] + img_shift(R, 1, img_coef(c0), img_coef(c1), img_coef(c2));
+                a.z[o] = p[2] + img_shift(R, 2, img_coef(c0), img_coef(c1), img_coef(c2));
+                a.cat[o] = cat;
+                if (a.cat_hi) { a.cat_hi[o] = a.cat_hi[i]; a.cat_narrow[o] = a.cat_narrow[i]; }
+                a.tag[o] = tag;
+                if (a.sid) a.sid[o] = a.sid[i];
+                ++o;
+            }
+}
+
 static unsigned img_blocks(int64_t n) { return (unsigned)((n + kImgScanSpan - 1) / kImgScanSpan); }
 void launch_img_count(hipStream_t s, const ImageArgs& a) {
     static const unsigned long long init[7] = {~0ull, ~0ull, ~0ull, 0ull, 0ull, 0ull, 0ull};
     (void)hipMemcpyAsync(a.bbox, init, sizeof init, hipMemcpyHostToDevice, s);
-    k_img_count<<<img_blocks(a.src.n), kImgScanSpan, 0, s>>>(a);
+    if (a.cells) k_img_count_cell<<<img_blocks(a.src.n), kImgScanSpan, 0, s>>>(a);
+    else k_img_count<<<img_blocks(a.src.n), kImgScanSpan, 0, s>>>(a);
 }
 void launch_img_scan(hipStream_t s, const ImageArgs& a) {
     const unsigned spans = img_blocks(a.src.n);
@@ -150,6 +261,9 @@ void launch_img_scan(hipStream_t s, const ImageArgs& a) {
         k_img_scan_sums<<<1, kImgScanSpan, 0, s>>>(a.span_sum, spans, a.bbox + 7);
     }
 }
-void launch_img_emit(hipStream_t s, const ImageArgs& a) { k_img_emit<<<img_blocks(a.src.n), kImgScanSpan, 0, s>>>(a); }
+void launch_img_emit(hipStream_t s, const ImageArgs& a) {
+    if (a.cells) k_img_emit_cell<<<img_blocks(a.src.n), kImgScanSpan, 0, s>>>(a);
+    else k_img_emit<<<img_blocks(a.src.n), kImgScanSpan, 0, s>>>(a);
+}
 
 }  // namespace lchd

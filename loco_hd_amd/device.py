@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .api import LoCoHD, periodic_boxes
+from .api import LoCoHD, periodic_boxes, periodic_cells
 
 
 def last_sweep_of(ctx):
@@ -157,19 +157,40 @@ class DeviceSession:
         xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
         N.check(N.lib().lchd_cloud_set_coords(self._ctx, cloud, N.dp(xyz)))
 
-    def periodic_images(self, cloud, box, reach: float):
+    def periodic_images(self, cloud, box=None, reach: float = None, *, cell=None):
         """The periodic images of an uploaded structure / batch / frames buffer as a cloud of its own (lchd_cloud_create_images):
         the wrapped atoms at their indices, then every image within `reach` of the orthorhombic `box` (Lx, Ly, Lz; one, or one
         per structure).  Use it in place of `cloud` in from_primitives with threshold_distance <= reach <= the smallest edge;
-        the session owns it like any other cloud."""
-        arr = periodic_boxes(box, self._n_structures(cloud), reach)
+        the session owns it like any other cloud.
+
+        `cell` (keyword-only) in place of `box`: a triclinic cell, 3 x 3 with the lattice vectors as rows (one, or one per structure;
+        lchd_cloud_create_images_cell); reach <= its smallest perpendicular width."""
+        if (box is None) == (cell is None):
+            raise ValueError("periodic_images takes a box or a cell" + (", not both" if box is not None else "; neither was given"))
+        if reach is None:
+            raise ValueError("periodic_images needs the reach of the images (the largest threshold_distance to be used)")
         h = C.c_void_p()
-        N.check(N.lib().lchd_cloud_create_images(self._ctx, cloud, N.dp(arr), len(arr), float(reach), C.byref(h)))
+        if cell is not None:
+            arr = periodic_cells(cell, self._n_structures(cloud), reach)
+            N.check(N.lib().lchd_cloud_create_images_cell(self._ctx, cloud, N.dp(arr), len(arr), float(reach), C.byref(h)))
+        else:
+            arr = periodic_boxes(box, self._n_structures(cloud), reach)
+            N.check(N.lib().lchd_cloud_create_images(self._ctx, cloud, N.dp(arr), len(arr), float(reach), C.byref(h)))
         self._clouds.append(h)
         return h
 
-    def update_images(self, images, cloud, box):
-        """Rebuild an image cloud in place from the current coordinates of `cloud` (lchd_cloud_update_images); its reach stays."""
+    def update_images(self, images, cloud, box=None, *, cell=None):
+        """Rebuild an image cloud in place from the current coordinates of `cloud` (lchd_cloud_update_images); its reach stays.
+        A cloud made with `cell=` is updated with `cell=` (lchd_cloud_update_images_cell), one made with a box with `box`."""
+        if (box is None) == (cell is None):
+            raise ValueError("update_images takes a box or a cell" + (", not both" if box is not None else "; neither was given"))
+        if cell is not None:
+            arr = np.ascontiguousarray(cell, dtype=np.float64)
+            arr = arr.reshape(1, 3, 3) if arr.shape == (3, 3) else arr
+            if arr.ndim != 3 or arr.shape[1:] != (3, 3):
+                raise ValueError(f"cell must be a 3 x 3 matrix of lattice vectors (rows a, b, c), got an array of shape {arr.shape}")
+            N.check(N.lib().lchd_cloud_update_images_cell(self._ctx, images, cloud, N.dp(arr), len(arr)))
+            return
         arr = np.ascontiguousarray(box, dtype=np.float64)
         arr = arr.reshape(1, 3) if arr.shape == (3,) else arr
         if arr.ndim != 2 or arr.shape[1] != 3:
@@ -302,7 +323,7 @@ class DeviceSession:
         return out
 
     def score_trajectory(self, ref_cloud, frames_xyz: np.ndarray, local_pairs, threshold_distance: float, chunk: int = 1024,
-                         topology=None, ref_box=None, boxes=None):
+                         topology=None, ref_box=None, boxes=None, ref_cell=None, cells=None):
         """MD-trajectory mode (python_codes/trajectory_analyzer.py:97-119): score every frame of `frames_xyz`
         [n_frames][n_atoms][3] against the reference structure for the anchor pairs `local_pairs` [(atom in reference,
         atom in frame)].  Frames are streamed in chunks: while chunk k is scored, chunk k+1 is copied on a second
@@ -314,7 +335,14 @@ class DeviceSession:
 
         `ref_box` / `boxes` (additive): orthorhombic periodic boxes (Lx, Ly, Lz) of the reference structure and of the frames
         ([n_frames][3], or [3] for a constant box); environments then hold the periodic images within `threshold_distance`.
-        The reference's image cloud is built once, a chunk's is rebuilt on the scoring stream behind the chunk's upload."""
+        The reference's image cloud is built once, a chunk's is rebuilt on the scoring stream behind the chunk's upload.
+
+        `ref_cell` / `cells` (additive): triclinic cells (3 x 3, rows = lattice vectors) in place of `ref_box` / `boxes`:
+        [n_frames][3][3] (a cell per frame, NPT) or [3][3] for a constant cell."""
+        if ref_box is not None and ref_cell is not None:
+            raise ValueError("ref_box and ref_cell were both given: the reference has one periodic box or one periodic cell")
+        if boxes is not None and cells is not None:
+            raise ValueError("boxes and cells were both given: the frames are periodic in boxes or in cells")
         torch = self.torch
         if topology is not None:
             frames_xyz = np.ascontiguousarray(frames_xyz, dtype=np.float32)
@@ -329,7 +357,12 @@ class DeviceSession:
         thr = float(threshold_distance)
         if boxes is not None:
             boxes = periodic_boxes(boxes, n_frames, thr, "boxes")
-        ref_side = ref_cloud if ref_box is None else self.periodic_images(ref_cloud, ref_box, thr)
+        if cells is not None:
+            cells = periodic_cells(cells, n_frames, thr, "cells")
+        if ref_cell is not None:
+            ref_side = self.periodic_images(ref_cloud, reach=thr, cell=ref_cell)
+        else:
+            ref_side = ref_cloud if ref_box is None else self.periodic_images(ref_cloud, ref_box, thr)
         lp = np.ascontiguousarray(local_pairs, dtype=np.int64).reshape(-1, 2)
         chunk = max(1, min(int(chunk), n_frames))
         dev = torch.device("cuda", self.device)
@@ -356,6 +389,13 @@ class DeviceSession:
                         images[k % 2] = self.periodic_images(side_b, bx, thr)
                     else:
                         self.update_images(images[k % 2], side_b, bx)
+                    side_b = images[k % 2]
+                if cells is not None:
+                    cx = cells if len(cells) == 1 else cells[f0:f0 + nf]
+                    if images[k % 2] is None:
+                        images[k % 2] = self.periodic_images(side_b, reach=thr, cell=cx)
+                    else:
+                        self.update_images(images[k % 2], side_b, cell=cx)
                     side_b = images[k % 2]
                 self.from_primitives_async(ref_side, side_b, anchors[: nf * len(lp)], threshold_distance,
                                            out[f0 * len(lp):(f0 + nf) * len(lp)])

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Periodic-boundary measurements quoted in DESIGN.md section 5 (run on the MI355X box from the repository root):
     python3 profiles/periodic_workloads.py > periodic_workloads.json
-C2a cloud in its box (10^4 atoms, L = 58.5, threshold 10): image-build time, ghost count, pass time with and without the box.
+C2a cloud in its box (10^4 atoms, L = 58.5, threshold 10): image-build time, ghost count, pass time with and without the box; the
+image build again through the triclinic kernels, with diag(L) and with the rhombic dodecahedron of the box's volume.
 C4-shaped trajectory (2001 primitive atoms per frame, chunks of 500 frames): image rebuild per chunk against the chunk's pass.
 """
 import json
@@ -51,6 +52,27 @@ res["c2a_in_its_box"] = {"atoms": w["n"], "atoms_and_ghosts": n_img, "ghosts_per
                          "geometric_expectation": ((L + 2 * w["thr"]) / L) ** 3 - 1.0, "image_build_ms_host_call": build_ms,
                          "pass_ms_open": open_ms, "pass_ms_in_the_box": box_ms, "kernel_ms_open": open_phases,
                          "kernel_ms_in_the_box": sess.last_ms(), "env_points_open": open_points, "env_points_in_the_box": sess.last_env_points()}
+
+
+# the same cloud through the cell path (k_img_count_cell / k_img_emit_cell)
+def cell_widths(cell):
+    det = abs(np.linalg.det(cell))
+    return [det / np.linalg.norm(np.cross(cell[(k + 1) % 3], cell[(k + 2) % 3])) for k in range(3)]
+
+
+d = L * 2.0 ** (1.0 / 6.0)  # image distance of the rhombic dodecahedron of volume L^3 (d^3 sqrt(2) / 2)
+for name, cell in (("diag", np.diag([L, L, L])), ("dodecahedron", np.array([[d, 0.0, 0.0], [0.0, d, 0.0], [d / 2, d / 2, d * np.sqrt(2.0) / 2]]))):
+    ic = sess.periodic_images(a, reach=w["thr"], cell=cell)
+    ms = timed(lambda: sess.update_images(ic, a, cell=cell), reps=20, warm=3)
+    n_ic = int(N.lib().lchd_cloud_size(ic))
+    res["c2a_in_its_box"]["cell_" + name] = {"widths": cell_widths(cell), "volume": abs(float(np.linalg.det(cell))), "atoms_and_ghosts": n_ic,
+                                             "ghosts_per_atom": n_ic / w["n"] - 1.0, "image_build_ms_host_call": ms,
+                                             "geometric_expectation": float(np.prod([1.0 + 2.0 * w["thr"] / wk for wk in cell_widths(cell)])) - 1.0}
+# atoms uniform in the dodecahedron itself (the C2a cloud is uniform in the cube, which is no fundamental domain of that lattice)
+uni = sess.upload(np.random.default_rng(5).uniform(0.0, 1.0, (w["n"], 3)) @ cell, w["cat_a"])
+n_uni = int(N.lib().lchd_cloud_size(sess.periodic_images(uni, reach=w["thr"], cell=cell)))
+res["c2a_in_its_box"]["cell_dodecahedron"]["ghosts_per_atom_of_a_cloud_uniform_in_the_cell"] = n_uni / w["n"] - 1.0
+res["c2a_in_its_box"]["image_build_ms_host_call_box_again"] = timed(lambda: sess.update_images(ia, a, (L, L, L)), reps=20, warm=3)
 sess.close()
 
 # ---- a C4-shaped trajectory: one reference against frames of 2001 primitive atoms, every third atom an anchor ----------------
