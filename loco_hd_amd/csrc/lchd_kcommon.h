@@ -104,6 +104,24 @@ __device__ __forceinline__ int merge_path(const uint64_t* A, int nA, const uint6
     }
     return lo;
 }
+// The same partition for the team tiles: a wave-uniform number of trips and no branch.  wmax (wave-uniform) bounds the width hi - lo
+// of every lane's window; the steps are the powers of two below 2^bits(wmax), largest first: after them pos = lo + the number of
+// m in [lo, hi) with A[m] <= B[d - 1 - m] -- the predicate is true up to the partition and false behind it, so that is merge_path's
+// result for every input, ties included.  A probe behind the window (m >= hi) counts as false; its reads are moved into the lists
+// (mc <= max(hi - 1, 0), and B's index d - 1 - mc lies in [0, nB]: entry nB is one of the buffers' spare entries).
+// profiles/merge_path_model.py is this loop in numpy, with the trip counts of both forms.
+__device__ __forceinline__ int merge_path_fixed(const uint64_t* A, int nA, const uint64_t* B, int nB, int d, int wmax) {
+    const int lo = max(0, d - nB), hi = min(d, nA);
+    const int mcl = max(hi - 1, 0), dm1 = max(d - 1, 0);
+    int pos = lo;
+    for (int step = wmax > 0 ? 1 << (31 - __builtin_clz((unsigned)wmax)) : 0; step > 0; step >>= 1) {
+        const int m = pos + (step - 1);
+        const int mc = min(m, mcl);
+        const bool ok = (m < hi) & (A[mc] <= B[dm1 - mc]);
+        pos = ok ? m + 1 : pos;
+    }
+    return pos;
+}
 // spread the four 4-bit fields of the low 16 bits of x into four 16-bit fields
 __device__ __forceinline__ uint64_t spread4(uint64_t x) {
     // two 32-bit halves, three operations each (and, and / bfe, shift-or); the 64-bit shift-or-mask form is compiled to

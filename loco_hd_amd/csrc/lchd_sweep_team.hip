@@ -182,31 +182,38 @@ __global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8
                 for (int k = 1; k < TEAMS; ++k) epl2_w = max(epl2_w, __builtin_amdgcn_readlane(epl2, k * TL));
                 key2_t rk[EPL2];
                 uint32_t rc[EPL2];
-                const uint64_t* kBs = kB - mAe;
-                const uint8_t* tBs = tB - mAe;
+                // Per-lane state, once per tile: the lane's entry of round 0 in either list, as pointers -- round u lies 2 TL u entries
+                // further, a CONSTANT that the loads and the LDS writes carry as their immediate offsets.  A lane crosses from list A to
+                // list B once (at the first round with 2 TL u >= toB: mAe and the lane's entry are both even, so no pair straddles): the
+                // round picks one of the two pointers.  Rounds with 2 TL u >= left lie behind the buffer's used part: nothing is loaded or
+                // written (an unusable pair has Tb = 0: no round at all, its pointers are never followed).
+                const int e0 = 2 * tl, toB = mAe - e0, left = Tb - e0;
+                const uint64_t* pkA = kA + 1 + e0;
+                const uint64_t* pkB = kB + 1 + e0 - mAe;
+                const uint8_t* pcA = tA + 1 + e0;
+                const uint8_t* pcB = tB + 1 + e0 - mAe;
 #pragma unroll
                 for (int u = 0; u < EPL2; ++u) { rk[u] = key2_t{0ull, 0ull}; rc[u] = 0u; }
-                if (valid) {
 #pragma unroll
-                    for (int u = 0; u < EPL2; ++u) {
-                        if (u < epl2_w) {  // (wave-uniform: rounds no team of this wavefront needs are skipped)
-                            const int t0 = 2 * (tl + TL * u);
-                            const int tt = t0 < Tb ? t0 : 0;  // (beyond the used part: re-read the row's first pair, nothing is written)
-                            const bool isA = tt < mAe;
-                            const uint64_t* src = (isA ? kA : kBs) + 1 + tt;
-                            const uint8_t* csrc = (isA ? tA : tBs) + 1 + tt;
+                for (int u = 0; u < EPL2; ++u) {
+                    if (u < epl2_w) {  // (wave-uniform: rounds no team of this wavefront needs are skipped)
+                        if (2 * TL * u < left) {
+                            const bool inB = 2 * TL * u >= toB;
+                            const uint64_t* src = (inB ? pkB : pkA) + 2 * TL * u;
+                            const uint8_t* csrc = (inB ? pcB : pcA) + 2 * TL * u;
                             rk[u] = *reinterpret_cast<const key2_t*>(src);
                             rc[u] = (uint32_t)csrc[0] | ((uint32_t)csrc[1] << 8);
                         }
                     }
                 }
+                uint64_t* dk = sA + e0;
+                uint8_t* dc = cA + e0;
 #pragma unroll
                 for (int u = 0; u < EPL2; ++u) {
                     if (u < epl2_w) {
-                        const int t0 = 2 * (tl + TL * u);
-                        if (t0 < Tb) {
-                            *reinterpret_cast<ulonglong2*>(sA + t0) = ulonglong2{rk[u].x, rk[u].y};
-                            *reinterpret_cast<uint16_t*>(cA + t0) = (uint16_t)rc[u];
+                        if (2 * TL * u < left) {
+                            *reinterpret_cast<ulonglong2*>(dk + 2 * TL * u) = ulonglong2{rk[u].x, rk[u].y};
+                            *reinterpret_cast<uint16_t*>(dc + 2 * TL * u) = (uint16_t)rc[u];
                         }
                     }
                 }

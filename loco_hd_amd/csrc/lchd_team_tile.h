@@ -118,7 +118,12 @@ struct TeamTile {
         const double H0 = (c0a == c0b) ? 0.0 : 1.0;            // two point masses
         // lane tl of a team owns merged events [d0, d1) of its pair
         const int d0 = min(tl * epl, T), d1 = min(d0 + epl, T);
-        const int i1 = merge_path(sA, mA, sB, mB, d1);
+        // (the search runs as many trips as the widest window of the wavefront's lanes needs: a window is at most min(mA, mB) wide)
+        const int mw = min(mA, mB);
+        int mw_w = __builtin_amdgcn_readlane(mw, 0);
+#pragma unroll
+        for (int k = 1; k < TEAMS; ++k) mw_w = max(mw_w, __builtin_amdgcn_readlane(mw, k * TL));
+        const int i1 = merge_path_fixed(sA, mA, sB, mB, d1, mw_w);
         int i0 = __builtin_amdgcn_update_dpp(i1, i1, 0x138, 0xf, 0xf, false);  // wave_shr:1
         if (tl == 0) i0 = 0;
         const int j0 = d0 - i0, j1 = d1 - i1;
@@ -148,13 +153,10 @@ struct TeamTile {
 #pragma unroll
             for (int m = 0; m < kPreStep - 1; ++m) {
                 // 1 where point m lies before the chunk's start (m < q, q <= 3), else 0 -- without a compare
-                // (the last arm is never reached, m < 3: without it the same instructions come out with other registers, and this
-                // file's clean-up was held to byte-identical code objects -- drop it with the next change that moves the code anyway)
                 uint32_t va_, vb_;
                 if (m == 0) { va_ = min(qa_, 1u); vb_ = min(qb_, 1u); }
                 else if (m == 1) { va_ = qa_ >> 1; vb_ = qb_ >> 1; }
-                else if (m == 2) { va_ = qa_ & (qa_ >> 1); vb_ = qb_ & (qb_ >> 1); }
-                else { va_ = (unsigned)m < qa_ ? 1u : 0u; vb_ = (unsigned)m < qb_ ? 1u : 0u; }
+                else { va_ = qa_ & (qa_ >> 1); vb_ = qb_ & (qb_ >> 1); }
                 const unsigned ca_ = pa_[m], cb_ = pb_[m];
                 ta_ += va_ << ((2u * ca_) & 31u);  // (a point's category is below CMAX <= 16; a byte that is no point may hold anything)
                 tb_ += vb_ << ((2u * cb_) & 31u);
