@@ -266,7 +266,8 @@ int lchd_cloud_get_coords(lchd_ctx *ctx, lchd_cloud *cloud, double *xyz_out, int
  *           combination of per-axis choices other than "all original" (up to 26 per atom), written in ascending image code
  *           cx + 3 cy + 9 cz (c = 0 original, 1 +L, 2 -L) behind the ghosts of the atoms in front: the cloud is a function of its input
  *   reach   threshold_distance <= reach <= min(Lx, Ly, Lz): one layer of images suffices and an anchor never meets its own image
- * Triclinic cells have calls of their own further down; the dense from_coords / from_dmxs paths and device groups are out of scope. */
+ * Triclinic cells have calls of their own further down, the dense from_coords paths theirs behind those ("minimum-image dense rows");
+ * device groups are out of scope. */
 /* Host only, no device: LCHD_EVALUE for a non-finite or non-positive edge or reach, or reach > the smallest edge of a box. */
 int lchd_box_validate(const double *boxes /* [n_boxes][3] */, int32_t n_boxes, double reach);
 /* The image cloud of `src` -- a single structure, a batch (ragged included) or a frames buffer (the frames loaded last).  boxes: HOST
@@ -322,6 +323,47 @@ int lchd_from_primitives_periodic_cell(lchd_ctx *ctx, const lchd_config *cfg, co
                                        const int32_t *tag_a, int64_t n_a, const double *xyz_b, const int32_t *cat_b,
                                        const int32_t *tag_b, int64_t n_b, const int64_t *anchors, const int32_t *wf_index,
                                        int64_t n_pairs, double threshold_distance, const double *cell_a, const double *cell_b, double *out);
+
+/* ---- minimum-image dense rows (additive) -------------------------------------------------------------
+ * The dense calls (lchd_from_coords*, lchd_ensemble_from_coords*) in a periodic cell.  A dense row has no threshold, so it follows the
+ * MINIMUM-IMAGE convention: every atom of the structure appears exactly once, at the distance of its nearest periodic image to the
+ * row's atom; row length and categories do not change, entry r of row r is exactly 0.  This differs from the thresholded calls above,
+ * where an atom beyond half an edge may enter an environment through two images.  A cell is the 3 x 3 matrix above (rows a, b, c), any
+ * non-singular one (the singularity rule of lchd_cell_validate; no width condition, there is no reach); an orthorhombic box
+ * (Lx, Ly, Lz) is the diagonal cell and takes the per-axis form.  Coordinates need not be wrapped; a non-finite one is LCHD_EVALUE.
+ * The rows are materialised on the device (8 n^2 bytes per periodic structure of a single pair, in the context's workspace) in front
+ * of the unchanged given-row sorts and sweeps, so a score is the one lchd_from_dmxs computes from these rows:
+ *   d        = (row atom) - (column atom), per axis
+ *   diagonal d_k = d_k - L_k * rint(d_k / L_k) (IEEE division, round to nearest even), distance = sqrt((dx dx + dy dy) + dz dz)
+ *   other    with R / I = the reduced cell and its inverse from lchd_cell_reduce:  f_k = (dx I[0][k] + dy I[1][k]) + dz I[2][k],
+ *            f_k = f_k - rint(f_k), v = (f_0 a + f_1 b) + f_2 c per component (a, b, c = the rows of R); for i, j, k in {-1, 0, 1}
+ *            t = (i a + j b) + k c (the rule of the ghosts above), w = v + t, d2 = (wx wx + wy wy) + wz wz; distance = sqrt(min d2)
+ * Plain f64, left to right, nothing fused: a caller can compute the very same rows. */
+/* Host only, no device.  Minkowski-reduces a cell: `reduced` spans the same lattice (an integer combination of the rows of `cell` of
+ * determinant +-1, each reduced vector evaluated as (T_0 a + T_1 b) + T_2 c from the caller's vectors), and no reduced vector gets
+ * shorter by adding a {-1, 0, 1} combination of the other two -- then the nearest lattice translate of a displacement whose fractional
+ * coordinates are wrapped to [-1/2, 1/2] is among the 27 shifts {-1, 0, 1}^3, which does not hold for an arbitrary cell.  `inverse` is
+ * the inverse of `reduced` in the arithmetic of lchd_cell_validate (inverse[d][k] = (cross product of the other two vectors)[d] / det).
+ * A diagonal cell is returned untouched with the inverse diag(1 / L).  LCHD_EVALUE for a non-finite entry or a singular cell. */
+int lchd_cell_reduce(const double *cell /* [9] */, double *reduced /* [9] */, double *inverse /* [9] */);
+/* lchd_from_coords in periodic cells: cell_a / cell_b are HOST [9] matrices of the two structures, NULL for an open side (its rows are
+ * those of lchd_from_coords); with both NULL the call IS lchd_from_coords.  Row-length limits are those of lchd_from_dmxs; a workspace
+ * that does not fit the device is LCHD_EUNSUPPORTED.  With lchd_ctx_enable_timing, "cells" of lchd_ctx_last_ms is the time of the row
+ * producers of both sides. */
+int lchd_from_coords_periodic(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                              int64_t len_seq_b, const double *xyz_a, int64_t n_a, const double *xyz_b, int64_t n_b,
+                              const int32_t *wf_index, const double *cell_a, const double *cell_b, double *out);
+/* The same on two device-resident structures (lchd_from_coords_dev); the cells stay HOST pointers. */
+int lchd_from_coords_periodic_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, const double *cell_a,
+                                  const double *cell_b, double *d_out);
+/* lchd_ensemble_from_coords / _dev in periodic cells: cells is HOST [n_cells][9], n_cells = 1 (one cell for every structure) or the
+ * number of structures (NPT).  Excluded entries count as +inf on top of the minimum-image rows; blocks rebuild their rows as before. */
+int lchd_ensemble_from_coords_periodic(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq, int64_t n, const double *xyz,
+                                       int64_t n_struct, const int32_t *pairs, int64_t n_pairs, const int32_t *excl_start,
+                                       const int32_t *excl_idx, const int32_t *wf_index, const double *cells, int32_t n_cells, double *out);
+int lchd_ensemble_from_coords_periodic_dev(lchd_ctx *ctx, lchd_cloud *cloud, const int32_t *d_pairs, int64_t n_pairs,
+                                           const int32_t *d_excl_start, const int32_t *d_excl_idx, const int32_t *d_wf_index,
+                                           const double *cells, int32_t n_cells, double *d_out);
 
 /* ---- multi-GPU ------------------------------------------------------------------------------------
  * The reference's parallelism lives INSIDE the core call: a thread pool that is a field of `LoCoHD` (src/locohd.rs:53,

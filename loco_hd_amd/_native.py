@@ -102,6 +102,11 @@ _PROTOS = {
     "lchd_cloud_create_images_cell": (C.c_int, [_VP, _VP, _DP, _i32, _f64, C.POINTER(_VP)]),
     "lchd_cloud_update_images_cell": (C.c_int, [_VP, _VP, _VP, _DP, _i32]),
     "lchd_from_primitives_periodic_cell": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _DP, _DP, _DP]),
+    "lchd_cell_reduce": (C.c_int, [_DP, _DP, _DP]),
+    "lchd_from_coords_periodic": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _i64, _DP, _i64, _IP, _DP, _DP, _DP]),
+    "lchd_from_coords_periodic_dev": (C.c_int, [_VP, _VP, _VP, _VP, _DP, _DP, _VP]),
+    "lchd_ensemble_from_coords_periodic": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _DP, _i64, _IP, _i64, _IP, _IP, _IP, _DP, _i32, _DP]),
+    "lchd_ensemble_from_coords_periodic_dev": (C.c_int, [_VP, _VP, _VP, _i64, _VP, _VP, _VP, _DP, _i32, _VP]),
     "lchd_cloud_create": (C.c_int, [_VP, _DP, _IP, _IP, _i64, C.POINTER(_VP)]),
     "lchd_cloud_create_batch": (C.c_int, [_VP, _DP, _IP, _IP, _IP, _i64, _i32, C.POINTER(_VP)]),
     "lchd_cloud_size": (C.c_int64, [_VP]),

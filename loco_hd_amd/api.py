@@ -72,6 +72,58 @@ def periodic_cells(cell, n_structures: int, reach: float, what: str = "cell") ->
     return arr
 
 
+def dense_cells(box, cell, n_structures: int, what_box: str = "box", what_cell: str = "cell") -> Optional[np.ndarray]:
+    """The periodic cells of a dense (minimum-image) call as a float64 array [n_cells][3][3] (n_cells is 1 or `n_structures`), or None
+    when neither is given: a box (Lx, Ly, Lz) becomes its diagonal cell.  The shape checks of `periodic_boxes` / `periodic_cells`
+    without a reach (a dense row has no threshold); ValueError for an edge that is not finite and > 0 and for what lchd_cell_reduce
+    rejects (a non-finite entry, a singular cell).  No device is touched."""
+    if box is None and cell is None:
+        return None
+    if box is not None:
+        try:
+            arr = _f64(box)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what_box} must be three edge lengths (Lx, Ly, Lz)") from None
+        if arr.shape == (3,):
+            arr = arr.reshape(1, 3)
+        elif arr.ndim != 2 or arr.shape[1] != 3:
+            raise ValueError(f"{what_box} must be three edge lengths (Lx, Ly, Lz), got an array of shape {arr.shape}")
+        if len(arr) not in (1, int(n_structures)):
+            raise ValueError(f"{what_box}: {len(arr)} boxes given for {n_structures} structures (pass one box, or one per structure)")
+        if not (np.isfinite(arr).all() and (arr > 0.0).all()):
+            raise ValueError(f"{what_box}: every edge must be finite and > 0")
+        cells = np.zeros((len(arr), 3, 3))
+        for k in range(3):
+            cells[:, k, k] = arr[:, k]
+    else:
+        try:
+            cells = _f64(cell)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what_cell} must be a 3 x 3 matrix of lattice vectors (rows a, b, c)") from None
+        if cells.shape == (3, 3):
+            cells = cells.reshape(1, 3, 3)
+        elif cells.ndim != 3 or cells.shape[1:] != (3, 3):
+            raise ValueError(f"{what_cell} must be a 3 x 3 matrix of lattice vectors (rows a, b, c), got an array of shape {cells.shape}")
+        if len(cells) not in (1, int(n_structures)):
+            raise ValueError(f"{what_cell}: {len(cells)} cells given for {n_structures} structures (pass one cell, or one per structure)")
+    cells = np.ascontiguousarray(cells, dtype=np.float64)
+    reduced, inverse = np.empty(9), np.empty(9)
+    for c in cells:
+        N.check(N.lib().lchd_cell_reduce(N.dp(np.ascontiguousarray(c)), N.dp(reduced), N.dp(inverse)))
+    return cells
+
+
+def cell_reduce(cell) -> Tuple[np.ndarray, np.ndarray]:
+    """lchd_cell_reduce: the Minkowski-reduced form of a 3 x 3 cell (same lattice) and the inverse of the reduced cell, the two
+    matrices the minimum-image rows of the dense periodic calls are computed with.  A diagonal cell comes back unchanged."""
+    c = _f64(cell)
+    if c.shape != (3, 3):
+        raise ValueError(f"cell must be a 3 x 3 matrix of lattice vectors (rows a, b, c), got an array of shape {c.shape}")
+    reduced, inverse = np.empty((3, 3)), np.empty((3, 3))
+    N.check(N.lib().lchd_cell_reduce(N.dp(c), N.dp(reduced), N.dp(inverse)))
+    return reduced, inverse
+
+
 def cell_from_lengths_angles(a: float, b: float, c: float, alpha: float, beta: float, gamma: float) -> np.ndarray:
     """The 3 x 3 cell (rows = lattice vectors) of the lengths a, b, c and the angles alpha = (b, c), beta = (a, c), gamma = (a, b) in
     degrees, in the orientation of PDB / GROMACS / MDAnalysis: a along x, b in the xy plane.  An angle of exactly 90 gives exact
@@ -527,8 +579,23 @@ class LoCoHD:
                                                   N.ip(idx), N.dp(out)))
         return out.tolist()
 
-    def from_coords(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None) -> List[float]:
-        """src/locohd.rs:463-476."""
+    def from_coords(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None, *, box_a=None, box_b=None,
+                    cell_a=None, cell_b=None) -> List[float]:
+        """src/locohd.rs:463-476.
+
+        ``box_a`` / ``box_b`` / ``cell_a`` / ``cell_b`` (keyword-only, additive): an orthorhombic periodic box (Lx, Ly, Lz) or a triclinic
+        cell (3 x 3, rows = lattice vectors, any non-singular one) of the structure.  A dense row then follows the MINIMUM-IMAGE
+        convention: every atom appears exactly once, at the distance of its nearest periodic image (coordinates need not be wrapped).
+        This differs from ``from_primitives(..., box_a=...)``, where an atom beyond half an edge may enter through two images.  A side
+        takes a box or a cell, not both; the two sides are independent."""
+        periodic = box_a is not None or box_b is not None or cell_a is not None or cell_b is not None
+        if periodic:
+            for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+                if box is not None and cell is not None:
+                    raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
+            self._no_device_group_with_box()
+            pc_a = dense_cells(box_a, cell_a, 1, "box_a", "cell_a")
+            pc_b = dense_cells(box_b, cell_b, 1, "box_b", "cell_b")
         xa, xb = self._coords(coords_a), self._coords(coords_b)
         if len(xa) != len(xb):
             raise ValueError(f"Expected matrices with the same length, got lengths {len(xa)} and {len(xb)}!")
@@ -538,18 +605,29 @@ class LoCoHD:
         out = np.empty(len(xa))
         if len(xa) == 0:
             return []
+        if periodic:
+            N.check(N.lib().lchd_from_coords_periodic(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(xa), len(xa),
+                                                      N.dp(xb), len(xb), N.ip(idx), N.dp(pc_a), N.dp(pc_b), N.dp(out)))
+            return out.tolist()
         N.check(N.lib().lchd_from_coords(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(xa), len(xa),
                                          N.dp(xb), len(xb), N.ip(idx), N.dp(out)))
         return out.tolist()
 
     # ---- dense ensembles (additive) ----------------------------------------------------------------------
     def from_coords_ensemble(self, seq, coords, structure_pairs=None, w_func_keys: Optional[Sequence[str]] = None,
-                             excluded_pairs=None) -> np.ndarray:
+                             excluded_pairs=None, *, boxes=None, cells=None) -> np.ndarray:
         """Additive: `from_coords(seq, seq, coords[i], coords[j])` for every structure pair (i, j) of M structures of one
         topology, in one call -- python_codes/ensembles/compare_ensembles.py:277-296, where each structure's dense rows are
         sorted once.  `coords`: (M, n, 3) or a list of (n, 3); `structure_pairs`: (i, j) pairs, default every i < j (i outer);
         `excluded_pairs`: (r, c) atom-index pairs whose distance counts as +inf in every structure (directional: give both
-        orders, as the script's homo-residue ban does).  Returns a float64 array (P, n)."""
+        orders, as the script's homo-residue ban does).  Returns a float64 array (P, n).
+
+        ``boxes`` / ``cells`` (keyword-only, additive): one orthorhombic box (Lx, Ly, Lz) or one triclinic cell (3 x 3) for all
+        structures, or one per structure (NPT); the rows then follow the minimum-image convention of ``from_coords(..., box_a=...)``."""
+        if boxes is not None and cells is not None:
+            raise ValueError("boxes and cells were both given: a batch is periodic in boxes or in cells")
+        if boxes is not None or cells is not None:
+            self._no_device_group_with_box()
         xs = [self._coords(x) for x in coords]
         n = len(xs[0]) if xs else 0
         for x in xs[1:]:
@@ -565,6 +643,11 @@ class LoCoHD:
         cfg, keep = self._config()
         p = len(pairs) if pairs is not None else len(xs) * (len(xs) - 1) // 2
         out = np.empty((p, n))
+        pc = dense_cells(boxes, cells, len(xs), "boxes", "cells")
+        if pc is not None:
+            N.check(N.lib().lchd_ensemble_from_coords_periodic(self._context(), C.byref(cfg), N.ip(cs), n, N.dp(xyz), len(xs),
+                                                               N.ip(pairs), p, N.ip(xstart), N.ip(xidx), N.ip(idx), N.dp(pc), len(pc), N.dp(out)))
+            return out
         N.check(N.lib().lchd_ensemble_from_coords(self._context(), C.byref(cfg), N.ip(cs), n, N.dp(xyz), len(xs),
                                                   N.ip(pairs), p, N.ip(xstart), N.ip(xidx), N.ip(idx), N.dp(out)))
         return out

@@ -176,6 +176,17 @@ struct lchd_cloud {
 
 enum { PH_CELLS = 0, PH_ANCHORS = 1, PH_ENV = 2, PH_SWEEP = 3, PH_N = 4 };
 
+// The periodic cells of a dense call (lchd_from_coords_periodic*, lchd_ensemble_from_coords_periodic*).  A periodic entry reduces its
+// cells, hangs this on the context (lchd_ctx::min_image) and makes the open call; dense_pass and ensemble_core then take every
+// structure's distance rows from launch_min_image_rows instead of the coordinates.  Null outside such a call.
+struct MinImage {
+    MinImageCell side[2];           // single pair: the cells of A and B; ensembles with one cell for all structures: side[0]
+    bool on[2] = {false, false};    // single pair: the side is periodic
+    const double* d_recs = nullptr; // ensembles with a cell per structure: DEVICE [M][kMinImageRecord]
+    int32_t n_cells = 0;            // ensembles: 1 or M
+    bool all_diagonal = false;      // ensembles: every cell is diagonal
+};
+
 // What lchd_ctx_last_grid reports about one side of a pass: the planned grid and which cell-list build launch_prologue picked.
 struct GridRecord {
     int32_t dim[3] = {0, 0, 0};
@@ -249,6 +260,7 @@ struct lchd_ctx {
     size_t io_cap = 0;
     std::vector<char> cfg_blob_host;  // last configuration blob uploaded (identical configurations are not uploaded again)
     PassHints hints{};  // what the thresholded passes of this context looked like so far (lchd_pass_plan.h): plan_pass and launch_sweep read it
+    const MinImage* min_image = nullptr;  // set for the duration of a periodic dense call
     bool last_dense_fused = false;  // the most recent dense pass ran the fused sort + sweep kernel (lchd_dense_fused.hip)
     int64_t n_per_pair_passes = 0;  // passes whose side B was not de-duplicated (PassPlan::per_pair)
     // second pass over the pairs of overflowed environments (lchd_ctx_finish): grow-only device blocks outside the arena
@@ -1771,6 +1783,24 @@ static int cell_records(const double* cells, int32_t n_cells, double reach, doub
 }
 extern "C" int lchd_cell_validate(const double* cells, int32_t n_cells, double reach) { return cell_records(cells, n_cells, reach, nullptr); }
 
+// The cell of the dense minimum-image calls (lchd_cell_reduce.h): validated with the messages of lchd_cell_validate (no reach: a dense
+// row has no threshold), Minkowski-reduced, with the inverse of the reduced cell.
+static int min_image_cell(const double* cell, int32_t index, double* reduced, double* inverse) {
+    if (int rc = cell_record(cell, index, 0.0, nullptr)) return rc;
+    if (cell_reduce(cell, reduced, inverse) != 0)
+        return fail(LCHD_EVALUE, "cell %d is singular: its three vectors must span a volume", index);
+    return LCHD_OK;
+}
+static int min_image_record(const double* cell, int32_t index, MinImageCell& rec) {
+    if (int rc = min_image_cell(cell, index, rec.v, rec.v + 9)) return rc;
+    rec.v[18] = cell_is_diagonal(rec.v) ? 1.0 : 0.0;
+    return LCHD_OK;
+}
+extern "C" int lchd_cell_reduce(const double* cell, double* reduced, double* inverse) {
+    if (!cell || !reduced || !inverse) return fail(LCHD_EVALUE, "null argument");
+    return min_image_cell(cell, 0, reduced, inverse);
+}
+
 template <class T>
 static int grow_array(T*& p, size_t n) {
     (void)hipFree(p);
@@ -2623,6 +2653,20 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
                       const double* h_ma = nullptr, const double* h_mb = nullptr, const int32_t* d_len_a = nullptr,
                       const int32_t* d_len_b = nullptr) {
     retry = false;
+    // a periodic dense call: both structures' rows are materialised in the workspace (an open side with k_ens_dist's arithmetic) and
+    // the pass runs in its given-row form
+    const MinImage* mi = (!d_ma && !d_mb && !h_ma && !h_mb) ? c->min_image : nullptr;
+    auto produce_rows = [&](double* w_a, double* w_b) {
+        mark(c, 0);
+        for (int side = 0; side < 2; ++side) {
+            const lchd_cloud& cl = side ? b : a;
+            const int64_t n = side ? cols_b : cols_a;
+            double* w = side ? w_b : w_a;
+            if (mi->on[side]) launch_min_image_rows(c->stream, cl.view(false), 0, (int32_t)n, rows, mi->side[side], nullptr, mi->side[side].v[18] != 0.0, nullptr, nullptr, w);
+            else launch_ens_dist(c->stream, cl.view(false), 0, (int32_t)n, rows, nullptr, nullptr, w);
+        }
+        mark(c, 1);
+    };
     const int cap_a = next_pow2_host(cols_a), cap_b = next_pow2_host(cols_b);
     // more than 255 categories: 16-bit ids in the environment store, k_env_rows<.., uint16_t> + k_sweep_wide<.., CAT16>
     const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
@@ -2647,7 +2691,7 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
             Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
             scr_key = ar.take<uint64_t>(scr_n);  // the distance pass's (key, value) pairs, one region per workgroup
             scr_val = ar.take<uint8_t>(scr_n);
-            if (h_ma) {
+            if (h_ma || mi) {
                 w_ma2 = ar.take<double>((size_t)rows * cols_a);
                 w_mb2 = ar.take<double>((size_t)rows * cols_b);
             }
@@ -2656,6 +2700,10 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
         if (h_ma) {
             HIP_TRY(hipMemcpyAsync(w_ma2, h_ma, sizeof(double) * rows * cols_a, hipMemcpyHostToDevice, c->stream));
             HIP_TRY(hipMemcpyAsync(w_mb2, h_mb, sizeof(double) * rows * cols_b, hipMemcpyHostToDevice, c->stream));
+            d_ma = w_ma2;
+            d_mb = w_mb2;
+        } else if (mi) {
+            produce_rows(w_ma2, w_mb2);
             d_ma = w_ma2;
             d_mb = w_mb2;
         }
@@ -2704,7 +2752,7 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
         eb.stride = cap_b;
         ea.cdf_keys = eb.cdf_keys = (c->h_cfg.n_wf == 1 && !c->tune.no_cdf_keys) ? 1 : 0;
         d_meta = ar.take<int4>((size_t)rows);
-        if (h_ma) {  // given distance matrices in host memory: straight from the caller's buffers into the workspace
+        if (h_ma || mi) {  // given distance matrices in host memory: straight from the caller's buffers into the workspace
             w_ma = ar.take<double>((size_t)rows * cols_a);
             w_mb = ar.take<double>((size_t)rows * cols_b);
         }
@@ -2714,6 +2762,10 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
     if (h_ma) {
         HIP_TRY(hipMemcpyAsync(w_ma, h_ma, sizeof(double) * rows * cols_a, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(w_mb, h_mb, sizeof(double) * rows * cols_b, hipMemcpyHostToDevice, s));
+        d_ma = w_ma;
+        d_mb = w_mb;
+    } else if (mi) {
+        produce_rows(w_ma, w_mb);
         d_ma = w_ma;
         d_mb = w_mb;
     }
@@ -3091,7 +3143,11 @@ static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, c
         for (int64_t k0 = 0; k0 < cnt; k0 += dist_structs) {
             const int64_t kc = std::min(dist_structs, cnt - k0), rows = kc * n;
             if (src.coords) {
-                launch_ens_dist(s, src.coords->view(cat16), (s0 + k0) * n, (int32_t)n, rows, src.excl_start, src.excl_idx, dmx);
+                if (const MinImage* mi = c->min_image)  // a periodic ensemble: minimum-image rows, exclusions on top as below
+                    launch_min_image_rows(s, src.coords->view(cat16), (s0 + k0) * n, (int32_t)n, rows, mi->side[0], mi->d_recs, mi->all_diagonal,
+                                          src.excl_start, src.excl_idx, dmx);
+                else
+                    launch_ens_dist(s, src.coords->view(cat16), (s0 + k0) * n, (int32_t)n, rows, src.excl_start, src.excl_idx, dmx);
             } else {
                 HIP_TRY(hipMemcpyAsync(dmx, src.h_dmx + (size_t)(s0 + k0) * n * n, sizeof(double) * (size_t)rows * n, hipMemcpyHostToDevice, s));
             }
@@ -3335,4 +3391,110 @@ extern "C" int lchd_ensemble_from_dmxs(lchd_ctx* c, const lchd_config* cfg, cons
     if (int rc = ensemble_core(c, EnsSrc{cats, nullptr, dmx, nullptr, nullptr}, n, n_struct, hp, d_wf, d_out)) return rc;
     HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * (size_t)(P * n), hipMemcpyDeviceToHost));
     return LCHD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// dense calls in periodic cells (minimum image): the cells are reduced on the host and hung on the context, the open call then
+// runs with every periodic structure's rows materialised by launch_min_image_rows (dense_pass, ensemble_core)
+// ------------------------------------------------------------------------------------------------
+struct MinImageScope {  // lchd_ctx::min_image for the duration of the open call
+    lchd_ctx* c;
+    MinImageScope(lchd_ctx* ctx, const MinImage* mi) : c(ctx) { c->min_image = mi; }
+    ~MinImageScope() { c->min_image = nullptr; }
+};
+// "cells" of lchd_ctx_last_ms after a periodic single-pair call: the row producers of both sides (events 0 and 1 of dense_pass)
+static void min_image_time(lchd_ctx* c) {
+    float t = -1.f;
+    if (c->timing && hipEventElapsedTime(&t, c->ev[0], c->ev[1]) == hipSuccess) c->ms[PH_CELLS] = t;
+}
+static int min_image_sides(const double* cell_a, const double* cell_b, MinImage& mi) {
+    const double* cells[2] = {cell_a, cell_b};
+    for (int side = 0; side < 2; ++side) {
+        mi.on[side] = cells[side] != nullptr;
+        if (cells[side])
+            if (int rc = min_image_record(cells[side], side, mi.side[side])) return rc;
+    }
+    return LCHD_OK;
+}
+
+extern "C" int lchd_from_coords_periodic_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
+                                             const double* cell_b, double* d_out) {
+    CTX_LOCK(c);
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (c->min_image) return fail(LCHD_EVALUE, "a periodic dense call is already running on this context");
+    if (!cell_a && !cell_b) return lchd_from_coords_dev(c, a, b, d_wf_index, d_out);
+    MinImage mi;
+    if (int rc = min_image_sides(cell_a, cell_b, mi)) return rc;
+    if (a->images || b->images) return fail(LCHD_EVALUE, "a periodic dense call takes the structures themselves, not their image clouds");
+    CTX_GUARD(c);
+    if (int rc = resolve_bbox(c, a)) return rc;  // (rejects non-finite coordinates of a buffer filled on the device)
+    if (int rc = resolve_bbox(c, b)) return rc;
+    MinImageScope scope(c, &mi);
+    const int rc = lchd_from_coords_dev(c, a, b, d_wf_index, d_out);
+    if (!rc) min_image_time(c);
+    return rc;
+}
+
+extern "C" int lchd_from_coords_periodic(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                         int64_t len_seq_b, const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b,
+                                         const int32_t* wf_index, const double* cell_a, const double* cell_b, double* out) {
+    CTX_LOCK(c);
+    if (!c) return fail(LCHD_EVALUE, "null context");
+    if (c->min_image) return fail(LCHD_EVALUE, "a periodic dense call is already running on this context");
+    MinImage mi;
+    if (int rc = min_image_sides(cell_a, cell_b, mi)) return rc;
+    MinImageScope scope(c, (cell_a || cell_b) ? &mi : nullptr);
+    const int rc = lchd_from_coords(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, n_a, xyz_b, n_b, wf_index, out);
+    if (!rc && (cell_a || cell_b)) min_image_time(c);
+    return rc;
+}
+
+// cells: HOST [n_cells][9], n_cells = 1 or the number of structures.  Fills `mi`; per-structure records go to the device through `bufs`.
+static int min_image_ensemble(const double* cells, int32_t n_cells, int64_t n_struct, MinImage& mi, EnsDevBufs& bufs) {
+    if (!cells || (n_cells != 1 && n_cells != n_struct))
+        return fail(LCHD_EVALUE, "%d cells given for %lld structures (pass one cell, or one per structure)", cells ? n_cells : 0, (long long)n_struct);
+    std::vector<MinImageCell> recs((size_t)n_cells);
+    mi.all_diagonal = true;
+    for (int32_t k = 0; k < n_cells; ++k) {
+        if (int rc = min_image_record(cells + 9 * (size_t)k, k, recs[(size_t)k])) return rc;
+        if (recs[(size_t)k].v[18] == 0.0) mi.all_diagonal = false;
+    }
+    mi.n_cells = n_cells;
+    mi.side[0] = recs[0];
+    if (n_cells > 1) {
+        double* d = nullptr;
+        if (int rc = bufs.put(recs[0].v, (size_t)n_cells * kMinImageRecord, &d)) return rc;
+        mi.d_recs = d;
+    }
+    return LCHD_OK;
+}
+
+extern "C" int lchd_ensemble_from_coords_periodic_dev(lchd_ctx* c, lchd_cloud* cl, const int32_t* d_pairs, int64_t n_pairs,
+                                                      const int32_t* d_excl_start, const int32_t* d_excl_idx, const int32_t* d_wf_index,
+                                                      const double* cells, int32_t n_cells, double* d_out) {
+    CTX_LOCK(c);
+    if (!c || !cl) return fail(LCHD_EVALUE, "null argument");
+    if (c->min_image) return fail(LCHD_EVALUE, "a periodic dense call is already running on this context");
+    if (cl->images) return fail(LCHD_EVALUE, "a periodic dense call takes the structures themselves, not their image clouds");
+    CTX_GUARD(c);
+    MinImage mi;
+    EnsDevBufs bufs;
+    if (int rc = min_image_ensemble(cells, n_cells, cl->n_struct, mi, bufs)) return rc;
+    MinImageScope scope(c, &mi);
+    return lchd_ensemble_from_coords_dev(c, cl, d_pairs, n_pairs, d_excl_start, d_excl_idx, d_wf_index, d_out);
+}
+
+extern "C" int lchd_ensemble_from_coords_periodic(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t n, const double* xyz,
+                                                  int64_t n_struct, const int32_t* pairs, int64_t n_pairs, const int32_t* excl_start,
+                                                  const int32_t* excl_idx, const int32_t* wf_index, const double* cells, int32_t n_cells,
+                                                  double* out) {
+    CTX_LOCK(c);
+    if (!c) return fail(LCHD_EVALUE, "null context");
+    if (c->min_image) return fail(LCHD_EVALUE, "a periodic dense call is already running on this context");
+    CTX_GUARD(c);
+    MinImage mi;
+    EnsDevBufs bufs;
+    if (int rc = min_image_ensemble(cells, n_cells, n_struct, mi, bufs)) return rc;
+    MinImageScope scope(c, &mi);
+    return lchd_ensemble_from_coords(c, cfg, seq, n, xyz, n_struct, pairs, n_pairs, excl_start, excl_idx, wf_index, out);
 }

@@ -7,6 +7,7 @@
 #include <iterator>
 #include <type_traits>
 
+#include "lchd_cell_reduce.h"  // host only: kMinImageRecord, the cell of the dense minimum-image calls
 #include "lchd_pass_plan.h"  // the host-only part: Tuning, HostStatus, the ST_* status bits, the pass planner
 
 struct lchd_sweep_query;  // include/loco_hd_hip.h
@@ -403,6 +404,11 @@ void launch_env_points(hipStream_t s, const SweepArgs& a, unsigned long long* ou
 // atom0 of c (row k * n + r: atom r of structure k), the excluded entries (CSR over the n rows of a structure, or null) +inf.
 void launch_ens_dist(hipStream_t s, const CloudView& c, int64_t atom0, int32_t n, int64_t n_rows, const int32_t* excl_start,
                      const int32_t* excl_idx, double* dmx);
+// The same rows in a periodic cell (minimum image).  `one`: the cell of every structure, or d_recs: DEVICE [structures][kMinImageRecord],
+// indexed by atom0 / n + the structure's position in the launch.  all_diagonal: every cell is diagonal (the orthorhombic kernel).
+struct MinImageCell { double v[kMinImageRecord]; };  // lchd_cell_reduce.h: reduced cell, inverse, 1.0 if diagonal
+void launch_min_image_rows(hipStream_t s, const CloudView& c, int64_t atom0, int32_t n, int64_t n_rows, const MinImageCell& one,
+                           const double* d_recs, bool all_diagonal, const int32_t* excl_start, const int32_t* excl_idx, double* dmx);
 void launch_ens_iota(hipStream_t s, uint32_t* slot, int64_t n);
 // plan[k] = {slot of structure i, slot of structure j, output pair, 0}: record k * n + r = (slot_i * n + r, slot_j * n + r),
 // weight function wf[r] (wf / wf_rec null: all 0); the scatter puts score k * n + r at out[plan[k].z * n + r]

@@ -7,6 +7,8 @@
 // structure pair becomes n sweep records (slot(i) * n + r, slot(j) * n + r) over that one store.  The kernels here:
 //   k_ens_dist     distance rows of a block of structures from their coordinates (utils.rs:1-8 order, uncontracted), the input
 //                  of the existing row sorts (lchd_env_rows.hip, given-row form)
+//   k_min_image_rows  the same rows in a periodic cell: every atom at the distance of its nearest periodic image (minimum image),
+//                  in a diagonal cell (orthorhombic box) per axis, in any other cell among the 27 shifts of the wrapped displacement
 //   k_ens_excl     the caller's excluded (row, column) entries set to +inf (the script's homo-residue ban, :261-263)
 //   k_ens_iota     identity slot map (SweepArgs::slot_a / slot_b: a record's "anchor" IS its environment slot)
 //   k_ens_records  structure-pair list -> sweep records and per-record weight-function indices, on the device
@@ -28,6 +30,87 @@ __global__ __launch_bounds__(256) void k_ens_dist(const double* __restrict__ x, 
             d2 = d2 + dy * dy;
             d2 = d2 + dz * dz;
             row[i] = sqrt(d2);
+        }
+    }
+}
+
+// ---- minimum-image rows (lchd_from_coords_periodic / lchd_ensemble_from_coords_periodic; the arithmetic is part of the contract in
+// include/loco_hd_hip.h: plain f64, IEEE division, rint = round to nearest even, every sum left to right, nothing fused) -----------
+// A diagonal cell: per axis d - L rint(d / L).
+__device__ __forceinline__ double min_image_box(double dx, double dy, double dz, double lx, double ly, double lz) {
+    dx = dx - lx * rint(dx / lx);
+    dy = dy - ly * rint(dy / ly);
+    dz = dz - lz * rint(dz / lz);
+    return sqrt((dx * dx + dy * dy) + dz * dz);
+}
+// Any other cell, R = the Minkowski-reduced vectors (rows), I = their inverse: fractional coordinates wrapped to [-1/2, 1/2], back to
+// Cartesian, then the shortest of the 27 neighbours v + (i a + j b) + k c (i outermost, k innermost; for a reduced cell no other
+// lattice translate is nearer, lchd_cell_reduce.h).
+__device__ __forceinline__ double min_image_cell(double dx, double dy, double dz, const double (&R)[9], const double (&I)[9]) {
+    double f0 = (dx * I[0] + dy * I[3]) + dz * I[6];
+    double f1 = (dx * I[1] + dy * I[4]) + dz * I[7];
+    double f2 = (dx * I[2] + dy * I[5]) + dz * I[8];
+    f0 = f0 - rint(f0);
+    f1 = f1 - rint(f1);
+    f2 = f2 - rint(f2);
+    const double vx = (f0 * R[0] + f1 * R[3]) + f2 * R[6];
+    const double vy = (f0 * R[1] + f1 * R[4]) + f2 * R[7];
+    const double vz = (f0 * R[2] + f1 * R[5]) + f2 * R[8];
+    double best = __builtin_inf();
+#pragma unroll
+    for (int i = -1; i <= 1; ++i)
+#pragma unroll
+        for (int j = -1; j <= 1; ++j)
+#pragma unroll
+            for (int k = -1; k <= 1; ++k) {
+                const double wx = vx + (((double)i * R[0] + (double)j * R[3]) + (double)k * R[6]);
+                const double wy = vy + (((double)i * R[1] + (double)j * R[4]) + (double)k * R[7]);
+                const double wz = vz + (((double)i * R[2] + (double)j * R[5]) + (double)k * R[8]);
+                best = fmin(best, (wx * wx + wy * wy) + wz * wz);
+            }
+    return sqrt(best);
+}
+
+// One workgroup per row, as k_ens_dist.  The cell is wave-uniform: `one` (kernel argument) or, with per-structure cells, record
+// struct0 + k of `recs`, loaded once per row through an index made of blockIdx only.  CELL = false: every cell is diagonal.
+// vec2: n and atom0 are even and every array is 16-byte aligned, so a lane takes two neighbours (16-byte loads and stores).
+template <bool CELL>
+__global__ __launch_bounds__(256) void k_min_image_rows(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z,
+                                                        int64_t atom0, int32_t n, int64_t n_rows, MinImageCell one,
+                                                        const double* __restrict__ recs, int64_t struct0, int32_t vec2,
+                                                        double* __restrict__ dmx) {
+    for (int64_t g = blockIdx.x; g < n_rows; g += gridDim.x) {
+        const int64_t k = g / n, r = g - k * n;
+        const int64_t base = atom0 + k * n;
+        double R[9], I[9], diag;
+        if (recs) {
+            const double* __restrict__ p = recs + (struct0 + k) * kMinImageRecord;
+#pragma unroll
+            for (int q = 0; q < 9; ++q) { R[q] = p[q]; I[q] = p[9 + q]; }
+            diag = p[18];
+        } else {
+#pragma unroll
+            for (int q = 0; q < 9; ++q) { R[q] = one.v[q]; I[q] = one.v[9 + q]; }
+            diag = one.v[18];
+        }
+        const bool box = !CELL || diag != 0.0;
+        const double ax = x[base + r], ay = y[base + r], az = z[base + r];
+        auto dist = [&](double px, double py, double pz) -> double {
+            const double dx = ax - px, dy = ay - py, dz = az - pz;
+            if (box) return min_image_box(dx, dy, dz, R[0], R[4], R[8]);
+            if constexpr (CELL) return min_image_cell(dx, dy, dz, R, I);
+            return 0.0;
+        };
+        double* __restrict__ row = dmx + g * n;
+        if (vec2) {
+            for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * (int)blockDim.x) {
+                const double2 px = *reinterpret_cast<const double2*>(x + base + i);
+                const double2 py = *reinterpret_cast<const double2*>(y + base + i);
+                const double2 pz = *reinterpret_cast<const double2*>(z + base + i);
+                *reinterpret_cast<double2*>(row + i) = make_double2(dist(px.x, py.x, pz.x), dist(px.y, py.y, pz.y));
+            }
+        } else {
+            for (int i = threadIdx.x; i < n; i += blockDim.x) row[i] = dist(x[base + i], y[base + i], z[base + i]);
         }
     }
 }
@@ -76,6 +159,17 @@ void launch_ens_dist(hipStream_t s, const CloudView& c, int64_t atom0, int32_t n
     if (n_rows <= 0) return;
     const unsigned grid = grid_for(n_rows, 1, 1u << 20);
     k_ens_dist<<<grid, 256, 0, s>>>(c.x, c.y, c.z, atom0, n, n_rows, dmx);
+    if (excl_start) k_ens_excl<<<grid, 256, 0, s>>>(excl_start, excl_idx, n, n_rows, dmx);
+}
+void launch_min_image_rows(hipStream_t s, const CloudView& c, int64_t atom0, int32_t n, int64_t n_rows, const MinImageCell& one,
+                           const double* d_recs, bool all_diagonal, const int32_t* excl_start, const int32_t* excl_idx, double* dmx) {
+    if (n_rows <= 0) return;
+    const unsigned grid = grid_for(n_rows, 1, 1u << 20);
+    auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    const int32_t vec2 = (n % 2 == 0 && atom0 % 2 == 0 && aligned(c.x) && aligned(c.y) && aligned(c.z) && aligned(dmx)) ? 1 : 0;
+    const int64_t struct0 = atom0 / n;
+    if (all_diagonal) k_min_image_rows<false><<<grid, 256, 0, s>>>(c.x, c.y, c.z, atom0, n, n_rows, one, d_recs, struct0, vec2, dmx);
+    else k_min_image_rows<true><<<grid, 256, 0, s>>>(c.x, c.y, c.z, atom0, n, n_rows, one, d_recs, struct0, vec2, dmx);
     if (excl_start) k_ens_excl<<<grid, 256, 0, s>>>(excl_start, excl_idx, n, n_rows, dmx);
 }
 void launch_ens_iota(hipStream_t s, uint32_t* slot, int64_t n) {

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .api import LoCoHD, periodic_boxes, periodic_cells
+from .api import LoCoHD, dense_cells, periodic_boxes, periodic_cells
 
 
 def last_sweep_of(ctx):
@@ -213,9 +213,17 @@ class DeviceSession:
                                                  float(threshold_distance), C.c_void_p(out.data_ptr())))
         return out
 
-    def from_coords(self, cloud_a, cloud_b, out=None, wf_index=None):
+    def from_coords(self, cloud_a, cloud_b, out=None, wf_index=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None):
         """LoCoHD.from_coords on two uploaded structures of equal size: pair r = (atom r, atom r), environments = the whole
-        structures.  Returns (or fills) a torch float64 CUDA tensor [n]."""
+        structures.  Returns (or fills) a torch float64 CUDA tensor [n].
+
+        `box_a` / `box_b` / `cell_a` / `cell_b` (keyword-only, host arrays): the periodic box (Lx, Ly, Lz) or cell (3 x 3) of a side;
+        its rows then follow the minimum-image convention (LoCoHD.from_coords; lchd_from_coords_periodic_dev)."""
+        for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+            if box is not None and cell is not None:
+                raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
+        pc_a = dense_cells(box_a, cell_a, 1, "box_a", "cell_a")
+        pc_b = dense_cells(box_b, cell_b, 1, "box_b", "cell_b")
         torch = self.torch
         n = int(N.lib().lchd_cloud_size(cloud_a))
         if out is None:
@@ -225,18 +233,27 @@ class DeviceSession:
         if wf_index is not None:
             assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= n
             wf_ptr = C.c_void_p(wf_index.data_ptr())
+        if pc_a is not None or pc_b is not None:
+            N.check(N.lib().lchd_from_coords_periodic_dev(self._ctx, cloud_a, cloud_b, wf_ptr, N.dp(pc_a), N.dp(pc_b), C.c_void_p(out.data_ptr())))
+            return out
         N.check(N.lib().lchd_from_coords_dev(self._ctx, cloud_a, cloud_b, wf_ptr, C.c_void_p(out.data_ptr())))
         return out
 
-    def from_coords_ensemble(self, batch, pairs=None, out=None, wf_index=None, excluded=None):
+    def from_coords_ensemble(self, batch, pairs=None, out=None, wf_index=None, excluded=None, *, boxes=None, cells=None):
         """LoCoHD.from_coords_ensemble on a batch from `upload_batch` (structures of equal size) or a frames buffer: row r of
         structure pair p = from_coords(seq, seq, X[i_p], X[j_p])[r].  pairs: torch int32 CUDA tensor [P][2] or None (every
         i < j); wf_index: torch int32 CUDA tensor [n] or None; excluded: iterable of (r, c) atom pairs counted as +inf.
-        Returns (or fills) a torch float64 CUDA tensor [P][n]."""
+        Returns (or fills) a torch float64 CUDA tensor [P][n].
+
+        `boxes` / `cells` (keyword-only, host arrays): one periodic box (Lx, Ly, Lz) or cell (3 x 3) for all structures, or one per
+        structure; the rows then follow the minimum-image convention (lchd_ensemble_from_coords_periodic_dev)."""
+        if boxes is not None and cells is not None:
+            raise ValueError("boxes and cells were both given: a batch is periodic in boxes or in cells")
         torch = self.torch
         dev = torch.device("cuda", self.device)
         total = int(N.lib().lchd_cloud_size(batch))
         m = self._n_structures(batch)
+        pc = dense_cells(boxes, cells, m, "boxes", "cells")
         n = total // m if m else 0
         pairs_ptr, p = None, m * (m - 1) // 2
         if pairs is not None:
@@ -256,6 +273,10 @@ class DeviceSession:
             xs_t, xi_t = torch.from_numpy(xs).to(dev), torch.from_numpy(xi if len(xi) else np.zeros(1, dtype=np.int32)).to(dev)
             keep += [xs_t, xi_t]
             xs_ptr, xi_ptr = C.c_void_p(xs_t.data_ptr()), C.c_void_p(xi_t.data_ptr())
+        if pc is not None:
+            N.check(N.lib().lchd_ensemble_from_coords_periodic_dev(self._ctx, batch, pairs_ptr, p, xs_ptr, xi_ptr, wf_ptr, N.dp(pc), len(pc),
+                                                                   C.c_void_p(out.data_ptr())))
+            return out
         N.check(N.lib().lchd_ensemble_from_coords_dev(self._ctx, batch, pairs_ptr, p, xs_ptr, xi_ptr, wf_ptr, C.c_void_p(out.data_ptr())))
         return out
 
