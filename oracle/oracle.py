@@ -15,6 +15,11 @@ from pathlib import Path
 
 import numpy as np
 
+try:  # POSIX; elsewhere concurrent builders are not serialised (the Makefile's rename still keeps every loaded file whole)
+    import fcntl
+except ImportError:  # pragma: no cover
+    fcntl = None
+
 _DIR = Path(__file__).resolve().parent
 # LCHD_ASAN=1: the AddressSanitizer / UBSan build of the checker (make -C oracle asan; README "Sanitizer run")
 _ASAN = bool(os.environ.get("LCHD_ASAN"))
@@ -28,10 +33,25 @@ class OraclePanic(RuntimeError):
     """Stands in for pyo3_runtime.PanicException (a Rust panic in the reference)."""
 
 
+def _stale(src: Path) -> bool:
+    return not _SO.exists() or _SO.stat().st_mtime < src.stat().st_mtime
+
+
 def build(force: bool = False) -> Path:
+    """Build the checker if it is missing or older than its source.  Processes that find it stale at the same time (the ranks
+    torch.multiprocessing spawns in tests/test_dist_gloo.py) take turns under a lock on the source file, and all but the first find
+    it fresh; the Makefile renames the finished library into place, so a process that does not build never loads a partial file."""
     src = _DIR / "locohd_oracle.c"
-    if force or not _SO.exists() or _SO.stat().st_mtime < src.stat().st_mtime:
-        subprocess.check_call(["make", "-C", str(_DIR), "-B", "asan" if _ASAN else "liblocohd_oracle.so"], stdout=subprocess.DEVNULL)
+    if force or _stale(src):
+        with open(src, "rb") as lock:
+            if fcntl is not None:
+                fcntl.flock(lock, fcntl.LOCK_EX)
+            try:
+                if force or _stale(src):
+                    subprocess.check_call(["make", "-C", str(_DIR), "-B", "asan" if _ASAN else "liblocohd_oracle.so"], stdout=subprocess.DEVNULL)
+            finally:
+                if fcntl is not None:
+                    fcntl.flock(lock, fcntl.LOCK_UN)
     return _SO
 
 

@@ -6,6 +6,7 @@ rows, with the CPU oracle's from_anchors on rows found by brute force over the s
 import numpy as np
 import pytest
 
+from dense_rows_util import oracle_rows
 from min_image_util import brute_rows, min_image_matrix
 from periodic_cell_util import CELLS
 
@@ -65,16 +66,6 @@ def geometry(rng, name, n):
 
 def matrix(x, cell):
     return min_image_matrix(x, cell=cell, reduce=reduce)
-
-
-def oracle_rows(lo, sa, sb, rows_a, rows_b):
-    """stat_dist_integral on the stably sorted rows (utils.rs:25-39), one from_anchors call per row pair."""
-    out = []
-    for ra, rb in zip(rows_a, rows_b):
-        ra, rb = np.asarray(ra, dtype=float) + 0.0, np.asarray(rb, dtype=float) + 0.0
-        oa, ob = np.argsort(ra, kind="stable"), np.argsort(rb, kind="stable")
-        out.append(lo.from_anchors([sa[k] for k in oa], [sb[k] for k in ob], ra[oa].tolist(), rb[ob].tolist()))
-    return np.asarray(out)
 
 
 @pytest.mark.parametrize("geo", GEOMETRIES)
