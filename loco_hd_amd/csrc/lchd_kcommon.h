@@ -108,7 +108,7 @@ __device__ __forceinline__ int merge_path(const uint64_t* A, int nA, const uint6
 // of every lane's window; the steps are the powers of two below 2^bits(wmax), largest first: after them pos = lo + the number of
 // m in [lo, hi) with A[m] <= B[d - 1 - m] -- the predicate is true up to the partition and false behind it, so that is merge_path's
 // result for every input, ties included.  A probe behind the window (m >= hi) counts as false; its reads are moved into the lists
-// (mc <= max(hi - 1, 0), and B's index d - 1 - mc lies in [0, nB]: entry nB is one of the buffers' spare entries).
+// (mc <= max(hi - 1, 0), and B's index d - 1 - mc lies in [0, nB]: entry nB is the list's sentinel).
 // profiles/merge_path_model.py is this loop in numpy, with the trip counts of both forms.
 __device__ __forceinline__ int merge_path_fixed(const uint64_t* A, int nA, const uint64_t* B, int nB, int d, int wmax) {
     const int lo = max(0, d - nB), hi = min(d, nA);

@@ -82,11 +82,14 @@ __global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8
     constexpr bool LCNT = TT::LCNT;
     constexpr int RULE = TILE_ == kDuoTile ? 0 : 2;
     __shared__ double t_sqrt[NT], t_rsqrt[NT];
-    // one buffer per team: list A's points, then list B's (at most TILE together; + the spare entries the head re-reads may touch)
-    __shared__ uint64_t s_[WPB][TEAMS][TILE + 2];
+    // one buffer per team: list A's points, its sentinel (and a pad entry behind an even list), list B's points, its sentinel: at most
+    // TILE points together, list B starts at entry TILE + 2 at most and its sentinel lies at entry TILE + 2 at most (TILE + 4: the teams'
+    // buffers stay 16-byte aligned)
+    __shared__ uint64_t s_[WPB][TEAMS][TILE + 4];
     __shared__ uint8_t c_[WPB][TEAMS][TILE + 8];
-    // (TeamTile's PRE branch reads up to kPreStep - 1 category bytes behind a chunk's start without a clamp: at most byte TILE + 1 + kPreStep - 1 of a team's row)
-    static_assert(!PRE || TILE + 1 + (kPreStep - 1) < TILE + 8, "spare category bytes behind list B for the unclamped reads of the prefix-count rows");
+    // (TeamTile's PRE branch reads up to kPreStep - 1 category bytes behind a chunk's start without a clamp: a chunk of list B starts at
+    // byte TILE + 2 of a team's row at most, so the reads end at byte TILE + 2 + kPreStep - 1)
+    static_assert(!PRE || TILE + 2 + (kPreStep - 1) < TILE + 8, "spare category bytes behind list B for the unclamped reads of the prefix-count rows");
     __shared__ uint64_t lc_[LCNT ? WPB : 1][LCNT ? LW * 64 : 1];  // (TeamTile::LCNT: per-lane count rows of the event loop)
     __shared__ double w_s[WGT ? 32 : 1];
     if (!args.forced && rule_in_force(args) != RULE) return;  // another rule's pairs are the majority, or none's: k_sweep sweeps everything
@@ -157,9 +160,10 @@ __global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8
             const uint8_t* __restrict__ tA = args.env_a.cat + offA;
             const uint8_t* __restrict__ tB = args.env_b.cat + offB;
             const double F0 = valid ? u2d(kA[0]) : 0.0;            // F(0): both anchors sit at distance 0
-            // list B starts at an EVEN entry of the buffer (one unused entry behind an odd list A): the staging below moves two entries per
-            // lane and round -- one 16-byte key load, one 16-byte LDS write -- and no pair of entries straddles the two lists
-            const int mAe = (mA + 1) & ~1, Tb = mAe + mB;  // <= TILE + 1: the buffers hold TILE + 2 entries
+            // list B starts at an EVEN entry of the buffer behind list A's SENTINEL entry sA[mA] (one entry behind an odd list A, two behind
+            // an even one): the staging below moves two entries per lane and round -- one 16-byte key load, one 16-byte LDS write -- and no
+            // pair of entries straddles the two lists.  An unusable pair stages nothing (Tb = 0).
+            const int mAe = valid ? (mA + 2) & ~1 : 0, Tb = mAe + mB;  // <= TILE + 2: list B's sentinel sB[mB] is entry Tb, the buffers hold TILE + 4
             uint64_t* sB = sA + mAe;
             uint8_t* cB = cA + mAe;
 
@@ -170,11 +174,13 @@ __global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8
             for (int k = 1; k < TEAMS; ++k) epl_w = max(epl_w, __builtin_amdgcn_readlane(epl, k * TL));
 
             wave_sync_lds();  // the previous pairs' tiles are fully consumed
-            {   // stage [A's points | pad | B's points]: entries 2 q and 2 q + 1 of the buffer by lane q % TL in round q / TL; all loads before
-                // the first LDS write.  A pair's second entry may lie one past its list's last point (still inside the environment's slot or,
-                // for the last slot, the workspace's slack): it lands in the pad entry or behind the buffer's used part and is never read.
+            {   // stage [A's points | sentinel, pad | B's points]: entries 2 q and 2 q + 1 of the buffer by lane q % TL in round q / TL; all
+                // loads before the first LDS write.  The pair of entries behind list A's last point reads one or two store entries past that
+                // point, the one that holds list B's last point at most one (still inside the environment's slot or, for the last slot, the
+                // bytes the host's arenas leave behind their last array): they land in the sentinel and pad entries, which are rewritten
+                // below or never read.
                 constexpr int EPL2 = (EPL + 1) / 2;
-                static_assert(2 * TL * EPL2 >= TILE_ + 1, "the rounds cover the buffer's used part (pad entry included)");
+                static_assert(2 * TL * EPL2 >= TILE_ + 2, "the rounds cover the buffer's used part: TILE points, list A's sentinel and pad entries");
                 typedef unsigned long long __attribute__((ext_vector_type(2), aligned(8))) key2_t;
                 const int epl2 = (Tb + 2 * TL - 1) / (2 * TL);
                 int epl2_w = __builtin_amdgcn_readlane(epl2, 0);
@@ -216,6 +222,13 @@ __global__ __launch_bounds__(64 * kSweepWaves, ((CMAX <= 16 && !(WGT && CMAX > 8
                             *reinterpret_cast<uint16_t*>(dc + 2 * TL * u) = (uint16_t)rc[u];
                         }
                     }
+                }
+                // the two sentinels: larger than every key (the bits of a non-negative finite F), so TeamTile's merge needs no test for
+                // the lists' ends.  After the rounds' writes: the staging may have put the store's next entry there, and LDS serves a
+                // wavefront's writes in order.
+                if (tl == 0 && valid) {
+                    sA[mA] = ~0ull;
+                    sB[mB] = ~0ull;
                 }
             }
             wave_sync_lds();

@@ -104,7 +104,8 @@ struct TeamTile {
     static constexpr int LW = LCNT ? (2 * CMAX + 7) / 8 : 1;  // u64 words of a lane's LDS count row ([LW][64] per wavefront)
     static_assert(!PRE || (!LCNT && !WGT && CMAX <= 16), "prefix-count rows: the register-resident forms of up to two count words per side");
 
-    // sA / cA, sB / cB: the two staged lists (mA, mB points; spare entries behind each: the head re-reads may touch one past the end);
+    // sA / cA, sB / cB: the two staged lists (mA, mB points).  sA[mA] and sB[mB] are SENTINELS, ~0ull: larger than every key, so a merge
+    // step that compares the two heads never takes from a list that has ended (the category bytes cA[mA], cB[mB] may hold anything);
     // T = mA + mB; epl = ceil(T / TL); epl_w = the largest epl of the wavefront's teams (wave-uniform trip counts);
     // c0a / c0b: the anchors' categories; F0 = F(0); Finf0 = F(+inf); t_sqrt / t_rsqrt: [NT] tables in LDS; w_s: [32] category
     // weights in LDS (WGT); lcl: this lane's eight bytes of word 0 of the wavefront's count rows (LCNT).
@@ -146,7 +147,7 @@ struct TeamTile {
             }
             // Bytes ra_ * kPreStep + m, m < kPreStep - 1, are read without a clamp.  The byte is a point of the list iff m < qa_ (then
             // ra_ * kPreStep + m < i0 <= mA); every other byte is multiplied by 0 below, and it lies inside the team's buffer whatever
-            // it holds: ra_ * kPreStep + m <= i0 + 2 <= mA + 2, list B's bytes end at most at TILE + 1 + 2, the buffer has TILE + 8.
+            // it holds: ra_ * kPreStep + m <= i0 + 2 <= mA + 2, list B's bytes end at most at TILE + 2 + 2, the buffer has TILE + 8.
             const uint8_t* pa_ = cA + ra_ * kPreStep;
             const uint8_t* pb_ = cB + rb_ * kPreStep;
             uint32_t ta_ = 0u, tb_ = 0u;
@@ -309,21 +310,36 @@ struct TeamTile {
         double Fp = 0.0, Hp = 0.0, local = 0.0;
         // F of the chunk's first event, for the stitching below: known from the heads.  Inside the loop the first event adds
         // (F - 0) * 0 = 0 like any other -- no "first event" selects per event.
-        const double firstF = u2d(((i < i1) & ((j >= j1) | (ka <= kb))) ? ka : kb);
+        // The merge step is ONE compare of the heads.  While a lane has events left, a run that has ended shows by its head alone:
+        // merge_path_fixed puts A first on ties, so A[i1] > B[j1 - 1] strictly and B[j1] >= A[i1 - 1] -- with A's run taken, ka = A[i1]
+        // is larger than every kb the lane still meets, and with B's run taken kb = B[j1] is no smaller than any ka; at the lists' ends
+        // A[mA] and B[mB] are the sentinels.
+        const double firstF = u2d((ka <= kb) ? ka : kb);
+        const int n_ev = d1 - d0;  // this lane's events: the guard compares the scalar trip counter with it
 #pragma unroll 1
         for (int e = 0; e < epl_w; ++e) {
-            if (d0 + e < d1) {
-                // both heads and their categories are re-read after every event (see k_sweep); run ends are tested on the indices
-                const bool takeA = (i < i1) & ((j >= j1) | (ka <= kb));
+            if (e < n_ev) {
+                // both heads and their categories are re-read after every event (see k_sweep)
+                // (the compare's lane mask, handed back as the per-lane condition: every select and both index updates below then use this
+                // ONE 64-bit compare and its scalar complement -- left to itself the compiler derives a `<` for the key select and a `>`
+                // for B's index from it, three 64-bit compares per event; no instruction is emitted for the round trip)
+                const uint64_t take_m = __builtin_amdgcn_ballot_w64(ka <= kb);
+                const bool takeA = __builtin_amdgcn_inverse_ballot_w64(take_m);
                 uint64_t key = takeA ? ka : kb;
                 const unsigned ct = takeA ? cta : ctb;
                 // (the event's key is selected HERE, before the next heads are loaded: the old heads are dead when the loads issue, so the
                 // loads land in the loop-carried registers -- left to itself the compiler sinks the select behind the literal-form
                 // branch and pays two v_mov_b64 per event to rotate the new heads in; no instruction is emitted for this)
                 asm volatile("" : "+v"(key));
-                i += takeA ? 1 : 0;
-                j += takeA ? 0 : 1;
-                ka = sA[i];  // (one past the run's end at most: the buffers have spare entries)
+                // i += takeA, j += !takeA: one add-with-carry each, the compare's mask as the carry, IN the loop-carried registers (the
+                // compiler's own forms are a v_cndmask 0 / 1 and an add per index, or an add-with-carry into a new register and a
+                // v_mov_b32 back)
+                {
+                    uint64_t carry_out;
+                    asm("v_addc_co_u32_e64 %0, %1, 0, %0, %2" : "+v"(i), "=&s"(carry_out) : "s"(take_m));
+                    asm("v_subb_co_u32_e64 %0, %1, %0, -1, %2" : "+v"(j), "=&s"(carry_out) : "s"(take_m));  // j - (-1) - takeA
+                }
+                ka = sA[i];  // (the list's sentinel at most)
                 kb = sB[j];
                 cta = cA[i];
                 ctb = cB[j];
