@@ -365,6 +365,52 @@ int lchd_ensemble_from_coords_periodic_dev(lchd_ctx *ctx, lchd_cloud *cloud, con
                                            const int32_t *d_excl_start, const int32_t *d_excl_idx, const int32_t *d_wf_index,
                                            const double *cells, int32_t n_cells, double *d_out);
 
+/* ---- local composition profiles (additive, not in the reference) -------------------------------------
+ * The quantity a LoCoHD score is the distance of: the weight-function-averaged local composition of ONE environment.  For an environment
+ * sorted by distance, d_0 = 0 (the anchor) <= d_1 <= ... <= d_{n-1}, d_n = +inf, with categories c_k, category weights w and the CDF F of
+ * the anchor's weight function:
+ *   n_c(k) = #{ j <= k : c_j = c },   p_c(k) = w_c n_c(k) / sum_c' w_c' n_c'(k)   (the PMF the sweeps use between d_k and d_{k+1})
+ *   P_c    = sum_{k = 0}^{n-1} (F(d_{k+1}) - F(d_k)) p_c(k)
+ * out is row-major [entries][n_categories] f64, one row per anchor (or dense row) in the caller's order, categories in the order of
+ * lchd_config; a row sums to F(inf) - F(0).  The environment is exactly the one the scoring call of the same name builds for the anchor:
+ * strict radius test, tag pairing rule, the anchor itself, periodic images or minimum-image rows, errors for an atom whose type is not in
+ * the category map (LCHD_EVALUE), anchors outside the structure (LCHD_EPANIC) -- the calls below run the same prologue and environment
+ * kernels on ONE list of anchors (repeated anchors are built once) and hand the store to the profile kernel (lchd_profile.hip)
+ * instead of a sweep.  With the Hellinger distance of exponent 1 (total variation), P_X = (F(inf) - F(0)) - score(this environment, a
+ * lone anchor of category X): tests/test_composition_model.py and tests/test_gpu_composition.py pin the rows to the oracle that way.
+ * Ties in distance carry zero weight, so P does not depend on tie order; under lchd_ctx_set_deterministic a row's bits are a function of
+ * the anchor's environment and the configuration alone (not of the other anchors, the slot size a call ended up with, or earlier calls).
+ * An environment that does not fit its slot repeats the pass with larger slots (every row is written again).  Limits: environments and
+ * dense rows of at most 65 535 points (LCHD_EUNSUPPORTED beyond).  The calls take the context's lock and run on its stream like every
+ * other entry point; device pointers follow the stream rules of lchd_from_primitives_dev (read and written in stream order, d_out
+ * complete on return).  They leave the hints of the scoring passes alone: scores before and after a profile call are the same bits.
+ * With lchd_ctx_enable_timing, "env" of lchd_ctx_last_ms is the environment build (key sets and tie canonicalisation included) and
+ * "sweep" the profile kernel.  Device groups have no profile call. */
+/* Thresholded, device-resident: `cloud` is a single structure, a batch, a frames buffer or an image cloud (periodic boxes / cells);
+ * d_anchors DEVICE int64 [n_anchors] atom indices, d_wf_index DEVICE int32 [n_anchors] or NULL, d_out DEVICE f64 [n_anchors][n_categories].
+ * Uses the configuration of lchd_ctx_set_config. */
+int lchd_composition_primitives_dev(lchd_ctx *ctx, lchd_cloud *cloud, const int64_t *d_anchors, const int32_t *d_wf_index,
+                                    int64_t n_anchors, double threshold_distance, double *d_out);
+/* The same from host arrays (one structure, as one side of lchd_from_primitives); out HOST [n_anchors][n_categories]. */
+int lchd_composition_primitives(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz, const int32_t *cat, const int32_t *tag, int64_t n,
+                                const int64_t *anchors, const int32_t *wf_index, int64_t n_anchors, double threshold_distance, double *out);
+/* ... in an orthorhombic box (HOST [3]) or a triclinic cell (HOST [9]); at most one of the two, both NULL: the call above.  The rules of
+ * lchd_from_primitives_periodic / _cell: reach = the threshold, which the box or cell must allow. */
+int lchd_composition_primitives_periodic(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz, const int32_t *cat, const int32_t *tag,
+                                         int64_t n, const int64_t *anchors, const int32_t *wf_index, int64_t n_anchors,
+                                         double threshold_distance, const double *box, const double *cell, double *out);
+/* Dense rows (lchd_from_coords: row r is the whole structure seen from atom r; no threshold, no tag rule), device-resident single structure;
+ * cell HOST [9] or NULL: minimum-image rows (lchd_cell_reduce, the row producer of lchd_from_coords_periodic).  d_out DEVICE [n][n_categories].
+ * The rows go through the row kernels that materialise the store (never the fused sort-and-sweep kernel). */
+int lchd_composition_coords_dev(lchd_ctx *ctx, lchd_cloud *cloud, const int32_t *d_wf_index, const double *cell, double *d_out);
+/* The same from host arrays: seq [len_seq] categories, xyz [n][3]; out HOST [n][n_categories]. */
+int lchd_composition_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq, int64_t len_seq, const double *xyz, int64_t n,
+                            const int32_t *wf_index, const double *cell, double *out);
+/* Given distance rows (lchd_from_dmxs): dmx HOST row-major [rows][cols], +inf entries allowed, every row must hold a 0; wf_index [rows] or
+ * NULL; out HOST [rows][n_categories]. */
+int lchd_composition_dmx(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq, int64_t len_seq, const double *dmx, int64_t rows,
+                         int64_t cols, const int32_t *wf_index, double *out);
+
 /* ---- multi-GPU ------------------------------------------------------------------------------------
  * The reference's parallelism lives INSIDE the core call: a thread pool that is a field of `LoCoHD` (src/locohd.rs:53,
  * 373-383) runs the anchor pairs of one call (:545-557, order-preserving collect).  The counterpart here is a GROUP of

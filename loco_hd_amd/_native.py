@@ -107,6 +107,12 @@ _PROTOS = {
     "lchd_from_coords_periodic_dev": (C.c_int, [_VP, _VP, _VP, _VP, _DP, _DP, _VP]),
     "lchd_ensemble_from_coords_periodic": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _DP, _i64, _IP, _i64, _IP, _IP, _IP, _DP, _i32, _DP]),
     "lchd_ensemble_from_coords_periodic_dev": (C.c_int, [_VP, _VP, _VP, _i64, _VP, _VP, _VP, _DP, _i32, _VP]),
+    "lchd_composition_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _i64, _f64, _VP]),
+    "lchd_composition_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _DP]),
+    "lchd_composition_primitives_periodic": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _DP, _DP, _DP]),
+    "lchd_composition_coords_dev": (C.c_int, [_VP, _VP, _VP, _DP, _VP]),
+    "lchd_composition_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _DP, _i64, _IP, _DP, _DP]),
+    "lchd_composition_dmx": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _DP, _i64, _i64, _IP, _DP]),
     "lchd_cloud_create": (C.c_int, [_VP, _DP, _IP, _IP, _i64, C.POINTER(_VP)]),
     "lchd_cloud_create_batch": (C.c_int, [_VP, _DP, _IP, _IP, _IP, _i64, _i32, C.POINTER(_VP)]),
     "lchd_cloud_size": (C.c_int64, [_VP]),

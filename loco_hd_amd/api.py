@@ -715,6 +715,76 @@ class LoCoHD:
         pa, pb, interner = self._packed_lists(prim_a, prim_b)
         return self.from_packed(pa, pb, pairs, threshold_distance, wf_index=idx, interner=interner).tolist()
 
+    # ---- local composition profiles (additive) -----------------------------------------------------------
+    # P[a][c] = sum_k (F(d_{k+1}) - F(d_k)) * w_c n_c(k) / sum_c' w_c' n_c'(k) over the sorted environment of anchor a: the
+    # weight-function-averaged local composition a score is the distance of (include/loco_hd_hip.h, "local composition profiles").
+    # Columns follow `categories`; a row sums to F(inf) - F(0).  The environment is the one the scoring call of the same name builds.
+    def _no_device_group_for_composition(self) -> None:
+        if self._devices is not None:
+            raise ValueError("a composition profile applies to one device (a device group has no profile call): drop devices=[...]")
+
+    def composition_from_primitives(self, prims: Sequence[PrimitiveAtom], anchors, threshold_distance: float,
+                                    w_func_keys: Optional[Sequence[str]] = None, *, box=None, cell=None) -> np.ndarray:
+        """Additive: the composition profile of the environment `from_primitives` would build around every anchor (an index into
+        `prims`; repeats allowed), as a float64 array (len(anchors), C).  `w_func_keys`: one key per anchor for a weight-function
+        dictionary (the pairing rules of the scoring calls).  `box` / `cell` (keyword-only): the structure's periodic box (Lx, Ly, Lz)
+        or triclinic cell (3 x 3), as `from_primitives(..., box_a=...)` / `cell_a=...` take them."""
+        if box is not None and cell is not None:
+            raise ValueError("box and cell were both given: a structure has one periodic box or one periodic cell")
+        self._no_device_group_for_composition()
+        thr = float(threshold_distance)
+        bx = None if box is None else periodic_boxes(box, 1, thr, "box")
+        cl = None if cell is None else periodic_cells(cell, 1, thr, "cell")
+        idx_list = [int(a) for a in anchors]
+        if any(a < 0 for a in idx_list):
+            raise OverflowError("can't convert negative int to unsigned")
+        anc = np.asarray(idx_list, dtype=np.int64).reshape(-1)
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], len(anc))
+        pk, _, interner = self._packed_lists(prims, prims)
+        cfg, keep = self._config(interner)
+        out = np.empty((len(anc), len(self._weights)))
+        if len(anc) == 0:
+            return out
+        xyz = _f64(pk.xyz).reshape(-1, 3)
+        if len(anc) and anc.max() >= len(xyz):
+            raise N.PanicException("index out of bounds: an anchor index is outside its structure (src/locohd.rs:521)")
+        N.check(N.lib().lchd_composition_primitives_periodic(self._context(), C.byref(cfg), N.dp(xyz), N.ip(pk.cat), N.ip(pk.tag), len(xyz),
+                                                             N.lp(anc), N.ip(idx), len(anc), thr, N.dp(bx), N.dp(cl), N.dp(out)))
+        return out
+
+    def composition_from_coords(self, seq, coords, w_func_keys: Optional[Sequence[str]] = None, *, box=None, cell=None) -> np.ndarray:
+        """Additive: the composition profile of every dense row `from_coords` would build (row r: the whole structure seen from atom r),
+        as a float64 array (n, C).  `box` / `cell` (keyword-only): minimum-image rows, as `from_coords(..., box_a=...)`."""
+        if box is not None and cell is not None:
+            raise ValueError("box and cell were both given: a structure has one periodic box or one periodic cell")
+        self._no_device_group_for_composition()
+        pc = dense_cells(box, cell, 1, "box", "cell")
+        x = self._coords(coords)
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], len(x))
+        cs = self._cats(list(seq))
+        cfg, keep = self._config()
+        out = np.empty((len(x), len(self._weights)))
+        if len(x) == 0:
+            return out
+        N.check(N.lib().lchd_composition_coords(self._context(), C.byref(cfg), N.ip(cs), cs.size, N.dp(x), len(x), N.ip(idx), N.dp(pc), N.dp(out)))
+        return out
+
+    def composition_from_dmx(self, seq, dmx, w_func_keys: Optional[Sequence[str]] = None) -> np.ndarray:
+        """Additive: the composition profile of every given distance row (`from_dmxs` semantics: row r sorted together with `seq`, +inf
+        entries allowed, every row holds a 0), as a float64 array (rows, C)."""
+        self._no_device_group_for_composition()
+        m, lens = self._matrix(dmx)
+        if lens is not None:
+            raise ValueError("composition_from_dmx takes a rectangular distance matrix (rows of equal length)")
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], m.shape[0])
+        cs = self._cats(list(seq))
+        cfg, keep = self._config()
+        out = np.empty((m.shape[0], len(self._weights)))
+        if m.shape[0] == 0:
+            return out
+        N.check(N.lib().lchd_composition_dmx(self._context(), C.byref(cfg), N.ip(cs), cs.size, N.dp(m), m.shape[0], m.shape[1], N.ip(idx), N.dp(out)))
+        return out
+
     def _no_device_group_with_box(self) -> None:
         if self._devices is not None:
             raise ValueError("a periodic box or cell applies to one device (a device group has no image clouds): drop devices=[...]")

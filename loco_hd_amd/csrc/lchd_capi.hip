@@ -3498,3 +3498,328 @@ extern "C" int lchd_ensemble_from_coords_periodic(lchd_ctx* c, const lchd_config
     MinImageScope scope(c, &mi);
     return lchd_ensemble_from_coords(c, cfg, seq, n, xyz, n_struct, pairs, n_pairs, excl_start, excl_idx, wf_index, out);
 }
+
+// ------------------------------------------------------------------------------------------------
+// local composition profiles (additive, not in the reference): one-sided passes over the environment store
+// ------------------------------------------------------------------------------------------------
+// A profile call builds the environments of ONE list of anchors with the kernels of the scoring passes -- prologue with its anchor
+// de-duplication, k_env_group / k_env_cells, the tie canonicalisation of deterministic mode, the key sets of a weight-function
+// dictionary; dense rows through k_env_rows -- and hands the store to launch_profile instead of a sweep.  It plans with neutral
+// hints and leaves the context's hints alone: the scoring passes before and after it pick their kernels as if it had not run.
+struct CompRequest {
+    lchd_cloud* cl;
+    const int64_t* anchors;  // DEVICE [n] atom indices
+    const int32_t* wf;       // DEVICE [n] or null
+    int64_t n;
+    double thr;
+    double* out;             // DEVICE [n][n_categories]
+};
+
+// One pass with slots of `cap` points: enqueued, waited for; *flags_out = its status words.
+static int comp_prims_pass(lchd_ctx* c, const CompRequest& R, int cap, uint32_t* flags_out) {
+    lchd_cloud* a = R.cl;
+    const int n_wf = c->h_cfg.n_wf;
+    PassQuery q;
+    q.n_a = q.n_b = a->n; q.n_pairs = R.n;
+    q.same_object = true;  // the pair list is (i, i): both columns share one cell list, one set of slots, one store
+    q.has_wf_index = R.wf != nullptr;
+    q.cap = cap;
+    q.n_categories = c->h_cfg.n_categories; q.n_wf = n_wf;
+    q.deterministic = c->deterministic; q.tag_mode = c->h_cfg.tag_mode;
+    q.tune = c->tune;
+    q.tune.no_share = false;
+    PassPlan plan = plan_pass(q);
+    // the profile kernel reads F keys whatever the dictionary's size or the environment kernel: set 0 keeps what the environment kernel
+    // writes (one function: its F values; a dictionary: the distances), k_env_key_sets fills one set per function behind it
+    plan.dict_sets = n_wf > 1;
+    plan.key_sets = n_wf > 1 ? n_wf + 1 : 1;
+    plan.pre_words = 0;
+    const GridPlan ga = plan_grid(a, R.thr, plan.reach);
+    PassBufs pb{};
+    int64_t* pairs = nullptr;
+    for (int dry = 1; dry >= 0; --dry) {
+        Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
+        carve_pass(ar, q, plan, ga.n_cells, ga.n_cells, pb);
+        pairs = ar.take<int64_t>(2 * (size_t)R.n);
+        if (dry) if (int rc = ensure_ws(c, ar.off + 4096)) return rc;
+    }
+    SideBufs &sa = pb.a, &sb = pb.b;
+    sa.env.cdf_keys = sb.env.cdf_keys = plan.dict_sets ? 0 : 1;
+    if (!plan.group) sa.env.cat0 = sb.env.cat0 = nullptr;
+    auto grid_view = [&](const SideBufs& sbuf) {
+        GridView v{};
+        for (int k = 0; k < 3; ++k) { v.min[k] = ga.min[k]; v.inv[k] = ga.inv[k]; v.cell[k] = 1.0 / ga.inv[k]; v.dim[k] = ga.dim[k]; }
+        v.n_cells = ga.n_cells;
+        v.cell_start = sbuf.cell_start; v.rec = sbuf.rec; v.pos_of = sbuf.pos_of;
+        return v;
+    };
+    auto prep_side = [](const CloudView& cv, const GridView& gv, const SideBufs& sbuf) {
+        PrepSide ps{};
+        ps.c = cv; ps.g = gv;
+        ps.cell_start = sbuf.cell_start; ps.rec = sbuf.rec; ps.pos_of = sbuf.pos_of;
+        ps.cell_of = sbuf.cell_of; ps.cell_count = sbuf.cell_count; ps.scan_tmp = sbuf.scan_tmp;
+        ps.flag8 = sbuf.flag8; ps.bits = sbuf.bits; ps.wpre = sbuf.wpre; ps.chunk_base = sbuf.chunk_base; ps.slot = sbuf.slot; ps.uniq = sbuf.uniq;
+        return ps;
+    };
+    const GridView gva = grid_view(sa), gvb = grid_view(sb);
+    const CloudView cv = a->view(plan.cat16);
+    hipStream_t s = c->stream;
+    if (a->ev_ready && a->cap_frames) HIP_TRY(hipStreamWaitEvent(s, a->ev_ready, 0));  // (a frames buffer is filled on another stream)
+    if (int rc = begin_pass(c)) return rc;
+    c->status_dirty = true;  // until the whole pass has been enqueued
+    ++c->n_passes;
+    mark(c, 0);
+    launch_profile_pairs(s, R.anchors, R.n, pairs);
+    (void)launch_prologue(s, c->tune, pairs, R.n, prep_side(cv, gva, sa), prep_side(cv, gvb, sb), pb.zero_base, pb.zero_bytes, c->d_status, true);
+    mark(c, 1);
+    mark(c, 2);
+    const EnvSide esa{cv, gva, sa.uniq, sa.env, plan.max_env_a, sa.raw_key, sa.raw_cat, sa.ovf_list},
+                  esb{cv, gvb, sb.uniq, sb.env, 0, sb.raw_key, sb.raw_cat, sb.ovf_list};
+    if (plan.group) {
+        if (!launch_env_group(s, c->d_cfg, plan.tag_list, plan.group_small, esa, esb, R.thr, plan.apw, c->d_status))
+            return fail(LCHD_EDEVICE, "the grouped environment kernel rejected its launch configuration");
+    } else if (!launch_env_cells(s, cap, c->d_cfg, plan.tag_list, esa, esb, R.thr, c->d_status))
+        return fail(LCHD_EUNSUPPORTED, plan.cat16 ? "with more than 255 categories an environment may hold at most 8192 points (capacity %d asked for)"
+                                                  : "no environment kernel variant with capacity %d", cap);
+    if (c->deterministic) launch_env_canon(s, sa.env, sa.env, plan.max_env_a, 0, c->d_status);
+    EnvStore store = sa.env;
+    if (plan.dict_sets) {
+        launch_env_key_sets(s, c->d_cfg, sa.env, sb.env, n_wf, plan.max_env_a, c->d_status);
+        store.key += store.set_stride;
+        store.cdf_keys = n_wf;
+    }
+    mark(c, 3);
+    ProfileArgs pa{};
+    pa.cfg = c->d_cfg; pa.env = store; pa.anchors = R.anchors; pa.slot = sa.slot; pa.n_atoms = a->n; pa.wf_index = R.wf;
+    pa.n = R.n; pa.out = R.out; pa.hst = c->h_status; pa.n_categories = c->h_cfg.n_categories;
+    launch_profile(s, pa);
+    launch_profile_publish(s, c->d_status, c->h_status, c->seq);
+    mark(c, 4);
+    if (a->ev_used) { HIP_TRY(hipEventRecord(a->ev_used, s)); a->used_valid = true; }
+    HIP_TRY(hipGetLastError());
+    c->status_dirty = false;  // launch_profile_publish leaves the device status clean
+    if (int rc = wait_pass(c, flags_out)) return rc;
+    collect_times(c, 0, 4);
+    return LCHD_OK;
+}
+
+extern "C" int lchd_composition_primitives_dev(lchd_ctx* c, lchd_cloud* cl, const int64_t* d_anchors, const int32_t* d_wf_index,
+                                               int64_t n_anchors, double thr, double* d_out) {
+    CTX_LOCK(c);
+    if (!c || !cl) return fail(LCHD_EVALUE, "null argument");
+    if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    c->last_valid = c->last_sweep_valid = false;
+    if (n_anchors <= 0) return LCHD_OK;
+    if (!d_anchors || !d_out) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    if (n_anchors > (int64_t)0x3FFFFFFF) return fail(LCHD_EUNSUPPORTED, "more than 2^30 - 1 anchors in one call (%lld): split the list", (long long)n_anchors);
+    if (!(thr > 0.0)) return fail(LCHD_EPANIC, "index out of bounds: threshold_distance = %g leaves every environment empty", thr);
+    if (cl->n == 0) return fail(LCHD_EPANIC, "index out of bounds: anchors given for an empty structure");
+    if (thr > cl->reach) return fail(LCHD_EVALUE, "threshold_distance = %g is beyond the reach %g the periodic images were built with", thr, cl->reach);
+    if (!std::isfinite(thr)) thr = 1.7e308;
+    CTX_GUARD(c);
+    if (int rc = resolve_bbox(c, cl)) return rc;
+    const CompRequest R{cl, d_anchors, d_wf_index, n_anchors, thr, d_out};
+    // The retry ladder: an environment that did not fit its slot repeats the pass with slots that hold the largest one reported (a
+    // candidate-table overflow of k_env_group reports a bound; k_env_cells then counts).  Every row is written again: a row's bits do not
+    // depend on the slot size.
+    int cap = kEnvGroupCap;
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        uint32_t f = 0;
+        if (int rc = comp_prims_pass(c, R, cap, &f)) return rc;
+        if ((f & ST_BAD_ANCHOR) || !(f & ST_ENV_OVERFLOW)) return status_to_rc(f & ~(uint32_t)ST_ENV_OVERFLOW, DRV_PRIMS);
+        const HostStatus h = *c->h_status;
+        const int64_t want = std::max<int64_t>(std::max<int64_t>(h.max_env, h.max_bound / 3), cap + 1);
+        if (h.max_env >= (uint32_t)kProfMaxPoints || cap >= kProfMaxPoints)
+            return fail(LCHD_EUNSUPPORTED, "an environment holds %u points; a composition profile takes at most %d", h.max_env, kProfMaxPoints - 1);
+        cap = std::min(next_pow2_host(want), kProfMaxPoints);
+    }
+    return fail(LCHD_EDEVICE, "environment capacity retry did not converge");
+}
+
+// Host arrays, one structure, optionally in an orthorhombic box or a triclinic cell (at most one of the two): the structure goes to the
+// device as a cloud of its own, a periodic one is replaced by its image cloud (reach = the threshold), and the pass is the one above.
+static int composition_primitives_host(lchd_ctx* c, const lchd_config* cfg, const double* xyz, const int32_t* cat, const int32_t* tag,
+                                       int64_t n, const int64_t* anchors, const int32_t* wf_index, int64_t n_anchors, double thr,
+                                       const double* box, const double* cell, double* out) {
+    CTX_LOCK(c);
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (box && cell) return fail(LCHD_EVALUE, "a box and a cell were both given: a structure has one periodic box or one periodic cell");
+    if (int rc = check_wf_index(cfg, wf_index, n_anchors)) return rc;
+    if (n < 0 || n > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "structure size out of range");
+    if (box) if (int rc = lchd_box_validate(box, 1, thr)) return rc;
+    if (cell) if (int rc = lchd_cell_validate(cell, 1, thr)) return rc;
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (n_anchors > 0 && (!anchors || !out)) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    for (int64_t p = 0; p < n_anchors; ++p)  // (an index beyond the structure would name a ghost atom of an image cloud)
+        if (anchors[p] < 0 || anchors[p] >= n)
+            return fail(LCHD_EPANIC, "index out of bounds: an anchor index is outside its structure (src/locohd.rs:521)");
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    if (n_anchors <= 0) return LCHD_OK;
+    lchd_cloud *cl = nullptr, *img = nullptr;
+    char* d_blk = nullptr;
+    const size_t C = (size_t)cfg->n_categories;
+    const size_t o_wf = sizeof(int64_t) * (size_t)n_anchors, o_out = (o_wf + sizeof(int32_t) * (size_t)n_anchors + 255) & ~size_t(255);
+    auto run = [&]() -> int {
+        if (int rc = lchd_cloud_create(c, xyz, cat, tag, n, &cl)) return rc;
+        if (box) if (int rc = lchd_cloud_create_images(c, cl, box, 1, thr, &img)) return rc;
+        if (cell) if (int rc = lchd_cloud_create_images_cell(c, cl, cell, 1, thr, &img)) return rc;
+        HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)n_anchors * C));
+        HIP_TRY(hipMemcpy(d_blk, anchors, o_wf, hipMemcpyHostToDevice));
+        if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)n_anchors, hipMemcpyHostToDevice));
+        if (int rc = lchd_composition_primitives_dev(c, img ? img : cl, reinterpret_cast<const int64_t*>(d_blk),
+                                                     wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, n_anchors, thr,
+                                                     reinterpret_cast<double*>(d_blk + o_out)))
+            return rc;
+        HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)n_anchors * C, hipMemcpyDeviceToHost));
+        return LCHD_OK;
+    };
+    const int rc = run();
+    const std::string msg = g_err;  // (the clean-up below makes calls of its own)
+    for (lchd_cloud* k : {img, cl}) lchd_cloud_destroy(c, k);
+    (void)hipFree(d_blk);
+    if (rc) snprintf(g_err, sizeof g_err, "%s", msg.c_str());
+    return rc;
+}
+extern "C" int lchd_composition_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz, const int32_t* cat, const int32_t* tag,
+                                           int64_t n, const int64_t* anchors, const int32_t* wf_index, int64_t n_anchors, double thr,
+                                           double* out) {
+    return composition_primitives_host(c, cfg, xyz, cat, tag, n, anchors, wf_index, n_anchors, thr, nullptr, nullptr, out);
+}
+extern "C" int lchd_composition_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const double* xyz, const int32_t* cat,
+                                                    const int32_t* tag, int64_t n, const int64_t* anchors, const int32_t* wf_index,
+                                                    int64_t n_anchors, double thr, const double* box, const double* cell, double* out) {
+    return composition_primitives_host(c, cfg, xyz, cat, tag, n, anchors, wf_index, n_anchors, thr, box, cell, out);
+}
+
+// Dense rows of one structure: row r is the whole structure seen from atom r (from_coords) or the given distance row r (from_dmxs).
+// d_m: DEVICE rows [rows][cols], or null: distances from the coordinates of `a`, through the minimum-image row producer with a cell.
+// The rows go through k_env_rows, which materialises the store (the fused sort-and-sweep kernel never writes one).
+static int comp_dense(lchd_ctx* c, const lchd_cloud& a, const double* d_m, int64_t rows, int64_t cols, const MinImageCell* cell,
+                      const int32_t* d_wf, double* d_out) {
+    const int n_wf = c->h_cfg.n_wf;
+    const int cap = next_pow2_host(cols);
+    const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
+    const size_t sets = n_wf > 1 ? (size_t)n_wf + 1 : 1;
+    EnvStore e{};
+    double* w_m = nullptr;
+    for (int dry = 1; dry >= 0; --dry) {
+        Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
+        e.key = ar.take<uint64_t>((size_t)rows * cap * sets);
+        e.cat = ar.take<uint8_t>((size_t)rows * cap * (cat16 ? 2 : 1));
+        e.len = ar.take<int32_t>((size_t)rows);
+        if (cell) w_m = ar.take<double>((size_t)rows * cols);
+        if (dry) if (int rc = ensure_ws(c, ar.off + 4096)) return rc;
+    }
+    e.stride = cap;
+    e.set_stride = (int64_t)rows * cap;
+    e.cat16 = cat16 ? 1 : 0;
+    e.cdf_keys = n_wf == 1 ? 1 : 0;
+    hipStream_t s = c->stream;
+    if (int rc = begin_pass(c)) return rc;
+    c->status_dirty = true;
+    mark(c, 0);
+    if (cell) {
+        launch_min_image_rows(s, a.view(false), 0, (int32_t)cols, rows, *cell, nullptr, cell->v[18] != 0.0, nullptr, nullptr, w_m);
+        d_m = w_m;
+    }
+    mark(c, 1);
+    mark(c, 2);
+    double diag2 = 0.0;  // squared diagonal of the bounding box, with a little headroom
+    for (int k = 0; k < 3; ++k) { const double ext = a.bbmax[k] - a.bbmin[k]; diag2 += ext * ext; }
+    diag2 = diag2 * (1.0 + 1e-9) + 1e-300;
+    if (!launch_env_rows(s, cap, c->d_cfg, a.view(cat16), d_m, cols, rows, cols, diag2, e, c->d_status))
+        return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
+    if (c->deterministic) launch_env_canon(s, e, e, rows, 0, nullptr);
+    if (n_wf > 1) {
+        launch_profile_rows(s, c->d_status, rows);
+        launch_env_key_sets(s, c->d_cfg, e, e, n_wf, rows, c->d_status);
+        e.key += e.set_stride;
+        e.cdf_keys = n_wf;
+    }
+    mark(c, 3);
+    ProfileArgs pa{};
+    pa.cfg = c->d_cfg; pa.env = e; pa.wf_index = d_wf; pa.n = rows; pa.out = d_out; pa.hst = c->h_status; pa.n_categories = c->h_cfg.n_categories;
+    launch_profile(s, pa);
+    launch_profile_publish(s, c->d_status, c->h_status, c->seq);
+    mark(c, 4);
+    HIP_TRY(hipGetLastError());
+    c->status_dirty = false;
+    uint32_t f = 0;
+    if (int rc = wait_pass(c, &f)) return rc;
+    collect_times(c, 0, 4);
+    return status_to_rc(f, DRV_DMXS);
+}
+static int comp_dense_check(lchd_ctx* c, int64_t cols) {
+    if (cols >= kProfMaxPoints)
+        return fail(LCHD_EUNSUPPORTED, "a composition profile takes dense rows of at most %d points (got %lld)", kProfMaxPoints - 1, (long long)cols);
+    return LCHD_OK;
+}
+
+extern "C" int lchd_composition_coords_dev(lchd_ctx* c, lchd_cloud* cl, const int32_t* d_wf_index, const double* cell, double* d_out) {
+    CTX_LOCK(c);
+    if (!c || !cl) return fail(LCHD_EVALUE, "null argument");
+    if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (cl->sid) return fail(LCHD_EVALUE, "from_coords takes single structures, not batches");
+    if (cell && cl->images) return fail(LCHD_EVALUE, "a periodic dense call takes the structures themselves, not their image clouds");
+    MinImageCell rec;
+    if (cell) if (int rc = min_image_record(cell, 0, rec)) return rc;
+    c->last_valid = c->last_sweep_valid = false;
+    if (cl->n == 0) return LCHD_OK;
+    if (!d_out) return fail(LCHD_EVALUE, "null output pointer");
+    if (int rc = comp_dense_check(c, cl->n)) return rc;
+    CTX_GUARD(c);
+    if (int rc = resolve_bbox(c, cl)) return rc;
+    return comp_dense(c, *cl, nullptr, cl->n, cl->n, cell ? &rec : nullptr, d_wf_index, d_out);
+}
+
+// Host arrays: coordinates (xyz set, dmx null; optional cell) or given rows (dmx [rows][cols], xyz null).
+static int composition_dense_host(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t len_seq, const double* xyz, const double* dmx,
+                                  int64_t rows, int64_t cols, const int32_t* wf_index, const double* cell, double* out) {
+    CTX_LOCK(c);
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    MinImageCell rec;
+    if (cell) if (int rc = min_image_record(cell, 0, rec)) return rc;
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    if (int rc = check_wf_index(cfg, wf_index, rows)) return rc;
+    c->last_valid = c->last_sweep_valid = false;
+    if (rows == 0) return LCHD_OK;
+    if (cols > len_seq) return fail(LCHD_EPANIC, "index out of bounds: a distance row is longer than its seq");
+    if (cols == 0) return fail(LCHD_EPANIC, "index out of bounds: empty distance row (src/locohd.rs:74)");
+    if (int rc = comp_dense_check(c, cols)) return rc;
+    if (!out || (!xyz && !dmx)) return fail(LCHD_EVALUE, "null pointer");
+    lchd_cloud* cl = nullptr;
+    char* d_blk = nullptr;
+    const size_t C = (size_t)cfg->n_categories;
+    const size_t o_wf = dmx ? sizeof(double) * (size_t)rows * (size_t)cols : 0, o_out = (o_wf + sizeof(int32_t) * (size_t)rows + 255) & ~size_t(255);
+    auto run = [&]() -> int {
+        if (int rc = lchd_cloud_create(c, xyz, seq, nullptr, cols, &cl)) return rc;  // (given rows: the cloud carries the categories alone)
+        HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)rows * C));
+        if (dmx) HIP_TRY(hipMemcpy(d_blk, dmx, o_wf, hipMemcpyHostToDevice));
+        if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice));
+        if (int rc = comp_dense(c, *cl, dmx ? reinterpret_cast<const double*>(d_blk) : nullptr, rows, cols, cell ? &rec : nullptr,
+                                wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, reinterpret_cast<double*>(d_blk + o_out)))
+            return rc;
+        HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)rows * C, hipMemcpyDeviceToHost));
+        return LCHD_OK;
+    };
+    const int rc = run();
+    const std::string msg = g_err;
+    lchd_cloud_destroy(c, cl);
+    (void)hipFree(d_blk);
+    if (rc) snprintf(g_err, sizeof g_err, "%s", msg.c_str());
+    return rc;
+}
+extern "C" int lchd_composition_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t len_seq, const double* xyz, int64_t n,
+                                       const int32_t* wf_index, const double* cell, double* out) {
+    return composition_dense_host(c, cfg, seq, len_seq, xyz, nullptr, n, n, wf_index, cell, out);
+}
+extern "C" int lchd_composition_dmx(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t len_seq, const double* dmx, int64_t rows,
+                                    int64_t cols, const int32_t* wf_index, double* out) {
+    if (rows > 0 && !dmx) return fail(LCHD_EVALUE, "null pointer");
+    return composition_dense_host(c, cfg, seq, len_seq, nullptr, dmx, rows, cols, wf_index, nullptr, out);
+}

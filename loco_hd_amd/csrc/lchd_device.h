@@ -393,6 +393,26 @@ void launch_env_key_sets(hipStream_t s, const DevConfig* cfg, const EnvStore& ea
 // st != nullptr (from_primitives): the environments in use are DeviceStatus::n_unique (n_a / n_b bound the launch), otherwise exactly
 // n_a / n_b; position 0 takes part (EnvStore::cat0, where there is one, follows it)
 void launch_env_canon(hipStream_t s, const EnvStore& ea, const EnvStore& eb, int64_t n_a, int64_t n_b, const DeviceStatus* st);
+// Local composition profiles (lchd_profile.hip): one row of n_categories doubles per entry, from a store whose keys are F values.
+constexpr int kProfMaxPoints = 65536;  // points of an environment the profile kernel takes (its chunk carries live in LDS)
+struct ProfileArgs {
+    const DevConfig* cfg;
+    EnvStore env;              // cdf_keys >= 1: entry p reads key set wf_index[p]
+    const int64_t* anchors;    // [n] atom indices, or nullptr: entry p is environment p (dense rows)
+    const uint32_t* slot;      // atom -> environment slot (with anchors)
+    int64_t n_atoms;           // bound of the atom indices
+    const int32_t* wf_index;   // [n] or nullptr => 0
+    const int64_t* out_row;    // [n] output row of entry p, or nullptr: row p
+    int64_t n;
+    double* out;               // [rows][n_categories]
+    int32_t n_categories;      // DevConfig::n_categories (the launcher sizes the LDS with it)
+    HostStatus* hst;           // host-mapped mirror: ST_BAD_WF is reported there
+};
+void launch_profile(hipStream_t s, const ProfileArgs& a);
+void launch_profile_pairs(hipStream_t s, const int64_t* anchors, int64_t n, int64_t* pairs);  // pairs[p] = (anchors[p], anchors[p])
+void launch_profile_rows(hipStream_t s, DeviceStatus* st, int64_t n_rows);  // DeviceStatus::n_unique = (n_rows, 0)
+// the end of a pass that has no record pass: status words into the host-mapped mirror, device status reset (publish_status)
+void launch_profile_publish(hipStream_t s, DeviceStatus* st, HostStatus* hst, uint32_t seq);
 void launch_mark_overflow(hipStream_t s, const uint32_t* list_a, uint32_t na, const uint32_t* list_b, uint32_t nb, uint32_t* bits_a, uint32_t* bits_b);
 void launch_count_overflow(hipStream_t s, const OverflowSelect& a, unsigned long long* total);
 void launch_write_overflow(hipStream_t s, const OverflowSelect& a);

@@ -239,6 +239,42 @@ class DeviceSession:
         N.check(N.lib().lchd_from_coords_dev(self._ctx, cloud_a, cloud_b, wf_ptr, C.c_void_p(out.data_ptr())))
         return out
 
+    def composition(self, cloud, anchors, threshold_distance: float, out=None, wf_index=None):
+        """Composition profiles (LoCoHD.composition_from_primitives) of anchors of an uploaded structure, batch, frames buffer or
+        image cloud.  anchors: torch int64 CUDA tensor [P] of global atom indices (repeats allowed); wf_index: torch int32 CUDA tensor
+        [P] or None; returns (or fills) a torch float64 CUDA tensor [P][C] (lchd_composition_primitives_dev)."""
+        torch = self.torch
+        assert anchors.is_cuda and anchors.dtype == torch.int64 and anchors.is_contiguous() and anchors.dim() == 1
+        p, n_cat = anchors.shape[0], int(self._cfg.n_categories)
+        if out is None:
+            out = torch.empty((p, n_cat), dtype=torch.float64, device=anchors.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= p * n_cat
+        wf_ptr = None
+        if wf_index is not None:
+            assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= p
+            wf_ptr = C.c_void_p(wf_index.data_ptr())
+        N.check(N.lib().lchd_composition_primitives_dev(self._ctx, cloud, C.c_void_p(anchors.data_ptr()), wf_ptr, p,
+                                                        float(threshold_distance), C.c_void_p(out.data_ptr())))
+        return out
+
+    def composition_coords(self, cloud, out=None, wf_index=None, *, box=None, cell=None):
+        """Composition profiles of the dense rows of an uploaded structure (LoCoHD.composition_from_coords): returns (or fills) a torch
+        float64 CUDA tensor [n][C].  `box` / `cell` (keyword-only, host arrays): minimum-image rows (lchd_composition_coords_dev)."""
+        if box is not None and cell is not None:
+            raise ValueError("box and cell were both given: a structure has one periodic box or one periodic cell")
+        pc = dense_cells(box, cell, 1, "box", "cell")
+        torch = self.torch
+        n, n_cat = int(N.lib().lchd_cloud_size(cloud)), int(self._cfg.n_categories)
+        if out is None:
+            out = torch.empty((n, n_cat), dtype=torch.float64, device=torch.device("cuda", self.device))
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= n * n_cat
+        wf_ptr = None
+        if wf_index is not None:
+            assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= n
+            wf_ptr = C.c_void_p(wf_index.data_ptr())
+        N.check(N.lib().lchd_composition_coords_dev(self._ctx, cloud, wf_ptr, N.dp(pc), C.c_void_p(out.data_ptr())))
+        return out
+
     def from_coords_ensemble(self, batch, pairs=None, out=None, wf_index=None, excluded=None, *, boxes=None, cells=None):
         """LoCoHD.from_coords_ensemble on a batch from `upload_batch` (structures of equal size) or a frames buffer: row r of
         structure pair p = from_coords(seq, seq, X[i_p], X[j_p])[r].  pairs: torch int32 CUDA tensor [P][2] or None (every
