@@ -1111,7 +1111,7 @@ static void carve_pass(Arena& ar, const PassQuery& q, const PassPlan& plan, int 
         b.env.set_stride = (int64_t)(ne * (size_t)cap);
         b.env.cat = ar.take<uint8_t>(ne * (size_t)cap * (cat16 ? 2 : 1));
         b.env.len = ar.take<int32_t>(ne);
-        b.env.cat0 = (cap == kEnvGroupCap && !cat16) ? ar.take<uint8_t>(ne) : nullptr;  // (written by k_env_group only: prims_enqueue drops it otherwise)
+        b.env.cat0 = (cap == kEnvGroupCap && !cat16) ? ar.take<uint8_t>(ne) : nullptr;  // (written by k_env_group only: build_prims_store drops it otherwise)
         const int pw = plan.pre_words;  // prefix-count rows (k_env_group, configurations of at most 16 categories)
         b.env.pre = pw > 0 ? ar.take<uint64_t>(ne * (size_t)(cap / kPreStep) * (size_t)pw) : nullptr;  // (one row per kPreStep points)
         b.env.pre_words = pw;
@@ -1168,79 +1168,84 @@ static PassQuery pass_query(const lchd_ctx* c) {
     return q;
 }
 
-// Everything of one from_primitives pass: plan -> grids -> workspace -> launches; no host synchronisation (the workspace only grows
-// between passes).
-static int prims_enqueue(lchd_ctx* c) {
-    const auto& R = c->pend.req;
-    auto& L = c->pend.run;
-    ++c->n_passes;
-    lchd_cloud *a = R.a, *b = R.b;
-    const int64_t n_pairs = R.n_pairs;
-    const double thr = R.thr;
-    const int cap = R.cap;
-    const PassQuery q = pass_query(c);
-    const PassPlan plan = c->pend.plan = plan_pass(q);
+// The grid of one side as the kernels read it, and the side as the prologue takes it.
+static GridView grid_view(const GridPlan& g, const SideBufs& s) {
+    GridView v{};
+    for (int k = 0; k < 3; ++k) { v.min[k] = g.min[k]; v.inv[k] = g.inv[k]; v.cell[k] = 1.0 / g.inv[k]; v.dim[k] = g.dim[k]; }
+    v.n_cells = g.n_cells;
+    v.cell_start = s.cell_start;
+    v.rec = s.rec;
+    v.pos_of = s.pos_of;
+    return v;
+}
+static PrepSide prep_side(const CloudView& cv, const GridView& gv, const SideBufs& sbuf) {
+    PrepSide ps{};
+    ps.c = cv; ps.g = gv;
+    ps.cell_start = sbuf.cell_start; ps.rec = sbuf.rec; ps.pos_of = sbuf.pos_of;
+    ps.cell_of = sbuf.cell_of; ps.cell_count = sbuf.cell_count; ps.scan_tmp = sbuf.scan_tmp;
+    ps.flag8 = sbuf.flag8; ps.bits = sbuf.bits; ps.wpre = sbuf.wpre; ps.chunk_base = sbuf.chunk_base; ps.slot = sbuf.slot; ps.uniq = sbuf.uniq;
+    return ps;
+}
+
+// The environment store of one thresholded pass, and what its consumer (a sweep: prims_enqueue; the profile kernel: comp_prims_pass)
+// reads next to it.
+struct PrimsStore {
+    bool begun = false;     // begin_pass has succeeded and the prologue is on the stream: the pass counts, and the members below describe it
+    GridPlan grid[2];
+    PassBufs pb{};          // (pb.a.env / pb.b.env: the stores as the environment kernels wrote them, set 0 first)
+    EnvStore env[2];        // the stores as a consumer reads them: the F sets of a dictionary, else pb's
+    int builds[2] = {0, 0}, dedup[2] = {0, 0};  // launch_prologue's builds_out / dedup_out
+    size_t store_bytes = 0; // keys + categories of both sides
+};
+
+// The front half of a thresholded pass, shared by the scoring pass and the composition pass: grids -> workspace -> prologue ->
+// environment kernel -> tie canonicalisation (deterministic mode) -> key sets of a dictionary; timing marks 0 to 3; no host
+// synchronisation (the workspace only grows between passes).  `plan` is the caller's, amended as it sees fit.
+// pairs: DEVICE [n_pairs][2], or null: the list is (anchors[p], anchors[p]), written into the workspace behind the pass's buffers.
+static int build_prims_store(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* pairs, const int64_t* anchors, int64_t n_pairs,
+                             double thr, const PassQuery& q, const PassPlan& plan, PrimsStore& st) {
     const bool same = plan.same, per_pair = plan.per_pair;
     const int64_t max_env_a = plan.max_env_a, max_env_b = plan.max_env_b;
-    const GridPlan ga = plan_grid(a, thr, plan.reach), gb = plan_grid(b, thr, plan.reach);
-    PassBufs pb{};
-    {
-        Arena dry(nullptr, 0, true);
-        carve_pass(dry, q, plan, ga.n_cells, gb.n_cells, pb);
-        if (int rc = ensure_ws(c, dry.off + 4096)) return rc;
+    const int cap = q.cap;
+    st.grid[0] = plan_grid(a, thr, plan.reach);
+    st.grid[1] = plan_grid(b, thr, plan.reach);
+    const GridPlan &ga = st.grid[0], &gb = st.grid[1];
+    PassBufs& pb = st.pb;
+    int64_t* own_pairs = nullptr;
+    for (int dry = 1; dry >= 0; --dry) {
+        Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
+        carve_pass(ar, q, plan, ga.n_cells, gb.n_cells, pb);
+        if (!pairs) own_pairs = ar.take<int64_t>(2 * (size_t)n_pairs);
+        if (dry) if (int rc = ensure_ws(c, ar.off + 4096)) return rc;
     }
-    Arena ar(c->ws, c->ws_cap, false);
-    carve_pass(ar, q, plan, ga.n_cells, gb.n_cells, pb);
     SideBufs &sa = pb.a, &sb = pb.b;
     sa.env.cdf_keys = sb.env.cdf_keys = plan.dict_sets ? 0 : plan.key_sets;  // (what the environment kernels write into set 0)
     if (!plan.group) sa.env.cat0 = sb.env.cat0 = nullptr;
-
-    auto grid_view = [](const GridPlan& g, const SideBufs& s) {
-        GridView v{};
-        for (int k = 0; k < 3; ++k) { v.min[k] = g.min[k]; v.inv[k] = g.inv[k]; v.cell[k] = 1.0 / g.inv[k]; v.dim[k] = g.dim[k]; }
-        v.n_cells = g.n_cells;
-        v.cell_start = s.cell_start;
-        v.rec = s.rec;
-        v.pos_of = s.pos_of;
-        return v;
-    };
     const GridView gva = grid_view(ga, sa), gvb = grid_view(gb, sb);
     const CloudView cva = a->view(plan.cat16), cvb = b->view(plan.cat16);
     hipStream_t s = c->stream;
     // frames buffers are filled on another stream: order this pass behind their upload
     if (a->ev_ready && a->cap_frames) HIP_TRY(hipStreamWaitEvent(s, a->ev_ready, 0));
-    if (b->ev_ready && b->cap_frames) HIP_TRY(hipStreamWaitEvent(s, b->ev_ready, 0));
+    if (b != a && b->ev_ready && b->cap_frames) HIP_TRY(hipStreamWaitEvent(s, b->ev_ready, 0));
     if (int rc = begin_pass(c)) return rc;
     c->status_dirty = true;  // until the whole pass has been enqueued
+    st.begun = true;
     mark(c, 0);
-    auto prep_side = [](const CloudView& cv, const GridView& gv, const SideBufs& sbuf) {
-        PrepSide ps{};
-        ps.c = cv; ps.g = gv;
-        ps.cell_start = sbuf.cell_start; ps.rec = sbuf.rec; ps.pos_of = sbuf.pos_of;
-        ps.cell_of = sbuf.cell_of; ps.cell_count = sbuf.cell_count; ps.scan_tmp = sbuf.scan_tmp;
-        ps.flag8 = sbuf.flag8; ps.bits = sbuf.bits; ps.wpre = sbuf.wpre; ps.chunk_base = sbuf.chunk_base; ps.slot = sbuf.slot; ps.uniq = sbuf.uniq;
-        return ps;
-    };
+    if (!pairs) {
+        launch_profile_pairs(s, anchors, n_pairs, own_pairs);
+        pairs = own_pairs;
+    }
     {
         PrepSide psa = prep_side(cva, gva, sa), psb = prep_side(cvb, gvb, sb);
         psb.no_anchors = per_pair ? 1 : 0;  // (side B without de-duplication: no flags, no slots -- one environment per pair)
-        int builds[2] = {0, 0};
-        (void)launch_prologue(s, c->tune, R.anchors, n_pairs, psa, psb, pb.zero_base, pb.zero_bytes, c->d_status, same, builds, L.dedup);
-        for (int side = 0; side < 2; ++side) {
-            const GridPlan& g = side ? gb : ga;
-            L.grid[side] = GridRecord{{g.dim[0], g.dim[1], g.dim[2]}, g.n_cells, builds[side]};
-        }
-        if (per_pair) launch_pair_anchor_recs(s, R.anchors, n_pairs, psb, c->d_status);
+        (void)launch_prologue(s, c->tune, pairs, n_pairs, psa, psb, pb.zero_base, pb.zero_bytes, c->d_status, same, st.builds, st.dedup);
+        if (per_pair) launch_pair_anchor_recs(s, pairs, n_pairs, psb, c->d_status);
     }
     mark(c, 1);
     mark(c, 2);  // (cell lists and anchor de-duplication are one phase now; "anchors" reads 0)
     const EnvSide esa{cva, gva, sa.uniq, sa.env, max_env_a, sa.raw_key, sa.raw_cat, sa.ovf_list},
                   esb{cvb, gvb, sb.uniq, sb.env, max_env_b, sb.raw_key, sb.raw_cat, sb.ovf_list};
-    L.ovf_a = sa.ovf_list;
-    L.ovf_b = sb.ovf_list;
-    L.n_slots_a = max_env_a;
-    L.n_slots_b = max_env_b;
-    c->last_store_bytes += (size_t)(std::max<int64_t>(max_env_a, 1) + std::max<int64_t>(max_env_b, 1)) * (size_t)cap * ((plan.cat16 ? 2 : 1) + 8 * (size_t)std::max(plan.key_sets, 1));
+    st.store_bytes = (size_t)(std::max<int64_t>(max_env_a, 1) + std::max<int64_t>(max_env_b, 1)) * (size_t)cap * ((plan.cat16 ? 2 : 1) + 8 * (size_t)std::max(plan.key_sets, 1));
     if (plan.group) {
         if (!launch_env_group(s, c->d_cfg, plan.tag_list, plan.group_small, esa, esb, thr, plan.apw, c->d_status))
             return fail(LCHD_EDEVICE, "the grouped environment kernel rejected its launch configuration");
@@ -1249,22 +1254,54 @@ static int prims_enqueue(lchd_ctx* c) {
                                                   : "no environment kernel variant with capacity %d", cap);
     if (c->deterministic)  // one order among equal keys, whatever order the cell lists' and the buckets' atomics produced (utils.rs:25-39: a stable sort)
         launch_env_canon(s, sa.env, same ? sa.env : sb.env, max_env_a, same ? 0 : max_env_b, c->d_status);
+    st.env[0] = sa.env;
+    st.env[1] = sb.env;
     if (plan.dict_sets) {
         const int n_wf = c->h_cfg.n_wf;
         launch_env_key_sets(s, c->d_cfg, sa.env, sb.env, n_wf, max_env_a + max_env_b, c->d_status);
-        for (SideBufs* sb_ : {&sa, &sb}) {  // the sweeps' view of the store: the F sets
-            sb_->env.key += sb_->env.set_stride;
-            sb_->env.cdf_keys = n_wf;
+        for (EnvStore& e : st.env) {  // a consumer's view of the store: the F sets
+            e.key += e.set_stride;
+            e.cdf_keys = n_wf;
         }
     }
     mark(c, 3);
+    return LCHD_OK;
+}
+
+// Everything of one from_primitives pass: plan -> environment store -> sweep.
+static int prims_enqueue(lchd_ctx* c) {
+    const auto& R = c->pend.req;
+    auto& L = c->pend.run;
+    ++c->n_passes;
+    lchd_cloud *a = R.a, *b = R.b;
+    const int64_t n_pairs = R.n_pairs;
+    const PassQuery q = pass_query(c);
+    const PassPlan plan = c->pend.plan = plan_pass(q);
+    const bool same = plan.same, per_pair = plan.per_pair;
+    PrimsStore st;
+    const int rc = build_prims_store(c, a, b, R.anchors, nullptr, n_pairs, R.thr, q, plan, st);
+    if (st.begun) {
+        for (int side = 0; side < 2; ++side) {
+            const GridPlan& g = st.grid[side];
+            L.grid[side] = GridRecord{{g.dim[0], g.dim[1], g.dim[2]}, g.n_cells, st.builds[side]};
+            L.dedup[side] = st.dedup[side];
+        }
+        L.ovf_a = st.pb.a.ovf_list;
+        L.ovf_b = st.pb.b.ovf_list;
+        L.n_slots_a = plan.max_env_a;
+        L.n_slots_b = plan.max_env_b;
+        c->last_store_bytes += st.store_bytes;
+    }
+    if (rc) return rc;
+    const PassBufs& pb = st.pb;
+    hipStream_t s = c->stream;
     SweepArgs sw{};
     fill_sweep_args(c, sw);
-    sw.env_a = sa.env;
-    sw.env_b = same ? sa.env : sb.env;
+    sw.env_a = st.env[0];
+    sw.env_b = st.env[same ? 0 : 1];
     sw.anchors = R.anchors;
-    sw.slot_a = sa.slot;
-    sw.slot_b = same ? sa.slot : (per_pair ? nullptr : sb.slot);  // (nullptr: side B's slot of pair p is p)
+    sw.slot_a = pb.a.slot;
+    sw.slot_b = same ? pb.a.slot : (per_pair ? nullptr : pb.b.slot);  // (nullptr: side B's slot of pair p is p)
     sw.n_slot_a = a->n;
     sw.n_slot_b = b->n;
     sw.wf_index = R.wf;
@@ -2189,6 +2226,24 @@ extern "C" int lchd_from_primitives(lchd_ctx* c, const lchd_config* cfg, const d
     return host_call_finish(c, hc, nullptr, out);
 }
 
+// What a host-array entry point that runs as a device call holds for its duration: temporary clouds and one device block.  Destroyed
+// on exit (the clouds in the order given); a failed call keeps its own error message, whatever the clean-up's calls report.
+struct HostTemps {
+    lchd_ctx* c;
+    lchd_cloud* clouds[4] = {nullptr, nullptr, nullptr, nullptr};
+    char* d_blk = nullptr;
+    int rc = LCHD_OK;  // the call's result, set by the owner before it returns
+    explicit HostTemps(lchd_ctx* ctx) : c(ctx) {}
+    ~HostTemps() {
+        const std::string msg = g_err;
+        for (lchd_cloud* cl : clouds) lchd_cloud_destroy(c, cl);
+        (void)hipFree(d_blk);
+        if (rc) snprintf(g_err, sizeof g_err, "%s", msg.c_str());
+    }
+    HostTemps(const HostTemps&) = delete;
+    HostTemps& operator=(const HostTemps&) = delete;
+};
+
 // from_primitives in a periodic box: both structures go to the device as clouds of their own, a side with a box is replaced by its
 // image cloud (reach = the threshold) and the pass runs as for any two clouds.  lchd_from_primitives above is untouched.
 // (a side has at most one of box / cell; the public calls below pass one family each)
@@ -2212,8 +2267,9 @@ static int from_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const d
     CTX_GUARD(c);
     if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
     if (n_pairs <= 0) return LCHD_OK;
-    lchd_cloud *ca = nullptr, *cb = nullptr, *ia = nullptr, *ib = nullptr;
-    char* d_blk = nullptr;
+    HostTemps t(c);
+    lchd_cloud *&ia = t.clouds[0], *&ib = t.clouds[1], *&ca = t.clouds[2], *&cb = t.clouds[3];
+    char*& d_blk = t.d_blk;
     const size_t o_wf = sizeof(int64_t) * 2 * (size_t)n_pairs, o_out = (o_wf + sizeof(int32_t) * (size_t)n_pairs + 255) & ~size_t(255);
     auto run = [&]() -> int {
         if (int rc = lchd_cloud_create(c, xyz_a, cat_a, tag_a, n_a, &ca)) return rc;
@@ -2232,14 +2288,10 @@ static int from_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const d
         HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost));
         return LCHD_OK;
     };
-    const int rc = run();
-    const std::string msg = g_err;  // (the clean-up below makes calls of its own)
-    c->last_valid = false;  // the anchors and the clouds of this call go away
+    t.rc = run();
+    c->last_valid = false;  // the anchors and the clouds of this call go away (`t` destroys them on return)
     c->pend.req.a = c->pend.req.b = nullptr;
-    for (lchd_cloud* cl : {ia, ib, ca, cb}) lchd_cloud_destroy(c, cl);
-    (void)hipFree(d_blk);
-    if (rc) snprintf(g_err, sizeof g_err, "%s", msg.c_str());
-    return rc;
+    return t.rc;
 }
 extern "C" int lchd_from_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a,
                                              const int32_t* tag_a, int64_t n_a, const double* xyz_b, const int32_t* cat_b,
@@ -2642,12 +2694,34 @@ static int sweep_rows(lchd_ctx* c, const EnvStore& ea, const EnvStore& eb, const
     return status_to_rc(f, drv);
 }
 
+// Squared diagonal of a cloud's bounding box, with a little headroom: the bound the row kernels take on a squared distance.
+static double diag2(const lchd_cloud& cl) {
+    double s2 = 0.0;
+    for (int k = 0; k < 3; ++k) { const double e = cl.bbmax[k] - cl.bbmin[k]; s2 += e * e; }
+    return s2 * (1.0 + 1e-9) + 1e-300;
+}
+// The store of one side's dense rows: `rows` slots of `cap` points, `sets` key sets (cdf_keys is the caller's).
+static EnvStore carve_row_store(Arena& ar, int64_t rows, int64_t cap, size_t sets, bool cat16) {
+    EnvStore e{};
+    e.key = ar.take<uint64_t>((size_t)rows * cap * sets);
+    e.cat = ar.take<uint8_t>((size_t)rows * cap * (cat16 ? 2 : 1));
+    e.len = ar.take<int32_t>((size_t)rows);
+    e.stride = cap;
+    e.set_stride = rows * cap;
+    e.cat16 = cat16 ? 1 : 0;
+    return e;
+}
+// One side's distance rows from its coordinates into w [rows][n]: minimum-image distances with a cell, else the open ones
+// (k_ens_dist's arithmetic).
+static void produce_rows(hipStream_t s, const lchd_cloud& cl, int64_t n, int64_t rows, const MinImageCell* cell, double* w) {
+    if (cell) launch_min_image_rows(s, cl.view(false), 0, (int32_t)n, rows, *cell, nullptr, cell->v[18] != 0.0, nullptr, nullptr, w);
+    else launch_ens_dist(s, cl.view(false), 0, (int32_t)n, rows, nullptr, nullptr, w);
+}
+
 // One dense pass (from_coords / from_dmxs semantics: pair r = row r of A against row r of B, the environment is the whole
 // structure): row sort of both structures, sweep.  a / b: device-resident structures (coordinates used unless d_ma / d_mb,
 // DEVICE pointers to given distance rows, are set); d_wf: device weight-function indices or nullptr; d_out: device or
 // host-mapped scores.  `retry` reports that a long row defeated the segmented in-LDS sort (repeat with old_rows).
-static bool unit_weights_for_dense(const lchd_ctx* c) { return c->unit_weights; }
-
 static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, const double* d_ma, const double* d_mb, int64_t rows,
                       int64_t cols_a, int64_t cols_b, const int32_t* d_wf, double* d_out, bool old_rows, bool& retry,
                       const double* h_ma = nullptr, const double* h_mb = nullptr, const int32_t* d_len_a = nullptr,
@@ -2656,30 +2730,19 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
     // a periodic dense call: both structures' rows are materialised in the workspace (an open side with k_ens_dist's arithmetic) and
     // the pass runs in its given-row form
     const MinImage* mi = (!d_ma && !d_mb && !h_ma && !h_mb) ? c->min_image : nullptr;
-    auto produce_rows = [&](double* w_a, double* w_b) {
+    auto produce_both = [&](double* w_a, double* w_b) {
         mark(c, 0);
-        for (int side = 0; side < 2; ++side) {
-            const lchd_cloud& cl = side ? b : a;
-            const int64_t n = side ? cols_b : cols_a;
-            double* w = side ? w_b : w_a;
-            if (mi->on[side]) launch_min_image_rows(c->stream, cl.view(false), 0, (int32_t)n, rows, mi->side[side], nullptr, mi->side[side].v[18] != 0.0, nullptr, nullptr, w);
-            else launch_ens_dist(c->stream, cl.view(false), 0, (int32_t)n, rows, nullptr, nullptr, w);
-        }
+        produce_rows(c->stream, a, cols_a, rows, mi->on[0] ? &mi->side[0] : nullptr, w_a);
+        produce_rows(c->stream, b, cols_b, rows, mi->on[1] ? &mi->side[1] : nullptr, w_b);
         mark(c, 1);
     };
     const int cap_a = next_pow2_host(cols_a), cap_b = next_pow2_host(cols_b);
     // more than 255 categories: 16-bit ids in the environment store, k_env_rows<.., uint16_t> + k_sweep_wide<.., CAT16>
     const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
-    const size_t cat_bytes = cat16 ? 2 : 1;
-    auto diag2 = [](const lchd_cloud& cl) {  // squared diagonal of the bounding box, with a little headroom
-        double s2 = 0.0;
-        for (int k = 0; k < 3; ++k) { const double e = cl.bbmax[k] - cl.bbmin[k]; s2 += e * e; }
-        return s2 * (1.0 + 1e-9) + 1e-300;
-    };
     c->last_dense_fused = false;
     // The common configuration (Hellinger-2, unit category weights, <= 16 categories, rows of 1025 .. 20480 points = kDenseFusedMaxRow): sort and
     // sweep in ONE kernel per row pair, nothing but the score is written (lchd_dense_fused.hip).  No environment store.
-    if (!old_rows && !c->tune.no_dense_fused && !cat16 && c->hellinger2 && unit_weights_for_dense(c) &&
+    if (!old_rows && !c->tune.no_dense_fused && !cat16 && c->hellinger2 && c->unit_weights &&
         dense_fused_applies(c->h_cfg.n_categories, cols_a, cols_b)) {
         double* w_ma2 = nullptr;
         double* w_mb2 = nullptr;
@@ -2703,7 +2766,7 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
             d_ma = w_ma2;
             d_mb = w_mb2;
         } else if (mi) {
-            produce_rows(w_ma2, w_mb2);
+            produce_both(w_ma2, w_mb2);
             d_ma = w_ma2;
             d_mb = w_mb2;
         }
@@ -2741,15 +2804,8 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
     int4* d_meta = nullptr;
     for (int dry = 1; dry >= 0; --dry) {
         Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
-        ea.key = ar.take<uint64_t>((size_t)rows * cap_a);
-        ea.cat = ar.take<uint8_t>((size_t)rows * cap_a * cat_bytes);
-        ea.len = ar.take<int32_t>((size_t)rows);
-        ea.stride = cap_a;
-        ea.cat16 = eb.cat16 = cat16 ? 1 : 0;
-        eb.key = ar.take<uint64_t>((size_t)rows * cap_b);
-        eb.cat = ar.take<uint8_t>((size_t)rows * cap_b * cat_bytes);
-        eb.len = ar.take<int32_t>((size_t)rows);
-        eb.stride = cap_b;
+        ea = carve_row_store(ar, rows, cap_a, 1, cat16);
+        eb = carve_row_store(ar, rows, cap_b, 1, cat16);
         ea.cdf_keys = eb.cdf_keys = (c->h_cfg.n_wf == 1 && !c->tune.no_cdf_keys) ? 1 : 0;
         d_meta = ar.take<int4>((size_t)rows);
         if (h_ma || mi) {  // given distance matrices in host memory: straight from the caller's buffers into the workspace
@@ -2765,7 +2821,7 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
         d_ma = w_ma;
         d_mb = w_mb;
     } else if (mi) {
-        produce_rows(w_ma, w_mb);
+        produce_both(w_ma, w_mb);
         d_ma = w_ma;
         d_mb = w_mb;
     }
@@ -3103,9 +3159,7 @@ static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, c
     size_t blk_bytes = 0;
     for (int dry = 1; dry >= 0; --dry) {
         Arena ar(blk, blk_bytes, dry != 0);
-        st.key = ar.take<uint64_t>((size_t)(slots * n + 1) * cap);  // (+1 row: the odd row of a row-sort launch, below)
-        st.cat = ar.take<uint8_t>((size_t)(slots * n + 1) * cap * cat_bytes);
-        st.len = ar.take<int32_t>((size_t)(slots * n + 1));
+        st = carve_row_store(ar, slots * n + 1, cap, 1, cat16);  // (+1 row: the odd row of a row-sort launch, below)
         iota = ar.take<uint32_t>((size_t)(slots * n));
         dmx = ar.take<double>((size_t)(dist_structs * n) * n);
         anchors = ar.take<int64_t>((size_t)q_cap * 2);
@@ -3126,8 +3180,6 @@ static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, c
         char* p;
         ~Release() { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); }
     } release{c, blk};
-    st.stride = cap;
-    st.cat16 = cat16 ? 1 : 0;
     st.cdf_keys = (c->h_cfg.n_wf == 1 && !c->tune.no_cdf_keys) ? 1 : 0;
     hipStream_t s = c->stream;
     launch_ens_iota(s, iota, slots * n);
@@ -3502,10 +3554,9 @@ extern "C" int lchd_ensemble_from_coords_periodic(lchd_ctx* c, const lchd_config
 // ------------------------------------------------------------------------------------------------
 // local composition profiles (additive, not in the reference): one-sided passes over the environment store
 // ------------------------------------------------------------------------------------------------
-// A profile call builds the environments of ONE list of anchors with the kernels of the scoring passes -- prologue with its anchor
-// de-duplication, k_env_group / k_env_cells, the tie canonicalisation of deterministic mode, the key sets of a weight-function
-// dictionary; dense rows through k_env_rows -- and hands the store to launch_profile instead of a sweep.  It plans with neutral
-// hints and leaves the context's hints alone: the scoring passes before and after it pick their kernels as if it had not run.
+// A profile call builds the environments of ONE list of anchors with the builder of the scoring passes (build_prims_store; dense rows:
+// carve_row_store + k_env_rows) and hands the store to launch_profile instead of a sweep.  It plans with neutral hints and leaves the
+// context's hints and records alone: the scoring passes before and after it pick their kernels as if it had not run.
 struct CompRequest {
     lchd_cloud* cl;
     const int64_t* anchors;  // DEVICE [n] atom indices
@@ -3534,63 +3585,13 @@ static int comp_prims_pass(lchd_ctx* c, const CompRequest& R, int cap, uint32_t*
     plan.dict_sets = n_wf > 1;
     plan.key_sets = n_wf > 1 ? n_wf + 1 : 1;
     plan.pre_words = 0;
-    const GridPlan ga = plan_grid(a, R.thr, plan.reach);
-    PassBufs pb{};
-    int64_t* pairs = nullptr;
-    for (int dry = 1; dry >= 0; --dry) {
-        Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
-        carve_pass(ar, q, plan, ga.n_cells, ga.n_cells, pb);
-        pairs = ar.take<int64_t>(2 * (size_t)R.n);
-        if (dry) if (int rc = ensure_ws(c, ar.off + 4096)) return rc;
-    }
-    SideBufs &sa = pb.a, &sb = pb.b;
-    sa.env.cdf_keys = sb.env.cdf_keys = plan.dict_sets ? 0 : 1;
-    if (!plan.group) sa.env.cat0 = sb.env.cat0 = nullptr;
-    auto grid_view = [&](const SideBufs& sbuf) {
-        GridView v{};
-        for (int k = 0; k < 3; ++k) { v.min[k] = ga.min[k]; v.inv[k] = ga.inv[k]; v.cell[k] = 1.0 / ga.inv[k]; v.dim[k] = ga.dim[k]; }
-        v.n_cells = ga.n_cells;
-        v.cell_start = sbuf.cell_start; v.rec = sbuf.rec; v.pos_of = sbuf.pos_of;
-        return v;
-    };
-    auto prep_side = [](const CloudView& cv, const GridView& gv, const SideBufs& sbuf) {
-        PrepSide ps{};
-        ps.c = cv; ps.g = gv;
-        ps.cell_start = sbuf.cell_start; ps.rec = sbuf.rec; ps.pos_of = sbuf.pos_of;
-        ps.cell_of = sbuf.cell_of; ps.cell_count = sbuf.cell_count; ps.scan_tmp = sbuf.scan_tmp;
-        ps.flag8 = sbuf.flag8; ps.bits = sbuf.bits; ps.wpre = sbuf.wpre; ps.chunk_base = sbuf.chunk_base; ps.slot = sbuf.slot; ps.uniq = sbuf.uniq;
-        return ps;
-    };
-    const GridView gva = grid_view(sa), gvb = grid_view(sb);
-    const CloudView cv = a->view(plan.cat16);
+    PrimsStore st;
+    const int built = build_prims_store(c, a, a, nullptr, R.anchors, R.n, R.thr, q, plan, st);
+    if (st.begun) ++c->n_passes;
+    if (built) return built;
     hipStream_t s = c->stream;
-    if (a->ev_ready && a->cap_frames) HIP_TRY(hipStreamWaitEvent(s, a->ev_ready, 0));  // (a frames buffer is filled on another stream)
-    if (int rc = begin_pass(c)) return rc;
-    c->status_dirty = true;  // until the whole pass has been enqueued
-    ++c->n_passes;
-    mark(c, 0);
-    launch_profile_pairs(s, R.anchors, R.n, pairs);
-    (void)launch_prologue(s, c->tune, pairs, R.n, prep_side(cv, gva, sa), prep_side(cv, gvb, sb), pb.zero_base, pb.zero_bytes, c->d_status, true);
-    mark(c, 1);
-    mark(c, 2);
-    const EnvSide esa{cv, gva, sa.uniq, sa.env, plan.max_env_a, sa.raw_key, sa.raw_cat, sa.ovf_list},
-                  esb{cv, gvb, sb.uniq, sb.env, 0, sb.raw_key, sb.raw_cat, sb.ovf_list};
-    if (plan.group) {
-        if (!launch_env_group(s, c->d_cfg, plan.tag_list, plan.group_small, esa, esb, R.thr, plan.apw, c->d_status))
-            return fail(LCHD_EDEVICE, "the grouped environment kernel rejected its launch configuration");
-    } else if (!launch_env_cells(s, cap, c->d_cfg, plan.tag_list, esa, esb, R.thr, c->d_status))
-        return fail(LCHD_EUNSUPPORTED, plan.cat16 ? "with more than 255 categories an environment may hold at most 8192 points (capacity %d asked for)"
-                                                  : "no environment kernel variant with capacity %d", cap);
-    if (c->deterministic) launch_env_canon(s, sa.env, sa.env, plan.max_env_a, 0, c->d_status);
-    EnvStore store = sa.env;
-    if (plan.dict_sets) {
-        launch_env_key_sets(s, c->d_cfg, sa.env, sb.env, n_wf, plan.max_env_a, c->d_status);
-        store.key += store.set_stride;
-        store.cdf_keys = n_wf;
-    }
-    mark(c, 3);
     ProfileArgs pa{};
-    pa.cfg = c->d_cfg; pa.env = store; pa.anchors = R.anchors; pa.slot = sa.slot; pa.n_atoms = a->n; pa.wf_index = R.wf;
+    pa.cfg = c->d_cfg; pa.env = st.env[0]; pa.anchors = R.anchors; pa.slot = st.pb.a.slot; pa.n_atoms = a->n; pa.wf_index = R.wf;
     pa.n = R.n; pa.out = R.out; pa.hst = c->h_status; pa.n_categories = c->h_cfg.n_categories;
     launch_profile(s, pa);
     launch_profile_publish(s, c->d_status, c->h_status, c->seq);
@@ -3657,8 +3658,9 @@ static int composition_primitives_host(lchd_ctx* c, const lchd_config* cfg, cons
     CTX_GUARD(c);
     if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
     if (n_anchors <= 0) return LCHD_OK;
-    lchd_cloud *cl = nullptr, *img = nullptr;
-    char* d_blk = nullptr;
+    HostTemps t(c);
+    lchd_cloud *&img = t.clouds[0], *&cl = t.clouds[1];
+    char*& d_blk = t.d_blk;
     const size_t C = (size_t)cfg->n_categories;
     const size_t o_wf = sizeof(int64_t) * (size_t)n_anchors, o_out = (o_wf + sizeof(int32_t) * (size_t)n_anchors + 255) & ~size_t(255);
     auto run = [&]() -> int {
@@ -3675,12 +3677,7 @@ static int composition_primitives_host(lchd_ctx* c, const lchd_config* cfg, cons
         HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)n_anchors * C, hipMemcpyDeviceToHost));
         return LCHD_OK;
     };
-    const int rc = run();
-    const std::string msg = g_err;  // (the clean-up below makes calls of its own)
-    for (lchd_cloud* k : {img, cl}) lchd_cloud_destroy(c, k);
-    (void)hipFree(d_blk);
-    if (rc) snprintf(g_err, sizeof g_err, "%s", msg.c_str());
-    return rc;
+    return t.rc = run();
 }
 extern "C" int lchd_composition_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz, const int32_t* cat, const int32_t* tag,
                                            int64_t n, const int64_t* anchors, const int32_t* wf_index, int64_t n_anchors, double thr,
@@ -3706,30 +3703,22 @@ static int comp_dense(lchd_ctx* c, const lchd_cloud& a, const double* d_m, int64
     double* w_m = nullptr;
     for (int dry = 1; dry >= 0; --dry) {
         Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
-        e.key = ar.take<uint64_t>((size_t)rows * cap * sets);
-        e.cat = ar.take<uint8_t>((size_t)rows * cap * (cat16 ? 2 : 1));
-        e.len = ar.take<int32_t>((size_t)rows);
+        e = carve_row_store(ar, rows, cap, sets, cat16);
         if (cell) w_m = ar.take<double>((size_t)rows * cols);
         if (dry) if (int rc = ensure_ws(c, ar.off + 4096)) return rc;
     }
-    e.stride = cap;
-    e.set_stride = (int64_t)rows * cap;
-    e.cat16 = cat16 ? 1 : 0;
     e.cdf_keys = n_wf == 1 ? 1 : 0;
     hipStream_t s = c->stream;
     if (int rc = begin_pass(c)) return rc;
     c->status_dirty = true;
     mark(c, 0);
     if (cell) {
-        launch_min_image_rows(s, a.view(false), 0, (int32_t)cols, rows, *cell, nullptr, cell->v[18] != 0.0, nullptr, nullptr, w_m);
+        produce_rows(s, a, cols, rows, cell, w_m);
         d_m = w_m;
     }
     mark(c, 1);
     mark(c, 2);
-    double diag2 = 0.0;  // squared diagonal of the bounding box, with a little headroom
-    for (int k = 0; k < 3; ++k) { const double ext = a.bbmax[k] - a.bbmin[k]; diag2 += ext * ext; }
-    diag2 = diag2 * (1.0 + 1e-9) + 1e-300;
-    if (!launch_env_rows(s, cap, c->d_cfg, a.view(cat16), d_m, cols, rows, cols, diag2, e, c->d_status))
+    if (!launch_env_rows(s, cap, c->d_cfg, a.view(cat16), d_m, cols, rows, cols, diag2(a), e, c->d_status))
         return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
     if (c->deterministic) launch_env_canon(s, e, e, rows, 0, nullptr);
     if (n_wf > 1) {
@@ -3792,8 +3781,9 @@ static int composition_dense_host(lchd_ctx* c, const lchd_config* cfg, const int
     if (cols == 0) return fail(LCHD_EPANIC, "index out of bounds: empty distance row (src/locohd.rs:74)");
     if (int rc = comp_dense_check(c, cols)) return rc;
     if (!out || (!xyz && !dmx)) return fail(LCHD_EVALUE, "null pointer");
-    lchd_cloud* cl = nullptr;
-    char* d_blk = nullptr;
+    HostTemps t(c);
+    lchd_cloud*& cl = t.clouds[0];
+    char*& d_blk = t.d_blk;
     const size_t C = (size_t)cfg->n_categories;
     const size_t o_wf = dmx ? sizeof(double) * (size_t)rows * (size_t)cols : 0, o_out = (o_wf + sizeof(int32_t) * (size_t)rows + 255) & ~size_t(255);
     auto run = [&]() -> int {
@@ -3807,12 +3797,7 @@ static int composition_dense_host(lchd_ctx* c, const lchd_config* cfg, const int
         HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)rows * C, hipMemcpyDeviceToHost));
         return LCHD_OK;
     };
-    const int rc = run();
-    const std::string msg = g_err;
-    lchd_cloud_destroy(c, cl);
-    (void)hipFree(d_blk);
-    if (rc) snprintf(g_err, sizeof g_err, "%s", msg.c_str());
-    return rc;
+    return t.rc = run();
 }
 extern "C" int lchd_composition_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t len_seq, const double* xyz, int64_t n,
                                        const int32_t* wf_index, const double* cell, double* out) {

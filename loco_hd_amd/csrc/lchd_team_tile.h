@@ -127,7 +127,7 @@ struct TeamTile {
         const int i1 = merge_path_fixed(sA, mA, sB, mB, d1, mw_w);
         int i0 = __builtin_amdgcn_update_dpp(i1, i1, 0x138, 0xf, 0xf, false);  // wave_shr:1
         if (tl == 0) i0 = 0;
-        const int j0 = d0 - i0, j1 = d1 - i1;
+        const int j0 = d0 - i0;
 
         uint64_t exA[NW], exB[NW];
         if constexpr (PRE) {
