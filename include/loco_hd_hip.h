@@ -411,6 +411,60 @@ int lchd_composition_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t
 int lchd_composition_dmx(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq, int64_t len_seq, const double *dmx, int64_t rows,
                          int64_t cols, const int32_t *wf_index, double *out);
 
+/* ---- radial score profiles (additive, not in the reference) -------------------------------------------
+ * A LoCoHD score is one number per anchor pair, S = integral of w(r) H(A(r), B(r)) dr.  A radial profile resolves that integrand over
+ * distance bins.  Edges e_0 < e_1 < ... < e_K (K >= 1, e_0 >= 0, all finite except that e_K may be +inf, at most 64 bins).  For a pair
+ * with merged breakpoints u_0 = 0 <= u_1 <= ... <= u_J (the distances of the points of both environments), u_{J+1} = +inf, and H_j the
+ * statistical distance of the two PMFs between u_j and u_{j+1} -- exactly what the scoring call integrates, the anchors included:
+ *   out[p][k] = sum_j H_j * max(0, min(F(u_{j+1}), F(e_{k+1})) - max(F(u_j), F(e_k)))
+ * with F the CDF of the pair's weight function (wf_index picks it per pair, as in the scoring calls).  out is row-major [pairs][K] f64.
+ *   - with e_0 = 0 and e_K = +inf a row sums to the pair's score
+ *   - the last bin carries the tail (F(inf) - F(u_J)) H_J beyond the threshold when e_K = +inf, as the reference's definition does
+ *   - a bin that does not overlap the weight function's support is exactly 0.0
+ *   - mass below e_0 or above a finite e_K is dropped
+ *   - ties have zero width: the result does not depend on tie order when H is finite
+ * With bins on a fine grid and a uniform weight function the output is the integral of H per bin, and the score under ANY
+ * piecewise-constant weight function on that grid is a dot product on the host: the pairs never need rescoring.
+ * The environments are exactly those of the scoring call of the same name (strict radius test, tag pairing rule, periodic images or
+ * minimum-image rows) and so are the errors (LCHD_EPANIC for an anchor outside its structure, LCHD_EVALUE for a type outside the
+ * category map, ...), plus LCHD_EVALUE for bad edges.  The kernel (lchd_radial.hip) works in key space: the bin bounds F(e_k) are
+ * computed on the device with the routine that writes the stores' keys, so a point at distance exactly e_k falls on the bound bit for
+ * bit.  Every sum has a fixed shape and there are no floating-point atomics: under lchd_ctx_set_deterministic a row's bits depend on
+ * the pair, the configuration and the edges alone.  An environment that does not fit its slot repeats the whole pass with larger slots.
+ * Limits: at most 512 categories, environments and rows of at most 65 535 points (LCHD_EUNSUPPORTED beyond).  The calls take the
+ * context's lock and run on its stream; device pointers follow the stream rules of lchd_from_primitives_dev (d_out complete on return).
+ * They leave the hints of the scoring passes and lchd_ctx_last_sweep alone: scores before and after a radial call are the same bits.
+ * With lchd_ctx_enable_timing, "env" of lchd_ctx_last_ms is the store build and "sweep" the pair records plus the radial kernel.
+ * Device groups have no radial call. */
+/* Host only, no device: LCHD_EVALUE for fewer than 2 or more than 65 edges, a negative or NaN edge, edges that do not ascend strictly,
+ * +inf anywhere but last. */
+int lchd_radial_validate(const double *edges, int32_t n_edges);
+/* Thresholded, device-resident: a / b as lchd_from_primitives_dev takes them (single structures, batches, frames buffers, image
+ * clouds); d_anchors DEVICE int64 [n_pairs][2], d_wf_index DEVICE int32 [n_pairs] or NULL, edges HOST [n_edges], d_out DEVICE f64
+ * [n_pairs][n_edges - 1].  Uses the configuration of lchd_ctx_set_config. */
+int lchd_radial_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors, const int32_t *d_wf_index,
+                               int64_t n_pairs, double threshold_distance, const double *edges, int32_t n_edges, double *d_out);
+/* The same from host arrays (both sides as lchd_from_primitives).  box_x HOST [3] / cell_x HOST [9]: the periodic box or cell of a side
+ * (at most one of the two per side, NULL: open), by the rules of lchd_from_primitives_periodic / _cell.  out HOST [n_pairs][n_edges - 1]. */
+int lchd_radial_primitives(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a, const int32_t *tag_a, int64_t n_a,
+                           const double *xyz_b, const int32_t *cat_b, const int32_t *tag_b, int64_t n_b, const int64_t *anchors,
+                           const int32_t *wf_index, int64_t n_pairs, double threshold_distance, const double *box_a, const double *cell_a,
+                           const double *box_b, const double *cell_b, const double *edges, int32_t n_edges, double *out);
+/* Dense rows (lchd_from_coords: pair r = atom r of a against atom r of b, the environments are the whole structures), device-resident
+ * single structures of equal size; cell_x HOST [9] or NULL: minimum-image rows.  d_out DEVICE [n][n_edges - 1].  The rows go through
+ * the row kernels that materialise the stores (never the fused sort-and-sweep kernel). */
+int lchd_radial_coords_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, const double *cell_a, const double *cell_b,
+                           const double *edges, int32_t n_edges, double *d_out);
+/* The same from host arrays, as lchd_from_coords takes them; out HOST [n][n_edges - 1]. */
+int lchd_radial_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b, int64_t len_seq_b,
+                       const double *xyz_a, int64_t n_a, const double *xyz_b, int64_t n_b, const int32_t *wf_index, const double *cell_a,
+                       const double *cell_b, const double *edges, int32_t n_edges, double *out);
+/* Given distance rows (lchd_from_dmxs): dmx_x HOST row-major [rows][cols_x], +inf entries allowed, every row must hold a 0; wf_index
+ * [rows] or NULL; out HOST [rows][n_edges - 1]. */
+int lchd_radial_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b, int64_t len_seq_b,
+                     const double *dmx_a, const double *dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b, const int32_t *wf_index,
+                     const double *edges, int32_t n_edges, double *out);
+
 /* ---- multi-GPU ------------------------------------------------------------------------------------
  * The reference's parallelism lives INSIDE the core call: a thread pool that is a field of `LoCoHD` (src/locohd.rs:53,
  * 373-383) runs the anchor pairs of one call (:545-557, order-preserving collect).  The counterpart here is a GROUP of

@@ -785,6 +785,95 @@ class LoCoHD:
         N.check(N.lib().lchd_composition_dmx(self._context(), C.byref(cfg), N.ip(cs), cs.size, N.dp(m), m.shape[0], m.shape[1], N.ip(idx), N.dp(out)))
         return out
 
+    # ---- radial score profiles (additive) ----------------------------------------------------------------
+    # R[p][k] = sum_j H_j * |[F(u_j), F(u_{j+1})] n [F(e_k), F(e_{k+1})]| over the merged breakpoints u_j of pair p: the integrand of the
+    # pair's score resolved over the distance bins `edges` (include/loco_hd_hip.h, "radial score profiles").  With edges[0] = 0 and
+    # edges[-1] = inf a row sums to the pair's score.
+    @staticmethod
+    def _radial_edges(edges) -> np.ndarray:
+        """The edges as a float64 array, checked on the host (lchd_radial_validate: ValueError before any device is touched)."""
+        ed = np.ascontiguousarray(np.asarray(list(edges) if not isinstance(edges, np.ndarray) else edges, dtype=np.float64).reshape(-1))
+        N.check(N.lib().lchd_radial_validate(N.dp(ed), len(ed)))
+        return ed
+
+    def _no_device_group_for_radial(self) -> None:
+        if self._devices is not None:
+            raise ValueError("a radial profile applies to one device (a device group has no radial call): drop devices=[...]")
+
+    def radial_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                               threshold_distance: float, edges, *, box_a=None, box_b=None, cell_a=None, cell_b=None) -> np.ndarray:
+        """Additive: the radial profile of every anchor pair `from_primitives` would score, as a float64 array (P, K) for K + 1
+        `edges` (ascending distances, the first >= 0, the last may be inf; at most 64 bins).  Bin k holds the part of the pair's score
+        that the distances between edges[k] and edges[k + 1] contribute; with edges[0] = 0 and edges[-1] = inf a row sums to the score.
+        `anchor_pairs`, `box_a` / `box_b` / `cell_a` / `cell_b`: as `from_primitives` takes them."""
+        ed = self._radial_edges(edges)
+        for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+            if box is not None and cell is not None:
+                raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
+        self._no_device_group_for_radial()
+        thr = float(threshold_distance)
+        ba = None if box_a is None else periodic_boxes(box_a, 1, thr, "box_a")
+        bb = None if box_b is None else periodic_boxes(box_b, 1, thr, "box_b")
+        ca = None if cell_a is None else periodic_cells(cell_a, 1, thr, "cell_a")
+        cb = None if cell_b is None else periodic_cells(cell_b, 1, thr, "cell_b")
+        pairs, idx = self._anchor_arrays(anchor_pairs)
+        pa, pb, interner = self._packed_lists(prim_a, prim_b)
+        anchors = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        cfg, keep = self._config(interner)
+        out = np.empty((len(anchors), len(ed) - 1))
+        if len(anchors) == 0:
+            return out
+        xa, xb = _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3)
+        N.check(N.lib().lchd_radial_primitives(self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa), N.dp(xb),
+                                               N.ip(pb.cat), N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx), len(anchors), thr, N.dp(ba),
+                                               N.dp(ca), N.dp(bb), N.dp(cb), N.dp(ed), len(ed), N.dp(out)))
+        return out
+
+    def radial_from_coords(self, seq_a, seq_b, coords_a, coords_b, edges, w_func_keys: Optional[Sequence[str]] = None, *, box_a=None,
+                           box_b=None, cell_a=None, cell_b=None) -> np.ndarray:
+        """Additive: the radial profile of every dense row pair `from_coords` would score (pair r: the two structures seen from their
+        atoms r), as a float64 array (n, K).  `box_a` / `box_b` / `cell_a` / `cell_b` (keyword-only): minimum-image rows, as
+        `from_coords(..., box_a=...)`."""
+        ed = self._radial_edges(edges)
+        for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+            if box is not None and cell is not None:
+                raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
+        self._no_device_group_for_radial()
+        pc_a = dense_cells(box_a, cell_a, 1, "box_a", "cell_a")
+        pc_b = dense_cells(box_b, cell_b, 1, "box_b", "cell_b")
+        xa, xb = self._coords(coords_a), self._coords(coords_b)
+        if len(xa) != len(xb):
+            raise ValueError(f"Expected matrices with the same length, got lengths {len(xa)} and {len(xb)}!")
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], len(xa))
+        ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
+        cfg, keep = self._config()
+        out = np.empty((len(xa), len(ed) - 1))
+        if len(xa) == 0:
+            return out
+        N.check(N.lib().lchd_radial_coords(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(xa), len(xa), N.dp(xb),
+                                           len(xb), N.ip(idx), N.dp(pc_a), N.dp(pc_b), N.dp(ed), len(ed), N.dp(out)))
+        return out
+
+    def radial_from_dmxs(self, seq_a, seq_b, dmx_a, dmx_b, edges, w_func_keys: Optional[Sequence[str]] = None) -> np.ndarray:
+        """Additive: the radial profile of every row pair `from_dmxs` would score (rectangular matrices with the same number of rows,
+        +inf entries allowed, every row holds a 0), as a float64 array (rows, K)."""
+        ed = self._radial_edges(edges)
+        self._no_device_group_for_radial()
+        (ma, la), (mb, lb) = self._matrix(dmx_a), self._matrix(dmx_b)
+        if la is not None or lb is not None:
+            raise ValueError("radial_from_dmxs takes rectangular distance matrices (rows of equal length)")
+        if ma.shape[0] != mb.shape[0]:
+            raise ValueError(f"Expected matrices with the same length, got lengths {ma.shape[0]} and {mb.shape[0]}!")
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], ma.shape[0])
+        ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
+        cfg, keep = self._config()
+        out = np.empty((ma.shape[0], len(ed) - 1))
+        if ma.shape[0] == 0:
+            return out
+        N.check(N.lib().lchd_radial_dmxs(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(ma), N.dp(mb), ma.shape[0],
+                                         ma.shape[1], mb.shape[1], N.ip(idx), N.dp(ed), len(ed), N.dp(out)))
+        return out
+
     def _no_device_group_with_box(self) -> None:
         if self._devices is not None:
             raise ValueError("a periodic box or cell applies to one device (a device group has no image clouds): drop devices=[...]")

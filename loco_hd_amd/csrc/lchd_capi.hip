@@ -21,6 +21,7 @@
 #include "../../include/loco_hd_hip.h"
 #include "lchd_device.h"
 #include "lchd_math.h"
+#include "lchd_radial_bins.h"
 
 using namespace lchd;
 
@@ -266,6 +267,8 @@ struct lchd_ctx {
     // second pass over the pairs of overflowed environments (lchd_ctx_finish): grow-only device blocks outside the arena
     char *d_ovf_bits = nullptr, *d_ovf_lists = nullptr;
     size_t ovf_bits_cap = 0, ovf_lists_cap = 0;
+    char* d_radial_bounds = nullptr;  // radial profiles: [n_wf][edges] bin bounds in key space (grow-only, outside the arena: the store builders lay the arena out)
+    size_t radial_bounds_cap = 0;
     int64_t n_subset_passes = 0;    // second passes run so far
     size_t last_store_bytes = 0;    // environment-store bytes (keys + categories, both sides) of the passes of the last from_primitives call
     int64_t n_passes = 0;           // from_primitives passes enqueued so far (a call is one pass unless a capacity / launch-set retry repeats it)
@@ -498,6 +501,7 @@ extern "C" void lchd_ctx_destroy(lchd_ctx* c) {
     (void)hipFree(c->d_io);
     (void)hipFree(c->d_ovf_bits);
     (void)hipFree(c->d_ovf_lists);
+    (void)hipFree(c->d_radial_bounds);
     (void)hipFree(c->d_shard);
     (void)hipFree(c->d_bad);
     if (c->shard_stream) (void)hipStreamDestroy(c->shard_stream);
@@ -3807,4 +3811,357 @@ extern "C" int lchd_composition_dmx(lchd_ctx* c, const lchd_config* cfg, const i
                                     int64_t cols, const int32_t* wf_index, double* out) {
     if (rows > 0 && !dmx) return fail(LCHD_EVALUE, "null pointer");
     return composition_dense_host(c, cfg, seq, len_seq, nullptr, dmx, rows, cols, wf_index, nullptr, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// radial score profiles (additive, not in the reference): a pair's integrand resolved over distance bins
+// ------------------------------------------------------------------------------------------------
+// A radial call builds the environments of a pair list with the builders of the scoring passes (build_prims_store; dense rows:
+// carve_row_store + produce_rows + k_env_rows), runs the record pass (k_pair_meta, which also hands the status over) and gives stores
+// and records to launch_radial instead of a sweep.  Like a composition call it plans with neutral hints and leaves the context's hints
+// and sweep record alone: the scoring passes before and after it pick their kernels as if it had not run.
+extern "C" int lchd_radial_validate(const double* edges, int32_t n_edges) {
+    if (!edges) return fail(LCHD_EVALUE, "null edges");
+    if (n_edges < 2) return fail(LCHD_EVALUE, "a radial profile needs at least 2 edges (one bin), got %d", n_edges);
+    if (n_edges > kRadialMaxBins + 1) return fail(LCHD_EVALUE, "a radial profile takes at most %d edges (%d bins), got %d", kRadialMaxBins + 1, kRadialMaxBins, n_edges);
+    for (int32_t k = 0; k < n_edges; ++k) {
+        const double e = edges[k];
+        if (std::isnan(e) || e < 0.0) return fail(LCHD_EVALUE, "edge %d is %g: edges are distances >= 0", k, e);
+        if (std::isinf(e) && k + 1 < n_edges) return fail(LCHD_EVALUE, "edge %d is +inf: only the last edge may be", k);
+        if (k && !(e > edges[k - 1])) return fail(LCHD_EVALUE, "edge %d (%g) does not exceed edge %d (%g): edges ascend strictly", k, e, k - 1, edges[k - 1]);
+    }
+    return LCHD_OK;
+}
+static int radial_limits(const lchd_ctx* c) {
+    if (c->h_cfg.n_categories > kWideCategories)
+        return fail(LCHD_EUNSUPPORTED, "a radial profile takes at most %d categories (got %d)", kWideCategories, c->h_cfg.n_categories);
+    return LCHD_OK;
+}
+static RadialEdges radial_edges(const double* edges, int32_t n_edges) {
+    RadialEdges ed{};
+    ed.n = n_edges;
+    for (int32_t k = 0; k < n_edges; ++k) ed.e[k] = edges[k];
+    return ed;
+}
+// Records, bounds and the kernel behind a finished store build (stream order); sw: the stores, the pair list and its slots.
+static int radial_enqueue(lchd_ctx* c, SweepArgs& sw, const RadialEdges& ed, double* d_out) {
+    const int n_wf = c->h_cfg.n_wf;
+    if (int rc = grow_block(c->d_radial_bounds, c->radial_bounds_cap, sizeof(double) * (size_t)n_wf * (size_t)ed.n)) return rc;
+    hipStream_t s = c->stream;
+    fill_sweep_args(c, sw);
+    launch_pair_meta(s, sw);
+    launch_radial_bounds(s, c->d_cfg, n_wf, ed, reinterpret_cast<double*>(c->d_radial_bounds));
+    RadialArgs ra{};
+    ra.sw = sw;
+    ra.bounds = reinterpret_cast<const double*>(c->d_radial_bounds);
+    ra.n_bins = ed.n - 1;
+    ra.n_categories = c->h_cfg.n_categories;
+    ra.out = d_out;
+    if (!launch_radial(s, c->hellinger2 && c->unit_weights && !c->tune.force_generic, ra))
+        return fail(LCHD_EDEVICE, "internal error: the radial kernel rejected its launch configuration");
+    return LCHD_OK;
+}
+
+struct RadialRequest {
+    lchd_cloud *a, *b;
+    const int64_t* anchors;  // DEVICE [n_pairs][2]
+    const int32_t* wf;       // DEVICE [n_pairs] or null
+    int64_t n_pairs;
+    double thr;
+    RadialEdges edges;
+    double* out;             // DEVICE [n_pairs][bins]
+};
+// One thresholded pass with slots of `cap` points: enqueued, waited for; *flags_out = its status words.
+static int radial_prims_pass(lchd_ctx* c, const RadialRequest& R, int cap, uint32_t* flags_out) {
+    lchd_cloud *a = R.a, *b = R.b;
+    const int n_wf = c->h_cfg.n_wf;
+    PassQuery q;
+    q.n_a = a->n; q.n_b = b->n; q.n_pairs = R.n_pairs;
+    q.same_object = a == b;
+    q.has_wf_index = R.wf != nullptr;
+    q.cap = cap;
+    q.n_categories = c->h_cfg.n_categories; q.n_wf = n_wf;
+    q.deterministic = c->deterministic; q.tag_mode = c->h_cfg.tag_mode;
+    q.tune = c->tune;
+    PassPlan plan = plan_pass(q);
+    // the kernel reads F keys whatever the dictionary's size or the environment kernel (comp_prims_pass: the same amendment)
+    plan.dict_sets = n_wf > 1;
+    plan.key_sets = n_wf > 1 ? n_wf + 1 : 1;
+    plan.pre_words = 0;
+    PrimsStore st;
+    const int built = build_prims_store(c, a, b, R.anchors, nullptr, R.n_pairs, R.thr, q, plan, st);
+    if (st.begun) ++c->n_passes;
+    if (built) return built;
+    hipStream_t s = c->stream;
+    SweepArgs sw{};
+    sw.env_a = st.env[0];
+    sw.env_b = st.env[plan.same ? 0 : 1];
+    sw.anchors = R.anchors;
+    sw.slot_a = st.pb.a.slot;
+    sw.slot_b = plan.same ? st.pb.a.slot : (plan.per_pair ? nullptr : st.pb.b.slot);
+    sw.n_slot_a = a->n;
+    sw.n_slot_b = b->n;
+    sw.wf_index = R.wf;
+    sw.n_pairs = R.n_pairs;
+    sw.meta = st.pb.pair_meta;
+    if (int rc = radial_enqueue(c, sw, R.edges, R.out)) return rc;
+    mark(c, 4);
+    if (a->ev_used) { HIP_TRY(hipEventRecord(a->ev_used, s)); a->used_valid = true; }
+    if (b->ev_used) { HIP_TRY(hipEventRecord(b->ev_used, s)); b->used_valid = true; }
+    HIP_TRY(hipGetLastError());
+    c->status_dirty = false;  // the record pass leaves the device status clean
+    if (int rc = wait_pass(c, flags_out)) return rc;
+    collect_times(c, 0, 4);
+    return LCHD_OK;
+}
+
+extern "C" int lchd_radial_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
+                                          int64_t n_pairs, double thr, const double* edges, int32_t n_edges, double* d_out) {
+    CTX_LOCK(c);
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
+    if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (int rc = radial_limits(c)) return rc;
+    if (n_pairs <= 0) return LCHD_OK;
+    if (!d_anchors || !d_out) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    if (n_pairs > (int64_t)0x7FFFFFFF / kRadialMaxBins) return fail(LCHD_EUNSUPPORTED, "more than %d anchor pairs in one radial call (%lld): split the list", 0x7FFFFFFF / kRadialMaxBins, (long long)n_pairs);
+    if (!(thr > 0.0)) return fail(LCHD_EPANIC, "index out of bounds: threshold_distance = %g leaves every environment empty", thr);
+    if (a->n == 0 || b->n == 0) return fail(LCHD_EPANIC, "index out of bounds: anchor pairs given for an empty structure");
+    if (thr > a->reach || thr > b->reach)
+        return fail(LCHD_EVALUE, "threshold_distance = %g is beyond the reach %g the periodic images were built with", thr, std::min(a->reach, b->reach));
+    if (!std::isfinite(thr)) thr = 1.7e308;
+    CTX_GUARD(c);
+    if (int rc = resolve_bbox(c, a)) return rc;
+    if (int rc = resolve_bbox(c, b)) return rc;
+    const bool keep_sweep_record = c->last_sweep_valid;  // (host data: the record of the last scoring pass stands)
+    c->last_valid = false;                               // (its arrays do not: the arena is laid out anew)
+    const RadialRequest R{a, b, d_anchors, d_wf_index, n_pairs, thr, radial_edges(edges, n_edges), d_out};
+    // The retry ladder of the composition calls: an environment that did not fit its slot repeats the WHOLE pass with slots that hold
+    // the largest one reported.  Every row is written again: a row's bits do not depend on the slot size.
+    int cap = kEnvGroupCap, rc = fail(LCHD_EDEVICE, "environment capacity retry did not converge");
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        uint32_t f = 0;
+        if ((rc = radial_prims_pass(c, R, cap, &f)) != LCHD_OK) break;
+        if ((f & ST_BAD_ANCHOR) || !(f & ST_ENV_OVERFLOW)) { rc = status_to_rc(f & ~(uint32_t)ST_ENV_OVERFLOW, DRV_PRIMS); break; }
+        const HostStatus h = *c->h_status;
+        const int64_t want = std::max<int64_t>(std::max<int64_t>(h.max_env, h.max_bound / 3), cap + 1);
+        if (h.max_env > (uint32_t)kRadialMaxPoints || cap > kRadialMaxPoints) {
+            rc = fail(LCHD_EUNSUPPORTED, "an environment holds %u points; a radial profile takes at most %d", h.max_env, kRadialMaxPoints);
+            break;
+        }
+        cap = std::min(next_pow2_host(want), kRadialMaxPoints + 1);
+        rc = fail(LCHD_EDEVICE, "environment capacity retry did not converge");
+    }
+    if (keep_sweep_record) c->last_sweep_valid = true;  // (a grown workspace drops both records; this one is host data)
+    return rc;
+}
+
+extern "C" int lchd_radial_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
+                                      int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
+                                      const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, const double* box_a,
+                                      const double* cell_a, const double* box_b, const double* cell_b, const double* edges, int32_t n_edges,
+                                      double* out) {
+    CTX_LOCK(c);
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
+    if ((box_a && cell_a) || (box_b && cell_b))
+        return fail(LCHD_EVALUE, "a box and a cell were both given: a structure has one periodic box or one periodic cell");
+    if (int rc = check_wf_index(cfg, wf_index, n_pairs)) return rc;
+    if (n_a < 0 || n_b < 0 || n_a > ((int64_t)1 << 27) || n_b > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "structure size out of range");
+    if (box_a) if (int rc = lchd_box_validate(box_a, 1, thr)) return rc;
+    if (box_b) if (int rc = lchd_box_validate(box_b, 1, thr)) return rc;
+    if (cell_a) if (int rc = lchd_cell_validate(cell_a, 1, thr)) return rc;
+    if (cell_b) if (int rc = lchd_cell_validate(cell_b, 1, thr)) return rc;
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (n_pairs > 0 && (!anchors || !out)) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    for (int64_t p = 0; p < n_pairs; ++p)  // (an index beyond the structure would name a ghost atom of an image cloud)
+        if (anchors[2 * p] < 0 || anchors[2 * p] >= n_a || anchors[2 * p + 1] < 0 || anchors[2 * p + 1] >= n_b)
+            return fail(LCHD_EPANIC, "index out of bounds: an anchor index is outside its structure (src/locohd.rs:521)");
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    if (n_pairs <= 0) return LCHD_OK;
+    HostTemps t(c);
+    lchd_cloud *&ia = t.clouds[0], *&ib = t.clouds[1], *&ca = t.clouds[2], *&cb = t.clouds[3];
+    char*& d_blk = t.d_blk;
+    const size_t K = (size_t)n_edges - 1;
+    const size_t o_wf = sizeof(int64_t) * 2 * (size_t)n_pairs, o_out = (o_wf + sizeof(int32_t) * (size_t)n_pairs + 255) & ~size_t(255);
+    auto run = [&]() -> int {
+        if (int rc = lchd_cloud_create(c, xyz_a, cat_a, tag_a, n_a, &ca)) return rc;
+        if (int rc = lchd_cloud_create(c, xyz_b, cat_b, tag_b, n_b, &cb)) return rc;
+        if (box_a) if (int rc = lchd_cloud_create_images(c, ca, box_a, 1, thr, &ia)) return rc;
+        if (box_b) if (int rc = lchd_cloud_create_images(c, cb, box_b, 1, thr, &ib)) return rc;
+        if (cell_a) if (int rc = lchd_cloud_create_images_cell(c, ca, cell_a, 1, thr, &ia)) return rc;
+        if (cell_b) if (int rc = lchd_cloud_create_images_cell(c, cb, cell_b, 1, thr, &ib)) return rc;
+        HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)n_pairs * K));
+        HIP_TRY(hipMemcpy(d_blk, anchors, o_wf, hipMemcpyHostToDevice));
+        if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice));
+        if (int rc = lchd_radial_primitives_dev(c, ia ? ia : ca, ib ? ib : cb, reinterpret_cast<const int64_t*>(d_blk),
+                                                wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, n_pairs, thr, edges, n_edges,
+                                                reinterpret_cast<double*>(d_blk + o_out)))
+            return rc;
+        HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)n_pairs * K, hipMemcpyDeviceToHost));
+        return LCHD_OK;
+    };
+    return t.rc = run();
+}
+
+// Dense rows: pair r = row r of A against row r of B.  d_ma / d_mb: DEVICE rows [rows][cols], or null: distances from the side's
+// coordinates, through the minimum-image row producer with a cell.  Both sides go through k_env_rows, which materialises the stores
+// (the fused sort-and-sweep kernel never writes one).
+static int radial_dense(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, const double* d_ma, const double* d_mb, int64_t rows,
+                        int64_t cols_a, int64_t cols_b, const MinImageCell* cell_a, const MinImageCell* cell_b, const int32_t* d_wf,
+                        const RadialEdges& ed, double* d_out) {
+    const int n_wf = c->h_cfg.n_wf;
+    const int cap_a = next_pow2_host(cols_a), cap_b = next_pow2_host(cols_b);
+    const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
+    const size_t sets = n_wf > 1 ? (size_t)n_wf + 1 : 1;
+    EnvStore ea{}, eb{};
+    double *w_a = nullptr, *w_b = nullptr;
+    int4* d_meta = nullptr;
+    for (int dry = 1; dry >= 0; --dry) {
+        Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
+        ea = carve_row_store(ar, rows, cap_a, sets, cat16);
+        eb = carve_row_store(ar, rows, cap_b, sets, cat16);
+        d_meta = ar.take<int4>((size_t)rows);
+        if (cell_a) w_a = ar.take<double>((size_t)rows * cols_a);
+        if (cell_b) w_b = ar.take<double>((size_t)rows * cols_b);
+        if (dry) if (int rc = ensure_ws(c, ar.off + 4096)) return rc;
+    }
+    ea.cdf_keys = eb.cdf_keys = n_wf == 1 ? 1 : 0;
+    hipStream_t s = c->stream;
+    if (int rc = begin_pass(c)) return rc;
+    c->status_dirty = true;
+    mark(c, 0);
+    if (cell_a) { produce_rows(s, a, cols_a, rows, cell_a, w_a); d_ma = w_a; }
+    if (cell_b) { produce_rows(s, b, cols_b, rows, cell_b, w_b); d_mb = w_b; }
+    mark(c, 1);
+    mark(c, 2);
+    if (!launch_env_rows(s, cap_a, c->d_cfg, a.view(cat16), d_ma, cols_a, rows, cols_a, diag2(a), ea, c->d_status) ||
+        !launch_env_rows(s, cap_b, c->d_cfg, b.view(cat16), d_mb, cols_b, rows, cols_b, diag2(b), eb, c->d_status))
+        return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
+    if (c->deterministic) launch_env_canon(s, ea, eb, rows, rows, nullptr);
+    if (n_wf > 1) {
+        launch_profile_rows(s, c->d_status, rows);  // (the key-set kernel walks DeviceStatus::n_unique[0] rows of its first store)
+        launch_env_key_sets(s, c->d_cfg, ea, ea, n_wf, rows, c->d_status);
+        launch_env_key_sets(s, c->d_cfg, eb, eb, n_wf, rows, c->d_status);
+        for (EnvStore* e : {&ea, &eb}) {
+            e->key += e->set_stride;
+            e->cdf_keys = n_wf;
+        }
+    }
+    mark(c, 3);
+    SweepArgs sw{};
+    sw.env_a = ea;
+    sw.env_b = eb;
+    sw.wf_index = d_wf;
+    sw.n_pairs = rows;
+    sw.meta = d_meta;
+    if (int rc = radial_enqueue(c, sw, ed, d_out)) return rc;
+    mark(c, 4);
+    HIP_TRY(hipGetLastError());
+    c->status_dirty = false;
+    uint32_t f = 0;
+    if (int rc = wait_pass(c, &f)) return rc;
+    collect_times(c, 0, 4);
+    return status_to_rc(f, DRV_DMXS);
+}
+static int radial_dense_check(lchd_ctx* c, int64_t cols_a, int64_t cols_b) {
+    if (int rc = radial_limits(c)) return rc;
+    if (cols_a > kRadialMaxPoints || cols_b > kRadialMaxPoints)
+        return fail(LCHD_EUNSUPPORTED, "a radial profile takes dense rows of at most %d points (got %lld / %lld)", kRadialMaxPoints, (long long)cols_a, (long long)cols_b);
+    return LCHD_OK;
+}
+
+extern "C" int lchd_radial_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
+                                      const double* cell_b, const double* edges, int32_t n_edges, double* d_out) {
+    CTX_LOCK(c);
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
+    if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (a->sid || b->sid) return fail(LCHD_EVALUE, "from_coords takes single structures, not batches");
+    if ((cell_a && a->images) || (cell_b && b->images)) return fail(LCHD_EVALUE, "a periodic dense call takes the structures themselves, not their image clouds");
+    if (a->n != b->n)
+        return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)a->n, (long long)b->n);
+    MinImageCell rec_a, rec_b;
+    if (cell_a) if (int rc = min_image_record(cell_a, 0, rec_a)) return rc;
+    if (cell_b) if (int rc = min_image_record(cell_b, 0, rec_b)) return rc;
+    if (a->n == 0) return LCHD_OK;
+    if (!d_out) return fail(LCHD_EVALUE, "null output pointer");
+    if (int rc = radial_dense_check(c, a->n, b->n)) return rc;
+    CTX_GUARD(c);
+    if (int rc = resolve_bbox(c, a)) return rc;
+    if (int rc = resolve_bbox(c, b)) return rc;
+    const bool keep_sweep_record = c->last_sweep_valid;
+    c->last_valid = false;
+    const int rc = radial_dense(c, *a, *b, nullptr, nullptr, a->n, a->n, b->n, cell_a ? &rec_a : nullptr, cell_b ? &rec_b : nullptr, d_wf_index,
+                                radial_edges(edges, n_edges), d_out);
+    if (keep_sweep_record) c->last_sweep_valid = true;
+    return rc;
+}
+
+// Host arrays: coordinates (xyz set, dmx null; optional cells) or given rows (dmx [rows][cols], xyz null).
+static int radial_dense_host(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b, int64_t len_seq_b,
+                             const double* xyz_a, const double* xyz_b, const double* dmx_a, const double* dmx_b, int64_t rows, int64_t cols_a,
+                             int64_t cols_b, const int32_t* wf_index, const double* cell_a, const double* cell_b, const double* edges,
+                             int32_t n_edges, double* out) {
+    CTX_LOCK(c);
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    MinImageCell rec_a, rec_b;
+    if (cell_a) if (int rc = min_image_record(cell_a, 0, rec_a)) return rc;
+    if (cell_b) if (int rc = min_image_record(cell_b, 0, rec_b)) return rc;
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    if (int rc = check_wf_index(cfg, wf_index, rows)) return rc;
+    if (rows == 0) return LCHD_OK;
+    if (cols_a > len_seq_a || cols_b > len_seq_b) return fail(LCHD_EPANIC, "index out of bounds: a distance row is longer than its seq");
+    if (cols_a == 0 || cols_b == 0) return fail(LCHD_EPANIC, "index out of bounds: empty distance row (src/locohd.rs:74)");
+    if (int rc = radial_dense_check(c, cols_a, cols_b)) return rc;
+    if (!out || (!xyz_a && !dmx_a) || (!xyz_b && !dmx_b)) return fail(LCHD_EVALUE, "null pointer");
+    const bool keep_sweep_record = c->last_sweep_valid;
+    c->last_valid = false;
+    HostTemps t(c);
+    lchd_cloud *&ca = t.clouds[0], *&cb = t.clouds[1];
+    char*& d_blk = t.d_blk;
+    const size_t K = (size_t)n_edges - 1;
+    const size_t o_mb = dmx_a ? (sizeof(double) * (size_t)rows * (size_t)cols_a + 255) & ~size_t(255) : 0;
+    const size_t o_wf = o_mb + (dmx_b ? sizeof(double) * (size_t)rows * (size_t)cols_b : 0);
+    const size_t o_out = (o_wf + sizeof(int32_t) * (size_t)rows + 255) & ~size_t(255);
+    auto run = [&]() -> int {
+        if (int rc = lchd_cloud_create(c, xyz_a, seq_a, nullptr, cols_a, &ca)) return rc;  // (given rows: the cloud carries the categories alone)
+        if (int rc = lchd_cloud_create(c, xyz_b, seq_b, nullptr, cols_b, &cb)) return rc;
+        HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)rows * K));
+        if (dmx_a) HIP_TRY(hipMemcpy(d_blk, dmx_a, sizeof(double) * (size_t)rows * (size_t)cols_a, hipMemcpyHostToDevice));
+        if (dmx_b) HIP_TRY(hipMemcpy(d_blk + o_mb, dmx_b, sizeof(double) * (size_t)rows * (size_t)cols_b, hipMemcpyHostToDevice));
+        if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice));
+        if (int rc = radial_dense(c, *ca, *cb, dmx_a ? reinterpret_cast<const double*>(d_blk) : nullptr,
+                                  dmx_b ? reinterpret_cast<const double*>(d_blk + o_mb) : nullptr, rows, cols_a, cols_b, cell_a ? &rec_a : nullptr,
+                                  cell_b ? &rec_b : nullptr, wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr,
+                                  radial_edges(edges, n_edges), reinterpret_cast<double*>(d_blk + o_out)))
+            return rc;
+        HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)rows * K, hipMemcpyDeviceToHost));
+        return LCHD_OK;
+    };
+    t.rc = run();
+    if (keep_sweep_record) c->last_sweep_valid = true;
+    return t.rc;
+}
+extern "C" int lchd_radial_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                  int64_t len_seq_b, const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b, const int32_t* wf_index,
+                                  const double* cell_a, const double* cell_b, const double* edges, int32_t n_edges, double* out) {
+    if (n_a != n_b)  // src/locohd.rs:420-428 via :472-475
+        return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)n_a, (long long)n_b);
+    if (n_a > 0 && (!xyz_a || !xyz_b)) return fail(LCHD_EVALUE, "null pointer");
+    return radial_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n_a, n_a, n_b, wf_index, cell_a, cell_b, edges,
+                             n_edges, out);
+}
+extern "C" int lchd_radial_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                int64_t len_seq_b, const double* dmx_a, const double* dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
+                                const int32_t* wf_index, const double* edges, int32_t n_edges, double* out) {
+    if (rows > 0 && (!dmx_a || !dmx_b)) return fail(LCHD_EVALUE, "null pointer");
+    return radial_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr, nullptr,
+                             edges, n_edges, out);
 }

@@ -413,6 +413,24 @@ void launch_profile_pairs(hipStream_t s, const int64_t* anchors, int64_t n, int6
 void launch_profile_rows(hipStream_t s, DeviceStatus* st, int64_t n_rows);  // DeviceStatus::n_unique = (n_rows, 0)
 // the end of a pass that has no record pass: status words into the host-mapped mirror, device status reset (publish_status)
 void launch_profile_publish(hipStream_t s, DeviceStatus* st, HostStatus* hst, uint32_t seq);
+// Radial score profiles (lchd_radial.hip): a pair's integrand resolved over distance bins, one row of n_bins doubles per pair, from
+// stores whose keys are F values.  The pair list, the stores, the records and the status words travel in a SweepArgs, as for a sweep.
+constexpr int kRadialMaxPoints = 65535;  // points of an environment or row (the 16-bit count fields; the 16-bit-category pair record)
+struct RadialEdges {                     // the caller's edges e_0 < ... < e_K, by value (lchd_radial_bins.h: kRadialMaxBins + 1 of them at most)
+    double e[65];
+    int32_t n;
+};
+struct RadialArgs {
+    SweepArgs sw;         // cfg, env_a / env_b (cdf_keys >= 1), anchors / slots, wf_index, n_pairs, meta, sqrt tables, st / hst / seq / done; out unused
+    const double* bounds; // [n_wf][n_bins + 1] E_k = F_w(e_k), written by launch_radial_bounds
+    int32_t n_bins;
+    int32_t n_categories; // DevConfig::n_categories (the launcher sizes the LDS with it)
+    double* out;          // [n_pairs][n_bins]
+};
+void launch_pair_meta(hipStream_t s, const SweepArgs& a);  // k_pair_meta alone (lchd_kernels.hip): the records, the counts, the status hand-over
+void launch_radial_bounds(hipStream_t s, const DevConfig* cfg, int n_wf, const RadialEdges& edges, double* bounds);
+bool launch_radial(hipStream_t s, bool hellinger2_unit, const RadialArgs& a);  // false: nothing launched (more than kWideCategories categories)
+void init_radial_kernels();  // per device (dynamic LDS above 64 KB), called by init_device_kernels
 void launch_mark_overflow(hipStream_t s, const uint32_t* list_a, uint32_t na, const uint32_t* list_b, uint32_t nb, uint32_t* bits_a, uint32_t* bits_b);
 void launch_count_overflow(hipStream_t s, const OverflowSelect& a, unsigned long long* total);
 void launch_write_overflow(hipStream_t s, const OverflowSelect& a);

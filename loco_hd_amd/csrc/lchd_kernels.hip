@@ -361,6 +361,19 @@ void init_device_kernels() {
     init_env_cells_kernels();
     init_env_rows_kernels();
     init_sweep_wide_kernels();
+    init_radial_kernels();
+}
+// The record pass alone, for a consumer of the pair records that is not a sweep (lchd_radial.hip): no small-pair rule is in force, no
+// leftover list is kept; the counts it publishes are those of any pass.
+void launch_pair_meta(hipStream_t s, const SweepArgs& a_in) {
+    if (a_in.n_pairs <= 0) return;
+    SweepArgs a = a_in;
+    a.duo_enabled = a.forced = a.small_rule = a.second_rule = a.left_listing = 0;
+    a.c8_rule = 2;
+    a.left_list = nullptr;
+    a.left_count = a.left_zero = nullptr;
+    const int64_t nb = (a.n_pairs + 255) / 256;
+    k_pair_meta<<<(int)(nb < kMetaPartials ? nb : kMetaPartials), 256, 0, s>>>(a);
 }
 
 // sum over pairs of n_A + n_B (algorithmic-bytes accounting for bench.py; not part of the scoring path)
