@@ -232,6 +232,46 @@ def test_300_categories_and_the_limit():
         lh.LoCoHD(cats513, lh.WeightFunction(*UNI)).radial_from_primitives(pa[:5], pb[:5], [(0, 0)], 8.0, EDGES)
 
 
+@pytest.mark.parametrize("n_cat", [64, 65, 255, 256, 257])
+def test_category_counts_at_the_kernel_switches(n_cat):
+    """64 / 65: four pairs per workgroup against one (one-byte ids); 255 / 256 / 257: the one-byte against the 16-bit store.  The
+    highest id sits on an anchor and on an atom that is no anchor but inside an anchor's environment, on both sides."""
+    lh = _lh()
+    rng = np.random.default_rng(1000 + n_cat)
+    cats = [f"k{k}" for k in range(n_cat)]
+    n, thr = 120, 7.0
+    pairs = [(int(i), int(j)) for i, j in rng.integers(0, n, (12, 2))]
+    sides = []
+    for col in (0, 1):
+        xyz, cat = rng.uniform(0.0, 14.0, (n, 3)), rng.integers(0, n_cat, n)
+        anchors = {p[col] for p in pairs}
+        first = pairs[0][col]
+        near = [int(q) for q in np.argsort(np.linalg.norm(xyz - xyz[first], axis=1)) if q not in anchors][0]
+        assert np.linalg.norm(xyz[near] - xyz[first]) < thr
+        cat[first] = cat[near] = n_cat - 1
+        sides.append((xyz, cat, _atoms(lh, [cats[k] for k in cat], ["x"] * n, xyz)))
+    (xa, ca, pa), (xb, cb, pb) = sides
+    weights = rng.uniform(0.3, 3.0, n_cat)
+    for dist in ("hellinger2", "ks"):
+        for w in (None, weights):
+            l = lh.LoCoHD(cats, lh.WeightFunction(*UNI), category_weights=None if w is None else list(w),
+                          statistical_distance=lh.StatisticalDistance(*DISTANCES[dist]))
+            got = l.radial_from_primitives(pa, pb, pairs, thr, EDGES)
+            want = ru.from_primitives(ca, xa, None, cb, xb, None, pairs, thr, n_cat, UNI, EDGES, DISTANCES[dist], w)
+            _check(got, want, f"{n_cat} categories, {dist}, {'weighted' if w is not None else 'unit weights'}")
+
+
+def test_63_bins_and_one_bin_too_many(two_clouds, pairs40):
+    lh, (a, b) = _lh(), two_clouds
+    l = lh.LoCoHD(CATS7, lh.WeightFunction(*UNI))
+    e63 = list(np.linspace(0.0, 11.0, 63)) + [INF]
+    got = l.radial_from_primitives(a.atoms, b.atoms, pairs40, 8.0, e63)
+    assert got.shape == (40, 63)
+    _check(got, _restated(a, b, pairs40, 8.0, UNI, edges=e63), "K = 63")
+    with pytest.raises(ValueError):
+        l.radial_from_primitives(a.atoms, b.atoms, pairs40, 8.0, list(np.linspace(0.0, 11.0, 65)) + [INF])  # K = 65
+
+
 # ---- dense and device-resident calls --------------------------------------------------------------------------------------------------
 def test_from_coords_open_and_in_a_cell():
     lh = _lh()

@@ -584,6 +584,138 @@ def test_inputs_written_behind_a_delay_on_the_session_stream(env, ref, delay, na
 
 
 # ------------------------------------------------------------------------------------------------------------------------
+# 2b. the profile calls: anchors, weight-function indices and the coordinates of side B behind a delay
+# ------------------------------------------------------------------------------------------------------------------------
+PROFILE_CALLS = ("radial", "radial_coords", "composition", "composition_coords")
+PROFILE_EDGES = [0.0, 2.0, 3.0, 4.5, 6.0, 7.25, float("inf")]  # (a host list: read before the call returns)
+
+
+def _dense(x):
+    d = x[:, None, :] - x[None, :, :]
+    return np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+
+
+def _profile_inputs(cfg, kind, stale=False):
+    """(anchors, wf_index) host arrays of a profile call on the small structures: pairs for radial, side-B atoms for composition."""
+    if kind in ("radial", "composition"):
+        anc, wf = (cfg.anc_small_stale, cfg.wf_small_stale) if stale else (cfg.anc_small, cfg.wf_small)
+        return (anc if kind == "radial" else np.ascontiguousarray(anc[:, 1])), wf
+    wf = cfg.wf_rows_small
+    return None, (wf if wf is None or not stale else 1 - wf)
+
+
+def _profile_call(b, kind, first, wf, out=None):
+    s = b.sess
+    if kind == "radial":
+        return s.radial(b.a_s, b.b_s, first, THR, PROFILE_EDGES, out=out, wf_index=wf)
+    if kind == "radial_coords":
+        return s.radial_coords(b.a_s, b.b_s, PROFILE_EDGES, out=out, wf_index=wf)
+    if kind == "composition":
+        return s.composition(b.b_s, first, THR, out=out, wf_index=wf)
+    return s.composition_coords(b.b_s, out=out, wf_index=wf)
+
+
+def _profile_expected(env, name, kind):
+    """radial_util / composition_util on the RIGHT data: side B at its second coordinate set.  Computed once per (configuration, call)."""
+    import composition_util as cu
+    import radial_util as ru
+
+    cache = env.__dict__.setdefault("profile_want", {})
+    if (name, kind) not in cache:
+        c = env.cfgs[name]
+        k, n_cat = c.n_small, len(c.cats)
+        xa, ca, xb, cb = c.xa[:k], c.ca[:k], c.xb2[:k], c.cb[:k]
+        anc, wf = _profile_inputs(c, kind)
+        specs = list(c.w_func.values()) if c.dict else [c.w_func]
+        per_item = [specs[i] for i in wf] if c.dict else None
+        if kind == "radial":
+            want = ru.from_primitives(ca, xa, None, cb, xb, None, anc, THR, n_cat, per_item if c.dict else specs[0], PROFILE_EDGES)
+        elif kind == "radial_coords":
+            da, db = _dense(xa), _dense(xb)
+            want = np.asarray([ru.profile(ca, da[r], cb, db[r], n_cat, per_item[r] if c.dict else specs[0], PROFILE_EDGES) for r in range(k)])
+        else:
+            fns = [env.orc.WeightFunction(sp[0], list(sp[1])) for sp in specs]
+            cdfs = [lambda x, f=f: np.asarray(f.integral_vec(np.asarray(x, dtype=np.float64).tolist())) for f in fns]
+            per_cdf = [cdfs[i] for i in wf] if c.dict else cdfs[0]
+            if kind == "composition":
+                want = cu.profiles_of_cloud(xb, cb, np.zeros(k, dtype=np.int32), anc, THR, np.ones(n_cat), per_cdf)
+            else:
+                want = cu.profiles_of_rows(_dense(xb), cb, np.ones(n_cat), per_cdf)
+        cache[name, kind] = want
+    return cache[name, kind]
+
+
+def _profile_bits(env, name, kind):
+    """The same call on the DEFAULT stream with complete, host-synchronised inputs, deterministic mode: the bit pattern to reproduce."""
+    cache = env.__dict__.setdefault("profile_bits", {})
+    if (name, kind) not in cache:
+        cfg = env.cfgs[name]
+        b = Bench(env, cfg, deterministic=True)
+        try:
+            b.sess.set_coords(b.b_s, cfg.xb2[:cfg.n_small])
+            env.torch.cuda.synchronize()
+            first, wf = (b.dev(x) for x in _profile_inputs(cfg, kind))
+            got = _profile_call(b, kind, first, wf).cpu().numpy().copy()
+        finally:
+            b.close()
+        want = _profile_expected(env, name, kind)
+        assert got.shape == want.shape and float(np.max(np.abs(got - want))) < TIGHT, (name, kind)
+        cache[name, kind] = got
+    return cache[name, kind]
+
+
+@pytest.mark.parametrize("kind", PROFILE_CALLS)
+@pytest.mark.parametrize("name", ["A", "D"])
+def test_profile_inputs_written_behind_a_delay_on_the_session_stream(env, ref, delay, name, kind):
+    torch, cfg = env.torch, env.cfgs[name]
+    bits, want = _profile_bits(env, name, kind), _profile_expected(env, name, kind)
+    s = delay.streams(1)[0]
+    with torch.cuda.stream(s):
+        b = Bench(env, cfg, deterministic=True)  # (side B of the small structures holds xb: the stale coordinates, the same bounding box)
+        try:
+            real = [b.dev(x) for x in _profile_inputs(cfg, kind)]
+            held = [b.dev(x) for x in _profile_inputs(cfg, kind, stale=True)]  # what the buffers hold while the delay runs
+            out = torch.zeros(bits.shape, dtype=torch.float64, device="cuda")
+            torch.cuda.synchronize()
+            delay.on(s)
+            for h, r in zip(held, real):
+                if h is not None:
+                    h.copy_(r)  # the right inputs, written by a torch kernel behind the delay
+            b.sess.set_coords(b.b_s, cfg.xb2[:cfg.n_small])  # the right coordinates of side B, queued behind the delay
+            out.fill_(SENTINEL)
+            got = _profile_call(b, kind, held[0], held[1], out=out)
+            g = got.cpu().numpy()
+            assert not np.any(g == SENTINEL), f"{kind}: the sentinel written before the call survived in {int(np.sum(g == SENTINEL))} slots"
+            _same(got, bits, want, f"{name}.{kind} delayed producers")
+        finally:
+            b.close()
+
+
+@pytest.mark.parametrize("how", ["created_on_stream", "moved_to_stream"])
+def test_radial_session_on_a_side_stream(env, ref, delay, how):
+    torch, cfg = env.torch, env.cfgs["A"]
+    kinds = ("radial", "radial_coords")
+    bits = {kind: _profile_bits(env, "A", kind) for kind in kinds}  # (on the default stream: before this test leaves it)
+    s = delay.streams(1)[0]
+    if how == "created_on_stream":
+        with torch.cuda.stream(s):
+            b = Bench(env, cfg, deterministic=True)
+    else:
+        b = Bench(env, cfg, deterministic=True)
+        with torch.cuda.stream(s):
+            b.sess.use_current_stream()
+    try:
+        with torch.cuda.stream(s):
+            b.sess.set_coords(b.b_s, cfg.xb2[:cfg.n_small])
+            for kind in kinds:
+                first, wf = (b.dev(x) for x in _profile_inputs(cfg, kind))
+                got = _profile_call(b, kind, first, wf)  # (the library call returns with d_out complete: no torch synchronise before the read-back)
+                _same(got, bits[kind], _profile_expected(env, "A", kind), f"A.{kind} on a side stream")
+    finally:
+        b.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
 # 3. upload, then score without a pause
 # ------------------------------------------------------------------------------------------------------------------------
 def test_upload_and_set_coords_on_a_delayed_stream(env, ref, delay):
