@@ -465,6 +465,48 @@ int lchd_radial_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a
                      const double *dmx_a, const double *dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b, const int32_t *wf_index,
                      const double *edges, int32_t n_edges, double *out);
 
+/* ---- score attribution by category (additive, not in the reference) -----------------------------------
+ * Which categories carry a pair's score.  For the Hellinger distance with exponent e, between two merged breakpoints (the notation of
+ * the radial profiles above) with a / b the two sides' weighted, normalised PMFs, anchors included:
+ *   t_c = |a_c^(1/e) - b_c^(1/e)|^e      T = sum_c t_c      H = (T / 2)^(1/e)
+ *   out[p][c] = sum_j (F(u_{j+1}) - F(u_j)) * H_j * t_{c,j} / T_j          (a piece with T_j = 0 adds 0 to every column)
+ * out is row-major [pairs][n_categories] f64, categories in the order of lchd_config.
+ *   - a row sums to the pair's score (the scoring call of the same name)
+ *   - a pair of identical environments gives a row of exact zeros; swapping the sides leaves the row unchanged
+ *   - a category neither environment holds has an exactly zero column
+ *   - e = 2: t_c is the literal (sqrt a_c - sqrt b_c)^2 and H t_c / T = t_c / (2 H); e = 1 (total variation): 1/2 integral w |a_c - b_c| dr
+ *   - this is not the difference of the two composition profiles: a swap at 4 A that is undone at 8 A cancels there, and counts here
+ *     at every radius in between
+ * Only the Hellinger distance is a sum of per-category terms: under Kolmogorov-Smirnov, Kullback-Leibler and Renyi configurations these
+ * calls fail with LCHD_EUNSUPPORTED (the message names the distance); the scoring calls are untouched.
+ * The calls are the radial calls without edges: the same environments, store builds, record pass, capacity repeats and errors
+ * (LCHD_EPANIC for an anchor outside its structure, LCHD_EVALUE for a type outside the category map, a zero norm under category weights
+ * or a weight-function index outside the dictionary, ...), the same stream and lock rules (d_out complete on return), and they too leave
+ * the hints of the scoring passes and lchd_ctx_last_sweep alone.  The kernel (lchd_attribution.hip) keeps one accumulator per category
+ * and lane and reduces them in lane order: no floating-point atomics, and under lchd_ctx_set_deterministic a row's bits depend on the
+ * pair and the configuration alone.
+ * Limits: at most 64 categories (LCHD_EUNSUPPORTED beyond; the accumulators of a wavefront live in the LDS), environments and rows of at
+ * most 65 535 points.  Device groups have no attribution call. */
+/* Thresholded, device-resident (lchd_radial_primitives_dev without edges); d_out DEVICE f64 [n_pairs][n_categories]. */
+int lchd_attribution_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors, const int32_t *d_wf_index,
+                                    int64_t n_pairs, double threshold_distance, double *d_out);
+/* The same from host arrays (lchd_radial_primitives without edges); out HOST [n_pairs][n_categories]. */
+int lchd_attribution_primitives(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a, const int32_t *tag_a,
+                                int64_t n_a, const double *xyz_b, const int32_t *cat_b, const int32_t *tag_b, int64_t n_b,
+                                const int64_t *anchors, const int32_t *wf_index, int64_t n_pairs, double threshold_distance,
+                                const double *box_a, const double *cell_a, const double *box_b, const double *cell_b, double *out);
+/* Dense rows, device-resident single structures of equal size (lchd_radial_coords_dev without edges); d_out DEVICE [n][n_categories]. */
+int lchd_attribution_coords_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, const double *cell_a,
+                                const double *cell_b, double *d_out);
+/* The same from host arrays, as lchd_from_coords takes them; out HOST [n][n_categories]. */
+int lchd_attribution_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                            int64_t len_seq_b, const double *xyz_a, int64_t n_a, const double *xyz_b, int64_t n_b, const int32_t *wf_index,
+                            const double *cell_a, const double *cell_b, double *out);
+/* Given distance rows (lchd_radial_dmxs without edges); out HOST [rows][n_categories]. */
+int lchd_attribution_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                          int64_t len_seq_b, const double *dmx_a, const double *dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
+                          const int32_t *wf_index, double *out);
+
 /* ---- multi-GPU ------------------------------------------------------------------------------------
  * The reference's parallelism lives INSIDE the core call: a thread pool that is a field of `LoCoHD` (src/locohd.rs:53,
  * 373-383) runs the anchor pairs of one call (:545-557, order-preserving collect).  The counterpart here is a GROUP of

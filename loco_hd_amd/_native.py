@@ -120,6 +120,12 @@ _PROTOS = {
     "lchd_radial_coords_dev": (C.c_int, [_VP, _VP, _VP, _VP, _DP, _DP, _DP, _i32, _VP]),
     "lchd_radial_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _i64, _DP, _i64, _IP, _DP, _DP, _DP, _i32, _DP]),
     "lchd_radial_dmxs": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _i64, _i64, _IP, _DP, _i32, _DP]),
+    "lchd_attribution_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _i64, _f64, _VP]),
+    "lchd_attribution_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _DP, _DP,
+                                              _DP, _DP, _DP]),
+    "lchd_attribution_coords_dev": (C.c_int, [_VP, _VP, _VP, _VP, _DP, _DP, _VP]),
+    "lchd_attribution_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _i64, _DP, _i64, _IP, _DP, _DP, _DP]),
+    "lchd_attribution_dmxs": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _i64, _i64, _IP, _DP]),
     "lchd_cloud_create": (C.c_int, [_VP, _DP, _IP, _IP, _i64, C.POINTER(_VP)]),
     "lchd_cloud_create_batch": (C.c_int, [_VP, _DP, _IP, _IP, _IP, _i64, _i32, C.POINTER(_VP)]),
     "lchd_cloud_size": (C.c_int64, [_VP]),

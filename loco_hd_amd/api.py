@@ -796,21 +796,18 @@ class LoCoHD:
         N.check(N.lib().lchd_radial_validate(N.dp(ed), len(ed)))
         return ed
 
-    def _no_device_group_for_radial(self) -> None:
+    def _no_device_group_for_pair_rows(self, ed) -> None:
         if self._devices is not None:
-            raise ValueError("a radial profile applies to one device (a device group has no radial call): drop devices=[...]")
+            what, call = ("an attribution", "attribution") if ed is None else ("a radial profile", "radial")
+            raise ValueError(f"{what} applies to one device (a device group has no {call} call): drop devices=[...]")
 
-    def radial_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
-                               threshold_distance: float, edges, *, box_a=None, box_b=None, cell_a=None, cell_b=None) -> np.ndarray:
-        """Additive: the radial profile of every anchor pair `from_primitives` would score, as a float64 array (P, K) for K + 1
-        `edges` (ascending distances, the first >= 0, the last may be inf; at most 64 bins).  Bin k holds the part of the pair's score
-        that the distances between edges[k] and edges[k + 1] contribute; with edges[0] = 0 and edges[-1] = inf a row sums to the score.
-        `anchor_pairs`, `box_a` / `box_b` / `cell_a` / `cell_b`: as `from_primitives` takes them."""
-        ed = self._radial_edges(edges)
+    # The three radial methods and the three attribution methods differ in the kernel their pass ends in and in the row it writes:
+    # `ed` is the checked edge array of a radial call (rows of len(ed) - 1 bins) or None for an attribution (rows of C categories).
+    def _pair_rows_from_primitives(self, ed, prim_a, prim_b, anchor_pairs, threshold_distance, box_a, box_b, cell_a, cell_b) -> np.ndarray:
         for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
             if box is not None and cell is not None:
                 raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
-        self._no_device_group_for_radial()
+        self._no_device_group_for_pair_rows(ed)
         thr = float(threshold_distance)
         ba = None if box_a is None else periodic_boxes(box_a, 1, thr, "box_a")
         bb = None if box_b is None else periodic_boxes(box_b, 1, thr, "box_b")
@@ -820,25 +817,23 @@ class LoCoHD:
         pa, pb, interner = self._packed_lists(prim_a, prim_b)
         anchors = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
         cfg, keep = self._config(interner)
-        out = np.empty((len(anchors), len(ed) - 1))
+        out = np.empty((len(anchors), len(self._weights) if ed is None else len(ed) - 1))
         if len(anchors) == 0:
             return out
         xa, xb = _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3)
-        N.check(N.lib().lchd_radial_primitives(self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa), N.dp(xb),
-                                               N.ip(pb.cat), N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx), len(anchors), thr, N.dp(ba),
-                                               N.dp(ca), N.dp(bb), N.dp(cb), N.dp(ed), len(ed), N.dp(out)))
+        head = (self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa), N.dp(xb), N.ip(pb.cat), N.ip(pb.tag), len(xb),
+                N.lp(anchors), N.ip(idx), len(anchors), thr, N.dp(ba), N.dp(ca), N.dp(bb), N.dp(cb))
+        if ed is None:
+            N.check(N.lib().lchd_attribution_primitives(*head, N.dp(out)))
+        else:
+            N.check(N.lib().lchd_radial_primitives(*head, N.dp(ed), len(ed), N.dp(out)))
         return out
 
-    def radial_from_coords(self, seq_a, seq_b, coords_a, coords_b, edges, w_func_keys: Optional[Sequence[str]] = None, *, box_a=None,
-                           box_b=None, cell_a=None, cell_b=None) -> np.ndarray:
-        """Additive: the radial profile of every dense row pair `from_coords` would score (pair r: the two structures seen from their
-        atoms r), as a float64 array (n, K).  `box_a` / `box_b` / `cell_a` / `cell_b` (keyword-only): minimum-image rows, as
-        `from_coords(..., box_a=...)`."""
-        ed = self._radial_edges(edges)
+    def _pair_rows_from_coords(self, ed, seq_a, seq_b, coords_a, coords_b, w_func_keys, box_a, box_b, cell_a, cell_b) -> np.ndarray:
         for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
             if box is not None and cell is not None:
                 raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
-        self._no_device_group_for_radial()
+        self._no_device_group_for_pair_rows(ed)
         pc_a = dense_cells(box_a, cell_a, 1, "box_a", "cell_a")
         pc_b = dense_cells(box_b, cell_b, 1, "box_b", "cell_b")
         xa, xb = self._coords(coords_a), self._coords(coords_b)
@@ -847,32 +842,80 @@ class LoCoHD:
         idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], len(xa))
         ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
         cfg, keep = self._config()
-        out = np.empty((len(xa), len(ed) - 1))
+        out = np.empty((len(xa), len(self._weights) if ed is None else len(ed) - 1))
         if len(xa) == 0:
             return out
-        N.check(N.lib().lchd_radial_coords(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(xa), len(xa), N.dp(xb),
-                                           len(xb), N.ip(idx), N.dp(pc_a), N.dp(pc_b), N.dp(ed), len(ed), N.dp(out)))
+        head = (self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(xa), len(xa), N.dp(xb), len(xb), N.ip(idx), N.dp(pc_a),
+                N.dp(pc_b))
+        if ed is None:
+            N.check(N.lib().lchd_attribution_coords(*head, N.dp(out)))
+        else:
+            N.check(N.lib().lchd_radial_coords(*head, N.dp(ed), len(ed), N.dp(out)))
         return out
 
-    def radial_from_dmxs(self, seq_a, seq_b, dmx_a, dmx_b, edges, w_func_keys: Optional[Sequence[str]] = None) -> np.ndarray:
-        """Additive: the radial profile of every row pair `from_dmxs` would score (rectangular matrices with the same number of rows,
-        +inf entries allowed, every row holds a 0), as a float64 array (rows, K)."""
-        ed = self._radial_edges(edges)
-        self._no_device_group_for_radial()
+    def _pair_rows_from_dmxs(self, ed, seq_a, seq_b, dmx_a, dmx_b, w_func_keys) -> np.ndarray:
+        self._no_device_group_for_pair_rows(ed)
         (ma, la), (mb, lb) = self._matrix(dmx_a), self._matrix(dmx_b)
         if la is not None or lb is not None:
-            raise ValueError("radial_from_dmxs takes rectangular distance matrices (rows of equal length)")
+            name = "attribution_from_dmxs" if ed is None else "radial_from_dmxs"
+            raise ValueError(f"{name} takes rectangular distance matrices (rows of equal length)")
         if ma.shape[0] != mb.shape[0]:
             raise ValueError(f"Expected matrices with the same length, got lengths {ma.shape[0]} and {mb.shape[0]}!")
         idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], ma.shape[0])
         ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
         cfg, keep = self._config()
-        out = np.empty((ma.shape[0], len(ed) - 1))
+        out = np.empty((ma.shape[0], len(self._weights) if ed is None else len(ed) - 1))
         if ma.shape[0] == 0:
             return out
-        N.check(N.lib().lchd_radial_dmxs(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(ma), N.dp(mb), ma.shape[0],
-                                         ma.shape[1], mb.shape[1], N.ip(idx), N.dp(ed), len(ed), N.dp(out)))
+        head = (self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(ma), N.dp(mb), ma.shape[0], ma.shape[1], mb.shape[1],
+                N.ip(idx))
+        if ed is None:
+            N.check(N.lib().lchd_attribution_dmxs(*head, N.dp(out)))
+        else:
+            N.check(N.lib().lchd_radial_dmxs(*head, N.dp(ed), len(ed), N.dp(out)))
         return out
+
+    def radial_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                               threshold_distance: float, edges, *, box_a=None, box_b=None, cell_a=None, cell_b=None) -> np.ndarray:
+        """Additive: the radial profile of every anchor pair `from_primitives` would score, as a float64 array (P, K) for K + 1
+        `edges` (ascending distances, the first >= 0, the last may be inf; at most 64 bins).  Bin k holds the part of the pair's score
+        that the distances between edges[k] and edges[k + 1] contribute; with edges[0] = 0 and edges[-1] = inf a row sums to the score.
+        `anchor_pairs`, `box_a` / `box_b` / `cell_a` / `cell_b`: as `from_primitives` takes them."""
+        return self._pair_rows_from_primitives(self._radial_edges(edges), prim_a, prim_b, anchor_pairs, threshold_distance, box_a, box_b, cell_a,
+                                               cell_b)
+
+    def radial_from_coords(self, seq_a, seq_b, coords_a, coords_b, edges, w_func_keys: Optional[Sequence[str]] = None, *, box_a=None,
+                           box_b=None, cell_a=None, cell_b=None) -> np.ndarray:
+        """Additive: the radial profile of every dense row pair `from_coords` would score (pair r: the two structures seen from their
+        atoms r), as a float64 array (n, K).  `box_a` / `box_b` / `cell_a` / `cell_b` (keyword-only): minimum-image rows, as
+        `from_coords(..., box_a=...)`."""
+        return self._pair_rows_from_coords(self._radial_edges(edges), seq_a, seq_b, coords_a, coords_b, w_func_keys, box_a, box_b, cell_a, cell_b)
+
+    def radial_from_dmxs(self, seq_a, seq_b, dmx_a, dmx_b, edges, w_func_keys: Optional[Sequence[str]] = None) -> np.ndarray:
+        """Additive: the radial profile of every row pair `from_dmxs` would score (rectangular matrices with the same number of rows,
+        +inf entries allowed, every row holds a 0), as a float64 array (rows, K)."""
+        return self._pair_rows_from_dmxs(self._radial_edges(edges), seq_a, seq_b, dmx_a, dmx_b, w_func_keys)
+
+    # ---- score attribution by category (additive) ----------------------------------------------------------
+    # A[p][c] = sum_j (F(u_{j+1}) - F(u_j)) * H_j * t_{c,j} / T_j with t_c = |a_c^(1/e) - b_c^(1/e)|^e, T = sum_c t_c, H = (T / 2)^(1/e): the
+    # part of pair p's score that category c carries (include/loco_hd_hip.h, "score attribution by category").  Columns follow
+    # `categories`; a row sums to the pair's score.  Hellinger distances only (NotImplementedError otherwise), at most 64 categories.
+    def attribution_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                                    threshold_distance: float, *, box_a=None, box_b=None, cell_a=None, cell_b=None) -> np.ndarray:
+        """Additive: the score of every anchor pair `from_primitives` would score, split over the categories, as a float64 array
+        (P, C) with columns in `categories` order; a row sums to the pair's score.  `anchor_pairs`, `box_a` / `box_b` / `cell_a` /
+        `cell_b`: as `from_primitives` takes them."""
+        return self._pair_rows_from_primitives(None, prim_a, prim_b, anchor_pairs, threshold_distance, box_a, box_b, cell_a, cell_b)
+
+    def attribution_from_coords(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None, *, box_a=None,
+                                box_b=None, cell_a=None, cell_b=None) -> np.ndarray:
+        """Additive: the score of every dense row pair `from_coords` would score, split over the categories, as a float64 array
+        (n, C).  `box_a` / `box_b` / `cell_a` / `cell_b` (keyword-only): minimum-image rows, as `from_coords(..., box_a=...)`."""
+        return self._pair_rows_from_coords(None, seq_a, seq_b, coords_a, coords_b, w_func_keys, box_a, box_b, cell_a, cell_b)
+
+    def attribution_from_dmxs(self, seq_a, seq_b, dmx_a, dmx_b, w_func_keys: Optional[Sequence[str]] = None) -> np.ndarray:
+        """Additive: the score of every row pair `from_dmxs` would score, split over the categories, as a float64 array (rows, C)."""
+        return self._pair_rows_from_dmxs(None, seq_a, seq_b, dmx_a, dmx_b, w_func_keys)
 
     def _no_device_group_with_box(self) -> None:
         if self._devices is not None:

@@ -3832,33 +3832,58 @@ extern "C" int lchd_radial_validate(const double* edges, int32_t n_edges) {
     }
     return LCHD_OK;
 }
-static int radial_limits(const lchd_ctx* c) {
-    if (c->h_cfg.n_categories > kWideCategories)
-        return fail(LCHD_EUNSUPPORTED, "a radial profile takes at most %d categories (got %d)", kWideCategories, c->h_cfg.n_categories);
+// The consumer of a radial pass's stores and pair records: the radial kernel (edges.n >= 2) or -- score attribution by category, the
+// section below -- the attribution kernel (edges.n == 0).  Everything up to the consumer's launch is one code path.
+struct PairConsumer {
+    RadialEdges edges;  // n == 0: attribution by category
+    const char* what;   // in messages: "a radial profile" / "an attribution"
+    const char* call;   // "radial" / "attribution"
+};
+static PairConsumer radial_consumer(const double* edges, int32_t n_edges) {
+    PairConsumer use{{}, "a radial profile", "radial"};
+    use.edges.n = n_edges;
+    for (int32_t k = 0; k < n_edges; ++k) use.edges.e[k] = edges[k];
+    return use;
+}
+// doubles per pair in the consumer's output: the bins / the categories of the context's configuration (at most kRadialMaxBins both)
+static size_t consumer_row(const lchd_ctx* c, const PairConsumer& use) {
+    return use.edges.n ? (size_t)use.edges.n - 1 : (size_t)c->h_cfg.n_categories;
+}
+static int consumer_limits(const lchd_ctx* c, const PairConsumer& use) {
+    static const char* names[4] = {"Hellinger", "Kolmogorov-Smirnov", "Kullback-Leibler", "Renyi"};
+    const int most = use.edges.n ? kWideCategories : kAttributionMaxCategories;
+    if (!use.edges.n && c->h_cfg.sd_kind != SD_HELLINGER)
+        return fail(LCHD_EUNSUPPORTED, "an attribution splits the Hellinger distance over the categories; the %s distance is no sum of per-category terms",
+                    names[c->h_cfg.sd_kind & 3]);
+    if (c->h_cfg.n_categories > most)
+        return fail(LCHD_EUNSUPPORTED, "%s takes at most %d categories (got %d)", use.what, most, c->h_cfg.n_categories);
     return LCHD_OK;
 }
-static RadialEdges radial_edges(const double* edges, int32_t n_edges) {
-    RadialEdges ed{};
-    ed.n = n_edges;
-    for (int32_t k = 0; k < n_edges; ++k) ed.e[k] = edges[k];
-    return ed;
-}
-// Records, bounds and the kernel behind a finished store build (stream order); sw: the stores, the pair list and its slots.
-static int radial_enqueue(lchd_ctx* c, SweepArgs& sw, const RadialEdges& ed, double* d_out) {
+// Records, (bounds) and the kernel behind a finished store build (stream order); sw: the stores, the pair list and its slots.
+static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use, double* d_out) {
     const int n_wf = c->h_cfg.n_wf;
-    if (int rc = grow_block(c->d_radial_bounds, c->radial_bounds_cap, sizeof(double) * (size_t)n_wf * (size_t)ed.n)) return rc;
+    if (int rc = grow_block(c->d_radial_bounds, c->radial_bounds_cap, sizeof(double) * (size_t)n_wf * (size_t)use.edges.n)) return rc;
     hipStream_t s = c->stream;
     fill_sweep_args(c, sw);
     launch_pair_meta(s, sw);
-    launch_radial_bounds(s, c->d_cfg, n_wf, ed, reinterpret_cast<double*>(c->d_radial_bounds));
-    RadialArgs ra{};
-    ra.sw = sw;
-    ra.bounds = reinterpret_cast<const double*>(c->d_radial_bounds);
-    ra.n_bins = ed.n - 1;
-    ra.n_categories = c->h_cfg.n_categories;
-    ra.out = d_out;
-    if (!launch_radial(s, c->hellinger2 && c->unit_weights && !c->tune.force_generic, ra))
-        return fail(LCHD_EDEVICE, "internal error: the radial kernel rejected its launch configuration");
+    bool launched;
+    if (use.edges.n) {
+        launch_radial_bounds(s, c->d_cfg, n_wf, use.edges, reinterpret_cast<double*>(c->d_radial_bounds));
+        RadialArgs ra{};
+        ra.sw = sw;
+        ra.bounds = reinterpret_cast<const double*>(c->d_radial_bounds);
+        ra.n_bins = use.edges.n - 1;
+        ra.n_categories = c->h_cfg.n_categories;
+        ra.out = d_out;
+        launched = launch_radial(s, c->hellinger2 && c->unit_weights && !c->tune.force_generic, ra);
+    } else {
+        AttributionArgs aa{};
+        aa.sw = sw;
+        aa.n_categories = c->h_cfg.n_categories;
+        aa.out = d_out;
+        launched = launch_attribution(s, c->hellinger2, c->unit_weights, aa);
+    }
+    if (!launched) return fail(LCHD_EDEVICE, "internal error: the %s kernel rejected its launch configuration", use.call);
     return LCHD_OK;
 }
 
@@ -3868,8 +3893,8 @@ struct RadialRequest {
     const int32_t* wf;       // DEVICE [n_pairs] or null
     int64_t n_pairs;
     double thr;
-    RadialEdges edges;
-    double* out;             // DEVICE [n_pairs][bins]
+    const PairConsumer& use;
+    double* out;             // DEVICE [n_pairs][consumer_row]
 };
 // One thresholded pass with slots of `cap` points: enqueued, waited for; *flags_out = its status words.
 static int radial_prims_pass(lchd_ctx* c, const RadialRequest& R, int cap, uint32_t* flags_out) {
@@ -3904,7 +3929,7 @@ static int radial_prims_pass(lchd_ctx* c, const RadialRequest& R, int cap, uint3
     sw.wf_index = R.wf;
     sw.n_pairs = R.n_pairs;
     sw.meta = st.pb.pair_meta;
-    if (int rc = radial_enqueue(c, sw, R.edges, R.out)) return rc;
+    if (int rc = consumer_enqueue(c, sw, R.use, R.out)) return rc;
     mark(c, 4);
     if (a->ev_used) { HIP_TRY(hipEventRecord(a->ev_used, s)); a->used_valid = true; }
     if (b->ev_used) { HIP_TRY(hipEventRecord(b->ev_used, s)); b->used_valid = true; }
@@ -3915,17 +3940,16 @@ static int radial_prims_pass(lchd_ctx* c, const RadialRequest& R, int cap, uint3
     return LCHD_OK;
 }
 
-extern "C" int lchd_radial_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
-                                          int64_t n_pairs, double thr, const double* edges, int32_t n_edges, double* d_out) {
+// The thresholded, device-resident call of either consumer (lchd_radial_primitives_dev / lchd_attribution_primitives_dev).
+static int consumer_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index, int64_t n_pairs,
+                                   double thr, const PairConsumer& use, double* d_out) {
     CTX_LOCK(c);
-    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
-    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
     if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
-    if (int rc = radial_limits(c)) return rc;
+    if (int rc = consumer_limits(c, use)) return rc;
     if (n_pairs <= 0) return LCHD_OK;
     if (!d_anchors || !d_out) return fail(LCHD_EVALUE, "null anchor / output pointer");
-    if (n_pairs > (int64_t)0x7FFFFFFF / kRadialMaxBins) return fail(LCHD_EUNSUPPORTED, "more than %d anchor pairs in one radial call (%lld): split the list", 0x7FFFFFFF / kRadialMaxBins, (long long)n_pairs);
+    if (n_pairs > (int64_t)0x7FFFFFFF / kRadialMaxBins) return fail(LCHD_EUNSUPPORTED, "more than %d anchor pairs in one %s call (%lld): split the list", 0x7FFFFFFF / kRadialMaxBins, use.call, (long long)n_pairs);
     if (!(thr > 0.0)) return fail(LCHD_EPANIC, "index out of bounds: threshold_distance = %g leaves every environment empty", thr);
     if (a->n == 0 || b->n == 0) return fail(LCHD_EPANIC, "index out of bounds: anchor pairs given for an empty structure");
     if (thr > a->reach || thr > b->reach)
@@ -3936,7 +3960,7 @@ extern "C" int lchd_radial_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud
     if (int rc = resolve_bbox(c, b)) return rc;
     const bool keep_sweep_record = c->last_sweep_valid;  // (host data: the record of the last scoring pass stands)
     c->last_valid = false;                               // (its arrays do not: the arena is laid out anew)
-    const RadialRequest R{a, b, d_anchors, d_wf_index, n_pairs, thr, radial_edges(edges, n_edges), d_out};
+    const RadialRequest R{a, b, d_anchors, d_wf_index, n_pairs, thr, use, d_out};
     // The retry ladder of the composition calls: an environment that did not fit its slot repeats the WHOLE pass with slots that hold
     // the largest one reported.  Every row is written again: a row's bits do not depend on the slot size.
     int cap = kEnvGroupCap, rc = fail(LCHD_EDEVICE, "environment capacity retry did not converge");
@@ -3947,7 +3971,7 @@ extern "C" int lchd_radial_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud
         const HostStatus h = *c->h_status;
         const int64_t want = std::max<int64_t>(std::max<int64_t>(h.max_env, h.max_bound / 3), cap + 1);
         if (h.max_env > (uint32_t)kRadialMaxPoints || cap > kRadialMaxPoints) {
-            rc = fail(LCHD_EUNSUPPORTED, "an environment holds %u points; a radial profile takes at most %d", h.max_env, kRadialMaxPoints);
+            rc = fail(LCHD_EUNSUPPORTED, "an environment holds %u points; %s takes at most %d", h.max_env, use.what, kRadialMaxPoints);
             break;
         }
         cap = std::min(next_pow2_host(want), kRadialMaxPoints + 1);
@@ -3956,15 +3980,19 @@ extern "C" int lchd_radial_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud
     if (keep_sweep_record) c->last_sweep_valid = true;  // (a grown workspace drops both records; this one is host data)
     return rc;
 }
-
-extern "C" int lchd_radial_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
-                                      int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
-                                      const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, const double* box_a,
-                                      const double* cell_a, const double* box_b, const double* cell_b, const double* edges, int32_t n_edges,
-                                      double* out) {
-    CTX_LOCK(c);
-    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+extern "C" int lchd_radial_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
+                                          int64_t n_pairs, double thr, const double* edges, int32_t n_edges, double* d_out) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
     if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
+    return consumer_primitives_dev(c, a, b, d_anchors, d_wf_index, n_pairs, thr, radial_consumer(edges, n_edges), d_out);
+}
+
+// ... and from host arrays, both sides as lchd_from_primitives takes them (lchd_radial_primitives / lchd_attribution_primitives).
+static int consumer_primitives_host(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
+                                    int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
+                                    const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, const double* box_a,
+                                    const double* cell_a, const double* box_b, const double* cell_b, const PairConsumer& use, double* out) {
+    CTX_LOCK(c);
     if ((box_a && cell_a) || (box_b && cell_b))
         return fail(LCHD_EVALUE, "a box and a cell were both given: a structure has one periodic box or one periodic cell");
     if (int rc = check_wf_index(cfg, wf_index, n_pairs)) return rc;
@@ -3984,7 +4012,7 @@ extern "C" int lchd_radial_primitives(lchd_ctx* c, const lchd_config* cfg, const
     HostTemps t(c);
     lchd_cloud *&ia = t.clouds[0], *&ib = t.clouds[1], *&ca = t.clouds[2], *&cb = t.clouds[3];
     char*& d_blk = t.d_blk;
-    const size_t K = (size_t)n_edges - 1;
+    const size_t K = consumer_row(c, use);
     const size_t o_wf = sizeof(int64_t) * 2 * (size_t)n_pairs, o_out = (o_wf + sizeof(int32_t) * (size_t)n_pairs + 255) & ~size_t(255);
     auto run = [&]() -> int {
         if (int rc = lchd_cloud_create(c, xyz_a, cat_a, tag_a, n_a, &ca)) return rc;
@@ -3996,14 +4024,24 @@ extern "C" int lchd_radial_primitives(lchd_ctx* c, const lchd_config* cfg, const
         HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)n_pairs * K));
         HIP_TRY(hipMemcpy(d_blk, anchors, o_wf, hipMemcpyHostToDevice));
         if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice));
-        if (int rc = lchd_radial_primitives_dev(c, ia ? ia : ca, ib ? ib : cb, reinterpret_cast<const int64_t*>(d_blk),
-                                                wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, n_pairs, thr, edges, n_edges,
-                                                reinterpret_cast<double*>(d_blk + o_out)))
+        if (int rc = consumer_primitives_dev(c, ia ? ia : ca, ib ? ib : cb, reinterpret_cast<const int64_t*>(d_blk),
+                                             wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, n_pairs, thr, use,
+                                             reinterpret_cast<double*>(d_blk + o_out)))
             return rc;
         HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)n_pairs * K, hipMemcpyDeviceToHost));
         return LCHD_OK;
     };
     return t.rc = run();
+}
+extern "C" int lchd_radial_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
+                                      int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
+                                      const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, const double* box_a,
+                                      const double* cell_a, const double* box_b, const double* cell_b, const double* edges, int32_t n_edges,
+                                      double* out) {
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
+    return consumer_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, box_a, cell_a, box_b,
+                                    cell_b, radial_consumer(edges, n_edges), out);
 }
 
 // Dense rows: pair r = row r of A against row r of B.  d_ma / d_mb: DEVICE rows [rows][cols], or null: distances from the side's
@@ -4011,7 +4049,7 @@ extern "C" int lchd_radial_primitives(lchd_ctx* c, const lchd_config* cfg, const
 // (the fused sort-and-sweep kernel never writes one).
 static int radial_dense(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, const double* d_ma, const double* d_mb, int64_t rows,
                         int64_t cols_a, int64_t cols_b, const MinImageCell* cell_a, const MinImageCell* cell_b, const int32_t* d_wf,
-                        const RadialEdges& ed, double* d_out) {
+                        const PairConsumer& use, double* d_out) {
     const int n_wf = c->h_cfg.n_wf;
     const int cap_a = next_pow2_host(cols_a), cap_b = next_pow2_host(cols_b);
     const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
@@ -4057,7 +4095,7 @@ static int radial_dense(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, c
     sw.wf_index = d_wf;
     sw.n_pairs = rows;
     sw.meta = d_meta;
-    if (int rc = radial_enqueue(c, sw, ed, d_out)) return rc;
+    if (int rc = consumer_enqueue(c, sw, use, d_out)) return rc;
     mark(c, 4);
     HIP_TRY(hipGetLastError());
     c->status_dirty = false;
@@ -4066,18 +4104,17 @@ static int radial_dense(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, c
     collect_times(c, 0, 4);
     return status_to_rc(f, DRV_DMXS);
 }
-static int radial_dense_check(lchd_ctx* c, int64_t cols_a, int64_t cols_b) {
-    if (int rc = radial_limits(c)) return rc;
+static int radial_dense_check(lchd_ctx* c, const PairConsumer& use, int64_t cols_a, int64_t cols_b) {
+    if (int rc = consumer_limits(c, use)) return rc;
     if (cols_a > kRadialMaxPoints || cols_b > kRadialMaxPoints)
-        return fail(LCHD_EUNSUPPORTED, "a radial profile takes dense rows of at most %d points (got %lld / %lld)", kRadialMaxPoints, (long long)cols_a, (long long)cols_b);
+        return fail(LCHD_EUNSUPPORTED, "%s takes dense rows of at most %d points (got %lld / %lld)", use.what, kRadialMaxPoints, (long long)cols_a, (long long)cols_b);
     return LCHD_OK;
 }
 
-extern "C" int lchd_radial_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
-                                      const double* cell_b, const double* edges, int32_t n_edges, double* d_out) {
+// The dense, device-resident call of either consumer (lchd_radial_coords_dev / lchd_attribution_coords_dev).
+static int consumer_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a, const double* cell_b,
+                               const PairConsumer& use, double* d_out) {
     CTX_LOCK(c);
-    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
-    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
     if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     if (a->sid || b->sid) return fail(LCHD_EVALUE, "from_coords takes single structures, not batches");
@@ -4089,26 +4126,30 @@ extern "C" int lchd_radial_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b,
     if (cell_b) if (int rc = min_image_record(cell_b, 0, rec_b)) return rc;
     if (a->n == 0) return LCHD_OK;
     if (!d_out) return fail(LCHD_EVALUE, "null output pointer");
-    if (int rc = radial_dense_check(c, a->n, b->n)) return rc;
+    if (int rc = radial_dense_check(c, use, a->n, b->n)) return rc;
     CTX_GUARD(c);
     if (int rc = resolve_bbox(c, a)) return rc;
     if (int rc = resolve_bbox(c, b)) return rc;
     const bool keep_sweep_record = c->last_sweep_valid;
     c->last_valid = false;
     const int rc = radial_dense(c, *a, *b, nullptr, nullptr, a->n, a->n, b->n, cell_a ? &rec_a : nullptr, cell_b ? &rec_b : nullptr, d_wf_index,
-                                radial_edges(edges, n_edges), d_out);
+                                use, d_out);
     if (keep_sweep_record) c->last_sweep_valid = true;
     return rc;
 }
+extern "C" int lchd_radial_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
+                                      const double* cell_b, const double* edges, int32_t n_edges, double* d_out) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
+    return consumer_coords_dev(c, a, b, d_wf_index, cell_a, cell_b, radial_consumer(edges, n_edges), d_out);
+}
 
-// Host arrays: coordinates (xyz set, dmx null; optional cells) or given rows (dmx [rows][cols], xyz null).
+// Host arrays: coordinates (xyz set, dmx null; optional cells) or given rows (dmx [rows][cols], xyz null).  The caller has checked c and cfg.
 static int radial_dense_host(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b, int64_t len_seq_b,
                              const double* xyz_a, const double* xyz_b, const double* dmx_a, const double* dmx_b, int64_t rows, int64_t cols_a,
-                             int64_t cols_b, const int32_t* wf_index, const double* cell_a, const double* cell_b, const double* edges,
-                             int32_t n_edges, double* out) {
+                             int64_t cols_b, const int32_t* wf_index, const double* cell_a, const double* cell_b, const PairConsumer& use,
+                             double* out) {
     CTX_LOCK(c);
-    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
-    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     MinImageCell rec_a, rec_b;
     if (cell_a) if (int rc = min_image_record(cell_a, 0, rec_a)) return rc;
@@ -4119,14 +4160,14 @@ static int radial_dense_host(lchd_ctx* c, const lchd_config* cfg, const int32_t*
     if (rows == 0) return LCHD_OK;
     if (cols_a > len_seq_a || cols_b > len_seq_b) return fail(LCHD_EPANIC, "index out of bounds: a distance row is longer than its seq");
     if (cols_a == 0 || cols_b == 0) return fail(LCHD_EPANIC, "index out of bounds: empty distance row (src/locohd.rs:74)");
-    if (int rc = radial_dense_check(c, cols_a, cols_b)) return rc;
+    if (int rc = radial_dense_check(c, use, cols_a, cols_b)) return rc;
     if (!out || (!xyz_a && !dmx_a) || (!xyz_b && !dmx_b)) return fail(LCHD_EVALUE, "null pointer");
     const bool keep_sweep_record = c->last_sweep_valid;
     c->last_valid = false;
     HostTemps t(c);
     lchd_cloud *&ca = t.clouds[0], *&cb = t.clouds[1];
     char*& d_blk = t.d_blk;
-    const size_t K = (size_t)n_edges - 1;
+    const size_t K = consumer_row(c, use);
     const size_t o_mb = dmx_a ? (sizeof(double) * (size_t)rows * (size_t)cols_a + 255) & ~size_t(255) : 0;
     const size_t o_wf = o_mb + (dmx_b ? sizeof(double) * (size_t)rows * (size_t)cols_b : 0);
     const size_t o_out = (o_wf + sizeof(int32_t) * (size_t)rows + 255) & ~size_t(255);
@@ -4139,8 +4180,8 @@ static int radial_dense_host(lchd_ctx* c, const lchd_config* cfg, const int32_t*
         if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice));
         if (int rc = radial_dense(c, *ca, *cb, dmx_a ? reinterpret_cast<const double*>(d_blk) : nullptr,
                                   dmx_b ? reinterpret_cast<const double*>(d_blk + o_mb) : nullptr, rows, cols_a, cols_b, cell_a ? &rec_a : nullptr,
-                                  cell_b ? &rec_b : nullptr, wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr,
-                                  radial_edges(edges, n_edges), reinterpret_cast<double*>(d_blk + o_out)))
+                                  cell_b ? &rec_b : nullptr, wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, use,
+                                  reinterpret_cast<double*>(d_blk + o_out)))
             return rc;
         HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)rows * K, hipMemcpyDeviceToHost));
         return LCHD_OK;
@@ -4149,19 +4190,70 @@ static int radial_dense_host(lchd_ctx* c, const lchd_config* cfg, const int32_t*
     if (keep_sweep_record) c->last_sweep_valid = true;
     return t.rc;
 }
-extern "C" int lchd_radial_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
-                                  int64_t len_seq_b, const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b, const int32_t* wf_index,
-                                  const double* cell_a, const double* cell_b, const double* edges, int32_t n_edges, double* out) {
+// from_coords' argument rule (both consumers)
+static int coords_lengths(const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b) {
     if (n_a != n_b)  // src/locohd.rs:420-428 via :472-475
         return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)n_a, (long long)n_b);
     if (n_a > 0 && (!xyz_a || !xyz_b)) return fail(LCHD_EVALUE, "null pointer");
-    return radial_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n_a, n_a, n_b, wf_index, cell_a, cell_b, edges,
-                             n_edges, out);
+    return LCHD_OK;
+}
+extern "C" int lchd_radial_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                  int64_t len_seq_b, const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b, const int32_t* wf_index,
+                                  const double* cell_a, const double* cell_b, const double* edges, int32_t n_edges, double* out) {
+    if (int rc = coords_lengths(xyz_a, n_a, xyz_b, n_b)) return rc;
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
+    return radial_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n_a, n_a, n_b, wf_index, cell_a, cell_b,
+                             radial_consumer(edges, n_edges), out);
 }
 extern "C" int lchd_radial_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
                                 int64_t len_seq_b, const double* dmx_a, const double* dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
                                 const int32_t* wf_index, const double* edges, int32_t n_edges, double* out) {
     if (rows > 0 && (!dmx_a || !dmx_b)) return fail(LCHD_EVALUE, "null pointer");
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
     return radial_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr, nullptr,
-                             edges, n_edges, out);
+                             radial_consumer(edges, n_edges), out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// score attribution by category (additive, not in the reference): which categories carry a pair's score
+// ------------------------------------------------------------------------------------------------
+// The radial calls above with the other consumer: the same store builds, record pass, capacity-repeat loop, limits and neutral hints;
+// the stores and records go to launch_attribution (lchd_attribution.hip), the output is [n][n_categories].  Hellinger distances only.
+static const PairConsumer kAttribution{{}, "an attribution", "attribution"};
+
+extern "C" int lchd_attribution_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
+                                               int64_t n_pairs, double thr, double* d_out) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    return consumer_primitives_dev(c, a, b, d_anchors, d_wf_index, n_pairs, thr, kAttribution, d_out);
+}
+extern "C" int lchd_attribution_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
+                                           int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
+                                           const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, const double* box_a,
+                                           const double* cell_a, const double* box_b, const double* cell_b, double* out) {
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    return consumer_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, box_a, cell_a, box_b,
+                                    cell_b, kAttribution, out);
+}
+extern "C" int lchd_attribution_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
+                                           const double* cell_b, double* d_out) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    return consumer_coords_dev(c, a, b, d_wf_index, cell_a, cell_b, kAttribution, d_out);
+}
+extern "C" int lchd_attribution_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                       int64_t len_seq_b, const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b,
+                                       const int32_t* wf_index, const double* cell_a, const double* cell_b, double* out) {
+    if (int rc = coords_lengths(xyz_a, n_a, xyz_b, n_b)) return rc;
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    return radial_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n_a, n_a, n_b, wf_index, cell_a, cell_b,
+                             kAttribution, out);
+}
+extern "C" int lchd_attribution_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                     int64_t len_seq_b, const double* dmx_a, const double* dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
+                                     const int32_t* wf_index, double* out) {
+    if (rows > 0 && (!dmx_a || !dmx_b)) return fail(LCHD_EVALUE, "null pointer");
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    return radial_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr, nullptr,
+                             kAttribution, out);
 }

@@ -431,6 +431,17 @@ void launch_pair_meta(hipStream_t s, const SweepArgs& a);  // k_pair_meta alone 
 void launch_radial_bounds(hipStream_t s, const DevConfig* cfg, int n_wf, const RadialEdges& edges, double* bounds);
 bool launch_radial(hipStream_t s, bool hellinger2_unit, const RadialArgs& a);  // false: nothing launched (more than kWideCategories categories)
 void init_radial_kernels();  // per device (dynamic LDS above 64 KB), called by init_device_kernels
+// Score attribution by category (lchd_attribution.hip): a pair's score split over the categories (Hellinger distances only), one row of
+// n_categories doubles per pair, from the stores and records a radial call reads.
+constexpr int kAttributionMaxCategories = 64;  // (the per-lane accumulator columns, 512 bytes per category and wavefront, live in LDS)
+struct AttributionArgs {
+    SweepArgs sw;          // as RadialArgs::sw
+    int32_t n_categories;  // DevConfig::n_categories (the launcher sizes the LDS with it)
+    double* out;           // [n_pairs][n_categories]
+};
+// false: nothing launched (more than kAttributionMaxCategories categories, 16-bit category stores)
+bool launch_attribution(hipStream_t s, bool exponent2, bool unit_weights, const AttributionArgs& a);
+void init_attribution_kernels();  // per device, as init_radial_kernels
 void launch_mark_overflow(hipStream_t s, const uint32_t* list_a, uint32_t na, const uint32_t* list_b, uint32_t nb, uint32_t* bits_a, uint32_t* bits_b);
 void launch_count_overflow(hipStream_t s, const OverflowSelect& a, unsigned long long* total);
 void launch_write_overflow(hipStream_t s, const OverflowSelect& a);

@@ -275,16 +275,17 @@ class DeviceSession:
         N.check(N.lib().lchd_composition_coords_dev(self._ctx, cloud, wf_ptr, N.dp(pc), C.c_void_p(out.data_ptr())))
         return out
 
-    def radial(self, cloud_a, cloud_b, anchors, threshold_distance: float, edges, out=None, wf_index=None):
-        """Radial profiles (LoCoHD.radial_from_primitives) of anchor pairs of two uploaded clouds of any kind (structures, batches,
-        frames buffers, image clouds).  anchors: torch int64 CUDA tensor [P][2]; edges: host array of K + 1 ascending distances;
-        wf_index: torch int32 CUDA tensor [P] or None; returns (or fills) a torch float64 CUDA tensor [P][K]
-        (lchd_radial_primitives_dev)."""
+    @staticmethod
+    def _radial_edges(edges) -> np.ndarray:
         ed = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
         N.check(N.lib().lchd_radial_validate(N.dp(ed), len(ed)))
+        return ed
+
+    # `ed`: the checked edges of a radial call (rows of len(ed) - 1 bins), or None: an attribution (rows of C categories)
+    def _pair_rows(self, ed, cloud_a, cloud_b, anchors, threshold_distance, out, wf_index):
         torch = self.torch
         assert anchors.is_cuda and anchors.dtype == torch.int64 and anchors.is_contiguous()
-        p, k = anchors.shape[0], len(ed) - 1
+        p, k = anchors.shape[0], int(self._cfg.n_categories) if ed is None else len(ed) - 1
         if out is None:
             out = torch.empty((p, k), dtype=torch.float64, device=anchors.device)
         assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= p * k
@@ -292,23 +293,21 @@ class DeviceSession:
         if wf_index is not None:
             assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= p
             wf_ptr = C.c_void_p(wf_index.data_ptr())
-        N.check(N.lib().lchd_radial_primitives_dev(self._ctx, cloud_a, cloud_b, C.c_void_p(anchors.data_ptr()), wf_ptr, p,
-                                                   float(threshold_distance), N.dp(ed), len(ed), C.c_void_p(out.data_ptr())))
+        head = (self._ctx, cloud_a, cloud_b, C.c_void_p(anchors.data_ptr()), wf_ptr, p, float(threshold_distance))
+        if ed is None:
+            N.check(N.lib().lchd_attribution_primitives_dev(*head, C.c_void_p(out.data_ptr())))
+        else:
+            N.check(N.lib().lchd_radial_primitives_dev(*head, N.dp(ed), len(ed), C.c_void_p(out.data_ptr())))
         return out
 
-    def radial_coords(self, cloud_a, cloud_b, edges, out=None, wf_index=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None):
-        """Radial profiles of the dense row pairs of two uploaded structures of equal size (LoCoHD.radial_from_coords): returns (or
-        fills) a torch float64 CUDA tensor [n][K].  `box_a` / `box_b` / `cell_a` / `cell_b` (keyword-only, host arrays): minimum-image
-        rows (lchd_radial_coords_dev)."""
-        ed = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
-        N.check(N.lib().lchd_radial_validate(N.dp(ed), len(ed)))
+    def _pair_rows_coords(self, ed, cloud_a, cloud_b, out, wf_index, box_a, box_b, cell_a, cell_b):
         for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
             if box is not None and cell is not None:
                 raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
         pc_a = dense_cells(box_a, cell_a, 1, "box_a", "cell_a")
         pc_b = dense_cells(box_b, cell_b, 1, "box_b", "cell_b")
         torch = self.torch
-        n, k = int(N.lib().lchd_cloud_size(cloud_a)), len(ed) - 1
+        n, k = int(N.lib().lchd_cloud_size(cloud_a)), int(self._cfg.n_categories) if ed is None else len(ed) - 1
         if out is None:
             out = torch.empty((n, k), dtype=torch.float64, device=torch.device("cuda", self.device))
         assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= n * k
@@ -316,9 +315,36 @@ class DeviceSession:
         if wf_index is not None:
             assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= n
             wf_ptr = C.c_void_p(wf_index.data_ptr())
-        N.check(N.lib().lchd_radial_coords_dev(self._ctx, cloud_a, cloud_b, wf_ptr, N.dp(pc_a), N.dp(pc_b), N.dp(ed), len(ed),
-                                               C.c_void_p(out.data_ptr())))
+        head = (self._ctx, cloud_a, cloud_b, wf_ptr, N.dp(pc_a), N.dp(pc_b))
+        if ed is None:
+            N.check(N.lib().lchd_attribution_coords_dev(*head, C.c_void_p(out.data_ptr())))
+        else:
+            N.check(N.lib().lchd_radial_coords_dev(*head, N.dp(ed), len(ed), C.c_void_p(out.data_ptr())))
         return out
+
+    def radial(self, cloud_a, cloud_b, anchors, threshold_distance: float, edges, out=None, wf_index=None):
+        """Radial profiles (LoCoHD.radial_from_primitives) of anchor pairs of two uploaded clouds of any kind (structures, batches,
+        frames buffers, image clouds).  anchors: torch int64 CUDA tensor [P][2]; edges: host array of K + 1 ascending distances;
+        wf_index: torch int32 CUDA tensor [P] or None; returns (or fills) a torch float64 CUDA tensor [P][K]
+        (lchd_radial_primitives_dev)."""
+        return self._pair_rows(self._radial_edges(edges), cloud_a, cloud_b, anchors, threshold_distance, out, wf_index)
+
+    def radial_coords(self, cloud_a, cloud_b, edges, out=None, wf_index=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None):
+        """Radial profiles of the dense row pairs of two uploaded structures of equal size (LoCoHD.radial_from_coords): returns (or
+        fills) a torch float64 CUDA tensor [n][K].  `box_a` / `box_b` / `cell_a` / `cell_b` (keyword-only, host arrays): minimum-image
+        rows (lchd_radial_coords_dev)."""
+        return self._pair_rows_coords(self._radial_edges(edges), cloud_a, cloud_b, out, wf_index, box_a, box_b, cell_a, cell_b)
+
+    def attribution(self, cloud_a, cloud_b, anchors, threshold_distance: float, out=None, wf_index=None):
+        """Score attribution by category (LoCoHD.attribution_from_primitives) of anchor pairs of two uploaded clouds of any kind.
+        anchors: torch int64 CUDA tensor [P][2]; wf_index: torch int32 CUDA tensor [P] or None; returns (or fills) a torch float64
+        CUDA tensor [P][C] (lchd_attribution_primitives_dev)."""
+        return self._pair_rows(None, cloud_a, cloud_b, anchors, threshold_distance, out, wf_index)
+
+    def attribution_coords(self, cloud_a, cloud_b, out=None, wf_index=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None):
+        """Score attribution by category of the dense row pairs of two uploaded structures of equal size
+        (LoCoHD.attribution_from_coords): returns (or fills) a torch float64 CUDA tensor [n][C] (lchd_attribution_coords_dev)."""
+        return self._pair_rows_coords(None, cloud_a, cloud_b, out, wf_index, box_a, box_b, cell_a, cell_b)
 
     def from_coords_ensemble(self, batch, pairs=None, out=None, wf_index=None, excluded=None, *, boxes=None, cells=None):
         """LoCoHD.from_coords_ensemble on a batch from `upload_batch` (structures of equal size) or a frames buffer: row r of
