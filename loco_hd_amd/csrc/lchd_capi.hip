@@ -1191,7 +1191,7 @@ static PrepSide prep_side(const CloudView& cv, const GridView& gv, const SideBuf
     return ps;
 }
 
-// The environment store of one thresholded pass, and what its consumer (a sweep: prims_enqueue; the profile kernel: comp_prims_pass)
+// The environment store of one thresholded pass, and what its consumer (a sweep: prims_enqueue; a profile kernel: consumer_prims_pass)
 // reads next to it.
 struct PrimsStore {
     bool begun = false;     // begin_pass has succeeded and the prologue is on the stream: the pass counts, and the members below describe it
@@ -3556,270 +3556,13 @@ extern "C" int lchd_ensemble_from_coords_periodic(lchd_ctx* c, const lchd_config
 }
 
 // ------------------------------------------------------------------------------------------------
-// local composition profiles (additive, not in the reference): one-sided passes over the environment store
+// profile calls (additive, not in the reference): local composition, radial score profiles, score attribution by category
 // ------------------------------------------------------------------------------------------------
-// A profile call builds the environments of ONE list of anchors with the builder of the scoring passes (build_prims_store; dense rows:
-// carve_row_store + k_env_rows) and hands the store to launch_profile instead of a sweep.  It plans with neutral hints and leaves the
-// context's hints and records alone: the scoring passes before and after it pick their kernels as if it had not run.
-struct CompRequest {
-    lchd_cloud* cl;
-    const int64_t* anchors;  // DEVICE [n] atom indices
-    const int32_t* wf;       // DEVICE [n] or null
-    int64_t n;
-    double thr;
-    double* out;             // DEVICE [n][n_categories]
-};
-
-// One pass with slots of `cap` points: enqueued, waited for; *flags_out = its status words.
-static int comp_prims_pass(lchd_ctx* c, const CompRequest& R, int cap, uint32_t* flags_out) {
-    lchd_cloud* a = R.cl;
-    const int n_wf = c->h_cfg.n_wf;
-    PassQuery q;
-    q.n_a = q.n_b = a->n; q.n_pairs = R.n;
-    q.same_object = true;  // the pair list is (i, i): both columns share one cell list, one set of slots, one store
-    q.has_wf_index = R.wf != nullptr;
-    q.cap = cap;
-    q.n_categories = c->h_cfg.n_categories; q.n_wf = n_wf;
-    q.deterministic = c->deterministic; q.tag_mode = c->h_cfg.tag_mode;
-    q.tune = c->tune;
-    q.tune.no_share = false;
-    PassPlan plan = plan_pass(q);
-    // the profile kernel reads F keys whatever the dictionary's size or the environment kernel: set 0 keeps what the environment kernel
-    // writes (one function: its F values; a dictionary: the distances), k_env_key_sets fills one set per function behind it
-    plan.dict_sets = n_wf > 1;
-    plan.key_sets = n_wf > 1 ? n_wf + 1 : 1;
-    plan.pre_words = 0;
-    PrimsStore st;
-    const int built = build_prims_store(c, a, a, nullptr, R.anchors, R.n, R.thr, q, plan, st);
-    if (st.begun) ++c->n_passes;
-    if (built) return built;
-    hipStream_t s = c->stream;
-    ProfileArgs pa{};
-    pa.cfg = c->d_cfg; pa.env = st.env[0]; pa.anchors = R.anchors; pa.slot = st.pb.a.slot; pa.n_atoms = a->n; pa.wf_index = R.wf;
-    pa.n = R.n; pa.out = R.out; pa.hst = c->h_status; pa.n_categories = c->h_cfg.n_categories;
-    launch_profile(s, pa);
-    launch_profile_publish(s, c->d_status, c->h_status, c->seq);
-    mark(c, 4);
-    if (a->ev_used) { HIP_TRY(hipEventRecord(a->ev_used, s)); a->used_valid = true; }
-    HIP_TRY(hipGetLastError());
-    c->status_dirty = false;  // launch_profile_publish leaves the device status clean
-    if (int rc = wait_pass(c, flags_out)) return rc;
-    collect_times(c, 0, 4);
-    return LCHD_OK;
-}
-
-extern "C" int lchd_composition_primitives_dev(lchd_ctx* c, lchd_cloud* cl, const int64_t* d_anchors, const int32_t* d_wf_index,
-                                               int64_t n_anchors, double thr, double* d_out) {
-    CTX_LOCK(c);
-    if (!c || !cl) return fail(LCHD_EVALUE, "null argument");
-    if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
-    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
-    c->last_valid = c->last_sweep_valid = false;
-    if (n_anchors <= 0) return LCHD_OK;
-    if (!d_anchors || !d_out) return fail(LCHD_EVALUE, "null anchor / output pointer");
-    if (n_anchors > (int64_t)0x3FFFFFFF) return fail(LCHD_EUNSUPPORTED, "more than 2^30 - 1 anchors in one call (%lld): split the list", (long long)n_anchors);
-    if (!(thr > 0.0)) return fail(LCHD_EPANIC, "index out of bounds: threshold_distance = %g leaves every environment empty", thr);
-    if (cl->n == 0) return fail(LCHD_EPANIC, "index out of bounds: anchors given for an empty structure");
-    if (thr > cl->reach) return fail(LCHD_EVALUE, "threshold_distance = %g is beyond the reach %g the periodic images were built with", thr, cl->reach);
-    if (!std::isfinite(thr)) thr = 1.7e308;
-    CTX_GUARD(c);
-    if (int rc = resolve_bbox(c, cl)) return rc;
-    const CompRequest R{cl, d_anchors, d_wf_index, n_anchors, thr, d_out};
-    // The retry ladder: an environment that did not fit its slot repeats the pass with slots that hold the largest one reported (a
-    // candidate-table overflow of k_env_group reports a bound; k_env_cells then counts).  Every row is written again: a row's bits do not
-    // depend on the slot size.
-    int cap = kEnvGroupCap;
-    for (int attempt = 0; attempt < 8; ++attempt) {
-        uint32_t f = 0;
-        if (int rc = comp_prims_pass(c, R, cap, &f)) return rc;
-        if ((f & ST_BAD_ANCHOR) || !(f & ST_ENV_OVERFLOW)) return status_to_rc(f & ~(uint32_t)ST_ENV_OVERFLOW, DRV_PRIMS);
-        const HostStatus h = *c->h_status;
-        const int64_t want = std::max<int64_t>(std::max<int64_t>(h.max_env, h.max_bound / 3), cap + 1);
-        if (h.max_env >= (uint32_t)kProfMaxPoints || cap >= kProfMaxPoints)
-            return fail(LCHD_EUNSUPPORTED, "an environment holds %u points; a composition profile takes at most %d", h.max_env, kProfMaxPoints - 1);
-        cap = std::min(next_pow2_host(want), kProfMaxPoints);
-    }
-    return fail(LCHD_EDEVICE, "environment capacity retry did not converge");
-}
-
-// Host arrays, one structure, optionally in an orthorhombic box or a triclinic cell (at most one of the two): the structure goes to the
-// device as a cloud of its own, a periodic one is replaced by its image cloud (reach = the threshold), and the pass is the one above.
-static int composition_primitives_host(lchd_ctx* c, const lchd_config* cfg, const double* xyz, const int32_t* cat, const int32_t* tag,
-                                       int64_t n, const int64_t* anchors, const int32_t* wf_index, int64_t n_anchors, double thr,
-                                       const double* box, const double* cell, double* out) {
-    CTX_LOCK(c);
-    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
-    if (box && cell) return fail(LCHD_EVALUE, "a box and a cell were both given: a structure has one periodic box or one periodic cell");
-    if (int rc = check_wf_index(cfg, wf_index, n_anchors)) return rc;
-    if (n < 0 || n > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "structure size out of range");
-    if (box) if (int rc = lchd_box_validate(box, 1, thr)) return rc;
-    if (cell) if (int rc = lchd_cell_validate(cell, 1, thr)) return rc;
-    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
-    if (n_anchors > 0 && (!anchors || !out)) return fail(LCHD_EVALUE, "null anchor / output pointer");
-    for (int64_t p = 0; p < n_anchors; ++p)  // (an index beyond the structure would name a ghost atom of an image cloud)
-        if (anchors[p] < 0 || anchors[p] >= n)
-            return fail(LCHD_EPANIC, "index out of bounds: an anchor index is outside its structure (src/locohd.rs:521)");
-    CTX_GUARD(c);
-    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
-    if (n_anchors <= 0) return LCHD_OK;
-    HostTemps t(c);
-    lchd_cloud *&img = t.clouds[0], *&cl = t.clouds[1];
-    char*& d_blk = t.d_blk;
-    const size_t C = (size_t)cfg->n_categories;
-    const size_t o_wf = sizeof(int64_t) * (size_t)n_anchors, o_out = (o_wf + sizeof(int32_t) * (size_t)n_anchors + 255) & ~size_t(255);
-    auto run = [&]() -> int {
-        if (int rc = lchd_cloud_create(c, xyz, cat, tag, n, &cl)) return rc;
-        if (box) if (int rc = lchd_cloud_create_images(c, cl, box, 1, thr, &img)) return rc;
-        if (cell) if (int rc = lchd_cloud_create_images_cell(c, cl, cell, 1, thr, &img)) return rc;
-        HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)n_anchors * C));
-        HIP_TRY(hipMemcpy(d_blk, anchors, o_wf, hipMemcpyHostToDevice));
-        if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)n_anchors, hipMemcpyHostToDevice));
-        if (int rc = lchd_composition_primitives_dev(c, img ? img : cl, reinterpret_cast<const int64_t*>(d_blk),
-                                                     wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, n_anchors, thr,
-                                                     reinterpret_cast<double*>(d_blk + o_out)))
-            return rc;
-        HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)n_anchors * C, hipMemcpyDeviceToHost));
-        return LCHD_OK;
-    };
-    return t.rc = run();
-}
-extern "C" int lchd_composition_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz, const int32_t* cat, const int32_t* tag,
-                                           int64_t n, const int64_t* anchors, const int32_t* wf_index, int64_t n_anchors, double thr,
-                                           double* out) {
-    return composition_primitives_host(c, cfg, xyz, cat, tag, n, anchors, wf_index, n_anchors, thr, nullptr, nullptr, out);
-}
-extern "C" int lchd_composition_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const double* xyz, const int32_t* cat,
-                                                    const int32_t* tag, int64_t n, const int64_t* anchors, const int32_t* wf_index,
-                                                    int64_t n_anchors, double thr, const double* box, const double* cell, double* out) {
-    return composition_primitives_host(c, cfg, xyz, cat, tag, n, anchors, wf_index, n_anchors, thr, box, cell, out);
-}
-
-// Dense rows of one structure: row r is the whole structure seen from atom r (from_coords) or the given distance row r (from_dmxs).
-// d_m: DEVICE rows [rows][cols], or null: distances from the coordinates of `a`, through the minimum-image row producer with a cell.
-// The rows go through k_env_rows, which materialises the store (the fused sort-and-sweep kernel never writes one).
-static int comp_dense(lchd_ctx* c, const lchd_cloud& a, const double* d_m, int64_t rows, int64_t cols, const MinImageCell* cell,
-                      const int32_t* d_wf, double* d_out) {
-    const int n_wf = c->h_cfg.n_wf;
-    const int cap = next_pow2_host(cols);
-    const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
-    const size_t sets = n_wf > 1 ? (size_t)n_wf + 1 : 1;
-    EnvStore e{};
-    double* w_m = nullptr;
-    for (int dry = 1; dry >= 0; --dry) {
-        Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
-        e = carve_row_store(ar, rows, cap, sets, cat16);
-        if (cell) w_m = ar.take<double>((size_t)rows * cols);
-        if (dry) if (int rc = ensure_ws(c, ar.off + 4096)) return rc;
-    }
-    e.cdf_keys = n_wf == 1 ? 1 : 0;
-    hipStream_t s = c->stream;
-    if (int rc = begin_pass(c)) return rc;
-    c->status_dirty = true;
-    mark(c, 0);
-    if (cell) {
-        produce_rows(s, a, cols, rows, cell, w_m);
-        d_m = w_m;
-    }
-    mark(c, 1);
-    mark(c, 2);
-    if (!launch_env_rows(s, cap, c->d_cfg, a.view(cat16), d_m, cols, rows, cols, diag2(a), e, c->d_status))
-        return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
-    if (c->deterministic) launch_env_canon(s, e, e, rows, 0, nullptr);
-    if (n_wf > 1) {
-        launch_profile_rows(s, c->d_status, rows);
-        launch_env_key_sets(s, c->d_cfg, e, e, n_wf, rows, c->d_status);
-        e.key += e.set_stride;
-        e.cdf_keys = n_wf;
-    }
-    mark(c, 3);
-    ProfileArgs pa{};
-    pa.cfg = c->d_cfg; pa.env = e; pa.wf_index = d_wf; pa.n = rows; pa.out = d_out; pa.hst = c->h_status; pa.n_categories = c->h_cfg.n_categories;
-    launch_profile(s, pa);
-    launch_profile_publish(s, c->d_status, c->h_status, c->seq);
-    mark(c, 4);
-    HIP_TRY(hipGetLastError());
-    c->status_dirty = false;
-    uint32_t f = 0;
-    if (int rc = wait_pass(c, &f)) return rc;
-    collect_times(c, 0, 4);
-    return status_to_rc(f, DRV_DMXS);
-}
-static int comp_dense_check(lchd_ctx* c, int64_t cols) {
-    if (cols >= kProfMaxPoints)
-        return fail(LCHD_EUNSUPPORTED, "a composition profile takes dense rows of at most %d points (got %lld)", kProfMaxPoints - 1, (long long)cols);
-    return LCHD_OK;
-}
-
-extern "C" int lchd_composition_coords_dev(lchd_ctx* c, lchd_cloud* cl, const int32_t* d_wf_index, const double* cell, double* d_out) {
-    CTX_LOCK(c);
-    if (!c || !cl) return fail(LCHD_EVALUE, "null argument");
-    if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
-    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
-    if (cl->sid) return fail(LCHD_EVALUE, "from_coords takes single structures, not batches");
-    if (cell && cl->images) return fail(LCHD_EVALUE, "a periodic dense call takes the structures themselves, not their image clouds");
-    MinImageCell rec;
-    if (cell) if (int rc = min_image_record(cell, 0, rec)) return rc;
-    c->last_valid = c->last_sweep_valid = false;
-    if (cl->n == 0) return LCHD_OK;
-    if (!d_out) return fail(LCHD_EVALUE, "null output pointer");
-    if (int rc = comp_dense_check(c, cl->n)) return rc;
-    CTX_GUARD(c);
-    if (int rc = resolve_bbox(c, cl)) return rc;
-    return comp_dense(c, *cl, nullptr, cl->n, cl->n, cell ? &rec : nullptr, d_wf_index, d_out);
-}
-
-// Host arrays: coordinates (xyz set, dmx null; optional cell) or given rows (dmx [rows][cols], xyz null).
-static int composition_dense_host(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t len_seq, const double* xyz, const double* dmx,
-                                  int64_t rows, int64_t cols, const int32_t* wf_index, const double* cell, double* out) {
-    CTX_LOCK(c);
-    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
-    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
-    MinImageCell rec;
-    if (cell) if (int rc = min_image_record(cell, 0, rec)) return rc;
-    CTX_GUARD(c);
-    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
-    if (int rc = check_wf_index(cfg, wf_index, rows)) return rc;
-    c->last_valid = c->last_sweep_valid = false;
-    if (rows == 0) return LCHD_OK;
-    if (cols > len_seq) return fail(LCHD_EPANIC, "index out of bounds: a distance row is longer than its seq");
-    if (cols == 0) return fail(LCHD_EPANIC, "index out of bounds: empty distance row (src/locohd.rs:74)");
-    if (int rc = comp_dense_check(c, cols)) return rc;
-    if (!out || (!xyz && !dmx)) return fail(LCHD_EVALUE, "null pointer");
-    HostTemps t(c);
-    lchd_cloud*& cl = t.clouds[0];
-    char*& d_blk = t.d_blk;
-    const size_t C = (size_t)cfg->n_categories;
-    const size_t o_wf = dmx ? sizeof(double) * (size_t)rows * (size_t)cols : 0, o_out = (o_wf + sizeof(int32_t) * (size_t)rows + 255) & ~size_t(255);
-    auto run = [&]() -> int {
-        if (int rc = lchd_cloud_create(c, xyz, seq, nullptr, cols, &cl)) return rc;  // (given rows: the cloud carries the categories alone)
-        HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)rows * C));
-        if (dmx) HIP_TRY(hipMemcpy(d_blk, dmx, o_wf, hipMemcpyHostToDevice));
-        if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice));
-        if (int rc = comp_dense(c, *cl, dmx ? reinterpret_cast<const double*>(d_blk) : nullptr, rows, cols, cell ? &rec : nullptr,
-                                wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, reinterpret_cast<double*>(d_blk + o_out)))
-            return rc;
-        HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)rows * C, hipMemcpyDeviceToHost));
-        return LCHD_OK;
-    };
-    return t.rc = run();
-}
-extern "C" int lchd_composition_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t len_seq, const double* xyz, int64_t n,
-                                       const int32_t* wf_index, const double* cell, double* out) {
-    return composition_dense_host(c, cfg, seq, len_seq, xyz, nullptr, n, n, wf_index, cell, out);
-}
-extern "C" int lchd_composition_dmx(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t len_seq, const double* dmx, int64_t rows,
-                                    int64_t cols, const int32_t* wf_index, double* out) {
-    if (rows > 0 && !dmx) return fail(LCHD_EVALUE, "null pointer");
-    return composition_dense_host(c, cfg, seq, len_seq, nullptr, dmx, rows, cols, wf_index, nullptr, out);
-}
-
-// ------------------------------------------------------------------------------------------------
-// radial score profiles (additive, not in the reference): a pair's integrand resolved over distance bins
-// ------------------------------------------------------------------------------------------------
-// A radial call builds the environments of a pair list with the builders of the scoring passes (build_prims_store; dense rows:
-// carve_row_store + produce_rows + k_env_rows), runs the record pass (k_pair_meta, which also hands the status over) and gives stores
-// and records to launch_radial instead of a sweep.  Like a composition call it plans with neutral hints and leaves the context's hints
-// and sweep record alone: the scoring passes before and after it pick their kernels as if it had not run.
+// A profile call builds the environments of a list of anchors (composition) or anchor pairs (radial, attribution) with the builders of
+// the scoring passes (build_prims_store; dense rows: carve_row_store + produce_rows + k_env_rows) and hands the stores to its consumer's
+// kernel instead of a sweep.  It plans with neutral hints and leaves the context's hints alone: the scoring passes before and after it
+// pick their kernels as if it had not run.  The record of the last scoring pass's arrays goes (the arena is laid out anew); the sweep
+// record, host data, stands across a radial or an attribution call, while a composition call clears it with the other.
 extern "C" int lchd_radial_validate(const double* edges, int32_t n_edges) {
     if (!edges) return fail(LCHD_EVALUE, "null edges");
     if (n_edges < 2) return fail(LCHD_EVALUE, "a radial profile needs at least 2 edges (one bin), got %d", n_edges);
@@ -3832,25 +3575,33 @@ extern "C" int lchd_radial_validate(const double* edges, int32_t n_edges) {
     }
     return LCHD_OK;
 }
-// The consumer of a radial pass's stores and pair records: the radial kernel (edges.n >= 2) or -- score attribution by category, the
-// section below -- the attribution kernel (edges.n == 0).  Everything up to the consumer's launch is one code path.
+// The consumer of a profile pass's stores: the profile kernel on ONE store (sides == 1: composition, lchd_profile.hip), or, on two
+// stores and the pair records of k_pair_meta, the radial kernel (edges.n >= 2) or the attribution kernel (edges.n == 0).  Everything
+// up to the consumer's launch is one code path; it asks which consumer it serves in the three helpers below, in consumer_list_limit,
+// in consumer_drop_records and where consumer_prims_pass fills a one-sided query; what else differs is data of the descriptor.
 struct PairConsumer {
-    RadialEdges edges;  // n == 0: attribution by category
-    const char* what;   // in messages: "a radial profile" / "an attribution"
-    const char* call;   // "radial" / "attribution"
+    RadialEdges edges;  // n >= 2: a radial profile
+    const char* what;   // in messages: "a composition profile" / "a radial profile" / "an attribution"
+    const char* call;   // "composition" / "radial" / "attribution"
+    const char* items;  // what its list holds: "anchors" / "anchor pairs"
+    int sides;          // structures (stores) of a call, columns of its list: 1 composition, 2 the others
+    bool records;       // its kernel reads the pair records of k_pair_meta (a dense pass carves them)
 };
+static const PairConsumer kComposition{{}, "a composition profile", "composition", "anchors", 1, false};
+static const PairConsumer kAttribution{{}, "an attribution", "attribution", "anchor pairs", 2, true};
 static PairConsumer radial_consumer(const double* edges, int32_t n_edges) {
-    PairConsumer use{{}, "a radial profile", "radial"};
+    PairConsumer use{{}, "a radial profile", "radial", "anchor pairs", 2, true};
     use.edges.n = n_edges;
     for (int32_t k = 0; k < n_edges; ++k) use.edges.e[k] = edges[k];
     return use;
 }
-// doubles per pair in the consumer's output: the bins / the categories of the context's configuration (at most kRadialMaxBins both)
+// doubles per entry in the consumer's output: the bins / the categories of the context's configuration
 static size_t consumer_row(const lchd_ctx* c, const PairConsumer& use) {
     return use.edges.n ? (size_t)use.edges.n - 1 : (size_t)c->h_cfg.n_categories;
 }
 static int consumer_limits(const lchd_ctx* c, const PairConsumer& use) {
     static const char* names[4] = {"Hellinger", "Kolmogorov-Smirnov", "Kullback-Leibler", "Renyi"};
+    if (use.sides == 1) return LCHD_OK;  // a composition has no distance, and its kernel takes every category count
     const int most = use.edges.n ? kWideCategories : kAttributionMaxCategories;
     if (!use.edges.n && c->h_cfg.sd_kind != SD_HELLINGER)
         return fail(LCHD_EUNSUPPORTED, "an attribution splits the Hellinger distance over the categories; the %s distance is no sum of per-category terms",
@@ -3859,11 +3610,20 @@ static int consumer_limits(const lchd_ctx* c, const PairConsumer& use) {
         return fail(LCHD_EUNSUPPORTED, "%s takes at most %d categories (got %d)", use.what, most, c->h_cfg.n_categories);
     return LCHD_OK;
 }
-// Records, (bounds) and the kernel behind a finished store build (stream order); sw: the stores, the pair list and its slots.
+// The consumer's kernel behind a finished store build (stream order), with what hands the status over: the record pass (k_pair_meta)
+// in front of a pair kernel, launch_profile_publish behind the profile kernel.  sw: the stores, the list and its slots.
 static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use, double* d_out) {
     const int n_wf = c->h_cfg.n_wf;
-    if (int rc = grow_block(c->d_radial_bounds, c->radial_bounds_cap, sizeof(double) * (size_t)n_wf * (size_t)use.edges.n)) return rc;
     hipStream_t s = c->stream;
+    if (use.sides == 1) {
+        ProfileArgs pa{};
+        pa.cfg = c->d_cfg; pa.env = sw.env_a; pa.anchors = sw.anchors; pa.slot = sw.slot_a; pa.n_atoms = sw.n_slot_a; pa.wf_index = sw.wf_index;
+        pa.n = sw.n_pairs; pa.out = d_out; pa.hst = c->h_status; pa.n_categories = c->h_cfg.n_categories;
+        launch_profile(s, pa);
+        launch_profile_publish(s, c->d_status, c->h_status, c->seq);
+        return LCHD_OK;
+    }
+    if (int rc = grow_block(c->d_radial_bounds, c->radial_bounds_cap, sizeof(double) * (size_t)n_wf * (size_t)use.edges.n)) return rc;
     fill_sweep_args(c, sw);
     launch_pair_meta(s, sw);
     bool launched;
@@ -3886,35 +3646,52 @@ static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use,
     if (!launched) return fail(LCHD_EDEVICE, "internal error: the %s kernel rejected its launch configuration", use.call);
     return LCHD_OK;
 }
+// The longest list of one thresholded call.
+static int consumer_list_limit(const PairConsumer& use, int64_t n) {
+    if (use.sides == 1) {
+        if (n > (int64_t)0x3FFFFFFF) return fail(LCHD_EUNSUPPORTED, "more than 2^30 - 1 anchors in one call (%lld): split the list", (long long)n);
+        return LCHD_OK;
+    }
+    if (n > (int64_t)0x7FFFFFFF / kRadialMaxBins) return fail(LCHD_EUNSUPPORTED, "more than %d anchor pairs in one %s call (%lld): split the list", 0x7FFFFFFF / kRadialMaxBins, use.call, (long long)n);
+    return LCHD_OK;
+}
+// A composition call drops both records of the last scoring pass where it starts; the pair consumers keep the sweep record (below).
+static void consumer_drop_records(lchd_ctx* c, const PairConsumer& use) {
+    if (use.sides == 1) c->last_valid = c->last_sweep_valid = false;
+}
 
-struct RadialRequest {
-    lchd_cloud *a, *b;
-    const int64_t* anchors;  // DEVICE [n_pairs][2]
-    const int32_t* wf;       // DEVICE [n_pairs] or null
-    int64_t n_pairs;
+struct ConsumerRequest {
+    lchd_cloud* cl[2];       // [use.sides]
+    const int64_t* anchors;  // DEVICE [n][use.sides]
+    const int32_t* wf;       // DEVICE [n] or null
+    int64_t n;
     double thr;
     const PairConsumer& use;
-    double* out;             // DEVICE [n_pairs][consumer_row]
+    double* out;             // DEVICE [n][consumer_row]
 };
 // One thresholded pass with slots of `cap` points: enqueued, waited for; *flags_out = its status words.
-static int radial_prims_pass(lchd_ctx* c, const RadialRequest& R, int cap, uint32_t* flags_out) {
-    lchd_cloud *a = R.a, *b = R.b;
+static int consumer_prims_pass(lchd_ctx* c, const ConsumerRequest& R, int cap, uint32_t* flags_out) {
+    const int sides = R.use.sides;
+    lchd_cloud *a = R.cl[0], *b = R.cl[sides - 1];
     const int n_wf = c->h_cfg.n_wf;
     PassQuery q;
-    q.n_a = a->n; q.n_b = b->n; q.n_pairs = R.n_pairs;
-    q.same_object = a == b;
+    q.n_a = a->n; q.n_b = b->n; q.n_pairs = R.n;
+    q.same_object = a == b;  // (one side: the pair list is (i, i), both columns share one cell list, one set of slots, one store)
     q.has_wf_index = R.wf != nullptr;
     q.cap = cap;
     q.n_categories = c->h_cfg.n_categories; q.n_wf = n_wf;
     q.deterministic = c->deterministic; q.tag_mode = c->h_cfg.tag_mode;
     q.tune = c->tune;
+    if (sides == 1) q.tune.no_share = false;
     PassPlan plan = plan_pass(q);
-    // the kernel reads F keys whatever the dictionary's size or the environment kernel (comp_prims_pass: the same amendment)
+    // the consumer's kernel reads F keys whatever the dictionary's size or the environment kernel: set 0 keeps what the environment kernel
+    // writes (one function: its F values; a dictionary: the distances), k_env_key_sets fills one set per function behind it
     plan.dict_sets = n_wf > 1;
     plan.key_sets = n_wf > 1 ? n_wf + 1 : 1;
     plan.pre_words = 0;
     PrimsStore st;
-    const int built = build_prims_store(c, a, b, R.anchors, nullptr, R.n_pairs, R.thr, q, plan, st);
+    const int built = sides == 1 ? build_prims_store(c, a, a, nullptr, R.anchors, R.n, R.thr, q, plan, st)
+                                 : build_prims_store(c, a, b, R.anchors, nullptr, R.n, R.thr, q, plan, st);
     if (st.begun) ++c->n_passes;
     if (built) return built;
     hipStream_t s = c->stream;
@@ -3927,171 +3704,174 @@ static int radial_prims_pass(lchd_ctx* c, const RadialRequest& R, int cap, uint3
     sw.n_slot_a = a->n;
     sw.n_slot_b = b->n;
     sw.wf_index = R.wf;
-    sw.n_pairs = R.n_pairs;
+    sw.n_pairs = R.n;
     sw.meta = st.pb.pair_meta;
     if (int rc = consumer_enqueue(c, sw, R.use, R.out)) return rc;
     mark(c, 4);
-    if (a->ev_used) { HIP_TRY(hipEventRecord(a->ev_used, s)); a->used_valid = true; }
-    if (b->ev_used) { HIP_TRY(hipEventRecord(b->ev_used, s)); b->used_valid = true; }
+    for (int k = 0; k < sides; ++k)
+        if (R.cl[k]->ev_used) { HIP_TRY(hipEventRecord(R.cl[k]->ev_used, s)); R.cl[k]->used_valid = true; }
     HIP_TRY(hipGetLastError());
-    c->status_dirty = false;  // the record pass leaves the device status clean
+    c->status_dirty = false;  // the record pass / launch_profile_publish leaves the device status clean
     if (int rc = wait_pass(c, flags_out)) return rc;
     collect_times(c, 0, 4);
     return LCHD_OK;
 }
 
-// The thresholded, device-resident call of either consumer (lchd_radial_primitives_dev / lchd_attribution_primitives_dev).
-static int consumer_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index, int64_t n_pairs,
-                                   double thr, const PairConsumer& use, double* d_out) {
+// The thresholded, device-resident call of a consumer (lchd_{composition,radial,attribution}_primitives_dev); cl: [use.sides].
+static int consumer_primitives_dev(lchd_ctx* c, lchd_cloud* const* cl, const int64_t* d_anchors, const int32_t* d_wf_index, int64_t n, double thr,
+                                   const PairConsumer& use, double* d_out) {
     CTX_LOCK(c);
+    lchd_cloud *a = cl[0], *b = cl[use.sides - 1];
     if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    consumer_drop_records(c, use);
     if (int rc = consumer_limits(c, use)) return rc;
-    if (n_pairs <= 0) return LCHD_OK;
+    if (n <= 0) return LCHD_OK;
     if (!d_anchors || !d_out) return fail(LCHD_EVALUE, "null anchor / output pointer");
-    if (n_pairs > (int64_t)0x7FFFFFFF / kRadialMaxBins) return fail(LCHD_EUNSUPPORTED, "more than %d anchor pairs in one %s call (%lld): split the list", 0x7FFFFFFF / kRadialMaxBins, use.call, (long long)n_pairs);
+    if (int rc = consumer_list_limit(use, n)) return rc;
     if (!(thr > 0.0)) return fail(LCHD_EPANIC, "index out of bounds: threshold_distance = %g leaves every environment empty", thr);
-    if (a->n == 0 || b->n == 0) return fail(LCHD_EPANIC, "index out of bounds: anchor pairs given for an empty structure");
+    if (a->n == 0 || b->n == 0) return fail(LCHD_EPANIC, "index out of bounds: %s given for an empty structure", use.items);
     if (thr > a->reach || thr > b->reach)
         return fail(LCHD_EVALUE, "threshold_distance = %g is beyond the reach %g the periodic images were built with", thr, std::min(a->reach, b->reach));
     if (!std::isfinite(thr)) thr = 1.7e308;
     CTX_GUARD(c);
-    if (int rc = resolve_bbox(c, a)) return rc;
-    if (int rc = resolve_bbox(c, b)) return rc;
+    for (int k = 0; k < use.sides; ++k)
+        if (int rc = resolve_bbox(c, cl[k])) return rc;
     const bool keep_sweep_record = c->last_sweep_valid;  // (host data: the record of the last scoring pass stands)
     c->last_valid = false;                               // (its arrays do not: the arena is laid out anew)
-    const RadialRequest R{a, b, d_anchors, d_wf_index, n_pairs, thr, use, d_out};
-    // The retry ladder of the composition calls: an environment that did not fit its slot repeats the WHOLE pass with slots that hold
-    // the largest one reported.  Every row is written again: a row's bits do not depend on the slot size.
-    int cap = kEnvGroupCap, rc = fail(LCHD_EDEVICE, "environment capacity retry did not converge");
-    for (int attempt = 0; attempt < 8; ++attempt) {
-        uint32_t f = 0;
-        if ((rc = radial_prims_pass(c, R, cap, &f)) != LCHD_OK) break;
-        if ((f & ST_BAD_ANCHOR) || !(f & ST_ENV_OVERFLOW)) { rc = status_to_rc(f & ~(uint32_t)ST_ENV_OVERFLOW, DRV_PRIMS); break; }
-        const HostStatus h = *c->h_status;
-        const int64_t want = std::max<int64_t>(std::max<int64_t>(h.max_env, h.max_bound / 3), cap + 1);
-        if (h.max_env > (uint32_t)kRadialMaxPoints || cap > kRadialMaxPoints) {
-            rc = fail(LCHD_EUNSUPPORTED, "an environment holds %u points; %s takes at most %d", h.max_env, use.what, kRadialMaxPoints);
-            break;
+    const ConsumerRequest R{{a, b}, d_anchors, d_wf_index, n, thr, use, d_out};
+    // The retry ladder: an environment that did not fit its slot repeats the WHOLE pass with slots that hold the largest one reported (a
+    // candidate-table overflow of k_env_group reports a bound; k_env_cells then counts).  Every row is written again: a row's bits do
+    // not depend on the slot size.
+    auto ladder = [&]() -> int {
+        int cap = kEnvGroupCap;
+        for (int attempt = 0; attempt < 8; ++attempt) {
+            uint32_t f = 0;
+            if (int rc = consumer_prims_pass(c, R, cap, &f)) return rc;
+            if ((f & ST_BAD_ANCHOR) || !(f & ST_ENV_OVERFLOW)) return status_to_rc(f & ~(uint32_t)ST_ENV_OVERFLOW, DRV_PRIMS);
+            const HostStatus h = *c->h_status;
+            const int64_t want = std::max<int64_t>(std::max<int64_t>(h.max_env, h.max_bound / 3), cap + 1);
+            if (h.max_env > (uint32_t)kRadialMaxPoints || cap > kRadialMaxPoints)
+                return fail(LCHD_EUNSUPPORTED, "an environment holds %u points; %s takes at most %d", h.max_env, use.what, kRadialMaxPoints);
+            cap = std::min(next_pow2_host(want), kRadialMaxPoints + 1);
         }
-        cap = std::min(next_pow2_host(want), kRadialMaxPoints + 1);
-        rc = fail(LCHD_EDEVICE, "environment capacity retry did not converge");
-    }
+        return fail(LCHD_EDEVICE, "environment capacity retry did not converge");
+    };
+    const int rc = ladder();
     if (keep_sweep_record) c->last_sweep_valid = true;  // (a grown workspace drops both records; this one is host data)
     return rc;
 }
-extern "C" int lchd_radial_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
-                                          int64_t n_pairs, double thr, const double* edges, int32_t n_edges, double* d_out) {
-    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
-    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
-    return consumer_primitives_dev(c, a, b, d_anchors, d_wf_index, n_pairs, thr, radial_consumer(edges, n_edges), d_out);
-}
 
-// ... and from host arrays, both sides as lchd_from_primitives takes them (lchd_radial_primitives / lchd_attribution_primitives).
-static int consumer_primitives_host(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
-                                    int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
-                                    const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, const double* box_a,
-                                    const double* cell_a, const double* box_b, const double* cell_b, const PairConsumer& use, double* out) {
+// One structure of a thresholded host call, as lchd_from_primitives takes it, optionally in an orthorhombic box or a triclinic cell.
+struct ProfilePrimsSide {
+    const double* xyz;
+    const int32_t *cat, *tag;
+    int64_t n;
+    const double *box, *cell;
+};
+// ... and from host arrays (lchd_{composition,radial,attribution}_primitives[_periodic]); sd: [use.sides].  Every structure goes to the
+// device as a cloud of its own, a periodic one is replaced by its image cloud (reach = the threshold), and the call is the one above.
+// The caller has checked c and cfg.
+static int consumer_primitives_host(lchd_ctx* c, const lchd_config* cfg, const ProfilePrimsSide* sd, const int64_t* anchors, const int32_t* wf_index,
+                                    int64_t n, double thr, const PairConsumer& use, double* out) {
     CTX_LOCK(c);
-    if ((box_a && cell_a) || (box_b && cell_b))
-        return fail(LCHD_EVALUE, "a box and a cell were both given: a structure has one periodic box or one periodic cell");
-    if (int rc = check_wf_index(cfg, wf_index, n_pairs)) return rc;
-    if (n_a < 0 || n_b < 0 || n_a > ((int64_t)1 << 27) || n_b > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "structure size out of range");
-    if (box_a) if (int rc = lchd_box_validate(box_a, 1, thr)) return rc;
-    if (box_b) if (int rc = lchd_box_validate(box_b, 1, thr)) return rc;
-    if (cell_a) if (int rc = lchd_cell_validate(cell_a, 1, thr)) return rc;
-    if (cell_b) if (int rc = lchd_cell_validate(cell_b, 1, thr)) return rc;
+    const int sides = use.sides;
+    for (int k = 0; k < sides; ++k)
+        if (sd[k].box && sd[k].cell)
+            return fail(LCHD_EVALUE, "a box and a cell were both given: a structure has one periodic box or one periodic cell");
+    if (int rc = check_wf_index(cfg, wf_index, n)) return rc;
+    for (int k = 0; k < sides; ++k)
+        if (sd[k].n < 0 || sd[k].n > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "structure size out of range");
+    for (int k = 0; k < sides; ++k)
+        if (sd[k].box) if (int rc = lchd_box_validate(sd[k].box, 1, thr)) return rc;
+    for (int k = 0; k < sides; ++k)
+        if (sd[k].cell) if (int rc = lchd_cell_validate(sd[k].cell, 1, thr)) return rc;
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
-    if (n_pairs > 0 && (!anchors || !out)) return fail(LCHD_EVALUE, "null anchor / output pointer");
-    for (int64_t p = 0; p < n_pairs; ++p)  // (an index beyond the structure would name a ghost atom of an image cloud)
-        if (anchors[2 * p] < 0 || anchors[2 * p] >= n_a || anchors[2 * p + 1] < 0 || anchors[2 * p + 1] >= n_b)
-            return fail(LCHD_EPANIC, "index out of bounds: an anchor index is outside its structure (src/locohd.rs:521)");
+    if (n > 0 && (!anchors || !out)) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    for (int64_t p = 0; p < n; ++p)  // (an index beyond the structure would name a ghost atom of an image cloud)
+        for (int k = 0; k < sides; ++k)
+            if (anchors[sides * p + k] < 0 || anchors[sides * p + k] >= sd[k].n)
+                return fail(LCHD_EPANIC, "index out of bounds: an anchor index is outside its structure (src/locohd.rs:521)");
     CTX_GUARD(c);
     if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
-    if (n_pairs <= 0) return LCHD_OK;
+    if (n <= 0) return LCHD_OK;
     HostTemps t(c);
-    lchd_cloud *&ia = t.clouds[0], *&ib = t.clouds[1], *&ca = t.clouds[2], *&cb = t.clouds[3];
+    lchd_cloud** const img = t.clouds;       // [sides] image clouds, destroyed before
+    lchd_cloud** const own = t.clouds + 2;   // [sides] the structures themselves
     char*& d_blk = t.d_blk;
     const size_t K = consumer_row(c, use);
-    const size_t o_wf = sizeof(int64_t) * 2 * (size_t)n_pairs, o_out = (o_wf + sizeof(int32_t) * (size_t)n_pairs + 255) & ~size_t(255);
+    const size_t o_wf = sizeof(int64_t) * (size_t)sides * (size_t)n, o_out = (o_wf + sizeof(int32_t) * (size_t)n + 255) & ~size_t(255);
     auto run = [&]() -> int {
-        if (int rc = lchd_cloud_create(c, xyz_a, cat_a, tag_a, n_a, &ca)) return rc;
-        if (int rc = lchd_cloud_create(c, xyz_b, cat_b, tag_b, n_b, &cb)) return rc;
-        if (box_a) if (int rc = lchd_cloud_create_images(c, ca, box_a, 1, thr, &ia)) return rc;
-        if (box_b) if (int rc = lchd_cloud_create_images(c, cb, box_b, 1, thr, &ib)) return rc;
-        if (cell_a) if (int rc = lchd_cloud_create_images_cell(c, ca, cell_a, 1, thr, &ia)) return rc;
-        if (cell_b) if (int rc = lchd_cloud_create_images_cell(c, cb, cell_b, 1, thr, &ib)) return rc;
-        HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)n_pairs * K));
+        for (int k = 0; k < sides; ++k)
+            if (int rc = lchd_cloud_create(c, sd[k].xyz, sd[k].cat, sd[k].tag, sd[k].n, &own[k])) return rc;
+        for (int k = 0; k < sides; ++k)
+            if (sd[k].box) if (int rc = lchd_cloud_create_images(c, own[k], sd[k].box, 1, thr, &img[k])) return rc;
+        for (int k = 0; k < sides; ++k)
+            if (sd[k].cell) if (int rc = lchd_cloud_create_images_cell(c, own[k], sd[k].cell, 1, thr, &img[k])) return rc;
+        HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)n * K));
         HIP_TRY(hipMemcpy(d_blk, anchors, o_wf, hipMemcpyHostToDevice));
-        if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice));
-        if (int rc = consumer_primitives_dev(c, ia ? ia : ca, ib ? ib : cb, reinterpret_cast<const int64_t*>(d_blk),
-                                             wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, n_pairs, thr, use,
+        if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+        lchd_cloud* cl[2] = {nullptr, nullptr};
+        for (int k = 0; k < sides; ++k) cl[k] = img[k] ? img[k] : own[k];
+        if (int rc = consumer_primitives_dev(c, cl, reinterpret_cast<const int64_t*>(d_blk),
+                                             wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, n, thr, use,
                                              reinterpret_cast<double*>(d_blk + o_out)))
             return rc;
-        HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)n_pairs * K, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)n * K, hipMemcpyDeviceToHost));
         return LCHD_OK;
     };
     return t.rc = run();
 }
-extern "C" int lchd_radial_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
-                                      int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
-                                      const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, const double* box_a,
-                                      const double* cell_a, const double* box_b, const double* cell_b, const double* edges, int32_t n_edges,
-                                      double* out) {
-    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
-    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
-    return consumer_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, box_a, cell_a, box_b,
-                                    cell_b, radial_consumer(edges, n_edges), out);
-}
 
-// Dense rows: pair r = row r of A against row r of B.  d_ma / d_mb: DEVICE rows [rows][cols], or null: distances from the side's
-// coordinates, through the minimum-image row producer with a cell.  Both sides go through k_env_rows, which materialises the stores
-// (the fused sort-and-sweep kernel never writes one).
-static int radial_dense(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, const double* d_ma, const double* d_mb, int64_t rows,
-                        int64_t cols_a, int64_t cols_b, const MinImageCell* cell_a, const MinImageCell* cell_b, const int32_t* d_wf,
-                        const PairConsumer& use, double* d_out) {
+// Dense rows: entry r = row r of every side (composition: of the one structure).  Row r is the whole structure seen from atom r
+// (from_coords) or the given distance row r (from_dmxs).  d_m[k]: DEVICE rows [rows][cols[k]], or null: distances from the side's
+// coordinates, through the minimum-image row producer with a cell.  Every side goes through k_env_rows, which materialises the store
+// (the fused sort-and-sweep kernel never writes one).  All arrays: [use.sides].
+static int consumer_dense(lchd_ctx* c, const lchd_cloud* const* cl, const double* const* d_m_in, int64_t rows, const int64_t* cols,
+                          const MinImageCell* const* cell, const int32_t* d_wf, const PairConsumer& use, double* d_out) {
+    const int sides = use.sides;
     const int n_wf = c->h_cfg.n_wf;
-    const int cap_a = next_pow2_host(cols_a), cap_b = next_pow2_host(cols_b);
     const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
     const size_t sets = n_wf > 1 ? (size_t)n_wf + 1 : 1;
-    EnvStore ea{}, eb{};
-    double *w_a = nullptr, *w_b = nullptr;
+    int cap[2] = {0, 0};
+    EnvStore e[2] = {};
+    double* w_m[2] = {nullptr, nullptr};
+    const double* d_m[2] = {nullptr, nullptr};
     int4* d_meta = nullptr;
+    for (int k = 0; k < sides; ++k) { cap[k] = next_pow2_host(cols[k]); d_m[k] = d_m_in[k]; }
     for (int dry = 1; dry >= 0; --dry) {
         Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
-        ea = carve_row_store(ar, rows, cap_a, sets, cat16);
-        eb = carve_row_store(ar, rows, cap_b, sets, cat16);
-        d_meta = ar.take<int4>((size_t)rows);
-        if (cell_a) w_a = ar.take<double>((size_t)rows * cols_a);
-        if (cell_b) w_b = ar.take<double>((size_t)rows * cols_b);
+        for (int k = 0; k < sides; ++k) e[k] = carve_row_store(ar, rows, cap[k], sets, cat16);
+        if (use.records) d_meta = ar.take<int4>((size_t)rows);
+        for (int k = 0; k < sides; ++k)
+            if (cell[k]) w_m[k] = ar.take<double>((size_t)rows * cols[k]);
         if (dry) if (int rc = ensure_ws(c, ar.off + 4096)) return rc;
     }
-    ea.cdf_keys = eb.cdf_keys = n_wf == 1 ? 1 : 0;
+    for (int k = 0; k < sides; ++k) e[k].cdf_keys = n_wf == 1 ? 1 : 0;
     hipStream_t s = c->stream;
     if (int rc = begin_pass(c)) return rc;
     c->status_dirty = true;
     mark(c, 0);
-    if (cell_a) { produce_rows(s, a, cols_a, rows, cell_a, w_a); d_ma = w_a; }
-    if (cell_b) { produce_rows(s, b, cols_b, rows, cell_b, w_b); d_mb = w_b; }
+    for (int k = 0; k < sides; ++k)
+        if (cell[k]) { produce_rows(s, *cl[k], cols[k], rows, cell[k], w_m[k]); d_m[k] = w_m[k]; }
     mark(c, 1);
     mark(c, 2);
-    if (!launch_env_rows(s, cap_a, c->d_cfg, a.view(cat16), d_ma, cols_a, rows, cols_a, diag2(a), ea, c->d_status) ||
-        !launch_env_rows(s, cap_b, c->d_cfg, b.view(cat16), d_mb, cols_b, rows, cols_b, diag2(b), eb, c->d_status))
-        return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
-    if (c->deterministic) launch_env_canon(s, ea, eb, rows, rows, nullptr);
+    for (int k = 0; k < sides; ++k)
+        if (!launch_env_rows(s, cap[k], c->d_cfg, cl[k]->view(cat16), d_m[k], cols[k], rows, cols[k], diag2(*cl[k]), e[k], c->d_status))
+            return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
+    if (c->deterministic) launch_env_canon(s, e[0], e[sides - 1], rows, rows * (sides - 1), nullptr);  // (one launch; one side: no rows of a second store)
     if (n_wf > 1) {
         launch_profile_rows(s, c->d_status, rows);  // (the key-set kernel walks DeviceStatus::n_unique[0] rows of its first store)
-        launch_env_key_sets(s, c->d_cfg, ea, ea, n_wf, rows, c->d_status);
-        launch_env_key_sets(s, c->d_cfg, eb, eb, n_wf, rows, c->d_status);
-        for (EnvStore* e : {&ea, &eb}) {
-            e->key += e->set_stride;
-            e->cdf_keys = n_wf;
+        for (int k = 0; k < sides; ++k) launch_env_key_sets(s, c->d_cfg, e[k], e[k], n_wf, rows, c->d_status);
+        for (int k = 0; k < sides; ++k) {
+            e[k].key += e[k].set_stride;
+            e[k].cdf_keys = n_wf;
         }
     }
     mark(c, 3);
     SweepArgs sw{};
-    sw.env_a = ea;
-    sw.env_b = eb;
+    sw.env_a = e[0];
+    sw.env_b = e[sides - 1];
     sw.wf_index = d_wf;
     sw.n_pairs = rows;
     sw.meta = d_meta;
@@ -4104,84 +3884,115 @@ static int radial_dense(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, c
     collect_times(c, 0, 4);
     return status_to_rc(f, DRV_DMXS);
 }
-static int radial_dense_check(lchd_ctx* c, const PairConsumer& use, int64_t cols_a, int64_t cols_b) {
+static int consumer_dense_check(lchd_ctx* c, const PairConsumer& use, const int64_t* cols) {
     if (int rc = consumer_limits(c, use)) return rc;
-    if (cols_a > kRadialMaxPoints || cols_b > kRadialMaxPoints)
-        return fail(LCHD_EUNSUPPORTED, "%s takes dense rows of at most %d points (got %lld / %lld)", use.what, kRadialMaxPoints, (long long)cols_a, (long long)cols_b);
-    return LCHD_OK;
+    bool over = false;
+    for (int k = 0; k < use.sides; ++k) over = over || cols[k] > kRadialMaxPoints;
+    if (!over) return LCHD_OK;
+    char got[64];
+    int len = 0;
+    for (int k = 0; k < use.sides; ++k) len += snprintf(got + len, sizeof got - (size_t)len, k ? " / %lld" : "%lld", (long long)cols[k]);
+    return fail(LCHD_EUNSUPPORTED, "%s takes dense rows of at most %d points (got %s)", use.what, kRadialMaxPoints, got);
 }
 
-// The dense, device-resident call of either consumer (lchd_radial_coords_dev / lchd_attribution_coords_dev).
-static int consumer_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a, const double* cell_b,
-                               const PairConsumer& use, double* d_out) {
+// The dense, device-resident call of a consumer (lchd_{composition,radial,attribution}_coords_dev); cl, cells: [use.sides].
+static int consumer_coords_dev(lchd_ctx* c, lchd_cloud* const* cl, const int32_t* d_wf_index, const double* const* cells, const PairConsumer& use,
+                               double* d_out) {
     CTX_LOCK(c);
+    const int sides = use.sides;
+    lchd_cloud *a = cl[0], *b = cl[sides - 1];
     if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     if (a->sid || b->sid) return fail(LCHD_EVALUE, "from_coords takes single structures, not batches");
-    if ((cell_a && a->images) || (cell_b && b->images)) return fail(LCHD_EVALUE, "a periodic dense call takes the structures themselves, not their image clouds");
+    for (int k = 0; k < sides; ++k)
+        if (cells[k] && cl[k]->images) return fail(LCHD_EVALUE, "a periodic dense call takes the structures themselves, not their image clouds");
     if (a->n != b->n)
         return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)a->n, (long long)b->n);
-    MinImageCell rec_a, rec_b;
-    if (cell_a) if (int rc = min_image_record(cell_a, 0, rec_a)) return rc;
-    if (cell_b) if (int rc = min_image_record(cell_b, 0, rec_b)) return rc;
+    MinImageCell rec[2];
+    const MinImageCell* cell[2] = {nullptr, nullptr};
+    for (int k = 0; k < sides; ++k)
+        if (cells[k]) {
+            if (int rc = min_image_record(cells[k], 0, rec[k])) return rc;
+            cell[k] = &rec[k];
+        }
+    consumer_drop_records(c, use);
     if (a->n == 0) return LCHD_OK;
     if (!d_out) return fail(LCHD_EVALUE, "null output pointer");
-    if (int rc = radial_dense_check(c, use, a->n, b->n)) return rc;
+    const int64_t cols[2] = {a->n, b->n};
+    if (int rc = consumer_dense_check(c, use, cols)) return rc;
     CTX_GUARD(c);
-    if (int rc = resolve_bbox(c, a)) return rc;
-    if (int rc = resolve_bbox(c, b)) return rc;
+    for (int k = 0; k < sides; ++k)
+        if (int rc = resolve_bbox(c, cl[k])) return rc;
     const bool keep_sweep_record = c->last_sweep_valid;
     c->last_valid = false;
-    const int rc = radial_dense(c, *a, *b, nullptr, nullptr, a->n, a->n, b->n, cell_a ? &rec_a : nullptr, cell_b ? &rec_b : nullptr, d_wf_index,
-                                use, d_out);
+    const double* const no_rows[2] = {nullptr, nullptr};
+    const int rc = consumer_dense(c, cl, no_rows, a->n, cols, cell, d_wf_index, use, d_out);
     if (keep_sweep_record) c->last_sweep_valid = true;
     return rc;
 }
-extern "C" int lchd_radial_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
-                                      const double* cell_b, const double* edges, int32_t n_edges, double* d_out) {
-    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
-    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
-    return consumer_coords_dev(c, a, b, d_wf_index, cell_a, cell_b, radial_consumer(edges, n_edges), d_out);
-}
 
-// Host arrays: coordinates (xyz set, dmx null; optional cells) or given rows (dmx [rows][cols], xyz null).  The caller has checked c and cfg.
-static int radial_dense_host(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b, int64_t len_seq_b,
-                             const double* xyz_a, const double* xyz_b, const double* dmx_a, const double* dmx_b, int64_t rows, int64_t cols_a,
-                             int64_t cols_b, const int32_t* wf_index, const double* cell_a, const double* cell_b, const PairConsumer& use,
-                             double* out) {
+// One side of a dense host call: coordinates (xyz set, dmx null; optional cell) or given rows (dmx [rows][cols], xyz null).
+struct ProfileDenseSide {
+    const int32_t* seq;
+    int64_t len_seq;
+    const double *xyz, *dmx;
+    int64_t cols;
+    const double* cell;
+};
+// ... and from host arrays (lchd_{composition,radial,attribution}_{coords,dmx[s]}); sd: [use.sides].  The caller has checked c and cfg.
+static int consumer_dense_host(lchd_ctx* c, const lchd_config* cfg, const ProfileDenseSide* sd, int64_t rows, const int32_t* wf_index,
+                               const PairConsumer& use, double* out) {
     CTX_LOCK(c);
+    const int sides = use.sides;
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
-    MinImageCell rec_a, rec_b;
-    if (cell_a) if (int rc = min_image_record(cell_a, 0, rec_a)) return rc;
-    if (cell_b) if (int rc = min_image_record(cell_b, 0, rec_b)) return rc;
+    MinImageCell rec[2];
+    const MinImageCell* cell[2] = {nullptr, nullptr};
+    for (int k = 0; k < sides; ++k)
+        if (sd[k].cell) {
+            if (int rc = min_image_record(sd[k].cell, 0, rec[k])) return rc;
+            cell[k] = &rec[k];
+        }
     CTX_GUARD(c);
     if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
     if (int rc = check_wf_index(cfg, wf_index, rows)) return rc;
+    consumer_drop_records(c, use);
     if (rows == 0) return LCHD_OK;
-    if (cols_a > len_seq_a || cols_b > len_seq_b) return fail(LCHD_EPANIC, "index out of bounds: a distance row is longer than its seq");
-    if (cols_a == 0 || cols_b == 0) return fail(LCHD_EPANIC, "index out of bounds: empty distance row (src/locohd.rs:74)");
-    if (int rc = radial_dense_check(c, use, cols_a, cols_b)) return rc;
-    if (!out || (!xyz_a && !dmx_a) || (!xyz_b && !dmx_b)) return fail(LCHD_EVALUE, "null pointer");
+    int64_t cols[2] = {0, 0};
+    bool longer = false, empty = false, null_side = false;
+    for (int k = 0; k < sides; ++k) {
+        cols[k] = sd[k].cols;
+        longer = longer || sd[k].cols > sd[k].len_seq;
+        empty = empty || sd[k].cols == 0;
+        null_side = null_side || (!sd[k].xyz && !sd[k].dmx);
+    }
+    if (longer) return fail(LCHD_EPANIC, "index out of bounds: a distance row is longer than its seq");
+    if (empty) return fail(LCHD_EPANIC, "index out of bounds: empty distance row (src/locohd.rs:74)");
+    if (int rc = consumer_dense_check(c, use, cols)) return rc;
+    if (!out || null_side) return fail(LCHD_EVALUE, "null pointer");
     const bool keep_sweep_record = c->last_sweep_valid;
     c->last_valid = false;
     HostTemps t(c);
-    lchd_cloud *&ca = t.clouds[0], *&cb = t.clouds[1];
     char*& d_blk = t.d_blk;
     const size_t K = consumer_row(c, use);
-    const size_t o_mb = dmx_a ? (sizeof(double) * (size_t)rows * (size_t)cols_a + 255) & ~size_t(255) : 0;
-    const size_t o_wf = o_mb + (dmx_b ? sizeof(double) * (size_t)rows * (size_t)cols_b : 0);
+    size_t o_m[2] = {0, 0}, o_wf = 0;  // the given rows of every side, 256-byte aligned, then the weight-function indices
+    for (int k = 0; k < sides; ++k) {
+        o_m[k] = o_wf;
+        if (sd[k].dmx) o_wf = (o_wf + sizeof(double) * (size_t)rows * (size_t)sd[k].cols + 255) & ~size_t(255);
+    }
     const size_t o_out = (o_wf + sizeof(int32_t) * (size_t)rows + 255) & ~size_t(255);
     auto run = [&]() -> int {
-        if (int rc = lchd_cloud_create(c, xyz_a, seq_a, nullptr, cols_a, &ca)) return rc;  // (given rows: the cloud carries the categories alone)
-        if (int rc = lchd_cloud_create(c, xyz_b, seq_b, nullptr, cols_b, &cb)) return rc;
+        const double* d_m[2] = {nullptr, nullptr};
+        for (int k = 0; k < sides; ++k)  // (given rows: the cloud carries the categories alone)
+            if (int rc = lchd_cloud_create(c, sd[k].xyz, sd[k].seq, nullptr, sd[k].cols, &t.clouds[k])) return rc;
         HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)rows * K));
-        if (dmx_a) HIP_TRY(hipMemcpy(d_blk, dmx_a, sizeof(double) * (size_t)rows * (size_t)cols_a, hipMemcpyHostToDevice));
-        if (dmx_b) HIP_TRY(hipMemcpy(d_blk + o_mb, dmx_b, sizeof(double) * (size_t)rows * (size_t)cols_b, hipMemcpyHostToDevice));
+        for (int k = 0; k < sides; ++k)
+            if (sd[k].dmx) {
+                HIP_TRY(hipMemcpy(d_blk + o_m[k], sd[k].dmx, sizeof(double) * (size_t)rows * (size_t)sd[k].cols, hipMemcpyHostToDevice));
+                d_m[k] = reinterpret_cast<const double*>(d_blk + o_m[k]);
+            }
         if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice));
-        if (int rc = radial_dense(c, *ca, *cb, dmx_a ? reinterpret_cast<const double*>(d_blk) : nullptr,
-                                  dmx_b ? reinterpret_cast<const double*>(d_blk + o_mb) : nullptr, rows, cols_a, cols_b, cell_a ? &rec_a : nullptr,
-                                  cell_b ? &rec_b : nullptr, wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, use,
-                                  reinterpret_cast<double*>(d_blk + o_out)))
+        if (int rc = consumer_dense(c, t.clouds, d_m, rows, cols, cell, wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, use,
+                                    reinterpret_cast<double*>(d_blk + o_out)))
             return rc;
         HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)rows * K, hipMemcpyDeviceToHost));
         return LCHD_OK;
@@ -4190,12 +4001,92 @@ static int radial_dense_host(lchd_ctx* c, const lchd_config* cfg, const int32_t*
     if (keep_sweep_record) c->last_sweep_valid = true;
     return t.rc;
 }
-// from_coords' argument rule (both consumers)
+// from_coords' argument rule (the pair consumers)
 static int coords_lengths(const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b) {
     if (n_a != n_b)  // src/locohd.rs:420-428 via :472-475
         return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)n_a, (long long)n_b);
     if (n_a > 0 && (!xyz_a || !xyz_b)) return fail(LCHD_EVALUE, "null pointer");
     return LCHD_OK;
+}
+
+// ---- the entry points: argument adapters ----------------------------------------------------------------------------
+// local composition profiles: one structure, one list of anchors, rows of n_categories doubles
+extern "C" int lchd_composition_primitives_dev(lchd_ctx* c, lchd_cloud* cl, const int64_t* d_anchors, const int32_t* d_wf_index,
+                                               int64_t n_anchors, double thr, double* d_out) {
+    if (!c || !cl) return fail(LCHD_EVALUE, "null argument");
+    return consumer_primitives_dev(c, &cl, d_anchors, d_wf_index, n_anchors, thr, kComposition, d_out);
+}
+extern "C" int lchd_composition_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const double* xyz, const int32_t* cat,
+                                                    const int32_t* tag, int64_t n, const int64_t* anchors, const int32_t* wf_index,
+                                                    int64_t n_anchors, double thr, const double* box, const double* cell, double* out) {
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    const ProfilePrimsSide sd{xyz, cat, tag, n, box, cell};
+    return consumer_primitives_host(c, cfg, &sd, anchors, wf_index, n_anchors, thr, kComposition, out);
+}
+extern "C" int lchd_composition_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz, const int32_t* cat, const int32_t* tag,
+                                           int64_t n, const int64_t* anchors, const int32_t* wf_index, int64_t n_anchors, double thr,
+                                           double* out) {
+    return lchd_composition_primitives_periodic(c, cfg, xyz, cat, tag, n, anchors, wf_index, n_anchors, thr, nullptr, nullptr, out);
+}
+extern "C" int lchd_composition_coords_dev(lchd_ctx* c, lchd_cloud* cl, const int32_t* d_wf_index, const double* cell, double* d_out) {
+    if (!c || !cl) return fail(LCHD_EVALUE, "null argument");
+    return consumer_coords_dev(c, &cl, d_wf_index, &cell, kComposition, d_out);
+}
+extern "C" int lchd_composition_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t len_seq, const double* xyz, int64_t n,
+                                       const int32_t* wf_index, const double* cell, double* out) {
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    const ProfileDenseSide sd{seq, len_seq, xyz, nullptr, n, cell};
+    return consumer_dense_host(c, cfg, &sd, n, wf_index, kComposition, out);
+}
+extern "C" int lchd_composition_dmx(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t len_seq, const double* dmx, int64_t rows,
+                                    int64_t cols, const int32_t* wf_index, double* out) {
+    if (rows > 0 && !dmx) return fail(LCHD_EVALUE, "null pointer");
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    const ProfileDenseSide sd{seq, len_seq, nullptr, dmx, cols, nullptr};
+    return consumer_dense_host(c, cfg, &sd, rows, wf_index, kComposition, out);
+}
+
+// the pair consumers: two structures, one list of anchor pairs.  edges null: attribution (rows of n_categories doubles), else the
+// radial profile over these edges (rows of n_edges - 1 doubles); each entry point validates its edges where it did before the merge.
+static int pair_primitives_host(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a, int64_t n_a,
+                                const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b, const int64_t* anchors,
+                                const int32_t* wf_index, int64_t n_pairs, double thr, const double* box_a, const double* cell_a,
+                                const double* box_b, const double* cell_b, const PairConsumer& use, double* out) {
+    const ProfilePrimsSide sd[2] = {{xyz_a, cat_a, tag_a, n_a, box_a, cell_a}, {xyz_b, cat_b, tag_b, n_b, box_b, cell_b}};
+    return consumer_primitives_host(c, cfg, sd, anchors, wf_index, n_pairs, thr, use, out);
+}
+static int pair_dense_host(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b, int64_t len_seq_b,
+                           const double* xyz_a, const double* xyz_b, const double* dmx_a, const double* dmx_b, int64_t rows, int64_t cols_a,
+                           int64_t cols_b, const int32_t* wf_index, const double* cell_a, const double* cell_b, const PairConsumer& use,
+                           double* out) {
+    const ProfileDenseSide sd[2] = {{seq_a, len_seq_a, xyz_a, dmx_a, cols_a, cell_a}, {seq_b, len_seq_b, xyz_b, dmx_b, cols_b, cell_b}};
+    return consumer_dense_host(c, cfg, sd, rows, wf_index, use, out);
+}
+
+extern "C" int lchd_radial_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
+                                          int64_t n_pairs, double thr, const double* edges, int32_t n_edges, double* d_out) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
+    lchd_cloud* const cl[2] = {a, b};
+    return consumer_primitives_dev(c, cl, d_anchors, d_wf_index, n_pairs, thr, radial_consumer(edges, n_edges), d_out);
+}
+extern "C" int lchd_radial_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
+                                      int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
+                                      const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, const double* box_a,
+                                      const double* cell_a, const double* box_b, const double* cell_b, const double* edges, int32_t n_edges,
+                                      double* out) {
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
+    return pair_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, box_a, cell_a, box_b,
+                                cell_b, radial_consumer(edges, n_edges), out);
+}
+extern "C" int lchd_radial_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
+                                      const double* cell_b, const double* edges, int32_t n_edges, double* d_out) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
+    lchd_cloud* const cl[2] = {a, b};
+    const double* const cells[2] = {cell_a, cell_b};
+    return consumer_coords_dev(c, cl, d_wf_index, cells, radial_consumer(edges, n_edges), d_out);
 }
 extern "C" int lchd_radial_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
                                   int64_t len_seq_b, const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b, const int32_t* wf_index,
@@ -4203,8 +4094,8 @@ extern "C" int lchd_radial_coords(lchd_ctx* c, const lchd_config* cfg, const int
     if (int rc = coords_lengths(xyz_a, n_a, xyz_b, n_b)) return rc;
     if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
     if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
-    return radial_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n_a, n_a, n_b, wf_index, cell_a, cell_b,
-                             radial_consumer(edges, n_edges), out);
+    return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n_a, n_a, n_b, wf_index, cell_a, cell_b,
+                           radial_consumer(edges, n_edges), out);
 }
 extern "C" int lchd_radial_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
                                 int64_t len_seq_b, const double* dmx_a, const double* dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
@@ -4212,48 +4103,46 @@ extern "C" int lchd_radial_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32
     if (rows > 0 && (!dmx_a || !dmx_b)) return fail(LCHD_EVALUE, "null pointer");
     if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
     if (int rc = lchd_radial_validate(edges, n_edges)) return rc;
-    return radial_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr, nullptr,
-                             radial_consumer(edges, n_edges), out);
+    return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr, nullptr,
+                           radial_consumer(edges, n_edges), out);
 }
 
-// ------------------------------------------------------------------------------------------------
-// score attribution by category (additive, not in the reference): which categories carry a pair's score
-// ------------------------------------------------------------------------------------------------
-// The radial calls above with the other consumer: the same store builds, record pass, capacity-repeat loop, limits and neutral hints;
-// the stores and records go to launch_attribution (lchd_attribution.hip), the output is [n][n_categories].  Hellinger distances only.
-static const PairConsumer kAttribution{{}, "an attribution", "attribution"};
-
+// score attribution by category: the radial calls with the other consumer; the stores and records go to launch_attribution
+// (lchd_attribution.hip).  Hellinger distances only.
 extern "C" int lchd_attribution_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
                                                int64_t n_pairs, double thr, double* d_out) {
     if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
-    return consumer_primitives_dev(c, a, b, d_anchors, d_wf_index, n_pairs, thr, kAttribution, d_out);
+    lchd_cloud* const cl[2] = {a, b};
+    return consumer_primitives_dev(c, cl, d_anchors, d_wf_index, n_pairs, thr, kAttribution, d_out);
 }
 extern "C" int lchd_attribution_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
                                            int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
                                            const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, const double* box_a,
                                            const double* cell_a, const double* box_b, const double* cell_b, double* out) {
     if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
-    return consumer_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, box_a, cell_a, box_b,
-                                    cell_b, kAttribution, out);
+    return pair_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, box_a, cell_a, box_b,
+                                cell_b, kAttribution, out);
 }
 extern "C" int lchd_attribution_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
                                            const double* cell_b, double* d_out) {
     if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
-    return consumer_coords_dev(c, a, b, d_wf_index, cell_a, cell_b, kAttribution, d_out);
+    lchd_cloud* const cl[2] = {a, b};
+    const double* const cells[2] = {cell_a, cell_b};
+    return consumer_coords_dev(c, cl, d_wf_index, cells, kAttribution, d_out);
 }
 extern "C" int lchd_attribution_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
                                        int64_t len_seq_b, const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b,
                                        const int32_t* wf_index, const double* cell_a, const double* cell_b, double* out) {
     if (int rc = coords_lengths(xyz_a, n_a, xyz_b, n_b)) return rc;
     if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
-    return radial_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n_a, n_a, n_b, wf_index, cell_a, cell_b,
-                             kAttribution, out);
+    return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n_a, n_a, n_b, wf_index, cell_a, cell_b,
+                           kAttribution, out);
 }
 extern "C" int lchd_attribution_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
                                      int64_t len_seq_b, const double* dmx_a, const double* dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
                                      const int32_t* wf_index, double* out) {
     if (rows > 0 && (!dmx_a || !dmx_b)) return fail(LCHD_EVALUE, "null pointer");
     if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
-    return radial_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr, nullptr,
-                             kAttribution, out);
+    return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr, nullptr,
+                           kAttribution, out);
 }
