@@ -81,6 +81,8 @@ const char *lchd_version(void);
 int lchd_wf_validate(int32_t kind, const double *params, int32_t n_params);
 /* WeightFunction::integral_vec / integral_point, weight_function.rs:95-116: out[i] = CDF(x[i]); x<0 -> LCHD_EVALUE */
 int lchd_wf_cdf(int32_t kind, const double *params, int32_t n_params, const double *x, int64_t n, double *out);
+/* The density F' of the same weight function (additive): out[i] = w(x[i]); 0 for x < 0 and outside a bounded support. */
+int lchd_wf_pdf(int32_t kind, const double *params, int32_t n_params, const double *x, int64_t n, double *out);
 /* StatisticalDistance::build validation, statistical_distances.rs:96-121 */
 int lchd_sd_validate(int32_t kind, int32_t n_params);
 /* StatisticalDistance::run, statistical_distances.rs:123-142 */
@@ -506,6 +508,41 @@ int lchd_attribution_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t
 int lchd_attribution_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
                           int64_t len_seq_b, const double *dmx_a, const double *dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
                           const int32_t *wf_index, double *out);
+
+/* ---- neighbour sensitivities (additive, not in the reference) ------------------------------------------
+ * Which members of the two environments carry a pair's score, and how it changes when one of them moves: the derivative of the score
+ * with respect to the distance d of every environment member.  On the piecewise-constant integrand the sweeps walk,
+ *   S = sum_j (F(u_{j+1}) - F(u_j)) * H_j          g = dS/dd = w(d) * (H- - H+)
+ * with w = F' the density of the pair's weight function (lchd_wf_pdf) and H- / H+ the statistical distance on the piece that ends /
+ * starts at the member.  With x the member's and x0 the anchor's coordinates, dS/dx = g (x - x0) / d and dS/dx0 = -g (x - x0) / d.
+ *   - the derivative ignores members entering or leaving at the threshold: it is exact when the weight function's support ends at or
+ *     inside the threshold (the default: uniform [3, 10] with threshold 10), else the derivative of the score at fixed membership
+ *   - at exact ties it is one-sided: tied members are treated one at a time in list order
+ *   - every statistical distance is supported (only values of H are needed); at most 64 categories, environments of at most 65 535 points
+ * Every environment is returned as a list sorted ascending by (distance bits, atom index) with the anchor in slot 0 -- one defined
+ * order among ties.  Per pair p and side, with K = width the caller's row width:
+ *   count[p]     members, the anchor included (0: an unusable pair)
+ *   idx[p][K]    atom index of every member (i32), padded with -1
+ *   dist[p][K]   its distance, padded with 0
+ *   g[p][K]      dS/dd; 0 in slot 0 and in the padding.  A member at d == 0 other than the anchor has a g but no direction.
+ *   scores[p]    the pair's score from the same walk (the scoring call of the same inputs, to rounding)
+ * The pair of an out-of-range weight-function index has NaN scores and g rows, count 0, and the call fails as the attribution call does.
+ * Row width: a call whose longest environment holds more than `width` points fails with LCHD_EVALUE (the message names the width it
+ * takes) after one pass; lchd_sensitivity_needed_width then returns that width, and after a successful call the longest list.
+ * Errors, stream and lock rules, capacity repeats and the untouched hints / lchd_ctx_last_sweep: as lchd_attribution_primitives(_dev).
+ * Thresholded calls on the structures themselves only: no periodic boxes, cells or image clouds (LCHD_EUNSUPPORTED), no dense
+ * (from_coords / from_dmxs) form, no device groups. */
+int lchd_sensitivity_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors, const int32_t *d_wf_index,
+                                    int64_t n_pairs, double threshold_distance, int32_t width, double *d_scores, int32_t *d_count_a,
+                                    int32_t *d_idx_a, double *d_dist_a, double *d_g_a, int32_t *d_count_b, int32_t *d_idx_b,
+                                    double *d_dist_b, double *d_g_b);
+/* The same from host arrays (the structures as lchd_attribution_primitives takes them, without boxes and cells); outputs HOST. */
+int lchd_sensitivity_primitives(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a, const int32_t *tag_a,
+                                int64_t n_a, const double *xyz_b, const int32_t *cat_b, const int32_t *tag_b, int64_t n_b,
+                                const int64_t *anchors, const int32_t *wf_index, int64_t n_pairs, double threshold_distance, int32_t width,
+                                double *scores, int32_t *count_a, int32_t *idx_a, double *dist_a, double *g_a, int32_t *count_b,
+                                int32_t *idx_b, double *dist_b, double *g_b);
+int64_t lchd_sensitivity_needed_width(lchd_ctx *ctx);
 
 /* ---- multi-GPU ------------------------------------------------------------------------------------
  * The reference's parallelism lives INSIDE the core call: a thread pool that is a field of `LoCoHD` (src/locohd.rs:53,

@@ -17,11 +17,15 @@ from __future__ import annotations
 
 import ctypes as C
 import threading
+from collections import namedtuple
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
 from . import _native as N
+
+# what LoCoHD.sensitivity_from_primitives returns (DeviceSession.sensitivity: the same fields as torch tensors)
+Sensitivity = namedtuple("Sensitivity", "scores count_a idx_a dist_a g_a count_b idx_b dist_b g_b")
 
 try:  # built by `make -C loco_hd_amd/csrc`; argument conversion only -- without it the same conversion runs as a Python loop
     from . import _fastpack
@@ -173,6 +177,16 @@ class WeightFunction:
         out = np.empty_like(x)
         N.check(N.lib().lchd_wf_cdf(self._kind, N.dp(self._p), len(self._p), N.dp(x), x.size, N.dp(out)))
         return out.tolist()
+
+    def density_vec(self, points: Sequence[float]) -> List[float]:
+        """Additive: the density w = F' of the weight function at every point (0 below 0 and outside a bounded support)."""
+        x = _f64(points).reshape(-1)
+        out = np.empty_like(x)
+        N.check(N.lib().lchd_wf_pdf(self._kind, N.dp(self._p), len(self._p), N.dp(x), x.size, N.dp(out)))
+        return out.tolist()
+
+    def density_point(self, point: float) -> float:
+        return self.density_vec([float(point)])[0]
 
     def integral_point(self, point: float) -> float:
         return self.integral_vec([float(point)])[0]
@@ -916,6 +930,90 @@ class LoCoHD:
     def attribution_from_dmxs(self, seq_a, seq_b, dmx_a, dmx_b, w_func_keys: Optional[Sequence[str]] = None) -> np.ndarray:
         """Additive: the score of every row pair `from_dmxs` would score, split over the categories, as a float64 array (rows, C)."""
         return self._pair_rows_from_dmxs(None, seq_a, seq_b, dmx_a, dmx_b, w_func_keys)
+
+    # ---- neighbour sensitivities and coordinate gradients (additive) ---------------------------------------
+    # g = dS/dd = w(d) (H- - H+) for every member of the pair's two environments (include/loco_hd_hip.h, "neighbour sensitivities"): which
+    # neighbours carry the score, and -- through dd/dx = (x - x_anchor) / d -- in which direction they would have to move to change it.
+    def sensitivity_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                                    threshold_distance: float, *, width: Optional[int] = None, box_a=None, box_b=None, cell_a=None,
+                                    cell_b=None) -> Sensitivity:
+        """Additive: for every anchor pair `from_primitives` would score, the derivative of its score with respect to the distance of
+        every member of its two environments.  Returns `Sensitivity(scores, count_a, idx_a, dist_a, g_a, count_b, idx_b, dist_b, g_b)` of
+        NumPy arrays: per pair and side the environment as a list sorted by (distance, atom index) with the anchor in slot 0 -- `count`
+        members, their atom indices `idx` (padded with -1), distances `dist` and sensitivities `g` (padded with 0; slot 0 is 0) -- and
+        the pair's score.  Rows are as wide as the longest environment, or `width` (ValueError if that is too small).
+
+        The derivative ignores points entering or leaving at the threshold: it is exact when the weight function's support ends at or
+        inside the threshold (the default, uniform [3, 10] with threshold 10), and it is one-sided at ties.  Every statistical distance
+        is supported.  Periodic boxes and cells, the dense calls and device groups are not (NotImplementedError)."""
+        if box_a is not None or box_b is not None or cell_a is not None or cell_b is not None:
+            raise NotImplementedError("sensitivity_from_primitives takes open structures: periodic boxes and cells are not supported")
+        if self._devices is not None:
+            raise NotImplementedError("a sensitivity call applies to one device (a device group has no sensitivity call): drop devices=[...]")
+        thr = float(threshold_distance)
+        pairs, idx = self._anchor_arrays(anchor_pairs)
+        pa, pb, interner = self._packed_lists(prim_a, prim_b)
+        anchors = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        cfg, keep = self._config(interner)
+        n = len(anchors)
+        if width is not None and int(width) < 1:
+            raise ValueError(f"width = {width}: a row holds at least the anchor")
+        xa, xb = _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3)
+        k = 128 if width is None else int(width)
+        while True:
+            scores = np.empty(n)
+            cnt = [np.empty(n, dtype=np.int32) for _ in range(2)]
+            ix = [np.empty((n, k), dtype=np.int32) for _ in range(2)]
+            ds = [np.empty((n, k)) for _ in range(2)]
+            gs = [np.empty((n, k)) for _ in range(2)]
+            if n == 0:
+                break
+            ctx = self._context()
+            rc = N.lib().lchd_sensitivity_primitives(ctx, C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa), N.dp(xb), N.ip(pb.cat),
+                                                     N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx), n, thr, k, N.dp(scores), N.ip(cnt[0]),
+                                                     N.ip(ix[0]), N.dp(ds[0]), N.dp(gs[0]), N.ip(cnt[1]), N.ip(ix[1]), N.dp(ds[1]), N.dp(gs[1]))
+            need = int(N.lib().lchd_sensitivity_needed_width(ctx))
+            if rc == N.EVALUE and width is None and need > k:  # the first guess was too narrow: once more with the width the pairs take
+                k = need
+                continue
+            N.check(rc)
+            if width is None and 0 < need < k:
+                ix, ds, gs = ([np.ascontiguousarray(a[:, :need]) for a in t] for t in (ix, ds, gs))
+            break
+        return Sensitivity(scores, cnt[0], ix[0], ds[0], gs[0], cnt[1], ix[1], ds[1], gs[1])
+
+    @staticmethod
+    def _assemble_gradient(sens: "Sensitivity", xyz_a: np.ndarray, xyz_b: np.ndarray, pair_weights=None):
+        """grad = sum_p v_p dS_p/dx from a Sensitivity: member += v g (x_m - x_anchor) / d, anchor -= the same, members at d == 0 skipped;
+        np.add.at in pair order, then slot order: one fixed summation order."""
+        v = np.ones(len(sens.scores)) if pair_weights is None else _f64(pair_weights).reshape(-1)
+        if len(v) != len(sens.scores):
+            raise ValueError(f"pair_weights has {len(v)} entries for {len(sens.scores)} anchor pairs")
+        grads = []
+        for xyz, idx, dist, g in ((xyz_a, sens.idx_a, sens.dist_a, sens.g_a), (xyz_b, sens.idx_b, sens.dist_b, sens.g_b)):
+            grad = np.zeros((len(xyz), 3))
+            if idx.size:
+                use = (idx >= 0) & (dist > 0.0) & np.isfinite(g)
+                use[:, 0] = False
+                p, k = np.nonzero(use)  # (row-major: pair order, then slot order)
+                member, anchor = idx[p, k], idx[p, 0]
+                step = (v[p] * g[p, k] / dist[p, k])[:, None] * (xyz[member] - xyz[anchor])
+                np.add.at(grad, member, step)
+                np.add.at(grad, anchor, -step)
+            grads.append(grad)
+        return grads[0], grads[1]
+
+    def gradient_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                                 threshold_distance: float, pair_weights=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None):
+        """Additive: `(scores, grad_a[Na, 3], grad_b[Nb, 3])` with grad = sum_p v_p dS_p/dx over the anchor pairs, v = `pair_weights`
+        (default: ones): the coordinate gradient of a weighted sum of scores, assembled on the host from `sensitivity_from_primitives`
+        in a fixed order.  The derivative ignores points entering or leaving at the threshold (exact when the weight function's support
+        ends at or inside it) and is one-sided at ties; members at distance 0 contribute no direction."""
+        sens = self.sensitivity_from_primitives(prim_a, prim_b, anchor_pairs, threshold_distance, box_a=box_a, box_b=box_b, cell_a=cell_a,
+                                                cell_b=cell_b)
+        pa, pb, _ = self._packed_lists(prim_a, prim_b)
+        ga, gb = self._assemble_gradient(sens, _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3), pair_weights)
+        return sens.scores, ga, gb
 
     def _no_device_group_with_box(self) -> None:
         if self._devices is not None:

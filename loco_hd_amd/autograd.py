@@ -1,0 +1,45 @@
+"""LoCoHD scores as a differentiable torch function (additive): a movable structure against a fixed uploaded reference.
+
+    scores = locohd_scores(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, threshold_distance)
+    scores.sum().backward()          # xyz_a.grad = d sum(scores) / d xyz_a
+
+Forward is DeviceSession.sensitivity, backward is DeviceSession.assemble_gradient with grad_output as the pair weights.  The derivative
+ignores points entering or leaving at the threshold (exact when the weight function's support ends at or inside it: the default, uniform
+[3, 10] with threshold 10) and is one-sided at ties.  The movable structure is uploaded from the host on every forward call.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _native as N
+
+
+class _LoCoHDScores(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, threshold_distance):
+        x = xyz_a.detach()
+        cloud_a = session.upload(x.cpu().numpy(), np.asarray(cat_a, dtype=np.int32), None if tag_a is None else np.asarray(tag_a, dtype=np.int32))
+        try:
+            sens = session.sensitivity(cloud_a, cloud_b_ref, anchors, threshold_distance)
+        finally:
+            session._clouds.remove(cloud_a)
+            N.lib().lchd_cloud_destroy(session._ctx, cloud_a)
+        ctx.session = session
+        ctx.sens = sens
+        ctx.save_for_backward(x)
+        return sens.scores
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (x,) = ctx.saved_tensors
+        s = ctx.sens
+        grad_a = ctx.session.side_gradient(s.scores, s.idx_a, s.dist_a, s.g_a, x.to(torch.float64), grad_output)  # side A alone moves
+        return grad_a.to(x.dtype), None, None, None, None, None, None
+
+
+def locohd_scores(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, threshold_distance):
+    """The scores of the anchor pairs (torch int64 CUDA tensor [P][2]: atom of the movable structure, atom of the reference) of a
+    movable structure -- xyz_a: torch float64 CUDA tensor [Na][3], cat_a / tag_a: its category ids and interned tags (host arrays) --
+    against `cloud_b_ref`, a cloud uploaded to `session`; differentiable with respect to xyz_a."""
+    return _LoCoHDScores.apply(xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, float(threshold_distance))

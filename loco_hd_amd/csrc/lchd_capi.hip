@@ -92,6 +92,13 @@ extern "C" int lchd_wf_cdf(int32_t kind, const double* p, int32_t np, const doub
     return LCHD_OK;
 }
 
+// the density F' of the same function (additive: lchd_math.h); a negative x is no error here, the density there is 0
+extern "C" int lchd_wf_pdf(int32_t kind, const double* p, int32_t np, const double* x, int64_t n, double* out) {
+    if (n > 0 && (!p || !x || !out)) return fail(LCHD_EVALUE, "null pointer");
+    for (int64_t i = 0; i < n; ++i) out[i] = pdf_eval(kind, p, np, x[i]);
+    return LCHD_OK;
+}
+
 extern "C" int lchd_sd_validate(int32_t kind, int32_t np) {  // statistical_distances.rs:96-121
     static const int want[4] = {1, 0, 1, 2};
     static const char* names[4] = {"Hellinger", "Kolmogorov-Smirnov", "Kullback-Leibler", "Renyi"};
@@ -269,6 +276,9 @@ struct lchd_ctx {
     size_t ovf_bits_cap = 0, ovf_lists_cap = 0;
     char* d_radial_bounds = nullptr;  // radial profiles: [n_wf][edges] bin bounds in key space (grow-only, outside the arena: the store builders lay the arena out)
     size_t radial_bounds_cap = 0;
+    char* d_indexed = nullptr;        // sensitivity calls: the indexed environment lists of both sides (grow-only, outside the arena likewise)
+    size_t indexed_cap = 0;
+    int64_t sens_needed = 0;          // lchd_sensitivity_needed_width: the longest list among the pairs of the last sensitivity call
     int64_t n_subset_passes = 0;    // second passes run so far
     size_t last_store_bytes = 0;    // environment-store bytes (keys + categories, both sides) of the passes of the last from_primitives call
     int64_t n_passes = 0;           // from_primitives passes enqueued so far (a call is one pass unless a capacity / launch-set retry repeats it)
@@ -502,6 +512,7 @@ extern "C" void lchd_ctx_destroy(lchd_ctx* c) {
     (void)hipFree(c->d_ovf_bits);
     (void)hipFree(c->d_ovf_lists);
     (void)hipFree(c->d_radial_bounds);
+    (void)hipFree(c->d_indexed);
     (void)hipFree(c->d_shard);
     (void)hipFree(c->d_bad);
     if (c->shard_stream) (void)hipStreamDestroy(c->shard_stream);
@@ -3586,6 +3597,8 @@ struct PairConsumer {
     const char* items;  // what its list holds: "anchors" / "anchor pairs"
     int sides;          // structures (stores) of a call, columns of its list: 1 composition, 2 the others
     bool records;       // its kernel reads the pair records of k_pair_meta (a dense pass carves them)
+    int width;          // > 0: a sensitivity call with rows of this many slots (thresholded calls only: it needs the cell lists)
+    SensitivityOut sens;  // ... and its DEVICE outputs, or all null: they are carved from the pass's one output block (sens_carve)
 };
 static const PairConsumer kComposition{{}, "a composition profile", "composition", "anchors", 1, false};
 static const PairConsumer kAttribution{{}, "an attribution", "attribution", "anchor pairs", 2, true};
@@ -3595,15 +3608,33 @@ static PairConsumer radial_consumer(const double* edges, int32_t n_edges) {
     for (int32_t k = 0; k < n_edges; ++k) use.edges.e[k] = edges[k];
     return use;
 }
-// doubles per entry in the consumer's output: the bins / the categories of the context's configuration
+static PairConsumer sensitivity_consumer(int32_t width, const SensitivityOut& out) {
+    PairConsumer use{{}, "a sensitivity call", "sensitivity", "anchor pairs", 2, true};
+    use.width = width;
+    use.sens = out;
+    return use;
+}
+// A sensitivity call's outputs as ONE block of n * (5 w + 2) doubles (host or device): scores | g_a | g_b | dist_a | dist_b | idx_a | idx_b |
+// count_a | count_b -- what the host call moves in one copy.
+static SensitivityOut sens_carve(double* blk, int64_t n, int w) {
+    const size_t nw = (size_t)n * (size_t)w;
+    SensitivityOut o{};
+    o.scores = blk;
+    o.g_a = blk + n; o.g_b = o.g_a + nw; o.dist_a = o.g_b + nw; o.dist_b = o.dist_a + nw;
+    o.idx_a = reinterpret_cast<int32_t*>(o.dist_b + nw); o.idx_b = o.idx_a + nw;
+    o.count_a = o.idx_b + nw; o.count_b = o.count_a + n;
+    return o;
+}
+// doubles per entry in the consumer's output: the bins / the categories of the context's configuration / a sensitivity call's block
 static size_t consumer_row(const lchd_ctx* c, const PairConsumer& use) {
+    if (use.width) return 5 * (size_t)use.width + 2;
     return use.edges.n ? (size_t)use.edges.n - 1 : (size_t)c->h_cfg.n_categories;
 }
 static int consumer_limits(const lchd_ctx* c, const PairConsumer& use) {
     static const char* names[4] = {"Hellinger", "Kolmogorov-Smirnov", "Kullback-Leibler", "Renyi"};
     if (use.sides == 1) return LCHD_OK;  // a composition has no distance, and its kernel takes every category count
-    const int most = use.edges.n ? kWideCategories : kAttributionMaxCategories;
-    if (!use.edges.n && c->h_cfg.sd_kind != SD_HELLINGER)
+    const int most = use.width ? kSensitivityMaxCategories : (use.edges.n ? kWideCategories : kAttributionMaxCategories);
+    if (!use.edges.n && !use.width && c->h_cfg.sd_kind != SD_HELLINGER)
         return fail(LCHD_EUNSUPPORTED, "an attribution splits the Hellinger distance over the categories; the %s distance is no sum of per-category terms",
                     names[c->h_cfg.sd_kind & 3]);
     if (c->h_cfg.n_categories > most)
@@ -3612,7 +3643,8 @@ static int consumer_limits(const lchd_ctx* c, const PairConsumer& use) {
 }
 // The consumer's kernel behind a finished store build (stream order), with what hands the status over: the record pass (k_pair_meta)
 // in front of a pair kernel, launch_profile_publish behind the profile kernel.  sw: the stores, the list and its slots.
-static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use, double* d_out) {
+// ix: a sensitivity call's indexed-list build (the prologue's cell lists and anchor records), launched behind the record pass.
+static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use, double* d_out, const IndexedArgs* ix = nullptr) {
     const int n_wf = c->h_cfg.n_wf;
     hipStream_t s = c->stream;
     if (use.sides == 1) {
@@ -3627,7 +3659,17 @@ static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use,
     fill_sweep_args(c, sw);
     launch_pair_meta(s, sw);
     bool launched;
-    if (use.edges.n) {
+    if (use.width) {
+        if (!ix) return fail(LCHD_EUNSUPPORTED, "a sensitivity call takes thresholded environments (it needs the cell lists)");
+        SensitivityArgs sa{};
+        sa.sw = sw;
+        sa.env_a = ix->s[0].env;
+        sa.env_b = ix->s[1].max_envs > 0 ? ix->s[1].env : ix->s[0].env;  // (both sides one object: one set of lists)
+        sa.n_categories = c->h_cfg.n_categories;
+        sa.width = use.width;
+        sa.out = use.sens.scores ? use.sens : sens_carve(d_out, sw.n_pairs, use.width);
+        launched = launch_env_indexed(s, *ix) && launch_sensitivity(s, sa);
+    } else if (use.edges.n) {
         launch_radial_bounds(s, c->d_cfg, n_wf, use.edges, reinterpret_cast<double*>(c->d_radial_bounds));
         RadialArgs ra{};
         ra.sw = sw;
@@ -3689,6 +3731,29 @@ static int consumer_prims_pass(lchd_ctx* c, const ConsumerRequest& R, int cap, u
     plan.dict_sets = n_wf > 1;
     plan.key_sets = n_wf > 1 ? n_wf + 1 : 1;
     plan.pre_words = 0;
+    // a sensitivity call: the indexed lists of both sides, slots and stride as the scoring stores', in a block of their own
+    IndexedArgs ix{};
+    if (R.use.width) {
+        const int64_t ne[2] = {plan.max_env_a, plan.same ? 0 : plan.max_env_b}, na[2] = {a->n, b->n};
+        size_t off[2][5], need = 0;
+        for (int k = 0; k < 2; ++k) {
+            const size_t pts = (size_t)ne[k] * (size_t)cap;
+            const size_t bytes[5] = {4 * (size_t)na[k], 4 * (size_t)ne[k], 8 * pts, 4 * pts, pts};  // atom_of, len, dist, idx, cat
+            for (int j = 0; j < 5; ++j) { off[k][j] = need; need = (need + bytes[j] + 255) & ~size_t(255); }
+        }
+        if (int rc = grow_block(c->d_indexed, c->indexed_cap, need + 256)) return rc;
+        for (int k = 0; k < 2; ++k) {
+            IndexedSide& S = ix.s[k];
+            S.max_envs = ne[k];
+            S.n = (int32_t)na[k];
+            S.atom_of = reinterpret_cast<uint32_t*>(c->d_indexed + off[k][0]);
+            S.env.len = reinterpret_cast<int32_t*>(c->d_indexed + off[k][1]);
+            S.env.dist = reinterpret_cast<double*>(c->d_indexed + off[k][2]);
+            S.env.idx = reinterpret_cast<uint32_t*>(c->d_indexed + off[k][3]);
+            S.env.cat = reinterpret_cast<uint8_t*>(c->d_indexed + off[k][4]);
+            S.env.stride = cap;
+        }
+    }
     PrimsStore st;
     const int built = sides == 1 ? build_prims_store(c, a, a, nullptr, R.anchors, R.n, R.thr, q, plan, st)
                                  : build_prims_store(c, a, b, R.anchors, nullptr, R.n, R.thr, q, plan, st);
@@ -3706,7 +3771,19 @@ static int consumer_prims_pass(lchd_ctx* c, const ConsumerRequest& R, int cap, u
     sw.wf_index = R.wf;
     sw.n_pairs = R.n;
     sw.meta = st.pb.pair_meta;
-    if (int rc = consumer_enqueue(c, sw, R.use, R.out)) return rc;
+    if (R.use.width) {
+        ix.cfg = c->d_cfg; ix.thr = R.thr; ix.reach = plan.reach; ix.tag_list = plan.tag_list ? 1 : 0; ix.st = c->d_status;
+        const SideBufs* sb[2] = {&st.pb.a, &st.pb.b};
+        for (int k = 0; k < 2; ++k) {
+            GridView g{};
+            const GridPlan& gp = st.grid[k];
+            for (int q3 = 0; q3 < 3; ++q3) { g.min[q3] = gp.min[q3]; g.inv[q3] = gp.inv[q3]; g.cell[q3] = 1.0 / gp.inv[q3]; g.dim[q3] = gp.dim[q3]; }
+            g.n_cells = gp.n_cells; g.cell_start = sb[k]->cell_start; g.rec = sb[k]->rec; g.pos_of = sb[k]->pos_of;
+            ix.s[k].g = g;
+            ix.s[k].uniq = sb[k]->uniq;
+        }
+    }
+    if (int rc = consumer_enqueue(c, sw, R.use, R.out, R.use.width ? &ix : nullptr)) return rc;
     mark(c, 4);
     for (int k = 0; k < sides; ++k)
         if (R.cl[k]->ev_used) { HIP_TRY(hipEventRecord(R.cl[k]->ev_used, s)); R.cl[k]->used_valid = true; }
@@ -3748,8 +3825,17 @@ static int consumer_primitives_dev(lchd_ctx* c, lchd_cloud* const* cl, const int
         for (int attempt = 0; attempt < 8; ++attempt) {
             uint32_t f = 0;
             if (int rc = consumer_prims_pass(c, R, cap, &f)) return rc;
-            if ((f & ST_BAD_ANCHOR) || !(f & ST_ENV_OVERFLOW)) return status_to_rc(f & ~(uint32_t)ST_ENV_OVERFLOW, DRV_PRIMS);
             const HostStatus h = *c->h_status;
+            if ((f & ST_BAD_ANCHOR) || !(f & ST_ENV_OVERFLOW)) {
+                if (int rc = status_to_rc(f & ~(uint32_t)ST_ENV_OVERFLOW, DRV_PRIMS)) return rc;
+                if (use.width) {  // (the record pass publishes the longest environment among the pairs: the row width the call takes)
+                    c->sens_needed = (int64_t)h.max_env;
+                    if (h.max_env > (uint32_t)use.width)
+                        return fail(LCHD_EVALUE, "row width %d is too small: the longest environment of these pairs holds %u points (lchd_sensitivity_needed_width)",
+                                    use.width, h.max_env);
+                }
+                return LCHD_OK;
+            }
             const int64_t want = std::max<int64_t>(std::max<int64_t>(h.max_env, h.max_bound / 3), cap + 1);
             if (h.max_env > (uint32_t)kRadialMaxPoints || cap > kRadialMaxPoints)
                 return fail(LCHD_EUNSUPPORTED, "an environment holds %u points; %s takes at most %d", h.max_env, use.what, kRadialMaxPoints);
@@ -4146,3 +4232,54 @@ extern "C" int lchd_attribution_dmxs(lchd_ctx* c, const lchd_config* cfg, const 
     return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr, nullptr,
                            kAttribution, out);
 }
+
+// neighbour sensitivities: thresholded calls only (the kernels walk the pass's cell lists); every statistical distance.  The pass is the
+// attribution call's with the indexed lists and k_sensitivity (lchd_sensitivity.hip) behind the record pass.
+static int sens_args(lchd_ctx* c, int64_t n_pairs, int32_t width) {
+    if (c) c->sens_needed = 0;
+    if (width < 1 || width > kRadialMaxPoints) return fail(LCHD_EVALUE, "row width %d is outside 1 .. %d", width, kRadialMaxPoints);
+    if (n_pairs > 0 && (size_t)n_pairs > ((size_t)1 << 40) / (5 * (size_t)width + 2))
+        return fail(LCHD_EUNSUPPORTED, "%lld pairs with rows of %d slots exceed 8 TiB of output: split the list", (long long)n_pairs, width);
+    return LCHD_OK;
+}
+extern "C" int lchd_sensitivity_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
+                                               int64_t n_pairs, double thr, int32_t width, double* d_scores, int32_t* d_count_a, int32_t* d_idx_a,
+                                               double* d_dist_a, double* d_g_a, int32_t* d_count_b, int32_t* d_idx_b, double* d_dist_b,
+                                               double* d_g_b) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (int rc = sens_args(c, n_pairs, width)) return rc;
+    if (n_pairs > 0 && (!d_scores || !d_count_a || !d_idx_a || !d_dist_a || !d_g_a || !d_count_b || !d_idx_b || !d_dist_b || !d_g_b))
+        return fail(LCHD_EVALUE, "null output pointer");
+    if (a->images || b->images) return fail(LCHD_EUNSUPPORTED, "a sensitivity call takes the structures themselves, not periodic image clouds");
+    SensitivityOut o{};
+    o.scores = d_scores; o.count_a = d_count_a; o.count_b = d_count_b; o.idx_a = d_idx_a; o.idx_b = d_idx_b;
+    o.dist_a = d_dist_a; o.dist_b = d_dist_b; o.g_a = d_g_a; o.g_b = d_g_b;
+    lchd_cloud* const cl[2] = {a, b};
+    return consumer_primitives_dev(c, cl, d_anchors, d_wf_index, n_pairs, thr, sensitivity_consumer(width, o), d_scores);
+}
+extern "C" int lchd_sensitivity_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
+                                           int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
+                                           const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, int32_t width,
+                                           double* scores, int32_t* count_a, int32_t* idx_a, double* dist_a, double* g_a, int32_t* count_b,
+                                           int32_t* idx_b, double* dist_b, double* g_b) {
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = sens_args(c, n_pairs, width)) return rc;
+    if (n_pairs > 0 && (!scores || !count_a || !idx_a || !dist_a || !g_a || !count_b || !idx_b || !dist_b || !g_b))
+        return fail(LCHD_EVALUE, "null output pointer");
+    const size_t n = n_pairs > 0 ? (size_t)n_pairs : 0, nw = n * (size_t)width;
+    double* blk = n ? static_cast<double*>(malloc(sizeof(double) * n * (5 * (size_t)width + 2))) : nullptr;
+    if (n && !blk) return fail(LCHD_EUNSUPPORTED, "no host memory for the outputs of %lld pairs", (long long)n_pairs);
+    const int rc = pair_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, nullptr, nullptr,
+                                        nullptr, nullptr, sensitivity_consumer(width, SensitivityOut{}), blk);
+    if (rc == LCHD_OK && n) {
+        const SensitivityOut o = sens_carve(blk, n_pairs, width);
+        memcpy(scores, o.scores, 8 * n);
+        memcpy(g_a, o.g_a, 8 * nw); memcpy(g_b, o.g_b, 8 * nw);
+        memcpy(dist_a, o.dist_a, 8 * nw); memcpy(dist_b, o.dist_b, 8 * nw);
+        memcpy(idx_a, o.idx_a, 4 * nw); memcpy(idx_b, o.idx_b, 4 * nw);
+        memcpy(count_a, o.count_a, 4 * n); memcpy(count_b, o.count_b, 4 * n);
+    }
+    free(blk);
+    return rc;
+}
+extern "C" int64_t lchd_sensitivity_needed_width(lchd_ctx* c) { return c ? c->sens_needed : 0; }

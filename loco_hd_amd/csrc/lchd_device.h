@@ -442,6 +442,49 @@ struct AttributionArgs {
 // false: nothing launched (more than kAttributionMaxCategories categories, 16-bit category stores)
 bool launch_attribution(hipStream_t s, bool exponent2, bool unit_weights, const AttributionArgs& a);
 void init_attribution_kernels();  // per device, as init_radial_kernels
+// Neighbour sensitivities (lchd_sensitivity.hip): dS/dd of every member of a pair's two environments, and the score, from INDEXED
+// environment lists -- (distance, atom index, category) per point, ascending by (distance bits, atom index), the anchor first -- built
+// next to the scoring stores of the pass from the same cell lists and anchor records.
+constexpr int kSensitivityMaxCategories = 64;  // (tested up to here; the count columns of a wavefront, 260 bytes per category, live in LDS)
+struct IndexedStore {
+    double* dist;      // [slots][stride]
+    uint32_t* idx;     // [slots][stride] atom index in the cloud
+    uint8_t* cat;      // [slots][stride] category (255: not in the map)
+    int32_t* len;      // [slots] points incl. the anchor; 1 (the anchor alone) for a list that did not fit, 0 for an empty one
+    int64_t stride;    // a power of two, at most kRadialMaxPoints + 1
+};
+struct IndexedSide {
+    GridView g;              // the pass's cell list of the side
+    const AnchorRec* uniq;   // its anchor records
+    int64_t max_envs;        // slots (0: side B of a pass whose two sides are one object)
+    int32_t n;               // atoms
+    uint32_t* atom_of;       // [n] workspace: cell-order position -> atom (written by the launch)
+    IndexedStore env;
+};
+struct IndexedArgs {
+    const DevConfig* cfg;
+    IndexedSide s[2];
+    double thr;
+    int32_t reach;           // PassPlan::reach: the cell neighbourhood walked
+    int32_t tag_list;        // PassPlan::tag_list
+    const DeviceStatus* st;  // n_unique: the slots in use
+};
+bool launch_env_indexed(hipStream_t s, const IndexedArgs& a);  // false: nothing launched (a stride that is no power of two)
+struct SensitivityOut {      // all DEVICE; K = SensitivityArgs::width
+    double* scores;          // [P]
+    int32_t *count_a, *count_b;        // [P] members incl. the anchor (0: an unusable pair)
+    int32_t *idx_a, *idx_b;            // [P][K], padded with -1
+    double *dist_a, *dist_b, *g_a, *g_b;  // [P][K], padded with 0
+};
+struct SensitivityArgs {
+    SweepArgs sw;            // as RadialArgs::sw; the stores only through the pair records
+    IndexedStore env_a, env_b;
+    int32_t n_categories;    // DevConfig::n_categories (the launcher sizes the LDS with it)
+    int32_t width;           // K
+    SensitivityOut out;
+};
+bool launch_sensitivity(hipStream_t s, const SensitivityArgs& a);  // false: nothing launched (more than kSensitivityMaxCategories categories)
+void init_sensitivity_kernels();  // per device, as init_radial_kernels
 void launch_mark_overflow(hipStream_t s, const uint32_t* list_a, uint32_t na, const uint32_t* list_b, uint32_t nb, uint32_t* bits_a, uint32_t* bits_b);
 void launch_count_overflow(hipStream_t s, const OverflowSelect& a, unsigned long long* total);
 void launch_write_overflow(hipStream_t s, const OverflowSelect& a);

@@ -61,6 +61,41 @@ LCHD_HD double cdf_eval(int kind, const double* p, int np, double x) {
     }
 }
 
+// The densities w = F' (additive, not in the reference): the analytic derivative of each CDF as written above; 0 for x < 0.
+// d/dx [1 - sum_i a_i exp(-b_i x) / sum_i a_i]
+LCHD_HD double pdf_hyper_exp(const double* p, int np, double x) {
+    if (x < 0.0) return 0.0;
+    double norm = 0.0, sum = 0.0;
+    const int n = np / 2;
+    for (int i = 0; i < n; ++i) {
+        sum += p[i] * p[n + i] * exp(-p[n + i] * x);
+        norm += p[i];
+    }
+    return sum / norm;
+}
+// d/dx (1 + (x/B)^-A)^-P = (A P / x) t (1 + t)^(-P - 1), t = (x/B)^-A; 0 at x = 0 (the limit for A P > 1)
+LCHD_HD double pdf_dagum(const double* p, double x) {
+    if (!(x > 0.0)) return 0.0;
+    const double t = pow(x / p[1], -p[0]);
+    return p[0] * p[2] / x * t * pow(1.0 + t, -p[2] - 1.0);
+}
+// 1 / (b - a) on [a, b), 0 elsewhere
+LCHD_HD double pdf_uniform(const double* p, double x) { return (x < 0.0 || x < p[0] || !(x < p[1])) ? 0.0 : 1.0 / (p[1] - p[0]); }
+// d/dx [1 - (1 - z^a)^b] = a b z^(a-1) (1 - z^a)^(b-1) / (x_max - x_min) on [x_min, x_max], 0 elsewhere
+LCHD_HD double pdf_kumaraswamy(const double* p, double x) {
+    if (x < 0.0 || x < p[0] || x > p[1]) return 0.0;
+    const double z = (x - p[0]) / (p[1] - p[0]);
+    return p[2] * p[3] * pow(z, p[2] - 1.0) * pow(1.0 - pow(z, p[2]), p[3] - 1.0) / (p[1] - p[0]);
+}
+LCHD_HD double pdf_eval(int kind, const double* p, int np, double x) {
+    switch (kind) {
+        case WF_HYPER_EXP: return pdf_hyper_exp(p, np, x);
+        case WF_DAGUM: return pdf_dagum(p, x);
+        case WF_UNIFORM: return pdf_uniform(p, x);
+        default: return pdf_kumaraswamy(p, x);
+    }
+}
+
 // statistical_distances.rs:4-10.  P1/P2 are callables c -> probability so that kernels can feed
 // register-resident state without materialising the normalised vectors (pmf.rs:78-81 does).
 template <int NMAX, class P1, class P2>

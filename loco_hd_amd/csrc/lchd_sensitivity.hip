@@ -1,0 +1,414 @@
+// lchd_sensitivity.hip -- neighbour sensitivities of a pair's score (additive, not in the reference): the derivative of the score with
+// respect to the distance of every member of the pair's two environments.
+//
+//   S = sum_j (F(u_{j+1}) - F(u_j)) * H_j                    (merged breakpoints u_j, H_j the statistical distance on piece j)
+//   g = dS/dd = w(d) * (H- - H+)                             (w = F', H- / H+ the distance on the piece that ends / starts at the point)
+//
+// Moving a member moves one breakpoint: the piece in front of it grows by w(d) dd, the piece behind it shrinks by as much.  Members
+// entering or leaving at the threshold are ignored (exact when the weight function's support ends at or inside the threshold), and at
+// ties the derivative is one-sided: tied events are treated one at a time in list order.
+//
+// The environment stores of the scoring passes hold keys and categories only, so a sorted slot cannot be traced back to an atom.  This
+// translation unit therefore builds its own lists and sweeps them:
+//   k_atom_of_pos   the inverse of the prologue's atom -> cell-order position map
+//   k_env_indexed   one INDEXED environment list per de-duplicated anchor: (distance f64, atom index u32, category u8) per accepted
+//                   point, sorted ascending by (distance bits, atom index) with the anchor first -- one defined order among ties,
+//                   whatever order the appends took.  Same cell walk, distance expression, threshold comparison and tag rule as
+//                   k_env_cells (env_dist2 / env_accepts below are those lines; tag_pair_accepted and cell_coord are lchd_kcommon.h's).
+//   k_sensitivity   k_attribution's shape (lchd_attribution.hip): one pair per wavefront, tiles of kSweepTile merged events (merge path
+//                   on the distance bits, A first on ties), a wave scan of the per-lane category histograms for the counts at each
+//                   lane's first event, then every lane walks its events.  Per event it evaluates H on the counts behind the event
+//                   (sd_eval on the weighted, normalised counts: every statistical distance), has H in front of it from the previous
+//                   event -- a lane's first event takes it from the previous lane, lane 0 from the previous tile, carried like F --
+//                   and writes g to the event's slot of the pair's row of side A or B.  The same walk sums dF * H: the call returns
+//                   the scores without a second pass.  No floating-point atomics: every output element has one writer, and the
+//                   score is one wave reduction in lane order.
+#include "lchd_sweep_common.h"
+
+namespace lchd {
+
+constexpr int kIdxLdsPoints = 2048;       // k_env_indexed sorts lists of at most this many (padded) points in LDS, longer ones in place
+constexpr int kSensDynMax = 150 * 1024;   // dynamic LDS the k_sensitivity instantiations are allowed
+
+// ---- indexed environment lists -------------------------------------------------------------------------------------------------------
+__global__ void k_atom_of_pos(const uint32_t* __restrict__ pos_a, int32_t n_a, uint32_t* __restrict__ inv_a, const uint32_t* __restrict__ pos_b,
+                              int32_t n_b, uint32_t* __restrict__ inv_b) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_a) { const uint32_t p = pos_a[i]; if (p < (uint32_t)n_a) inv_a[p] = (uint32_t)i; }
+    else if (i - n_a < n_b) { const uint32_t p = pos_b[i - n_a]; if (p < (uint32_t)n_b) inv_b[p] = (uint32_t)(i - n_a); }
+}
+
+// k_env_cells' distance (utils.rs:1-8 order; the TU is built with -ffp-contract=off) and acceptance test (:521, :524-528)
+__device__ __forceinline__ double env_dist2(const CellRec& r, double ax, double ay, double az) {
+    const double dx = r.x - ax, dy = r.y - ay, dz = r.z - az;
+    double d2 = dx * dx;
+    d2 = d2 + dy * dy;
+    d2 = d2 + dz * dz;
+    return d2;
+}
+template <bool TAGLIST>
+__device__ __forceinline__ bool env_accepts(const DevConfig& cfg, double d2, double thr2, bool is_anchor, int32_t atag, int32_t tag) {
+    if (!(d2 < thr2)) return false;
+    if constexpr (TAGLIST) return is_anchor || tag_pair_accepted(cfg, atag, tag);
+    else return is_anchor || ((atag == tag) == (cfg.tag_accept_same != 0));
+}
+
+// bitonic sort of n2 (a power of two) triples by (key, sec); pads carry (kPadKey, ~0u)
+template <int NT>
+__device__ __forceinline__ void bitonic_sort_indexed(uint64_t* key, uint32_t* sec, uint8_t* cat, int n2, int tid) {
+    for (int k = 2; k <= n2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (n2 >> 1); t += NT) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int l = i | j;
+                const bool up = ((i & k) == 0);
+                const uint64_t a = key[i], b = key[l];
+                const uint32_t sa = sec[i], sb = sec[l];
+                const bool a_gt = a > b || (a == b && sa > sb), a_lt = a < b || (a == b && sa < sb);
+                if (up ? a_gt : a_lt) {
+                    key[i] = b; key[l] = a;
+                    sec[i] = sb; sec[l] = sa;
+                    const uint8_t ca = cat[i];
+                    cat[i] = cat[l];
+                    cat[l] = ca;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// One 256-thread workgroup per de-duplicated anchor; workgroups [0, s[0].max_envs) build side A, the rest side B.
+template <bool TAGLIST>
+__global__ __launch_bounds__(256) void k_env_indexed(IndexedArgs ia) {
+    constexpr int NT = 256;
+    __shared__ uint64_t l_key[kIdxLdsPoints];
+    __shared__ uint32_t l_sec[kIdxLdsPoints];
+    __shared__ uint8_t l_cat[kIdxLdsPoints];
+    __shared__ int count_s;
+    const int side = (int64_t)blockIdx.x >= ia.s[0].max_envs ? 1 : 0;
+    const IndexedSide& S = ia.s[side];
+    const int64_t e = (int64_t)blockIdx.x - (side ? ia.s[0].max_envs : 0);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (e >= (int64_t)ia.st->n_unique[side] || e >= S.max_envs) return;
+    const DevConfig cfg = *ia.cfg;
+    const GridView g = S.g;
+    const AnchorRec arec = S.uniq[e];
+    const double ax = arec.x, ay = arec.y, az = arec.z, thr2 = ia.thr * ia.thr;
+    const int32_t atag = (int32_t)arec.tag;
+    const int cap = (int)S.env.stride, reach = ia.reach;
+    uint64_t* const gk = reinterpret_cast<uint64_t*>(S.env.dist) + e * S.env.stride;
+    uint32_t* const gi = S.env.idx + e * S.env.stride;
+    uint8_t* const gc = S.env.cat + e * S.env.stride;
+    const int cx = cell_coord(ax, g.min[0], g.inv[0], g.dim[0]);
+    const int cy = cell_coord(ay, g.min[1], g.inv[1], g.dim[1]);
+    const int cz = cell_coord(az, g.min[2], g.inv[2], g.dim[2]);
+    const int x0 = max(cx - reach, 0), x1 = min(cx + reach, g.dim[0] - 1);
+    if (tid == 0) count_s = 0;
+    __syncthreads();
+    for (int zz = max(cz - reach, 0); zz <= min(cz + reach, g.dim[2] - 1); ++zz)
+        for (int yy = max(cy - reach, 0); yy <= min(cy + reach, g.dim[1] - 1); ++yy) {
+            // the x-neighbour cells of one (y, z) row are contiguous in the cell-ordered records
+            const int row = (int)((((int64_t)arec.sid * g.dim[2] + zz) * g.dim[1] + yy) * g.dim[0]);
+            const int beg = (int)g.cell_start[row + x0], end = (int)g.cell_start[row + x1 + 1];
+            for (int base = beg + wave * 64; base < end; base += NT) {
+                const int idx = base + lane;
+                bool ok = false;
+                double d2 = 0.0;
+                uint32_t ccat = 0;
+                if (idx < end) {
+                    const CellRec r = g.rec[idx];
+                    d2 = env_dist2(r, ax, ay, az);
+                    ccat = r.cat;
+                    ok = env_accepts<TAGLIST>(cfg, d2, thr2, (uint32_t)idx == arec.apos, atag, (int32_t)r.tag);
+                }
+                const unsigned long long m = __ballot(ok);
+                int wbase = 0;
+                if (lane == 0 && m) wbase = atomicAdd(&count_s, __popcll(m));
+                wbase = __shfl(wbase, 0);
+                if (ok) {
+                    const int pos = wbase + __popcll(m & ((1ull << lane) - 1ull));
+                    if (pos < cap) {
+                        gk[pos] = d2u(sqrt(d2));
+                        gi[pos] = (uint32_t)idx == arec.apos ? 0u : S.atom_of[idx] + 1u;  // the anchor sorts in front of every other point at distance 0
+                        gc[pos] = (uint8_t)(ccat > 255u ? 255u : ccat);
+                    }
+                }
+            }
+        }
+    __syncthreads();
+    const int count = count_s;
+    if (count > cap || count == 0) {
+        // Does not fit its slot: the scoring store of this pass flagged the same environment (the host repeats the pass with larger
+        // slots); the slot receives the anchor alone, a valid one-point list.  An empty list (non-finite coordinates) stays empty.
+        if (tid == 0) {
+            S.env.len[e] = count ? 1 : 0;
+            gk[0] = 0ull;
+            gi[0] = arec.atom;
+            const uint32_t acat = g.rec[arec.apos].cat;
+            gc[0] = (uint8_t)(acat > 255u ? 255u : acat);
+        }
+        return;
+    }
+    const int n2 = next_pow2(count);  // <= cap: the launcher takes power-of-two strides only
+    if (n2 <= kIdxLdsPoints) {
+        for (int i = tid; i < n2; i += NT) {
+            const bool in = i < count;
+            l_key[i] = in ? gk[i] : kPadKey;
+            l_sec[i] = in ? gi[i] : ~0u;
+            l_cat[i] = in ? gc[i] : (uint8_t)0;
+        }
+        __syncthreads();
+        bitonic_sort_indexed<NT>(l_key, l_sec, l_cat, n2, tid);
+        for (int i = tid; i < count; i += NT) {
+            gk[i] = l_key[i];
+            gi[i] = l_sec[i] ? l_sec[i] - 1u : arec.atom;
+            gc[i] = l_cat[i];
+        }
+    } else {
+        for (int i = count + tid; i < n2; i += NT) { gk[i] = kPadKey; gi[i] = ~0u; gc[i] = 0; }
+        __syncthreads();
+        bitonic_sort_indexed<NT>(gk, gi, gc, n2, tid);
+        for (int i = tid; i < count; i += NT) gi[i] = gi[i] ? gi[i] - 1u : arec.atom;
+    }
+    if (tid == 0) S.env.len[e] = count;
+}
+
+bool launch_env_indexed(hipStream_t s, const IndexedArgs& a) {
+    const int64_t blocks = a.s[0].max_envs + a.s[1].max_envs;
+    if (blocks <= 0) return true;
+    for (int k = 0; k < 2; ++k) {
+        const int64_t st = a.s[k].env.stride;
+        if (a.s[k].max_envs > 0 && (st < 1 || st > kRadialMaxPoints + 1 || (st & (st - 1)))) return false;
+    }
+    if (blocks > 0x7FFFFFFF || a.reach < 1) return false;
+    const int64_t n = (int64_t)a.s[0].n + (a.s[1].max_envs > 0 ? (int64_t)a.s[1].n : 0);
+    k_atom_of_pos<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(a.s[0].g.pos_of, a.s[0].n, a.s[0].atom_of, a.s[1].g.pos_of,
+                                                            a.s[1].max_envs > 0 ? a.s[1].n : 0, a.s[1].atom_of);
+    if (a.tag_list) k_env_indexed<true><<<(unsigned)blocks, 256, 0, s>>>(a);
+    else k_env_indexed<false><<<(unsigned)blocks, 256, 0, s>>>(a);
+    return true;
+}
+
+// ---- the sweep -----------------------------------------------------------------------------------------------------------------------
+// StatisticalDistance::run on one lane's count column (cnt[c * 64] = count_A | count_B << 16), normalised like pmf.rs:65-83; out of line:
+// the library's pow / log stay out of the event loop's code.
+static __device__ __noinline__ double sens_sd(int kind, double p0, double p1, const uint32_t* cnt, const double* __restrict__ w, int C, double ia,
+                                              double ib) {
+    return sd_eval<0>(kind, p0, p1, [&](int c) { return (w[c] * (double)(cnt[c * 64] & 0xFFFFu)) * ia; },
+                      [&](int c) { return (w[c] * (double)(cnt[c * 64] >> 16)) * ib; }, C);
+}
+static __device__ __noinline__ double sens_pdf(int kind, const double* p, int np, double x) { return pdf_eval(kind, p, np, x); }
+
+// Per wavefront, in dynamic LDS: two key tiles | count columns [C][64] | carry row [C] | two category tiles
+static size_t sensitivity_wave_bytes(int C) {
+    return ((size_t)kSweepTile * 16 + (size_t)C * 260 + (size_t)kSweepTile * 4 + 15) & ~(size_t)15;
+}
+
+// WPB: pairs (wavefronts) per workgroup.
+template <int WPB>
+__global__ __launch_bounds__(64 * WPB) void k_sensitivity(SensitivityArgs sa, int wave_bytes) {
+    constexpr int TILE = kSweepTile;
+    constexpr uint32_t kOneA = 1u, kOneB = 1u << 16, kMaskA = 0xFFFFu;
+    extern __shared__ __attribute__((aligned(16))) unsigned char sens_smem[];
+    const SweepArgs& args = sa.sw;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const DevConfig* __restrict__ cfgp = args.cfg;
+    const int C = cfgp->n_categories, K = sa.width;
+    const double* __restrict__ cat_w = cfgp->cat_w;
+    unsigned char* const base = sens_smem + (size_t)wv * wave_bytes;
+    uint64_t* const sA = reinterpret_cast<uint64_t*>(base);
+    uint64_t* const sB = sA + TILE;
+    uint32_t* const cnt0 = reinterpret_cast<uint32_t*>(sB + TILE);
+    uint32_t* const cnt = cnt0 + lane;                        // this lane's count column: cnt[c * 64]
+    uint32_t* const carry = cnt0 + (size_t)C * 64;            // per category: counts before the current tile
+    uint16_t* const cA = reinterpret_cast<uint16_t*>(carry + C);
+    uint16_t* const cB = cA + TILE;
+
+    const int n_wf = cfgp->n_wf;
+    const int sd_kind = cfgp->sd_kind;
+    const double prm0 = cfgp->sd_p0, prm1 = cfgp->sd_p1;
+    const int64_t pstride = (int64_t)gridDim.x * WPB;
+    for (int64_t p = (int64_t)blockIdx.x * WPB + wv; p < args.n_pairs; p += pstride) {
+        const int64_t row = p * (int64_t)K;
+        double *const gA = sa.out.g_a + row, *const gB = sa.out.g_b + row;
+        const int4 m = args.meta[p];
+        const int mx = __builtin_amdgcn_readfirstlane(m.x), my = __builtin_amdgcn_readfirstlane(m.y);
+        const int mz = __builtin_amdgcn_readfirstlane(m.z), mw = __builtin_amdgcn_readfirstlane(m.w);
+        const bool usable = (mz & 0xFFFFFF) > 0 && (mw & 0xFFFFFF) > 0;  // (anchor out of range, overflowed or empty environment: flagged where it happened)
+        const int64_t ea = mx, eb = my;
+        const int nA = usable ? __builtin_amdgcn_readfirstlane(sa.env_a.len[ea]) : 0, nB = usable ? __builtin_amdgcn_readfirstlane(sa.env_b.len[eb]) : 0;
+        const int wfi = __builtin_amdgcn_readfirstlane(args.wf_index ? args.wf_index[p] : 0);
+        const bool bad_wf = wfi < 0 || wfi >= n_wf;
+        // ... or an index outside the dictionary, or a list longer than the caller's rows (the host reports the width it takes)
+        if (nA <= 0 || nB <= 0 || nA > kRadialMaxPoints || nB > kRadialMaxPoints || nA > K || nB > K || bad_wf) {
+            if (bad_wf && lane == 0) sweep_report(args.hst, ST_BAD_WF);
+            for (int t = lane; t < K; t += 64) {
+                gA[t] = nan(""); gB[t] = nan("");
+                sa.out.dist_a[row + t] = 0.0; sa.out.dist_b[row + t] = 0.0;
+                sa.out.idx_a[row + t] = -1; sa.out.idx_b[row + t] = -1;
+            }
+            if (lane == 0) { sa.out.scores[p] = nan(""); sa.out.count_a[p] = 0; sa.out.count_b[p] = 0; }
+            continue;
+        }
+        const uint64_t* __restrict__ kA = reinterpret_cast<const uint64_t*>(sa.env_a.dist) + ea * sa.env_a.stride;
+        const uint64_t* __restrict__ kB = reinterpret_cast<const uint64_t*>(sa.env_b.dist) + eb * sa.env_b.stride;
+        const uint8_t* __restrict__ tA = sa.env_a.cat + ea * sa.env_a.stride;
+        const uint8_t* __restrict__ tB = sa.env_b.cat + eb * sa.env_b.stride;
+        const uint32_t* __restrict__ xA = sa.env_a.idx + ea * sa.env_a.stride;
+        const uint32_t* __restrict__ xB = sa.env_b.idx + eb * sa.env_b.stride;
+        const WfEntry wf = cfgp->wf[wfi];
+        const double* __restrict__ prm = cfgp->wf_params + wf.offset;
+        const double winv = cfgp->wf_inv[wfi], Finf = cfgp->wf_finf[wfi];
+        // the lists themselves, the padding, and the slots no event writes: the anchor's (0) and those behind the list
+        for (int t = lane; t < K; t += 64) {
+            sa.out.idx_a[row + t] = t < nA ? (int32_t)xA[t] : -1;
+            sa.out.idx_b[row + t] = t < nB ? (int32_t)xB[t] : -1;
+            sa.out.dist_a[row + t] = t < nA ? u2d(kA[t]) : 0.0;
+            sa.out.dist_b[row + t] = t < nB ? u2d(kB[t]) : 0.0;
+            if (t == 0 || t >= nA) gA[t] = 0.0;
+            if (t == 0 || t >= nB) gB[t] = 0.0;
+        }
+        if (lane == 0) { sa.out.count_a[p] = nA; sa.out.count_b[p] = nB; }
+
+        const int c0a = tA[0], c0b = tB[0];
+        bool bad_cat = c0a >= C || c0b >= C, zero_norm = false;
+        // H on this lane's counts
+        auto distance = [&]() -> double {
+            double sa_ = 0.0, sb_ = 0.0;  // pmf.rs:67-68: fresh sums
+            for (int c = 0; c < C; ++c) {
+                const uint32_t v = cnt[c * 64];
+                sa_ += cat_w[c] * (double)(v & kMaskA);
+                sb_ += cat_w[c] * (double)(v >> 16);
+            }
+            if (sa_ == 0.0 || sb_ == 0.0) { zero_norm = true; return 0.0; }
+            return sens_sd(sd_kind, prm0, prm1, cnt, cat_w, C, 1.0 / sa_, 1.0 / sb_);
+        };
+
+        // the two anchors (src/locohd.rs:82-84) in the carry row and in every lane's column
+        wave_sync_lds();
+        for (int c = lane; c < C; c += 64) carry[c] = (c == c0a ? kOneA : 0u) | (c == c0b ? kOneB : 0u);
+        for (int c = 0; c < C; ++c) cnt[c * 64] = (c == c0a ? kOneA : 0u) | (c == c0b ? kOneB : 0u);
+        wave_sync_lds();
+        double F_carry = cdf_lean(wf.kind, prm, wf.n_params, winv, 0.0) + 0.0;  // F(0): both anchors sit at distance 0
+        double H_carry = bad_cat ? 0.0 : distance();
+        double score = 0.0;  // this lane's part of sum dF * H
+
+        const int mA = nA - 1, mB = nB - 1, M = mA + mB;  // non-anchor events
+        int ia = 0, ib = 0;
+        for (int k0 = 0; k0 < M; k0 += TILE) {
+            const int T = min(TILE, M - k0);
+            const int nAt = min(TILE, mA - ia), nBt = min(TILE, mB - ib);
+            wave_sync_lds();  // previous tile fully consumed
+            for (int t = lane; t < nAt; t += 64) { sA[t] = kA[1 + ia + t]; cA[t] = tA[1 + ia + t]; }
+            for (int t = lane; t < nBt; t += 64) { sB[t] = kB[1 + ib + t]; cB[t] = tB[1 + ib + t]; }
+            wave_sync_lds();
+            const int epl = (T + 63) >> 6;
+            const int d0 = min(lane * epl, T), d1 = min(d0 + epl, T);
+            const int i1 = merge_path(sA, nAt, sB, nBt, d1);
+            int i0 = __shfl_up(i1, 1);
+            if (lane == 0) i0 = 0;
+            const int iend = __builtin_amdgcn_readlane(i1, 63);
+            const int j0 = d0 - i0, j1 = d1 - i1;
+            const int last = (T - 1) / epl;  // the last lane with events (wave-uniform)
+            const bool has = d0 < d1;
+
+            // pass 1: histogram of this lane's chunk into its column, wave scan per category
+            for (int c = 0; c < C; ++c) cnt[c * 64] = 0u;
+            for (int i = i0; i < i1; ++i) {
+                const int ct = cA[i];
+                if (ct >= C) bad_cat = true; else cnt[ct * 64] += kOneA;
+            }
+            for (int j = j0; j < j1; ++j) {
+                const int ct = cB[j];
+                if (ct >= C) bad_cat = true; else cnt[ct * 64] += kOneB;
+            }
+            for (int c = 0; c < C; ++c) {
+                const uint32_t own = cnt[c * 64];
+                const uint32_t incl = wave_incl_scan_u32(own + (lane == 0 ? carry[c] : 0u));
+                cnt[c * 64] = incl - own;
+                if (lane == 63) carry[c] = incl;
+            }
+
+            // pass 2: this lane's events, one after the other
+            int i = i0, j = j0;
+            uint64_t ka = (i < i1) ? sA[i] : kPadKey, kb = (j < j1) ? sB[j] : kPadKey;
+            const double firstF = has ? cdf_lean(wf.kind, prm, wf.n_params, winv, u2d(ka <= kb ? ka : kb)) + 0.0 : 0.0;
+            const double nextF = shfl_f64(firstF, min(lane + 1, 63));  // F at the first event of the next lane's chunk
+            double Fp = F_carry, Hp = 0.0;
+            bool open = lane == 0;  // lane 0 closes the interval the previous tile (or the anchors) left open, on H_carry
+            // the lane's first event: H in front of it is the previous lane's (lane 0: the previous tile's) last value -- written after the walk
+            double* first_out = nullptr;
+            double first_w = 0.0, first_H = 0.0;
+            for (int e = d0; e < d1; ++e) {
+                const bool takeA = (ka <= kb);  // an exhausted run shows the pad key (> every real key); A first on ties
+                const uint64_t key = takeA ? ka : kb;
+                const int ct = takeA ? cA[i] : cB[j];
+                double* const slot = takeA ? gA + (1 + ia + i) : gB + (1 + ib + j);
+                if (takeA) { ++i; ka = (i < i1) ? sA[i] : kPadKey; } else { ++j; kb = (j < j1) ? sB[j] : kPadKey; }
+                const double d = u2d(key);
+                double F = cdf_lean(wf.kind, prm, wf.n_params, winv, d) + 0.0;
+                F = F < Fp ? Fp : F;  // (F is monotone; its floating-point evaluation may invert the last bit between neighbours)
+                if (open && !bad_cat) score += (F - Fp) * (e == d0 ? H_carry : Hp);
+                // pmf.rs:47-63: one more point of category ct on one side
+                if (ct < C) cnt[ct * 64] += takeA ? kOneA : kOneB;
+                else bad_cat = true;
+                const double Hn = bad_cat ? 0.0 : distance();
+                const double w = sens_pdf(wf.kind, prm, wf.n_params, d);
+                if (e == d0) { first_out = slot; first_w = w; first_H = Hn; }
+                else *slot = w * (Hp - Hn);
+                open = true;
+                Hp = Hn;
+                Fp = F;
+            }
+            if (has && lane < last && !bad_cat) score += ((nextF < Fp ? Fp : nextF) - Fp) * Hp;
+            double Hprev = shfl_up_f64(Hp, 1);  // (lanes 1 .. last: lane - 1 has events)
+            if (lane == 0) Hprev = H_carry;
+            if (first_out) *first_out = first_w * (Hprev - first_H);
+            F_carry = readlane_f64(Fp, last);
+            H_carry = readlane_f64(Hp, last);
+            ia += iend;
+            ib += T - iend;
+        }
+        // the last interval to +inf (:165-171,204-210,212-221) on the counts of the whole pair
+        const unsigned long long anybad = __ballot(bad_cat), anyzero = __ballot(zero_norm);
+        if (lane == 0 && Finf > F_carry) score += (Finf - F_carry) * H_carry;
+        const double total = wave_sum_f64(score);
+        if (lane == 0) {
+            if (anybad) sweep_report(args.hst, ST_BAD_CATEGORY);
+            if (anyzero) sweep_report(args.hst, ST_ZERO_NORM);
+            sa.out.scores[p] = (anybad || anyzero) ? nan("") : total;
+        }
+        if (anybad || anyzero) {  // the rows of an unusable pair are NaN, as its score is (the event stores above have landed first)
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+            for (int t = lane; t < K; t += 64) { gA[t] = nan(""); gB[t] = nan(""); }
+        }
+    }
+}
+
+bool launch_sensitivity(hipStream_t s, const SensitivityArgs& a) {
+    if (a.sw.n_pairs <= 0) return true;
+    if (a.n_categories < 1 || a.n_categories > kSensitivityMaxCategories || a.width < 1) return false;
+    const size_t wb = sensitivity_wave_bytes(a.n_categories);
+    auto go = [&](auto wpb) {
+        constexpr int WPB = decltype(wpb)::value;
+        const int64_t blocks = (a.sw.n_pairs + WPB - 1) / WPB;
+        k_sensitivity<WPB><<<(unsigned)(blocks < 8192 ? blocks : 8192), 64 * WPB, wb * WPB, s>>>(a, (int)wb);
+    };
+    // the most pairs per workgroup (4, 2 or 1) whose LDS fits
+    if (wb * 4 <= (size_t)kSensDynMax) go(std::integral_constant<int, 4>{});
+    else if (wb * 2 <= (size_t)kSensDynMax) go(std::integral_constant<int, 2>{});
+    else if (wb <= (size_t)kSensDynMax) go(std::integral_constant<int, 1>{});
+    else return false;
+    return true;
+}
+
+void init_sensitivity_kernels() {
+    const void* list[] = {reinterpret_cast<const void*>(&k_sensitivity<4>), reinterpret_cast<const void*>(&k_sensitivity<2>),
+                          reinterpret_cast<const void*>(&k_sensitivity<1>)};
+    for (const void* fn : list) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kSensDynMax);
+    (void)hipGetLastError();
+}
+
+}  // namespace lchd

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .api import LoCoHD, dense_cells, periodic_boxes, periodic_cells
+from .api import LoCoHD, Sensitivity, dense_cells, periodic_boxes, periodic_cells
 
 
 def last_sweep_of(ctx):
@@ -340,6 +340,77 @@ class DeviceSession:
         anchors: torch int64 CUDA tensor [P][2]; wf_index: torch int32 CUDA tensor [P] or None; returns (or fills) a torch float64
         CUDA tensor [P][C] (lchd_attribution_primitives_dev)."""
         return self._pair_rows(None, cloud_a, cloud_b, anchors, threshold_distance, out, wf_index)
+
+    def sensitivity(self, cloud_a, cloud_b, anchors, threshold_distance: float, out=None, wf_index=None, *, width=None):
+        """Neighbour sensitivities (LoCoHD.sensitivity_from_primitives) of anchor pairs of two uploaded structures or batches (no image
+        clouds).  anchors: torch int64 CUDA tensor [P][2]; wf_index: torch int32 CUDA tensor [P] or None.  Returns a `Sensitivity` of
+        torch CUDA tensors: scores [P] f64, count_a / count_b [P] i32, idx_a / idx_b [P][K] i32 (padded with -1), dist_a / dist_b /
+        g_a / g_b [P][K] f64 (padded with 0).  K: `width`, or the width of `out` (a `Sensitivity` of such tensors, filled and
+        returned; ValueError if an environment is longer), or -- with neither -- the longest environment, found by repeating a call
+        whose first guess of 128 was too narrow (lchd_sensitivity_primitives_dev).  The derivative ignores points entering or leaving at
+        the threshold and is one-sided at ties."""
+        torch = self.torch
+        assert anchors.is_cuda and anchors.dtype == torch.int64 and anchors.is_contiguous()
+        p = anchors.shape[0]
+        wf_ptr = None
+        if wf_index is not None:
+            assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= p
+            wf_ptr = C.c_void_p(wf_index.data_ptr())
+        fixed = out is not None or width is not None
+        k = int(out.idx_a.shape[1]) if out is not None else (128 if width is None else int(width))
+        while True:
+            if out is None:
+                dev = anchors.device
+                f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)  # noqa: E731
+                i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)  # noqa: E731
+                res = Sensitivity(f64(p), i32(p), i32(p, k), f64(p, k), f64(p, k), i32(p), i32(p, k), f64(p, k), f64(p, k))
+            else:
+                res = out
+                for name, t in zip(Sensitivity._fields, res):
+                    want = torch.int32 if name.startswith(("count", "idx")) else torch.float64
+                    rows = (p,) if name in ("scores", "count_a", "count_b") else (p, k)
+                    assert t.is_cuda and t.dtype == want and t.is_contiguous() and tuple(t.shape) == rows, name
+            if p == 0:
+                return res
+            rc = N.lib().lchd_sensitivity_primitives_dev(self._ctx, cloud_a, cloud_b, C.c_void_p(anchors.data_ptr()), wf_ptr, p,
+                                                         float(threshold_distance), k, *[C.c_void_p(t.data_ptr()) for t in res])
+            need = int(N.lib().lchd_sensitivity_needed_width(self._ctx))
+            if rc == N.EVALUE and not fixed and need > k:
+                k = need
+                continue
+            N.check(rc)
+            if not fixed and 0 < need < k:  # rows as wide as the longest environment, as the host call returns them
+                res = Sensitivity(*[t[:, :need].contiguous() if t.dim() == 2 else t for t in res])
+            return res
+
+    def gradient(self, cloud_a, cloud_b, anchors, threshold_distance: float, xyz_a, xyz_b, pair_weights=None, wf_index=None):
+        """`(scores, grad_a[Na, 3], grad_b[Nb, 3])` with grad = sum_p v_p dS_p/dx (LoCoHD.gradient_from_primitives) as torch CUDA tensors.
+        xyz_a / xyz_b: the coordinates of the two clouds as torch float64 CUDA tensors [N][3]; pair_weights: v, a tensor [P] (default:
+        ones).  Assembled from `sensitivity` with torch.Tensor.index_add_: its summation order, and so the last bits, follow torch's
+        determinism setting."""
+        sens = self.sensitivity(cloud_a, cloud_b, anchors, threshold_distance, wf_index=wf_index)
+        return (sens.scores,) + self.assemble_gradient(sens, xyz_a, xyz_b, pair_weights)
+
+    def assemble_gradient(self, sens, xyz_a, xyz_b, pair_weights=None):
+        """The two coordinate gradients of sum_p v_p S_p from a `Sensitivity` of tensors: member += v g (x_m - x_anchor) / d, anchor -= the
+        same; members at distance 0 and the padding are skipped."""
+        return (self.side_gradient(sens.scores, sens.idx_a, sens.dist_a, sens.g_a, xyz_a, pair_weights),
+                self.side_gradient(sens.scores, sens.idx_b, sens.dist_b, sens.g_b, xyz_b, pair_weights))
+
+    def side_gradient(self, scores, idx, dist, g, xyz, pair_weights=None):
+        """One side of assemble_gradient: [N][3] f64."""
+        torch = self.torch
+        v = torch.ones_like(scores) if pair_weights is None else pair_weights.to(scores.dtype).reshape(-1)
+        grad = torch.zeros(xyz.shape, dtype=torch.float64, device=xyz.device)
+        use = (idx >= 0) & (dist > 0.0) & torch.isfinite(g)
+        use[:, 0] = False
+        member = idx.clamp(min=0).long()
+        anchor = member[:, :1].expand_as(member)
+        coef = torch.where(use, v[:, None] * g / torch.where(use, dist, torch.ones_like(dist)), torch.zeros_like(g))
+        step = coef[..., None] * (xyz[member] - xyz[anchor])  # [P][K][3]; zero rows where `use` is false
+        grad.index_add_(0, member.reshape(-1), step.reshape(-1, 3))
+        grad.index_add_(0, anchor.reshape(-1), -step.reshape(-1, 3))
+        return grad
 
     def attribution_coords(self, cloud_a, cloud_b, out=None, wf_index=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None):
         """Score attribution by category of the dense row pairs of two uploaded structures of equal size
