@@ -544,6 +544,48 @@ int lchd_sensitivity_primitives(lchd_ctx *ctx, const lchd_config *cfg, const dou
                                 int32_t *idx_b, double *dist_b, double *g_b);
 int64_t lchd_sensitivity_needed_width(lchd_ctx *ctx);
 
+/* ---- cross-scoring (additive, not in the reference) ------------------------------------------------------
+ * Every anchor of one list against every anchor of another: which environments of B look like this environment of A.
+ *   cross:   out[i][j] = the score lchd_from_primitives_dev gives the pair (anchors_a[i], anchors_b[j]) -- same threshold, configuration
+ *            and tag rule; a row-major [n_a][n_b] matrix.
+ *   nearest: per row i the k columns with the smallest (score, j), ascending in that key: scores[n_a][k] and cols[n_a][k] (i32 positions
+ *            in anchors_b).  The secondary key j makes the order a function of the score matrix alone.  1 <= k <= min(n_b, 64).
+ * anchors_a / anchors_b: [n_a] / [n_b] atom indices into side A / side B (for batches, frames buffers and image clouds: positions in the
+ * concatenated arrays, as in lchd_from_primitives_dev); repeats are allowed on both sides.  wf_index: one weight function of the
+ * configuration for the whole call, or -1: none (the pass runs without an index list, as lchd_from_primitives_dev with d_wf_index NULL).
+ * No pair list exists on the host: the call walks A in tiles of tile_rows anchors, writes the [tile_rows * n_b][2] pair records of a tile
+ * on the device (k_cross_pairs), scores them with the pass of lchd_from_primitives_dev -- unchanged, capacity repeats and the second pass
+ * over overflowed environments included -- and, for nearest, reduces the tile's scores to k per row (k_nearest_rows, one wavefront per
+ * row).  Rows never span tiles and a score does not depend on the tile it is computed in under lchd_ctx_set_deterministic, so both
+ * results are then bit-identical for every tile_rows; nearest is always the exact selection on the scores its own passes computed.
+ * tile_rows: 0 = lchd_cross_plan on a quarter of the free device memory; > 0: that many rows per tile (memory control, tests), clamped
+ * to n_a; a tile of more than 2^31 - 1 pairs is LCHD_EVALUE, as is tile_rows < 0 and a k outside 1 .. min(n_b, 64).
+ * Other errors: those lchd_from_primitives_dev gives for the same defect (an anchor outside its structure: LCHD_EPANIC, ...); with n_a
+ * or n_b == 0 there is nothing to score and the cross form returns LCHD_OK, as that call does for no pairs.  Stream and lock rules as lchd_from_primitives_dev: the context is held once for the whole call, all work
+ * runs on the context's stream, the call returns with the outputs complete.  Afterwards the context's hints and lchd_ctx_last_*
+ * read-backs describe the last tile's pass. */
+/* Pure host arithmetic, no device: the largest tile_rows in 1 .. n_a for which a tile's pair records (16 bytes per pair), weight-function
+ * indices (4) and score scratch (8) fit in budget_bytes and the tile holds at most 2^31 - 1 pairs.  LCHD_EUNSUPPORTED if one row does not
+ * fit (a row of more than 2^31 - 1 pairs included), LCHD_EVALUE for n_a < 1, n_b < 1, budget_bytes < 0 or a null output. */
+int lchd_cross_plan(int64_t n_a, int64_t n_b, int64_t budget_bytes, int64_t *tile_rows_out);
+/* anchors and outputs DEVICE; d_out: [n_a][n_b] doubles */
+int lchd_cross_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors_a, int64_t n_a,
+                              const int64_t *d_anchors_b, int64_t n_b, int32_t wf_index, double threshold_distance, int64_t tile_rows,
+                              double *d_out);
+/* d_scores: [n_a][k] doubles, d_cols: [n_a][k] i32 */
+int lchd_nearest_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors_a, int64_t n_a,
+                                const int64_t *d_anchors_b, int64_t n_b, int32_t wf_index, double threshold_distance, int64_t tile_rows,
+                                int32_t k, double *d_scores, int32_t *d_cols);
+/* The same from host arrays (open structures, as lchd_from_primitives takes them): temporary clouds, then the _dev forms; outputs HOST. */
+int lchd_cross_primitives(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a, const int32_t *tag_a, int64_t n_atoms_a,
+                          const double *xyz_b, const int32_t *cat_b, const int32_t *tag_b, int64_t n_atoms_b, const int64_t *anchors_a,
+                          int64_t n_a, const int64_t *anchors_b, int64_t n_b, int32_t wf_index, double threshold_distance, int64_t tile_rows,
+                          double *out);
+int lchd_nearest_primitives(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a, const int32_t *tag_a,
+                            int64_t n_atoms_a, const double *xyz_b, const int32_t *cat_b, const int32_t *tag_b, int64_t n_atoms_b,
+                            const int64_t *anchors_a, int64_t n_a, const int64_t *anchors_b, int64_t n_b, int32_t wf_index,
+                            double threshold_distance, int64_t tile_rows, int32_t k, double *scores, int32_t *cols);
+
 /* ---- multi-GPU ------------------------------------------------------------------------------------
  * The reference's parallelism lives INSIDE the core call: a thread pool that is a field of `LoCoHD` (src/locohd.rs:53,
  * 373-383) runs the anchor pairs of one call (:545-557, order-preserving collect).  The counterpart here is a GROUP of

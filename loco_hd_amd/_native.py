@@ -131,6 +131,13 @@ _PROTOS = {
     "lchd_sensitivity_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _i32,
                                               _DP, _IP, _IP, _DP, _DP, _IP, _IP, _DP, _DP]),
     "lchd_sensitivity_needed_width": (C.c_int64, [_VP]),
+    "lchd_cross_plan": (C.c_int, [_i64, _i64, _i64, _LP]),
+    "lchd_cross_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _i64, _VP, _i64, _i32, _f64, _i64, _VP]),
+    "lchd_nearest_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _i64, _VP, _i64, _i32, _f64, _i64, _i32, _VP, _VP]),
+    "lchd_cross_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _i64, _LP, _i64, _i32, _f64, _i64,
+                                        _DP]),
+    "lchd_nearest_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _i64, _LP, _i64, _i32, _f64, _i64,
+                                          _i32, _DP, _IP]),
     "lchd_cloud_create": (C.c_int, [_VP, _DP, _IP, _IP, _i64, C.POINTER(_VP)]),
     "lchd_cloud_create_batch": (C.c_int, [_VP, _DP, _IP, _IP, _IP, _i64, _i32, C.POINTER(_VP)]),
     "lchd_cloud_size": (C.c_int64, [_VP]),

@@ -26,6 +26,8 @@ from . import _native as N
 
 # what LoCoHD.sensitivity_from_primitives returns (DeviceSession.sensitivity: the same fields as torch tensors)
 Sensitivity = namedtuple("Sensitivity", "scores count_a idx_a dist_a g_a count_b idx_b dist_b g_b")
+# what LoCoHD.nearest_from_primitives returns (DeviceSession.nearest: the same fields as torch tensors)
+Nearest = namedtuple("Nearest", "scores cols")
 
 try:  # built by `make -C loco_hd_amd/csrc`; argument conversion only -- without it the same conversion runs as a Python loop
     from . import _fastpack
@@ -1014,6 +1016,63 @@ class LoCoHD:
         pa, pb, _ = self._packed_lists(prim_a, prim_b)
         ga, gb = self._assemble_gradient(sens, _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3), pair_weights)
         return sens.scores, ga, gb
+
+    # ---- cross-scoring (additive) ---------------------------------------------------------------------------
+    # Every anchor of one list against every anchor of another (include/loco_hd_hip.h, "cross-scoring"): the pair list is generated on the
+    # device tile by tile, scored by the pass of from_primitives, and -- for nearest -- reduced to the k best columns per row there.
+    def _cross_arguments(self, what: str, anchors_a, anchors_b, w_func_key, tile_rows, k=None):
+        """The checks that need no device; returns (anchors_a, anchors_b, wf index or -1, tile_rows) as arrays / ints."""
+        if self._devices is not None:
+            raise NotImplementedError(f"{what} applies to one device (the device group {self._devices} has no cross-scoring call): "
+                                      "drop devices=[...]")
+        lists = []
+        for anchors in (anchors_a, anchors_b):
+            idx_list = [int(a) for a in anchors]
+            if any(a < 0 for a in idx_list):
+                raise OverflowError("can't convert negative int to unsigned")
+            lists.append(np.asarray(idx_list, dtype=np.int64).reshape(-1))
+        na, nb = len(lists[0]), len(lists[1])
+        if k is not None and not 1 <= int(k) <= min(nb, 64):
+            raise ValueError(f"k = {int(k)} is outside 1 .. min(Nb, 64) with Nb = {nb}")
+        if int(tile_rows) < 0:
+            raise ValueError(f"tile_rows = {int(tile_rows)} is negative (0: planned from the free device memory)")
+        if na == 0 or nb == 0:  # what from_primitives makes of an empty pair list (AnchorPairSpecifier: the with-key variant)
+            self._wf_indices([], 0)
+            raise ValueError("Invalid pairing for the LoCoHD instance's w_func option and the method's w_func_keys parameter!")
+        idx = self._wf_indices(None if w_func_key is None else [str(w_func_key)], 1)
+        return lists[0], lists[1], -1 if idx is None else int(idx[0]), int(tile_rows)
+
+    def _cross_call(self, what, prim_a, prim_b, anchors_a, anchors_b, threshold_distance, w_func_key, tile_rows, k):
+        anc_a, anc_b, wf, tile_rows = self._cross_arguments(what, anchors_a, anchors_b, w_func_key, tile_rows, k)
+        pa, pb, interner = self._packed_lists(prim_a, prim_b)
+        cfg, keep = self._config(interner)
+        xa, xb = _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3)
+        head = (self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa), N.dp(xb), N.ip(pb.cat), N.ip(pb.tag), len(xb),
+                N.lp(anc_a), len(anc_a), N.lp(anc_b), len(anc_b), wf, float(threshold_distance), tile_rows)
+        if k is None:
+            out = np.empty((len(anc_a), len(anc_b)))
+            N.check(N.lib().lchd_cross_primitives(*head, N.dp(out)))
+            return out
+        scores, cols = np.empty((len(anc_a), int(k))), np.empty((len(anc_a), int(k)), dtype=np.int32)
+        N.check(N.lib().lchd_nearest_primitives(*head, int(k), N.dp(scores), N.ip(cols)))
+        return Nearest(scores, cols)
+
+    def cross_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchors_a, anchors_b,
+                              threshold_distance: float, w_func_key: Optional[str] = None, *, tile_rows: int = 0) -> np.ndarray:
+        """Additive: every anchor of `anchors_a` (indices into `prim_a`) against every anchor of `anchors_b` (indices into `prim_b`;
+        repeats allowed in both) as a float64 array (Na, Nb): out[i][j] is the score `from_primitives` gives the pair (anchors_a[i],
+        anchors_b[j]).  `w_func_key`: the key of one weight function for the whole call, resolved as a key in an anchor-pair specifier
+        is.  `tile_rows` (keyword-only): rows of A scored per pass -- 0 lets the library plan it from the free device memory; a number
+        bounds the device memory of the call and lets tests force tiling.  Open structures only; no device groups."""
+        return self._cross_call("cross_from_primitives", prim_a, prim_b, anchors_a, anchors_b, threshold_distance, w_func_key, tile_rows, None)
+
+    def nearest_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchors_a, anchors_b,
+                                threshold_distance: float, k: int, w_func_key: Optional[str] = None, *, tile_rows: int = 0) -> Nearest:
+        """Additive: for every anchor of `anchors_a` the `k` anchors of `anchors_b` with the smallest (score, j), ascending, as
+        `Nearest(scores (Na, k) float64, cols (Na, k) int32)` -- `cols` are positions in `anchors_b`, and the secondary key j makes the
+        order a function of the score matrix of `cross_from_primitives` alone.  1 <= k <= min(Nb, 64).  The score matrix is never moved
+        to the host: it is reduced on the device tile by tile.  Other arguments as `cross_from_primitives`."""
+        return self._cross_call("nearest_from_primitives", prim_a, prim_b, anchors_a, anchors_b, threshold_distance, w_func_key, tile_rows, int(k))
 
     def _no_device_group_with_box(self) -> None:
         if self._devices is not None:

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/loco_hd_hip.h"
+#include "lchd_cross_plan.h"
 #include "lchd_device.h"
 #include "lchd_math.h"
 #include "lchd_radial_bins.h"
@@ -279,6 +280,8 @@ struct lchd_ctx {
     char* d_indexed = nullptr;        // sensitivity calls: the indexed environment lists of both sides (grow-only, outside the arena likewise)
     size_t indexed_cap = 0;
     int64_t sens_needed = 0;          // lchd_sensitivity_needed_width: the longest list among the pairs of the last sensitivity call
+    char* d_cross = nullptr;          // cross-scoring calls: the pair records, wf indices and score scratch of one row tile (grow-only likewise)
+    size_t cross_cap = 0;
     int64_t n_subset_passes = 0;    // second passes run so far
     size_t last_store_bytes = 0;    // environment-store bytes (keys + categories, both sides) of the passes of the last from_primitives call
     int64_t n_passes = 0;           // from_primitives passes enqueued so far (a call is one pass unless a capacity / launch-set retry repeats it)
@@ -513,6 +516,7 @@ extern "C" void lchd_ctx_destroy(lchd_ctx* c) {
     (void)hipFree(c->d_ovf_lists);
     (void)hipFree(c->d_radial_bounds);
     (void)hipFree(c->d_indexed);
+    (void)hipFree(c->d_cross);
     (void)hipFree(c->d_shard);
     (void)hipFree(c->d_bad);
     if (c->shard_stream) (void)hipStreamDestroy(c->shard_stream);
@@ -4283,3 +4287,157 @@ extern "C" int lchd_sensitivity_primitives(lchd_ctx* c, const lchd_config* cfg, 
     return rc;
 }
 extern "C" int64_t lchd_sensitivity_needed_width(lchd_ctx* c) { return c ? c->sens_needed : 0; }
+
+// ------------------------------------------------------------------------------------------------
+// cross-scoring: all anchors of one list against all anchors of another, in row tiles (include/loco_hd_hip.h, "cross-scoring")
+// ------------------------------------------------------------------------------------------------
+// A tile is tile_rows anchors of A against all of B: k_cross_pairs (lchd_cross.hip) writes its pair records into the context's cross
+// block, lchd_from_primitives_dev scores them as it scores any list -- the context is held by this call, the owner re-enters -- and a
+// nearest call reduces the tile's scores with k_nearest_rows.  Side B's environments are built again for every tile (about 0.16 ms per
+// 10^4 anchors, against several ms of sweep for a tile of 5 10^6 pairs): no store outlives a pass.
+extern "C" int lchd_cross_plan(int64_t n_a, int64_t n_b, int64_t budget_bytes, int64_t* tile_rows_out) {
+    if (!tile_rows_out) return fail(LCHD_EVALUE, "null output pointer");
+    *tile_rows_out = 0;
+    if (n_a < 1 || n_b < 1 || budget_bytes < 0)
+        return fail(LCHD_EVALUE, "a cross-scoring plan takes n_a >= 1, n_b >= 1 and a budget >= 0 (got %lld, %lld, %lld)", (long long)n_a,
+                    (long long)n_b, (long long)budget_bytes);
+    const int64_t rows = cross_plan_rows(n_a, n_b, budget_bytes);
+    if (rows < 1) {
+        if (n_b > kCrossMaxTilePairs)
+            return fail(LCHD_EUNSUPPORTED, "one row of %lld anchor pairs exceeds the 2^31 - 1 pairs of a pass: split anchors_b", (long long)n_b);
+        return fail(LCHD_EUNSUPPORTED, "one row of %lld anchor pairs takes %lld bytes of pair records, indices and scores; the budget is %lld",
+                    (long long)n_b, (long long)(n_b * kCrossPairBytes), (long long)budget_bytes);
+    }
+    *tile_rows_out = rows;
+    return LCHD_OK;
+}
+
+struct CrossRequest {
+    lchd_cloud *a, *b;
+    const int64_t *anchors_a, *anchors_b;  // DEVICE
+    int64_t n_a, n_b;
+    int32_t wf;          // -1: none
+    double thr;
+    int64_t tile_rows;   // 0: lchd_cross_plan
+    int32_t k;           // 0: the cross form (the nearest entry points refuse a k < 1 before they get here)
+    double* out;        // DEVICE: cross [n_a][n_b] / nearest scores [n_a][k]
+    int32_t* cols;       // DEVICE: nearest [n_a][k]
+};
+// what needs no context: k and tile_rows against the list lengths
+static int cross_args(int64_t n_a, int64_t n_b, int64_t tile_rows, bool nearest, int32_t k) {
+    if (n_a < 0 || n_b < 0) return fail(LCHD_EVALUE, "negative anchor count");
+    if (nearest && (k < 1 || k > kNearestMaxK || k > n_b))
+        return fail(LCHD_EVALUE, "k = %d is outside 1 .. min(n_b, %d) with n_b = %lld", k, kNearestMaxK, (long long)n_b);
+    if (tile_rows < 0) return fail(LCHD_EVALUE, "tile_rows = %lld is negative (0: planned from the free device memory)", (long long)tile_rows);
+    if (tile_rows > 0 && n_b > 0 && std::min(tile_rows, std::max<int64_t>(n_a, 1)) > kCrossMaxTilePairs / n_b)
+        return fail(LCHD_EVALUE, "tile_rows = %lld with n_b = %lld is a tile of more than 2^31 - 1 pairs", (long long)tile_rows, (long long)n_b);
+    return LCHD_OK;
+}
+static int cross_core(lchd_ctx* c, const CrossRequest& R) {
+    if (!c || !R.a || !R.b) return fail(LCHD_EVALUE, "null argument");
+    if (int rc = cross_args(R.n_a, R.n_b, R.tile_rows, R.k != 0, R.k)) return rc;
+    if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (R.wf < -1 || R.wf >= c->h_cfg.n_wf) return fail(LCHD_EVALUE, "weight-function index %d out of range (-1: none)", R.wf);
+    if (R.n_a == 0 || R.n_b == 0) return LCHD_OK;
+    if (!R.anchors_a || !R.anchors_b || !R.out || (R.k && !R.cols)) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    CTX_GUARD(c);
+    int64_t rows = std::min(R.tile_rows, R.n_a);
+    if (R.tile_rows == 0) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        // (the pass itself takes about as much per pair in its arena, next to the environment stores)
+        if (int rc = lchd_cross_plan(R.n_a, R.n_b, (int64_t)(std::min<size_t>(free_b, (size_t)1 << 62) / 4), &rows)) return rc;
+    }
+    const size_t tile_pairs = (size_t)rows * (size_t)R.n_b;
+    const size_t o_wf = 16 * tile_pairs, o_sc = (o_wf + 4 * tile_pairs + 255) & ~size_t(255);
+    if (int rc = grow_block(c->d_cross, c->cross_cap, o_sc + (R.k ? 8 * tile_pairs : 0))) return rc;
+    int64_t* d_pairs = reinterpret_cast<int64_t*>(c->d_cross);
+    int32_t* d_wf = reinterpret_cast<int32_t*>(c->d_cross + o_wf);
+    double* d_tile = reinterpret_cast<double*>(c->d_cross + o_sc);
+    hipStream_t s = c->stream;
+    for (int64_t r0 = 0; r0 < R.n_a; r0 += rows) {
+        const int64_t tr = std::min(rows, R.n_a - r0);
+        launch_cross_pairs(s, R.anchors_a, R.anchors_b, r0, tr, R.n_b, R.wf, d_pairs, d_wf);
+        HIP_TRY(hipGetLastError());
+        double* scores = R.k ? d_tile : R.out + (size_t)r0 * (size_t)R.n_b;  // (the cross form: the tile's scores go to their place)
+        if (int rc = lchd_from_primitives_dev(c, R.a, R.b, d_pairs, R.wf >= 0 ? d_wf : nullptr, tr * R.n_b, R.thr, scores)) return rc;
+        if (R.k) {
+            launch_nearest_rows(s, d_tile, tr, R.n_b, R.k, R.out + (size_t)r0 * (size_t)R.k, R.cols + (size_t)r0 * (size_t)R.k);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (R.k) HIP_TRY(hipStreamSynchronize(s));  // the call returns with the outputs complete, as the scoring call does
+    c->last_valid = false;  // (the anchors of the last pass live in the cross block, which the next cross call overwrites)
+    return LCHD_OK;
+}
+extern "C" int lchd_cross_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors_a, int64_t n_a,
+                                         const int64_t* d_anchors_b, int64_t n_b, int32_t wf_index, double thr, int64_t tile_rows, double* d_out) {
+    CTX_LOCK(c);
+    return cross_core(c, CrossRequest{a, b, d_anchors_a, d_anchors_b, n_a, n_b, wf_index, thr, tile_rows, 0, d_out, nullptr});
+}
+extern "C" int lchd_nearest_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors_a, int64_t n_a,
+                                           const int64_t* d_anchors_b, int64_t n_b, int32_t wf_index, double thr, int64_t tile_rows, int32_t k,
+                                           double* d_scores, int32_t* d_cols) {
+    CTX_LOCK(c);
+    if (int rc = cross_args(n_a, n_b, tile_rows, true, k)) return rc;
+    return cross_core(c, CrossRequest{a, b, d_anchors_a, d_anchors_b, n_a, n_b, wf_index, thr, tile_rows, k, d_scores, d_cols});
+}
+// The host-array forms: both structures as temporary clouds, the anchors and the outputs in one temporary device block.  k == 0: cross.
+static int cross_host(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a, int64_t n_atoms_a,
+                      const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_atoms_b, const int64_t* anchors_a, int64_t n_a,
+                      const int64_t* anchors_b, int64_t n_b, int32_t wf_index, double thr, int64_t tile_rows, int32_t k, double* out,
+                      int32_t* cols) {
+    CTX_LOCK(c);
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = cross_args(n_a, n_b, tile_rows, k != 0, k)) return rc;
+    if (wf_index < -1 || wf_index >= cfg->n_weight_functions) return fail(LCHD_EVALUE, "weight-function index %d out of range (-1: none)", wf_index);
+    if (n_atoms_a < 0 || n_atoms_b < 0 || n_atoms_a > ((int64_t)1 << 30) || n_atoms_b > ((int64_t)1 << 30))
+        return fail(LCHD_EUNSUPPORTED, "structure size out of range");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    if (n_a == 0 || n_b == 0) return LCHD_OK;
+    if (!anchors_a || !anchors_b || !out || (k && !cols)) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    const size_t width = k ? (size_t)k : (size_t)n_b;
+    if ((size_t)n_a > ((size_t)1 << 40) / width) return fail(LCHD_EUNSUPPORTED, "%lld x %zu outputs exceed 8 TiB: split anchors_a", (long long)n_a, width);
+    HostTemps t(c);
+    const size_t o_b = 8 * (size_t)n_a, o_out = (o_b + 8 * (size_t)n_b + 255) & ~size_t(255), n_out = (size_t)n_a * width,
+                 o_cols = o_out + 8 * n_out;
+    auto run = [&]() -> int {
+        if (int rc = lchd_cloud_create(c, xyz_a, cat_a, tag_a, n_atoms_a, &t.clouds[0])) return rc;
+        if (int rc = lchd_cloud_create(c, xyz_b, cat_b, tag_b, n_atoms_b, &t.clouds[1])) return rc;
+        if (hipMalloc(&t.d_blk, o_cols + (k ? 4 * n_out : 0)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(LCHD_EUNSUPPORTED, "no device memory for the %zu outputs of this call: split anchors_a", n_out);
+        }
+        HIP_TRY(hipMemcpy(t.d_blk, anchors_a, 8 * (size_t)n_a, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(t.d_blk + o_b, anchors_b, 8 * (size_t)n_b, hipMemcpyHostToDevice));
+        const CrossRequest R{t.clouds[0], t.clouds[1], reinterpret_cast<const int64_t*>(t.d_blk), reinterpret_cast<const int64_t*>(t.d_blk + o_b),
+                             n_a, n_b, wf_index, thr, tile_rows, k, reinterpret_cast<double*>(t.d_blk + o_out),
+                             k ? reinterpret_cast<int32_t*>(t.d_blk + o_cols) : nullptr};
+        if (int rc = cross_core(c, R)) return rc;
+        HIP_TRY(hipMemcpy(out, t.d_blk + o_out, 8 * n_out, hipMemcpyDeviceToHost));
+        if (k) HIP_TRY(hipMemcpy(cols, t.d_blk + o_cols, 4 * n_out, hipMemcpyDeviceToHost));
+        return LCHD_OK;
+    };
+    t.rc = run();
+    c->last_valid = false;  // the clouds of this call go away (`t` destroys them on return)
+    c->pend.req.a = c->pend.req.b = nullptr;
+    return t.rc;
+}
+extern "C" int lchd_cross_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
+                                     int64_t n_atoms_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_atoms_b,
+                                     const int64_t* anchors_a, int64_t n_a, const int64_t* anchors_b, int64_t n_b, int32_t wf_index, double thr,
+                                     int64_t tile_rows, double* out) {
+    return cross_host(c, cfg, xyz_a, cat_a, tag_a, n_atoms_a, xyz_b, cat_b, tag_b, n_atoms_b, anchors_a, n_a, anchors_b, n_b, wf_index, thr,
+                      tile_rows, 0, out, nullptr);
+}
+extern "C" int lchd_nearest_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
+                                       int64_t n_atoms_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_atoms_b,
+                                       const int64_t* anchors_a, int64_t n_a, const int64_t* anchors_b, int64_t n_b, int32_t wf_index, double thr,
+                                       int64_t tile_rows, int32_t k, double* scores, int32_t* cols) {
+    if (int rc = cross_args(n_a, n_b, tile_rows, true, k)) return rc;
+    return cross_host(c, cfg, xyz_a, cat_a, tag_a, n_atoms_a, xyz_b, cat_b, tag_b, n_atoms_b, anchors_a, n_a, anchors_b, n_b, wf_index, thr,
+                      tile_rows, k, scores, cols);
+}

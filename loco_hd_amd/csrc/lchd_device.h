@@ -485,6 +485,13 @@ struct SensitivityArgs {
 };
 bool launch_sensitivity(hipStream_t s, const SensitivityArgs& a);  // false: nothing launched (more than kSensitivityMaxCategories categories)
 void init_sensitivity_kernels();  // per device, as init_radial_kernels
+// Cross-scoring (lchd_cross.hip): the pair records of one row tile -- anchors_a[row0 .. row0 + rows) against all n_b anchors of B, pair
+// p = i * n_b + j -- written on the device in the [P][2] int64 form the thresholded pass reads, with the constant wf index when wf >= 0
+// (wf_out is not touched otherwise); and the reduction of a tile's [rows][n_b] scores to the k smallest (score, column) per row, ascending.
+// rows * n_b <= 2^31 - 1; 1 <= k <= min(n_b, kNearestMaxK).
+void launch_cross_pairs(hipStream_t s, const int64_t* anchors_a, const int64_t* anchors_b, int64_t row0, int64_t rows, int64_t n_b, int32_t wf,
+                        int64_t* pairs, int32_t* wf_out);
+void launch_nearest_rows(hipStream_t s, const double* scores, int64_t rows, int64_t n_b, int32_t k, double* out_scores, int32_t* out_cols);
 void launch_mark_overflow(hipStream_t s, const uint32_t* list_a, uint32_t na, const uint32_t* list_b, uint32_t nb, uint32_t* bits_a, uint32_t* bits_b);
 void launch_count_overflow(hipStream_t s, const OverflowSelect& a, unsigned long long* total);
 void launch_write_overflow(hipStream_t s, const OverflowSelect& a);

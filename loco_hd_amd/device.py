@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .api import LoCoHD, Sensitivity, dense_cells, periodic_boxes, periodic_cells
+from .api import LoCoHD, Nearest, Sensitivity, dense_cells, periodic_boxes, periodic_cells
 
 
 def last_sweep_of(ctx):
@@ -382,6 +382,49 @@ class DeviceSession:
             if not fixed and 0 < need < k:  # rows as wide as the longest environment, as the host call returns them
                 res = Sensitivity(*[t[:, :need].contiguous() if t.dim() == 2 else t for t in res])
             return res
+
+    def _cross_head(self, cloud_a, cloud_b, anchors_a, anchors_b, threshold_distance, wf_index, tile_rows):
+        torch = self.torch
+        for t in (anchors_a, anchors_b):
+            assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 1
+        if int(tile_rows) < 0:
+            raise ValueError(f"tile_rows = {int(tile_rows)} is negative (0: planned from the free device memory)")
+        return (self._ctx, cloud_a, cloud_b, C.c_void_p(anchors_a.data_ptr()), anchors_a.shape[0], C.c_void_p(anchors_b.data_ptr()),
+                anchors_b.shape[0], -1 if wf_index is None else int(wf_index), float(threshold_distance), int(tile_rows))
+
+    def cross(self, cloud_a, cloud_b, anchors_a, anchors_b, threshold_distance: float, out=None, wf_index=None, *, tile_rows=0):
+        """Cross-scoring (LoCoHD.cross_from_primitives) of two uploaded clouds of any kind (structures, batches, frames buffers, image
+        clouds): every anchor of anchors_a against every anchor of anchors_b, torch int64 CUDA tensors [Na] and [Nb] of global atom
+        indices (repeats allowed).  wf_index: ONE weight-function index for the whole call (an int) or None.  Returns (or fills) a torch
+        float64 CUDA tensor [Na][Nb]; no pair list is built (lchd_cross_primitives_dev).  tile_rows: rows of A per pass, 0 = planned
+        from the free device memory."""
+        torch = self.torch
+        head = self._cross_head(cloud_a, cloud_b, anchors_a, anchors_b, threshold_distance, wf_index, tile_rows)
+        na, nb = anchors_a.shape[0], anchors_b.shape[0]
+        if out is None:
+            out = torch.empty((na, nb), dtype=torch.float64, device=anchors_a.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= na * nb
+        N.check(N.lib().lchd_cross_primitives_dev(*head, C.c_void_p(out.data_ptr())))
+        return out
+
+    def nearest(self, cloud_a, cloud_b, anchors_a, anchors_b, threshold_distance: float, k: int, out=None, wf_index=None, *, tile_rows=0):
+        """The k best matches of every anchor of anchors_a among anchors_b (LoCoHD.nearest_from_primitives): a `Nearest` of torch CUDA
+        tensors, scores [Na][k] f64 and cols [Na][k] i32 (positions in anchors_b), each row ascending in (score, j); `out`: such a
+        pair of tensors, filled and returned.  With a batch as cloud_b this searches a set of structures in one call
+        (lchd_nearest_primitives_dev).  Other arguments as `cross`."""
+        torch = self.torch
+        head = self._cross_head(cloud_a, cloud_b, anchors_a, anchors_b, threshold_distance, wf_index, tile_rows)
+        na, nb, k = anchors_a.shape[0], anchors_b.shape[0], int(k)
+        if not 1 <= k <= min(nb, 64):
+            raise ValueError(f"k = {k} is outside 1 .. min(Nb, 64) with Nb = {nb}")
+        if out is None:
+            out = Nearest(torch.empty((na, k), dtype=torch.float64, device=anchors_a.device),
+                          torch.empty((na, k), dtype=torch.int32, device=anchors_a.device))
+        scores, cols = out
+        assert scores.is_cuda and scores.dtype == torch.float64 and scores.is_contiguous() and tuple(scores.shape) == (na, k)
+        assert cols.is_cuda and cols.dtype == torch.int32 and cols.is_contiguous() and tuple(cols.shape) == (na, k)
+        N.check(N.lib().lchd_nearest_primitives_dev(*head, k, C.c_void_p(scores.data_ptr()), C.c_void_p(cols.data_ptr())))
+        return Nearest(scores, cols)
 
     def gradient(self, cloud_a, cloud_b, anchors, threshold_distance: float, xyz_a, xyz_b, pair_weights=None, wf_index=None):
         """`(scores, grad_a[Na, 3], grad_b[Nb, 3])` with grad = sum_p v_p dS_p/dx (LoCoHD.gradient_from_primitives) as torch CUDA tensors.
