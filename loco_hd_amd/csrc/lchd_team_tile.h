@@ -382,6 +382,33 @@ struct TeamTile {
                     exA[0] += takeA ? inc8 : 0ull;
                     exB[0] += takeA ? 0ull : inc8;
                 } else {
+                if constexpr (NW == 2 && NH == 1) {
+                    // 9 .. 16 slots, two count words per side.  Measured in place (profiles/r20/issue_rates_patterns.json), an instruction of
+                    // this bookkeeping costs about the same whatever its class, so what counts is how many there are:
+                    //  - the count byte is ONE v_perm_b32 over the side's selected word, selector ct % 8 (its upper three bytes repeat
+                    //    byte 0: the add below reads BYTE_0, as it did behind the 64-bit shift) -- no 64-bit shift and no aligned register
+                    //    pair; up to 12 slots the second word's upper half is empty and its categories sit in bytes 0 .. 3, so only the
+                    //    LOWER half of the word is selected (16 slots: both halves, as before);
+                    //  - the word select is  ct >= 8  (a category is below CMAX <= 16), one compare, not  (ct & ~7) == 8;
+                    //  - the chunk-local 4-bit fields are kept for side A and for BOTH sides together (dT, in dB[0]): every event adds
+                    //    its field to dT unconditionally and to dA under the merge mask; B's field is the difference (a field of dT
+                    //    is never smaller than dA's: no borrow) -- one subtraction instead of a second 64-bit select.
+                    const bool hiw = uct >= (unsigned)FPW;
+                    const uint32_t sel = uct % FPW;
+                    const uint32_t loA = hiw ? (uint32_t)exA[1] : (uint32_t)exA[0], loB = hiw ? (uint32_t)exB[1] : (uint32_t)exB[0];
+                    uint32_t hiA = (uint32_t)(exA[0] >> 32), hiB = (uint32_t)(exB[0] >> 32);
+                    if constexpr (CMAX > 12) {
+                        hiA = hiw ? (uint32_t)(exA[1] >> 32) : hiA;
+                        hiB = hiw ? (uint32_t)(exB[1] >> 32) : hiB;
+                    }
+                    const uint32_t bA = __builtin_amdgcn_perm(hiA, loA, sel), bB = __builtin_amdgcn_perm(hiB, loB, sel);
+                    const int nA = (int)((dA[0] >> sh4) & (H4)15), nT = (int)((dB[0] >> sh4) & (H4)15);
+                    cntA_ = (int)(bA & 0xFFu) + nA;
+                    cntB_ = (int)(bB & 0xFFu) + nT - nA;
+                    const H4 inc4 = (H4)1 << sh4;
+                    dB[0] += inc4;
+                    dA[0] += takeA ? inc4 : (H4)0;
+                } else {
                 uint64_t wA = exA[0], wB = exB[0];
 #pragma unroll
                 for (int k = 1; k < NW; ++k) {
@@ -403,6 +430,7 @@ struct TeamTile {
                 } else {
                     dA[0] += takeA ? inc4 : (H4)0;
                     dB[0] += takeA ? (H4)0 : inc4;
+                }
                 }
                 }
                 if constexpr (KSM) {
@@ -468,7 +496,8 @@ struct TeamTile {
                             uint64_t wA = exA[0], wB = exB[0];
 #pragma unroll
                             for (int k = 1; k < NW; ++k) { wA = (c / FPW == k) ? exA[k] : wA; wB = (c / FPW == k) ? exB[k] : wB; }
-                            const H4 qA = (c & 16) ? dA[NH - 1] : dA[0], qB = (c & 16) ? dB[NH - 1] : dB[0];
+                            // (two count words per side: dB[0] holds the fields of both sides together, see above)
+                            const H4 qA = (c & 16) ? dA[NH - 1] : dA[0], qB = (NW == 2 && NH == 1) ? (H4)(dB[0] - dA[0]) : ((c & 16) ? dB[NH - 1] : dB[0]);
                             const int ca = (int)((wA >> ((c % FPW) * FB)) & 0xFFull) + (int)((qA >> ((c & 15) * 4)) & (H4)15);
                             const int cb = (int)((wB >> ((c % FPW) * FB)) & 0xFFull) + (int)((qB >> ((c & 15) * 4)) & (H4)15);
                             const double dd = t_sqrt[ca] * ra - t_sqrt[cb] * rb;

@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
 """Instruction-class histogram of a kernel's hot loop + its class-weighted VALU issue ceiling.
 
-    python3 profiles/isa_histogram.py <file.hip> '<kernel regex on the demangled name>' profiles/r04/issue_rates.json [--loop N] > out.json
+    python3 profiles/isa_histogram.py <file.hip> '<kernel regex on the demangled name>' profiles/r04/issue_rates.json [--loop N]
+                                      [--patterns profiles/r20/issue_rates_patterns.json] > out.json
 
 The kernel is compiled to gfx950 assembly with the Makefile's flags (`hipcc -S --cuda-device-only`: the very instruction
 stream of the code object in libloco_hd_hip.so -- the same compiler, flags and source; no GPU needed).  Loops are the
 backward branches of the function; the HOT loop is the smallest loop that evaluates sqrt(H^2) (the per-event loop of the sweep kernels;
 kernels without one: the innermost loop with the most instructions), override with --loop.  Every vector instruction is put into one of the classes that
 profiles/ubench/issue_rates.hip measured; the loop's average cost per vector instruction (ns per instruction per SIMD at 4
-resident waves) is what bench.py multiplies the measured instruction count of a launch with (roofline.valu_ceiling_frac)."""
+resident waves) is what bench.py multiplies the measured instruction count of a launch with (roofline.valu_ceiling_frac).
+
+`weighted_ns` of a loop is the sum over its vector instructions of the class cost (4 resident waves): the model's time of one
+trip per SIMD.  With --patterns, the classes that `issue_rates --patterns` measured IN PLACE (between the event loop's own
+neighbours) take that cost instead of the isolated one: the two v_cndmask_b32 encodings, each (nine selects + nine neighbours
+- the nine neighbours alone) / 9."""
 import collections
 import json
 import re
@@ -61,8 +67,20 @@ def classify(mn: str) -> str:
     return "other_valu"
 
 
+IN_PLACE = {}  # class -> ns per instruction at 4 waves, from --patterns
+
+
+def load_patterns(path: str) -> None:
+    p = json.load(open(path))["classes"]
+    base = p["pat_neighbours_9"]["w4_ns_per_group_per_simd"]
+    IN_PLACE["cndmask_e32_in_mix"] = (p["pat_sel9_vcc"]["w4_ns_per_group_per_simd"] - base) / 9
+    IN_PLACE["cndmask_e64_sgpr"] = (p["pat_sel9_sgpr"]["w4_ns_per_group_per_simd"] - base) / 9
+
+
 def cost_ns(cls: str, rates: dict, w: str = "w4") -> float:
     c = rates["classes"]
+    if w == "w4" and cls in IN_PLACE:
+        return IN_PLACE[cls]
     if cls == "cndmask_e32_in_mix":
         # a select behind a compare: (cmp + 2 cndmask + add) / 4 = mix_cmp_2cndmask_e32_add  ->  solve for the cndmask
         mix = c["mix_cmp_2cndmask_e32_add"][w]["ns_per_instr_per_simd"]
@@ -74,8 +92,14 @@ def main():
     src, kernel_rx, rates_path = sys.argv[1:4]
     loop_pick = int(sys.argv[sys.argv.index("--loop") + 1]) if "--loop" in sys.argv else None
     rates = json.load(open(rates_path))
-    import hashlib, os
-    cache = f"/tmp/isa_{hashlib.sha1(open(src, 'rb').read()).hexdigest()[:16]}.s"  # (the kernels file takes 90 s to compile)
+    if "--patterns" in sys.argv:
+        load_patterns(sys.argv[sys.argv.index("--patterns") + 1])
+    import glob, hashlib, os
+    # (the kernels file takes 90 s to compile: cached by the contents of the file and of the headers next to it)
+    digest = hashlib.sha1(open(src, "rb").read())
+    for h in sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(src)), "*.h"))):
+        digest.update(open(h, "rb").read())
+    cache = f"/tmp/isa_{digest.hexdigest()[:16]}.s"
     if not os.path.exists(cache):
         subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, src, "-o", cache], check=True)
     asm = open(cache).read()
@@ -153,6 +177,9 @@ def main():
         for w in ("w4", "w8"):
             tot = sum(v * cost_ns(k, rates, w) for k, v in valu.items())
             out[f"avg_ns_per_valu_instr_{w}"] = tot / max(n_valu, 1)
+        out["weighted_ns"] = sum(v * cost_ns(k, rates) for k, v in valu.items())
+        out["class_table"] = {k: {"count": v, "ns_each": round(cost_ns(k, rates), 4), "ns": round(v * cost_ns(k, rates), 3)}
+                              for k, v in sorted(valu.items(), key=lambda kv: -kv[1] * cost_ns(kv[0], rates))}
         fast = sum(v for k, v in valu.items() if cost_ns(k, rates) < 1.45)
         out["share_of_2_cycle_class"] = fast / max(n_valu, 1)
         if other:

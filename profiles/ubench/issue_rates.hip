@@ -3,6 +3,7 @@
 // per loop iteration, so neither a dependency chain nor the loop overhead (two scalar instructions per 64) shows.
 //
 //   hipcc -O3 --offload-arch=gfx950 profiles/ubench/issue_rates.hip -o /tmp/issue_rates && /tmp/issue_rates > profiles/r04/issue_rates.json
+//   /tmp/issue_rates --patterns > profiles/r20/issue_rates_patterns.json   (the event-loop patterns of the team sweep, see body<40..>)
 //
 // Output (JSON): per class and occupancy, ns per instruction per SIMD = kernel wall time / (instructions per wave x waves per SIMD),
 // the same in shader cycles (s_memtime deltas / instructions per wave / waves per SIMD) and the clock the chip held
@@ -63,14 +64,47 @@ __device__ __forceinline__ void body(unsigned& a0, unsigned& a1, unsigned& a2, u
     if constexpr (K == 37) { REP16(G4("v_cmp_lt_u32_e32 vcc, %0, %1", "v_cmp_gt_u32_e32 vcc, %1, %2", "v_cmp_eq_u32_e32 vcc, %2, %3", "v_cmp_ne_u32_e32 vcc, %3, %0");) }
     if constexpr (K == 38) { REP16(G4("v_add_u32_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0", "v_add_u32_sdwa %1, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1", "v_add_u32_sdwa %2, %2, %3 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2", "v_add_u32_sdwa %3, %3, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1");) }
     if constexpr (K == 39) { REP16(G4("v_cmp_lt_u32 s[10:11], %0, %1", "v_cndmask_b32_e64 %1, %1, %2, s[10:11]", "v_cndmask_b32_e64 %2, %2, %3, s[10:11]", "v_add_u32 %3, %3, %0");) }
+    // PATTERNS of the team sweep's event loop (--patterns; kGroup[K] instructions per group): the loop's selects and count
+    // extraction in place, between the 32-bit shifts, adds and LDS address arithmetic that surround them there -- not isolated
+    // instructions.  NB = the nine neighbours alone; k selects are spread between them.  The mask is written once, outside the timed loop.
+#define NB3a "v_lshlrev_b32 %0, 3, %1\n v_add_u32 %1, %16, %0\n v_lshlrev_b32 %2, 2, %3\n"
+#define NB3b "v_and_b32 %3, 15, %2\n v_add_u32 %0, %0, %3\n v_lshrrev_b32 %1, 3, %1\n"
+#define NB3c "v_add_u32 %2, %16, %1\n v_lshlrev_b32 %3, 3, %0\n v_add_u32 %1, %1, %2\n"
+#define SELV(d, a, b) "v_cndmask_b32_e32 " d ", " a ", " b ", vcc\n"
+#define SELS(d, a, b) "v_cndmask_b32_e64 " d ", " a ", " b ", s[10:11]\n"
+    if constexpr (K == 40) { REP16(G4(NB3a, NB3b, NB3c, "");) }
+    if constexpr (K == 41) { REP16(G4(NB3a SELV("%3", "%0", "%1"), NB3b, NB3c SELV("%0", "%2", "%3"), "");) }
+    if constexpr (K == 42) { REP16(G4(NB3a SELS("%3", "%0", "%1"), NB3b, NB3c SELS("%0", "%2", "%3"), "");) }
+    if constexpr (K == 43) { REP16(G4(NB3a SELV("%3", "%0", "%1") SELV("%0", "%1", "%2"), NB3b SELV("%2", "%3", "%0"), NB3c SELV("%0", "%2", "%3"), "");) }
+    if constexpr (K == 44) { REP16(G4(NB3a SELS("%3", "%0", "%1") SELS("%0", "%1", "%2"), NB3b SELS("%2", "%3", "%0"), NB3c SELS("%0", "%2", "%3"), "");) }
+    if constexpr (K == 45) { REP16(G4(NB3a SELV("%3", "%0", "%1") SELV("%0", "%1", "%2") SELV("%2", "%0", "%3"), NB3b SELV("%2", "%3", "%0") SELV("%1", "%2", "%3") SELV("%3", "%1", "%0"),
+                                      NB3c SELV("%0", "%2", "%3") SELV("%2", "%1", "%0") SELV("%3", "%2", "%1"), "");) }
+    if constexpr (K == 46) { REP16(G4(NB3a SELS("%3", "%0", "%1") SELS("%0", "%1", "%2") SELS("%2", "%0", "%3"), NB3b SELS("%2", "%3", "%0") SELS("%1", "%2", "%3") SELS("%3", "%1", "%0"),
+                                      NB3c SELS("%0", "%2", "%3") SELS("%2", "%1", "%0") SELS("%3", "%2", "%1"), "");) }
+    // one count of a category, between three neighbours: a 64-bit word select + 64-bit shift + mask (4 + 3) against a 32-bit word
+    // select + v_bfe_u32 / v_perm_b32 byte pick (2 + 3); %2 holds the shift / the selector
+    if constexpr (K == 47) { REP16(G4(NB3a, "v_cndmask_b32_e32 %0, %1, %3, vcc\n v_cndmask_b32_e32 %1, %3, %0, vcc", "v_lshrrev_b64 %7, %2, %4", "v_and_b32 %3, 0xff, %0");) }
+    if constexpr (K == 48) { REP16(G4(NB3a, "v_cndmask_b32_e32 %0, %1, %3, vcc", "v_bfe_u32 %3, %0, %2, 8", "");) }
+    if constexpr (K == 49) { REP16(G4(NB3a, "v_cndmask_b32_e32 %0, %1, %3, vcc", "v_perm_b32 %3, %0, %1, %2", "");) }
+    // a conditional add of 1 << sh, between three neighbours: 64-bit (shift, two selects, add: 4 + 3) against 32-bit (3 + 3),
+    // the selects on an SGPR pair and on VCC
+    if constexpr (K == 50) { REP16(G4(NB3a, "v_lshlrev_b64 %4, %2, 1", "v_cndmask_b32_e64 %0, 0, %3, s[10:11]\n v_cndmask_b32_e64 %1, 0, %0, s[10:11]", "v_lshl_add_u64 %6, %5, 0, %6");) }
+    if constexpr (K == 51) { REP16(G4(NB3a, "v_lshlrev_b64 %4, %2, 1", "v_cndmask_b32_e32 %0, 0, %3, vcc\n v_cndmask_b32_e32 %1, 0, %0, vcc", "v_lshl_add_u64 %6, %5, 0, %6");) }
+    if constexpr (K == 52) { REP16(G4(NB3a, "v_lshlrev_b32 %3, %2, 1", "v_cndmask_b32_e64 %0, 0, %3, s[10:11]", "v_add_u32 %1, %1, %0");) }
+    if constexpr (K == 53) { REP16(G4(NB3a, "v_lshlrev_b32 %3, %2, 1", "v_cndmask_b32_e32 %0, 0, %3, vcc", "v_add_u32 %1, %1, %0");) }
 }
-constexpr int kClasses = 40;
+constexpr int kBaseClasses = 40, kClasses = 54;
+// vector instructions of one group of the pattern classes (every class before them: four)
+constexpr int kGroup[kClasses - kBaseClasses] = {9, 11, 11, 13, 13, 18, 18, 7, 5, 5, 7, 7, 6, 6};
 static const char* kNames[kClasses] = {
     "b32_add", "b32_logic_shift", "b32_three_operand", "cndmask_e32_vcc", "cndmask_e64_sgpr", "cmp_u32", "b64_shift", "cmp_u64", "lshl_add_u64",
     "add_co_addc_pair_half", "f64_add", "f64_mul", "f64_fma", "f64_rsq", "f64_sqrt_rcp", "f32_alu", "cvt_to_f64", "cvt_from_f64", "mov_b32", "mov_b64",
     "dpp_add_u32", "readlane", "mul_u32", "mad_u64_u32", "ds_read_b64", "ds_read_u8", "ds_read_b32", "ds_write_mixed", "f64_minmax", "cmp_f64",
     "f64_ldexp_rndne", "s_nop", "mix_2cndmask_e32_2add", "mix_cmp_2cndmask_e32_add", "mix_cndmask_e32_add_alternating",
-    "mix_cmp64_2cndmask_e32_shift64", "b32_add_vop3_encoding", "cmp_u32_e32_vcc", "b32_add_sdwa", "mix_cmp_2cndmask_e64_add"};
+    "mix_cmp64_2cndmask_e32_shift64", "b32_add_vop3_encoding", "cmp_u32_e32_vcc", "b32_add_sdwa", "mix_cmp_2cndmask_e64_add",
+    "pat_neighbours_9", "pat_sel2_vcc", "pat_sel2_sgpr", "pat_sel4_vcc", "pat_sel4_sgpr", "pat_sel9_vcc", "pat_sel9_sgpr",
+    "pat_count_word64_shift64_mask", "pat_count_word32_bfe", "pat_count_word32_perm", "pat_condadd64_sgpr", "pat_condadd64_vcc",
+    "pat_condadd32_sgpr", "pat_condadd32_vcc"};
 
 template <int K>
 __global__ __launch_bounds__(256) void bench(unsigned long long* out, int iters, double* sink, const double* src) {
@@ -83,6 +117,8 @@ __global__ __launch_bounds__(256) void bench(unsigned long long* out, int iters,
     unsigned a0 = tid, a1 = tid * 3 + 1, a2 = tid ^ 0x55, a3 = tid + 9;
     float f0 = tid * 0.5f + 1.0f, f1 = tid + 2.0f, f2 = 1.0001f, f3 = 0.9999f;
     const unsigned la = (unsigned)(size_t)lds + (unsigned)(tid & 63) * 32u;  // LDS byte address (low 32 bits of the generic pointer's offset)
+    // the lane masks the pattern classes select on: half the lanes each, written once, outside the timed loop
+    if constexpr (K >= 40) asm volatile("v_cmp_gt_u32 vcc, %0, %1\n v_cmp_gt_u32 s[10:11], %0, %1\n s_nop 4" : : "v"(a0 & 1u), "v"(0u) : "vcc", "s10", "s11");
     const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
     for (int it = 0; it < iters; ++it) body<K>(a0, a1, a2, a3, u0, u1, u2, u3, d0, d1, d2, d3, f0, f1, f2, f3, la);
     const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
@@ -109,25 +145,28 @@ void run(int blocks_per_cu, unsigned long long* d_out, double* d_sink, double* d
     double tick = 0, real = 0;
     for (size_t i = 0; i < h.size(); i += 2) { tick += (double)h[i]; real += (double)h[i + 1]; }
     tick /= h.size() / 2; real /= h.size() / 2;
-    const double instr = (double)iters * 64;  // per wave
+    const double instr = (double)iters * 16 * (K < kBaseClasses ? 4 : kGroup[K < kBaseClasses ? 0 : K - kBaseClasses]);  // per wave
     rows.push_back({kNames[K], blocks_per_cu, ms * 1e6 / (instr * blocks_per_cu), tick / (instr * blocks_per_cu), tick / real * 0.1});
     hipEventDestroy(e0); hipEventDestroy(e1);
 }
-template <int K> void run_all(unsigned long long* o, double* s, double* src) {
+template <int K, int END> void run_all(unsigned long long* o, double* s, double* src) {
     for (int w : {1, 2, 4, 8}) run<K>(w, o, s, src);
-    if constexpr (K + 1 < kClasses) run_all<K + 1>(o, s, src);
+    if constexpr (K + 1 < END) run_all<K + 1, END>(o, s, src);
 }
-int main() {
+int main(int argc, char** argv) {
+    const bool patterns = argc > 1 && std::string(argv[1]) == "--patterns";  // the event-loop patterns alone (profiles/r20/issue_rates_patterns.json)
     unsigned long long* d_out; double *d_sink, *d_src;
     hipMalloc(&d_out, sizeof(unsigned long long) * 256 * 8 * 8);
     hipMalloc(&d_sink, sizeof(double) * 256 * 8 * 256);
     hipMalloc(&d_src, sizeof(double) * 4096);
     std::vector<double> h(4096); for (int i = 0; i < 4096; ++i) h[i] = 0.5 + i * 1e-3;
     hipMemcpy(d_src, h.data(), sizeof(double) * 4096, hipMemcpyHostToDevice);
-    run_all<0>(d_out, d_sink, d_src);
+    if (patterns) run_all<kBaseClasses, kClasses>(d_out, d_sink, d_src);
+    else run_all<0, kBaseClasses>(d_out, d_sink, d_src);
     printf("{\n \"device\": \"gfx950 (MI355X)\", \"method\": \"4 independent streams x 16 per loop iteration, 2000 iterations, 256 x W workgroups of 256 threads (one wavefront per SIMD and workgroup); ns = kernel wall time / (instructions per wave x W)\",\n \"classes\": {\n");
     for (size_t i = 0; i < rows.size(); i += 4) {
         printf("  \"%s\": {", rows[i].name.c_str());
+        if (patterns) printf("\"instructions_per_group\": %d, \"w4_ns_per_group_per_simd\": %.4f, ", kGroup[i / 4], rows[i + 2].ns * kGroup[i / 4]);
         for (int k = 0; k < 4; ++k)
             printf("\"w%d\": {\"ns_per_instr_per_simd\": %.4f, \"cycles_per_instr_per_simd\": %.3f, \"clock_ghz\": %.3f}%s", rows[i + k].w, rows[i + k].ns,
                    rows[i + k].cyc, rows[i + k].ghz, k < 3 ? ", " : "");
