@@ -522,7 +522,8 @@ int lchd_attribution_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *
  * Every environment is returned as a list sorted ascending by (distance bits, atom index) with the anchor in slot 0 -- one defined
  * order among ties.  Per pair p and side, with K = width the caller's row width:
  *   count[p]     members, the anchor included (0: an unusable pair)
- *   idx[p][K]    atom index of every member (i32), padded with -1
+ *   idx[p][K]    atom index of every member (i32), padded with -1; for a batch the GLOBAL index (the position in the concatenated arrays,
+ *                as the anchors are given), not the index within the member's structure
  *   dist[p][K]   its distance, padded with 0
  *   g[p][K]      dS/dd; 0 in slot 0 and in the padding.  A member at d == 0 other than the anchor has a g but no direction.
  *   scores[p]    the pair's score from the same walk (the scoring call of the same inputs, to rounding)

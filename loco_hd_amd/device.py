@@ -344,7 +344,8 @@ class DeviceSession:
     def sensitivity(self, cloud_a, cloud_b, anchors, threshold_distance: float, out=None, wf_index=None, *, width=None):
         """Neighbour sensitivities (LoCoHD.sensitivity_from_primitives) of anchor pairs of two uploaded structures or batches (no image
         clouds).  anchors: torch int64 CUDA tensor [P][2]; wf_index: torch int32 CUDA tensor [P] or None.  Returns a `Sensitivity` of
-        torch CUDA tensors: scores [P] f64, count_a / count_b [P] i32, idx_a / idx_b [P][K] i32 (padded with -1), dist_a / dist_b /
+        torch CUDA tensors: scores [P] f64, count_a / count_b [P] i32, idx_a / idx_b [P][K] i32 (padded with -1; for a batch the global
+        atom indices of `upload_batch`, as the anchors are), dist_a / dist_b /
         g_a / g_b [P][K] f64 (padded with 0).  K: `width`, or the width of `out` (a `Sensitivity` of such tensors, filled and
         returned; ValueError if an environment is longer), or -- with neither -- the longest environment, found by repeating a call
         whose first guess of 128 was too narrow (lchd_sensitivity_primitives_dev).  The derivative ignores points entering or leaving at
