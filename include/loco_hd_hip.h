@@ -731,9 +731,65 @@ int lchd_plan_sweep(const lchd_sweep_query *query, lchd_sweep_plan *plan_out);
  * (from_coords, from_dmxs, from_anchors, the ensembles).  One difference: the record is host data, so a host-pointer
  * lchd_from_primitives / lchd_group_from_primitives call (after which the grid is no longer reported) keeps it. */
 int lchd_ctx_last_sweep(lchd_ctx *ctx, lchd_sweep_plan *plan_out, int64_t stats_out[4], int32_t *rule_out, int32_t *repeated_out);
+/* ---- which kernels sort the dense rows of from_coords / from_dmxs / the dense ensembles ----
+ * One of three paths takes a call: the fused sort + sweep kernel (k_dense_fused: nothing but the scores is written), the register-resident
+ * row sort of both sides in one launch (k_env_rows2) followed by the sweep, or the three-pass row sort (k_env_rows), one launch per side,
+ * followed by the sweep.  Which one, and which instantiation of it, is a pure function of the query below. */
+typedef enum { LCHD_DENSE_NONE = 0, LCHD_DENSE_FUSED = 1, LCHD_DENSE_ROWS2 = 2, LCHD_DENSE_ROWS = 3 } lchd_dense_path;
+/* The tuning hooks the choice depends on (lchd_dense_query::hooks): LCHD_OLD_ROWS, LCHD_NO_DENSE_FUSED (deterministic mode sets the latter). */
+typedef enum { LCHD_DENSE_HOOK_OLD_ROWS = 1, LCHD_DENSE_HOOK_NO_FUSED = 2 } lchd_dense_hook;
+typedef struct lchd_dense_query {
+    int64_t cols_a, cols_b;    /* points per row of either side (ragged rows: of the longest row) */
+    int32_t n_categories;
+    int32_t hellinger2;        /* the distance is Hellinger with exponent 2 */
+    int32_t unit_weights;      /* every category weight is 1 */
+    int32_t cat16;             /* 16-bit category ids in the environment store (the library: more than 255 categories) */
+    int32_t given_rows;        /* the rows are given (from_dmxs, minimum-image rows), not computed from coordinates inside the kernel */
+    int32_t ragged;            /* every row carries its own length (lchd_from_dmxs_ragged) */
+    uint32_t hooks;            /* lchd_dense_hook bits */
+    int32_t attempt;           /* 0, or 1: the repeat of a call in which a row defeated the fused kernel or the segmented sort */
+    int32_t single_attempt;    /* the caller cannot repeat (the dense ensembles): no kernel that may give up on a row */
+    int32_t reserved;          /* 0 */
+} lchd_dense_query;
+/* One side of the LCHD_DENSE_ROWS path: k_env_rows<nt, globalkv, 8- or 16-bit ids>. */
+typedef struct lchd_dense_rows_side {
+    int32_t nt;                /* threads per row: 64, 256 or 1024 */
+    int32_t globalkv;          /* keys sorted in place in the environment store (only the bucket histogram in LDS) */
+    int32_t cat_bytes;         /* 1 or 2 bytes per category id */
+    int32_t buckets;           /* distance buckets of the sort: 2048, 16384 or 32768 */
+    int32_t cap;               /* points per environment slot (a power of two >= the row) */
+} lchd_dense_rows_side;
+typedef struct lchd_dense_plan {
+    int32_t path;              /* lchd_dense_path; LCHD_DENSE_NONE with unsupported == 1 */
+    int32_t unsupported;       /* no kernel takes such rows (LCHD_EUNSUPPORTED / LCHD_EPANIC from the scoring calls) */
+    /* LCHD_DENSE_FUSED: k_dense_fused<fused_slots, fused_dmx>, scr_segs distance segments of scratch per workgroup; else 0 */
+    int32_t fused_slots;       /* 8, 12 or 16 category slots */
+    int32_t fused_dmx;         /* the given-rows form */
+    int32_t scr_segs;
+    /* LCHD_DENSE_ROWS2: k_env_rows2<nt, ept, seg>, key array of n2 points; else 0 */
+    int32_t nt, ept, seg, n2;
+    /* LCHD_DENSE_ROWS: per side; else 0 */
+    lchd_dense_rows_side rows[2];
+} lchd_dense_plan;
+/* The plan of a dense call, as a pure function (no context, no device); the launchers take their instantiation from it and decide
+ * nothing themselves.  Returns LCHD_OK (also for an unsupported query: see lchd_dense_plan::unsupported), or LCHD_EVALUE (null
+ * argument, n_categories < 1, attempt outside 0 .. 1, unknown hook bits). */
+int lchd_plan_dense(const lchd_dense_query *query, lchd_dense_plan *plan_out);
+/* What the most recent from_coords / from_dmxs / dense-ensemble call of the context ran. */
+typedef struct lchd_dense_record {
+    lchd_dense_plan plan;      /* the plan of the attempt whose scores stand */
+    int32_t attempts;          /* 1, or 2: a row defeated the first attempt's kernel (ST_ROW_RETRY) and the call was repeated */
+    int32_t canon;             /* the tie-canonicalisation kernel ran behind the row sort (deterministic mode) */
+    int64_t n_bitonic;         /* rows of that attempt whose sort met a bucket of more than 64 points and took the bitonic network
+                                  (counted on the device, one atomic per such row; an ensemble: over all its row-sort launches) */
+} lchd_dense_record;
+/* Returns 0, or -1 (null argument; no dense call yet; the most recent dense call failed).  Calls of other entry points leave the
+ * record alone. */
+int lchd_ctx_last_dense(lchd_ctx *ctx, lchd_dense_record *record_out);
 /* 1 if the most recent from_coords / from_dmxs call of the context ran the fused sort + sweep kernel (one launch per
  * call, nothing but the scores written: Hellinger-2, unit category weights, at most 16 categories, rows of 1 025 .. 20 480
- * points), 0 if it ran the row sort followed by the sweep (src/locohd.rs:410-476 either way). */
+ * points), 0 if it ran the row sort followed by the sweep (src/locohd.rs:410-476 either way).  Reads the record of
+ * lchd_ctx_last_dense: plan.path == LCHD_DENSE_FUSED. */
 int32_t lchd_ctx_last_dense_fused(lchd_ctx *ctx);
 /* Determinism switch.  The reference is ONE code path (src/locohd.rs:61-226): the same anchor pair gives the same bits whatever
  * else the call holds.  By default this library picks among several sweep kernels per call -- from the call's size, from what the

@@ -68,6 +68,41 @@ class SweepPlanC(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class DenseQueryC(C.Structure):
+    """lchd_dense_query: what the choice of the dense-row kernels depends on (include/loco_hd_hip.h)."""
+    _fields_ = [("cols_a", C.c_int64), ("cols_b", C.c_int64), ("n_categories", C.c_int32), ("hellinger2", C.c_int32),
+                ("unit_weights", C.c_int32), ("cat16", C.c_int32), ("given_rows", C.c_int32), ("ragged", C.c_int32), ("hooks", C.c_uint32),
+                ("attempt", C.c_int32), ("single_attempt", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DenseRowsSideC(C.Structure):
+    """lchd_dense_rows_side: one side of the k_env_rows path."""
+    _fields_ = [("nt", C.c_int32), ("globalkv", C.c_int32), ("cat_bytes", C.c_int32), ("buckets", C.c_int32), ("cap", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class DensePlanC(C.Structure):
+    """lchd_dense_plan: the path of a dense call and the instantiation of its kernels."""
+    _fields_ = [("path", C.c_int32), ("unsupported", C.c_int32), ("fused_slots", C.c_int32), ("fused_dmx", C.c_int32), ("scr_segs", C.c_int32),
+                ("nt", C.c_int32), ("ept", C.c_int32), ("seg", C.c_int32), ("n2", C.c_int32), ("rows", DenseRowsSideC * 2)]
+
+    def as_dict(self) -> dict:
+        rec = {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "rows"}
+        rec["rows"] = [self.rows[0].as_dict(), self.rows[1].as_dict()]
+        return rec
+
+
+class DenseRecordC(C.Structure):
+    """lchd_dense_record: what the most recent dense call ran."""
+    _fields_ = [("plan", DensePlanC), ("attempts", C.c_int32), ("canon", C.c_int32), ("n_bitonic", C.c_int64)]
+
+
+# lchd_dense_path / lchd_dense_hook
+DENSE_NONE, DENSE_FUSED, DENSE_ROWS2, DENSE_ROWS = 0, 1, 2, 3
+DENSE_HOOK_OLD_ROWS, DENSE_HOOK_NO_FUSED = 1, 2
+
 # lchd_sweep_family / lchd_sweep_hook bits
 SWEEP_INLINE, SWEEP_TEAM240, SWEEP_TEAM480, SWEEP_C8, SWEEP_INDIRECT, SWEEP_PLAIN, SWEEP_INC, SWEEP_WIDE = (1 << k for k in range(8))
 HOOK_NO_DUO, HOOK_NO_COUNT8, HOOK_NO_C8_TEAM, HOOK_NO_INLINE_META, HOOK_FORCE_WIDE, HOOK_FORCE_GENERIC, HOOK_FORCE_BIGENV, HOOK_NO_SWEEP_HINT = (
@@ -174,6 +209,8 @@ _PROTOS = {
     "lchd_ctx_last_anchors": (C.c_int, [_VP, _i32, _LP, _IP, _LP]),
     "lchd_plan_sweep": (C.c_int, [C.POINTER(SweepQueryC), C.POINTER(SweepPlanC)]),
     "lchd_ctx_last_sweep": (C.c_int, [_VP, C.POINTER(SweepPlanC), _LP, _IP, _IP]),
+    "lchd_plan_dense": (C.c_int, [C.POINTER(DenseQueryC), C.POINTER(DensePlanC)]),
+    "lchd_ctx_last_dense": (C.c_int, [_VP, C.POINTER(DenseRecordC)]),
     "lchd_ctx_last_dense_fused": (C.c_int32, [_VP]),
     "lchd_ctx_set_deterministic": (C.c_int, [_VP, _i32]),
     "lchd_ctx_get_deterministic": (C.c_int32, [_VP]),

@@ -270,7 +270,8 @@ struct lchd_ctx {
     std::vector<char> cfg_blob_host;  // last configuration blob uploaded (identical configurations are not uploaded again)
     PassHints hints{};  // what the thresholded passes of this context looked like so far (lchd_pass_plan.h): plan_pass and launch_sweep read it
     const MinImage* min_image = nullptr;  // set for the duration of a periodic dense call
-    bool last_dense_fused = false;  // the most recent dense pass ran the fused sort + sweep kernel (lchd_dense_fused.hip)
+    lchd_dense_record last_dense{};  // what the most recent dense call ran (lchd_ctx_last_dense): plan of the attempt that stood, attempts, canon, bitonic rows
+    bool last_dense_valid = false;   // ... and whether it ran to its end
     int64_t n_per_pair_passes = 0;  // passes whose side B was not de-duplicated (PassPlan::per_pair)
     // second pass over the pairs of overflowed environments (lchd_ctx_finish): grow-only device blocks outside the arena
     char *d_ovf_bits = nullptr, *d_ovf_lists = nullptr;
@@ -619,7 +620,16 @@ extern "C" int lchd_ctx_set_deterministic(lchd_ctx* c, int32_t on) {
 }
 extern "C" int32_t lchd_ctx_get_deterministic(lchd_ctx* c) { CTX_LOCK(c); return (c && c->deterministic) ? 1 : 0; }
 
-extern "C" int32_t lchd_ctx_last_dense_fused(lchd_ctx* c) { CTX_LOCK(c); return (c && c->last_dense_fused) ? 1 : 0; }
+extern "C" int lchd_ctx_last_dense(lchd_ctx* c, lchd_dense_record* record_out) {
+    CTX_LOCK(c);
+    if (!c || !record_out || !c->last_dense_valid) return -1;
+    *record_out = c->last_dense;
+    return 0;
+}
+extern "C" int32_t lchd_ctx_last_dense_fused(lchd_ctx* c) {
+    CTX_LOCK(c);
+    return (c && c->last_dense_valid && c->last_dense.plan.path == LCHD_DENSE_FUSED) ? 1 : 0;
+}
 extern "C" int64_t lchd_ctx_pass_count(lchd_ctx* c) { CTX_LOCK(c); return c ? c->n_passes : -1; }
 
 extern "C" int lchd_ctx_set_config(lchd_ctx* c, const lchd_config* cfg) {
@@ -1050,6 +1060,13 @@ extern "C" int lchd_plan_grid(const double bbmin[3], const double bbmax[3], int3
     return LCHD_OK;
 }
 
+// Which kernel sorts the dense rows of a call: plan_dense (lchd_dense_plan.h), the decision dense_pass and ensemble_core follow.
+extern "C" int lchd_plan_dense(const lchd_dense_query* query, lchd_dense_plan* plan_out) {
+    if (!query || !plan_out) return fail(LCHD_EVALUE, "null argument");
+    if (!dense_query_ok(*query)) return fail(LCHD_EVALUE, "lchd_plan_dense: n_categories >= 1, attempt 0 or 1 and known hook bits are required");
+    *plan_out = plan_dense(*query);
+    return LCHD_OK;
+}
 // Which sweep kernels a pass launches: plan_sweep (lchd_kernels.hip), the decision launch_sweep follows.
 extern "C" int lchd_plan_sweep(const lchd_sweep_query* query, lchd_sweep_plan* plan_out) {
     if (!query || !plan_out) return fail(LCHD_EVALUE, "null argument");
@@ -2740,9 +2757,25 @@ static void produce_rows(hipStream_t s, const lchd_cloud& cl, int64_t n, int64_t
 // One dense pass (from_coords / from_dmxs semantics: pair r = row r of A against row r of B, the environment is the whole
 // structure): row sort of both structures, sweep.  a / b: device-resident structures (coordinates used unless d_ma / d_mb,
 // DEVICE pointers to given distance rows, are set); d_wf: device weight-function indices or nullptr; d_out: device or
-// host-mapped scores.  `retry` reports that a long row defeated the segmented in-LDS sort (repeat with old_rows).
+// host-mapped scores.  `attempt`: 0, or 1 for the repeat of a call; `retry` reports that a row defeated this attempt's kernel (the fused
+// kernel, the segmented in-LDS sort): repeat with attempt 1.  The attempt's plan, canon flag and bitonic rows go into c->last_dense.
+static lchd_dense_query dense_query(const lchd_ctx* c, int64_t cols_a, int64_t cols_b, bool given_rows, bool ragged, int attempt, bool single_attempt) {
+    lchd_dense_query q{};
+    q.cols_a = cols_a;
+    q.cols_b = cols_b;
+    q.n_categories = c->h_cfg.n_categories;
+    q.hellinger2 = c->hellinger2 ? 1 : 0;
+    q.unit_weights = c->unit_weights ? 1 : 0;
+    q.cat16 = c->h_cfg.n_categories > kMaxCategories ? 1 : 0;  // 16-bit ids in the environment store, k_env_rows<.., uint16_t> + k_sweep_wide<.., CAT16>
+    q.given_rows = given_rows ? 1 : 0;
+    q.ragged = ragged ? 1 : 0;
+    q.hooks = (c->tune.old_rows ? (uint32_t)LCHD_DENSE_HOOK_OLD_ROWS : 0u) | (c->tune.no_dense_fused ? (uint32_t)LCHD_DENSE_HOOK_NO_FUSED : 0u);
+    q.attempt = attempt;
+    q.single_attempt = single_attempt ? 1 : 0;
+    return q;
+}
 static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, const double* d_ma, const double* d_mb, int64_t rows,
-                      int64_t cols_a, int64_t cols_b, const int32_t* d_wf, double* d_out, bool old_rows, bool& retry,
+                      int64_t cols_a, int64_t cols_b, const int32_t* d_wf, double* d_out, int attempt, bool& retry,
                       const double* h_ma = nullptr, const double* h_mb = nullptr, const int32_t* d_len_a = nullptr,
                       const int32_t* d_len_b = nullptr) {
     retry = false;
@@ -2756,19 +2789,25 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
         mark(c, 1);
     };
     const int cap_a = next_pow2_host(cols_a), cap_b = next_pow2_host(cols_b);
-    // more than 255 categories: 16-bit ids in the environment store, k_env_rows<.., uint16_t> + k_sweep_wide<.., CAT16>
-    const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
-    c->last_dense_fused = false;
-    // The common configuration (Hellinger-2, unit category weights, <= 16 categories, rows of 1025 .. 20480 points = kDenseFusedMaxRow): sort and
+    c->last_dense_valid = false;
+    const lchd_dense_query query = dense_query(c, cols_a, cols_b, d_ma || h_ma || mi, d_len_a || d_len_b, attempt, false);
+    const lchd_dense_plan plan = plan_dense(query);
+    if (plan.unsupported) return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
+    const bool cat16 = query.cat16 != 0;
+    c->last_dense.plan = plan;
+    c->last_dense.attempts = attempt + 1;
+    c->last_dense.canon = 0;
+    c->last_dense.n_bitonic = 0;
+    // The common configuration (plan_dense: Hellinger-2, unit category weights, <= 16 categories, rows of 1025 .. kDenseFusedMaxRow points): sort and
     // sweep in ONE kernel per row pair, nothing but the score is written (lchd_dense_fused.hip).  No environment store.
-    if (!old_rows && !c->tune.no_dense_fused && !cat16 && c->hellinger2 && c->unit_weights &&
-        dense_fused_applies(c->h_cfg.n_categories, cols_a, cols_b)) {
+    if (plan.path == LCHD_DENSE_FUSED) {
         double* w_ma2 = nullptr;
         double* w_mb2 = nullptr;
         uint64_t* scr_key = nullptr;
         uint8_t* scr_val = nullptr;
-        int32_t scr_grid = 0, scr_segs = 0;
-        const size_t scr_n = dense_fused_scratch(rows, cols_a, cols_b, &scr_grid, &scr_segs);
+        int32_t scr_grid = 0;
+        const int32_t scr_segs = plan.scr_segs;
+        const size_t scr_n = dense_fused_scratch(rows, scr_segs, &scr_grid);
         for (int dry = 1; dry >= 0; --dry) {
             Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
             scr_key = ar.take<uint64_t>(scr_n);  // the distance pass's (key, value) pairs, one region per workgroup
@@ -2805,18 +2844,19 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
         da.scr_segs = scr_segs;
         da.ticket = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->d_done) + sizeof(DoneState));
         mark(c, 2);
-        if (launch_dense_fused(c->stream, c->h_cfg.n_categories, da, c->h_status, c->seq)) {
-            mark(c, 3);
-            mark(c, 4);
-            HIP_TRY(hipGetLastError());
-            c->status_dirty = false;  // the kernel's companion launch hands the status over and resets it
-            uint32_t f = 0;
-            if (int rc2 = wait_pass(c, &f)) return rc2;
-            collect_times(c, 2, 4);
-            c->last_dense_fused = true;
-            if (f & ST_ROW_RETRY) { retry = true; return LCHD_OK; }  // a row the fused kernel gives up on: the caller repeats with the two-kernel path
-            return status_to_rc(f, DRV_DMXS);
-        }
+        if (!launch_dense_fused(c->stream, plan, da, c->h_status, c->seq))
+            return fail(LCHD_EDEVICE, "internal error: the dense plan names no instantiation of the fused kernel");
+        mark(c, 3);
+        mark(c, 4);
+        HIP_TRY(hipGetLastError());
+        c->status_dirty = false;  // the kernel's companion launch hands the status over and resets it
+        uint32_t f = 0;
+        if (int rc2 = wait_pass(c, &f)) return rc2;
+        collect_times(c, 2, 4);
+        if (f & ST_ROW_RETRY) { retry = true; return LCHD_OK; }  // a row the fused kernel gives up on: the caller repeats with the two-kernel path
+        if (int rc2 = status_to_rc(f, DRV_DMXS)) return rc2;
+        c->last_dense_valid = true;
+        return LCHD_OK;
     }
     EnvStore ea{}, eb{};
     double *w_ma = nullptr, *w_mb = nullptr;
@@ -2846,17 +2886,25 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
     }
     mark(c, 2);
     const RowSide rsa{a.view(cat16), d_ma, cols_a, cols_a, diag2(a), ea, d_len_a}, rsb{b.view(cat16), d_mb, cols_b, cols_b, diag2(b), eb, d_len_b};
-    if (old_rows || cat16 || !launch_env_rows2(s, c->d_cfg, rsa, rsb, rows, c->d_status)) {  // (rows beyond 20480 points: keys sorted in global memory)
+    bool launched;
+    if (plan.path == LCHD_DENSE_ROWS2) {
+        launched = launch_env_rows2(s, plan, c->d_cfg, rsa, rsb, rows, c->d_status);
+    } else {  // (LCHD_DENSE_ROWS: one launch per side)
         const RowExtras exa{nullptr, d_len_a, nullptr}, exb{nullptr, d_len_b, nullptr};
-        if (!launch_env_rows(s, cap_a, c->d_cfg, a.view(cat16), d_ma, cols_a, rows, cols_a, diag2(a), ea, c->d_status, exa) ||
-            !launch_env_rows(s, cap_b, c->d_cfg, b.view(cat16), d_mb, cols_b, rows, cols_b, diag2(b), eb, c->d_status, exb))
-            return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
+        launched = launch_env_rows(s, plan.rows[0], c->d_cfg, a.view(cat16), d_ma, cols_a, rows, cols_a, diag2(a), ea, c->d_status, exa) &&
+                   launch_env_rows(s, plan.rows[1], c->d_cfg, b.view(cat16), d_mb, cols_b, rows, cols_b, diag2(b), eb, c->d_status, exb);
     }
-    if (c->deterministic) launch_env_canon(s, ea, eb, rows, rows, nullptr);  // one order among equal keys (a row's sort places ties by LDS-atomic order)
+    if (!launched) return fail(LCHD_EDEVICE, "internal error: the dense plan names no instantiation of the row kernels");
+    if (c->deterministic) {  // one order among equal keys (a row's sort places ties by LDS-atomic order)
+        launch_env_canon(s, ea, eb, rows, rows, nullptr);
+        c->last_dense.canon = 1;
+    }
     mark(c, 3);
     uint32_t f = 0;
     if (int rc2 = sweep_rows(c, ea, eb, d_wf, rows, d_out, d_meta, DRV_DMXS, &f)) return rc2;
+    c->last_dense.n_bitonic = c->h_status->n_bitonic;
     if (f & ST_ROW_RETRY) retry = true;
+    else c->last_dense_valid = true;
     return LCHD_OK;
 }
 
@@ -2918,7 +2966,7 @@ static int dense_driver(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_
         if (int rc2 = begin_pass(c)) return rc2;
         c->status_dirty = true;  // until the record pass has been enqueued (sweep_rows)
         HIP_TRY(hipMemcpyAsync(c->d_io, c->h_io, in_bytes, hipMemcpyHostToDevice, c->stream));
-        rc = dense_pass(c, a, b, nullptr, nullptr, rows, cols_a, cols_b, d_wf, d_out, c->tune.old_rows || attempt > 0, retry, dmx_a, dmx_b, d_la, d_lb);
+        rc = dense_pass(c, a, b, nullptr, nullptr, rows, cols_a, cols_b, d_wf, d_out, attempt, retry, dmx_a, dmx_b, d_la, d_lb);
         if (rc || !retry) break;
     }
     if (rc) return rc;
@@ -2952,7 +3000,7 @@ extern "C" int lchd_from_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, c
     for (int attempt = 0; attempt < 2; ++attempt) {
         if (int rc = begin_pass(c)) return rc;
         c->status_dirty = true;
-        if (int rc = dense_pass(c, *a, *b, nullptr, nullptr, a->n, a->n, b->n, d_wf_index, d_out, c->tune.old_rows || attempt > 0, retry)) return rc;
+        if (int rc = dense_pass(c, *a, *b, nullptr, nullptr, a->n, a->n, b->n, d_wf_index, d_out, attempt, retry)) return rc;
         if (!retry) break;
     }
     return LCHD_OK;
@@ -3137,15 +3185,21 @@ static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, c
                          double* d_out) {
     const int64_t P = (int64_t)pairs.size() / 2;
     c->last_valid = c->last_sweep_valid = false;
-    c->last_dense_fused = false;
+    c->last_dense_valid = false;
     if (P == 0 || n == 0) return LCHD_OK;
-    const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
-    if (n > 65535 && (cat16 || n > (1 << 23)))
+    // (a call that cannot be repeated: k_env_rows2 up to its one-segment limit, longer rows through k_env_rows, which needs no retry)
+    const lchd_dense_query query = dense_query(c, n, n, true, false, 0, true);
+    const lchd_dense_plan dplan = plan_dense(query);
+    const bool cat16 = query.cat16 != 0;
+    if (dplan.unsupported)
         return fail(LCHD_EUNSUPPORTED, "dense rows of more than 65535 points are supported with at most %d categories and 2^23 points (got %lld)",
                     kMaxCategories, (long long)n);
+    c->last_dense = lchd_dense_record{};
+    c->last_dense.plan = dplan;
+    c->last_dense.attempts = 1;
     const int64_t cap = next_pow2_host(n);
     const size_t cat_bytes = cat16 ? 2 : 1;
-    const bool rows2 = !cat16 && !c->tune.old_rows && n <= 16384;  // (longer rows: k_env_rows, which needs no segmented-sort retry)
+    const bool rows2 = dplan.path == LCHD_DENSE_ROWS2;
     const int64_t dist_structs = std::max<int64_t>(1, std::min<int64_t>(M, kEnsDistBytes / (8 * n * n)));
     const int64_t pass_pairs = std::max<int64_t>(1, std::min<int64_t>(P, kEnsRecords / n));
     const int64_t q_cap = pass_pairs * n;
@@ -3228,24 +3282,25 @@ static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, c
                 const int64_t h = rows / 2;
                 EnvStore e1 = e0;
                 e1.key += h * cap; e1.cat += h * cap; e1.len += h;
-                ok = launch_env_rows2(s, c->d_cfg, RowSide{src.cats, dmx, n, n, 0.0, e0, nullptr}, RowSide{src.cats, dmx + h * n, n, n, 0.0, e1, nullptr}, h,
+                ok = launch_env_rows2(s, dplan, c->d_cfg, RowSide{src.cats, dmx, n, n, 0.0, e0, nullptr}, RowSide{src.cats, dmx + h * n, n, n, 0.0, e1, nullptr}, h,
                                       c->d_status);
                 if (ok && (rows & 1)) {
                     EnvStore el = e0, spare = st;
                     el.key += (rows - 1) * cap; el.cat += (rows - 1) * cap; el.len += rows - 1;
                     spare.key += slots * n * cap; spare.cat += slots * n * cap; spare.len += slots * n;
                     const double* last = dmx + (rows - 1) * n;
-                    ok = launch_env_rows2(s, c->d_cfg, RowSide{src.cats, last, n, n, 0.0, el, nullptr}, RowSide{src.cats, last, n, n, 0.0, spare, nullptr}, 1,
+                    ok = launch_env_rows2(s, dplan, c->d_cfg, RowSide{src.cats, last, n, n, 0.0, el, nullptr}, RowSide{src.cats, last, n, n, 0.0, spare, nullptr}, 1,
                                           c->d_status);
                 }
             } else {
-                ok = launch_env_rows(s, (int)cap, c->d_cfg, src.cats, dmx, n, rows, n, 0.0, e0, c->d_status);
+                ok = launch_env_rows(s, dplan.rows[0], c->d_cfg, src.cats, dmx, n, rows, n, 0.0, e0, c->d_status);
             }
             if (!ok) return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for rows of %lld points", (long long)n);
         }
         if (c->deterministic) {  // one order among equal keys, as deterministic from_coords / from_dmxs
             const EnvStore e = rows_of(slot0);
             launch_env_canon(s, e, e, cnt * n, 0, nullptr);
+            c->last_dense.canon = 1;
         }
         HIP_TRY(hipGetLastError());
         return LCHD_OK;
@@ -3293,12 +3348,14 @@ static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, c
             }
             launch_ens_records(s, plan + k0, kc, (int32_t)n, d_wf, anchors, wf_rec);
             if (int rc = ens_sweep(c, st, anchors, iota, slots * n, wf_rec, kc * n, tmp, meta)) return rc;
+            c->last_dense.n_bitonic += c->h_status->n_bitonic;  // (rows of the row-sort launches since the previous record pass)
             launch_ens_scatter(s, tmp, plan + k0, kc, (int32_t)n, d_out);
         }
         g0 = g1;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
+    c->last_dense_valid = true;
     return LCHD_OK;
 }
 
@@ -3946,9 +4003,12 @@ static int consumer_dense(lchd_ctx* c, const lchd_cloud* const* cl, const double
         if (cell[k]) { produce_rows(s, *cl[k], cols[k], rows, cell[k], w_m[k]); d_m[k] = w_m[k]; }
     mark(c, 1);
     mark(c, 2);
-    for (int k = 0; k < sides; ++k)
-        if (!launch_env_rows(s, cap[k], c->d_cfg, cl[k]->view(cat16), d_m[k], cols[k], rows, cols[k], diag2(*cl[k]), e[k], c->d_status))
+    for (int k = 0; k < sides; ++k) {
+        lchd_dense_rows_side side;
+        if (!plan_dense_rows_side(cap[k], cols[k], cat16, side) ||
+            !launch_env_rows(s, side, c->d_cfg, cl[k]->view(cat16), d_m[k], cols[k], rows, cols[k], diag2(*cl[k]), e[k], c->d_status))
             return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
+    }
     if (c->deterministic) launch_env_canon(s, e[0], e[sides - 1], rows, rows * (sides - 1), nullptr);  // (one launch; one side: no rows of a second store)
     if (n_wf > 1) {
         launch_profile_rows(s, c->d_status, rows);  // (the key-set kernel walks DeviceStatus::n_unique[0] rows of its first store)

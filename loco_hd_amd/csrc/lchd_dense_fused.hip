@@ -62,18 +62,18 @@ __device__ __forceinline__ const LCHD_AS4 T* df_const(const T* p) {  // memory t
 }
 
 constexpr int kNT = 512, kWaves = kNT / 64;  // threads per workgroup (1024 with segments of 14336 events -- one workgroup per CU -- was slower: DESIGN.md)
-constexpr int kCap = 6144;            // events of one distance segment (keys + values in LDS)
+constexpr int kCap = kDenseFusedSegCap;  // (6144) events of one distance segment (keys + values in LDS)
 constexpr int kEpt = kCap / kNT;      // 14 events per thread in the sort and in the sweep (<= 15: 4-bit chunk-local counters)
-constexpr int kSample = 4;            // the coarse CDF of a row pair is estimated from every kSample-th point of either row
+constexpr int kSample = kDenseFusedSample;  // (4) the coarse CDF of a row pair is estimated from every kSample-th point of either row
 constexpr int kCoarse = 512;          // uniform bins of the distance image; bin kCoarse holds +inf entries of a distance matrix
-constexpr int kGrid = 512;            // workgroups of a launch (two per CU): each owns one scratch region and takes rows blockIdx, + grid, ...
+constexpr int kGrid = kDenseFusedGrid;  // (512) workgroups of a launch (two per CU): each owns one scratch region and takes rows blockIdx, + grid, ...
 // events a segment may be PLANNED to hold: the plan sees a sample, the segment must hold the real thing (six standard deviations of the
 // count that a sample of one in kSample predicts, and a coarse bin's worth)
-__host__ __device__ inline int df_seg_margin(int est) { return 6 * (int)sqrtf((float)(est * kSample)) + 70; }
+__host__ __device__ inline int df_seg_margin(int est) { return dense_fused_seg_margin(est); }  // (lchd_dense_plan.h: the host's plan uses the same)
 constexpr int kBuckets = 8192;        // buckets of a segment's sort, two 16-bit counters per LDS word
 constexpr int kBucketLimit = 64;      // a fuller bucket sends the call to the two-kernel path
 constexpr int kPart = kBuckets / 4;   // sqrt(k) for k < kPart from LDS (the histogram's bytes), larger counts are computed
-constexpr int kMaxSeg = 16;           // (<= 64: the plan gives every boundary a lane)
+constexpr int kMaxSeg = kDenseFusedMaxSeg;  // (16; <= 64: the plan gives every boundary a lane)
 constexpr double kExactBelow = 1e-6;  // as lchd_team_tile.h (kExactH2Below): below this H^2 the literal difference-of-roots form
 static_assert(kEpt <= 15 && kCap % kNT == 0, "chunk-local counters are 4-bit fields");
 static_assert((kBuckets / 2) % (4 * kNT) == 0 && kBuckets <= 8192, "the bucket scan gives every thread whole 16-byte groups of histogram words; 13-bit bucket ids");
@@ -810,9 +810,11 @@ __global__ void k_dense_publish(DeviceStatus* st, HostStatus* h, uint32_t seq, u
     h->n_unique[0] = h->n_unique[1] = 0u;
     h->n_small = 0ull;
     h->n_duo = h->n_c8 = 0ull;
+    h->n_bitonic = st->n_bitonic;
     h->snapshot_seq = seq;
     st->flags = 0u;
     st->max_env = 0u;
+    st->n_bitonic = 0u;
 }
 
 #ifdef LCHD_DF_STAMPS
@@ -826,22 +828,10 @@ extern "C" int lchd_debug_dense_stamps(unsigned long long* out16, int reset) {
 }
 #endif
 
-bool dense_fused_applies(int n_categories, int64_t len_a, int64_t len_b) {
-    const int64_t longest = len_a > len_b ? len_a : len_b;
-    return n_categories <= 16 && longest > kDenseFusedMinRow && longest <= kDenseFusedMaxRow && len_a >= 1 && len_b >= 1;
-}
-
-size_t dense_fused_scratch(int64_t n_rows, int64_t len_a, int64_t len_b, int32_t* grid_out, int32_t* segs_out) {
-    const int64_t total = len_a + len_b;
-    // the plan starts at ceil(total / kCap) segments and adds some until the sample's estimates fit with their margin: two more
-    // than the balanced plan needs cover every row pair whose sample is not grossly off (otherwise: ST_ROW_RETRY)
-    int S = (int)std::max<int64_t>(1, (total + kCap - 1) / kCap);
-    while (S < kMaxSeg && (int)(total / S) + df_seg_margin((int)(total / S)) > kCap) ++S;
-    const int segs = std::min(kMaxSeg, S + 2);
+size_t dense_fused_scratch(int64_t n_rows, int32_t scr_segs, int32_t* grid_out) {
     const int grid = (int)std::min<int64_t>(n_rows, kGrid);
     if (grid_out) *grid_out = grid;
-    if (segs_out) *segs_out = segs;
-    return (size_t)std::max(grid, 1) * (size_t)segs * (size_t)kCap;
+    return (size_t)std::max(grid, 1) * (size_t)scr_segs * (size_t)kCap;
 }
 
 void init_dense_fused_kernels() {
@@ -855,19 +845,17 @@ void init_dense_fused_kernels() {
     (void)hipGetLastError();
 }
 
-bool launch_dense_fused(hipStream_t s, int n_categories, const DenseArgs& a, HostStatus* hst, uint32_t seq) {
+bool launch_dense_fused(hipStream_t s, const lchd_dense_plan& plan, const DenseArgs& a, HostStatus* hst, uint32_t seq) {
     if (a.n_rows <= 0) return true;
-    const bool dmx = a.s[0].dmx != nullptr;
-    if (dmx != (a.s[1].dmx != nullptr)) return false;
-    if (!dense_fused_applies(n_categories, a.s[0].row_len, a.s[1].row_len)) return false;
-    if (!a.scr_key || !a.scr_val || !a.ticket || a.scr_segs < 1 || a.scr_grid < 1) return false;
+    const bool dmx = plan.fused_dmx != 0;
+    if (plan.path != LCHD_DENSE_FUSED || dmx != (a.s[0].dmx != nullptr) || dmx != (a.s[1].dmx != nullptr)) return false;
+    if (!a.scr_key || !a.scr_val || !a.ticket || a.scr_segs != plan.scr_segs || a.scr_segs < 1 || a.scr_grid < 1) return false;
     const unsigned grid = (unsigned)std::min<int64_t>(a.n_rows, a.scr_grid);  // (a workgroup per scratch region; rows blockIdx, + grid, ...)
-    if (n_categories <= 8) {
-        if (dmx) k_dense_fused<8, true><<<grid, kNT, kDynLds, s>>>(a); else k_dense_fused<8, false><<<grid, kNT, kDynLds, s>>>(a);
-    } else if (n_categories <= 12) {
-        if (dmx) k_dense_fused<12, true><<<grid, kNT, kDynLds, s>>>(a); else k_dense_fused<12, false><<<grid, kNT, kDynLds, s>>>(a);
-    } else {
-        if (dmx) k_dense_fused<16, true><<<grid, kNT, kDynLds, s>>>(a); else k_dense_fused<16, false><<<grid, kNT, kDynLds, s>>>(a);
+    switch (plan.fused_slots) {
+        case 8: if (dmx) k_dense_fused<8, true><<<grid, kNT, kDynLds, s>>>(a); else k_dense_fused<8, false><<<grid, kNT, kDynLds, s>>>(a); break;
+        case 12: if (dmx) k_dense_fused<12, true><<<grid, kNT, kDynLds, s>>>(a); else k_dense_fused<12, false><<<grid, kNT, kDynLds, s>>>(a); break;
+        case 16: if (dmx) k_dense_fused<16, true><<<grid, kNT, kDynLds, s>>>(a); else k_dense_fused<16, false><<<grid, kNT, kDynLds, s>>>(a); break;
+        default: return false;
     }
     k_dense_publish<<<1, 1, 0, s>>>(a.st, hst, seq, a.ticket);
     return true;

@@ -9,6 +9,7 @@
 
 #include "lchd_cell_reduce.h"  // host only: kMinImageRecord, the cell of the dense minimum-image calls
 #include "lchd_pass_plan.h"  // the host-only part: Tuning, HostStatus, the ST_* status bits, the pass planner
+#include "lchd_dense_plan.h"  // host only: the dense-row planner and every limit of its three kernels
 
 struct lchd_sweep_query;  // include/loco_hd_hip.h
 struct lchd_sweep_plan;
@@ -51,6 +52,9 @@ struct DeviceStatus {
                              //  then only says "more than the capacity"); reset with the flags
     uint32_t n_dup_b;        // a pass without de-duplication of side B (k_pair_anchor_recs): pairs whose side-B anchor another pair of the list had
                              //  marked before (a bit set in the side's flag region, one returning atomic per pair); reset with the flags
+    uint32_t n_bitonic;      // dense rows whose sort met a bucket beyond kRowBucketLimit points and took the bitonic network (k_env_rows, k_env_rows2:
+                             //  one atomic per such row); reset with the flags
+    uint32_t pad;
 };
 
 
@@ -210,7 +214,8 @@ struct RowExtras {            // all null for from_coords / from_dmxs
     const int32_t* row_lens;  // [n_rows] points of each row (<= 0: skip the row)
     const uint32_t* n_unique; // rows at or beyond *n_unique do not exist
 };
-bool launch_env_rows(hipStream_t s, int cap, const DevConfig* cfg, const CloudView& c, const double* dmx, int64_t ld,
+// side: the instantiation (plan_dense_rows_side / lchd_dense_plan::rows, lchd_dense_plan.h); false: it names none, nothing launched
+bool launch_env_rows(hipStream_t s, const lchd_dense_rows_side& side, const DevConfig* cfg, const CloudView& c, const double* dmx, int64_t ld,
                      int64_t n_rows, int64_t row_len, double image_bound /* coords: >= largest squared distance, or 0 */, EnvStore env,
                      DeviceStatus* st, const RowExtras& ex = RowExtras{nullptr, nullptr, nullptr});
 
@@ -233,12 +238,13 @@ struct RowSides {
     RowSide s[2];
     int64_t n_rows;
 };
-// rows of at most 16384 points on both sides; returns false (nothing launched) otherwise
-bool launch_env_rows2(hipStream_t s, const DevConfig* cfg, const RowSide& a, const RowSide& b, int64_t n_rows, DeviceStatus* st);
+// both sides in one launch of the plan's k_env_rows2<nt, ept, seg> (path LCHD_DENSE_ROWS2); false: the plan names no instantiation
+bool launch_env_rows2(hipStream_t s, const lchd_dense_plan& plan, const DevConfig* cfg, const RowSide& a, const RowSide& b, int64_t n_rows,
+                      DeviceStatus* st);
 
 // Dense rows, sort and sweep fused (lchd_dense_fused.hip): one workgroup per row pair, only the score is written.
-// Applies to Hellinger-2 with unit category weights, at most 16 categories and rows of kDenseFusedMinRow < n <= kDenseFusedMaxRow points.
-constexpr int kDenseFusedMinRow = 1024, kDenseFusedMaxRow = 20480;
+// Applies to Hellinger-2 with unit category weights, at most 16 categories and rows of kDenseFusedMinRow < n <= kDenseFusedMaxRow points
+// (lchd_dense_plan.h: plan_dense decides, launch_dense_fused follows lchd_dense_plan::fused_slots / fused_dmx).
 struct DenseSide {
     CloudView c;              // categories (and coordinates when dmx == nullptr)
     const double* dmx;        // given distance rows [n_rows][ld], or nullptr
@@ -262,11 +268,10 @@ struct DenseArgs {
     int32_t scr_segs, scr_grid;
     unsigned long long* ticket;  // context-owned: rows handed out beyond the first one of every workgroup (zero between launches)
 };
-// workgroups of a launch and segments per workgroup for rows of up to (len_a, len_b) points; returns the ENTRIES of either scratch array
-size_t dense_fused_scratch(int64_t n_rows, int64_t len_a, int64_t len_b, int32_t* grid_out, int32_t* segs_out);
-bool dense_fused_applies(int n_categories, int64_t len_a, int64_t len_b);
-// returns false (nothing launched) when the kernel does not apply; otherwise the kernel and the status hand-over are enqueued
-bool launch_dense_fused(hipStream_t s, int n_categories, const DenseArgs& a, HostStatus* hst, uint32_t seq);
+// workgroups of a launch of n_rows row pairs with the plan's scr_segs segments per workgroup; returns the ENTRIES of either scratch array
+size_t dense_fused_scratch(int64_t n_rows, int32_t scr_segs, int32_t* grid_out);
+// returns false (nothing launched) when the plan or the arguments are not the kernel's; otherwise the kernel and the status hand-over are enqueued
+bool launch_dense_fused(hipStream_t s, const lchd_dense_plan& plan, const DenseArgs& a, HostStatus* hst, uint32_t seq);
 void init_dense_fused_kernels();  // per device (dynamic LDS above 64 KB), called by lchd_ctx_create
 
 struct SweepArgs {

@@ -456,7 +456,9 @@ bool launch_env_cells(hipStream_t s, int cap, const DevConfig* cfg, bool tag_lis
             const EnvSide& S = side ? b : a;
             if (S.max_envs <= 0) continue;
             RowExtras ex{S.raw_cat, S.env.len, &st->n_unique[side]};
-            if (!launch_env_rows(s, cap, cfg, S.c, S.raw_key, cap, S.max_envs, cap, 0.0, S.env, st, ex)) return false;
+            lchd_dense_rows_side rows;
+            if (!plan_dense_rows_side(cap, cap, false, rows)) return false;
+            if (!launch_env_rows(s, rows, cfg, S.c, S.raw_key, cap, S.max_envs, cap, 0.0, S.env, st, ex)) return false;
         }
         return true;
     }

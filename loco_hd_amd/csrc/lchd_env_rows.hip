@@ -17,10 +17,7 @@ __device__ unsigned long long g_rows_stamps[8];
 // utils.rs:10-22 + :25-39) or from_dmxs (a caller-supplied distance-matrix row, src/locohd.rs:439-440).
 // Dynamic LDS: n2 * 9 bytes.
 // ------------------------------------------------------------------------------------------------
-constexpr int kRowBucketsSmall = 2048;   // distance buckets of the dense-row sort (rows <= 16384 points)
-constexpr int kRowBucketsMax = 8192;     // ... of k_env_rows2 when the row leaves room for them
-constexpr int kRowBucketsBig = 16384;    // ... for rows of up to 65535 points (keys stay in global memory)
-constexpr int kRowBucketsHuge = 32768;   // ... for longer rows
+// (kRowBucketsSmall / Max / Big / Huge, the distance buckets of the sorts below, and every row-length limit: lchd_dense_plan.h)
 constexpr int kRowCoarse = 256;       // uniform bins of the row's empirical distance CDF
 constexpr int kRowBucketLimit = 64;   // a fuller bucket sends the row to the bitonic network instead
 
@@ -135,6 +132,7 @@ __global__ __launch_bounds__(NT) void k_env_rows(const DevConfig* __restrict__ c
     for (int w = 0; w < NT / 64; ++w) biggest = max(biggest, red_cnt[w]);
 
     if (biggest > (uint32_t)kRowBucketLimit) {
+        if (tid == 0) atomicAdd(&st->n_bitonic, 1u);  // (lchd_ctx_last_dense: rows that took this branch)
         for (int i = tid; i < n2; i += NT) {
             key[i] = i < n ? d2u(dist_of(i, bad)) : kPadKey;
             val[i] = i < n ? cat_at(i) : (VT)0;
@@ -218,6 +216,8 @@ __global__ __launch_bounds__(NT) void k_env_rows(const DevConfig* __restrict__ c
 // ------------------------------------------------------------------------------------------------
 constexpr int kRowSegCap = 11776;  // rows of more than 16384 points: most points of one distance segment (keys in LDS)
 constexpr int kRowLongEpt = 20;    // ... and the points per thread of such a row (<= 20480 points, 1024 threads)
+static_assert(1024 * kRowLongEpt == kRows2MaxRow && 1024 * kRows2SegEpt >= kRowSegCap && 2 * kRowSegCap >= kRows2MaxRow,
+              "plan_dense's two-segment limit is what 1024 threads hold, and a balanced segment fits the key array");
 constexpr size_t kRowSegLds = (size_t)kRowSegCap * 9 + (size_t)(kRowBucketsMax + 1) * 4;  // keys, categories, histogram
 static_assert(((size_t)kRowSegCap * 9) % 16 == 0, "histogram alignment");
 // EPT: points per thread of ONE sort -- the whole row, or one distance segment of a long row (NSEG = 2).
@@ -535,6 +535,7 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 2 : 4)) void k_env_rows2(const Dev
                 return;
             }
             // a pathological row (thousands of identical distances): the bitonic network on the exact keys
+            if (tl == 0) atomicAdd(&st->n_bitonic, 1u);  // (lchd_ctx_last_dense: rows that took this branch)
 #pragma unroll
             for (int q = 0; q < EPT; ++q) {
                 const int i = tl + q * NT;
@@ -652,82 +653,81 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 2 : 4)) void k_env_rows2(const Dev
     if (__ballot(bad_c) && lane == 0) atomicOr(&st->flags, ST_BAD_CATEGORY);
 }
 
-bool launch_env_rows2(hipStream_t s, const DevConfig* cfg, const RowSide& a, const RowSide& b, int64_t n_rows, DeviceStatus* st) {
+// The instantiations plan_dense (lchd_dense_plan.h) may name, each with the longest row it is named for.
+template <int NT, int EPT, int UPTO>
+struct Rows2Fits {
+    static_assert(NT * EPT >= UPTO && UPTO <= kRows2OneSeg, "every point of the row has a register");
+    static constexpr bool value = true;
+};
+static_assert(Rows2Fits<64, 16, 1024>::value && Rows2Fits<256, 16, 4096>::value && Rows2Fits<1024, 8, 8192>::value &&
+              Rows2Fits<1024, 10, 10240>::value && Rows2Fits<1024, 16, 16384>::value, "kRows2Ladder");
+// LDS of a one-segment launch with a key array of n2 points: keys, categories, histogram
+static size_t rows2_lds(int n2) { return (size_t)n2 * 9 + 16 + (size_t)(kRowBucketsSmall + 1) * sizeof(uint32_t); }
+// ... of a k_env_rows launch that sorts in LDS
+static size_t rows_lds(int cap, int cat_bytes) { return (size_t)cap * (8 + cat_bytes) + 16 + (size_t)(kRowBucketsSmall + 1) * sizeof(uint32_t); }
+
+bool launch_env_rows2(hipStream_t s, const lchd_dense_plan& plan, const DevConfig* cfg, const RowSide& a, const RowSide& b, int64_t n_rows,
+                      DeviceStatus* st) {
     if (n_rows <= 0) return true;
-    const int64_t longest = std::max(a.row_len, b.row_len);
-    if (longest > 20480 || a.row_len < 1 || b.row_len < 1) return false;
-    int n2 = 64;
-    while (n2 < longest && n2 < 16384) n2 <<= 1;
-    // rows of 16385 .. 20480 points: sorted in distance segments of ~10^4 points each (the segment's keys in LDS)
-    const int n_seg = longest > 16384 ? 2 : 1;
-    if (n_seg > 1 && (std::min(a.row_len, b.row_len) <= 16384)) return false;  // (one launch, one segment count: both sides must be long)
-    if (n_seg > 1 && (a.row_lens || b.row_lens)) return false;  // (ragged rows may be short: same reason)
+    if (plan.path != LCHD_DENSE_ROWS2) return false;
     RowSides sides;
     sides.s[0] = a; sides.s[1] = b;
     if (a.dmx) sides.s[0].image_bound = 0.0;  // given rows: the kernel finds the largest finite entry itself
     if (b.dmx) sides.s[1].image_bound = 0.0;
     sides.n_rows = n_rows;
     const dim3 grid((unsigned)(2 * n_rows));
-    const size_t lds = (size_t)n2 * 9 + 16 + (size_t)(kRowBucketsSmall + 1) * sizeof(uint32_t);
-    if (n_seg > 1) k_env_rows2<1024, 12, 2><<<grid, 1024, kRowSegLds, s>>>(cfg, sides, n2, st);
-    else if (n2 <= 1024) k_env_rows2<64, 16, 1><<<grid, 64, lds, s>>>(cfg, sides, n2, st);
-    else if (n2 <= 4096) k_env_rows2<256, 16, 1><<<grid, 256, lds, s>>>(cfg, sides, n2, st);
-    else if (n2 <= 8192) k_env_rows2<1024, 8, 1><<<grid, 1024, lds, s>>>(cfg, sides, n2, st);
-    else if (longest <= 10240) k_env_rows2<1024, 10, 1><<<grid, 1024, lds, s>>>(cfg, sides, n2, st);
-    else k_env_rows2<1024, 16, 1><<<grid, 1024, lds, s>>>(cfg, sides, n2, st);
+    const int n2 = plan.n2;
+    const size_t lds = rows2_lds(n2);
+    const int inst = plan.nt * 10000 + plan.ept * 10 + plan.seg;
+    switch (inst) {
+        // rows of 16385 .. 20480 points: sorted in distance segments of ~10^4 points each (the segment's keys in LDS)
+        case 1024 * 10000 + 12 * 10 + 2: k_env_rows2<1024, 12, 2><<<grid, 1024, kRowSegLds, s>>>(cfg, sides, n2, st); break;
+        case 64 * 10000 + 16 * 10 + 1: k_env_rows2<64, 16, 1><<<grid, 64, lds, s>>>(cfg, sides, n2, st); break;
+        case 256 * 10000 + 16 * 10 + 1: k_env_rows2<256, 16, 1><<<grid, 256, lds, s>>>(cfg, sides, n2, st); break;
+        case 1024 * 10000 + 8 * 10 + 1: k_env_rows2<1024, 8, 1><<<grid, 1024, lds, s>>>(cfg, sides, n2, st); break;
+        case 1024 * 10000 + 10 * 10 + 1: k_env_rows2<1024, 10, 1><<<grid, 1024, lds, s>>>(cfg, sides, n2, st); break;
+        case 1024 * 10000 + 16 * 10 + 1: k_env_rows2<1024, 16, 1><<<grid, 1024, lds, s>>>(cfg, sides, n2, st); break;
+        default: return false;
+    }
     return true;
 }
 
-bool launch_env_rows(hipStream_t s, int cap, const DevConfig* cfg, const CloudView& c, const double* dmx, int64_t ld,
+bool launch_env_rows(hipStream_t s, const lchd_dense_rows_side& side, const DevConfig* cfg, const CloudView& c, const double* dmx, int64_t ld,
                      int64_t n_rows, int64_t row_len, double image_bound, EnvStore env, DeviceStatus* st, const RowExtras& ex) {
     if (dmx) image_bound = 0.0;  // given rows: the kernel finds the largest finite entry itself
     if (n_rows <= 0) return true;
-    if (row_len > cap || cap > (1 << 23)) return false;
+    const int cap = side.cap, nb = side.buckets;
+    if ((side.cat_bytes == 2) != (env.cat16 != 0)) return false;
+    if (side.cat_bytes == 2 && ex.row_cat) return false;  // (the collected rows of k_env_collect are one-byte only)
     const dim3 grid((unsigned)n_rows);
-    if (cap > 65536) {  // rows of more than 65 535 points (swept by k_sweep_wide<.., BIG>): keys in the store, 32768 buckets (128 KB of LDS)
-        if (env.cat16) return false;
-        const size_t lds = (size_t)(kRowBucketsHuge + 1) * sizeof(uint32_t) + 16;
-        k_env_rows<1024, true><<<grid, 1024, lds, s>>>(cfg, c, dmx, ld, row_len, cap, kRowBucketsHuge, image_bound, env, st, ex);
-        return true;
-    }
-    if (env.cat16) {  // more than 255 categories: two bytes per point (rows of up to 8192 points in LDS, longer ones in the store)
-        if (ex.row_cat) return false;
-        if (cap > 8192) {
-            const size_t lds = (size_t)(kRowBucketsBig + 1) * sizeof(uint32_t) + 16;
-            k_env_rows<1024, true, uint16_t><<<grid, 1024, lds, s>>>(cfg, c, dmx, ld, row_len, cap, kRowBucketsBig, image_bound, env, st, ex);
-        } else {
-            const size_t lds = (size_t)cap * 10 + 16 + (size_t)(kRowBucketsSmall + 1) * sizeof(uint32_t);
-            if (cap <= 1024) k_env_rows<64, false, uint16_t><<<grid, 64, lds, s>>>(cfg, c, dmx, ld, row_len, cap, kRowBucketsSmall, image_bound, env, st, ex);
-            else k_env_rows<1024, false, uint16_t><<<grid, 1024, lds, s>>>(cfg, c, dmx, ld, row_len, cap, kRowBucketsSmall, image_bound, env, st, ex);
-        }
-        return true;
-    }
-    if (cap > 16384) {  // keys in global memory, 64 KB histogram in LDS
-        const size_t lds = (size_t)(kRowBucketsBig + 1) * sizeof(uint32_t) + 16;
-        k_env_rows<1024, true><<<grid, 1024, lds, s>>>(cfg, c, dmx, ld, row_len, cap, kRowBucketsBig, image_bound, env, st, ex);
-        return true;
-    }
-    const size_t lds = (size_t)cap * 9 + 16 + (size_t)(kRowBucketsSmall + 1) * sizeof(uint32_t);
-    if (cap <= 1024) {
-        k_env_rows<64, false><<<grid, 64, lds, s>>>(cfg, c, dmx, ld, row_len, cap, kRowBucketsSmall, image_bound, env, st, ex);
-    } else if (cap <= 4096) {
-        k_env_rows<256, false><<<grid, 256, lds, s>>>(cfg, c, dmx, ld, row_len, cap, kRowBucketsSmall, image_bound, env, st, ex);
-    } else {
-        k_env_rows<1024, false><<<grid, 1024, lds, s>>>(cfg, c, dmx, ld, row_len, cap, kRowBucketsSmall, image_bound, env, st, ex);
+    const size_t lds = side.globalkv ? (size_t)(nb + 1) * sizeof(uint32_t) + 16 : rows_lds(cap, side.cat_bytes);
+    const int inst = side.nt * 100 + side.globalkv * 10 + side.cat_bytes;
+    switch (inst) {
+        // keys in the store (global memory), the histogram alone in LDS: 16384 buckets (64 KB), or 32768 (128 KB) for rows swept by k_sweep_wide<.., BIG>
+        case 1024 * 100 + 10 + 1: k_env_rows<1024, true><<<grid, 1024, lds, s>>>(cfg, c, dmx, ld, row_len, cap, nb, image_bound, env, st, ex); break;
+        case 1024 * 100 + 10 + 2: k_env_rows<1024, true, uint16_t><<<grid, 1024, lds, s>>>(cfg, c, dmx, ld, row_len, cap, nb, image_bound, env, st, ex); break;
+        // keys and categories in LDS
+        case 64 * 100 + 1: k_env_rows<64, false><<<grid, 64, lds, s>>>(cfg, c, dmx, ld, row_len, cap, nb, image_bound, env, st, ex); break;
+        case 256 * 100 + 1: k_env_rows<256, false><<<grid, 256, lds, s>>>(cfg, c, dmx, ld, row_len, cap, nb, image_bound, env, st, ex); break;
+        case 1024 * 100 + 1: k_env_rows<1024, false><<<grid, 1024, lds, s>>>(cfg, c, dmx, ld, row_len, cap, nb, image_bound, env, st, ex); break;
+        // more than 255 categories: two bytes per point
+        case 64 * 100 + 2: k_env_rows<64, false, uint16_t><<<grid, 64, lds, s>>>(cfg, c, dmx, ld, row_len, cap, nb, image_bound, env, st, ex); break;
+        case 1024 * 100 + 2: k_env_rows<1024, false, uint16_t><<<grid, 1024, lds, s>>>(cfg, c, dmx, ld, row_len, cap, nb, image_bound, env, st, ex); break;
+        default: return false;
     }
     return true;
 }
 
 void init_env_rows_kernels() {
-    auto raise = [](const void* fn, int bytes) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
-    raise(reinterpret_cast<const void*>(&k_env_rows<1024, true>), (int)((kRowBucketsHuge + 1) * sizeof(uint32_t) + 16));
-    raise(reinterpret_cast<const void*>(&k_env_rows<1024, false>), 16384 * 9 + 16 + (kRowBucketsSmall + 1) * 4);
-    raise(reinterpret_cast<const void*>(&k_env_rows<1024, true, uint16_t>), (int)((kRowBucketsBig + 1) * sizeof(uint32_t) + 16));
-    raise(reinterpret_cast<const void*>(&k_env_rows<1024, false, uint16_t>), 8192 * 10 + 16 + (kRowBucketsSmall + 1) * 4);
-    raise(reinterpret_cast<const void*>(&k_env_rows2<1024, 16, 1>), 16384 * 9 + 16 + (kRowBucketsSmall + 1) * 4);
-    raise(reinterpret_cast<const void*>(&k_env_rows2<1024, 10, 1>), 16384 * 9 + 16 + (kRowBucketsSmall + 1) * 4);
-    raise(reinterpret_cast<const void*>(&k_env_rows2<1024, 12, 2>), (int)kRowSegLds);
-    raise(reinterpret_cast<const void*>(&k_env_rows2<1024, 8, 1>), 8192 * 9 + 16 + (kRowBucketsSmall + 1) * 4);
+    auto raise = [](const void* fn, size_t bytes) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+    raise(reinterpret_cast<const void*>(&k_env_rows<1024, true>), (size_t)(kRowBucketsHuge + 1) * sizeof(uint32_t) + 16);
+    raise(reinterpret_cast<const void*>(&k_env_rows<1024, false>), rows_lds(kRowsLdsCap, 1));
+    raise(reinterpret_cast<const void*>(&k_env_rows<1024, true, uint16_t>), (size_t)(kRowBucketsBig + 1) * sizeof(uint32_t) + 16);
+    raise(reinterpret_cast<const void*>(&k_env_rows<1024, false, uint16_t>), rows_lds(kRowsLdsCap16, 2));
+    raise(reinterpret_cast<const void*>(&k_env_rows2<1024, 16, 1>), rows2_lds(kRows2OneSeg));
+    raise(reinterpret_cast<const void*>(&k_env_rows2<1024, 10, 1>), rows2_lds(kRows2OneSeg));
+    raise(reinterpret_cast<const void*>(&k_env_rows2<1024, 12, 2>), kRowSegLds);
+    raise(reinterpret_cast<const void*>(&k_env_rows2<1024, 8, 1>), rows2_lds(8192));
     (void)hipGetLastError();
 }
 

@@ -46,6 +46,8 @@ struct HostStatus {
     uint32_t n_overflow[2];  // DeviceStatus::n_overflow at the end of the record pass
     uint32_t max_bound;      // DeviceStatus::max_bound
     uint32_t n_dup_b;        // DeviceStatus::n_dup_b
+    uint32_t n_bitonic;      // DeviceStatus::n_bitonic
+    uint32_t pad2;
 };
 
 // Test / tuning hooks.  Read from the environment ONCE, when a context is created (lchd_ctx_create), and handed to the

@@ -103,6 +103,7 @@ __device__ __forceinline__ void publish_status(const SweepArgs& args, unsigned l
     h->n_overflow[1] = st->n_overflow[1];
     h->max_bound = __hip_atomic_load(&st->max_bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     h->n_dup_b = __hip_atomic_load(&st->n_dup_b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    h->n_bitonic = __hip_atomic_load(&st->n_bitonic, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     h->snapshot_seq = args.seq;
     st->flags = 0u;
     st->max_env = 0u;
@@ -110,6 +111,7 @@ __device__ __forceinline__ void publish_status(const SweepArgs& args, unsigned l
     st->n_overflow[1] = 0u;
     st->max_bound = 0u;
     st->n_dup_b = 0u;
+    st->n_bitonic = 0u;
 }
 
 // StatisticalDistance::run for Hellinger with a general exponent (statistical_distances.rs:4-10) and Renyi (:31-78) on the

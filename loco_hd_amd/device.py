@@ -27,6 +27,16 @@ def last_sweep_of(ctx):
     return rec
 
 
+def last_dense_of(ctx):
+    """lchd_ctx_last_dense of a context handle as a dict (DeviceSession.last_dense), or None."""
+    rec = N.DenseRecordC()
+    if N.lib().lchd_ctx_last_dense(ctx, C.byref(rec)) != 0:
+        return None
+    out = rec.plan.as_dict()
+    out.update(attempts=int(rec.attempts), canon=bool(rec.canon), n_bitonic=int(rec.n_bitonic))
+    return out
+
+
 def last_anchors_of(ctx):
     """lchd_ctx_last_anchors of a context handle as a list of two dicts (DeviceSession.last_anchors), or None."""
     sides = []
@@ -112,6 +122,13 @@ class DeviceSession:
         where none ran), "rule" (the rule in force: -1, 0, 1, 2) and "repeated" (the pass repeated one whose companion sweep had been
         left out); None where last_grid() returns None."""
         return last_sweep_of(self._ctx)
+
+    def last_dense(self):
+        """What the most recent from_coords / from_coords_ensemble call ran (lchd_ctx_last_dense): the fields of lchd_dense_plan for the
+        attempt whose scores stand ("path" is one of the _native.DENSE_* values, "rows" a list of two dicts) plus "attempts" (1, or 2: a
+        row defeated the first kernel and the call was repeated), "canon" (the tie-canonicalisation kernel ran) and "n_bitonic" (rows
+        whose sort took the bitonic network); None before the first dense call and after one that failed."""
+        return last_dense_of(self._ctx)
 
     def last_dense_fused(self) -> bool:
         """True if the most recent from_coords call ran the fused sort + sweep kernel (lchd_ctx_last_dense_fused)."""

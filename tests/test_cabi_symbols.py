@@ -15,7 +15,8 @@ def declared_functions():
 def test_header_declares_the_four_drivers():
     names = declared_functions()
     for fn in ("lchd_from_anchors", "lchd_from_dmxs", "lchd_from_coords", "lchd_from_primitives", "lchd_from_primitives_dev",
-               "lchd_ctx_create", "lchd_wf_cdf", "lchd_sd_run", "lchd_last_error"):
+               "lchd_ctx_create", "lchd_wf_cdf", "lchd_sd_run", "lchd_last_error", "lchd_plan_dense", "lchd_ctx_last_dense",
+               "lchd_ctx_last_dense_fused"):
         assert fn in names
 
 
