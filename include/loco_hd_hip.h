@@ -531,8 +531,8 @@ int lchd_attribution_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *
  * Row width: a call whose longest environment holds more than `width` points fails with LCHD_EVALUE (the message names the width it
  * takes) after one pass; lchd_sensitivity_needed_width then returns that width, and after a successful call the longest list.
  * Errors, stream and lock rules, capacity repeats and the untouched hints / lchd_ctx_last_sweep: as lchd_attribution_primitives(_dev).
- * Thresholded calls on the structures themselves only: no periodic boxes, cells or image clouds (LCHD_EUNSUPPORTED), no dense
- * (from_coords / from_dmxs) form, no device groups. */
+ * The thresholded calls take the structures themselves only: no periodic boxes, cells or image clouds (LCHD_EUNSUPPORTED).  The dense
+ * forms are the calls of their own below.  Device groups have no sensitivity call. */
 int lchd_sensitivity_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors, const int32_t *d_wf_index,
                                     int64_t n_pairs, double threshold_distance, int32_t width, double *d_scores, int32_t *d_count_a,
                                     int32_t *d_idx_a, double *d_dist_a, double *d_g_a, int32_t *d_count_b, int32_t *d_idx_b,
@@ -544,6 +544,31 @@ int lchd_sensitivity_primitives(lchd_ctx *ctx, const lchd_config *cfg, const dou
                                 double *scores, int32_t *count_a, int32_t *idx_a, double *dist_a, double *g_a, int32_t *count_b,
                                 int32_t *idx_b, double *dist_b, double *g_b);
 int64_t lchd_sensitivity_needed_width(lchd_ctx *ctx);
+/* Dense rows (lchd_attribution_coords_dev / _coords / _dmxs with the sensitivity outputs): pair r = row r of both sides, and EVERY column
+ * of a row is a member.  A dense row has no threshold, so no member enters or leaves: g is the whole derivative of the row's score with
+ * respect to the row's entries, for any weight function, away from ties (one-sided there).
+ *   - the list of a row is sorted ascending by (distance bits, column index) with NO forced anchor: slot 0 is the first of that order, the
+ *     reference's stable co-sort of the row with seq -- for coordinates atom r itself, unless an atom of lower index sits on the same point
+ *   - idx are column (atom) indices, count = cols of the side, dist the row's entries bit for bit (coordinates: the distances of
+ *     lchd_from_coords, bit-identical to rows computed in its operation order)
+ *   - `width` must reach max(cols_a, cols_b): a smaller one fails with LCHD_EVALUE before any pass; lchd_sensitivity_needed_width
+ *     reports that length either way
+ *   - rows are checked as the scoring calls check them (a negative or NaN entry, a row without a 0, a type outside the category map:
+ *     LCHD_EVALUE with the scoring call's message)
+ * Rows of up to LCHD_SENSITIVITY_ROWS_LDS_POINTS (padded) points are sorted in the LDS of one workgroup, longer ones (up to 65 535) in
+ * place in device memory.  No periodic cells, no ragged rows, no batches or image clouds. */
+#define LCHD_SENSITIVITY_ROWS_LDS_POINTS 8192
+int lchd_sensitivity_coords_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, int32_t width, double *d_scores,
+                                int32_t *d_count_a, int32_t *d_idx_a, double *d_dist_a, double *d_g_a, int32_t *d_count_b,
+                                int32_t *d_idx_b, double *d_dist_b, double *d_g_b);
+int lchd_sensitivity_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                            int64_t len_seq_b, const double *xyz_a, const double *xyz_b, int64_t n, const int32_t *wf_index, int32_t width,
+                            double *scores, int32_t *count_a, int32_t *idx_a, double *dist_a, double *g_a, int32_t *count_b,
+                            int32_t *idx_b, double *dist_b, double *g_b);
+int lchd_sensitivity_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                          int64_t len_seq_b, const double *dmx_a, const double *dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
+                          const int32_t *wf_index, int32_t width, double *scores, int32_t *count_a, int32_t *idx_a, double *dist_a,
+                          double *g_a, int32_t *count_b, int32_t *idx_b, double *dist_b, double *g_b);
 
 /* ---- cross-scoring (additive, not in the reference) ------------------------------------------------------
  * Every anchor of one list against every anchor of another: which environments of B look like this environment of A.

@@ -1017,6 +1017,113 @@ class LoCoHD:
         ga, gb = self._assemble_gradient(sens, _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3), pair_weights)
         return sens.scores, ga, gb
 
+    # ---- ... of dense rows (additive) ----------------------------------------------------------------------
+    # Row r of both sides, every column a member (include/loco_hd_hip.h, "Dense rows" under "neighbour sensitivities").  A dense row has
+    # no threshold: g is the whole derivative of the row's score with respect to the row's entries, for any weight function.
+    def _dense_sensitivity(self, name: str, seq_a, seq_b, a, b, w_func_keys, width, pair_weights=None, weighted=False):
+        """sensitivity_from_coords / sensitivity_from_dmxs (`name`) and the head of the two gradient calls: every check that needs no
+        device, then the call.  Returns (Sensitivity, the two inputs as arrays, pair_weights as an array or None)."""
+        if self._devices is not None:
+            raise NotImplementedError("a sensitivity call applies to one device (a device group has no sensitivity call): drop devices=[...]")
+        if name.endswith("coords"):
+            ma, mb = self._coords(a), self._coords(b)
+            if len(ma) != len(mb):
+                raise ValueError(f"Expected matrices with the same length, got lengths {len(ma)} and {len(mb)}!")
+            rows, cols = len(ma), (len(ma), len(mb))
+        else:
+            (ma, la), (mb, lb) = self._matrix(a), self._matrix(b)
+            if la is not None or lb is not None:
+                raise ValueError(f"{name} takes rectangular distance matrices (rows of equal length)")
+            if ma.shape[0] != mb.shape[0]:
+                raise ValueError(f"Expected matrices with the same length, got lengths {ma.shape[0]} and {mb.shape[0]}!")
+            rows, cols = ma.shape[0], (ma.shape[1], mb.shape[1])
+        if width is not None and int(width) < 1:
+            raise ValueError(f"width = {width}: a row holds at least one member")
+        v = None
+        if weighted:
+            v = np.ones(rows) if pair_weights is None else _f64(pair_weights).reshape(-1)
+            if len(v) != rows:
+                raise ValueError(f"pair_weights has {len(v)} entries for {rows} rows")
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], rows)
+        if len(self._weights) > 64:
+            raise NotImplementedError(f"a sensitivity call takes at most 64 categories (got {len(self._weights)})")
+        if max(cols) > 65535:
+            raise NotImplementedError(f"a sensitivity call takes dense rows of at most 65535 points (got {cols[0]} / {cols[1]})")
+        ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
+        cfg, keep = self._config()
+        k = max(cols) if width is None else int(width)
+        scores = np.empty(rows)
+        cnt = [np.empty(rows, dtype=np.int32) for _ in range(2)]
+        ix = [np.empty((rows, k), dtype=np.int32) for _ in range(2)]
+        ds = [np.empty((rows, k)) for _ in range(2)]
+        gs = [np.empty((rows, k)) for _ in range(2)]
+        if rows:
+            outs = (N.dp(scores), N.ip(cnt[0]), N.ip(ix[0]), N.dp(ds[0]), N.dp(gs[0]), N.ip(cnt[1]), N.ip(ix[1]), N.dp(ds[1]), N.dp(gs[1]))
+            head = (self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(ma), N.dp(mb))
+            if name.endswith("coords"):
+                N.check(N.lib().lchd_sensitivity_coords(*head, rows, N.ip(idx), k, *outs))
+            else:
+                N.check(N.lib().lchd_sensitivity_dmxs(*head, rows, cols[0], cols[1], N.ip(idx), k, *outs))
+        return Sensitivity(scores, cnt[0], ix[0], ds[0], gs[0], cnt[1], ix[1], ds[1], gs[1]), ma, mb, v
+
+    def sensitivity_from_dmxs(self, seq_a, seq_b, dmx_a, dmx_b, w_func_keys: Optional[Sequence[str]] = None, *,
+                              width: Optional[int] = None) -> Sensitivity:
+        """Additive: for every row pair `from_dmxs` would score (rectangular matrices with the same number of rows), the derivative of
+        its score with respect to every entry of the two rows, as a `Sensitivity`: row p is dense row p sorted by (distance, column) --
+        the reference's stable co-sort of the row with seq, no forced anchor -- `idx` the column indices, `dist` the entries,
+        `count` = the side's number of columns, `g` the derivatives (0 in slot 0).  Rows are max(cols_a, cols_b) wide, or `width`
+        (ValueError if that is smaller).  A dense row has no threshold, so the derivative is exact for any weight function away from
+        ties, and one-sided at ties.  Arguments and errors as `attribution_from_dmxs`; every statistical distance; no device groups."""
+        return self._dense_sensitivity("sensitivity_from_dmxs", seq_a, seq_b, dmx_a, dmx_b, w_func_keys, width)[0]
+
+    def sensitivity_from_coords(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None, *,
+                                width: Optional[int] = None) -> Sensitivity:
+        """Additive: `sensitivity_from_dmxs` on the rows `from_coords` scores (pair r: the two structures of equal size seen from
+        their atoms r).  `idx` are atom indices; slot 0 of row r is atom r, unless an atom of lower index sits on the same point.
+        Open structures only (no box / cell keywords)."""
+        return self._dense_sensitivity("sensitivity_from_coords", seq_a, seq_b, coords_a, coords_b, w_func_keys, width)[0]
+
+    @staticmethod
+    def _dense_scatter(idx: np.ndarray, values: np.ndarray, cols: int) -> np.ndarray:
+        """out[i][idx[i][k]] = values[i][k] for the members beyond slot 0 (0 elsewhere): sorted rows back into column order.  A column
+        occurs once per row, so every element has one writer."""
+        out = np.zeros((idx.shape[0], cols))
+        keep = idx >= 0
+        keep[:, :1] = False
+        r, _ = np.nonzero(keep)
+        out[r, idx[keep]] = values[keep]
+        return out
+
+    def gradient_from_dmxs(self, seq_a, seq_b, dmx_a, dmx_b, w_func_keys: Optional[Sequence[str]] = None, pair_weights=None):
+        """Additive: `(scores, G_a[rows, cols_a], G_b[rows, cols_b])` with G[i][j] = v_i dS_i / d dmx[i][j] in the input's column
+        order, v = `pair_weights` (default: ones): the gradient of a weighted sum of row scores with respect to the matrices
+        themselves, scattered from `sensitivity_from_dmxs`.  The slot-0 column of a row (its first zero) and non-finite derivatives
+        give 0.  Exact for any weight function (no threshold), one-sided at ties."""
+        sens, ma, mb, v = self._dense_sensitivity("gradient_from_dmxs", seq_a, seq_b, dmx_a, dmx_b, w_func_keys, None, pair_weights, True)
+        grads = [self._dense_scatter(idx, np.where(np.isfinite(g), v[:, None] * g, 0.0), m.shape[1])
+                 for idx, g, m in ((sens.idx_a, sens.g_a, ma), (sens.idx_b, sens.g_b, mb))]
+        return sens.scores, grads[0], grads[1]
+
+    @staticmethod
+    def _dense_coords_gradient(idx: np.ndarray, dist: np.ndarray, g: np.ndarray, v: np.ndarray, xyz: np.ndarray) -> np.ndarray:
+        """One side of gradient_from_coords: W = v g / d in column order (0 where d == 0), M = W + W^T, rowsum(M) x - M x."""
+        n = len(xyz)
+        use = (dist > 0.0) & np.isfinite(g)
+        w = LoCoHD._dense_scatter(idx,np.where(use, v[:, None] * g / np.where(use, dist, 1.0), 0.0), n)
+        m = w + w.T
+        return m.sum(axis=1)[:, None] * xyz - m @ xyz
+
+    def gradient_from_coords(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None, pair_weights=None):
+        """Additive: `(scores, grad_a[n, 3], grad_b[n, 3])` with grad = sum_r v_r dS_r / dx over the dense rows `from_coords` scores,
+        v = `pair_weights` (default: ones): the coordinate gradient of an all-atom LoCoHD loss.  Every atom is a member of every row
+        and there is no threshold, so this derivative is exact for any weight function; at ties (equal distances in a row pair) it is
+        one-sided.  Members at distance 0 contribute no direction.  Assembled on the host as one dense product: with W = v g / d in atom
+        order and M = W + W^T, grad = rowsum(M) x - M x."""
+        sens, xa, xb, v = self._dense_sensitivity("gradient_from_coords", seq_a, seq_b, coords_a, coords_b, w_func_keys, None, pair_weights,
+                                                  True)
+        return (sens.scores, self._dense_coords_gradient(sens.idx_a, sens.dist_a, sens.g_a, v, xa),
+                self._dense_coords_gradient(sens.idx_b, sens.dist_b, sens.g_b, v, xb))
+
     # ---- cross-scoring (additive) ---------------------------------------------------------------------------
     # Every anchor of one list against every anchor of another (include/loco_hd_hip.h, "cross-scoring"): the pair list is generated on the
     # device tile by tile, scored by the pass of from_primitives, and -- for nearest -- reduced to the k best columns per row there.

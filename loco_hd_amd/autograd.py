@@ -6,6 +6,10 @@
 Forward is DeviceSession.sensitivity, backward is DeviceSession.assemble_gradient with grad_output as the pair weights.  The derivative
 ignores points entering or leaving at the threshold (exact when the weight function's support ends at or inside it: the default, uniform
 [3, 10] with threshold 10) and is one-sided at ties.  The movable structure is uploaded from the host on every forward call.
+
+    scores = locohd_scores_dense(session, cloud_b_ref, xyz_a, cat_a)     # the dense rows of from_coords: no threshold, an exact derivative
+
+Forward is DeviceSession.sensitivity_coords, backward is side A of DeviceSession.gradient_coords (dense_side_gradient).
 """
 from __future__ import annotations
 
@@ -36,6 +40,37 @@ class _LoCoHDScores(torch.autograd.Function):
         s = ctx.sens
         grad_a = ctx.session.side_gradient(s.scores, s.idx_a, s.dist_a, s.g_a, x.to(torch.float64), grad_output)  # side A alone moves
         return grad_a.to(x.dtype), None, None, None, None, None, None
+
+
+class _LoCoHDScoresDense(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz_a, session, cloud_b_ref, cat_a, wf_index):
+        x = xyz_a.detach()
+        cloud_a = session.upload(x.cpu().numpy(), np.asarray(cat_a, dtype=np.int32))
+        try:
+            sens = session.sensitivity_coords(cloud_a, cloud_b_ref, wf_index=wf_index)
+        finally:
+            session._clouds.remove(cloud_a)
+            N.lib().lchd_cloud_destroy(session._ctx, cloud_a)
+        ctx.session = session
+        ctx.sens = sens
+        ctx.save_for_backward(x)
+        return sens.scores
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (x,) = ctx.saved_tensors
+        s = ctx.sens
+        grad_a = ctx.session.dense_side_gradient(s.idx_a, s.dist_a, s.g_a, x, grad_output)  # side A alone moves
+        return grad_a.to(x.dtype), None, None, None, None
+
+
+def locohd_scores_dense(session, cloud_b_ref, xyz_a, cat_a, wf_index=None):
+    """The scores of the dense rows (DeviceSession.sensitivity_coords: row r = both structures seen from their atoms r) of a movable
+    structure -- xyz_a: torch float64 CUDA tensor [n][3], cat_a: its category ids (host array) -- against `cloud_b_ref`, a structure of
+    the same size uploaded to `session`; differentiable with respect to xyz_a.  Backward is side A of DeviceSession.gradient_coords with
+    grad_output as the row weights: exact (no threshold), one-sided at ties."""
+    return _LoCoHDScoresDense.apply(xyz_a, session, cloud_b_ref, cat_a, wf_index)
 
 
 def locohd_scores(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, threshold_distance):

@@ -3658,7 +3658,7 @@ struct PairConsumer {
     const char* items;  // what its list holds: "anchors" / "anchor pairs"
     int sides;          // structures (stores) of a call, columns of its list: 1 composition, 2 the others
     bool records;       // its kernel reads the pair records of k_pair_meta (a dense pass carves them)
-    int width;          // > 0: a sensitivity call with rows of this many slots (thresholded calls only: it needs the cell lists)
+    int width;          // > 0: a sensitivity call with rows of this many slots
     SensitivityOut sens;  // ... and its DEVICE outputs, or all null: they are carved from the pass's one output block (sens_carve)
 };
 static const PairConsumer kComposition{{}, "a composition profile", "composition", "anchors", 1, false};
@@ -3704,8 +3704,13 @@ static int consumer_limits(const lchd_ctx* c, const PairConsumer& use) {
 }
 // The consumer's kernel behind a finished store build (stream order), with what hands the status over: the record pass (k_pair_meta)
 // in front of a pair kernel, launch_profile_publish behind the profile kernel.  sw: the stores, the list and its slots.
-// ix: a sensitivity call's indexed-list build (the prologue's cell lists and anchor records), launched behind the record pass.
-static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use, double* d_out, const IndexedArgs* ix = nullptr) {
+// A sensitivity call's indexed lists (c->d_indexed).  cells: the thresholded build from the prologue's cell lists and anchor records,
+// launched behind the record pass; null: the lists of dense rows, which launch_rows_indexed built in front of it.
+struct SensLists {
+    IndexedStore env[2];
+    const IndexedArgs* cells;
+};
+static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use, double* d_out, const SensLists* lists = nullptr) {
     const int n_wf = c->h_cfg.n_wf;
     hipStream_t s = c->stream;
     if (use.sides == 1) {
@@ -3721,15 +3726,14 @@ static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use,
     launch_pair_meta(s, sw);
     bool launched;
     if (use.width) {
-        if (!ix) return fail(LCHD_EUNSUPPORTED, "a sensitivity call takes thresholded environments (it needs the cell lists)");
         SensitivityArgs sa{};
         sa.sw = sw;
-        sa.env_a = ix->s[0].env;
-        sa.env_b = ix->s[1].max_envs > 0 ? ix->s[1].env : ix->s[0].env;  // (both sides one object: one set of lists)
+        sa.env_a = lists->env[0];
+        sa.env_b = lists->env[1];
         sa.n_categories = c->h_cfg.n_categories;
         sa.width = use.width;
         sa.out = use.sens.scores ? use.sens : sens_carve(d_out, sw.n_pairs, use.width);
-        launched = launch_env_indexed(s, *ix) && launch_sensitivity(s, sa);
+        launched = (!lists->cells || launch_env_indexed(s, *lists->cells)) && launch_sensitivity(s, sa);
     } else if (use.edges.n) {
         launch_radial_bounds(s, c->d_cfg, n_wf, use.edges, reinterpret_cast<double*>(c->d_radial_bounds));
         RadialArgs ra{};
@@ -3844,7 +3848,8 @@ static int consumer_prims_pass(lchd_ctx* c, const ConsumerRequest& R, int cap, u
             ix.s[k].uniq = sb[k]->uniq;
         }
     }
-    if (int rc = consumer_enqueue(c, sw, R.use, R.out, R.use.width ? &ix : nullptr)) return rc;
+    const SensLists lists{{ix.s[0].env, ix.s[1].max_envs > 0 ? ix.s[1].env : ix.s[0].env}, &ix};  // (both sides one object: one set of lists)
+    if (int rc = consumer_enqueue(c, sw, R.use, R.out, R.use.width ? &lists : nullptr)) return rc;
     mark(c, 4);
     for (int k = 0; k < sides; ++k)
         if (R.cl[k]->ev_used) { HIP_TRY(hipEventRecord(R.cl[k]->ev_used, s)); R.cl[k]->used_valid = true; }
@@ -3973,7 +3978,8 @@ static int consumer_primitives_host(lchd_ctx* c, const lchd_config* cfg, const P
 // Dense rows: entry r = row r of every side (composition: of the one structure).  Row r is the whole structure seen from atom r
 // (from_coords) or the given distance row r (from_dmxs).  d_m[k]: DEVICE rows [rows][cols[k]], or null: distances from the side's
 // coordinates, through the minimum-image row producer with a cell.  Every side goes through k_env_rows, which materialises the store
-// (the fused sort-and-sweep kernel never writes one).  All arrays: [use.sides].
+// (the fused sort-and-sweep kernel never writes one).  A sensitivity call also builds the indexed lists of both sides' rows
+// (launch_rows_indexed, from the same d_m or coordinates) for its kernel; the stores still feed the record pass.  All arrays: [use.sides].
 static int consumer_dense(lchd_ctx* c, const lchd_cloud* const* cl, const double* const* d_m_in, int64_t rows, const int64_t* cols,
                           const MinImageCell* const* cell, const int32_t* d_wf, const PairConsumer& use, double* d_out) {
     const int sides = use.sides;
@@ -3995,6 +4001,30 @@ static int consumer_dense(lchd_ctx* c, const lchd_cloud* const* cl, const double
         if (dry) if (int rc = ensure_ws(c, ar.off + 4096)) return rc;
     }
     for (int k = 0; k < sides; ++k) e[k].cdf_keys = n_wf == 1 ? 1 : 0;
+    // a sensitivity call: one indexed-list block per side, slots of the scoring stores' stride, in the block of the thresholded call
+    // (grow-only, outside the arena): 13 bytes per padded point and side
+    RowsIndexedArgs rx{};
+    if (use.width) {
+        size_t off[2][4], need = 0;
+        for (int k = 0; k < 2; ++k) {
+            const size_t pts = (size_t)rows * (size_t)cap[k];
+            const size_t bytes[4] = {4 * (size_t)rows, 8 * pts, 4 * pts, pts};  // len, dist, idx, cat
+            for (int j = 0; j < 4; ++j) { off[k][j] = need; need = (need + bytes[j] + 255) & ~size_t(255); }
+        }
+        if (int rc = grow_block(c->d_indexed, c->indexed_cap, need + 256)) return rc;
+        rx.cfg = c->d_cfg; rx.rows = rows; rx.st = c->d_status;
+        for (int k = 0; k < 2; ++k) {
+            RowsIndexedSide& S = rx.s[k];
+            S.c = cl[k]->view(cat16);
+            S.ld = cols[k];
+            S.cols = (int32_t)cols[k];
+            S.env.len = reinterpret_cast<int32_t*>(c->d_indexed + off[k][0]);
+            S.env.dist = reinterpret_cast<double*>(c->d_indexed + off[k][1]);
+            S.env.idx = reinterpret_cast<uint32_t*>(c->d_indexed + off[k][2]);
+            S.env.cat = reinterpret_cast<uint8_t*>(c->d_indexed + off[k][3]);
+            S.env.stride = cap[k];
+        }
+    }
     hipStream_t s = c->stream;
     if (int rc = begin_pass(c)) return rc;
     c->status_dirty = true;
@@ -4002,6 +4032,11 @@ static int consumer_dense(lchd_ctx* c, const lchd_cloud* const* cl, const double
     for (int k = 0; k < sides; ++k)
         if (cell[k]) { produce_rows(s, *cl[k], cols[k], rows, cell[k], w_m[k]); d_m[k] = w_m[k]; }
     mark(c, 1);
+    // (between events 1 and 2, which nothing else of a dense pass separates: lchd_ctx_last_ms "anchors" is the list build's time)
+    if (use.width) {
+        for (int k = 0; k < 2; ++k) rx.s[k].dmx = d_m[k];
+        if (!launch_rows_indexed(s, rx)) return fail(LCHD_EDEVICE, "internal error: the indexed-list kernel rejected its launch configuration");
+    }
     mark(c, 2);
     for (int k = 0; k < sides; ++k) {
         lchd_dense_rows_side side;
@@ -4025,7 +4060,8 @@ static int consumer_dense(lchd_ctx* c, const lchd_cloud* const* cl, const double
     sw.wf_index = d_wf;
     sw.n_pairs = rows;
     sw.meta = d_meta;
-    if (int rc = consumer_enqueue(c, sw, use, d_out)) return rc;
+    const SensLists lists{{rx.s[0].env, rx.s[1].env}, nullptr};
+    if (int rc = consumer_enqueue(c, sw, use, d_out, use.width ? &lists : nullptr)) return rc;
     mark(c, 4);
     HIP_TRY(hipGetLastError());
     c->status_dirty = false;
@@ -4038,7 +4074,16 @@ static int consumer_dense_check(lchd_ctx* c, const PairConsumer& use, const int6
     if (int rc = consumer_limits(c, use)) return rc;
     bool over = false;
     for (int k = 0; k < use.sides; ++k) over = over || cols[k] > kRadialMaxPoints;
-    if (!over) return LCHD_OK;
+    if (!over) {
+        if (!use.width) return LCHD_OK;
+        // every column is a member: the rows of a dense sensitivity call are as long as the longer side's
+        const int64_t longest = std::max(cols[0], cols[1]);
+        c->sens_needed = longest;
+        if (use.width < longest)
+            return fail(LCHD_EVALUE, "row width %d is too small: the longest row of these matrices holds %lld points (lchd_sensitivity_needed_width)",
+                        use.width, (long long)longest);
+        return LCHD_OK;
+    }
     char got[64];
     int len = 0;
     for (int k = 0; k < use.sides; ++k) len += snprintf(got + len, sizeof got - (size_t)len, k ? " / %lld" : "%lld", (long long)cols[k]);
@@ -4297,8 +4342,26 @@ extern "C" int lchd_attribution_dmxs(lchd_ctx* c, const lchd_config* cfg, const 
                            kAttribution, out);
 }
 
-// neighbour sensitivities: thresholded calls only (the kernels walk the pass's cell lists); every statistical distance.  The pass is the
-// attribution call's with the indexed lists and k_sensitivity (lchd_sensitivity.hip) behind the record pass.
+// neighbour sensitivities: every statistical distance.  The thresholded pass is the attribution call's with the indexed lists (built from
+// the pass's cell lists) and k_sensitivity (lchd_sensitivity.hip) behind the record pass; no periodic boxes, cells or image clouds.
+// A host call's pass writes ONE block (sens_carve), which `pass` receives; the nine HOST arrays of `o` are filled from it.
+template <class Pass>
+static int sens_host_call(int64_t n_pairs, int32_t width, const SensitivityOut& o, Pass&& pass) {
+    const size_t n = n_pairs > 0 ? (size_t)n_pairs : 0, nw = n * (size_t)width;
+    double* blk = n ? static_cast<double*>(malloc(sizeof(double) * n * (5 * (size_t)width + 2))) : nullptr;
+    if (n && !blk) return fail(LCHD_EUNSUPPORTED, "no host memory for the outputs of %lld pairs", (long long)n_pairs);
+    const int rc = pass(blk);
+    if (rc == LCHD_OK && n) {
+        const SensitivityOut b = sens_carve(blk, n_pairs, width);
+        memcpy(o.scores, b.scores, 8 * n);
+        memcpy(o.g_a, b.g_a, 8 * nw); memcpy(o.g_b, b.g_b, 8 * nw);
+        memcpy(o.dist_a, b.dist_a, 8 * nw); memcpy(o.dist_b, b.dist_b, 8 * nw);
+        memcpy(o.idx_a, b.idx_a, 4 * nw); memcpy(o.idx_b, b.idx_b, 4 * nw);
+        memcpy(o.count_a, b.count_a, 4 * n); memcpy(o.count_b, b.count_b, 4 * n);
+    }
+    free(blk);
+    return rc;
+}
 static int sens_args(lchd_ctx* c, int64_t n_pairs, int32_t width) {
     if (c) c->sens_needed = 0;
     if (width < 1 || width > kRadialMaxPoints) return fail(LCHD_EVALUE, "row width %d is outside 1 .. %d", width, kRadialMaxPoints);
@@ -4330,23 +4393,60 @@ extern "C" int lchd_sensitivity_primitives(lchd_ctx* c, const lchd_config* cfg, 
     if (int rc = sens_args(c, n_pairs, width)) return rc;
     if (n_pairs > 0 && (!scores || !count_a || !idx_a || !dist_a || !g_a || !count_b || !idx_b || !dist_b || !g_b))
         return fail(LCHD_EVALUE, "null output pointer");
-    const size_t n = n_pairs > 0 ? (size_t)n_pairs : 0, nw = n * (size_t)width;
-    double* blk = n ? static_cast<double*>(malloc(sizeof(double) * n * (5 * (size_t)width + 2))) : nullptr;
-    if (n && !blk) return fail(LCHD_EUNSUPPORTED, "no host memory for the outputs of %lld pairs", (long long)n_pairs);
-    const int rc = pair_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, nullptr, nullptr,
-                                        nullptr, nullptr, sensitivity_consumer(width, SensitivityOut{}), blk);
-    if (rc == LCHD_OK && n) {
-        const SensitivityOut o = sens_carve(blk, n_pairs, width);
-        memcpy(scores, o.scores, 8 * n);
-        memcpy(g_a, o.g_a, 8 * nw); memcpy(g_b, o.g_b, 8 * nw);
-        memcpy(dist_a, o.dist_a, 8 * nw); memcpy(dist_b, o.dist_b, 8 * nw);
-        memcpy(idx_a, o.idx_a, 4 * nw); memcpy(idx_b, o.idx_b, 4 * nw);
-        memcpy(count_a, o.count_a, 4 * n); memcpy(count_b, o.count_b, 4 * n);
-    }
-    free(blk);
-    return rc;
+    const SensitivityOut o{scores, count_a, count_b, idx_a, idx_b, dist_a, dist_b, g_a, g_b};
+    return sens_host_call(n_pairs, width, o, [&](double* blk) {
+        return pair_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, nullptr, nullptr,
+                                    nullptr, nullptr, sensitivity_consumer(width, SensitivityOut{}), blk);
+    });
 }
 extern "C" int64_t lchd_sensitivity_needed_width(lchd_ctx* c) { return c ? c->sens_needed : 0; }
+
+// ... and of dense rows: the attribution calls of the same name with the other consumer.  consumer_dense builds the indexed lists of
+// both sides' rows (launch_rows_indexed) next to the scoring stores, which stay in front of the record pass: its records, status
+// hand-over and checks are the attribution call's.  Every column is a member, so rows are max(cols_a, cols_b) wide at least.
+extern "C" int lchd_sensitivity_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, int32_t width, double* d_scores,
+                                           int32_t* d_count_a, int32_t* d_idx_a, double* d_dist_a, double* d_g_a, int32_t* d_count_b,
+                                           int32_t* d_idx_b, double* d_dist_b, double* d_g_b) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (int rc = sens_args(c, a->n, width)) return rc;
+    if (a->n > 0 && (!d_scores || !d_count_a || !d_idx_a || !d_dist_a || !d_g_a || !d_count_b || !d_idx_b || !d_dist_b || !d_g_b))
+        return fail(LCHD_EVALUE, "null output pointer");
+    if (a->images || b->images) return fail(LCHD_EUNSUPPORTED, "a sensitivity call takes the structures themselves, not periodic image clouds");
+    const SensitivityOut o{d_scores, d_count_a, d_count_b, d_idx_a, d_idx_b, d_dist_a, d_dist_b, d_g_a, d_g_b};
+    lchd_cloud* const cl[2] = {a, b};
+    const double* const cells[2] = {nullptr, nullptr};
+    return consumer_coords_dev(c, cl, d_wf_index, cells, sensitivity_consumer(width, o), d_scores);
+}
+extern "C" int lchd_sensitivity_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                       int64_t len_seq_b, const double* xyz_a, const double* xyz_b, int64_t n, const int32_t* wf_index,
+                                       int32_t width, double* scores, int32_t* count_a, int32_t* idx_a, double* dist_a, double* g_a,
+                                       int32_t* count_b, int32_t* idx_b, double* dist_b, double* g_b) {
+    if (int rc = coords_lengths(xyz_a, n, xyz_b, n)) return rc;
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = sens_args(c, n, width)) return rc;
+    if (n > 0 && (!scores || !count_a || !idx_a || !dist_a || !g_a || !count_b || !idx_b || !dist_b || !g_b))
+        return fail(LCHD_EVALUE, "null output pointer");
+    const SensitivityOut o{scores, count_a, count_b, idx_a, idx_b, dist_a, dist_b, g_a, g_b};
+    return sens_host_call(n, width, o, [&](double* blk) {
+        return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n, n, n, wf_index, nullptr, nullptr,
+                               sensitivity_consumer(width, SensitivityOut{}), blk);
+    });
+}
+extern "C" int lchd_sensitivity_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                     int64_t len_seq_b, const double* dmx_a, const double* dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
+                                     const int32_t* wf_index, int32_t width, double* scores, int32_t* count_a, int32_t* idx_a, double* dist_a,
+                                     double* g_a, int32_t* count_b, int32_t* idx_b, double* dist_b, double* g_b) {
+    if (rows > 0 && (!dmx_a || !dmx_b)) return fail(LCHD_EVALUE, "null pointer");
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = sens_args(c, rows, width)) return rc;
+    if (rows > 0 && (!scores || !count_a || !idx_a || !dist_a || !g_a || !count_b || !idx_b || !dist_b || !g_b))
+        return fail(LCHD_EVALUE, "null output pointer");
+    const SensitivityOut o{scores, count_a, count_b, idx_a, idx_b, dist_a, dist_b, g_a, g_b};
+    return sens_host_call(rows, width, o, [&](double* blk) {
+        return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr,
+                               nullptr, sensitivity_consumer(width, SensitivityOut{}), blk);
+    });
+}
 
 // ------------------------------------------------------------------------------------------------
 // cross-scoring: all anchors of one list against all anchors of another, in row tiles (include/loco_hd_hip.h, "cross-scoring")

@@ -475,6 +475,30 @@ struct IndexedArgs {
     const DeviceStatus* st;  // n_unique: the slots in use
 };
 bool launch_env_indexed(hipStream_t s, const IndexedArgs& a);  // false: nothing launched (a stride that is no power of two)
+// The indexed lists of DENSE rows (k_rows_indexed): slot r of a side = row r of its distance matrix (given rows, or distances from the
+// side's coordinates in the expression of k_env_rows), every column a member, sorted ascending by (distance bits, column index) -- the
+// reference's stable co-sort of a row with seq (utils.rs:25-39).  No forced anchor: slot 0 is the first of that order.  The row checks
+// are k_env_rows' (ST_BAD_DISTANCE, ST_FIRST_NOT_ZERO, ST_BAD_CATEGORY into DeviceStatus::flags: launch it in front of the record pass).
+// Rows of at most kRowsIdxLdsPoints (padded) points are sorted in LDS, 12 bytes per point -- only (key, column) pairs travel through
+// the sort, the category is gathered from the column behind it -- longer ones, up to kRadialMaxPoints, in place in the list block.  The
+// in-place path is a correctness path: every compare-exchange of the network goes through L2.  Measured on the MI355X (512 rows a side):
+// 0.127 ns per point at the capacity, 0.498 ns one point over it -- 3.9x, of which 2.3x is the network of the next power of two -- and
+// 0.352 ns at 16 384 points: well inside an order of magnitude ("Dense sensitivities").
+constexpr int kRowsIdxLdsPoints = LCHD_SENSITIVITY_ROWS_LDS_POINTS;  // 8192: 96 KB of the 160 KB of a CU (the public header exports it)
+struct RowsIndexedSide {
+    CloudView c;          // categories (and coordinates when dmx == nullptr)
+    const double* dmx;    // DEVICE rows [rows][ld], or nullptr: distances from the coordinates of c (row r seen from atom r)
+    int64_t ld;
+    int32_t cols;         // points of every row, 1 .. kRadialMaxPoints
+    IndexedStore env;     // [rows] slots of `stride` points, stride a power of two >= cols
+};
+struct RowsIndexedArgs {
+    const DevConfig* cfg;
+    RowsIndexedSide s[2];
+    int64_t rows;         // of each side: workgroups [0, rows) build side A, the rest side B
+    DeviceStatus* st;
+};
+bool launch_rows_indexed(hipStream_t s, const RowsIndexedArgs& a);  // false: nothing launched (a stride that is no power of two or below cols)
 struct SensitivityOut {      // all DEVICE; K = SensitivityArgs::width
     double* scores;          // [P]
     int32_t *count_a, *count_b;        // [P] members incl. the anchor (0: an unusable pair)

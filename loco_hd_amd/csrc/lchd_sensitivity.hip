@@ -15,6 +15,8 @@
 //                   point, sorted ascending by (distance bits, atom index) with the anchor first -- one defined order among ties,
 //                   whatever order the appends took.  Same cell walk, distance expression, threshold comparison and tag rule as
 //                   k_env_cells (env_dist2 / env_accepts below are those lines; tag_pair_accepted and cell_coord are lchd_kcommon.h's).
+//   k_rows_indexed  the same lists for DENSE rows (from_coords / from_dmxs): every column of row r a member, sorted by (distance bits,
+//                   column index) with no forced anchor; a dense row has no threshold, so dS/dd is the whole derivative away from ties
 //   k_sensitivity   k_attribution's shape (lchd_attribution.hip): one pair per wavefront, tiles of kSweepTile merged events (merge path
 //                   on the distance bits, A first on ties), a wave scan of the per-lane category histograms for the counts at each
 //                   lane's first event, then every lane walks its events.  Per event it evaluates H on the counts behind the event
@@ -187,6 +189,123 @@ bool launch_env_indexed(hipStream_t s, const IndexedArgs& a) {
                                                             a.s[1].max_envs > 0 ? a.s[1].n : 0, a.s[1].atom_of);
     if (a.tag_list) k_env_indexed<true><<<(unsigned)blocks, 256, 0, s>>>(a);
     else k_env_indexed<false><<<(unsigned)blocks, 256, 0, s>>>(a);
+    return true;
+}
+
+// ---- indexed lists of dense rows -----------------------------------------------------------------------------------------------------
+// bitonic sort of n2 (a power of two) pairs by (key, sec); pads carry (kPadKey, ~0u)
+template <int NT>
+__device__ __forceinline__ void bitonic_sort_pairs(uint64_t* key, uint32_t* sec, int n2, int tid) {
+    for (int k = 2; k <= n2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (n2 >> 1); t += NT) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int l = i | j;
+                const bool up = ((i & k) == 0);
+                const uint64_t a = key[i], b = key[l];
+                const uint32_t sa = sec[i], sb = sec[l];
+                const bool a_gt = a > b || (a == b && sa > sb), a_lt = a < b || (a == b && sa < sb);
+                if (up ? a_gt : a_lt) {
+                    key[i] = b; key[l] = a;
+                    sec[i] = sb; sec[l] = sa;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// One 256-thread workgroup per row; workgroups [0, rows) build side A, the rest side B.  Dynamic LDS (all of the kernel's: the base
+// stays 16-byte aligned): keys [n2] | columns [n2] of a row sorted in LDS, nothing for a row sorted in place.
+__global__ __launch_bounds__(256) void k_rows_indexed(RowsIndexedArgs ra) {
+    constexpr int NT = 256;
+    extern __shared__ __attribute__((aligned(16))) unsigned char rows_smem[];
+    const int side = (int64_t)blockIdx.x >= ra.rows ? 1 : 0;
+    const RowsIndexedSide& S = ra.s[side];
+    const int64_t r = (int64_t)blockIdx.x - (side ? ra.rows : 0);
+    const int tid = threadIdx.x;
+    const int n = S.cols, n2 = next_pow2(n);  // n2 <= stride: the launcher takes power-of-two strides of at least cols
+    const CloudView& c = S.c;
+    uint64_t* const gk = reinterpret_cast<uint64_t*>(S.env.dist) + r * S.env.stride;
+    uint32_t* const gi = S.env.idx + r * S.env.stride;
+    uint8_t* const gc = S.env.cat + r * S.env.stride;
+    const double* __restrict__ row = S.dmx ? S.dmx + r * S.ld : nullptr;
+    double ax = 0.0, ay = 0.0, az = 0.0;
+    if (!row) { ax = c.x[r]; ay = c.y[r]; az = c.z[r]; }
+    bool bad = false, bad_c = false;
+    // k_env_rows' distance: a given entry with its check (negative or NaN: reported, counted as 0; -0.0 -> +0.0), or the root of the
+    // squared distance in utils.rs:1-8 order, uncontracted
+    auto dist_of = [&](int i) -> double {
+        if (row) {
+            double v = row[i];
+            if (!(v >= 0.0)) { bad = true; v = 0.0; }
+            return v + 0.0;
+        }
+        const double dx = ax - c.x[i], dy = ay - c.y[i], dz = az - c.z[i];
+        double d2 = dx * dx;
+        d2 = d2 + dy * dy;
+        d2 = d2 + dz * dz;
+        return sqrt(d2);
+    };
+    const int C = ra.cfg->n_categories;
+    uint64_t first;
+    if (n2 <= kRowsIdxLdsPoints) {
+        uint64_t* const key = reinterpret_cast<uint64_t*>(rows_smem);
+        uint32_t* const sec = reinterpret_cast<uint32_t*>(rows_smem + (size_t)n2 * 8);
+        for (int i = tid; i < n2; i += NT) {
+            key[i] = i < n ? d2u(dist_of(i)) : kPadKey;
+            sec[i] = i < n ? (uint32_t)i : ~0u;
+        }
+        __syncthreads();
+        bitonic_sort_pairs<NT>(key, sec, n2, tid);
+        for (int i = tid; i < n; i += NT) {  // (the n real pairs sort in front of every pad: a column index is below ~0u)
+            const uint32_t col = sec[i];
+            const uint8_t ct = c.cat[col];
+            bad_c |= (int)ct >= C;
+            gk[i] = key[i];
+            gi[i] = col;
+            gc[i] = ct;
+        }
+        first = key[0];
+    } else {
+        for (int i = tid; i < n2; i += NT) {
+            gk[i] = i < n ? d2u(dist_of(i)) : kPadKey;
+            gi[i] = i < n ? (uint32_t)i : ~0u;
+        }
+        __syncthreads();
+        bitonic_sort_pairs<NT>(gk, gi, n2, tid);
+        for (int i = tid; i < n; i += NT) {
+            const uint8_t ct = c.cat[gi[i]];
+            bad_c |= (int)ct >= C;
+            gc[i] = ct;
+        }
+        first = gk[0];
+    }
+    if (tid == 0) {
+        S.env.len[r] = n;
+        if (first != 0ull) atomicOr(&ra.st->flags, ST_FIRST_NOT_ZERO);  // src/locohd.rs:74-77, on the distance
+    }
+    const unsigned long long any_bad = __ballot(bad), any_bad_c = __ballot(bad_c);
+    if ((tid & 63) == 0) {
+        if (any_bad) atomicOr(&ra.st->flags, ST_BAD_DISTANCE);
+        if (any_bad_c) atomicOr(&ra.st->flags, ST_BAD_CATEGORY);
+    }
+}
+
+bool launch_rows_indexed(hipStream_t s, const RowsIndexedArgs& a) {
+    const int64_t blocks = 2 * a.rows;
+    if (a.rows <= 0) return true;
+    size_t lds = 0;
+    for (int k = 0; k < 2; ++k) {
+        const int64_t st = a.s[k].env.stride;
+        const int cols = a.s[k].cols;
+        if (st < 1 || st > kRadialMaxPoints + 1 || (st & (st - 1)) || cols < 1 || cols > st || cols > kRadialMaxPoints) return false;
+        if (a.s[k].c.n < cols || (!a.s[k].dmx && a.s[k].c.n < a.rows)) return false;  // (a category per column, coordinates per row)
+        const size_t n2 = (size_t)next_pow2_host(cols);
+        if (n2 <= (size_t)kRowsIdxLdsPoints) lds = std::max(lds, n2 * 12);
+    }
+    if (blocks > 0x7FFFFFFF) return false;
+    k_rows_indexed<<<(unsigned)blocks, 256, lds, s>>>(a);
     return true;
 }
 
@@ -408,6 +527,7 @@ void init_sensitivity_kernels() {
     const void* list[] = {reinterpret_cast<const void*>(&k_sensitivity<4>), reinterpret_cast<const void*>(&k_sensitivity<2>),
                           reinterpret_cast<const void*>(&k_sensitivity<1>)};
     for (const void* fn : list) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kSensDynMax);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows_indexed), hipFuncAttributeMaxDynamicSharedMemorySize, kRowsIdxLdsPoints * 12);
     (void)hipGetLastError();
 }
 

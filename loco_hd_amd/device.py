@@ -473,6 +473,58 @@ class DeviceSession:
         grad.index_add_(0, anchor.reshape(-1), -step.reshape(-1, 3))
         return grad
 
+    def sensitivity_coords(self, cloud_a, cloud_b, out=None, wf_index=None, *, width=None):
+        """Neighbour sensitivities of the dense row pairs of two uploaded structures of equal size (LoCoHD.sensitivity_from_coords; no
+        batches, no image clouds).  wf_index: torch int32 CUDA tensor [n] or None.  Returns a `Sensitivity` of torch CUDA tensors as
+        `sensitivity` does, row r the whole structure seen from atom r sorted by (distance, atom index): K = `width`, or the width of
+        `out` (a `Sensitivity` of such tensors, filled and returned), or n; ValueError if K < n (lchd_sensitivity_coords_dev)."""
+        torch = self.torch
+        n = int(N.lib().lchd_cloud_size(cloud_a))
+        wf_ptr = None
+        if wf_index is not None:
+            assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= n
+            wf_ptr = C.c_void_p(wf_index.data_ptr())
+        if width is not None and int(width) < 1:
+            raise ValueError(f"width = {width}: a row holds at least one member")
+        k = int(out.idx_a.shape[1]) if out is not None else (n if width is None else int(width))
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)  # noqa: E731
+            i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)  # noqa: E731
+            out = Sensitivity(f64(n), i32(n), i32(n, k), f64(n, k), f64(n, k), i32(n), i32(n, k), f64(n, k), f64(n, k))
+        else:
+            for name, t in zip(Sensitivity._fields, out):
+                want = torch.int32 if name.startswith(("count", "idx")) else torch.float64
+                rows = (n,) if name in ("scores", "count_a", "count_b") else (n, k)
+                assert t.is_cuda and t.dtype == want and t.is_contiguous() and tuple(t.shape) == rows, name
+        if n:
+            N.check(N.lib().lchd_sensitivity_coords_dev(self._ctx, cloud_a, cloud_b, wf_ptr, k, *[C.c_void_p(t.data_ptr()) for t in out]))
+        return out
+
+    def gradient_coords(self, cloud_a, cloud_b, xyz_a, xyz_b, pair_weights=None, wf_index=None):
+        """`(scores, grad_a[n, 3], grad_b[n, 3])` with grad = sum_r v_r dS_r/dx over the dense rows (LoCoHD.gradient_from_coords) as
+        torch CUDA tensors: exact (a dense row has no threshold), one-sided at ties.  xyz_a / xyz_b: the coordinates of the two clouds
+        as torch float64 CUDA tensors [n][3]; pair_weights: v, a tensor [n] (default: ones).  Assembled from `sensitivity_coords` as one
+        dense product (`dense_side_gradient`): no index_add_, so the bits do not depend on torch's determinism setting."""
+        sens = self.sensitivity_coords(cloud_a, cloud_b, wf_index=wf_index)
+        return (sens.scores, self.dense_side_gradient(sens.idx_a, sens.dist_a, sens.g_a, xyz_a, pair_weights),
+                self.dense_side_gradient(sens.idx_b, sens.dist_b, sens.g_b, xyz_b, pair_weights))
+
+    def dense_side_gradient(self, idx, dist, g, xyz, pair_weights=None):
+        """One side of gradient_coords, [n][3] f64: W = v g / d scattered into atom order (every atom occurs once per row: one writer
+        per element; 0 in slot 0, where d == 0 and where g is not finite), M = W + W^T, grad = rowsum(M) x - M x."""
+        torch = self.torch
+        n = xyz.shape[0]
+        idx, dist, g = idx[:, :n], dist[:, :n], g[:, :n]  # (a wider row: the padding goes)
+        x = xyz.to(torch.float64)
+        v = torch.ones(n, dtype=torch.float64, device=x.device) if pair_weights is None else pair_weights.to(torch.float64).reshape(-1)
+        use = (idx >= 0) & (dist > 0.0) & torch.isfinite(g)
+        use[:, 0] = False
+        coef = torch.where(use, v[:, None] * g / torch.where(use, dist, torch.ones_like(dist)), torch.zeros_like(g))
+        w = torch.zeros((n, n), dtype=torch.float64, device=x.device).scatter_(1, idx.long(), coef)
+        m = w + w.t()
+        return m.sum(dim=1)[:, None] * x - m @ x
+
     def attribution_coords(self, cloud_a, cloud_b, out=None, wf_index=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None):
         """Score attribution by category of the dense row pairs of two uploaded structures of equal size
         (LoCoHD.attribution_from_coords): returns (or fills) a torch float64 CUDA tensor [n][C] (lchd_attribution_coords_dev)."""
