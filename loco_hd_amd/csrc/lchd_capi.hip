@@ -185,17 +185,6 @@ struct lchd_cloud {
 
 enum { PH_CELLS = 0, PH_ANCHORS = 1, PH_ENV = 2, PH_SWEEP = 3, PH_N = 4 };
 
-// The periodic cells of a dense call (lchd_from_coords_periodic*, lchd_ensemble_from_coords_periodic*).  A periodic entry reduces its
-// cells, hangs this on the context (lchd_ctx::min_image) and makes the open call; dense_pass and ensemble_core then take every
-// structure's distance rows from launch_min_image_rows instead of the coordinates.  Null outside such a call.
-struct MinImage {
-    MinImageCell side[2];           // single pair: the cells of A and B; ensembles with one cell for all structures: side[0]
-    bool on[2] = {false, false};    // single pair: the side is periodic
-    const double* d_recs = nullptr; // ensembles with a cell per structure: DEVICE [M][kMinImageRecord]
-    int32_t n_cells = 0;            // ensembles: 1 or M
-    bool all_diagonal = false;      // ensembles: every cell is diagonal
-};
-
 // What lchd_ctx_last_grid reports about one side of a pass: the planned grid and which cell-list build launch_prologue picked.
 struct GridRecord {
     int32_t dim[3] = {0, 0, 0};
@@ -269,7 +258,6 @@ struct lchd_ctx {
     size_t io_cap = 0;
     std::vector<char> cfg_blob_host;  // last configuration blob uploaded (identical configurations are not uploaded again)
     PassHints hints{};  // what the thresholded passes of this context looked like so far (lchd_pass_plan.h): plan_pass and launch_sweep read it
-    const MinImage* min_image = nullptr;  // set for the duration of a periodic dense call
     lchd_dense_record last_dense{};  // what the most recent dense call ran (lchd_ctx_last_dense): plan of the attempt that stood, attempts, canon, bitonic rows
     bool last_dense_valid = false;   // ... and whether it ran to its end
     int64_t n_per_pair_passes = 0;  // passes whose side B was not de-duplicated (PassPlan::per_pair)
@@ -2747,18 +2735,82 @@ static EnvStore carve_row_store(Arena& ar, int64_t rows, int64_t cap, size_t set
     e.cat16 = cat16 ? 1 : 0;
     return e;
 }
-// One side's distance rows from its coordinates into w [rows][n]: minimum-image distances with a cell, else the open ones
-// (k_ens_dist's arithmetic).
-static void produce_rows(hipStream_t s, const lchd_cloud& cl, int64_t n, int64_t rows, const MinImageCell* cell, double* w) {
-    if (cell) launch_min_image_rows(s, cl.view(false), 0, (int32_t)n, rows, *cell, nullptr, cell->v[18] != 0.0, nullptr, nullptr, w);
-    else launch_ens_dist(s, cl.view(false), 0, (int32_t)n, rows, nullptr, nullptr, w);
+// Where one side's dense rows come from: the side's cloud as the row kernels read it, its row length, and exactly ONE way to the rows.
+// Every dense host pass (dense_pass, consumer_dense, ensemble_core) describes its sides with this and materialises them with the pair
+// take_rows / produce_rows below; a periodic cell travels here and nowhere else.
+struct RowSource {
+    enum Kind {
+        COORDS,       // open coordinates: the row kernels read them, or (as_rows) k_ens_dist writes the rows out
+        CELL,         // coordinates in a periodic cell: minimum-image rows
+        DEVICE_ROWS,  // m: DEVICE [..][cols], passed through
+        HOST_ROWS     // m: HOST [..][cols], copied into the workspace
+    } kind;
+    CloudView view;         // categories; the coordinates of COORDS / CELL
+    int64_t cols;
+    double bound;           // coordinates read by a row kernel: >= the largest squared distance (diag2), or 0.0
+    bool as_rows;           // COORDS in a pass that runs in its given-row form (the other side has a cell; every ensemble)
+    const double* m;
+    MinImageCell cell;      // CELL: the cell of every structure, or ...
+    const double* d_cells;  // ... ensembles with a cell per structure: DEVICE [M][kMinImageRecord]
+    bool all_diagonal;      // CELL: every cell is diagonal
+    const int32_t* d_len;   // ragged given rows: DEVICE [rows] points of each row, or null
+    const int32_t *excl_start, *excl_idx;  // ensembles: DEVICE CSR of excluded columns per row, or null
+};
+// A single structure's coordinates (or, with `m` set afterwards, its categories alone), optionally in a reduced periodic cell.
+static RowSource cloud_source(const lchd_cloud& cl, bool cat16, int64_t cols, const MinImageCell* cell = nullptr) {
+    RowSource s{};
+    s.kind = cell ? RowSource::CELL : RowSource::COORDS;
+    s.view = cl.view(cat16);
+    s.cols = cols;
+    s.bound = diag2(cl);
+    if (cell) { s.cell = *cell; s.all_diagonal = cell->v[18] != 0.0; }
+    return s;
+}
+static bool reads_rows(const RowSource& s) { return s.kind != RowSource::COORDS || s.as_rows; }  // (else: the row kernels read the coordinates)
+// What a source needs from the arena for `rows` rows: nothing for rows on the device and coordinates read in place.
+static double* take_rows(Arena& ar, const RowSource& s, int64_t rows) {
+    return reads_rows(s) && s.kind != RowSource::DEVICE_ROWS ? ar.take<double>((size_t)rows * s.cols) : nullptr;
+}
+// Enqueues the copy or the producer of rows [row0, row0 + rows) into w (take_rows); d_m: what the row kernels read, null for "the
+// coordinates".  row0 is also the first atom (a regular batch: row k * cols + r is atom r of structure k).  Open rows have k_ens_dist's
+// arithmetic.  The only caller of the two row producers.
+static int produce_rows(lchd_ctx* c, const RowSource& s, int64_t row0, int64_t rows, double* w, const double*& d_m) {
+    d_m = w;
+    switch (s.kind) {
+    case RowSource::DEVICE_ROWS: d_m = s.m + row0 * s.cols; break;
+    case RowSource::HOST_ROWS:
+        HIP_TRY(hipMemcpyAsync(w, s.m + row0 * s.cols, sizeof(double) * (size_t)rows * s.cols, hipMemcpyHostToDevice, c->stream));
+        break;
+    case RowSource::CELL:
+        launch_min_image_rows(c->stream, s.view, row0, (int32_t)s.cols, rows, s.cell, s.d_cells, s.all_diagonal, s.excl_start, s.excl_idx, w);
+        break;
+    case RowSource::COORDS:
+        if (s.as_rows) launch_ens_dist(c->stream, s.view, row0, (int32_t)s.cols, rows, s.excl_start, s.excl_idx, w);
+        break;
+    }
+    return LCHD_OK;
+}
+// The row sort of a store-building pass: row r of every side into slot r of its store -- the plan's one k_env_rows2 launch for both
+// sides, or one k_env_rows launch per side (plan.rows) -- then, in deterministic mode, one order among equal keys (a row's sort places
+// ties by LDS-atomic order).  false: the plan names no instantiation of its kernel; *canon: whether k_env_canon ran.
+static bool sort_rows(lchd_ctx* c, const lchd_dense_plan& plan, int sides, const RowSource* src, const double* const* d_m, const EnvStore* e,
+                      int64_t rows, int32_t* canon) {
+    hipStream_t s = c->stream;
+    if (plan.path == LCHD_DENSE_ROWS2) {
+        const RowSide a{src[0].view, d_m[0], src[0].cols, src[0].cols, src[0].bound, e[0], src[0].d_len};
+        const RowSide b{src[1].view, d_m[1], src[1].cols, src[1].cols, src[1].bound, e[1], src[1].d_len};
+        if (!launch_env_rows2(s, plan, c->d_cfg, a, b, rows, c->d_status)) return false;
+    } else {
+        for (int k = 0; k < sides; ++k)
+            if (!launch_env_rows(s, plan.rows[k], c->d_cfg, src[k].view, d_m[k], src[k].cols, rows, src[k].cols, src[k].bound, e[k], c->d_status,
+                                 RowExtras{nullptr, src[k].d_len, nullptr}))
+                return false;
+    }
+    *canon = c->deterministic ? 1 : 0;
+    if (c->deterministic) launch_env_canon(s, e[0], e[sides - 1], rows, rows * (sides - 1), nullptr);  // (one side: no rows of a second store)
+    return true;
 }
 
-// One dense pass (from_coords / from_dmxs semantics: pair r = row r of A against row r of B, the environment is the whole
-// structure): row sort of both structures, sweep.  a / b: device-resident structures (coordinates used unless d_ma / d_mb,
-// DEVICE pointers to given distance rows, are set); d_wf: device weight-function indices or nullptr; d_out: device or
-// host-mapped scores.  `attempt`: 0, or 1 for the repeat of a call; `retry` reports that a row defeated this attempt's kernel (the fused
-// kernel, the segmented in-LDS sort): repeat with attempt 1.  The attempt's plan, canon flag and bitonic rows go into c->last_dense.
 static lchd_dense_query dense_query(const lchd_ctx* c, int64_t cols_a, int64_t cols_b, bool given_rows, bool ragged, int attempt, bool single_attempt) {
     lchd_dense_query q{};
     q.cols_a = cols_a;
@@ -2774,23 +2826,22 @@ static lchd_dense_query dense_query(const lchd_ctx* c, int64_t cols_a, int64_t c
     q.single_attempt = single_attempt ? 1 : 0;
     return q;
 }
-static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, const double* d_ma, const double* d_mb, int64_t rows,
-                      int64_t cols_a, int64_t cols_b, const int32_t* d_wf, double* d_out, int attempt, bool& retry,
-                      const double* h_ma = nullptr, const double* h_mb = nullptr, const int32_t* d_len_a = nullptr,
-                      const int32_t* d_len_b = nullptr) {
+// One dense pass (from_coords / from_dmxs semantics: pair r = row r of A against row r of B, the environment is the whole structure):
+// row sort of both structures, sweep.
+struct DensePass {
+    RowSource src[2];
+    int64_t rows;
+    const int32_t* d_wf;  // DEVICE weight-function indices or null
+    double* d_out;        // device or host-mapped scores
+};
+// `attempt`: 0, or 1 for the repeat of a call; `retry` reports that a row defeated this attempt's kernel (the fused kernel, the
+// segmented in-LDS sort): repeat with attempt 1.  The attempt's plan, canon flag and bitonic rows go into c->last_dense.
+static int dense_pass(lchd_ctx* c, const DensePass& P, int attempt, bool& retry) {
     retry = false;
-    // a periodic dense call: both structures' rows are materialised in the workspace (an open side with k_ens_dist's arithmetic) and
-    // the pass runs in its given-row form
-    const MinImage* mi = (!d_ma && !d_mb && !h_ma && !h_mb) ? c->min_image : nullptr;
-    auto produce_both = [&](double* w_a, double* w_b) {
-        mark(c, 0);
-        produce_rows(c->stream, a, cols_a, rows, mi->on[0] ? &mi->side[0] : nullptr, w_a);
-        produce_rows(c->stream, b, cols_b, rows, mi->on[1] ? &mi->side[1] : nullptr, w_b);
-        mark(c, 1);
-    };
-    const int cap_a = next_pow2_host(cols_a), cap_b = next_pow2_host(cols_b);
+    const RowSource *src = P.src, &a = P.src[0], &b = P.src[1];
+    const int64_t rows = P.rows;
     c->last_dense_valid = false;
-    const lchd_dense_query query = dense_query(c, cols_a, cols_b, d_ma || h_ma || mi, d_len_a || d_len_b, attempt, false);
+    const lchd_dense_query query = dense_query(c, a.cols, b.cols, reads_rows(a), a.d_len || b.d_len, attempt, false);
     const lchd_dense_plan plan = plan_dense(query);
     if (plan.unsupported) return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
     const bool cat16 = query.cat16 != 0;
@@ -2800,48 +2851,47 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
     c->last_dense.n_bitonic = 0;
     // The common configuration (plan_dense: Hellinger-2, unit category weights, <= 16 categories, rows of 1025 .. kDenseFusedMaxRow points): sort and
     // sweep in ONE kernel per row pair, nothing but the score is written (lchd_dense_fused.hip).  No environment store.
-    if (plan.path == LCHD_DENSE_FUSED) {
-        double* w_ma2 = nullptr;
-        double* w_mb2 = nullptr;
-        uint64_t* scr_key = nullptr;
-        uint8_t* scr_val = nullptr;
-        int32_t scr_grid = 0;
-        const int32_t scr_segs = plan.scr_segs;
-        const size_t scr_n = dense_fused_scratch(rows, scr_segs, &scr_grid);
-        for (int dry = 1; dry >= 0; --dry) {
-            Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
+    const bool fused = plan.path == LCHD_DENSE_FUSED;
+    uint64_t* scr_key = nullptr;
+    uint8_t* scr_val = nullptr;
+    int32_t scr_grid = 0;
+    const size_t scr_n = fused ? dense_fused_scratch(rows, plan.scr_segs, &scr_grid) : 0;
+    EnvStore e[2] = {};
+    int4* d_meta = nullptr;
+    double* w[2] = {nullptr, nullptr};
+    for (int dry = 1; dry >= 0; --dry) {
+        Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
+        if (fused) {
             scr_key = ar.take<uint64_t>(scr_n);  // the distance pass's (key, value) pairs, one region per workgroup
             scr_val = ar.take<uint8_t>(scr_n);
-            if (h_ma || mi) {
-                w_ma2 = ar.take<double>((size_t)rows * cols_a);
-                w_mb2 = ar.take<double>((size_t)rows * cols_b);
-            }
-            if (dry) if (int rc2 = ensure_ws(c, ar.off + 4096)) return rc2;
+        } else {
+            for (int k = 0; k < 2; ++k) e[k] = carve_row_store(ar, rows, next_pow2_host(src[k].cols), 1, cat16);  // (scoring: one key set)
+            d_meta = ar.take<int4>((size_t)rows);
         }
-        if (h_ma) {
-            HIP_TRY(hipMemcpyAsync(w_ma2, h_ma, sizeof(double) * rows * cols_a, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(w_mb2, h_mb, sizeof(double) * rows * cols_b, hipMemcpyHostToDevice, c->stream));
-            d_ma = w_ma2;
-            d_mb = w_mb2;
-        } else if (mi) {
-            produce_both(w_ma2, w_mb2);
-            d_ma = w_ma2;
-            d_mb = w_mb2;
-        }
+        for (int k = 0; k < 2; ++k) w[k] = take_rows(ar, src[k], rows);
+        if (dry) if (int rc2 = ensure_ws(c, ar.off + 4096)) return rc2;
+    }
+    // a periodic call: events 0 and 1 bracket the row producers of both sides ("cells" of lchd_ctx_last_ms, min_image_time)
+    const bool produced = a.kind == RowSource::CELL || b.kind == RowSource::CELL;
+    const double* d_m[2] = {nullptr, nullptr};
+    if (produced) mark(c, 0);
+    for (int k = 0; k < 2; ++k)
+        if (int rc2 = produce_rows(c, src[k], 0, rows, w[k], d_m[k])) return rc2;
+    if (produced) mark(c, 1);
+    if (fused) {
         DenseArgs da{};
         da.cfg = c->d_cfg;
-        da.s[0] = DenseSide{a.view(cat16), d_ma, cols_a, (int32_t)cols_a, d_len_a};
-        da.s[1] = DenseSide{b.view(cat16), d_mb, cols_b, (int32_t)cols_b, d_len_b};
+        for (int k = 0; k < 2; ++k) da.s[k] = DenseSide{src[k].view, d_m[k], src[k].cols, (int32_t)src[k].cols, src[k].d_len};
         da.n_rows = rows;
-        da.image_bound = std::max(diag2(a), diag2(b));
-        da.wf_index = d_wf;
-        da.out = d_out;
+        da.image_bound = std::max(a.bound, b.bound);
+        da.wf_index = P.d_wf;
+        da.out = P.d_out;
         da.st = c->d_status;
         da.sqrt_tab = c->d_tabs;
         da.scr_key = scr_key;
         da.scr_val = scr_val;
         da.scr_grid = scr_grid;
-        da.scr_segs = scr_segs;
+        da.scr_segs = plan.scr_segs;
         da.ticket = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->d_done) + sizeof(DoneState));
         mark(c, 2);
         if (!launch_dense_fused(c->stream, plan, da, c->h_status, c->seq))
@@ -2858,60 +2908,55 @@ static int dense_pass(lchd_ctx* c, const lchd_cloud& a, const lchd_cloud& b, con
         c->last_dense_valid = true;
         return LCHD_OK;
     }
-    EnvStore ea{}, eb{};
-    double *w_ma = nullptr, *w_mb = nullptr;
-    int4* d_meta = nullptr;
-    for (int dry = 1; dry >= 0; --dry) {
-        Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
-        ea = carve_row_store(ar, rows, cap_a, 1, cat16);
-        eb = carve_row_store(ar, rows, cap_b, 1, cat16);
-        ea.cdf_keys = eb.cdf_keys = (c->h_cfg.n_wf == 1 && !c->tune.no_cdf_keys) ? 1 : 0;
-        d_meta = ar.take<int4>((size_t)rows);
-        if (h_ma || mi) {  // given distance matrices in host memory: straight from the caller's buffers into the workspace
-            w_ma = ar.take<double>((size_t)rows * cols_a);
-            w_mb = ar.take<double>((size_t)rows * cols_b);
-        }
-        if (dry) if (int rc2 = ensure_ws(c, ar.off + 4096)) return rc2;
-    }
-    hipStream_t s = c->stream;
-    if (h_ma) {
-        HIP_TRY(hipMemcpyAsync(w_ma, h_ma, sizeof(double) * rows * cols_a, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(w_mb, h_mb, sizeof(double) * rows * cols_b, hipMemcpyHostToDevice, s));
-        d_ma = w_ma;
-        d_mb = w_mb;
-    } else if (mi) {
-        produce_both(w_ma, w_mb);
-        d_ma = w_ma;
-        d_mb = w_mb;
-    }
+    e[0].cdf_keys = e[1].cdf_keys = (c->h_cfg.n_wf == 1 && !c->tune.no_cdf_keys) ? 1 : 0;  // (scoring honours LCHD_NO_CDF_KEYS)
     mark(c, 2);
-    const RowSide rsa{a.view(cat16), d_ma, cols_a, cols_a, diag2(a), ea, d_len_a}, rsb{b.view(cat16), d_mb, cols_b, cols_b, diag2(b), eb, d_len_b};
-    bool launched;
-    if (plan.path == LCHD_DENSE_ROWS2) {
-        launched = launch_env_rows2(s, plan, c->d_cfg, rsa, rsb, rows, c->d_status);
-    } else {  // (LCHD_DENSE_ROWS: one launch per side)
-        const RowExtras exa{nullptr, d_len_a, nullptr}, exb{nullptr, d_len_b, nullptr};
-        launched = launch_env_rows(s, plan.rows[0], c->d_cfg, a.view(cat16), d_ma, cols_a, rows, cols_a, diag2(a), ea, c->d_status, exa) &&
-                   launch_env_rows(s, plan.rows[1], c->d_cfg, b.view(cat16), d_mb, cols_b, rows, cols_b, diag2(b), eb, c->d_status, exb);
-    }
-    if (!launched) return fail(LCHD_EDEVICE, "internal error: the dense plan names no instantiation of the row kernels");
-    if (c->deterministic) {  // one order among equal keys (a row's sort places ties by LDS-atomic order)
-        launch_env_canon(s, ea, eb, rows, rows, nullptr);
-        c->last_dense.canon = 1;
-    }
+    if (!sort_rows(c, plan, 2, src, d_m, e, rows, &c->last_dense.canon))  // (plan_dense's choice: k_env_rows2 or k_env_rows)
+        return fail(LCHD_EDEVICE, "internal error: the dense plan names no instantiation of the row kernels");
     mark(c, 3);
     uint32_t f = 0;
-    if (int rc2 = sweep_rows(c, ea, eb, d_wf, rows, d_out, d_meta, DRV_DMXS, &f)) return rc2;
+    if (int rc2 = sweep_rows(c, e[0], e[1], P.d_wf, rows, P.d_out, d_meta, DRV_DMXS, &f)) return rc2;
     c->last_dense.n_bitonic = c->h_status->n_bitonic;
     if (f & ST_ROW_RETRY) retry = true;
     else c->last_dense_valid = true;
     return LCHD_OK;
 }
 
-static int dense_driver(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
-                        int64_t len_seq_b, const double* xyz_a, const double* xyz_b, const double* dmx_a, const double* dmx_b,
-                        int64_t rows, int64_t cols_a, int64_t cols_b, const int32_t* wf_index, double* out,
-                        const int32_t* row_len_a = nullptr, const int32_t* row_len_b = nullptr) {
+// The attempts of a dense scoring call: the pass, once more when a row defeated the first attempt's kernel (a long row the fused kernel
+// or the segmented in-LDS sort gives up on).  in_bytes: a host call's staged inputs, copied from c->h_io at the head of every attempt.
+static int dense_attempts(lchd_ctx* c, const DensePass& P, size_t in_bytes) {
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if (int rc = begin_pass(c)) return rc;
+        c->status_dirty = true;  // until the record pass has been enqueued (sweep_rows)
+        if (in_bytes) HIP_TRY(hipMemcpyAsync(c->d_io, c->h_io, in_bytes, hipMemcpyHostToDevice, c->stream));
+        bool retry = false;
+        if (int rc = dense_pass(c, P, attempt, retry)) return rc;
+        if (!retry) break;
+    }
+    return LCHD_OK;
+}
+// The refusal of row lengths plan_dense has no kernel for (lchd_dense_plan::unsupported), naming one length or both.
+static int fail_dense_rows(int64_t cols_a, int64_t cols_b = -1) {
+    char got[48];
+    if (cols_b < 0) snprintf(got, sizeof got, "%lld", (long long)cols_a);
+    else snprintf(got, sizeof got, "%lld / %lld", (long long)cols_a, (long long)cols_b);
+    return fail(LCHD_EUNSUPPORTED, "dense rows of more than 65535 points are supported with at most %d categories and 2^23 points (got %s)",
+                kMaxCategories, got);
+}
+
+// One side of a dense host call: coordinates (xyz; optionally in a reduced periodic cell) or given rows (dmx [rows][cols]; ragged
+// with row_len).
+struct DenseHostSide {
+    const int32_t* seq;
+    int64_t len_seq;
+    const double *xyz, *dmx;
+    int64_t cols;
+    const int32_t* row_len;
+    const MinImageCell* cell;
+};
+static int dense_driver(lchd_ctx* c, const lchd_config* cfg, const DenseHostSide (&sd)[2], int64_t rows, const int32_t* wf_index, double* out) {
+    const int64_t cols_a = sd[0].cols, cols_b = sd[1].cols;
+    const int32_t *row_len_a = sd[0].row_len, *row_len_b = sd[1].row_len;
+    const bool periodic = sd[0].cell || sd[1].cell;  // both structures' rows are materialised and the pass runs in its given-row form
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     CTX_GUARD(c);
     if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
@@ -2919,11 +2964,10 @@ static int dense_driver(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_
     c->last_valid = c->last_sweep_valid = false;
     if (rows == 0) return LCHD_OK;
     // utils.rs:25-39: the sort mask has row-length entries and indexes seq => a row longer than seq panics
-    if (cols_a > len_seq_a || cols_b > len_seq_b) return fail(LCHD_EPANIC, "index out of bounds: a distance row is longer than its seq");
+    if (cols_a > sd[0].len_seq || cols_b > sd[1].len_seq) return fail(LCHD_EPANIC, "index out of bounds: a distance row is longer than its seq");
     if (cols_a == 0 || cols_b == 0) return fail(LCHD_EPANIC, "index out of bounds: empty distance row (src/locohd.rs:74)");
-    if ((cols_a > 65535 || cols_b > 65535) && (cfg->n_categories > kMaxCategories || cols_a > (1 << 23) || cols_b > (1 << 23)))
-        return fail(LCHD_EUNSUPPORTED, "dense rows of more than 65535 points are supported with at most %d categories and 2^23 points (got %lld / %lld)",
-                    kMaxCategories, (long long)cols_a, (long long)cols_b);
+    if (plan_dense(dense_query(c, cols_a, cols_b, sd[0].dmx || periodic, row_len_a || row_len_b, 0, false)).unsupported)
+        return fail_dense_rows(cols_a, cols_b);
     // The two structures (SoA coordinates + categories), the weight-function indices and -- for calls of up to kDirectOutPairs
     // rows -- the scores travel through the context's pinned staging block (one asynchronous copy in, none out); nothing is
     // allocated per call.
@@ -2937,12 +2981,13 @@ static int dense_driver(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_
         }
     }
     lchd_cloud a, b;
+    const bool cat16 = cfg->n_categories > kMaxCategories;
     size_t o_wf = 0, o_out = 0, in_bytes = 0, o_la = 0, o_lb = 0;
     for (int pass = 0; pass < 2; ++pass) {
         size_t off = 0;
         char* hb = pass ? c->h_io : nullptr;
-        if (int rc = stage_cloud(xyz_a, seq_a, nullptr, cols_a, hb, c->d_io, off, a, cfg->n_categories > kMaxCategories)) return rc;
-        if (int rc = stage_cloud(xyz_b, seq_b, nullptr, cols_b, hb, c->d_io, off, b, cfg->n_categories > kMaxCategories)) return rc;
+        if (int rc = stage_cloud(sd[0].xyz, sd[0].seq, nullptr, cols_a, hb, c->d_io, off, a, cat16)) return rc;
+        if (int rc = stage_cloud(sd[1].xyz, sd[1].seq, nullptr, cols_b, hb, c->d_io, off, b, cat16)) return rc;
         auto take = [&](size_t bytes) { off = (off + 255) & ~size_t(255); const size_t o = off; off += bytes; return o; };
         o_wf = take(wf_index ? sizeof(int32_t) * (size_t)rows : 0);
         o_la = take(row_len_a ? sizeof(int32_t) * (size_t)rows : 0);
@@ -2955,21 +3000,21 @@ static int dense_driver(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_
     if (wf_index) memcpy(c->h_io + o_wf, wf_index, sizeof(int32_t) * (size_t)rows);
     if (row_len_a) memcpy(c->h_io + o_la, row_len_a, sizeof(int32_t) * (size_t)rows);
     if (row_len_b) memcpy(c->h_io + o_lb, row_len_b, sizeof(int32_t) * (size_t)rows);
-    const int32_t* d_la = row_len_a ? reinterpret_cast<const int32_t*>(c->d_io + o_la) : nullptr;
-    const int32_t* d_lb = row_len_b ? reinterpret_cast<const int32_t*>(c->d_io + o_lb) : nullptr;
     const bool direct = rows <= kDirectOutPairs;
-    const int32_t* d_wf = wf_index ? reinterpret_cast<const int32_t*>(c->d_io + o_wf) : nullptr;
-    double* d_out = reinterpret_cast<double*>((direct ? c->h_io : c->d_io) + o_out);
-    int rc = LCHD_OK;
-    bool retry = false;
-    for (int attempt = 0; attempt < 2; ++attempt) {  // (second attempt: a long row defeated the segmented in-LDS sort)
-        if (int rc2 = begin_pass(c)) return rc2;
-        c->status_dirty = true;  // until the record pass has been enqueued (sweep_rows)
-        HIP_TRY(hipMemcpyAsync(c->d_io, c->h_io, in_bytes, hipMemcpyHostToDevice, c->stream));
-        rc = dense_pass(c, a, b, nullptr, nullptr, rows, cols_a, cols_b, d_wf, d_out, attempt, retry, dmx_a, dmx_b, d_la, d_lb);
-        if (rc || !retry) break;
+    const lchd_cloud* cl[2] = {&a, &b};
+    const size_t o_len[2] = {o_la, o_lb};
+    DensePass P{};
+    for (int k = 0; k < 2; ++k) {
+        RowSource& s = P.src[k] = cloud_source(*cl[k], cat16, sd[k].cols, sd[k].cell);
+        s.as_rows = periodic;
+        if (sd[k].dmx) { s.kind = RowSource::HOST_ROWS; s.m = sd[k].dmx; }  // (straight from the caller's buffers into the workspace)
+        if (sd[k].row_len) s.d_len = reinterpret_cast<const int32_t*>(c->d_io + o_len[k]);
     }
-    if (rc) return rc;
+    P.rows = rows;
+    P.d_wf = wf_index ? reinterpret_cast<const int32_t*>(c->d_io + o_wf) : nullptr;
+    P.d_out = reinterpret_cast<double*>((direct ? c->h_io : c->d_io) + o_out);
+    double* const d_out = P.d_out;
+    if (int rc = dense_attempts(c, P, in_bytes)) return rc;
     if (!direct) {
         HIP_TRY(hipMemcpyAsync(c->h_io + o_out, d_out, sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2980,10 +3025,9 @@ static int dense_driver(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_
 
 /* from_coords with both structures already on the device (what bench.py --workload c2b measures): pair r = (atom r of a,
  * atom r of b), the environments are the whole structures.  d_wf_index / d_out are device pointers ([n] int32 or NULL,
- * [n] double).  Uses the configuration of lchd_ctx_set_config; d_out is complete on return. */
-extern "C" int lchd_from_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, double* d_out) {
-    CTX_LOCK(c);
-    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+ * [n] double).  Uses the configuration of lchd_ctx_set_config; d_out is complete on return.  cell[k]: the reduced periodic cell of
+ * side k, or null (lchd_from_coords_periodic_dev). */
+static int coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const MinImageCell* const* cell, double* d_out) {
     if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     if (a->sid || b->sid) return fail(LCHD_EVALUE, "from_coords takes single structures, not batches");
@@ -2992,28 +3036,36 @@ extern "C" int lchd_from_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, c
     c->last_valid = c->last_sweep_valid = false;
     if (a->n == 0) return LCHD_OK;
     if (!d_out) return fail(LCHD_EVALUE, "null score pointer");
-    if (a->n > 65535 && (c->h_cfg.n_categories > kMaxCategories || a->n > (1 << 23)))
-        return fail(LCHD_EUNSUPPORTED, "dense rows of more than 65535 points are supported with at most %d categories and 2^23 points (got %lld)",
-                    kMaxCategories, (long long)a->n);
+    const bool periodic = cell[0] || cell[1];  // both structures' rows are materialised and the pass runs in its given-row form
+    if (plan_dense(dense_query(c, a->n, b->n, periodic, false, 0, false)).unsupported) return fail_dense_rows(a->n);
     CTX_GUARD(c);
-    bool retry = false;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (int rc = begin_pass(c)) return rc;
-        c->status_dirty = true;
-        if (int rc = dense_pass(c, *a, *b, nullptr, nullptr, a->n, a->n, b->n, d_wf_index, d_out, attempt, retry)) return rc;
-        if (!retry) break;
-    }
-    return LCHD_OK;
+    const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
+    DensePass P{{cloud_source(*a, cat16, a->n, cell[0]), cloud_source(*b, cat16, b->n, cell[1])}, a->n, d_wf_index, d_out};
+    P.src[0].as_rows = P.src[1].as_rows = periodic;
+    return dense_attempts(c, P, 0);
+}
+static const MinImageCell* const kNoCells[2] = {nullptr, nullptr};
+extern "C" int lchd_from_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, double* d_out) {
+    CTX_LOCK(c);
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    return coords_dev(c, a, b, d_wf_index, kNoCells, d_out);
 }
 
+// from_coords from host arrays; cell[k]: the reduced periodic cell of side k, or null (lchd_from_coords_periodic)
+static int coords_host(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b, int64_t len_seq_b,
+                       const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b, const int32_t* wf_index,
+                       const MinImageCell* const* cell, double* out) {
+    if (n_a != n_b)  // src/locohd.rs:420-428 via :472-475
+        return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)n_a, (long long)n_b);
+    const DenseHostSide sd[2] = {{seq_a, len_seq_a, xyz_a, nullptr, n_a, nullptr, cell[0]}, {seq_b, len_seq_b, xyz_b, nullptr, n_b, nullptr, cell[1]}};
+    return dense_driver(c, cfg, sd, n_a, wf_index, out);
+}
 extern "C" int lchd_from_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
                                 int64_t len_seq_b, const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b,
                                 const int32_t* wf_index, double* out) {
     CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
-    if (n_a != n_b)  // src/locohd.rs:420-428 via :472-475
-        return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)n_a, (long long)n_b);
-    return dense_driver(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n_a, n_a, n_b, wf_index, out);
+    return coords_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, n_a, xyz_b, n_b, wf_index, kNoCells, out);
 }
 
 extern "C" int lchd_from_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
@@ -3023,7 +3075,8 @@ extern "C" int lchd_from_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t
     if (!c) return fail(LCHD_EVALUE, "null context");
     if (rows_a != rows_b)  // src/locohd.rs:420-428
         return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)rows_a, (long long)rows_b);
-    return dense_driver(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows_a, cols_a, cols_b, wf_index, out);
+    const DenseHostSide sd[2] = {{seq_a, len_seq_a, nullptr, dmx_a, cols_a, nullptr, nullptr}, {seq_b, len_seq_b, nullptr, dmx_b, cols_b, nullptr, nullptr}};
+    return dense_driver(c, cfg, sd, rows_a, wf_index, out);
 }
 
 /* from_dmxs with ragged rows: the reference takes Vec<Vec<f64>> and sorts each row with a PREFIX of seq (utils.rs:25-39), so rows
@@ -3038,8 +3091,8 @@ extern "C" int lchd_from_dmxs_ragged(lchd_ctx* c, const lchd_config* cfg, const 
     if (rows_a != rows_b)  // src/locohd.rs:420-428
         return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)rows_a, (long long)rows_b);
     if (!row_len_a || !row_len_b) return fail(LCHD_EVALUE, "null row-length array");
-    return dense_driver(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows_a, cols_a, cols_b, wf_index, out, row_len_a,
-                        row_len_b);
+    const DenseHostSide sd[2] = {{seq_a, len_seq_a, nullptr, dmx_a, cols_a, row_len_a, nullptr}, {seq_b, len_seq_b, nullptr, dmx_b, cols_b, row_len_b, nullptr}};
+    return dense_driver(c, cfg, sd, rows_a, wf_index, out);
 }
 
 extern "C" int lchd_from_anchors(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const double* dists_a,
@@ -3152,13 +3205,6 @@ extern "C" int lchd_from_anchors(lchd_ctx* c, const lchd_config* cfg, const int3
 constexpr int64_t kEnsRecords = (int64_t)1 << 22;   // sweep records per pass (anchors, weight-function index, pair record, score: 44 B each)
 constexpr int64_t kEnsDistBytes = (int64_t)1 << 30; // distance rows materialised for one row-sort launch
 
-struct EnsSrc {
-    CloudView cats;             // the topology's categories (n atoms; coordinates unused)
-    const lchd_cloud* coords;   // regular batch of M structures of n atoms, or null (given rows)
-    const double* h_dmx;        // given rows: HOST [M][n][n], or null
-    const int32_t *excl_start, *excl_idx;  // DEVICE CSR of excluded columns per row, or null
-};
-
 static int ens_sweep(lchd_ctx* c, const EnvStore& st, const int64_t* anchors, const uint32_t* slots, int64_t n_slots, const int32_t* wf_rec,
                      int64_t q, double* out, int4* meta) {
     SweepArgs sw{};
@@ -3180,8 +3226,10 @@ static int ens_sweep(lchd_ctx* c, const EnvStore& st, const int64_t* anchors, co
     return status_to_rc(f, DRV_DMXS);
 }
 
-// pairs: host [P][2] structure indices (validated); d_wf: DEVICE [n] or null; d_out: DEVICE [P][n]
-static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, const std::vector<int32_t>& pairs, const int32_t* d_wf,
+// src: the rows of all M structures, [M * n][n] -- the coordinates of a regular batch (view: the topology's categories over the batch's
+// coordinate arrays; open with as_rows, or in its cells) or given HOST rows; pairs: host [P][2] structure indices (validated);
+// d_wf: DEVICE [n] or null; d_out: DEVICE [P][n]
+static int ensemble_core(lchd_ctx* c, const RowSource& src, int64_t n, int64_t M, const std::vector<int32_t>& pairs, const int32_t* d_wf,
                          double* d_out) {
     const int64_t P = (int64_t)pairs.size() / 2;
     c->last_valid = c->last_sweep_valid = false;
@@ -3191,9 +3239,7 @@ static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, c
     const lchd_dense_query query = dense_query(c, n, n, true, false, 0, true);
     const lchd_dense_plan dplan = plan_dense(query);
     const bool cat16 = query.cat16 != 0;
-    if (dplan.unsupported)
-        return fail(LCHD_EUNSUPPORTED, "dense rows of more than 65535 points are supported with at most %d categories and 2^23 points (got %lld)",
-                    kMaxCategories, (long long)n);
+    if (dplan.unsupported) return fail_dense_rows(n);
     c->last_dense = lchd_dense_record{};
     c->last_dense.plan = dplan;
     c->last_dense.attempts = 1;
@@ -3223,7 +3269,7 @@ static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, c
     if (slots * n >= ((int64_t)1 << 31)) return fail(LCHD_EUNSUPPORTED, "%lld resident rows exceed the 2^31 environment slots of a pass", (long long)(slots * n));
     // one device block for the call, released on every path out
     EnvStore st{};
-    double *dmx = nullptr, *tmp = nullptr;
+    double *w = nullptr, *tmp = nullptr;
     int64_t* anchors = nullptr;
     int32_t* wf_rec = nullptr;
     int4 *meta = nullptr, *plan = nullptr;
@@ -3234,7 +3280,7 @@ static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, c
         Arena ar(blk, blk_bytes, dry != 0);
         st = carve_row_store(ar, slots * n + 1, cap, 1, cat16);  // (+1 row: the odd row of a row-sort launch, below)
         iota = ar.take<uint32_t>((size_t)(slots * n));
-        dmx = ar.take<double>((size_t)(dist_structs * n) * n);
+        w = take_rows(ar, src, dist_structs * n);
         anchors = ar.take<int64_t>((size_t)q_cap * 2);
         wf_rec = d_wf ? ar.take<int32_t>((size_t)q_cap) : nullptr;
         meta = ar.take<int4>((size_t)q_cap);
@@ -3267,33 +3313,26 @@ static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, c
     auto build = [&](int64_t slot0, int64_t s0, int64_t cnt) -> int {
         for (int64_t k0 = 0; k0 < cnt; k0 += dist_structs) {
             const int64_t kc = std::min(dist_structs, cnt - k0), rows = kc * n;
-            if (src.coords) {
-                if (const MinImage* mi = c->min_image)  // a periodic ensemble: minimum-image rows, exclusions on top as below
-                    launch_min_image_rows(s, src.coords->view(cat16), (s0 + k0) * n, (int32_t)n, rows, mi->side[0], mi->d_recs, mi->all_diagonal,
-                                          src.excl_start, src.excl_idx, dmx);
-                else
-                    launch_ens_dist(s, src.coords->view(cat16), (s0 + k0) * n, (int32_t)n, rows, src.excl_start, src.excl_idx, dmx);
-            } else {
-                HIP_TRY(hipMemcpyAsync(dmx, src.h_dmx + (size_t)(s0 + k0) * n * n, sizeof(double) * (size_t)rows * n, hipMemcpyHostToDevice, s));
-            }
+            const double* dmx = nullptr;
+            if (int rc = produce_rows(c, src, (s0 + k0) * n, rows, w, dmx)) return rc;
             const EnvStore e0 = rows_of(slot0 + k0);
             bool ok;
             if (rows2) {  // both halves of the launch: rows [0, h) and [h, 2h); an odd last row goes with the store's spare row
                 const int64_t h = rows / 2;
                 EnvStore e1 = e0;
                 e1.key += h * cap; e1.cat += h * cap; e1.len += h;
-                ok = launch_env_rows2(s, dplan, c->d_cfg, RowSide{src.cats, dmx, n, n, 0.0, e0, nullptr}, RowSide{src.cats, dmx + h * n, n, n, 0.0, e1, nullptr}, h,
+                ok = launch_env_rows2(s, dplan, c->d_cfg, RowSide{src.view, dmx, n, n, 0.0, e0, nullptr}, RowSide{src.view, dmx + h * n, n, n, 0.0, e1, nullptr}, h,
                                       c->d_status);
                 if (ok && (rows & 1)) {
                     EnvStore el = e0, spare = st;
                     el.key += (rows - 1) * cap; el.cat += (rows - 1) * cap; el.len += rows - 1;
                     spare.key += slots * n * cap; spare.cat += slots * n * cap; spare.len += slots * n;
                     const double* last = dmx + (rows - 1) * n;
-                    ok = launch_env_rows2(s, dplan, c->d_cfg, RowSide{src.cats, last, n, n, 0.0, el, nullptr}, RowSide{src.cats, last, n, n, 0.0, spare, nullptr}, 1,
+                    ok = launch_env_rows2(s, dplan, c->d_cfg, RowSide{src.view, last, n, n, 0.0, el, nullptr}, RowSide{src.view, last, n, n, 0.0, spare, nullptr}, 1,
                                           c->d_status);
                 }
             } else {
-                ok = launch_env_rows(s, dplan.rows[0], c->d_cfg, src.cats, dmx, n, rows, n, 0.0, e0, c->d_status);
+                ok = launch_env_rows(s, dplan.rows[0], c->d_cfg, src.view, dmx, n, rows, n, 0.0, e0, c->d_status);
             }
             if (!ok) return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for rows of %lld points", (long long)n);
         }
@@ -3361,10 +3400,9 @@ static int ensemble_core(lchd_ctx* c, const EnsSrc& src, int64_t n, int64_t M, c
 
 // d_pairs: DEVICE [n_pairs][2] or null (every i < j, i outer); excluded columns: DEVICE CSR or null.  Copies the (small) pair and
 // exclusion lists to the host to validate them and to plan the blocks; the P * n records are made on the device.
-extern "C" int lchd_ensemble_from_coords_dev(lchd_ctx* c, lchd_cloud* cl, const int32_t* d_pairs, int64_t n_pairs, const int32_t* d_excl_start,
-                                             const int32_t* d_excl_idx, const int32_t* d_wf_index, double* d_out) {
-    CTX_LOCK(c);
-    if (!c || !cl) return fail(LCHD_EVALUE, "null argument");
+// cells: the cell fields of a periodic call's source (min_image_ensemble), or null.
+static int ensemble_coords_dev(lchd_ctx* c, lchd_cloud* cl, const int32_t* d_pairs, int64_t n_pairs, const int32_t* d_excl_start,
+                               const int32_t* d_excl_idx, const int32_t* d_wf_index, const RowSource* cells, double* d_out) {
     if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     if (!cl->sid || cl->struct_size <= 0 || cl->n != (int64_t)cl->n_struct * cl->struct_size)
@@ -3407,12 +3445,23 @@ extern "C" int lchd_ensemble_from_coords_dev(lchd_ctx* c, lchd_cloud* cl, const 
         for (size_t e = 0; e < xi.size(); ++e)
             if (xi[e] < 0 || xi[e] >= n) return fail(LCHD_EVALUE, "excluded column %d is outside [0, %lld)", xi[e], (long long)n);
     }
-    CloudView cats = cl->view(c->h_cfg.n_categories > kMaxCategories);  // (every structure carries the topology's categories: structure 0's are read)
-    cats.n = (int32_t)n;
-    cats.sid = nullptr;
-    cats.n_struct = 1;
-    cats.struct_size = 0;
-    return ensemble_core(c, EnsSrc{cats, cl, nullptr, d_excl_start, d_excl_idx}, n, M, pairs, d_wf_index, d_out);
+    RowSource src = cells ? *cells : RowSource{};  // (open: COORDS)
+    src.view = cl->view(c->h_cfg.n_categories > kMaxCategories);  // (every structure carries the topology's categories: structure 0's are read)
+    src.view.n = (int32_t)n;
+    src.view.sid = nullptr;
+    src.view.n_struct = 1;
+    src.view.struct_size = 0;
+    src.cols = n;
+    src.as_rows = true;
+    src.excl_start = d_excl_start;
+    src.excl_idx = d_excl_idx;
+    return ensemble_core(c, src, n, M, pairs, d_wf_index, d_out);
+}
+extern "C" int lchd_ensemble_from_coords_dev(lchd_ctx* c, lchd_cloud* cl, const int32_t* d_pairs, int64_t n_pairs, const int32_t* d_excl_start,
+                                             const int32_t* d_excl_idx, const int32_t* d_wf_index, double* d_out) {
+    CTX_LOCK(c);
+    if (!c || !cl) return fail(LCHD_EVALUE, "null argument");
+    return ensemble_coords_dev(c, cl, d_pairs, n_pairs, d_excl_start, d_excl_idx, d_wf_index, nullptr, d_out);
 }
 
 static int ens_check_pairs(const int32_t* pairs, int64_t n_pairs, int64_t M) {
@@ -3442,11 +3491,9 @@ struct EnsDevBufs {
     }
 };
 
-extern "C" int lchd_ensemble_from_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t n, const double* xyz, int64_t n_struct,
-                                         const int32_t* pairs, int64_t n_pairs, const int32_t* excl_start, const int32_t* excl_idx,
-                                         const int32_t* wf_index, double* out) {
-    CTX_LOCK(c);
-    if (!c) return fail(LCHD_EVALUE, "null context");
+static int ensemble_coords_host(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t n, const double* xyz, int64_t n_struct,
+                                const int32_t* pairs, int64_t n_pairs, const int32_t* excl_start, const int32_t* excl_idx,
+                                const int32_t* wf_index, const RowSource* cells, double* out) {
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
     if (n < 0 || n_struct < 0) return fail(LCHD_EVALUE, "negative size");
     if (n_struct * n > ((int64_t)1 << 30)) return fail(LCHD_EUNSUPPORTED, "%lld atoms in all exceed a batch", (long long)(n_struct * n));
@@ -3478,9 +3525,16 @@ extern "C" int lchd_ensemble_from_coords(lchd_ctx* c, const lchd_config* cfg, co
     }
     if (int rc = bufs.put(wf_index, (size_t)(wf_index ? n : 0), &d_wf)) return rc;
     if (int rc = bufs.put<double>(nullptr, (size_t)(P * n), &d_out)) return rc;
-    if (int rc = lchd_ensemble_from_coords_dev(c, cl, d_pairs, P, d_xs, d_xi, d_wf, d_out)) return rc;
+    if (int rc = ensemble_coords_dev(c, cl, d_pairs, P, d_xs, d_xi, d_wf, cells, d_out)) return rc;
     HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * (size_t)(P * n), hipMemcpyDeviceToHost));
     return LCHD_OK;
+}
+extern "C" int lchd_ensemble_from_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t n, const double* xyz, int64_t n_struct,
+                                         const int32_t* pairs, int64_t n_pairs, const int32_t* excl_start, const int32_t* excl_idx,
+                                         const int32_t* wf_index, double* out) {
+    CTX_LOCK(c);
+    if (!c) return fail(LCHD_EVALUE, "null context");
+    return ensemble_coords_host(c, cfg, seq, n, xyz, n_struct, pairs, n_pairs, excl_start, excl_idx, wf_index, nullptr, out);
 }
 
 extern "C" int lchd_ensemble_from_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t n, const double* dmx, int64_t n_struct,
@@ -3515,50 +3569,50 @@ extern "C" int lchd_ensemble_from_dmxs(lchd_ctx* c, const lchd_config* cfg, cons
     double* d_out = nullptr;
     if (int rc = bufs.put(wf_index, (size_t)(wf_index ? n : 0), &d_wf)) return rc;
     if (int rc = bufs.put<double>(nullptr, (size_t)(P * n), &d_out)) return rc;
-    const CloudView cats = cl->view(cfg->n_categories > kMaxCategories);
-    if (int rc = ensemble_core(c, EnsSrc{cats, nullptr, dmx, nullptr, nullptr}, n, n_struct, hp, d_wf, d_out)) return rc;
+    RowSource src{};
+    src.kind = RowSource::HOST_ROWS;
+    src.view = cl->view(cfg->n_categories > kMaxCategories);
+    src.cols = n;
+    src.m = dmx;
+    if (int rc = ensemble_core(c, src, n, n_struct, hp, d_wf, d_out)) return rc;
     HIP_TRY(hipMemcpy(out, d_out, sizeof(double) * (size_t)(P * n), hipMemcpyDeviceToHost));
     return LCHD_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
-// dense calls in periodic cells (minimum image): the cells are reduced on the host and hung on the context, the open call then
-// runs with every periodic structure's rows materialised by launch_min_image_rows (dense_pass, ensemble_core)
+// dense calls in periodic cells (minimum image): the cells are reduced on the host and travel in the call's row sources (RowSource),
+// whose rows launch_min_image_rows then materialises (produce_rows)
 // ------------------------------------------------------------------------------------------------
-struct MinImageScope {  // lchd_ctx::min_image for the duration of the open call
-    lchd_ctx* c;
-    MinImageScope(lchd_ctx* ctx, const MinImage* mi) : c(ctx) { c->min_image = mi; }
-    ~MinImageScope() { c->min_image = nullptr; }
-};
+// The cells of a call's sides, reduced: cell[k] = &rec[k], or null for an open side.  by_side: a refusal names cell k (else cell 0).
+static int reduce_cells(const double* const* cells, int sides, bool by_side, MinImageCell* rec, const MinImageCell** cell) {
+    for (int k = 0; k < 2; ++k) cell[k] = nullptr;
+    for (int k = 0; k < sides; ++k)
+        if (cells[k]) {
+            if (int rc = min_image_record(cells[k], by_side ? k : 0, rec[k])) return rc;
+            cell[k] = &rec[k];
+        }
+    return LCHD_OK;
+}
 // "cells" of lchd_ctx_last_ms after a periodic single-pair call: the row producers of both sides (events 0 and 1 of dense_pass)
 static void min_image_time(lchd_ctx* c) {
     float t = -1.f;
     if (c->timing && hipEventElapsedTime(&t, c->ev[0], c->ev[1]) == hipSuccess) c->ms[PH_CELLS] = t;
-}
-static int min_image_sides(const double* cell_a, const double* cell_b, MinImage& mi) {
-    const double* cells[2] = {cell_a, cell_b};
-    for (int side = 0; side < 2; ++side) {
-        mi.on[side] = cells[side] != nullptr;
-        if (cells[side])
-            if (int rc = min_image_record(cells[side], side, mi.side[side])) return rc;
-    }
-    return LCHD_OK;
 }
 
 extern "C" int lchd_from_coords_periodic_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
                                              const double* cell_b, double* d_out) {
     CTX_LOCK(c);
     if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
-    if (c->min_image) return fail(LCHD_EVALUE, "a periodic dense call is already running on this context");
-    if (!cell_a && !cell_b) return lchd_from_coords_dev(c, a, b, d_wf_index, d_out);
-    MinImage mi;
-    if (int rc = min_image_sides(cell_a, cell_b, mi)) return rc;
+    if (!cell_a && !cell_b) return coords_dev(c, a, b, d_wf_index, kNoCells, d_out);  // the open call
+    const double* const cells[2] = {cell_a, cell_b};
+    MinImageCell rec[2];
+    const MinImageCell* cell[2];
+    if (int rc = reduce_cells(cells, 2, true, rec, cell)) return rc;
     if (a->images || b->images) return fail(LCHD_EVALUE, "a periodic dense call takes the structures themselves, not their image clouds");
     CTX_GUARD(c);
     if (int rc = resolve_bbox(c, a)) return rc;  // (rejects non-finite coordinates of a buffer filled on the device)
     if (int rc = resolve_bbox(c, b)) return rc;
-    MinImageScope scope(c, &mi);
-    const int rc = lchd_from_coords_dev(c, a, b, d_wf_index, d_out);
+    const int rc = coords_dev(c, a, b, d_wf_index, cell, d_out);
     if (!rc) min_image_time(c);
     return rc;
 }
@@ -3568,31 +3622,32 @@ extern "C" int lchd_from_coords_periodic(lchd_ctx* c, const lchd_config* cfg, co
                                          const int32_t* wf_index, const double* cell_a, const double* cell_b, double* out) {
     CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
-    if (c->min_image) return fail(LCHD_EVALUE, "a periodic dense call is already running on this context");
-    MinImage mi;
-    if (int rc = min_image_sides(cell_a, cell_b, mi)) return rc;
-    MinImageScope scope(c, (cell_a || cell_b) ? &mi : nullptr);
-    const int rc = lchd_from_coords(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, n_a, xyz_b, n_b, wf_index, out);
+    const double* const cells[2] = {cell_a, cell_b};
+    MinImageCell rec[2];
+    const MinImageCell* cell[2];
+    if (int rc = reduce_cells(cells, 2, true, rec, cell)) return rc;
+    const int rc = coords_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, n_a, xyz_b, n_b, wf_index, cell, out);
     if (!rc && (cell_a || cell_b)) min_image_time(c);
     return rc;
 }
 
-// cells: HOST [n_cells][9], n_cells = 1 or the number of structures.  Fills `mi`; per-structure records go to the device through `bufs`.
-static int min_image_ensemble(const double* cells, int32_t n_cells, int64_t n_struct, MinImage& mi, EnsDevBufs& bufs) {
+// cells: HOST [n_cells][9], n_cells = 1 or the number of structures.  Fills the cell fields of `src`; per-structure records go to the
+// device through `bufs`.
+static int min_image_ensemble(const double* cells, int32_t n_cells, int64_t n_struct, RowSource& src, EnsDevBufs& bufs) {
     if (!cells || (n_cells != 1 && n_cells != n_struct))
         return fail(LCHD_EVALUE, "%d cells given for %lld structures (pass one cell, or one per structure)", cells ? n_cells : 0, (long long)n_struct);
     std::vector<MinImageCell> recs((size_t)n_cells);
-    mi.all_diagonal = true;
+    src.kind = RowSource::CELL;
+    src.all_diagonal = true;
     for (int32_t k = 0; k < n_cells; ++k) {
         if (int rc = min_image_record(cells + 9 * (size_t)k, k, recs[(size_t)k])) return rc;
-        if (recs[(size_t)k].v[18] == 0.0) mi.all_diagonal = false;
+        if (recs[(size_t)k].v[18] == 0.0) src.all_diagonal = false;
     }
-    mi.n_cells = n_cells;
-    mi.side[0] = recs[0];
+    src.cell = recs[0];
     if (n_cells > 1) {
         double* d = nullptr;
         if (int rc = bufs.put(recs[0].v, (size_t)n_cells * kMinImageRecord, &d)) return rc;
-        mi.d_recs = d;
+        src.d_cells = d;
     }
     return LCHD_OK;
 }
@@ -3602,14 +3657,12 @@ extern "C" int lchd_ensemble_from_coords_periodic_dev(lchd_ctx* c, lchd_cloud* c
                                                       const double* cells, int32_t n_cells, double* d_out) {
     CTX_LOCK(c);
     if (!c || !cl) return fail(LCHD_EVALUE, "null argument");
-    if (c->min_image) return fail(LCHD_EVALUE, "a periodic dense call is already running on this context");
     if (cl->images) return fail(LCHD_EVALUE, "a periodic dense call takes the structures themselves, not their image clouds");
     CTX_GUARD(c);
-    MinImage mi;
+    RowSource src{};
     EnsDevBufs bufs;
-    if (int rc = min_image_ensemble(cells, n_cells, cl->n_struct, mi, bufs)) return rc;
-    MinImageScope scope(c, &mi);
-    return lchd_ensemble_from_coords_dev(c, cl, d_pairs, n_pairs, d_excl_start, d_excl_idx, d_wf_index, d_out);
+    if (int rc = min_image_ensemble(cells, n_cells, cl->n_struct, src, bufs)) return rc;
+    return ensemble_coords_dev(c, cl, d_pairs, n_pairs, d_excl_start, d_excl_idx, d_wf_index, &src, d_out);
 }
 
 extern "C" int lchd_ensemble_from_coords_periodic(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq, int64_t n, const double* xyz,
@@ -3618,13 +3671,11 @@ extern "C" int lchd_ensemble_from_coords_periodic(lchd_ctx* c, const lchd_config
                                                   double* out) {
     CTX_LOCK(c);
     if (!c) return fail(LCHD_EVALUE, "null context");
-    if (c->min_image) return fail(LCHD_EVALUE, "a periodic dense call is already running on this context");
     CTX_GUARD(c);
-    MinImage mi;
+    RowSource src{};
     EnsDevBufs bufs;
-    if (int rc = min_image_ensemble(cells, n_cells, n_struct, mi, bufs)) return rc;
-    MinImageScope scope(c, &mi);
-    return lchd_ensemble_from_coords(c, cfg, seq, n, xyz, n_struct, pairs, n_pairs, excl_start, excl_idx, wf_index, out);
+    if (int rc = min_image_ensemble(cells, n_cells, n_struct, src, bufs)) return rc;
+    return ensemble_coords_host(c, cfg, seq, n, xyz, n_struct, pairs, n_pairs, excl_start, excl_idx, wf_index, &src, out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3976,31 +4027,35 @@ static int consumer_primitives_host(lchd_ctx* c, const lchd_config* cfg, const P
 }
 
 // Dense rows: entry r = row r of every side (composition: of the one structure).  Row r is the whole structure seen from atom r
-// (from_coords) or the given distance row r (from_dmxs).  d_m[k]: DEVICE rows [rows][cols[k]], or null: distances from the side's
-// coordinates, through the minimum-image row producer with a cell.  Every side goes through k_env_rows, which materialises the store
+// (from_coords) or the given distance row r (from_dmxs).  src[k]: the side's coordinates (an open side is read in place, whatever the
+// other side is) or DEVICE rows.  Every side goes through k_env_rows, which materialises the store
 // (the fused sort-and-sweep kernel never writes one).  A sensitivity call also builds the indexed lists of both sides' rows
-// (launch_rows_indexed, from the same d_m or coordinates) for its kernel; the stores still feed the record pass.  All arrays: [use.sides].
-static int consumer_dense(lchd_ctx* c, const lchd_cloud* const* cl, const double* const* d_m_in, int64_t rows, const int64_t* cols,
-                          const MinImageCell* const* cell, const int32_t* d_wf, const PairConsumer& use, double* d_out) {
+// (launch_rows_indexed, from the same rows or coordinates) for its kernel; the stores still feed the record pass.  src: [use.sides].
+static int consumer_dense(lchd_ctx* c, const RowSource* src, int64_t rows, const int32_t* d_wf, const PairConsumer& use, double* d_out) {
     const int sides = use.sides;
     const int n_wf = c->h_cfg.n_wf;
     const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
-    const size_t sets = n_wf > 1 ? (size_t)n_wf + 1 : 1;
+    const size_t sets = n_wf > 1 ? (size_t)n_wf + 1 : 1;  // (a dictionary: set 0 and one set per function, filled below)
     int cap[2] = {0, 0};
     EnvStore e[2] = {};
-    double* w_m[2] = {nullptr, nullptr};
+    double* w[2] = {nullptr, nullptr};
     const double* d_m[2] = {nullptr, nullptr};
     int4* d_meta = nullptr;
-    for (int k = 0; k < sides; ++k) { cap[k] = next_pow2_host(cols[k]); d_m[k] = d_m_in[k]; }
+    // the consumers always take the per-side k_env_rows, never k_env_rows2 or the fused kernel, and have no retry
+    lchd_dense_plan plan{};
+    plan.path = LCHD_DENSE_ROWS;
+    for (int k = 0; k < sides; ++k) {
+        cap[k] = next_pow2_host(src[k].cols);
+        if (!plan_dense_rows_side(cap[k], src[k].cols, cat16, plan.rows[k])) return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
+    }
     for (int dry = 1; dry >= 0; --dry) {
         Arena ar(dry ? nullptr : c->ws, dry ? 0 : c->ws_cap, dry != 0);
         for (int k = 0; k < sides; ++k) e[k] = carve_row_store(ar, rows, cap[k], sets, cat16);
         if (use.records) d_meta = ar.take<int4>((size_t)rows);
-        for (int k = 0; k < sides; ++k)
-            if (cell[k]) w_m[k] = ar.take<double>((size_t)rows * cols[k]);
+        for (int k = 0; k < sides; ++k) w[k] = take_rows(ar, src[k], rows);
         if (dry) if (int rc = ensure_ws(c, ar.off + 4096)) return rc;
     }
-    for (int k = 0; k < sides; ++k) e[k].cdf_keys = n_wf == 1 ? 1 : 0;
+    for (int k = 0; k < sides; ++k) e[k].cdf_keys = n_wf == 1 ? 1 : 0;  // (LCHD_NO_CDF_KEYS is the scoring passes' hook)
     // a sensitivity call: one indexed-list block per side, slots of the scoring stores' stride, in the block of the thresholded call
     // (grow-only, outside the arena): 13 bytes per padded point and side
     RowsIndexedArgs rx{};
@@ -4015,9 +4070,9 @@ static int consumer_dense(lchd_ctx* c, const lchd_cloud* const* cl, const double
         rx.cfg = c->d_cfg; rx.rows = rows; rx.st = c->d_status;
         for (int k = 0; k < 2; ++k) {
             RowsIndexedSide& S = rx.s[k];
-            S.c = cl[k]->view(cat16);
-            S.ld = cols[k];
-            S.cols = (int32_t)cols[k];
+            S.c = src[k].view;
+            S.ld = src[k].cols;
+            S.cols = (int32_t)src[k].cols;
             S.env.len = reinterpret_cast<int32_t*>(c->d_indexed + off[k][0]);
             S.env.dist = reinterpret_cast<double*>(c->d_indexed + off[k][1]);
             S.env.idx = reinterpret_cast<uint32_t*>(c->d_indexed + off[k][2]);
@@ -4030,7 +4085,7 @@ static int consumer_dense(lchd_ctx* c, const lchd_cloud* const* cl, const double
     c->status_dirty = true;
     mark(c, 0);
     for (int k = 0; k < sides; ++k)
-        if (cell[k]) { produce_rows(s, *cl[k], cols[k], rows, cell[k], w_m[k]); d_m[k] = w_m[k]; }
+        if (int rc = produce_rows(c, src[k], 0, rows, w[k], d_m[k])) return rc;
     mark(c, 1);
     // (between events 1 and 2, which nothing else of a dense pass separates: lchd_ctx_last_ms "anchors" is the list build's time)
     if (use.width) {
@@ -4038,13 +4093,8 @@ static int consumer_dense(lchd_ctx* c, const lchd_cloud* const* cl, const double
         if (!launch_rows_indexed(s, rx)) return fail(LCHD_EDEVICE, "internal error: the indexed-list kernel rejected its launch configuration");
     }
     mark(c, 2);
-    for (int k = 0; k < sides; ++k) {
-        lchd_dense_rows_side side;
-        if (!plan_dense_rows_side(cap[k], cols[k], cat16, side) ||
-            !launch_env_rows(s, side, c->d_cfg, cl[k]->view(cat16), d_m[k], cols[k], rows, cols[k], diag2(*cl[k]), e[k], c->d_status))
-            return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
-    }
-    if (c->deterministic) launch_env_canon(s, e[0], e[sides - 1], rows, rows * (sides - 1), nullptr);  // (one launch; one side: no rows of a second store)
+    int32_t canon = 0;  // (not recorded: a consumer call leaves c->last_dense, and last_sweep_valid, as it found them)
+    if (!sort_rows(c, plan, sides, src, d_m, e, rows, &canon)) return fail(LCHD_EUNSUPPORTED, "no dense environment kernel for this row length");
     if (n_wf > 1) {
         launch_profile_rows(s, c->d_status, rows);  // (the key-set kernel walks DeviceStatus::n_unique[0] rows of its first store)
         for (int k = 0; k < sides; ++k) launch_env_key_sets(s, c->d_cfg, e[k], e[k], n_wf, rows, c->d_status);
@@ -4104,12 +4154,8 @@ static int consumer_coords_dev(lchd_ctx* c, lchd_cloud* const* cl, const int32_t
     if (a->n != b->n)
         return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)a->n, (long long)b->n);
     MinImageCell rec[2];
-    const MinImageCell* cell[2] = {nullptr, nullptr};
-    for (int k = 0; k < sides; ++k)
-        if (cells[k]) {
-            if (int rc = min_image_record(cells[k], 0, rec[k])) return rc;
-            cell[k] = &rec[k];
-        }
+    const MinImageCell* cell[2];
+    if (int rc = reduce_cells(cells, sides, false, rec, cell)) return rc;
     consumer_drop_records(c, use);
     if (a->n == 0) return LCHD_OK;
     if (!d_out) return fail(LCHD_EVALUE, "null output pointer");
@@ -4120,8 +4166,10 @@ static int consumer_coords_dev(lchd_ctx* c, lchd_cloud* const* cl, const int32_t
         if (int rc = resolve_bbox(c, cl[k])) return rc;
     const bool keep_sweep_record = c->last_sweep_valid;
     c->last_valid = false;
-    const double* const no_rows[2] = {nullptr, nullptr};
-    const int rc = consumer_dense(c, cl, no_rows, a->n, cols, cell, d_wf_index, use, d_out);
+    const bool cat16 = c->h_cfg.n_categories > kMaxCategories;
+    RowSource src[2] = {};
+    for (int k = 0; k < sides; ++k) src[k] = cloud_source(*cl[k], cat16, cols[k], cell[k]);
+    const int rc = consumer_dense(c, src, a->n, d_wf_index, use, d_out);
     if (keep_sweep_record) c->last_sweep_valid = true;
     return rc;
 }
@@ -4140,13 +4188,10 @@ static int consumer_dense_host(lchd_ctx* c, const lchd_config* cfg, const Profil
     CTX_LOCK(c);
     const int sides = use.sides;
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    const double* const cells[2] = {sd[0].cell, sides > 1 ? sd[1].cell : nullptr};
     MinImageCell rec[2];
-    const MinImageCell* cell[2] = {nullptr, nullptr};
-    for (int k = 0; k < sides; ++k)
-        if (sd[k].cell) {
-            if (int rc = min_image_record(sd[k].cell, 0, rec[k])) return rc;
-            cell[k] = &rec[k];
-        }
+    const MinImageCell* cell[2];
+    if (int rc = reduce_cells(cells, sides, false, rec, cell)) return rc;
     CTX_GUARD(c);
     if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
     if (int rc = check_wf_index(cfg, wf_index, rows)) return rc;
@@ -4176,17 +4221,20 @@ static int consumer_dense_host(lchd_ctx* c, const lchd_config* cfg, const Profil
     }
     const size_t o_out = (o_wf + sizeof(int32_t) * (size_t)rows + 255) & ~size_t(255);
     auto run = [&]() -> int {
-        const double* d_m[2] = {nullptr, nullptr};
+        RowSource src[2] = {};
         for (int k = 0; k < sides; ++k)  // (given rows: the cloud carries the categories alone)
             if (int rc = lchd_cloud_create(c, sd[k].xyz, sd[k].seq, nullptr, sd[k].cols, &t.clouds[k])) return rc;
         HIP_TRY(hipMalloc(&d_blk, o_out + sizeof(double) * (size_t)rows * K));
-        for (int k = 0; k < sides; ++k)
-            if (sd[k].dmx) {
+        for (int k = 0; k < sides; ++k) {
+            src[k] = cloud_source(*t.clouds[k], cfg->n_categories > kMaxCategories, cols[k], cell[k]);
+            if (sd[k].dmx) {  // (the call's block holds them: rows on the device for the pass)
                 HIP_TRY(hipMemcpy(d_blk + o_m[k], sd[k].dmx, sizeof(double) * (size_t)rows * (size_t)sd[k].cols, hipMemcpyHostToDevice));
-                d_m[k] = reinterpret_cast<const double*>(d_blk + o_m[k]);
+                src[k].kind = RowSource::DEVICE_ROWS;
+                src[k].m = reinterpret_cast<const double*>(d_blk + o_m[k]);
             }
+        }
         if (wf_index) HIP_TRY(hipMemcpy(d_blk + o_wf, wf_index, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice));
-        if (int rc = consumer_dense(c, t.clouds, d_m, rows, cols, cell, wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, use,
+        if (int rc = consumer_dense(c, src, rows, wf_index ? reinterpret_cast<const int32_t*>(d_blk + o_wf) : nullptr, use,
                                     reinterpret_cast<double*>(d_blk + o_out)))
             return rc;
         HIP_TRY(hipMemcpy(out, d_blk + o_out, sizeof(double) * (size_t)rows * K, hipMemcpyDeviceToHost));
