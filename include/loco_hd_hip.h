@@ -531,8 +531,9 @@ int lchd_attribution_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *
  * Row width: a call whose longest environment holds more than `width` points fails with LCHD_EVALUE (the message names the width it
  * takes) after one pass; lchd_sensitivity_needed_width then returns that width, and after a successful call the longest list.
  * Errors, stream and lock rules, capacity repeats and the untouched hints / lchd_ctx_last_sweep: as lchd_attribution_primitives(_dev).
- * The thresholded calls take the structures themselves only: no periodic boxes, cells or image clouds (LCHD_EUNSUPPORTED).  The dense
- * forms are the calls of their own below.  Device groups have no sensitivity call. */
+ * The two thresholded calls right below refuse periodic boxes, cells and image clouds (LCHD_EUNSUPPORTED); lchd_sensitivity_images_dev and
+ * lchd_sensitivity_primitives_periodic further down take them.  The dense forms are calls of their own.  Device groups have no
+ * sensitivity call. */
 int lchd_sensitivity_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors, const int32_t *d_wf_index,
                                     int64_t n_pairs, double threshold_distance, int32_t width, double *d_scores, int32_t *d_count_a,
                                     int32_t *d_idx_a, double *d_dist_a, double *d_g_a, int32_t *d_count_b, int32_t *d_idx_b,
@@ -544,6 +545,46 @@ int lchd_sensitivity_primitives(lchd_ctx *ctx, const lchd_config *cfg, const dou
                                 double *scores, int32_t *count_a, int32_t *idx_a, double *dist_a, double *g_a, int32_t *count_b,
                                 int32_t *idx_b, double *dist_b, double *g_b);
 int64_t lchd_sensitivity_needed_width(lchd_ctx *ctx);
+/* Under periodic boundaries: the same pass on clouds of which any may be an IMAGE CLOUD, with every member resolved to its source atom.
+ * `a` / `b`: whatever lchd_sensitivity_primitives_dev takes, or the image clouds of such clouds, in any mix; threshold_distance <= reach
+ * is checked as the scoring pass checks it.  Per pair and side, next to count / dist / g as above:
+ *   idx[p][K]      the SOURCE atom of every member (i32, padded with -1; for a batch the global index): a ghost names the atom it is an
+ *                  image of, so an atom that enters through two images appears twice
+ *   image[p][K]    its image code (i8): 0 a home atom (or the padding, or a side that is no image cloud), else c0 + 3 c1 + 9 c2 of the
+ *                  periodic section above (c: 0 original, 1 plus, 2 minus, per axis / lattice vector)
+ *   disp[p][K][3]  (f64) x_img[member] - x_img[anchor] per axis, on the coordinates of the cloud the pass searched (an image cloud: the
+ *                  wrapped originals and their ghosts): the very subtractions behind dist, so dist = sqrt(disp . disp) in the scoring
+ *                  order; 0 in slot 0 and in the padding
+ * dS/dx(source atom idx) += g disp / dist and dS/dx(anchor) -= the same.  A wrap is a translation by a lattice vector, so this is the
+ * derivative with respect to the caller's own, unwrapped coordinates; no coordinates are needed to assemble it.  Not included: the
+ * derivative with respect to the box or cell (virial).
+ * List order: the one of the pass on the searched cloud -- ascending by (distance bits, index in that cloud) with the anchor first.  An
+ * image cloud holds the wrapped originals first and the ghosts behind them by (source atom, image code), so among exact ties: home atoms
+ * before ghosts, then the source index, then the image code.  The one-sided derivative at ties follows this order.
+ * Width, lchd_sensitivity_needed_width, the NaN rows of a bad weight-function index, errors, stream and lock rules and capacity repeats:
+ * as lchd_sensitivity_primitives_dev.  The origin map of an image cloud (lchd_cloud_image_origin) is built by the first such call after
+ * the cloud was built or updated, one launch on the context's stream; scoring calls on image clouds never build it. */
+int lchd_sensitivity_images_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors, const int32_t *d_wf_index,
+                                int64_t n_pairs, double threshold_distance, int32_t width, double *d_scores, int32_t *d_count_a,
+                                int32_t *d_idx_a, int8_t *d_image_a, double *d_dist_a, double *d_g_a, double *d_disp_a, int32_t *d_count_b,
+                                int32_t *d_idx_b, int8_t *d_image_b, double *d_dist_b, double *d_g_b, double *d_disp_b);
+/* The same from host arrays; outputs HOST.  box_* HOST [3], cell_* HOST [9] (row 0 = a): at most one of the two per side, NULL = an open
+ * side.  The image cloud of a periodic side is built with reach = threshold_distance and destroyed before the call returns, as
+ * lchd_from_primitives_periodic(_cell) and lchd_radial_primitives do; an anchor index beyond its structure fails with their error. */
+int lchd_sensitivity_primitives_periodic(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a,
+                                         const int32_t *tag_a, int64_t n_a, const double *xyz_b, const int32_t *cat_b, const int32_t *tag_b,
+                                         int64_t n_b, const int64_t *anchors, const int32_t *wf_index, int64_t n_pairs,
+                                         double threshold_distance, int32_t width, const double *box_a, const double *cell_a,
+                                         const double *box_b, const double *cell_b, double *scores, int32_t *count_a, int32_t *idx_a,
+                                         int8_t *image_a, double *dist_a, double *g_a, double *disp_a, int32_t *count_b, int32_t *idx_b,
+                                         int8_t *image_b, double *dist_b, double *g_b, double *disp_b);
+/* The way back from a slot of an image cloud to its source: origin_out[o] (i32) = the source atom of slot o (origin[i] = i for the wrapped
+ * originals), code_out[o] (i8) = its image code (0: an original), HOST arrays of n = lchd_cloud_size(images) entries.  LCHD_EVALUE for a
+ * cloud that is no image cloud or another n.  Stream and lock rules of lchd_cloud_get_coords.  The map is built on the first request
+ * after a build or update (lchd_cloud_create_images*, lchd_cloud_update_images*) and kept with the cloud until the next one. */
+int lchd_cloud_image_origin(lchd_ctx *ctx, lchd_cloud *images, int32_t *origin_out, int8_t *code_out, int64_t n);
+/* The source atoms of an image cloud (its slots 0 .. home - 1 hold them, wrapped); for any other cloud its own size. */
+int64_t lchd_cloud_home_size(const lchd_cloud *cloud);
 /* Dense rows (lchd_attribution_coords_dev / _coords / _dmxs with the sensitivity outputs): pair r = row r of both sides, and EVERY column
  * of a row is a member.  A dense row has no threshold, so no member enters or leaves: g is the whole derivative of the row's score with
  * respect to the row's entries, for any weight function, away from ties (one-sided there).

@@ -169,6 +169,12 @@ _PROTOS = {
     "lchd_sensitivity_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _i32,
                                               _DP, _IP, _IP, _DP, _DP, _IP, _IP, _DP, _DP]),
     "lchd_sensitivity_needed_width": (C.c_int64, [_VP]),
+    "lchd_sensitivity_images_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _i64, _f64, _i32, _VP] + [_VP] * 12),
+    "lchd_sensitivity_primitives_periodic": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64,
+                                                       _i32, _DP, _DP, _DP, _DP, _DP, _IP, _IP, _VP, _DP, _DP, _DP, _IP, _IP, _VP, _DP, _DP,
+                                                       _DP]),
+    "lchd_cloud_image_origin": (C.c_int, [_VP, _VP, _IP, _VP, _i64]),
+    "lchd_cloud_home_size": (C.c_int64, [_VP]),
     "lchd_sensitivity_coords_dev": (C.c_int, [_VP, _VP, _VP, _VP, _i32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lchd_sensitivity_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _IP, _i32,
                                           _DP, _IP, _IP, _DP, _DP, _IP, _IP, _DP, _DP]),

@@ -26,6 +26,8 @@ from . import _native as N
 
 # what LoCoHD.sensitivity_from_primitives returns (DeviceSession.sensitivity: the same fields as torch tensors)
 Sensitivity = namedtuple("Sensitivity", "scores count_a idx_a dist_a g_a count_b idx_b dist_b g_b")
+# what LoCoHD.sensitivity_from_primitives_periodic returns (DeviceSession.sensitivity_images: the same fields as torch tensors)
+PeriodicSensitivity = namedtuple("PeriodicSensitivity", "scores count_a idx_a image_a dist_a g_a disp_a count_b idx_b image_b dist_b g_b disp_b")
 # what LoCoHD.nearest_from_primitives returns (DeviceSession.nearest: the same fields as torch tensors)
 Nearest = namedtuple("Nearest", "scores cols")
 
@@ -950,6 +952,12 @@ class LoCoHD:
         is supported.  Periodic boxes and cells, the dense calls and device groups are not (NotImplementedError)."""
         if box_a is not None or box_b is not None or cell_a is not None or cell_b is not None:
             raise NotImplementedError("sensitivity_from_primitives takes open structures: periodic boxes and cells are not supported")
+        return self._sensitivity_primitives(prim_a, prim_b, anchor_pairs, threshold_distance, width, None)
+
+    def _sensitivity_primitives(self, prim_a, prim_b, anchor_pairs, threshold_distance, width, periodic):
+        """The thresholded sensitivity call and its retry on the row width.  periodic: None (lchd_sensitivity_primitives, a `Sensitivity`) or
+        the checked (box_a, cell_a, box_b, cell_b) arrays, None for an open side (lchd_sensitivity_primitives_periodic, a
+        `PeriodicSensitivity`)."""
         if self._devices is not None:
             raise NotImplementedError("a sensitivity call applies to one device (a device group has no sensitivity call): drop devices=[...]")
         thr = float(threshold_distance)
@@ -968,12 +976,19 @@ class LoCoHD:
             ix = [np.empty((n, k), dtype=np.int32) for _ in range(2)]
             ds = [np.empty((n, k)) for _ in range(2)]
             gs = [np.empty((n, k)) for _ in range(2)]
+            im = [np.zeros((n, k), dtype=np.int8) for _ in range(2)] if periodic is not None else None
+            dp = [np.zeros((n, k, 3)) for _ in range(2)] if periodic is not None else None
             if n == 0:
                 break
             ctx = self._context()
-            rc = N.lib().lchd_sensitivity_primitives(ctx, C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa), N.dp(xb), N.ip(pb.cat),
-                                                     N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx), n, thr, k, N.dp(scores), N.ip(cnt[0]),
-                                                     N.ip(ix[0]), N.dp(ds[0]), N.dp(gs[0]), N.ip(cnt[1]), N.ip(ix[1]), N.dp(ds[1]), N.dp(gs[1]))
+            head = (ctx, C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa), N.dp(xb), N.ip(pb.cat), N.ip(pb.tag), len(xb),
+                    N.lp(anchors), N.ip(idx), n, thr, k)
+            if periodic is None:
+                rc = N.lib().lchd_sensitivity_primitives(*head, N.dp(scores), N.ip(cnt[0]), N.ip(ix[0]), N.dp(ds[0]), N.dp(gs[0]), N.ip(cnt[1]),
+                                                         N.ip(ix[1]), N.dp(ds[1]), N.dp(gs[1]))
+            else:
+                sides = [(N.ip(cnt[j]), N.ip(ix[j]), C.c_void_p(im[j].ctypes.data), N.dp(ds[j]), N.dp(gs[j]), N.dp(dp[j])) for j in range(2)]
+                rc = N.lib().lchd_sensitivity_primitives_periodic(*head, *[N.dp(b) for b in periodic], N.dp(scores), *sides[0], *sides[1])
             need = int(N.lib().lchd_sensitivity_needed_width(ctx))
             if rc == N.EVALUE and width is None and need > k:  # the first guess was too narrow: once more with the width the pairs take
                 k = need
@@ -981,8 +996,72 @@ class LoCoHD:
             N.check(rc)
             if width is None and 0 < need < k:
                 ix, ds, gs = ([np.ascontiguousarray(a[:, :need]) for a in t] for t in (ix, ds, gs))
+                if periodic is not None:
+                    im, dp = ([np.ascontiguousarray(a[:, :need]) for a in t] for t in (im, dp))
             break
+        if periodic is not None:
+            return PeriodicSensitivity(scores, cnt[0], ix[0], im[0], ds[0], gs[0], dp[0], cnt[1], ix[1], im[1], ds[1], gs[1], dp[1])
         return Sensitivity(scores, cnt[0], ix[0], ds[0], gs[0], cnt[1], ix[1], ds[1], gs[1])
+
+    # ---- ... under periodic boundaries (additive) ---------------------------------------------------------
+    # The same pass on the periodic image clouds of the structures, every member resolved to the atom it is an image of
+    # (include/loco_hd_hip.h, lchd_sensitivity_images_dev).  The two calls above keep refusing boxes and cells.
+    def sensitivity_from_primitives_periodic(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                                             threshold_distance: float, *, width: Optional[int] = None, box_a=None, box_b=None, cell_a=None,
+                                             cell_b=None) -> PeriodicSensitivity:
+        """Additive: `sensitivity_from_primitives` for structures in periodic boxes (Lx, Ly, Lz) or triclinic cells (3 x 3, lattice
+        vectors as rows), given per side as `from_primitives` takes them; a side with neither is open.  Returns
+        `PeriodicSensitivity(scores, count_a, idx_a, image_a, dist_a, g_a, disp_a, count_b, ...)`: `idx` names the SOURCE atom of every
+        member -- an atom that enters through two periodic images appears twice --, `image` (int8) its image code (0: the atom itself,
+        else c0 + 3 c1 + 9 c2 with c = 0 original, 1 plus, 2 minus per axis) and `disp` (P, K, 3) the member's displacement from the
+        anchor as the pass saw it (dist = |disp|).  Among exact ties the list order is: home atoms before images, then source index,
+        then image code.  Device groups are not supported (NotImplementedError)."""
+        for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+            if box is not None and cell is not None:
+                raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
+        if self._devices is not None:
+            raise NotImplementedError("a sensitivity call applies to one device (a device group has no sensitivity call): drop devices=[...]")
+        thr = float(threshold_distance)
+        ba = None if box_a is None else periodic_boxes(box_a, 1, thr, "box_a")
+        bb = None if box_b is None else periodic_boxes(box_b, 1, thr, "box_b")
+        ca = None if cell_a is None else periodic_cells(cell_a, 1, thr, "cell_a")
+        cb = None if cell_b is None else periodic_cells(cell_b, 1, thr, "cell_b")
+        return self._sensitivity_primitives(prim_a, prim_b, anchor_pairs, thr, width, (ba, ca, bb, cb))
+
+    @staticmethod
+    def _assemble_gradient_periodic(sens: "PeriodicSensitivity", n_a: int, n_b: int, pair_weights=None):
+        """grad = sum_p v_p dS_p/dx from a PeriodicSensitivity: source atom += v g disp / d, anchor -= the same; the padding, members at
+        d == 0 and non-finite g are skipped; np.add.at in pair order, then slot order.  No coordinates are needed: disp carries them."""
+        v = np.ones(len(sens.scores)) if pair_weights is None else _f64(pair_weights).reshape(-1)
+        if len(v) != len(sens.scores):
+            raise ValueError(f"pair_weights has {len(v)} entries for {len(sens.scores)} anchor pairs")
+        grads = []
+        for n, idx, dist, g, disp in ((n_a, sens.idx_a, sens.dist_a, sens.g_a, sens.disp_a), (n_b, sens.idx_b, sens.dist_b, sens.g_b, sens.disp_b)):
+            grad = np.zeros((n, 3))
+            if idx.size:
+                use = (idx >= 0) & (dist > 0.0) & np.isfinite(g)
+                use[:, 0] = False
+                p, k = np.nonzero(use)  # (row-major: pair order, then slot order)
+                step = (v[p] * g[p, k] / dist[p, k])[:, None] * disp[p, k]
+                np.add.at(grad, idx[p, k], step)
+                np.add.at(grad, idx[p, 0], -step)
+            grads.append(grad)
+        return grads[0], grads[1]
+
+    def gradient_from_primitives_periodic(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                                          threshold_distance: float, pair_weights=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None):
+        """Additive: `gradient_from_primitives` under periodic boundaries: `(scores, grad_a[Na, 3], grad_b[Nb, 3])` assembled on the host
+        from `sensitivity_from_primitives_periodic` in a fixed order.  A wrap is a translation by a lattice vector, so this is the
+        gradient with respect to the coordinates as given (wrapped or not); an atom that enters an environment through two images
+        contributes both terms.  The derivative with respect to the box or cell is not part of it."""
+        if pair_weights is not None:  # (checked in front of the device call: the list length is known from the pairs alone)
+            n_pairs, n_w = len(self._anchor_arrays(anchor_pairs)[0]), len(_f64(pair_weights).reshape(-1))
+            if n_w != n_pairs:
+                raise ValueError(f"pair_weights has {n_w} entries for {n_pairs} anchor pairs")
+        sens = self.sensitivity_from_primitives_periodic(prim_a, prim_b, anchor_pairs, threshold_distance, box_a=box_a, box_b=box_b,
+                                                         cell_a=cell_a, cell_b=cell_b)
+        ga, gb = self._assemble_gradient_periodic(sens, len(prim_a), len(prim_b), pair_weights)
+        return sens.scores, ga, gb
 
     @staticmethod
     def _assemble_gradient(sens: "Sensitivity", xyz_a: np.ndarray, xyz_b: np.ndarray, pair_weights=None):

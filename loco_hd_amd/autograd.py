@@ -10,6 +10,11 @@ ignores points entering or leaving at the threshold (exact when the weight funct
     scores = locohd_scores_dense(session, cloud_b_ref, xyz_a, cat_a)     # the dense rows of from_coords: no threshold, an exact derivative
 
 Forward is DeviceSession.sensitivity_coords, backward is side A of DeviceSession.gradient_coords (dense_side_gradient).
+
+    scores = locohd_scores_periodic(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, threshold_distance, box=(Lx, Ly, Lz))
+
+The movable structure in a periodic box or cell: forward is DeviceSession.sensitivity_images on its image cloud, backward is side A of
+DeviceSession.gradient_images (side_gradient_images).
 """
 from __future__ import annotations
 
@@ -40,6 +45,31 @@ class _LoCoHDScores(torch.autograd.Function):
         s = ctx.sens
         grad_a = ctx.session.side_gradient(s.scores, s.idx_a, s.dist_a, s.g_a, x.to(torch.float64), grad_output)  # side A alone moves
         return grad_a.to(x.dtype), None, None, None, None, None, None
+
+
+class _LoCoHDScoresPeriodic(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, threshold_distance, box, cell):
+        x = xyz_a.detach()
+        mine = []  # the structure and its image cloud: both leave the session again
+        try:
+            mine.append(session.upload(x.cpu().numpy(), np.asarray(cat_a, dtype=np.int32), None if tag_a is None else np.asarray(tag_a, dtype=np.int32)))
+            mine.append(session.periodic_images(mine[0], box, threshold_distance, cell=cell))
+            sens = session.sensitivity_images(mine[1], cloud_b_ref, anchors, threshold_distance)
+        finally:
+            for cl in reversed(mine):
+                session._clouds.remove(cl)
+                N.lib().lchd_cloud_destroy(session._ctx, cl)
+        ctx.session = session
+        ctx.sens = sens
+        ctx.n_atoms, ctx.dtype = x.shape[0], x.dtype
+        return sens.scores
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        s = ctx.sens
+        grad_a = ctx.session.side_gradient_images(s.scores, s.idx_a, s.dist_a, s.g_a, s.disp_a, ctx.n_atoms, grad_output)  # side A alone moves
+        return grad_a.to(ctx.dtype), None, None, None, None, None, None, None, None
 
 
 class _LoCoHDScoresDense(torch.autograd.Function):
@@ -78,3 +108,11 @@ def locohd_scores(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, threshold_
     movable structure -- xyz_a: torch float64 CUDA tensor [Na][3], cat_a / tag_a: its category ids and interned tags (host arrays) --
     against `cloud_b_ref`, a cloud uploaded to `session`; differentiable with respect to xyz_a."""
     return _LoCoHDScores.apply(xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, float(threshold_distance))
+
+
+def locohd_scores_periodic(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, threshold_distance, *, box=None, cell=None):
+    """`locohd_scores` for a movable structure in a periodic box (Lx, Ly, Lz) or triclinic cell (3 x 3, lattice vectors as rows): the
+    structure is uploaded, its image cloud is built with reach = threshold_distance, and both leave the session again.  `cloud_b_ref` is
+    any cloud of `session`, an image cloud (DeviceSession.periodic_images) included.  xyz_a need not be wrapped: a wrap is a translation
+    by a lattice vector, so the gradient is the one with respect to xyz_a as given."""
+    return _LoCoHDScoresPeriodic.apply(xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, float(threshold_distance), box, cell)

@@ -176,6 +176,13 @@ struct lchd_cloud {
     double* d_cells = nullptr; // [cells_cap][kImgCellRecord]
     int32_t cells_cap = 0;
     std::vector<double> h_cells;  // what the last build copied to d_cells (the copy is asynchronous)
+    // the way back from a slot to its source atom (images_origin): built by the first call that asks after a build, stale after every build
+    int64_t n_home = 0;        // source atoms of the last build (slots 0 .. n_home - 1 hold the wrapped originals)
+    int32_t img_boxes = 0;     // boxes / cells the last build was given
+    int32_t* d_img_origin = nullptr;  // [origin_cap] source atom of every slot
+    int8_t* d_img_code = nullptr;     // [origin_cap] image code of every slot (0: an original)
+    int64_t origin_cap = 0;    // follows img_cap
+    bool origin_valid = false;
     // wide: the configuration has more than 255 categories (two-byte ids where the structure carries them)
     CloudView view(bool wide) const {
         const bool two = wide && cat_hi;
@@ -920,6 +927,8 @@ extern "C" void lchd_cloud_destroy(lchd_ctx* c, lchd_cloud* cl) {
     (void)hipFree(cl->d_img_count);
     (void)hipFree(cl->d_img_offset);
     (void)hipFree(cl->d_img_spans);
+    (void)hipFree(cl->d_img_origin);
+    (void)hipFree(cl->d_img_code);
     (void)hipFree(cl->d_boxes);
     (void)hipFree(cl->d_cells);
     if (cl->h_pinned32) (void)hipHostFree(cl->h_pinned32);
@@ -1907,6 +1916,8 @@ static int images_build(lchd_ctx* c, lchd_cloud* img, lchd_cloud* src, const dou
     const int64_t n = src->n;
     if (n > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "periodic images of %lld atoms: at most 2^27", (long long)n);
     hipStream_t s = c->stream;
+    img->origin_valid = false;  // (the ghosts move with the coordinates: the map is built again by the first call that needs it)
+    img->n_home = 0;
     img->n = 0;  // (until the build has succeeded)
     img->n_struct = src->n_struct;
     img->struct_size = 0;
@@ -1983,8 +1994,55 @@ static int images_build(lchd_ctx* c, lchd_cloud* img, lchd_cloud* src, const dou
     }
     if (!src->sid && img->sid) { (void)hipFree(img->sid); img->sid = nullptr; }
     img->n = total;
+    img->n_home = n;
+    img->img_boxes = n_boxes;
     return LCHD_OK;
 }
+
+// origin / code of every slot of a built image cloud, on the context's stream (behind the build, in front of whatever reads them).
+// Nothing is launched while the map of the last build stands; the arrays follow the cloud's capacity, so they move only when it grows.
+static int images_origin(lchd_ctx* c, lchd_cloud* img) {
+    if (img->origin_valid || img->n == 0) return LCHD_OK;
+    if (img->origin_cap < img->img_cap) {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (a call that read the old arrays has finished)
+        img->origin_cap = 0;
+        if (int rc = grow_array(img->d_img_origin, (size_t)img->img_cap)) return rc;
+        if (int rc = grow_array(img->d_img_code, (size_t)img->img_cap)) return rc;
+        img->origin_cap = img->img_cap;
+    }
+    ImageArgs ia{};
+    ia.src = CloudView{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (int32_t)img->n_home, img->sid, img->n_struct, 0};
+    ia.boxes = img->img_cell ? nullptr : img->d_boxes;
+    ia.cells = img->img_cell ? img->d_cells : nullptr;
+    ia.n_boxes = img->img_boxes;
+    ia.reach = img->reach;
+    ia.x = img->x; ia.y = img->y; ia.z = img->z;
+    ia.capacity = std::min(img->n, img->origin_cap);
+    ia.count = img->d_img_count;
+    ia.offset = img->d_img_offset;
+    ia.span_sum = img->n_home > kImgScanSpan ? img->d_img_spans : nullptr;
+    launch_img_origin(c->stream, ia, img->d_img_origin, img->d_img_code);
+    HIP_TRY(hipGetLastError());
+    img->origin_valid = true;
+    return LCHD_OK;
+}
+
+/* origin / code of every slot of an image cloud as HOST arrays (lchd_cloud_get_coords' rules). */
+extern "C" int lchd_cloud_image_origin(lchd_ctx* c, lchd_cloud* img, int32_t* origin_out, int8_t* code_out, int64_t n) {
+    CTX_LOCK(c);
+    if (!c || !img || !origin_out || !code_out) return fail(LCHD_EVALUE, "null argument");
+    if (!img->images) return fail(LCHD_EVALUE, "not an image cloud (lchd_cloud_create_images)");
+    if (n != img->n) return fail(LCHD_EVALUE, "the cloud holds %lld atoms, not %lld", (long long)img->n, (long long)n);
+    CTX_GUARD(c);
+    if (int rc = images_origin(c, img)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n) {
+        HIP_TRY(hipMemcpy(origin_out, img->d_img_origin, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(code_out, img->d_img_code, (size_t)n, hipMemcpyDeviceToHost));
+    }
+    return LCHD_OK;
+}
+extern "C" int64_t lchd_cloud_home_size(const lchd_cloud* cl) { return cl ? (cl->images ? cl->n_home : cl->n) : -1; }
 
 static int images_create(lchd_ctx* c, lchd_cloud* src, const double* boxes, int32_t n_boxes, double reach, bool cell, lchd_cloud** out) {
     CTX_LOCK(c);
@@ -3711,6 +3769,7 @@ struct PairConsumer {
     bool records;       // its kernel reads the pair records of k_pair_meta (a dense pass carves them)
     int width;          // > 0: a sensitivity call with rows of this many slots
     SensitivityOut sens;  // ... and its DEVICE outputs, or all null: they are carved from the pass's one output block (sens_carve)
+    bool images;        // ... which resolves members of image clouds to source atoms (launch_sens_resolve: image and disp outputs)
 };
 static const PairConsumer kComposition{{}, "a composition profile", "composition", "anchors", 1, false};
 static const PairConsumer kAttribution{{}, "an attribution", "attribution", "anchor pairs", 2, true};
@@ -3720,26 +3779,35 @@ static PairConsumer radial_consumer(const double* edges, int32_t n_edges) {
     for (int32_t k = 0; k < n_edges; ++k) use.edges.e[k] = edges[k];
     return use;
 }
-static PairConsumer sensitivity_consumer(int32_t width, const SensitivityOut& out) {
+static PairConsumer sensitivity_consumer(int32_t width, const SensitivityOut& out, bool images = false) {
     PairConsumer use{{}, "a sensitivity call", "sensitivity", "anchor pairs", 2, true};
     use.width = width;
     use.sens = out;
+    use.images = images;
     return use;
 }
-// A sensitivity call's outputs as ONE block of n * (5 w + 2) doubles (host or device): scores | g_a | g_b | dist_a | dist_b | idx_a | idx_b |
-// count_a | count_b -- what the host call moves in one copy.
-static SensitivityOut sens_carve(double* blk, int64_t n, int w) {
+// doubles per pair of a sensitivity call's block: the nine arrays, and with `images` the two disp rows and the two image rows behind them
+static size_t sens_row(int w, bool images) {
+    return 5 * (size_t)w + 2 + (images ? 6 * (size_t)w + (2 * (size_t)w + 7) / 8 : 0);
+}
+// A sensitivity call's outputs as ONE block of n * sens_row doubles (host or device): scores | g_a | g_b | dist_a | dist_b | idx_a | idx_b |
+// count_a | count_b [| disp_a | disp_b | image_a | image_b] -- what the host call moves in one copy.
+static SensitivityOut sens_carve(double* blk, int64_t n, int w, bool images = false) {
     const size_t nw = (size_t)n * (size_t)w;
     SensitivityOut o{};
     o.scores = blk;
     o.g_a = blk + n; o.g_b = o.g_a + nw; o.dist_a = o.g_b + nw; o.dist_b = o.dist_a + nw;
     o.idx_a = reinterpret_cast<int32_t*>(o.dist_b + nw); o.idx_b = o.idx_a + nw;
     o.count_a = o.idx_b + nw; o.count_b = o.count_a + n;
+    if (images) {
+        o.disp_a = blk + (size_t)n * (5 * (size_t)w + 2); o.disp_b = o.disp_a + 3 * nw;
+        o.image_a = reinterpret_cast<int8_t*>(o.disp_b + 3 * nw); o.image_b = o.image_a + nw;
+    }
     return o;
 }
 // doubles per entry in the consumer's output: the bins / the categories of the context's configuration / a sensitivity call's block
 static size_t consumer_row(const lchd_ctx* c, const PairConsumer& use) {
-    if (use.width) return 5 * (size_t)use.width + 2;
+    if (use.width) return sens_row(use.width, use.images);
     return use.edges.n ? (size_t)use.edges.n - 1 : (size_t)c->h_cfg.n_categories;
 }
 static int consumer_limits(const lchd_ctx* c, const PairConsumer& use) {
@@ -3760,6 +3828,7 @@ static int consumer_limits(const lchd_ctx* c, const PairConsumer& use) {
 struct SensLists {
     IndexedStore env[2];
     const IndexedArgs* cells;
+    lchd_cloud* cl[2];  // the clouds the lists index (read when the consumer resolves image clouds)
 };
 static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use, double* d_out, const SensLists* lists = nullptr) {
     const int n_wf = c->h_cfg.n_wf;
@@ -3783,8 +3852,21 @@ static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use,
         sa.env_b = lists->env[1];
         sa.n_categories = c->h_cfg.n_categories;
         sa.width = use.width;
-        sa.out = use.sens.scores ? use.sens : sens_carve(d_out, sw.n_pairs, use.width);
+        sa.out = use.sens.scores ? use.sens : sens_carve(d_out, sw.n_pairs, use.width, use.images);
         launched = (!lists->cells || launch_env_indexed(s, *lists->cells)) && launch_sensitivity(s, sa);
+        if (launched && use.images) {
+            SensResolveArgs ra{};
+            int32_t* const idx[2] = {sa.out.idx_a, sa.out.idx_b};
+            int8_t* const image[2] = {sa.out.image_a, sa.out.image_b};
+            double* const disp[2] = {sa.out.disp_a, sa.out.disp_b};
+            for (int k = 0; k < 2; ++k) {
+                lchd_cloud* const cl = lists->cl[k];
+                ra.s[k] = SensResolveSide{cl->x, cl->y, cl->z, cl->n, cl->images ? cl->d_img_origin : nullptr, cl->images ? cl->d_img_code : nullptr,
+                                          idx[k], image[k], disp[k]};
+            }
+            ra.anchors = sw.anchors; ra.n_pairs = sw.n_pairs; ra.width = use.width;
+            launched = launch_sens_resolve(s, ra);
+        }
     } else if (use.edges.n) {
         launch_radial_bounds(s, c->d_cfg, n_wf, use.edges, reinterpret_cast<double*>(c->d_radial_bounds));
         RadialArgs ra{};
@@ -3899,7 +3981,7 @@ static int consumer_prims_pass(lchd_ctx* c, const ConsumerRequest& R, int cap, u
             ix.s[k].uniq = sb[k]->uniq;
         }
     }
-    const SensLists lists{{ix.s[0].env, ix.s[1].max_envs > 0 ? ix.s[1].env : ix.s[0].env}, &ix};  // (both sides one object: one set of lists)
+    const SensLists lists{{ix.s[0].env, ix.s[1].max_envs > 0 ? ix.s[1].env : ix.s[0].env}, &ix, {a, b}};  // (both sides one object: one set of lists)
     if (int rc = consumer_enqueue(c, sw, R.use, R.out, R.use.width ? &lists : nullptr)) return rc;
     mark(c, 4);
     for (int k = 0; k < sides; ++k)
@@ -3931,6 +4013,9 @@ static int consumer_primitives_dev(lchd_ctx* c, lchd_cloud* const* cl, const int
     CTX_GUARD(c);
     for (int k = 0; k < use.sides; ++k)
         if (int rc = resolve_bbox(c, cl[k])) return rc;
+    if (use.images)  // (the origin maps the resolve step reads: built here, on the stream in front of the pass, if the last build left none)
+        for (int k = 0; k < use.sides; ++k)
+            if (cl[k]->images) if (int rc = images_origin(c, cl[k])) return rc;
     const bool keep_sweep_record = c->last_sweep_valid;  // (host data: the record of the last scoring pass stands)
     c->last_valid = false;                               // (its arrays do not: the arena is laid out anew)
     const ConsumerRequest R{{a, b}, d_anchors, d_wf_index, n, thr, use, d_out};
@@ -4391,21 +4476,28 @@ extern "C" int lchd_attribution_dmxs(lchd_ctx* c, const lchd_config* cfg, const 
 }
 
 // neighbour sensitivities: every statistical distance.  The thresholded pass is the attribution call's with the indexed lists (built from
-// the pass's cell lists) and k_sensitivity (lchd_sensitivity.hip) behind the record pass; no periodic boxes, cells or image clouds.
-// A host call's pass writes ONE block (sens_carve), which `pass` receives; the nine HOST arrays of `o` are filled from it.
+// the pass's cell lists) and k_sensitivity (lchd_sensitivity.hip) behind the record pass; periodic boxes, cells and image clouds only in
+// the calls that resolve the members (lchd_sensitivity_images_dev / _primitives_periodic: k_sens_resolve_images behind the two).
+// A host call's pass writes ONE block (sens_carve), which `pass` receives; the HOST arrays of `o` are filled from it: the nine, and the
+// four of a resolving call where `o` names them.
 template <class Pass>
 static int sens_host_call(int64_t n_pairs, int32_t width, const SensitivityOut& o, Pass&& pass) {
     const size_t n = n_pairs > 0 ? (size_t)n_pairs : 0, nw = n * (size_t)width;
-    double* blk = n ? static_cast<double*>(malloc(sizeof(double) * n * (5 * (size_t)width + 2))) : nullptr;
+    const bool images = o.disp_a != nullptr;
+    double* blk = n ? static_cast<double*>(malloc(sizeof(double) * n * sens_row(width, images))) : nullptr;
     if (n && !blk) return fail(LCHD_EUNSUPPORTED, "no host memory for the outputs of %lld pairs", (long long)n_pairs);
     const int rc = pass(blk);
     if (rc == LCHD_OK && n) {
-        const SensitivityOut b = sens_carve(blk, n_pairs, width);
+        const SensitivityOut b = sens_carve(blk, n_pairs, width, images);
         memcpy(o.scores, b.scores, 8 * n);
         memcpy(o.g_a, b.g_a, 8 * nw); memcpy(o.g_b, b.g_b, 8 * nw);
         memcpy(o.dist_a, b.dist_a, 8 * nw); memcpy(o.dist_b, b.dist_b, 8 * nw);
         memcpy(o.idx_a, b.idx_a, 4 * nw); memcpy(o.idx_b, b.idx_b, 4 * nw);
         memcpy(o.count_a, b.count_a, 4 * n); memcpy(o.count_b, b.count_b, 4 * n);
+        if (images) {
+            memcpy(o.disp_a, b.disp_a, 24 * nw); memcpy(o.disp_b, b.disp_b, 24 * nw);
+            memcpy(o.image_a, b.image_a, nw); memcpy(o.image_b, b.image_b, nw);
+        }
     }
     free(blk);
     return rc;
@@ -4448,6 +4540,40 @@ extern "C" int lchd_sensitivity_primitives(lchd_ctx* c, const lchd_config* cfg, 
     });
 }
 extern "C" int64_t lchd_sensitivity_needed_width(lchd_ctx* c) { return c ? c->sens_needed : 0; }
+
+// ... that name source atoms: the same pass on clouds of which any may be an image cloud, then k_sens_resolve_images on both sides' rows.
+extern "C" int lchd_sensitivity_images_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
+                                           int64_t n_pairs, double thr, int32_t width, double* d_scores, int32_t* d_count_a, int32_t* d_idx_a,
+                                           int8_t* d_image_a, double* d_dist_a, double* d_g_a, double* d_disp_a, int32_t* d_count_b,
+                                           int32_t* d_idx_b, int8_t* d_image_b, double* d_dist_b, double* d_g_b, double* d_disp_b) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (int rc = sens_args(c, n_pairs, width)) return rc;
+    if (n_pairs > 0 && (!d_scores || !d_count_a || !d_idx_a || !d_image_a || !d_dist_a || !d_g_a || !d_disp_a || !d_count_b || !d_idx_b ||
+                        !d_image_b || !d_dist_b || !d_g_b || !d_disp_b))
+        return fail(LCHD_EVALUE, "null output pointer");
+    const SensitivityOut o{d_scores, d_count_a, d_count_b, d_idx_a, d_idx_b, d_dist_a, d_dist_b, d_g_a, d_g_b, d_disp_a, d_disp_b, d_image_a, d_image_b};
+    lchd_cloud* const cl[2] = {a, b};
+    return consumer_primitives_dev(c, cl, d_anchors, d_wf_index, n_pairs, thr, sensitivity_consumer(width, o, true), d_scores);
+}
+extern "C" int lchd_sensitivity_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a,
+                                                    const int32_t* tag_a, int64_t n_a, const double* xyz_b, const int32_t* cat_b,
+                                                    const int32_t* tag_b, int64_t n_b, const int64_t* anchors, const int32_t* wf_index,
+                                                    int64_t n_pairs, double thr, int32_t width, const double* box_a, const double* cell_a,
+                                                    const double* box_b, const double* cell_b, double* scores, int32_t* count_a,
+                                                    int32_t* idx_a, int8_t* image_a, double* dist_a, double* g_a, double* disp_a,
+                                                    int32_t* count_b, int32_t* idx_b, int8_t* image_b, double* dist_b, double* g_b,
+                                                    double* disp_b) {
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = sens_args(c, n_pairs, width)) return rc;
+    if (n_pairs > 0 && (!scores || !count_a || !idx_a || !image_a || !dist_a || !g_a || !disp_a || !count_b || !idx_b || !image_b || !dist_b ||
+                        !g_b || !disp_b))
+        return fail(LCHD_EVALUE, "null output pointer");
+    const SensitivityOut o{scores, count_a, count_b, idx_a, idx_b, dist_a, dist_b, g_a, g_b, disp_a, disp_b, image_a, image_b};
+    return sens_host_call(n_pairs, width, o, [&](double* blk) {
+        return pair_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, box_a, cell_a,
+                                    box_b, cell_b, sensitivity_consumer(width, SensitivityOut{}, true), blk);
+    });
+}
 
 // ... and of dense rows: the attribution calls of the same name with the other consumer.  consumer_dense builds the indexed lists of
 // both sides' rows (launch_rows_indexed) next to the scoring stores, which stay in front of the record pass: its records, status

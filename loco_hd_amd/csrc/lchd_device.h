@@ -359,6 +359,10 @@ struct ImageArgs {
 void launch_img_count(hipStream_t s, const ImageArgs& a);  // wrapped originals, counts, bounding box (of originals and ghosts)
 void launch_img_scan(hipStream_t s, const ImageArgs& a);   // offsets, span sums, total
 void launch_img_emit(hipStream_t s, const ImageArgs& a);   // the ghosts
+// The way back from a slot of a built image cloud to its source atom (k_img_origin): origin[o] = the source atom (origin[i] = i for the
+// wrapped originals), code[o] = its image code (0: an original).  Reads only what the build left in the image cloud: `a` as the build
+// filled it, with src.n = the source atoms and src.sid = the image cloud's own structure ids; capacity bounds origin / code.
+void launch_img_origin(hipStream_t s, const ImageArgs& a, int32_t* origin, int8_t* code);
 void launch_fill_sqrt_tables(hipStream_t s, double* sqrt_tab, double* rsqrt_tab);  // 65536 entries each
 void launch_fill_pow_tables(hipStream_t s, double* tab /* [2][65536] */, double exponent);  // k^(1/e), k^(-1/e)
 
@@ -504,6 +508,9 @@ struct SensitivityOut {      // all DEVICE; K = SensitivityArgs::width
     int32_t *count_a, *count_b;        // [P] members incl. the anchor (0: an unusable pair)
     int32_t *idx_a, *idx_b;            // [P][K], padded with -1
     double *dist_a, *dist_b, *g_a, *g_b;  // [P][K], padded with 0
+    // launch_sens_resolve only (null otherwise): the image code of every member and its displacement from the anchor
+    double *disp_a, *disp_b;           // [P][K][3], padded with 0
+    int8_t *image_a, *image_b;         // [P][K], padded with 0
 };
 struct SensitivityArgs {
     SweepArgs sw;            // as RadialArgs::sw; the stores only through the pair records
@@ -514,6 +521,24 @@ struct SensitivityArgs {
 };
 bool launch_sensitivity(hipStream_t s, const SensitivityArgs& a);  // false: nothing launched (more than kSensitivityMaxCategories categories)
 void init_sensitivity_kernels();  // per device, as init_radial_kernels
+// Behind launch_sensitivity on lists that index image clouds (k_sens_resolve_images): per member slot the displacement from the anchor in
+// the cloud the list indexes, the image code, and -- in place -- the source atom instead of the cloud index.
+struct SensResolveSide {
+    const double *x, *y, *z;   // the cloud the side's lists index (an image cloud: wrapped originals, then ghosts)
+    int64_t n;                 // its atoms
+    const int32_t* origin;     // [n] launch_img_origin's map, or null: not an image cloud (idx stays, image = 0)
+    const int8_t* code;        // [n] with origin
+    int32_t* idx;              // [P][K] in: cloud indices (-1: padding), out: source atoms
+    int8_t* image;             // [P][K] out
+    double* disp;              // [P][K][3] out
+};
+struct SensResolveArgs {
+    SensResolveSide s[2];
+    const int64_t* anchors;    // [P][2] the pair list of the pass
+    int64_t n_pairs;
+    int32_t width;             // K
+};
+bool launch_sens_resolve(hipStream_t s, const SensResolveArgs& a);  // false: nothing launched (more slots than a grid covers)
 // Cross-scoring (lchd_cross.hip): the pair records of one row tile -- anchors_a[row0 .. row0 + rows) against all n_b anchors of B, pair
 // p = i * n_b + j -- written on the device in the [P][2] int64 form the thresholded pass reads, with the constant wf index when wf >= 0
 // (wf_out is not touched otherwise); and the reduction of a tile's [rows][n_b] scores to the k smallest (score, column) per row, ascending.

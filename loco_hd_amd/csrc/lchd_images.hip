@@ -245,6 +245,41 @@ __global__ __launch_bounds__(kImgScanSpan) void k_img_emit_cell(ImageArgs a) {
             }
 }
 
+// ---- the way back ---------------------------------------------------------------------------------------------------------------
+// One lane per source atom: origin / code of its own slot and of its ghosts.  Nothing of the build is kept but count / offset / span_sum
+// and the wrapped coordinates in slot i, so the per-axis choices are derived again from those by the rule that counted and emitted them
+// (img_choices on the box edges, img_choices_cell on the fractional coordinates), and the codes are walked in the emit kernels' order:
+// ghost number `rank` of atom i sits at n + span_sum[i / span] + offset[i] + rank.  CELL picks the rule; the rest is one body.
+template <bool CELL>
+__global__ __launch_bounds__(kImgScanSpan) void k_img_origin(ImageArgs a, int32_t* __restrict__ origin, int8_t* __restrict__ code) {
+    const int64_t i = (int64_t)blockIdx.x * kImgScanSpan + threadIdx.x;
+    if (i >= a.src.n || i >= a.capacity) return;
+    const double p[3] = {a.x[i], a.y[i], a.z[i]};
+    int ch[3];  // bit c: choice c of this axis exists (0 original, 1 plus, 2 minus)
+    if constexpr (CELL) {
+        const double* R = img_cell(a, i);
+        double g[3];
+        img_frac(R, p, g);
+        for (int k = 0; k < 3; ++k) ch[k] = img_choices_cell(g[k], R[18 + k], a.reach) << 1 | 1;
+    } else {
+        const double* L = img_box(a, i);
+        for (int k = 0; k < 3; ++k) ch[k] = img_choices(p[k], L[k], a.reach) << 1 | 1;
+    }
+    origin[i] = (int32_t)i;
+    code[i] = 0;
+    int64_t o = (int64_t)a.src.n + (int64_t)((a.span_sum ? a.span_sum[i / kImgScanSpan] : 0ull) + a.offset[i]);
+    const int64_t end = min(o + (int64_t)a.count[i], a.capacity);  // (what was counted and emitted: never more slots than those)
+    for (int c2 = 0; c2 < 3; ++c2)
+        for (int c1 = 0; c1 < 3; ++c1)
+            for (int c0 = 0; c0 < 3; ++c0) {
+                if (!((ch[0] >> c0) & (ch[1] >> c1) & (ch[2] >> c2) & 1) || (c0 | c1 | c2) == 0) continue;
+                if (o >= end) return;
+                origin[o] = (int32_t)i;
+                code[o] = (int8_t)(c0 + 3 * c1 + 9 * c2);
+                ++o;
+            }
+}
+
 static unsigned img_blocks(int64_t n) { return (unsigned)((n + kImgScanSpan - 1) / kImgScanSpan); }
 void launch_img_count(hipStream_t s, const ImageArgs& a) {
     static const unsigned long long init[7] = {~0ull, ~0ull, ~0ull, 0ull, 0ull, 0ull, 0ull};
@@ -264,6 +299,11 @@ void launch_img_scan(hipStream_t s, const ImageArgs& a) {
 void launch_img_emit(hipStream_t s, const ImageArgs& a) {
     if (a.cells) k_img_emit_cell<<<img_blocks(a.src.n), kImgScanSpan, 0, s>>>(a);
     else k_img_emit<<<img_blocks(a.src.n), kImgScanSpan, 0, s>>>(a);
+}
+void launch_img_origin(hipStream_t s, const ImageArgs& a, int32_t* origin, int8_t* code) {
+    if (a.src.n <= 0) return;
+    if (a.cells) k_img_origin<true><<<img_blocks(a.src.n), kImgScanSpan, 0, s>>>(a, origin, code);
+    else k_img_origin<false><<<img_blocks(a.src.n), kImgScanSpan, 0, s>>>(a, origin, code);
 }
 
 }  // namespace lchd

@@ -25,6 +25,8 @@
 //                   and writes g to the event's slot of the pair's row of side A or B.  The same walk sums dF * H: the call returns
 //                   the scores without a second pass.  No floating-point atomics: every output element has one writer, and the
 //                   score is one wave reduction in lane order.
+//   k_sens_resolve_images   behind the two above when a list indexes a periodic image cloud: per member slot the displacement from the
+//                   anchor, the image code, and the source atom in place of the cloud index (see the kernel)
 #include "lchd_sweep_common.h"
 
 namespace lchd {
@@ -520,6 +522,84 @@ bool launch_sensitivity(hipStream_t s, const SensitivityArgs& a) {
     else if (wb * 2 <= (size_t)kSensDynMax) go(std::integral_constant<int, 2>{});
     else if (wb <= (size_t)kSensDynMax) go(std::integral_constant<int, 1>{});
     else return false;
+    return true;
+}
+
+// ---- lists that index image clouds ---------------------------------------------------------------------------------------------------
+// Behind k_env_indexed + k_sensitivity on an image cloud a slot names a position of that cloud: a wrapped original or a ghost.  This
+// kernel turns the [P][K] slots of both sides (blockIdx.y) into what a caller can use, in place:
+//   disp   x_img[member] - x_img[anchor] per axis: the three subtractions env_dist2 made (same operands, uncontracted), so
+//          dist = sqrt(disp . disp) in its order; 0 in slot 0 and in the padding
+//   image  the member's image code (0: a home atom, the padding, a side that is no image cloud)
+//   idx    the member's source atom (unchanged for a side that is no image cloud; the padding stays -1)
+// The list order stays the one k_env_indexed gave: ascending by (distance bits, image-cloud index).  The wrapped originals come first in
+// an image cloud and the ghosts follow in (source atom, image code) order, so among exact ties: home atoms before ghosts, then the
+// source index, then the image code.
+// Lane-to-slot mapping: idx is rewritten in place, so the lane that reads a slot must be the one that writes it -- a lane owns whole
+// slots.  Four consecutive slots of the flat [P * K] range per lane make every stream a full 16-byte access where the arrays are
+// 16-byte aligned (VEC): one 16-byte load and store of idx, six 16-byte stores of its 96 contiguous bytes of disp, one 4-byte store of
+// image; consecutive lanes continue where the last ended, so a wavefront covers 1 KiB of idx and 6 KiB of disp without a gap.  The
+// coordinate reads are gathers by nature (member and anchor positions).  Every output element has one writer; no atomics.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_sens_resolve_images(SensResolveArgs ra) {
+    const int side = blockIdx.y;
+    const SensResolveSide& S = ra.s[side];
+    const int64_t K = ra.width, slots = ra.n_pairs * K;
+    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (s0 >= slots) return;
+    const int m = (int)(slots - s0 < 4 ? slots - s0 : 4);
+    const bool wide = VEC && m == 4;
+    int32_t id[4] = {-1, -1, -1, -1};
+    if (wide) {
+        const int4 v = *reinterpret_cast<const int4*>(S.idx + s0);
+        id[0] = v.x; id[1] = v.y; id[2] = v.z; id[3] = v.w;
+    } else {
+        for (int q = 0; q < m; ++q) id[q] = S.idx[s0 + q];
+    }
+    int8_t im[4] = {0, 0, 0, 0};
+    double d[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int64_t p = s0 / K, k = s0 - p * K;
+    bool fresh = true, anchored = false;
+    double ax = 0.0, ay = 0.0, az = 0.0;
+    for (int q = 0; q < m; ++q, ++k) {
+        if (k == K) { k = 0; ++p; fresh = true; }
+        if (fresh) {  // (an anchor below the source's size sits at its own index in the image cloud: the wrapped original)
+            const int64_t an = ra.anchors[2 * p + side];
+            anchored = an >= 0 && an < S.n;
+            if (anchored) { ax = S.x[an]; ay = S.y[an]; az = S.z[an]; }
+            fresh = false;
+        }
+        const int64_t mem = id[q];
+        if (mem < 0 || mem >= S.n || !anchored) continue;  // padding (or a pair the pass has flagged): idx stays, image 0, disp 0
+        if (k != 0) { d[3 * q] = S.x[mem] - ax; d[3 * q + 1] = S.y[mem] - ay; d[3 * q + 2] = S.z[mem] - az; }
+        if (S.origin) { im[q] = S.code[mem]; id[q] = S.origin[mem]; }
+    }
+    if (wide) {
+        if (S.origin) *reinterpret_cast<int4*>(S.idx + s0) = make_int4(id[0], id[1], id[2], id[3]);
+        *reinterpret_cast<uint32_t*>(S.image + s0) = (uint32_t)(uint8_t)im[0] | (uint32_t)(uint8_t)im[1] << 8 | (uint32_t)(uint8_t)im[2] << 16 |
+                                                    (uint32_t)(uint8_t)im[3] << 24;
+        double2* const out = reinterpret_cast<double2*>(S.disp + 3 * s0);
+        for (int j = 0; j < 6; ++j) out[j] = make_double2(d[2 * j], d[2 * j + 1]);
+    } else {
+        for (int q = 0; q < m; ++q) {
+            if (S.origin) S.idx[s0 + q] = id[q];
+            S.image[s0 + q] = im[q];
+            for (int j = 0; j < 3; ++j) S.disp[3 * (s0 + q) + j] = d[3 * q + j];
+        }
+    }
+}
+
+bool launch_sens_resolve(hipStream_t s, const SensResolveArgs& a) {
+    if (a.n_pairs <= 0) return true;
+    if (a.width < 1) return false;
+    const int64_t quads = (a.n_pairs * (int64_t)a.width + 3) / 4, blocks = (quads + 255) / 256;
+    if (blocks > 0x7FFFFFFF) return false;
+    uintptr_t low = 0;  // 16-byte accesses where every array of both sides allows them
+    for (int k = 0; k < 2; ++k)
+        low |= reinterpret_cast<uintptr_t>(a.s[k].idx) | reinterpret_cast<uintptr_t>(a.s[k].disp) | (reinterpret_cast<uintptr_t>(a.s[k].image) & 3) << 2;
+    const dim3 grid((unsigned)blocks, 2);
+    if ((low & 15) == 0) k_sens_resolve_images<true><<<grid, 256, 0, s>>>(a);
+    else k_sens_resolve_images<false><<<grid, 256, 0, s>>>(a);
     return true;
 }
 

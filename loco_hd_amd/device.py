@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .api import LoCoHD, Nearest, Sensitivity, dense_cells, periodic_boxes, periodic_cells
+from .api import LoCoHD, Nearest, PeriodicSensitivity, Sensitivity, dense_cells, periodic_boxes, periodic_cells
 
 
 def last_sweep_of(ctx):
@@ -400,6 +400,79 @@ class DeviceSession:
             if not fixed and 0 < need < k:  # rows as wide as the longest environment, as the host call returns them
                 res = Sensitivity(*[t[:, :need].contiguous() if t.dim() == 2 else t for t in res])
             return res
+
+    def image_origin(self, images):
+        """The way back from every slot of an image cloud (periodic_images) to its source: `(origin, code)` as NumPy arrays, int32 source
+        atom (origin[i] = i for the wrapped atoms themselves) and int8 image code (0: no shift) per slot (lchd_cloud_image_origin)."""
+        n = int(N.lib().lchd_cloud_size(images))
+        origin, code = np.empty(max(n, 0), dtype=np.int32), np.empty(max(n, 0), dtype=np.int8)
+        N.check(N.lib().lchd_cloud_image_origin(self._ctx, images, N.ip(origin), C.c_void_p(code.ctypes.data), n))
+        return origin, code
+
+    def sensitivity_images(self, cloud_a, cloud_b, anchors, threshold_distance: float, out=None, wf_index=None, *, width=None):
+        """`sensitivity` for clouds of which any may be an image cloud (periodic_images), every member resolved to its source atom
+        (LoCoHD.sensitivity_from_primitives_periodic).  Returns a `PeriodicSensitivity` of torch CUDA tensors: next to the fields of
+        `sensitivity`, idx names source atoms (global indices for a batch), image_a / image_b [P][K] int8 are the image codes and
+        disp_a / disp_b [P][K][3] f64 the members' displacements from their anchors.  K, `out` (a `PeriodicSensitivity` of such tensors)
+        and `width` as in `sensitivity`; ValueError naming the width the pairs take if K is too small (lchd_sensitivity_images_dev)."""
+        torch = self.torch
+        assert anchors.is_cuda and anchors.dtype == torch.int64 and anchors.is_contiguous()
+        p = anchors.shape[0]
+        wf_ptr = None
+        if wf_index is not None:
+            assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= p
+            wf_ptr = C.c_void_p(wf_index.data_ptr())
+        fixed = out is not None or width is not None
+        k = int(out.idx_a.shape[1]) if out is not None else (128 if width is None else int(width))
+        kinds = {"scores": torch.float64, "count": torch.int32, "idx": torch.int32, "image": torch.int8, "dist": torch.float64, "g": torch.float64,
+                 "disp": torch.float64}
+        while True:
+            shapes = {"scores": (p,), "count": (p,), "disp": (p, k, 3)}
+            if out is None:
+                res = PeriodicSensitivity(*[torch.empty(shapes.get(f.split("_")[0], (p, k)), dtype=kinds[f.split("_")[0]], device=anchors.device)
+                                            for f in PeriodicSensitivity._fields])
+            else:
+                res = out
+                for name, t in zip(PeriodicSensitivity._fields, res):
+                    kind = name.split("_")[0]
+                    assert t.is_cuda and t.dtype == kinds[kind] and t.is_contiguous() and tuple(t.shape) == shapes.get(kind, (p, k)), name
+            if p == 0:
+                return res
+            rc = N.lib().lchd_sensitivity_images_dev(self._ctx, cloud_a, cloud_b, C.c_void_p(anchors.data_ptr()), wf_ptr, p,
+                                                     float(threshold_distance), k, *[C.c_void_p(t.data_ptr()) for t in res])
+            need = int(N.lib().lchd_sensitivity_needed_width(self._ctx))
+            if rc == N.EVALUE and not fixed and need > k:
+                k = need
+                continue
+            N.check(rc)
+            if not fixed and 0 < need < k:  # rows as wide as the longest environment, as the host call returns them
+                res = PeriodicSensitivity(*[t[:, :need].contiguous() if t.dim() >= 2 else t for t in res])
+            return res
+
+    def gradient_images(self, cloud_a, cloud_b, anchors, threshold_distance: float, pair_weights=None, wf_index=None):
+        """`(scores, grad_a, grad_b)` with grad = sum_p v_p dS_p/dx (LoCoHD.gradient_from_primitives_periodic) as torch CUDA tensors, for
+        clouds of which any may be an image cloud.  grad_a / grad_b have one row per SOURCE atom (lchd_cloud_home_size): a ghost's term
+        goes to the atom it is an image of.  pair_weights: v, a tensor [P] (default: ones).  Assembled from `sensitivity_images` with
+        torch.Tensor.index_add_: its summation order, and so the last bits, follow torch's determinism setting."""
+        sens = self.sensitivity_images(cloud_a, cloud_b, anchors, threshold_distance, wf_index=wf_index)
+        na, nb = (int(N.lib().lchd_cloud_home_size(cl)) for cl in (cloud_a, cloud_b))
+        return (sens.scores, self.side_gradient_images(sens.scores, sens.idx_a, sens.dist_a, sens.g_a, sens.disp_a, na, pair_weights),
+                self.side_gradient_images(sens.scores, sens.idx_b, sens.dist_b, sens.g_b, sens.disp_b, nb, pair_weights))
+
+    def side_gradient_images(self, scores, idx, dist, g, disp, n_atoms: int, pair_weights=None):
+        """One side of gradient_images: [n_atoms][3] f64, `side_gradient` with the displacements given instead of coordinates."""
+        torch = self.torch
+        v = torch.ones_like(scores) if pair_weights is None else pair_weights.to(scores.dtype).reshape(-1)
+        grad = torch.zeros((n_atoms, 3), dtype=torch.float64, device=scores.device)
+        use = (idx >= 0) & (dist > 0.0) & torch.isfinite(g)
+        use[:, 0] = False
+        member = idx.clamp(min=0).long()
+        anchor = member[:, :1].expand_as(member)
+        coef = torch.where(use, v[:, None] * g / torch.where(use, dist, torch.ones_like(dist)), torch.zeros_like(g))
+        step = coef[..., None] * disp  # [P][K][3]; zero rows where `use` is false
+        grad.index_add_(0, member.reshape(-1), step.reshape(-1, 3))
+        grad.index_add_(0, anchor.reshape(-1), -step.reshape(-1, 3))
+        return grad
 
     def _cross_head(self, cloud_a, cloud_b, anchors_a, anchors_b, threshold_distance, wf_index, tile_rows):
         torch = self.torch
