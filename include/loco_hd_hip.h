@@ -597,7 +597,7 @@ int64_t lchd_cloud_home_size(const lchd_cloud *cloud);
  *   - rows are checked as the scoring calls check them (a negative or NaN entry, a row without a 0, a type outside the category map:
  *     LCHD_EVALUE with the scoring call's message)
  * Rows of up to LCHD_SENSITIVITY_ROWS_LDS_POINTS (padded) points are sorted in the LDS of one workgroup, longer ones (up to 65 535) in
- * place in device memory.  No periodic cells, no ragged rows, no batches or image clouds. */
+ * place in device memory.  No ragged rows, no batches or image clouds; periodic cells in the two calls of the next section. */
 #define LCHD_SENSITIVITY_ROWS_LDS_POINTS 8192
 int lchd_sensitivity_coords_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, int32_t width, double *d_scores,
                                 int32_t *d_count_a, int32_t *d_idx_a, double *d_dist_a, double *d_g_a, int32_t *d_count_b,
@@ -610,6 +610,39 @@ int lchd_sensitivity_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *
                           int64_t len_seq_b, const double *dmx_a, const double *dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
                           const int32_t *wf_index, int32_t width, double *scores, int32_t *count_a, int32_t *idx_a, double *dist_a,
                           double *g_a, int32_t *count_b, int32_t *idx_b, double *dist_b, double *g_b);
+
+/* Dense rows in periodic cells (lchd_sensitivity_coords / _dev on the rows of "minimum-image dense rows"): cell_a / cell_b are HOST [9]
+ * matrices or NULL for an open side, exactly as lchd_from_coords_periodic takes them (an orthorhombic box is its diagonal cell).  The
+ * nine outputs are those of lchd_sensitivity_coords on the minimum-image rows: dist holds the minimum-image distances bit for bit, the
+ * lists are sorted by (distance bits, atom index), scores are those of lchd_from_coords_periodic.  A minimum-image row stores a length
+ * alone, and once an image is chosen the direction of a member is no longer x[member] - x[r]; so the call also returns
+ *   disp[r][K][3]  (f64) the displacement from row atom r to the nearest image of member idx[r][k], 0 in the padding:  disp = -w with
+ *                  d = x[r] - x[member] per axis and, in the arithmetic of the row producer (same operands, plain f64, left to right,
+ *                  nothing fused),
+ *                    an open side     w = d
+ *                    a diagonal cell  w_k = d_k - L_k * rint(d_k / L_k)
+ *                    any other cell   v from the wrapped fractional coordinates of d (R / I of lchd_cell_reduce, as above), then the
+ *                                     27 candidates w = v + ((i a + j b) + k c), i outermost and k innermost: the chosen w is the FIRST
+ *                                     candidate in that order with the smallest (wx wx + wy wy) + wz wz (an update on strict < only)
+ *                  A negation is exact, so sqrt((dx dx + dy dy) + dz dz) of disp equals dist[r][k] bit for bit, on every side kind.
+ *                  Between two images at exactly the same distance (an atom half a cell away) the rule above decides; slot 0 is
+ *                  computed like every other slot (the row atom itself: 0).
+ * dS_r/dx(atom idx[r][k]) += g disp / dist and dS_r/dx(atom r) -= the same, for slots beyond 0 with dist > 0: the exact gradient of
+ * the row's score with respect to the coordinates as given (wrapped or not), for any weight function.  The derivative with respect to
+ * the cell (virial) is not part of it.  No image-code arrays: every atom appears once.  With both cells NULL the call is
+ * lchd_sensitivity_coords plus disp.  Errors: those of lchd_sensitivity_coords (width below n: LCHD_EVALUE naming the width needed, more
+ * than 65 535 points, batches, image clouds) and those of lchd_from_coords_periodic (a singular or non-finite cell, a non-finite
+ * coordinate).  With lchd_ctx_enable_timing, "cells" of lchd_ctx_last_ms is the time of the row producers and "sweep" includes the
+ * displacement kernel. */
+int lchd_sensitivity_coords_periodic_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, const double *cell_a,
+                                         const double *cell_b, int32_t width, double *d_scores, int32_t *d_count_a, int32_t *d_idx_a,
+                                         double *d_dist_a, double *d_g_a, int32_t *d_count_b, int32_t *d_idx_b, double *d_dist_b,
+                                         double *d_g_b, double *d_disp_a, double *d_disp_b);
+int lchd_sensitivity_coords_periodic(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                                     int64_t len_seq_b, const double *xyz_a, const double *xyz_b, int64_t n, const int32_t *wf_index,
+                                     const double *cell_a, const double *cell_b, int32_t width, double *scores, int32_t *count_a,
+                                     int32_t *idx_a, double *dist_a, double *g_a, int32_t *count_b, int32_t *idx_b, double *dist_b,
+                                     double *g_b, double *disp_a, double *disp_b);
 
 /* ---- cross-scoring (additive, not in the reference) ------------------------------------------------------
  * Every anchor of one list against every anchor of another: which environments of B look like this environment of A.

@@ -180,6 +180,9 @@ _PROTOS = {
                                           _DP, _IP, _IP, _DP, _DP, _IP, _IP, _DP, _DP]),
     "lchd_sensitivity_dmxs": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _i64, _i64, _IP, _i32,
                                         _DP, _IP, _IP, _DP, _DP, _IP, _IP, _DP, _DP]),
+    "lchd_sensitivity_coords_periodic_dev": (C.c_int, [_VP, _VP, _VP, _VP, _DP, _DP, _i32] + [_VP] * 11),
+    "lchd_sensitivity_coords_periodic": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _IP, _DP, _DP, _i32,
+                                                   _DP, _IP, _IP, _DP, _DP, _IP, _IP, _DP, _DP, _DP, _DP]),
     "lchd_cross_plan": (C.c_int, [_i64, _i64, _i64, _LP]),
     "lchd_cross_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _i64, _VP, _i64, _i32, _f64, _i64, _VP]),
     "lchd_nearest_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _i64, _VP, _i64, _i32, _f64, _i64, _i32, _VP, _VP]),

@@ -28,6 +28,10 @@ from . import _native as N
 Sensitivity = namedtuple("Sensitivity", "scores count_a idx_a dist_a g_a count_b idx_b dist_b g_b")
 # what LoCoHD.sensitivity_from_primitives_periodic returns (DeviceSession.sensitivity_images: the same fields as torch tensors)
 PeriodicSensitivity = namedtuple("PeriodicSensitivity", "scores count_a idx_a image_a dist_a g_a disp_a count_b idx_b image_b dist_b g_b disp_b")
+# what LoCoHD.sensitivity_from_coords_periodic returns (DeviceSession.sensitivity_coords_periodic: the same fields as torch tensors): a
+# Sensitivity of dense minimum-image rows plus, per side, disp[n, K, 3], the displacement from row atom r to the nearest image of member
+# idx[r, k] (dist = |disp| bit for bit); every atom occurs once, so there are no image codes
+MinImageSensitivity = namedtuple("MinImageSensitivity", "scores count_a idx_a dist_a g_a disp_a count_b idx_b dist_b g_b disp_b")
 # what LoCoHD.nearest_from_primitives returns (DeviceSession.nearest: the same fields as torch tensors)
 Nearest = namedtuple("Nearest", "scores cols")
 
@@ -1099,12 +1103,15 @@ class LoCoHD:
     # ---- ... of dense rows (additive) ----------------------------------------------------------------------
     # Row r of both sides, every column a member (include/loco_hd_hip.h, "Dense rows" under "neighbour sensitivities").  A dense row has
     # no threshold: g is the whole derivative of the row's score with respect to the row's entries, for any weight function.
-    def _dense_sensitivity(self, name: str, seq_a, seq_b, a, b, w_func_keys, width, pair_weights=None, weighted=False):
+    def _dense_sensitivity(self, name: str, seq_a, seq_b, a, b, w_func_keys, width, pair_weights=None, weighted=False, cells=None):
         """sensitivity_from_coords / sensitivity_from_dmxs (`name`) and the head of the two gradient calls: every check that needs no
-        device, then the call.  Returns (Sensitivity, the two inputs as arrays, pair_weights as an array or None)."""
+        device, then the call.  Returns (Sensitivity, the two inputs as arrays, pair_weights as an array or None).  cells: the
+        (cell_a, cell_b) of a `*_from_coords_periodic` call as `dense_cells` returns them (None: an open side); the first element
+        returned is then a MinImageSensitivity."""
         if self._devices is not None:
             raise NotImplementedError("a sensitivity call applies to one device (a device group has no sensitivity call): drop devices=[...]")
-        if name.endswith("coords"):
+        coords = cells is not None or name.endswith("coords")
+        if coords:
             ma, mb = self._coords(a), self._coords(b)
             if len(ma) != len(mb):
                 raise ValueError(f"Expected matrices with the same length, got lengths {len(ma)} and {len(mb)}!")
@@ -1136,13 +1143,19 @@ class LoCoHD:
         ix = [np.empty((rows, k), dtype=np.int32) for _ in range(2)]
         ds = [np.empty((rows, k)) for _ in range(2)]
         gs = [np.empty((rows, k)) for _ in range(2)]
+        dp = [np.empty((rows, k, 3)) for _ in range(2)] if cells is not None else None
         if rows:
             outs = (N.dp(scores), N.ip(cnt[0]), N.ip(ix[0]), N.dp(ds[0]), N.dp(gs[0]), N.ip(cnt[1]), N.ip(ix[1]), N.dp(ds[1]), N.dp(gs[1]))
             head = (self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(ma), N.dp(mb))
-            if name.endswith("coords"):
+            if cells is not None:
+                N.check(N.lib().lchd_sensitivity_coords_periodic(*head, rows, N.ip(idx), N.dp(cells[0]), N.dp(cells[1]), k, *outs,
+                                                                 N.dp(dp[0]), N.dp(dp[1])))
+            elif coords:
                 N.check(N.lib().lchd_sensitivity_coords(*head, rows, N.ip(idx), k, *outs))
             else:
                 N.check(N.lib().lchd_sensitivity_dmxs(*head, rows, cols[0], cols[1], N.ip(idx), k, *outs))
+        if cells is not None:
+            return MinImageSensitivity(scores, cnt[0], ix[0], ds[0], gs[0], dp[0], cnt[1], ix[1], ds[1], gs[1], dp[1]), ma, mb, v
         return Sensitivity(scores, cnt[0], ix[0], ds[0], gs[0], cnt[1], ix[1], ds[1], gs[1]), ma, mb, v
 
     def sensitivity_from_dmxs(self, seq_a, seq_b, dmx_a, dmx_b, w_func_keys: Optional[Sequence[str]] = None, *,
@@ -1202,6 +1215,62 @@ class LoCoHD:
                                                   True)
         return (sens.scores, self._dense_coords_gradient(sens.idx_a, sens.dist_a, sens.g_a, v, xa),
                 self._dense_coords_gradient(sens.idx_b, sens.dist_b, sens.g_b, v, xb))
+
+    # ---- ... of dense rows in periodic cells (additive) ------------------------------------------------------
+    # The minimum-image rows of from_coords(box_a= / cell_a= ...) (include/loco_hd_hip.h, lchd_sensitivity_coords_periodic).  A row
+    # stores the length of the chosen image's vector alone, so the open product rowsum(M) x - M x no longer gives the gradient: the
+    # call returns the vectors (disp) and the gradient is assembled from them.
+    def _dense_periodic_cells(self, box_a, box_b, cell_a, cell_b):
+        """The keyword checks of from_coords for a dense sensitivity call: (cell_a, cell_b) as dense_cells returns them."""
+        for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+            if box is not None and cell is not None:
+                raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
+        return dense_cells(box_a, cell_a, 1, "box_a", "cell_a"), dense_cells(box_b, cell_b, 1, "box_b", "cell_b")
+
+    def sensitivity_from_coords_periodic(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None, *,
+                                         width: Optional[int] = None, box_a=None, box_b=None, cell_a=None,
+                                         cell_b=None) -> MinImageSensitivity:
+        """Additive: `sensitivity_from_coords` on the minimum-image rows `from_coords(..., box_a= / cell_a= ...)` scores; boxes and
+        cells per side as `from_coords` takes them, a side with neither is open.  Returns `MinImageSensitivity(scores, count_a, idx_a,
+        dist_a, g_a, disp_a, count_b, ...)`: the fields of `Sensitivity` on those rows and `disp` (n, K, 3), the displacement from row
+        atom r to the nearest periodic image of member idx[r, k] (on an open side x[member] - x[r]); dist = |disp| bit for bit, the
+        padding is 0.  Between two images at exactly the same distance the first in the header's candidate order is taken.
+        Coordinates need not be wrapped.  Device groups are not supported (NotImplementedError)."""
+        cells = self._dense_periodic_cells(box_a, box_b, cell_a, cell_b)
+        return self._dense_sensitivity("sensitivity_from_coords_periodic", seq_a, seq_b, coords_a, coords_b, w_func_keys, width, cells=cells)[0]
+
+    @staticmethod
+    def _min_image_side_gradient(idx: np.ndarray, dist: np.ndarray, g: np.ndarray, disp: np.ndarray, v: np.ndarray, n: int) -> np.ndarray:
+        """One side of gradient_from_coords_periodic: c = v g / d (0 in slot 0, where d == 0 and where g is not finite), T = c disp
+        scattered into atom order one component at a time (`_dense_scatter`: one writer per element), grad = T.sum(axis=0) -
+        T.sum(axis=1): the atom as a member of every row, minus the atom as the row's own."""
+        use = (dist > 0.0) & np.isfinite(g)
+        c = np.where(use, v[:, None] * g / np.where(use, dist, 1.0), 0.0)
+        t = np.stack([LoCoHD._dense_scatter(idx, c * disp[..., d], n) for d in range(3)], axis=-1)  # [row][atom][3]
+        return t.sum(axis=0) - t.sum(axis=1)
+
+    @staticmethod
+    def _assemble_gradient_min_image(sens: "MinImageSensitivity", pair_weights=None):
+        """(grad_a, grad_b) = sum_r v_r dS_r/dx from a MinImageSensitivity; no coordinates are needed: disp carries the geometry."""
+        rows = len(sens.scores)
+        v = np.ones(rows) if pair_weights is None else _f64(pair_weights).reshape(-1)
+        if len(v) != rows:
+            raise ValueError(f"pair_weights has {len(v)} entries for {rows} rows")
+        return (LoCoHD._min_image_side_gradient(sens.idx_a, sens.dist_a, sens.g_a, sens.disp_a, v, rows),
+                LoCoHD._min_image_side_gradient(sens.idx_b, sens.dist_b, sens.g_b, sens.disp_b, v, rows))
+
+    def gradient_from_coords_periodic(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None, pair_weights=None,
+                                      *, box_a=None, box_b=None, cell_a=None, cell_b=None):
+        """Additive: `gradient_from_coords` under minimum-image periodic boundaries: `(scores, grad_a[n, 3], grad_b[n, 3])` with grad =
+        sum_r v_r dS_r / dx over the rows `from_coords(..., box_a= ...)` scores.  Exact for any weight function (a dense row has no
+        threshold), one-sided at ties and where an atom sits exactly half a cell from the row's atom.  A wrap is a translation by a
+        lattice vector, so this is the gradient with respect to the coordinates as given, wrapped or not; the derivative with respect
+        to the box or cell is not part of it.  Assembled on the host from `sensitivity_from_coords_periodic` in a fixed order."""
+        cells = self._dense_periodic_cells(box_a, box_b, cell_a, cell_b)
+        sens, _, _, v = self._dense_sensitivity("gradient_from_coords_periodic", seq_a, seq_b, coords_a, coords_b, w_func_keys, None,
+                                                pair_weights, True, cells=cells)
+        ga, gb = self._assemble_gradient_min_image(sens, v)
+        return sens.scores, ga, gb
 
     # ---- cross-scoring (additive) ---------------------------------------------------------------------------
     # Every anchor of one list against every anchor of another (include/loco_hd_hip.h, "cross-scoring"): the pair list is generated on the

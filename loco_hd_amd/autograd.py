@@ -11,6 +11,11 @@ ignores points entering or leaving at the threshold (exact when the weight funct
 
 Forward is DeviceSession.sensitivity_coords, backward is side A of DeviceSession.gradient_coords (dense_side_gradient).
 
+    scores = locohd_scores_dense_periodic(session, cloud_b_ref, xyz_a, cat_a, box=(Lx, Ly, Lz))   # ... on minimum-image rows
+
+Forward is DeviceSession.sensitivity_coords_periodic, backward is side A of DeviceSession.gradient_coords_periodic
+(dense_side_gradient_disp): the displacements of the chosen images carry the geometry.
+
     scores = locohd_scores_periodic(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, threshold_distance, box=(Lx, Ly, Lz))
 
 The movable structure in a periodic box or cell: forward is DeviceSession.sensitivity_images on its image cloud, backward is side A of
@@ -93,6 +98,37 @@ class _LoCoHDScoresDense(torch.autograd.Function):
         s = ctx.sens
         grad_a = ctx.session.dense_side_gradient(s.idx_a, s.dist_a, s.g_a, x, grad_output)  # side A alone moves
         return grad_a.to(x.dtype), None, None, None, None
+
+
+class _LoCoHDScoresDensePeriodic(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz_a, session, cloud_b_ref, cat_a, wf_index, box, cell, ref_box, ref_cell):
+        x = xyz_a.detach()
+        cloud_a = session.upload(x.cpu().numpy(), np.asarray(cat_a, dtype=np.int32))
+        try:
+            sens = session.sensitivity_coords_periodic(cloud_a, cloud_b_ref, wf_index=wf_index, box_a=box, cell_a=cell, box_b=ref_box,
+                                                       cell_b=ref_cell)
+        finally:
+            session._clouds.remove(cloud_a)
+            N.lib().lchd_cloud_destroy(session._ctx, cloud_a)
+        ctx.session = session
+        ctx.sens = sens
+        ctx.dtype = x.dtype
+        return sens.scores
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        s = ctx.sens
+        grad_a = ctx.session.dense_side_gradient_disp(s.idx_a, s.dist_a, s.g_a, s.disp_a, grad_output)  # side A alone moves
+        return grad_a.to(ctx.dtype), None, None, None, None, None, None, None, None
+
+
+def locohd_scores_dense_periodic(session, cloud_b_ref, xyz_a, cat_a, wf_index=None, *, box=None, cell=None, ref_box=None, ref_cell=None):
+    """`locohd_scores_dense` under minimum-image periodic boundaries (DeviceSession.sensitivity_coords_periodic): `box` / `cell` is the
+    periodic box (Lx, Ly, Lz) or cell (3 x 3) of the movable structure, `ref_box` / `ref_cell` that of the reference; a structure with
+    neither is open.  Backward is side A of DeviceSession.gradient_coords_periodic with grad_output as the row weights; xyz_a need not be
+    wrapped: the gradient is the one with respect to xyz_a as given."""
+    return _LoCoHDScoresDensePeriodic.apply(xyz_a, session, cloud_b_ref, cat_a, wf_index, box, cell, ref_box, ref_cell)
 
 
 def locohd_scores_dense(session, cloud_b_ref, xyz_a, cat_a, wf_index=None):

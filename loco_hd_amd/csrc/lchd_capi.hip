@@ -3769,8 +3769,11 @@ struct PairConsumer {
     bool records;       // its kernel reads the pair records of k_pair_meta (a dense pass carves them)
     int width;          // > 0: a sensitivity call with rows of this many slots
     SensitivityOut sens;  // ... and its DEVICE outputs, or all null: they are carved from the pass's one output block (sens_carve)
-    bool images;        // ... which resolves members of image clouds to source atoms (launch_sens_resolve: image and disp outputs)
+    int resolve;        // ... and what runs behind its kernel: kSensPlain nothing; kSensImages launch_sens_resolve, which resolves members
+                        // of image clouds to source atoms (image and disp outputs); kSensMinImage launch_sens_min_image_disp on dense rows
+                        // from coordinates (disp outputs alone)
 };
+enum { kSensPlain = 0, kSensImages = 1, kSensMinImage = 2 };
 static const PairConsumer kComposition{{}, "a composition profile", "composition", "anchors", 1, false};
 static const PairConsumer kAttribution{{}, "an attribution", "attribution", "anchor pairs", 2, true};
 static PairConsumer radial_consumer(const double* edges, int32_t n_edges) {
@@ -3779,35 +3782,34 @@ static PairConsumer radial_consumer(const double* edges, int32_t n_edges) {
     for (int32_t k = 0; k < n_edges; ++k) use.edges.e[k] = edges[k];
     return use;
 }
-static PairConsumer sensitivity_consumer(int32_t width, const SensitivityOut& out, bool images = false) {
+static PairConsumer sensitivity_consumer(int32_t width, const SensitivityOut& out, int resolve = kSensPlain) {
     PairConsumer use{{}, "a sensitivity call", "sensitivity", "anchor pairs", 2, true};
     use.width = width;
     use.sens = out;
-    use.images = images;
+    use.resolve = resolve;
     return use;
 }
-// doubles per pair of a sensitivity call's block: the nine arrays, and with `images` the two disp rows and the two image rows behind them
-static size_t sens_row(int w, bool images) {
-    return 5 * (size_t)w + 2 + (images ? 6 * (size_t)w + (2 * (size_t)w + 7) / 8 : 0);
+// doubles per pair of a sensitivity call's block: the nine arrays, behind them the two disp rows of a call that resolves, and behind
+// those the two image rows of kSensImages
+static size_t sens_row(int w, int resolve) {
+    return 5 * (size_t)w + 2 + (resolve ? 6 * (size_t)w : 0) + (resolve == kSensImages ? (2 * (size_t)w + 7) / 8 : 0);
 }
 // A sensitivity call's outputs as ONE block of n * sens_row doubles (host or device): scores | g_a | g_b | dist_a | dist_b | idx_a | idx_b |
-// count_a | count_b [| disp_a | disp_b | image_a | image_b] -- what the host call moves in one copy.
-static SensitivityOut sens_carve(double* blk, int64_t n, int w, bool images = false) {
+// count_a | count_b [| disp_a | disp_b [| image_a | image_b]] -- what the host call moves in one copy.
+static SensitivityOut sens_carve(double* blk, int64_t n, int w, int resolve = kSensPlain) {
     const size_t nw = (size_t)n * (size_t)w;
     SensitivityOut o{};
     o.scores = blk;
     o.g_a = blk + n; o.g_b = o.g_a + nw; o.dist_a = o.g_b + nw; o.dist_b = o.dist_a + nw;
     o.idx_a = reinterpret_cast<int32_t*>(o.dist_b + nw); o.idx_b = o.idx_a + nw;
     o.count_a = o.idx_b + nw; o.count_b = o.count_a + n;
-    if (images) {
-        o.disp_a = blk + (size_t)n * (5 * (size_t)w + 2); o.disp_b = o.disp_a + 3 * nw;
-        o.image_a = reinterpret_cast<int8_t*>(o.disp_b + 3 * nw); o.image_b = o.image_a + nw;
-    }
+    if (resolve) { o.disp_a = blk + (size_t)n * (5 * (size_t)w + 2); o.disp_b = o.disp_a + 3 * nw; }
+    if (resolve == kSensImages) { o.image_a = reinterpret_cast<int8_t*>(o.disp_b + 3 * nw); o.image_b = o.image_a + nw; }
     return o;
 }
 // doubles per entry in the consumer's output: the bins / the categories of the context's configuration / a sensitivity call's block
 static size_t consumer_row(const lchd_ctx* c, const PairConsumer& use) {
-    if (use.width) return sens_row(use.width, use.images);
+    if (use.width) return sens_row(use.width, use.resolve);
     return use.edges.n ? (size_t)use.edges.n - 1 : (size_t)c->h_cfg.n_categories;
 }
 static int consumer_limits(const lchd_ctx* c, const PairConsumer& use) {
@@ -3829,6 +3831,7 @@ struct SensLists {
     IndexedStore env[2];
     const IndexedArgs* cells;
     lchd_cloud* cl[2];  // the clouds the lists index (read when the consumer resolves image clouds)
+    const struct RowSource* rows;  // [2] the row sources of a dense pass (read by kSensMinImage: coordinates and cells), or null
 };
 static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use, double* d_out, const SensLists* lists = nullptr) {
     const int n_wf = c->h_cfg.n_wf;
@@ -3852,9 +3855,23 @@ static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use,
         sa.env_b = lists->env[1];
         sa.n_categories = c->h_cfg.n_categories;
         sa.width = use.width;
-        sa.out = use.sens.scores ? use.sens : sens_carve(d_out, sw.n_pairs, use.width, use.images);
+        sa.out = use.sens.scores ? use.sens : sens_carve(d_out, sw.n_pairs, use.width, use.resolve);
         launched = (!lists->cells || launch_env_indexed(s, *lists->cells)) && launch_sensitivity(s, sa);
-        if (launched && use.images) {
+        if (launched && use.resolve == kSensMinImage) {
+            SensDispArgs da{};
+            const int32_t* const idx[2] = {sa.out.idx_a, sa.out.idx_b};
+            double* const disp[2] = {sa.out.disp_a, sa.out.disp_b};
+            for (int k = 0; k < 2; ++k) {
+                const RowSource& src = lists->rows[k];
+                SensDispSide& S = da.s[k];
+                S.x = src.view.x; S.y = src.view.y; S.z = src.view.z; S.n = src.view.n;
+                S.idx = idx[k]; S.disp = disp[k];
+                S.kind = src.kind == RowSource::CELL ? (src.all_diagonal ? 1 : 2) : 0;
+                if (S.kind) S.cell = src.cell;
+            }
+            da.rows = sw.n_pairs; da.width = use.width;
+            launched = launch_sens_min_image_disp(s, da);
+        } else if (launched && use.resolve == kSensImages) {
             SensResolveArgs ra{};
             int32_t* const idx[2] = {sa.out.idx_a, sa.out.idx_b};
             int8_t* const image[2] = {sa.out.image_a, sa.out.image_b};
@@ -4013,7 +4030,7 @@ static int consumer_primitives_dev(lchd_ctx* c, lchd_cloud* const* cl, const int
     CTX_GUARD(c);
     for (int k = 0; k < use.sides; ++k)
         if (int rc = resolve_bbox(c, cl[k])) return rc;
-    if (use.images)  // (the origin maps the resolve step reads: built here, on the stream in front of the pass, if the last build left none)
+    if (use.resolve == kSensImages)  // (the origin maps the resolve step reads: built here, on the stream in front of the pass, if the last build left none)
         for (int k = 0; k < use.sides; ++k)
             if (cl[k]->images) if (int rc = images_origin(c, cl[k])) return rc;
     const bool keep_sweep_record = c->last_sweep_valid;  // (host data: the record of the last scoring pass stands)
@@ -4195,7 +4212,7 @@ static int consumer_dense(lchd_ctx* c, const RowSource* src, int64_t rows, const
     sw.wf_index = d_wf;
     sw.n_pairs = rows;
     sw.meta = d_meta;
-    const SensLists lists{{rx.s[0].env, rx.s[1].env}, nullptr};
+    const SensLists lists{{rx.s[0].env, rx.s[1].env}, nullptr, {nullptr, nullptr}, src};
     if (int rc = consumer_enqueue(c, sw, use, d_out, use.width ? &lists : nullptr)) return rc;
     mark(c, 4);
     HIP_TRY(hipGetLastError());
@@ -4478,26 +4495,24 @@ extern "C" int lchd_attribution_dmxs(lchd_ctx* c, const lchd_config* cfg, const 
 // neighbour sensitivities: every statistical distance.  The thresholded pass is the attribution call's with the indexed lists (built from
 // the pass's cell lists) and k_sensitivity (lchd_sensitivity.hip) behind the record pass; periodic boxes, cells and image clouds only in
 // the calls that resolve the members (lchd_sensitivity_images_dev / _primitives_periodic: k_sens_resolve_images behind the two).
-// A host call's pass writes ONE block (sens_carve), which `pass` receives; the HOST arrays of `o` are filled from it: the nine, and the
-// four of a resolving call where `o` names them.
+// A host call's pass writes ONE block (sens_carve) in the layout of `resolve`, which `pass` receives with that value: the consumer and
+// the copy back carve the same block.  The HOST arrays of `o` are filled from it: the nine, and the disp (and image) arrays of a
+// resolving call.
 template <class Pass>
-static int sens_host_call(int64_t n_pairs, int32_t width, const SensitivityOut& o, Pass&& pass) {
+static int sens_host_call(int64_t n_pairs, int32_t width, int resolve, const SensitivityOut& o, Pass&& pass) {
     const size_t n = n_pairs > 0 ? (size_t)n_pairs : 0, nw = n * (size_t)width;
-    const bool images = o.disp_a != nullptr;
-    double* blk = n ? static_cast<double*>(malloc(sizeof(double) * n * sens_row(width, images))) : nullptr;
+    double* blk = n ? static_cast<double*>(malloc(sizeof(double) * n * sens_row(width, resolve))) : nullptr;
     if (n && !blk) return fail(LCHD_EUNSUPPORTED, "no host memory for the outputs of %lld pairs", (long long)n_pairs);
-    const int rc = pass(blk);
+    const int rc = pass(blk, resolve);
     if (rc == LCHD_OK && n) {
-        const SensitivityOut b = sens_carve(blk, n_pairs, width, images);
+        const SensitivityOut b = sens_carve(blk, n_pairs, width, resolve);
         memcpy(o.scores, b.scores, 8 * n);
         memcpy(o.g_a, b.g_a, 8 * nw); memcpy(o.g_b, b.g_b, 8 * nw);
         memcpy(o.dist_a, b.dist_a, 8 * nw); memcpy(o.dist_b, b.dist_b, 8 * nw);
         memcpy(o.idx_a, b.idx_a, 4 * nw); memcpy(o.idx_b, b.idx_b, 4 * nw);
         memcpy(o.count_a, b.count_a, 4 * n); memcpy(o.count_b, b.count_b, 4 * n);
-        if (images) {
-            memcpy(o.disp_a, b.disp_a, 24 * nw); memcpy(o.disp_b, b.disp_b, 24 * nw);
-            memcpy(o.image_a, b.image_a, nw); memcpy(o.image_b, b.image_b, nw);
-        }
+        if (resolve) { memcpy(o.disp_a, b.disp_a, 24 * nw); memcpy(o.disp_b, b.disp_b, 24 * nw); }
+        if (resolve == kSensImages) { memcpy(o.image_a, b.image_a, nw); memcpy(o.image_b, b.image_b, nw); }
     }
     free(blk);
     return rc;
@@ -4534,9 +4549,9 @@ extern "C" int lchd_sensitivity_primitives(lchd_ctx* c, const lchd_config* cfg, 
     if (n_pairs > 0 && (!scores || !count_a || !idx_a || !dist_a || !g_a || !count_b || !idx_b || !dist_b || !g_b))
         return fail(LCHD_EVALUE, "null output pointer");
     const SensitivityOut o{scores, count_a, count_b, idx_a, idx_b, dist_a, dist_b, g_a, g_b};
-    return sens_host_call(n_pairs, width, o, [&](double* blk) {
+    return sens_host_call(n_pairs, width, kSensPlain, o, [&](double* blk, int resolve) {
         return pair_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, nullptr, nullptr,
-                                    nullptr, nullptr, sensitivity_consumer(width, SensitivityOut{}), blk);
+                                    nullptr, nullptr, sensitivity_consumer(width, SensitivityOut{}, resolve), blk);
     });
 }
 extern "C" int64_t lchd_sensitivity_needed_width(lchd_ctx* c) { return c ? c->sens_needed : 0; }
@@ -4553,7 +4568,7 @@ extern "C" int lchd_sensitivity_images_dev(lchd_ctx* c, lchd_cloud* a, lchd_clou
         return fail(LCHD_EVALUE, "null output pointer");
     const SensitivityOut o{d_scores, d_count_a, d_count_b, d_idx_a, d_idx_b, d_dist_a, d_dist_b, d_g_a, d_g_b, d_disp_a, d_disp_b, d_image_a, d_image_b};
     lchd_cloud* const cl[2] = {a, b};
-    return consumer_primitives_dev(c, cl, d_anchors, d_wf_index, n_pairs, thr, sensitivity_consumer(width, o, true), d_scores);
+    return consumer_primitives_dev(c, cl, d_anchors, d_wf_index, n_pairs, thr, sensitivity_consumer(width, o, kSensImages), d_scores);
 }
 extern "C" int lchd_sensitivity_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a,
                                                     const int32_t* tag_a, int64_t n_a, const double* xyz_b, const int32_t* cat_b,
@@ -4569,9 +4584,9 @@ extern "C" int lchd_sensitivity_primitives_periodic(lchd_ctx* c, const lchd_conf
                         !g_b || !disp_b))
         return fail(LCHD_EVALUE, "null output pointer");
     const SensitivityOut o{scores, count_a, count_b, idx_a, idx_b, dist_a, dist_b, g_a, g_b, disp_a, disp_b, image_a, image_b};
-    return sens_host_call(n_pairs, width, o, [&](double* blk) {
+    return sens_host_call(n_pairs, width, kSensImages, o, [&](double* blk, int resolve) {
         return pair_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, box_a, cell_a,
-                                    box_b, cell_b, sensitivity_consumer(width, SensitivityOut{}, true), blk);
+                                    box_b, cell_b, sensitivity_consumer(width, SensitivityOut{}, resolve), blk);
     });
 }
 
@@ -4601,9 +4616,44 @@ extern "C" int lchd_sensitivity_coords(lchd_ctx* c, const lchd_config* cfg, cons
     if (n > 0 && (!scores || !count_a || !idx_a || !dist_a || !g_a || !count_b || !idx_b || !dist_b || !g_b))
         return fail(LCHD_EVALUE, "null output pointer");
     const SensitivityOut o{scores, count_a, count_b, idx_a, idx_b, dist_a, dist_b, g_a, g_b};
-    return sens_host_call(n, width, o, [&](double* blk) {
+    return sens_host_call(n, width, kSensPlain, o, [&](double* blk, int resolve) {
         return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n, n, n, wf_index, nullptr, nullptr,
-                               sensitivity_consumer(width, SensitivityOut{}), blk);
+                               sensitivity_consumer(width, SensitivityOut{}, resolve), blk);
+    });
+}
+// ... in periodic cells (minimum image): the same two calls with the reduced cells in the row sources, and k_sens_min_image_disp behind
+// k_sensitivity for the displacement of every member -- the direction a minimum-image row, which stores |w| alone, does not carry.
+extern "C" int lchd_sensitivity_coords_periodic_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
+                                                    const double* cell_b, int32_t width, double* d_scores, int32_t* d_count_a, int32_t* d_idx_a,
+                                                    double* d_dist_a, double* d_g_a, int32_t* d_count_b, int32_t* d_idx_b, double* d_dist_b,
+                                                    double* d_g_b, double* d_disp_a, double* d_disp_b) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (int rc = sens_args(c, a->n, width)) return rc;
+    if (a->n > 0 && (!d_scores || !d_count_a || !d_idx_a || !d_dist_a || !d_g_a || !d_count_b || !d_idx_b || !d_dist_b || !d_g_b || !d_disp_a ||
+                     !d_disp_b))
+        return fail(LCHD_EVALUE, "null output pointer");
+    if (a->images || b->images) return fail(LCHD_EUNSUPPORTED, "a sensitivity call takes the structures themselves, not periodic image clouds");
+    SensitivityOut o{d_scores, d_count_a, d_count_b, d_idx_a, d_idx_b, d_dist_a, d_dist_b, d_g_a, d_g_b};
+    o.disp_a = d_disp_a; o.disp_b = d_disp_b;
+    lchd_cloud* const cl[2] = {a, b};
+    const double* const cells[2] = {cell_a, cell_b};
+    return consumer_coords_dev(c, cl, d_wf_index, cells, sensitivity_consumer(width, o, kSensMinImage), d_scores);
+}
+extern "C" int lchd_sensitivity_coords_periodic(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                                int64_t len_seq_b, const double* xyz_a, const double* xyz_b, int64_t n, const int32_t* wf_index,
+                                                const double* cell_a, const double* cell_b, int32_t width, double* scores, int32_t* count_a,
+                                                int32_t* idx_a, double* dist_a, double* g_a, int32_t* count_b, int32_t* idx_b, double* dist_b,
+                                                double* g_b, double* disp_a, double* disp_b) {
+    if (int rc = coords_lengths(xyz_a, n, xyz_b, n)) return rc;
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = sens_args(c, n, width)) return rc;
+    if (n > 0 && (!scores || !count_a || !idx_a || !dist_a || !g_a || !count_b || !idx_b || !dist_b || !g_b || !disp_a || !disp_b))
+        return fail(LCHD_EVALUE, "null output pointer");
+    SensitivityOut o{scores, count_a, count_b, idx_a, idx_b, dist_a, dist_b, g_a, g_b};
+    o.disp_a = disp_a; o.disp_b = disp_b;
+    return sens_host_call(n, width, kSensMinImage, o, [&](double* blk, int resolve) {
+        return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n, n, n, wf_index, cell_a, cell_b,
+                               sensitivity_consumer(width, SensitivityOut{}, resolve), blk);
     });
 }
 extern "C" int lchd_sensitivity_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
@@ -4616,9 +4666,9 @@ extern "C" int lchd_sensitivity_dmxs(lchd_ctx* c, const lchd_config* cfg, const 
     if (rows > 0 && (!scores || !count_a || !idx_a || !dist_a || !g_a || !count_b || !idx_b || !dist_b || !g_b))
         return fail(LCHD_EVALUE, "null output pointer");
     const SensitivityOut o{scores, count_a, count_b, idx_a, idx_b, dist_a, dist_b, g_a, g_b};
-    return sens_host_call(rows, width, o, [&](double* blk) {
+    return sens_host_call(rows, width, kSensPlain, o, [&](double* blk, int resolve) {
         return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr,
-                               nullptr, sensitivity_consumer(width, SensitivityOut{}), blk);
+                               nullptr, sensitivity_consumer(width, SensitivityOut{}, resolve), blk);
     });
 }
 

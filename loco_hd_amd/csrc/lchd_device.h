@@ -219,6 +219,9 @@ bool launch_env_rows(hipStream_t s, const lchd_dense_rows_side& side, const DevC
                      int64_t n_rows, int64_t row_len, double image_bound /* coords: >= largest squared distance, or 0 */, EnvStore env,
                      DeviceStatus* st, const RowExtras& ex = RowExtras{nullptr, nullptr, nullptr});
 
+// The cell of a dense minimum-image call as the kernels take it (by value: it is wave-uniform).
+struct MinImageCell { double v[kMinImageRecord]; };  // lchd_cell_reduce.h: reduced cell, inverse, 1.0 if diagonal
+
 // "last workgroup" detection + hand-over through memory-side atomics (lchd_sweep_common.h: last_workgroup_done)
 struct DoneState {
     uint32_t ctr[65 * 32];
@@ -508,7 +511,8 @@ struct SensitivityOut {      // all DEVICE; K = SensitivityArgs::width
     int32_t *count_a, *count_b;        // [P] members incl. the anchor (0: an unusable pair)
     int32_t *idx_a, *idx_b;            // [P][K], padded with -1
     double *dist_a, *dist_b, *g_a, *g_b;  // [P][K], padded with 0
-    // launch_sens_resolve only (null otherwise): the image code of every member and its displacement from the anchor
+    // launch_sens_resolve (both) and launch_sens_min_image_disp (disp alone), null otherwise: the image code of every member and its
+    // displacement from the anchor / the row's atom
     double *disp_a, *disp_b;           // [P][K][3], padded with 0
     int8_t *image_a, *image_b;         // [P][K], padded with 0
 };
@@ -539,6 +543,23 @@ struct SensResolveArgs {
     int32_t width;             // K
 };
 bool launch_sens_resolve(hipStream_t s, const SensResolveArgs& a);  // false: nothing launched (more slots than a grid covers)
+// Behind launch_sensitivity on the lists of dense rows from coordinates (k_sens_min_image_disp): per member slot of row r the
+// displacement from atom r to the member -- in a periodic cell to the member's nearest image, the vector behind the row's minimum-image
+// distance (lchd_min_image.h), on an open side x[member] - x[r] -- so that sqrt((dx dx + dy dy) + dz dz) of it is dist bit for bit.
+struct SensDispSide {
+    const double *x, *y, *z;   // the side's coordinates
+    int64_t n;                 // its atoms (rows and members are checked against it)
+    const int32_t* idx;        // [rows][K] members (-1: padding)
+    double* disp;              // [rows][K][3] out
+    MinImageCell cell;         // kind != 0: the reduced cell of the side
+    int32_t kind;              // 0 open, 1 a diagonal cell (the per-axis form), 2 any other cell (the 27 shifts)
+};
+struct SensDispArgs {
+    SensDispSide s[2];
+    int64_t rows;
+    int32_t width;             // K
+};
+bool launch_sens_min_image_disp(hipStream_t s, const SensDispArgs& a);  // false: nothing launched (more slots than a grid covers)
 // Cross-scoring (lchd_cross.hip): the pair records of one row tile -- anchors_a[row0 .. row0 + rows) against all n_b anchors of B, pair
 // p = i * n_b + j -- written on the device in the [P][2] int64 form the thresholded pass reads, with the constant wf index when wf >= 0
 // (wf_out is not touched otherwise); and the reduction of a tile's [rows][n_b] scores to the k smallest (score, column) per row, ascending.
@@ -559,7 +580,6 @@ void launch_ens_dist(hipStream_t s, const CloudView& c, int64_t atom0, int32_t n
                      const int32_t* excl_idx, double* dmx);
 // The same rows in a periodic cell (minimum image).  `one`: the cell of every structure, or d_recs: DEVICE [structures][kMinImageRecord],
 // indexed by atom0 / n + the structure's position in the launch.  all_diagonal: every cell is diagonal (the orthorhombic kernel).
-struct MinImageCell { double v[kMinImageRecord]; };  // lchd_cell_reduce.h: reduced cell, inverse, 1.0 if diagonal
 void launch_min_image_rows(hipStream_t s, const CloudView& c, int64_t atom0, int32_t n, int64_t n_rows, const MinImageCell& one,
                            const double* d_recs, bool all_diagonal, const int32_t* excl_start, const int32_t* excl_idx, double* dmx);
 void launch_ens_iota(hipStream_t s, uint32_t* slot, int64_t n);

@@ -14,6 +14,7 @@
 //   k_ens_records  structure-pair list -> sweep records and per-record weight-function indices, on the device
 //   k_ens_scatter  the scores of a pass into their (pair, row) places of the caller's output
 #include "lchd_device.h"
+#include "lchd_min_image.h"
 
 namespace lchd {
 
@@ -36,40 +37,7 @@ __global__ __launch_bounds__(256) void k_ens_dist(const double* __restrict__ x, 
 
 // ---- minimum-image rows (lchd_from_coords_periodic / lchd_ensemble_from_coords_periodic; the arithmetic is part of the contract in
 // include/loco_hd_hip.h: plain f64, IEEE division, rint = round to nearest even, every sum left to right, nothing fused) -----------
-// A diagonal cell: per axis d - L rint(d / L).
-__device__ __forceinline__ double min_image_box(double dx, double dy, double dz, double lx, double ly, double lz) {
-    dx = dx - lx * rint(dx / lx);
-    dy = dy - ly * rint(dy / ly);
-    dz = dz - lz * rint(dz / lz);
-    return sqrt((dx * dx + dy * dy) + dz * dz);
-}
-// Any other cell, R = the Minkowski-reduced vectors (rows), I = their inverse: fractional coordinates wrapped to [-1/2, 1/2], back to
-// Cartesian, then the shortest of the 27 neighbours v + (i a + j b) + k c (i outermost, k innermost; for a reduced cell no other
-// lattice translate is nearer, lchd_cell_reduce.h).
-__device__ __forceinline__ double min_image_cell(double dx, double dy, double dz, const double (&R)[9], const double (&I)[9]) {
-    double f0 = (dx * I[0] + dy * I[3]) + dz * I[6];
-    double f1 = (dx * I[1] + dy * I[4]) + dz * I[7];
-    double f2 = (dx * I[2] + dy * I[5]) + dz * I[8];
-    f0 = f0 - rint(f0);
-    f1 = f1 - rint(f1);
-    f2 = f2 - rint(f2);
-    const double vx = (f0 * R[0] + f1 * R[3]) + f2 * R[6];
-    const double vy = (f0 * R[1] + f1 * R[4]) + f2 * R[7];
-    const double vz = (f0 * R[2] + f1 * R[5]) + f2 * R[8];
-    double best = __builtin_inf();
-#pragma unroll
-    for (int i = -1; i <= 1; ++i)
-#pragma unroll
-        for (int j = -1; j <= 1; ++j)
-#pragma unroll
-            for (int k = -1; k <= 1; ++k) {
-                const double wx = vx + (((double)i * R[0] + (double)j * R[3]) + (double)k * R[6]);
-                const double wy = vy + (((double)i * R[1] + (double)j * R[4]) + (double)k * R[7]);
-                const double wz = vz + (((double)i * R[2] + (double)j * R[5]) + (double)k * R[8]);
-                best = fmin(best, (wx * wx + wy * wy) + wz * wz);
-            }
-    return sqrt(best);
-}
+// min_image_box / min_image_cell: lchd_min_image.h, shared with the displacement kernel of the dense sensitivity call.
 
 // One workgroup per row, as k_ens_dist.  The cell is wave-uniform: `one` (kernel argument) or, with per-structure cells, record
 // struct0 + k of `recs`, loaded once per row through an index made of blockIdx only.  CELL = false: every cell is diagonal.

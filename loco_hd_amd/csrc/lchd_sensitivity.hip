@@ -27,6 +27,9 @@
 //                   score is one wave reduction in lane order.
 //   k_sens_resolve_images   behind the two above when a list indexes a periodic image cloud: per member slot the displacement from the
 //                   anchor, the image code, and the source atom in place of the cloud index (see the kernel)
+//   k_sens_min_image_disp   behind k_rows_indexed + k_sensitivity on dense rows from coordinates: per member slot the displacement from
+//                   the row's atom to the member's nearest periodic image, the vector behind the minimum-image distance (see the kernel)
+#include "lchd_min_image.h"
 #include "lchd_sweep_common.h"
 
 namespace lchd {
@@ -600,6 +603,93 @@ bool launch_sens_resolve(hipStream_t s, const SensResolveArgs& a) {
     const dim3 grid((unsigned)blocks, 2);
     if ((low & 15) == 0) k_sens_resolve_images<true><<<grid, 256, 0, s>>>(a);
     else k_sens_resolve_images<false><<<grid, 256, 0, s>>>(a);
+    return true;
+}
+
+// ---- displacements of dense minimum-image rows ---------------------------------------------------------------------------------------
+// Behind k_rows_indexed + k_sensitivity on dense rows from coordinates: a minimum-image row stores |w| alone, and the direction of a
+// member is no longer x[member] - x[r] once an image was chosen.  For every slot [row r][k] of one side (one launch per side) this
+// kernel writes disp[r][k][3] = -w with d = x[r] - x[member] per axis and
+//   an open side      w = d
+//   a diagonal cell   w_k = d_k - L_k rint(d_k / L_k)
+//   any other cell    the first of the 27 candidates v + ((i a + j b) + k c) (i outermost, k innermost) with the smallest
+//                     (wx wx + wy wy) + wz wz, an update on strict < only
+// -- the arithmetic of the row producer (lchd_min_image.h) and, on an open side, of k_rows_indexed, so sqrt((dx dx + dy dy) + dz dz) of
+// disp is dist[r][k] bit for bit (a negation is exact).  Slot 0 is computed like every other slot; the padding (idx < 0) gets 0.
+// Lane-to-slot mapping and access widths are k_sens_resolve_images': four consecutive slots of the flat [rows * K] range per lane, one
+// 16-byte idx load and six 16-byte disp stores where the arrays are 16-byte aligned (VEC), the scalar form otherwise (a block carved
+// from a host call's output is not always aligned).  The coordinate reads are gathers; the cell is wave-uniform (a kernel argument,
+// by value).  Every output element has one writer; no atomics.
+// KIND (SensDispSide::kind) is a template parameter: the open and the per-axis form do not carry the registers of the 27-candidate
+// search (its lattice shifts are loop-invariant f64 values, which live in VGPRs).
+template <int KIND, bool VEC>
+__global__ __launch_bounds__(256) void k_sens_min_image_disp(SensDispSide S, int64_t rows, int32_t width) {
+    const int64_t K = width, slots = rows * K;
+    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (s0 >= slots) return;
+    const int m = (int)(slots - s0 < 4 ? slots - s0 : 4);
+    const bool wide = VEC && m == 4;
+    int32_t id[4] = {-1, -1, -1, -1};
+    if (wide) {
+        const int4 v = *reinterpret_cast<const int4*>(S.idx + s0);
+        id[0] = v.x; id[1] = v.y; id[2] = v.z; id[3] = v.w;
+    } else {
+        for (int q = 0; q < m; ++q) id[q] = S.idx[s0 + q];
+    }
+    double R[9], I[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) { R[q] = S.cell.v[q]; I[q] = S.cell.v[9 + q]; }  // (KIND 0 reads none of them, KIND 1 the diagonal of R)
+    double d[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int64_t r = s0 / K, k = s0 - r * K;
+    bool fresh = true;
+    double ax = 0.0, ay = 0.0, az = 0.0;
+    // one copy of the 27-candidate search in the code, not four: the loop stays rolled, and the slot's registers are picked by compares
+#pragma unroll 1
+    for (int q = 0; q < m; ++q, ++k) {
+        if (k == K) { k = 0; ++r; fresh = true; }
+        if (fresh) {
+            if (r < S.n) { ax = S.x[r]; ay = S.y[r]; az = S.z[r]; }
+            fresh = false;
+        }
+        const int64_t mem = q == 0 ? id[0] : (q == 1 ? id[1] : (q == 2 ? id[2] : id[3]));
+        if (mem < 0 || mem >= S.n || r >= S.n) continue;  // padding (or a row the pass has flagged): disp 0
+        const double dx = ax - S.x[mem], dy = ay - S.y[mem], dz = az - S.z[mem];
+        double w[3] = {dx, dy, dz};
+        if constexpr (KIND == 1) min_image_box_vec(dx, dy, dz, R[0], R[4], R[8], w);
+        else if constexpr (KIND == 2) min_image_cell_vec(dx, dy, dz, R, I, w);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (t == q) { d[3 * t] = -w[0]; d[3 * t + 1] = -w[1]; d[3 * t + 2] = -w[2]; }
+    }
+    if (wide) {
+        double2* const out = reinterpret_cast<double2*>(S.disp + 3 * s0);
+        for (int j = 0; j < 6; ++j) out[j] = make_double2(d[2 * j], d[2 * j + 1]);
+    } else {
+        for (int q = 0; q < m; ++q)
+            for (int j = 0; j < 3; ++j) S.disp[3 * (s0 + q) + j] = d[3 * q + j];
+    }
+}
+
+bool launch_sens_min_image_disp(hipStream_t s, const SensDispArgs& a) {
+    if (a.rows <= 0) return true;
+    if (a.width < 1) return false;
+    const int64_t quads = (a.rows * (int64_t)a.width + 3) / 4, blocks = (quads + 255) / 256;
+    if (blocks > 0x7FFFFFFF) return false;
+    for (int k = 0; k < 2; ++k)
+        if (a.s[k].kind < 0 || a.s[k].kind > 2 || a.s[k].n < a.rows) return false;
+    const unsigned grid = (unsigned)blocks;
+    for (int k = 0; k < 2; ++k) {  // one launch per side: the instantiation of the side's kind, 16-byte accesses where its arrays allow them
+        const SensDispSide& S = a.s[k];
+        const bool vec = ((reinterpret_cast<uintptr_t>(S.idx) | reinterpret_cast<uintptr_t>(S.disp)) & 15) == 0;
+        auto go = [&](auto kind) {
+            constexpr int KIND = decltype(kind)::value;
+            if (vec) k_sens_min_image_disp<KIND, true><<<grid, 256, 0, s>>>(S, a.rows, a.width);
+            else k_sens_min_image_disp<KIND, false><<<grid, 256, 0, s>>>(S, a.rows, a.width);
+        };
+        if (S.kind == 0) go(std::integral_constant<int, 0>{});
+        else if (S.kind == 1) go(std::integral_constant<int, 1>{});
+        else go(std::integral_constant<int, 2>{});
+    }
     return true;
 }
 

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .api import LoCoHD, Nearest, PeriodicSensitivity, Sensitivity, dense_cells, periodic_boxes, periodic_cells
+from .api import LoCoHD, MinImageSensitivity, Nearest, PeriodicSensitivity, Sensitivity, dense_cells, periodic_boxes, periodic_cells
 
 
 def last_sweep_of(ctx):
@@ -597,6 +597,71 @@ class DeviceSession:
         w = torch.zeros((n, n), dtype=torch.float64, device=x.device).scatter_(1, idx.long(), coef)
         m = w + w.t()
         return m.sum(dim=1)[:, None] * x - m @ x
+
+    def sensitivity_coords_periodic(self, cloud_a, cloud_b, out=None, wf_index=None, *, width=None, box_a=None, box_b=None, cell_a=None,
+                                    cell_b=None):
+        """`sensitivity_coords` on minimum-image rows (LoCoHD.sensitivity_from_coords_periodic): `box_a` / `box_b` / `cell_a` / `cell_b`
+        (keyword-only, host arrays) as `from_coords` takes them, a side with neither is open.  Returns a `MinImageSensitivity` of torch
+        CUDA tensors: the fields of `sensitivity_coords` and disp_a / disp_b [n][K][3] f64, the displacement from row atom r to the
+        nearest image of member idx[r][k] (dist = |disp| bit for bit).  K, `out` (a `MinImageSensitivity` of such tensors) and `width`
+        as in `sensitivity_coords` (lchd_sensitivity_coords_periodic_dev)."""
+        for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+            if box is not None and cell is not None:
+                raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
+        pc_a = dense_cells(box_a, cell_a, 1, "box_a", "cell_a")
+        pc_b = dense_cells(box_b, cell_b, 1, "box_b", "cell_b")
+        torch = self.torch
+        n = int(N.lib().lchd_cloud_size(cloud_a))
+        wf_ptr = None
+        if wf_index is not None:
+            assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= n
+            wf_ptr = C.c_void_p(wf_index.data_ptr())
+        if width is not None and int(width) < 1:
+            raise ValueError(f"width = {width}: a row holds at least one member")
+        k = int(out.idx_a.shape[1]) if out is not None else (n if width is None else int(width))
+        shapes = {"scores": (n,), "count": (n,), "disp": (n, k, 3)}
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            out = MinImageSensitivity(*[torch.empty(shapes.get(f.split("_")[0], (n, k)), device=dev,
+                                                    dtype=torch.int32 if f.startswith(("count", "idx")) else torch.float64)
+                                        for f in MinImageSensitivity._fields])
+        else:
+            for name, t in zip(MinImageSensitivity._fields, out):
+                want = torch.int32 if name.startswith(("count", "idx")) else torch.float64
+                assert t.is_cuda and t.dtype == want and t.is_contiguous() and tuple(t.shape) == shapes.get(name.split("_")[0], (n, k)), name
+        if n:
+            nine = [t for name, t in zip(MinImageSensitivity._fields, out) if not name.startswith("disp")]
+            N.check(N.lib().lchd_sensitivity_coords_periodic_dev(self._ctx, cloud_a, cloud_b, wf_ptr, N.dp(pc_a), N.dp(pc_b), k,
+                                                                 *[C.c_void_p(t.data_ptr()) for t in nine],
+                                                                 C.c_void_p(out.disp_a.data_ptr()), C.c_void_p(out.disp_b.data_ptr())))
+        return out
+
+    def gradient_coords_periodic(self, cloud_a, cloud_b, pair_weights=None, wf_index=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None):
+        """`(scores, grad_a[n, 3], grad_b[n, 3])` with grad = sum_r v_r dS_r/dx over the minimum-image rows
+        (LoCoHD.gradient_from_coords_periodic) as torch CUDA tensors.  No coordinates are passed: disp carries the geometry.
+        pair_weights: v, a tensor [n] (default: ones).  Assembled from `sensitivity_coords_periodic` by `dense_side_gradient_disp`."""
+        sens = self.sensitivity_coords_periodic(cloud_a, cloud_b, wf_index=wf_index, box_a=box_a, box_b=box_b, cell_a=cell_a, cell_b=cell_b)
+        return (sens.scores, self.dense_side_gradient_disp(sens.idx_a, sens.dist_a, sens.g_a, sens.disp_a, pair_weights),
+                self.dense_side_gradient_disp(sens.idx_b, sens.dist_b, sens.g_b, sens.disp_b, pair_weights))
+
+    def dense_side_gradient_disp(self, idx, dist, g, disp, pair_weights=None):
+        """One side of gradient_coords_periodic, [n][3] f64: c = v g / d (0 in slot 0, where d == 0 and where g is not finite), T = c disp
+        scattered into atom order by three [n][n] scatter_ passes (every atom occurs once per row and the padding has a column of its own: one
+        writer per element), grad =
+        T.sum(0) - T.sum(1): the atom as a member minus the atom as the row's own.  No index_add_, so the bits do not depend on torch's
+        determinism setting."""
+        torch = self.torch
+        n = idx.shape[0]
+        v = torch.ones(n, dtype=torch.float64, device=g.device) if pair_weights is None else pair_weights.to(torch.float64).reshape(-1)
+        use = (idx >= 0) & (dist > 0.0) & torch.isfinite(g)
+        use[:, 0] = False
+        coef = torch.where(use, v[:, None] * g / torch.where(use, dist, torch.ones_like(dist)), torch.zeros_like(g))
+        cols = torch.where(idx >= 0, idx, torch.full_like(idx, n)).long()  # (the padding goes to a spare column that is dropped)
+        grad = torch.empty((n, 3), dtype=torch.float64, device=g.device)
+        for d in range(3):
+            t = torch.zeros((n, n + 1), dtype=torch.float64, device=g.device).scatter_(1, cols, coef * disp[..., d])[:, :n]
+            grad[:, d] = t.sum(dim=0) - t.sum(dim=1)
+        return grad
 
     def attribution_coords(self, cloud_a, cloud_b, out=None, wf_index=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None):
         """Score attribution by category of the dense row pairs of two uploaded structures of equal size
