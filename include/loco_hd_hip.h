@@ -644,6 +644,64 @@ int lchd_sensitivity_coords_periodic(lchd_ctx *ctx, const lchd_config *cfg, cons
                                      int32_t *idx_a, double *dist_a, double *g_a, int32_t *count_b, int32_t *idx_b, double *dist_b,
                                      double *g_b, double *disp_a, double *disp_b);
 
+/* ---- native coordinate gradients (additive, not in the reference) ---------------------------------------
+ * grad = sum_p v_p dS_p/dx over the pairs of a call, v the pair weights: the backward pass of a loss built from LoCoHD scores.  The lists
+ * of the sensitivity calls above are reduced on the device and never reach the caller: a call returns scores, grad_a and grad_b alone.
+ * The contribution of slot k >= 1 of pair p on one side is fixed, in IEEE float64 with no contraction:
+ *
+ *     use   = idx[p][k] >= 0  &&  dist[p][k] > 0  &&  isfinite(g[p][k])
+ *     coef  = (v_p * g[p][k]) / dist[p][k]              (v_p = 1.0 without pair weights)
+ *     step_c = coef * (x[m][c] - x[a][c])               m = idx[p][k]
+ *     acc[m][c] += step_c ;  acc[a][c] += -step_c
+ *
+ * with idx / dist / g the lists of the sensitivity call of the same inputs and x the clouds' own coordinates.  The atom a is the anchor
+ * idx[p][0] in the thresholded form and the row's own atom p in the dense form (not idx[p][0], which is a coincident atom of lower index
+ * where one exists); slot 0 is skipped in both.
+ * Every acc[atom][c] is an exact fixed-point accumulator: LCHD_GRAD_LIMBS little-endian int64 limbs, each carrying one 32-bit chunk of
+ * trunc(step / q) with q = 2^LCHD_GRAD_QUANTUM_LOG2 (toward zero), added with 64-bit integer atomics; integer addition is associative,
+ * so the limbs do not depend on the order of the adds.  grad[atom][c] is THE correctly rounded (nearest, ties to even) double of the
+ * accumulated sum.  A gradient is therefore a function of the inputs alone: the same bits for every tile size, in default and
+ * deterministic mode, on every run -- given the same lists, which the sensitivity pass produces bit-identically for every slot size.
+ * A contribution must be finite and smaller than 2^LCHD_GRAD_LIMIT_LOG2 in magnitude: a call in which one was not completes and then
+ * fails with LCHD_EVALUE ("gradient contribution not finite or >= 2^63 (pair weights?)"); its scores are valid, its gradients
+ * unspecified, and the next call starts from clean accumulators.  Design constants: scores lie in [0, 1] and coordinates are in
+ * Angstrom, so contributions are O(1) times the pair weight; 63 bits cover any sane weight, and 2^-192 is below the last bit of anything
+ * a caller can observe.
+ *   scores[p]     as the sensitivity call returns them, bit for bit (NaN for an unusable pair, which contributes nothing)
+ *   grad_a/_b     [size(a)][3] / [size(b)][3] float64, every element written (0 for an atom no pair touches); for a batch the rows
+ *                 follow the GLOBAL atom indices
+ *   pair_weights  [n_pairs] float64 or NULL (ones)
+ * The thresholded form walks the pair list in tiles of tile_pairs: per tile the pass of lchd_sensitivity_primitives_dev -- unchanged --
+ * into a grow-only block of the context (40 width + 16 bytes per pair), then the accumulation; a tile is added only after its pass has
+ * succeeded, and a pass that reports too small a row width is repeated at lchd_sensitivity_needed_width first.  tile_pairs: 0 =
+ * lchd_gradient_plan on a quarter of the free device memory; > 0: that many pairs per tile, clamped to n_pairs; < 0: LCHD_EVALUE.
+ * lchd_gradient_plan: pure host arithmetic, the largest tile in 1 .. n_pairs with tile (40 width + 16) <= budget_bytes (1 if not even
+ * one pair fits: the allocation then decides); n_pairs < 1, a width outside 1 .. 65535 or a negative budget: LCHD_EVALUE.
+ * A list of n_pairs pairs whose rows sum to 2^31 slots or more is LCHD_EUNSUPPORTED (the limbs' headroom): split it.
+ * The dense form is one tile: the lists of lchd_sensitivity_coords_dev, the accumulation with a = the row, then the rounding.
+ * Clouds, batches, errors, stream and lock rules: those of lchd_sensitivity_primitives_dev / lchd_sensitivity_coords_dev; the context
+ * is held once for the whole call.  Image clouds are LCHD_EUNSUPPORTED, device groups have no gradient call; a block that cannot be
+ * allocated is LCHD_EUNSUPPORTED like every other out-of-memory condition.  The calls return with their outputs complete. */
+#define LCHD_GRAD_LIMBS 8
+#define LCHD_GRAD_QUANTUM_LOG2 (-192)
+#define LCHD_GRAD_LIMIT_LOG2 63
+int lchd_gradient_plan(int64_t n_pairs, int32_t width, int64_t budget_bytes, int64_t *tile_pairs_out);
+int lchd_gradient_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors, const int32_t *d_wf_index,
+                                 int64_t n_pairs, double threshold_distance, const double *d_pair_weights, int64_t tile_pairs,
+                                 double *d_scores, double *d_grad_a, double *d_grad_b);
+/* The same from host arrays (the structures as lchd_sensitivity_primitives takes them); outputs HOST. */
+int lchd_gradient_primitives(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a, const int32_t *tag_a,
+                             int64_t n_a, const double *xyz_b, const int32_t *cat_b, const int32_t *tag_b, int64_t n_b,
+                             const int64_t *anchors, const int32_t *wf_index, int64_t n_pairs, double threshold_distance,
+                             const double *pair_weights, int64_t tile_pairs, double *scores, double *grad_a, double *grad_b);
+/* Dense rows of two device-resident structures of equal size n: d_wf_index / d_pair_weights DEVICE [n] or NULL, d_scores DEVICE [n]. */
+int lchd_gradient_coords_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, const double *d_pair_weights,
+                             double *d_scores, double *d_grad_a, double *d_grad_b);
+/* The same from host arrays, as lchd_sensitivity_coords takes them; grad_a / grad_b HOST [n][3]. */
+int lchd_gradient_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                         int64_t len_seq_b, const double *xyz_a, const double *xyz_b, int64_t n, const int32_t *wf_index,
+                         const double *pair_weights, double *scores, double *grad_a, double *grad_b);
+
 /* ---- cross-scoring (additive, not in the reference) ------------------------------------------------------
  * Every anchor of one list against every anchor of another: which environments of B look like this environment of A.
  *   cross:   out[i][j] = the score lchd_from_primitives_dev gives the pair (anchors_a[i], anchors_b[j]) -- same threshold, configuration

@@ -106,6 +106,9 @@ DENSE_HOOK_OLD_ROWS, DENSE_HOOK_NO_FUSED = 1, 2
 # LCHD_SENSITIVITY_ROWS_LDS_POINTS: the longest (padded) dense row whose indexed list is sorted in LDS; longer ones are sorted in place
 SENSITIVITY_ROWS_LDS_POINTS = 8192
 
+# LCHD_GRAD_LIMBS / LCHD_GRAD_QUANTUM_LOG2 / LCHD_GRAD_LIMIT_LOG2: the exact accumulator of the native gradient calls
+GRAD_LIMBS, GRAD_QUANTUM_LOG2, GRAD_LIMIT_LOG2 = 8, -192, 63
+
 # lchd_sweep_family / lchd_sweep_hook bits
 SWEEP_INLINE, SWEEP_TEAM240, SWEEP_TEAM480, SWEEP_C8, SWEEP_INDIRECT, SWEEP_PLAIN, SWEEP_INC, SWEEP_WIDE = (1 << k for k in range(8))
 HOOK_NO_DUO, HOOK_NO_COUNT8, HOOK_NO_C8_TEAM, HOOK_NO_INLINE_META, HOOK_FORCE_WIDE, HOOK_FORCE_GENERIC, HOOK_FORCE_BIGENV, HOOK_NO_SWEEP_HINT = (
@@ -183,6 +186,12 @@ _PROTOS = {
     "lchd_sensitivity_coords_periodic_dev": (C.c_int, [_VP, _VP, _VP, _VP, _DP, _DP, _i32] + [_VP] * 11),
     "lchd_sensitivity_coords_periodic": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _IP, _DP, _DP, _i32,
                                                    _DP, _IP, _IP, _DP, _DP, _IP, _IP, _DP, _DP, _DP, _DP]),
+    "lchd_gradient_plan": (C.c_int, [_i64, _i32, _i64, _LP]),
+    "lchd_gradient_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _i64, _f64, _VP, _i64, _VP, _VP, _VP]),
+    "lchd_gradient_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _DP, _i64,
+                                           _DP, _DP, _DP]),
+    "lchd_gradient_coords_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lchd_gradient_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _IP, _DP, _DP, _DP, _DP]),
     "lchd_cross_plan": (C.c_int, [_i64, _i64, _i64, _LP]),
     "lchd_cross_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _i64, _VP, _i64, _i32, _f64, _i64, _VP]),
     "lchd_nearest_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _i64, _VP, _i64, _i32, _f64, _i64, _i32, _VP, _VP]),

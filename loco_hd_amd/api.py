@@ -1216,6 +1216,68 @@ class LoCoHD:
         return (sens.scores, self._dense_coords_gradient(sens.idx_a, sens.dist_a, sens.g_a, v, xa),
                 self._dense_coords_gradient(sens.idx_b, sens.dist_b, sens.g_b, v, xb))
 
+    # ---- native coordinate gradients (additive) ---------------------------------------------------------------
+    # The same gradients in one native call (include/loco_hd_hip.h, "native coordinate gradients"): the lists are reduced on the device
+    # into exact fixed-point accumulators, so the result is a function of the inputs alone and no list reaches the host.
+    def native_gradient_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                                        threshold_distance: float, pair_weights=None, *, tile_pairs: int = 0, box_a=None, box_b=None,
+                                        cell_a=None, cell_b=None):
+        """Additive: `(scores, grad_a[Na, 3], grad_b[Nb, 3])` as `gradient_from_primitives` defines them, reduced on the device
+        (lchd_gradient_primitives): every term v g (x_m - x_anchor) / d is computed in float64 as that call computes it, the terms of
+        an atom are summed EXACTLY (fixed point, quantum 2^-192) and rounded once.  The bits are the same for every `tile_pairs` (pairs
+        per pass; 0: planned from the free device memory), in default and deterministic mode, on every run.  `scores` are those of
+        `sensitivity_from_primitives`.  ValueError if a term is not finite or reaches 2^63.  Open structures on one device only."""
+        if int(tile_pairs) < 0:
+            raise ValueError(f"tile_pairs = {int(tile_pairs)} is negative (0: planned from the free device memory)")
+        if box_a is not None or box_b is not None or cell_a is not None or cell_b is not None:
+            raise NotImplementedError("native_gradient_from_primitives takes open structures: periodic boxes and cells are not supported")
+        if self._devices is not None:
+            raise NotImplementedError("a native gradient call applies to one device (a device group has no gradient call): drop devices=[...]")
+        pairs, idx = self._anchor_arrays(anchor_pairs)
+        anchors = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        n = len(anchors)
+        v = None
+        if pair_weights is not None:
+            v = np.ascontiguousarray(_f64(pair_weights).reshape(-1))
+            if len(v) != n:
+                raise ValueError(f"pair_weights has {len(v)} entries for {n} anchor pairs")
+        pa, pb, interner = self._packed_lists(prim_a, prim_b)
+        cfg, keep = self._config(interner)
+        xa, xb = _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3)
+        scores, ga, gb = np.empty(n), np.zeros((len(xa), 3)), np.zeros((len(xb), 3))
+        N.check(N.lib().lchd_gradient_primitives(self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa), N.dp(xb),
+                                                 N.ip(pb.cat), N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx), n, float(threshold_distance),
+                                                 N.dp(v), int(tile_pairs), N.dp(scores), N.dp(ga), N.dp(gb)))
+        return scores, ga, gb
+
+    def native_gradient_from_coords(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None, pair_weights=None):
+        """Additive: `(scores, grad_a[n, 3], grad_b[n, 3])` as `gradient_from_coords` defines them, reduced on the device
+        (lchd_gradient_coords): row r's terms v_r g (x_m - x_r) / d are summed exactly per atom and rounded once, as
+        `native_gradient_from_primitives` does.  Open structures on one device only."""
+        if self._devices is not None:
+            raise NotImplementedError("a native gradient call applies to one device (a device group has no gradient call): drop devices=[...]")
+        xa, xb = self._coords(coords_a), self._coords(coords_b)
+        if len(xa) != len(xb):
+            raise ValueError(f"Expected matrices with the same length, got lengths {len(xa)} and {len(xb)}!")
+        n = len(xa)
+        v = None
+        if pair_weights is not None:
+            v = np.ascontiguousarray(_f64(pair_weights).reshape(-1))
+            if len(v) != n:
+                raise ValueError(f"pair_weights has {len(v)} entries for {n} rows")
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], n)
+        if len(self._weights) > 64:
+            raise NotImplementedError(f"a sensitivity call takes at most 64 categories (got {len(self._weights)})")
+        if n > 65535:
+            raise NotImplementedError(f"a sensitivity call takes dense rows of at most 65535 points (got {n} / {n})")
+        ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
+        cfg, keep = self._config()
+        scores, ga, gb = np.empty(n), np.zeros((n, 3)), np.zeros((n, 3))
+        if n:
+            N.check(N.lib().lchd_gradient_coords(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(xa), N.dp(xb), n,
+                                                 N.ip(idx), N.dp(v), N.dp(scores), N.dp(ga), N.dp(gb)))
+        return scores, ga, gb
+
     # ---- ... of dense rows in periodic cells (additive) ------------------------------------------------------
     # The minimum-image rows of from_coords(box_a= / cell_a= ...) (include/loco_hd_hip.h, lchd_sensitivity_coords_periodic).  A row
     # stores the length of the chosen image's vector alone, so the open product rowsum(M) x - M x no longer gives the gradient: the

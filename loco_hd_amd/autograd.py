@@ -11,6 +11,9 @@ ignores points entering or leaving at the threshold (exact when the weight funct
 
 Forward is DeviceSession.sensitivity_coords, backward is side A of DeviceSession.gradient_coords (dense_side_gradient).
 
+Both take `native=True`: backward is then one DeviceSession.native_gradient / native_gradient_coords call with grad_output as the pair
+weights -- the gradient reduced on the device into exact accumulators, its bits a function of the inputs alone.
+
     scores = locohd_scores_dense_periodic(session, cloud_b_ref, xyz_a, cat_a, box=(Lx, Ly, Lz))   # ... on minimum-image rows
 
 Forward is DeviceSession.sensitivity_coords_periodic, backward is side A of DeviceSession.gradient_coords_periodic
@@ -50,6 +53,54 @@ class _LoCoHDScores(torch.autograd.Function):
         s = ctx.sens
         grad_a = ctx.session.side_gradient(s.scores, s.idx_a, s.dist_a, s.g_a, x.to(torch.float64), grad_output)  # side A alone moves
         return grad_a.to(x.dtype), None, None, None, None, None, None
+
+
+class _LoCoHDScoresNative(torch.autograd.Function):
+    """locohd_scores(native=True): forward and backward are one DeviceSession.native_gradient call each, no list is kept between them."""
+
+    @staticmethod
+    def forward(ctx, xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, threshold_distance):
+        x = xyz_a.detach()
+        ctx.session, ctx.cloud_b, ctx.anchors, ctx.thr = session, cloud_b_ref, anchors, threshold_distance
+        ctx.cat = np.asarray(cat_a, dtype=np.int32)
+        ctx.tag = None if tag_a is None else np.asarray(tag_a, dtype=np.int32)
+        ctx.save_for_backward(x)
+        return _native_call(ctx, x, None)[0]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (x,) = ctx.saved_tensors
+        return _native_call(ctx, x, grad_output)[1].to(x.dtype), None, None, None, None, None, None  # side A alone moves
+
+
+def _native_call(ctx, x, weights):
+    """The movable structure uploaded, one native gradient call (thresholded with ctx.anchors, dense without), the structure dropped."""
+    session = ctx.session
+    cloud_a = session.upload(x.cpu().numpy(), ctx.cat, ctx.tag)
+    try:
+        if ctx.anchors is None:
+            return session.native_gradient_coords(cloud_a, ctx.cloud_b, pair_weights=weights, wf_index=ctx.wf_index)
+        return session.native_gradient(cloud_a, ctx.cloud_b, ctx.anchors, ctx.thr, pair_weights=weights)
+    finally:
+        session._clouds.remove(cloud_a)
+        N.lib().lchd_cloud_destroy(session._ctx, cloud_a)
+
+
+class _LoCoHDScoresDenseNative(torch.autograd.Function):
+    """locohd_scores_dense(native=True): as _LoCoHDScoresNative, on DeviceSession.native_gradient_coords."""
+
+    @staticmethod
+    def forward(ctx, xyz_a, session, cloud_b_ref, cat_a, wf_index):
+        x = xyz_a.detach()
+        ctx.session, ctx.cloud_b, ctx.anchors, ctx.wf_index = session, cloud_b_ref, None, wf_index
+        ctx.cat, ctx.tag = np.asarray(cat_a, dtype=np.int32), None
+        ctx.save_for_backward(x)
+        return _native_call(ctx, x, None)[0]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (x,) = ctx.saved_tensors
+        return _native_call(ctx, x, grad_output)[1].to(x.dtype), None, None, None, None
 
 
 class _LoCoHDScoresPeriodic(torch.autograd.Function):
@@ -131,18 +182,26 @@ def locohd_scores_dense_periodic(session, cloud_b_ref, xyz_a, cat_a, wf_index=No
     return _LoCoHDScoresDensePeriodic.apply(xyz_a, session, cloud_b_ref, cat_a, wf_index, box, cell, ref_box, ref_cell)
 
 
-def locohd_scores_dense(session, cloud_b_ref, xyz_a, cat_a, wf_index=None):
+def locohd_scores_dense(session, cloud_b_ref, xyz_a, cat_a, wf_index=None, native=False):
     """The scores of the dense rows (DeviceSession.sensitivity_coords: row r = both structures seen from their atoms r) of a movable
     structure -- xyz_a: torch float64 CUDA tensor [n][3], cat_a: its category ids (host array) -- against `cloud_b_ref`, a structure of
     the same size uploaded to `session`; differentiable with respect to xyz_a.  Backward is side A of DeviceSession.gradient_coords with
-    grad_output as the row weights: exact (no threshold), one-sided at ties."""
+    grad_output as the row weights: exact (no threshold), one-sided at ties.  native=True: backward is one
+    DeviceSession.native_gradient_coords call with grad_output as the pair weights (its bits; forward is such a call too, so no list is
+    kept between the two)."""
+    if native:
+        return _LoCoHDScoresDenseNative.apply(xyz_a, session, cloud_b_ref, cat_a, wf_index)
     return _LoCoHDScoresDense.apply(xyz_a, session, cloud_b_ref, cat_a, wf_index)
 
 
-def locohd_scores(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, threshold_distance):
+def locohd_scores(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, threshold_distance, native=False):
     """The scores of the anchor pairs (torch int64 CUDA tensor [P][2]: atom of the movable structure, atom of the reference) of a
     movable structure -- xyz_a: torch float64 CUDA tensor [Na][3], cat_a / tag_a: its category ids and interned tags (host arrays) --
-    against `cloud_b_ref`, a cloud uploaded to `session`; differentiable with respect to xyz_a."""
+    against `cloud_b_ref`, a cloud uploaded to `session`; differentiable with respect to xyz_a.  native=True: backward is one
+    DeviceSession.native_gradient call with grad_output as the pair weights (its bits; forward is such a call too, so no list is kept
+    between the two); the default leaves the assembly in torch."""
+    if native:
+        return _LoCoHDScoresNative.apply(xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, float(threshold_distance))
     return _LoCoHDScores.apply(xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, float(threshold_distance))
 
 

@@ -278,6 +278,12 @@ struct lchd_ctx {
     int64_t sens_needed = 0;          // lchd_sensitivity_needed_width: the longest list among the pairs of the last sensitivity call
     char* d_cross = nullptr;          // cross-scoring calls: the pair records, wf indices and score scratch of one row tile (grow-only likewise)
     size_t cross_cap = 0;
+    char* d_grad = nullptr;           // native gradient calls: the sensitivity lists of one tile of pairs (grow-only likewise)
+    size_t grad_cap = 0;
+    char* d_grad_acc = nullptr;       // ... and the exact accumulators of both sides with the status word in front: all zero between calls
+    size_t grad_acc_cap = 0;
+    bool grad_acc_dirty = false;      // a gradient call was abandoned between its first tile and k_grad_finish: memset before the next one
+    int32_t grad_width = 0;           // the row width the last thresholded gradient call ended with (the next one starts there)
     int64_t n_subset_passes = 0;    // second passes run so far
     size_t last_store_bytes = 0;    // environment-store bytes (keys + categories, both sides) of the passes of the last from_primitives call
     int64_t n_passes = 0;           // from_primitives passes enqueued so far (a call is one pass unless a capacity / launch-set retry repeats it)
@@ -513,6 +519,8 @@ extern "C" void lchd_ctx_destroy(lchd_ctx* c) {
     (void)hipFree(c->d_radial_bounds);
     (void)hipFree(c->d_indexed);
     (void)hipFree(c->d_cross);
+    (void)hipFree(c->d_grad);
+    (void)hipFree(c->d_grad_acc);
     (void)hipFree(c->d_shard);
     (void)hipFree(c->d_bad);
     if (c->shard_stream) (void)hipStreamDestroy(c->shard_stream);
@@ -4824,4 +4832,243 @@ extern "C" int lchd_nearest_primitives(lchd_ctx* c, const lchd_config* cfg, cons
     if (int rc = cross_args(n_a, n_b, tile_rows, true, k)) return rc;
     return cross_host(c, cfg, xyz_a, cat_a, tag_a, n_atoms_a, xyz_b, cat_b, tag_b, n_atoms_b, anchors_a, n_a, anchors_b, n_b, wf_index, thr,
                       tile_rows, k, scores, cols);
+}
+
+// ------------------------------------------------------------------------------------------------
+// native coordinate gradients: the sensitivity lists reduced on the device (include/loco_hd_hip.h, "native coordinate gradients")
+// ------------------------------------------------------------------------------------------------
+// A thresholded call walks its pair list in tiles.  Per tile the sensitivity pass (lchd_sensitivity_primitives_dev, unchanged: the
+// context is held by this call, the owner re-enters) writes its lists into the context's gradient block -- the scores go straight to
+// the caller's array -- and k_grad_accumulate (lchd_gradient.hip) adds them into the exact accumulators of lchd_exact_sum.h.  A tile
+// is added only after its pass has succeeded: a pass that reports too small a width is repeated at lchd_sensitivity_needed_width first.
+// The dense form is one tile of lchd_sensitivity_coords_dev with the row's atom as the anchor.  k_grad_finish rounds once at the end.
+static int64_t grad_pair_bytes(int32_t width) { return 8 * (int64_t)sens_row(width, kSensPlain); }  // 40 width + 16
+constexpr int64_t kGradMaxAdds = (int64_t)1 << 31;  // additions a limb takes without carry propagation (lchd_exact_sum.h)
+
+extern "C" int lchd_gradient_plan(int64_t n_pairs, int32_t width, int64_t budget_bytes, int64_t* tile_pairs_out) {
+    if (!tile_pairs_out) return fail(LCHD_EVALUE, "null output pointer");
+    *tile_pairs_out = 0;
+    if (n_pairs < 1 || width < 1 || width > kRadialMaxPoints || budget_bytes < 0)
+        return fail(LCHD_EVALUE, "a gradient plan takes n_pairs >= 1, a width in 1 .. %d and a budget >= 0 (got %lld, %d, %lld)", kRadialMaxPoints,
+                    (long long)n_pairs, width, (long long)budget_bytes);
+    const int64_t fit = budget_bytes / grad_pair_bytes(width);
+    *tile_pairs_out = std::max<int64_t>(1, std::min(fit, n_pairs));
+    return LCHD_OK;
+}
+
+struct GradRequest {
+    lchd_cloud *a, *b;
+    const int64_t* anchors;   // DEVICE [n_pairs][2]; null: the dense form (pair r = row r, n_pairs = size(a))
+    const int32_t* wf;        // DEVICE or null
+    int64_t n_pairs;
+    double thr;
+    const double* weights;    // DEVICE [n_pairs] or null
+    int64_t tile_pairs;       // 0: lchd_gradient_plan
+    double *scores, *grad_a, *grad_b;  // DEVICE
+};
+static int grad_core(lchd_ctx* c, const GradRequest& R) {
+    if (!c || !R.a || !R.b) return fail(LCHD_EVALUE, "null argument");
+    const bool dense = R.anchors == nullptr;
+    if (R.tile_pairs < 0) return fail(LCHD_EVALUE, "tile_pairs = %lld is negative (0: planned from the free device memory)", (long long)R.tile_pairs);
+    if (R.n_pairs < 0) return fail(LCHD_EVALUE, "negative pair count");
+    if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (R.a->images || R.b->images) return fail(LCHD_EUNSUPPORTED, "a native gradient call takes the structures themselves, not periodic image clouds");
+    if (dense && R.a->n != R.b->n)
+        return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)R.a->n, (long long)R.b->n);
+    if (dense && (R.a->sid || R.b->sid)) return fail(LCHD_EVALUE, "from_coords takes single structures, not batches");
+    const int64_t n_at[2] = {R.a->n, R.b->n};
+    if ((n_at[0] > 0 && !R.grad_a) || (n_at[1] > 0 && !R.grad_b) || (R.n_pairs > 0 && !R.scores)) return fail(LCHD_EVALUE, "null output pointer");
+    if (dense && R.n_pairs > kRadialMaxPoints)
+        return fail(LCHD_EUNSUPPORTED, "a sensitivity call takes dense rows of at most %d points (got %lld / %lld)", kRadialMaxPoints, (long long)n_at[0],
+                    (long long)n_at[1]);
+    CTX_GUARD(c);
+    hipStream_t s = c->stream;
+    // the accumulators: [status word, 256 bytes] | side A [n_a][3][limbs] | side B; zero between calls (k_grad_finish leaves them so)
+    const size_t side_bytes[2] = {(size_t)n_at[0] * 3 * LCHD_GRAD_LIMBS * 8, (size_t)n_at[1] * 3 * LCHD_GRAD_LIMBS * 8};
+    const size_t acc_bytes = 256 + side_bytes[0] + side_bytes[1];
+    const bool grown = acc_bytes > c->grad_acc_cap;
+    if (grown) HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = grow_block(c->d_grad_acc, c->grad_acc_cap, acc_bytes)) return rc;
+    if (grown || c->grad_acc_dirty) HIP_TRY(hipMemsetAsync(c->d_grad_acc, 0, c->grad_acc_cap, s));
+    c->grad_acc_dirty = true;
+    uint32_t* const d_flag = reinterpret_cast<uint32_t*>(c->d_grad_acc);
+    int64_t* const acc[2] = {reinterpret_cast<int64_t*>(c->d_grad_acc + 256), reinterpret_cast<int64_t*>(c->d_grad_acc + 256 + side_bytes[0])};
+
+    int32_t width = dense ? (int32_t)std::max<int64_t>(R.n_pairs, 1) : std::min(std::max(128, c->grad_width), kRadialMaxPoints);
+    int64_t tile = dense ? R.n_pairs : std::min(R.tile_pairs, R.n_pairs);
+    const bool planned = !dense && R.tile_pairs == 0 && R.n_pairs > 0;
+    size_t budget = 0;
+    if (planned) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        budget = std::min<size_t>(free_b, (size_t)1 << 62) / 4;  // (the pass itself takes its stores and arena next to the lists)
+        if (int rc = lchd_gradient_plan(R.n_pairs, width, (int64_t)budget, &tile)) return rc;
+    }
+    int64_t adds = 0;  // slots handed to k_grad_accumulate so far: what one atom's limbs can have received at the most
+    for (int64_t p0 = 0; p0 < R.n_pairs;) {
+        const int64_t tp = std::min(tile, R.n_pairs - p0);
+        if (!dense && adds + tp * (int64_t)width >= kGradMaxAdds)
+            return fail(LCHD_EUNSUPPORTED, "%lld pairs with rows of %d slots exceed the 2^31 additions an exact accumulator takes: split the list",
+                        (long long)R.n_pairs, width);
+        const size_t lists = (size_t)tp * (size_t)grad_pair_bytes(width);
+        if (lists > c->grad_cap) HIP_TRY(hipStreamSynchronize(s));  // (the block about to be freed may still be read)
+        if (int rc = grow_block(c->d_grad, c->grad_cap, lists)) return rc;
+        SensitivityOut o = sens_carve(reinterpret_cast<double*>(c->d_grad), tp, width);
+        o.scores = R.scores + p0;
+        const int32_t* wf = R.wf ? R.wf + p0 : nullptr;
+        const int rc = dense ? lchd_sensitivity_coords_dev(c, R.a, R.b, wf, width, o.scores, o.count_a, o.idx_a, o.dist_a, o.g_a, o.count_b, o.idx_b,
+                                                           o.dist_b, o.g_b)
+                             : lchd_sensitivity_primitives_dev(c, R.a, R.b, R.anchors + 2 * p0, wf, tp, R.thr, width, o.scores, o.count_a, o.idx_a,
+                                                               o.dist_a, o.g_a, o.count_b, o.idx_b, o.dist_b, o.g_b);
+        if (rc == LCHD_EVALUE && !dense && c->sens_needed > width) {  // too narrow: nothing of this tile has been added; once more, wider
+            width = (int32_t)c->sens_needed;
+            if (planned) {
+                int64_t fit = tile;
+                if (int rc2 = lchd_gradient_plan(R.n_pairs, width, (int64_t)budget, &fit)) return rc2;
+                tile = std::min(tile, fit);
+            }
+            continue;
+        }
+        if (rc) return rc;
+        GradAccumArgs ga{};
+        const lchd_cloud* const cl[2] = {R.a, R.b};
+        for (int k = 0; k < 2; ++k) {
+            GradSide& S = ga.s[k];
+            S.idx = k ? o.idx_b : o.idx_a; S.dist = k ? o.dist_b : o.dist_a; S.g = k ? o.g_b : o.g_a;
+            S.disp = nullptr;
+            S.x = cl[k]->x; S.y = cl[k]->y; S.z = cl[k]->z;
+            S.n = n_at[k];
+            S.acc = acc[k];
+        }
+        ga.weights = R.weights ? R.weights + p0 : nullptr;
+        ga.n_pairs = tp;
+        ga.width = width;
+        ga.dense = dense ? 1 : 0;
+        ga.flag = d_flag;
+        if (!launch_grad_accumulate(s, ga)) return fail(LCHD_EDEVICE, "the gradient accumulation kernel rejected its launch configuration");
+        HIP_TRY(hipGetLastError());
+        adds += tp * (int64_t)width;
+        p0 += tp;
+    }
+    if (!dense) c->grad_width = width;
+    if (!launch_grad_finish(s, acc[0], n_at[0], R.grad_a) || !launch_grad_finish(s, acc[1], n_at[1], R.grad_b))
+        return fail(LCHD_EDEVICE, "the gradient finish kernel rejected its launch configuration");
+    HIP_TRY(hipGetLastError());
+    uint32_t flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));  // the call returns with the outputs complete, as the sensitivity call does
+    if (flag) HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof flag, s));
+    c->grad_acc_dirty = false;
+    if (flag) return fail(LCHD_EVALUE, "gradient contribution not finite or >= 2^63 (pair weights?)");
+    return LCHD_OK;
+}
+
+extern "C" int lchd_gradient_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
+                                            int64_t n_pairs, double thr, const double* d_pair_weights, int64_t tile_pairs, double* d_scores,
+                                            double* d_grad_a, double* d_grad_b) {
+    CTX_LOCK(c);
+    if (n_pairs > 0 && !d_anchors) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    static const int64_t no_pairs[2] = {0, 0};  // (a non-null list marks the thresholded form; with no pairs it is never read)
+    return grad_core(c, GradRequest{a, b, d_anchors ? d_anchors : no_pairs, d_wf_index, n_pairs, thr, d_pair_weights, tile_pairs, d_scores, d_grad_a,
+                                    d_grad_b});
+}
+extern "C" int lchd_gradient_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* d_pair_weights,
+                                        double* d_scores, double* d_grad_a, double* d_grad_b) {
+    CTX_LOCK(c);
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    return grad_core(c, GradRequest{a, b, nullptr, d_wf_index, a->n, 0.0, d_pair_weights, 0, d_scores, d_grad_a, d_grad_b});
+}
+
+// The host-array forms: both structures as temporary clouds; the list, the weights and the three outputs in one temporary device block.
+struct GradHostArrays {
+    const int64_t* anchors;   // null: the dense form
+    const int32_t* wf;
+    const double* weights;
+    int64_t n_pairs, n_a, n_b;
+    double thr;
+    int64_t tile_pairs;
+    double *scores, *grad_a, *grad_b;
+};
+static int grad_host(lchd_ctx* c, HostTemps& t, const GradHostArrays& H) {
+    const size_t P = (size_t)H.n_pairs, na = (size_t)H.n_a, nb = (size_t)H.n_b;
+    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t o_wf = up(H.anchors ? 16 * P : 0), o_w = up(o_wf + (H.wf ? 4 * P : 0)), o_sc = up(o_w + (H.weights ? 8 * P : 0)),
+                 o_ga = up(o_sc + 8 * P), o_gb = up(o_ga + 24 * na), total = o_gb + 24 * nb;
+    if (hipMalloc(&t.d_blk, total ? total : 256) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(LCHD_EUNSUPPORTED, "no device memory for the %zu bytes of lists and outputs of this call", total);
+    }
+    if (H.anchors && P) HIP_TRY(hipMemcpy(t.d_blk, H.anchors, 16 * P, hipMemcpyHostToDevice));
+    if (H.wf && P) HIP_TRY(hipMemcpy(t.d_blk + o_wf, H.wf, 4 * P, hipMemcpyHostToDevice));
+    if (H.weights && P) HIP_TRY(hipMemcpy(t.d_blk + o_w, H.weights, 8 * P, hipMemcpyHostToDevice));
+    static const int64_t no_pairs[2] = {0, 0};
+    const GradRequest R{t.clouds[0], t.clouds[1],
+                        H.anchors ? (P ? reinterpret_cast<const int64_t*>(t.d_blk) : no_pairs) : nullptr,
+                        H.wf ? reinterpret_cast<const int32_t*>(t.d_blk + o_wf) : nullptr, H.n_pairs, H.thr,
+                        H.weights ? reinterpret_cast<const double*>(t.d_blk + o_w) : nullptr, H.tile_pairs,
+                        reinterpret_cast<double*>(t.d_blk + o_sc), reinterpret_cast<double*>(t.d_blk + o_ga), reinterpret_cast<double*>(t.d_blk + o_gb)};
+    const int rc = grad_core(c, R);
+    // (an out-of-range contribution fails the call behind complete outputs: the scores are valid and go back)
+    const bool range = rc == LCHD_EVALUE && strstr(g_err, "gradient contribution") != nullptr;
+    if (rc == LCHD_OK || range) {
+        const std::string msg = g_err;
+        if (P) HIP_TRY(hipMemcpy(H.scores, t.d_blk + o_sc, 8 * P, hipMemcpyDeviceToHost));
+        if (na) HIP_TRY(hipMemcpy(H.grad_a, t.d_blk + o_ga, 24 * na, hipMemcpyDeviceToHost));
+        if (nb) HIP_TRY(hipMemcpy(H.grad_b, t.d_blk + o_gb, 24 * nb, hipMemcpyDeviceToHost));
+        if (rc) snprintf(g_err, sizeof g_err, "%s", msg.c_str());
+    }
+    return rc;
+}
+
+extern "C" int lchd_gradient_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
+                                        int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
+                                        const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, const double* pair_weights,
+                                        int64_t tile_pairs, double* scores, double* grad_a, double* grad_b) {
+    CTX_LOCK(c);
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (tile_pairs < 0) return fail(LCHD_EVALUE, "tile_pairs = %lld is negative (0: planned from the free device memory)", (long long)tile_pairs);
+    if (n_pairs < 0) return fail(LCHD_EVALUE, "negative pair count");
+    if (int rc = check_wf_index(cfg, wf_index, n_pairs)) return rc;
+    if (n_a < 0 || n_b < 0 || n_a > ((int64_t)1 << 27) || n_b > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "structure size out of range");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if ((n_pairs > 0 && (!anchors || !scores)) || (n_a > 0 && !grad_a) || (n_b > 0 && !grad_b)) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    static const int64_t no_pairs[2] = {0, 0};
+    HostTemps t(c);
+    auto run = [&]() -> int {
+        if (int rc = lchd_cloud_create(c, xyz_a, cat_a, tag_a, n_a, &t.clouds[0])) return rc;
+        if (int rc = lchd_cloud_create(c, xyz_b, cat_b, tag_b, n_b, &t.clouds[1])) return rc;
+        return grad_host(c, t, GradHostArrays{anchors ? anchors : no_pairs, wf_index, pair_weights, n_pairs, n_a, n_b, thr, tile_pairs, scores, grad_a, grad_b});
+    };
+    t.rc = run();
+    c->last_valid = false;  // the clouds of this call go away (`t` destroys them on return)
+    c->pend.req.a = c->pend.req.b = nullptr;
+    return t.rc;
+}
+extern "C" int lchd_gradient_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                    int64_t len_seq_b, const double* xyz_a, const double* xyz_b, int64_t n, const int32_t* wf_index,
+                                    const double* pair_weights, double* scores, double* grad_a, double* grad_b) {
+    CTX_LOCK(c);
+    if (n < 0) return fail(LCHD_EVALUE, "negative structure size");
+    if (int rc = coords_lengths(xyz_a, n, xyz_b, n)) return rc;
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    if (int rc = check_wf_index(cfg, wf_index, n)) return rc;
+    if (n == 0) return LCHD_OK;
+    if (n > len_seq_a || n > len_seq_b) return fail(LCHD_EPANIC, "index out of bounds: a distance row is longer than its seq");
+    if (!seq_a || !seq_b || !scores || !grad_a || !grad_b) return fail(LCHD_EVALUE, "null pointer");
+    HostTemps t(c);
+    auto run = [&]() -> int {
+        if (int rc = lchd_cloud_create(c, xyz_a, seq_a, nullptr, n, &t.clouds[0])) return rc;
+        if (int rc = lchd_cloud_create(c, xyz_b, seq_b, nullptr, n, &t.clouds[1])) return rc;
+        return grad_host(c, t, GradHostArrays{nullptr, wf_index, pair_weights, n, n, n, 0.0, 0, scores, grad_a, grad_b});
+    };
+    t.rc = run();
+    c->last_valid = false;
+    c->pend.req.a = c->pend.req.b = nullptr;
+    return t.rc;
 }

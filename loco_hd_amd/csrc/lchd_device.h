@@ -567,6 +567,26 @@ bool launch_sens_min_image_disp(hipStream_t s, const SensDispArgs& a);  // false
 void launch_cross_pairs(hipStream_t s, const int64_t* anchors_a, const int64_t* anchors_b, int64_t row0, int64_t rows, int64_t n_b, int32_t wf,
                         int64_t* pairs, int32_t* wf_out);
 void launch_nearest_rows(hipStream_t s, const double* scores, int64_t rows, int64_t n_b, int32_t k, double* out_scores, int32_t* out_cols);
+// Native coordinate gradients (lchd_gradient.hip): the sensitivity lists of one tile of pairs, in the layouts k_sensitivity writes, added
+// into exact fixed-point accumulators (lchd_exact_sum.h: LCHD_GRAD_LIMBS int64 limbs per atom and component), and their rounding to doubles.
+struct GradSide {
+    const int32_t* idx;        // [P][K] members (-1: padding)
+    const double *dist, *g;    // [P][K]
+    const double* disp;        // [P][K][3] the members' displacements, or null: x[member] - x[anchor] from the coordinates below
+    const double *x, *y, *z;   // the side's coordinates (not read with disp)
+    int64_t n;                 // its atoms (anchors and members are checked against it)
+    int64_t* acc;              // [n][3][LCHD_GRAD_LIMBS]
+};
+struct GradAccumArgs {
+    GradSide s[2];
+    const double* weights;     // [P] pair weights of the tile, or null: 1.0
+    int64_t n_pairs;           // P
+    int32_t width;             // K
+    int32_t dense;             // 0: the anchor of pair p is idx[p][0]; 1: dense rows, the anchor of row p is atom p
+    uint32_t* flag;            // LCHD_XS_OUT_OF_RANGE is ORed into it
+};
+bool launch_grad_accumulate(hipStream_t s, const GradAccumArgs& a);  // false: nothing launched (a null array, a side shorter than its rows)
+bool launch_grad_finish(hipStream_t s, int64_t* acc, int64_t n_atoms, double* grad);  // grad [n_atoms][3]; zeroes acc
 void launch_mark_overflow(hipStream_t s, const uint32_t* list_a, uint32_t na, const uint32_t* list_b, uint32_t nb, uint32_t* bits_a, uint32_t* bits_b);
 void launch_count_overflow(hipStream_t s, const OverflowSelect& a, unsigned long long* total);
 void launch_write_overflow(hipStream_t s, const OverflowSelect& a);

@@ -546,6 +546,55 @@ class DeviceSession:
         grad.index_add_(0, anchor.reshape(-1), -step.reshape(-1, 3))
         return grad
 
+    def _native_gradient_buffers(self, cloud_a, cloud_b, p, pair_weights, wf_index, out):
+        """Checked arguments of the two native gradient calls: (weights tensor or None, wf pointer, (scores, grad_a, grad_b))."""
+        torch = self.torch
+        na, nb = (int(N.lib().lchd_cloud_size(cl)) for cl in (cloud_a, cloud_b))
+        dev = torch.device("cuda", self.device)
+        w = wf_ptr = None
+        if pair_weights is not None:
+            if pair_weights.numel() != p:
+                raise ValueError(f"pair_weights has {pair_weights.numel()} entries for {p} pairs")
+            w = pair_weights.detach().to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+        if wf_index is not None:
+            assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= p
+            wf_ptr = C.c_void_p(wf_index.data_ptr())
+        if out is None:
+            out = (torch.empty(p, dtype=torch.float64, device=dev), torch.empty((na, 3), dtype=torch.float64, device=dev),
+                   torch.empty((nb, 3), dtype=torch.float64, device=dev))
+        for t, shape in zip(out, ((p,), (na, 3), (nb, 3))):
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
+        return w, wf_ptr, tuple(out)
+
+    def native_gradient(self, cloud_a, cloud_b, anchors, threshold_distance: float, pair_weights=None, wf_index=None, *, tile_pairs=0,
+                        out=None):
+        """`(scores, grad_a[Na, 3], grad_b[Nb, 3])` with grad = sum_p v_p dS_p/dx (LoCoHD.native_gradient_from_primitives) in ONE native
+        call (lchd_gradient_primitives_dev): the sensitivity lists are reduced on the device, tile by tile, into exact fixed-point
+        accumulators and never reach torch.  Coordinates are the clouds' own.  anchors: torch int64 CUDA tensor [P][2]; pair_weights: v, a
+        tensor [P] (default: ones); wf_index: torch int32 CUDA tensor [P] or None; tile_pairs: pairs per pass, 0 = planned from the free
+        device memory; out: three float64 CUDA tensors [P], [Na][3], [Nb][3], filled and returned.  The bits of the result are a
+        function of the inputs alone: the same for every tile size, mode and run.  ValueError if a contribution is not finite or reaches
+        2^63 (the scores in `out` are then valid)."""
+        torch = self.torch
+        assert anchors.is_cuda and anchors.dtype == torch.int64 and anchors.is_contiguous()
+        if int(tile_pairs) < 0:
+            raise ValueError(f"tile_pairs = {int(tile_pairs)} is negative (0: planned from the free device memory)")
+        p = anchors.shape[0]
+        w, wf_ptr, out = self._native_gradient_buffers(cloud_a, cloud_b, p, pair_weights, wf_index, out)
+        w_ptr = None if w is None else C.c_void_p(w.data_ptr())  # (`w` lives until the call, which returns with its outputs complete, is over)
+        N.check(N.lib().lchd_gradient_primitives_dev(self._ctx, cloud_a, cloud_b, C.c_void_p(anchors.data_ptr()), wf_ptr, p,
+                                                     float(threshold_distance), w_ptr, int(tile_pairs), *[C.c_void_p(t.data_ptr()) for t in out]))
+        return out
+
+    def native_gradient_coords(self, cloud_a, cloud_b, pair_weights=None, wf_index=None, *, out=None):
+        """`native_gradient` for the dense rows of two uploaded structures of equal size (LoCoHD.native_gradient_from_coords): row r is
+        anchored at atom r itself; pair_weights / wf_index: [n] or None (lchd_gradient_coords_dev)."""
+        n = int(N.lib().lchd_cloud_size(cloud_a))
+        w, wf_ptr, out = self._native_gradient_buffers(cloud_a, cloud_b, n, pair_weights, wf_index, out)
+        w_ptr = None if w is None else C.c_void_p(w.data_ptr())
+        N.check(N.lib().lchd_gradient_coords_dev(self._ctx, cloud_a, cloud_b, wf_ptr, w_ptr, *[C.c_void_p(t.data_ptr()) for t in out]))
+        return out
+
     def sensitivity_coords(self, cloud_a, cloud_b, out=None, wf_index=None, *, width=None):
         """Neighbour sensitivities of the dense row pairs of two uploaded structures of equal size (LoCoHD.sensitivity_from_coords; no
         batches, no image clouds).  wf_index: torch int32 CUDA tensor [n] or None.  Returns a `Sensitivity` of torch CUDA tensors as
