@@ -625,6 +625,9 @@ int lchd_sensitivity_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *
  *                                     27 candidates w = v + ((i a + j b) + k c), i outermost and k innermost: the chosen w is the FIRST
  *                                     candidate in that order with the smallest (wx wx + wy wy) + wz wz (an update on strict < only)
  *                  A negation is exact, so sqrt((dx dx + dy dy) + dz dz) of disp equals dist[r][k] bit for bit, on every side kind.
+ *                  disp = -w also means that a zero component is -0.0 where w is +0.0: the row's own atom (d = +0.0) has disp
+ *                  (-0.0, -0.0, -0.0), equal in value and not in bits to x[member] - x[r] = +0.0.  No gradient term is built from a
+ *                  slot at distance 0.
  *                  Between two images at exactly the same distance (an atom half a cell away) the rule above decides; slot 0 is
  *                  computed like every other slot (the row atom itself: 0).
  * dS_r/dx(atom idx[r][k]) += g disp / dist and dS_r/dx(atom r) -= the same, for slots beyond 0 with dist > 0: the exact gradient of
@@ -701,6 +704,69 @@ int lchd_gradient_coords_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const 
 int lchd_gradient_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
                          int64_t len_seq_b, const double *xyz_a, const double *xyz_b, int64_t n, const int32_t *wf_index,
                          const double *pair_weights, double *scores, double *grad_a, double *grad_b);
+
+/* ---- ... under periodic boundaries, and the strain derivative (additive) -----------------------------------
+ * The same reduction on the lists of the periodic sensitivity calls, which carry every member's displacement disp[p][k] from its anchor
+ * (an image cloud's member: to the image the pass saw; a minimum-image row: to the nearest image; an open side: x[m] - x[a]).  Per side,
+ * with use, coef and the accumulators as above:
+ *
+ *     use   = k >= 1  &&  idx[p][k] >= 0  &&  dist[p][k] > 0  &&  isfinite(g[p][k])
+ *     coef  = (v_p * g[p][k]) / dist[p][k]
+ *     step_c = coef * disp[p][k][c]                                             (c = 0, 1, 2)
+ *     grad[m][c] += step_c ;  grad[a][c] += -step_c                             m = idx[p][k] (a SOURCE atom), a = the anchor / the row's atom
+ *     W[i][j]   += step_i * disp[p][k][j]      for i <= j only;  W[j][i] is a copy of W[i][j]
+ *
+ * every product one IEEE float64 operation, no contraction; grad has one row per source atom (lchd_cloud_home_size), so the terms of an
+ * atom that enters an environment through two images, or as its own anchor's image, all meet in its row.  No coordinate is read.
+ * W (strain_a / strain_b, double[9] row-major, one per side) is the STRAIN DERIVATIVE of L = sum_p v_p S_p: for x -> x (I + eps) applied
+ * to a side's coordinates (rows) and its box or cell together, dL/d eps[i][j] = W[i][j].  It is symmetric by construction -- six exact
+ * sums, each rounded once, the lower triangle copied -- and trace W = sum v g d.  It needs no image code, only disp, so it is defined for
+ * an open side too.  From it, with h the cell (rows are the lattice vectors; a box is diag(Lx, Ly, Lz)):
+ *     dL/dh at fixed FRACTIONAL coordinates  = inv(h)^T W                      (host arithmetic: loco_hd_amd.cell_gradient)
+ *     dL/dh at fixed CARTESIAN coordinates   = inv(h)^T (W - sum_atoms x_atom^T (x) grad_atom)
+ * The caveats of the sensitivity calls carry over: the thresholded form ignores members that enter or leave at the threshold, and every
+ * form is one-sided at ties (and where a minimum-image member sits exactly half a cell away).
+ * The six sums of a side are accumulators like any other (LCHD_GRAD_LIMBS limbs each, next to the per-atom ones), but every slot of a
+ * call adds to them: k_strain_accumulate keeps them as integer partial sums in registers across a bounded grid and adds each wavefront's
+ * totals once.  Bits: a function of the inputs alone, as the gradients'.
+ *   strain_a/_b   both given or both NULL (one alone: LCHD_EVALUE); NULL: the strain kernel is not launched.  With a batch cloud on
+ *                 either side a strain request is LCHD_EUNSUPPORTED (one tensor for many boxes has no meaning); gradients work as
+ *                 lchd_sensitivity_images_dev takes batches.
+ *   slot rule     with strain requested, a call whose slots per side (sum over tiles of tile_pairs x width) reach 2^31 is
+ *                 LCHD_EUNSUPPORTED before anything of the offending tile is launched -- the dense form included (n >= 46341, beyond
+ *                 the row limit today); without strain the rules above hold.
+ * lchd_gradient_images_dev: lchd_gradient_primitives_dev on clouds of which any may be an image cloud, tiles from
+ * lchd_sensitivity_images_dev (88 width + 16 + 8 ceil(width / 4) bytes per pair).  lchd_gradient_coords_periodic_dev: lchd_gradient_coords_dev
+ * on minimum-image rows, cell_a / cell_b HOST [9] or NULL (an open side) as lchd_sensitivity_coords_periodic_dev takes them; with both
+ * NULL the gradients equal lchd_gradient_coords_dev's bit for bit.  Errors of the periodic sensitivity calls pass through unchanged; the
+ * out-of-range failure returns behind valid scores and leaves clean accumulators.
+ * lchd_gradient_plan_periodic: lchd_gradient_plan for the rows of `resolve` (LCHD_GRAD_PLAIN: 40 width + 16 bytes per pair; _MIN_IMAGE:
+ * 88 width + 16; _IMAGES: 8 ceil(width / 4) more), after the slot rule: n_pairs x width >= 2^31 is LCHD_EUNSUPPORTED; a resolve outside 0 .. 2: LCHD_EVALUE.
+ * The plan assumes a strain request: a dense call WITHOUT strain is not bound by the slot rule, so the plan refuses LCHD_GRAD_MIN_IMAGE
+ * shapes with n in 46341 .. 65535 that such a call takes (it is one tile and needs no plan).
+ * lchd_gradient_strain_waves: the wavefronts of the strain kernel's largest grid (tests size their pair lists by it). */
+#define LCHD_GRAD_PLAIN 0
+#define LCHD_GRAD_IMAGES 1
+#define LCHD_GRAD_MIN_IMAGE 2
+int lchd_gradient_plan_periodic(int64_t n_pairs, int32_t width, int32_t resolve, int64_t budget_bytes, int64_t *tile_pairs_out);
+int64_t lchd_gradient_strain_waves(void);
+int lchd_gradient_images_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors, const int32_t *d_wf_index,
+                             int64_t n_pairs, double threshold_distance, const double *d_pair_weights, int64_t tile_pairs,
+                             double *d_scores, double *d_grad_a, double *d_grad_b, double *d_strain_a, double *d_strain_b);
+/* The same from host arrays, boxes and cells as lchd_sensitivity_primitives_periodic takes them; outputs HOST. */
+int lchd_gradient_primitives_periodic(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a,
+                                      const int32_t *tag_a, int64_t n_a, const double *xyz_b, const int32_t *cat_b, const int32_t *tag_b,
+                                      int64_t n_b, const int64_t *anchors, const int32_t *wf_index, int64_t n_pairs,
+                                      double threshold_distance, const double *box_a, const double *cell_a, const double *box_b,
+                                      const double *cell_b, const double *pair_weights, int64_t tile_pairs, double *scores,
+                                      double *grad_a, double *grad_b, double *strain_a, double *strain_b);
+int lchd_gradient_coords_periodic_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, const double *cell_a,
+                                      const double *cell_b, const double *d_pair_weights, double *d_scores, double *d_grad_a,
+                                      double *d_grad_b, double *d_strain_a, double *d_strain_b);
+int lchd_gradient_coords_periodic(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                                  int64_t len_seq_b, const double *xyz_a, const double *xyz_b, int64_t n, const int32_t *wf_index,
+                                  const double *cell_a, const double *cell_b, const double *pair_weights, double *scores,
+                                  double *grad_a, double *grad_b, double *strain_a, double *strain_b);
 
 /* ---- cross-scoring (additive, not in the reference) ------------------------------------------------------
  * Every anchor of one list against every anchor of another: which environments of B look like this environment of A.

@@ -192,6 +192,14 @@ _PROTOS = {
                                            _DP, _DP, _DP]),
     "lchd_gradient_coords_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lchd_gradient_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _IP, _DP, _DP, _DP, _DP]),
+    "lchd_gradient_plan_periodic": (C.c_int, [_i64, _i32, _i32, _i64, _LP]),
+    "lchd_gradient_strain_waves": (C.c_int64, []),
+    "lchd_gradient_images_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _i64, _f64, _VP, _i64, _VP, _VP, _VP, _VP, _VP]),
+    "lchd_gradient_primitives_periodic": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64,
+                                                    _DP, _DP, _DP, _DP, _DP, _i64, _DP, _DP, _DP, _DP, _DP]),
+    "lchd_gradient_coords_periodic_dev": (C.c_int, [_VP, _VP, _VP, _VP, _DP, _DP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lchd_gradient_coords_periodic": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _IP, _DP, _DP, _DP, _DP, _DP,
+                                                _DP, _DP, _DP]),
     "lchd_cross_plan": (C.c_int, [_i64, _i64, _i64, _LP]),
     "lchd_cross_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _i64, _VP, _i64, _i32, _f64, _i64, _VP]),
     "lchd_nearest_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _i64, _VP, _i64, _i32, _f64, _i64, _i32, _VP, _VP]),

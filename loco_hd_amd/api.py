@@ -32,6 +32,9 @@ PeriodicSensitivity = namedtuple("PeriodicSensitivity", "scores count_a idx_a im
 # Sensitivity of dense minimum-image rows plus, per side, disp[n, K, 3], the displacement from row atom r to the nearest image of member
 # idx[r, k] (dist = |disp| bit for bit); every atom occurs once, so there are no image codes
 MinImageSensitivity = namedtuple("MinImageSensitivity", "scores count_a idx_a dist_a g_a disp_a count_b idx_b dist_b g_b disp_b")
+# what the native periodic gradient calls return with strain=True (DeviceSession: the same fields as torch tensors): strain_a / strain_b are
+# the (3, 3) strain derivatives of the weighted score sum, one per side (include/loco_hd_hip.h, "the strain derivative")
+NativeGradient = namedtuple("NativeGradient", "scores grad_a grad_b strain_a strain_b")
 # what LoCoHD.nearest_from_primitives returns (DeviceSession.nearest: the same fields as torch tensors)
 Nearest = namedtuple("Nearest", "scores cols")
 
@@ -134,6 +137,22 @@ def cell_reduce(cell) -> Tuple[np.ndarray, np.ndarray]:
     reduced, inverse = np.empty((3, 3)), np.empty((3, 3))
     N.check(N.lib().lchd_cell_reduce(N.dp(c), N.dp(reduced), N.dp(inverse)))
     return reduced, inverse
+
+
+def cell_gradient(strain, cell) -> np.ndarray:
+    """dL/dh at fixed fractional coordinates from a strain derivative W (`NativeGradient.strain_a` / `strain_b`): inv(h).T @ W for the
+    cell h (3 x 3, rows = the lattice vectors); a box (Lx, Ly, Lz) is taken as diag(Lx, Ly, Lz), the derivative with respect to Lx is
+    then element [0, 0].  Host arithmetic in float64; ValueError for another shape or a singular cell."""
+    w, h = _f64(strain), _f64(cell)
+    if w.shape != (3, 3):
+        raise ValueError(f"strain must be a 3 x 3 matrix, got an array of shape {w.shape}")
+    if h.shape == (3,):
+        h = np.diag(h)
+    if h.shape != (3, 3):
+        raise ValueError(f"cell must be a 3 x 3 matrix of lattice vectors (rows a, b, c) or three edge lengths, got an array of shape {h.shape}")
+    if not np.isfinite(h).all() or np.linalg.matrix_rank(h) < 3:
+        raise ValueError("cell is singular or not finite")
+    return np.linalg.solve(h.T, w)  # inv(h).T @ w
 
 
 def cell_from_lengths_angles(a: float, b: float, c: float, alpha: float, beta: float, gamma: float) -> np.ndarray:
@@ -1277,6 +1296,83 @@ class LoCoHD:
             N.check(N.lib().lchd_gradient_coords(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(xa), N.dp(xb), n,
                                                  N.ip(idx), N.dp(v), N.dp(scores), N.dp(ga), N.dp(gb)))
         return scores, ga, gb
+
+    # ---- ... under periodic boundaries, with the strain derivative (additive) ---------------------------------
+    # include/loco_hd_hip.h, "under periodic boundaries, and the strain derivative": the lists of the periodic sensitivity calls reduced on
+    # the device from their displacements; W = sum step (x) disp per side in six more exact accumulators.
+    def native_gradient_from_primitives_periodic(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                                                 threshold_distance: float, pair_weights=None, *, tile_pairs: int = 0, box_a=None,
+                                                 box_b=None, cell_a=None, cell_b=None, strain: bool = False):
+        """Additive: `native_gradient_from_primitives` for structures in periodic boxes (Lx, Ly, Lz) or triclinic cells (3 x 3, lattice
+        vectors as rows), given per side as `from_primitives` takes them; a side with neither is open.  `(scores, grad_a[Na, 3],
+        grad_b[Nb, 3])` as `gradient_from_primitives_periodic` defines them -- every term v g disp / d in float64, the terms of a source
+        atom summed exactly and rounded once (lchd_gradient_primitives_periodic).  strain=True: a `NativeGradient(scores, grad_a, grad_b,
+        strain_a, strain_b)` whose (3, 3) float64 strains W are the derivative of sum_p v_p S_p with respect to a strain x -> x (I + eps)
+        of the side's coordinates and cell together, symmetric, exact sums rounded once (`cell_gradient` turns one into dL/dcell).  The
+        bits are the same for every `tile_pairs`, mode and run.  ValueError if a term is not finite or reaches 2^63."""
+        if int(tile_pairs) < 0:
+            raise ValueError(f"tile_pairs = {int(tile_pairs)} is negative (0: planned from the free device memory)")
+        for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+            if box is not None and cell is not None:
+                raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
+        if self._devices is not None:
+            raise NotImplementedError("a native gradient call applies to one device (a device group has no gradient call): drop devices=[...]")
+        thr = float(threshold_distance)
+        ba = None if box_a is None else periodic_boxes(box_a, 1, thr, "box_a")
+        bb = None if box_b is None else periodic_boxes(box_b, 1, thr, "box_b")
+        ca = None if cell_a is None else periodic_cells(cell_a, 1, thr, "cell_a")
+        cb = None if cell_b is None else periodic_cells(cell_b, 1, thr, "cell_b")
+        pairs, idx = self._anchor_arrays(anchor_pairs)
+        anchors = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        n = len(anchors)
+        v = None
+        if pair_weights is not None:
+            v = np.ascontiguousarray(_f64(pair_weights).reshape(-1))
+            if len(v) != n:
+                raise ValueError(f"pair_weights has {len(v)} entries for {n} anchor pairs")
+        pa, pb, interner = self._packed_lists(prim_a, prim_b)
+        cfg, keep = self._config(interner)
+        xa, xb = _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3)
+        scores, ga, gb = np.empty(n), np.zeros((len(xa), 3)), np.zeros((len(xb), 3))
+        wa, wb = (np.zeros((3, 3)), np.zeros((3, 3))) if strain else (None, None)
+        N.check(N.lib().lchd_gradient_primitives_periodic(self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa), N.dp(xb),
+                                                          N.ip(pb.cat), N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx), n, thr, N.dp(ba),
+                                                          N.dp(ca), N.dp(bb), N.dp(cb), N.dp(v), int(tile_pairs), N.dp(scores), N.dp(ga),
+                                                          N.dp(gb), N.dp(wa), N.dp(wb)))
+        return NativeGradient(scores, ga, gb, wa, wb) if strain else (scores, ga, gb)
+
+    def native_gradient_from_coords_periodic(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None,
+                                             pair_weights=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None, strain: bool = False):
+        """Additive: `native_gradient_from_coords` on the minimum-image rows `from_coords(..., box_a= / cell_a= ...)` scores; boxes and
+        cells per side as `from_coords` takes them, a side with neither is open (with none at all: the bits of
+        `native_gradient_from_coords`).  `(scores, grad_a[n, 3], grad_b[n, 3])`, or with strain=True a `NativeGradient` as
+        `native_gradient_from_primitives_periodic` returns it (lchd_gradient_coords_periodic)."""
+        if self._devices is not None:
+            raise NotImplementedError("a native gradient call applies to one device (a device group has no gradient call): drop devices=[...]")
+        cells = self._dense_periodic_cells(box_a, box_b, cell_a, cell_b)
+        xa, xb = self._coords(coords_a), self._coords(coords_b)
+        if len(xa) != len(xb):
+            raise ValueError(f"Expected matrices with the same length, got lengths {len(xa)} and {len(xb)}!")
+        n = len(xa)
+        v = None
+        if pair_weights is not None:
+            v = np.ascontiguousarray(_f64(pair_weights).reshape(-1))
+            if len(v) != n:
+                raise ValueError(f"pair_weights has {len(v)} entries for {n} rows")
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], n)
+        if len(self._weights) > 64:
+            raise NotImplementedError(f"a sensitivity call takes at most 64 categories (got {len(self._weights)})")
+        if n > 65535:
+            raise NotImplementedError(f"a sensitivity call takes dense rows of at most 65535 points (got {n} / {n})")
+        ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
+        cfg, keep = self._config()
+        scores, ga, gb = np.empty(n), np.zeros((n, 3)), np.zeros((n, 3))
+        wa, wb = (np.zeros((3, 3)), np.zeros((3, 3))) if strain else (None, None)
+        if n:
+            N.check(N.lib().lchd_gradient_coords_periodic(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(xa), N.dp(xb),
+                                                          n, N.ip(idx), N.dp(cells[0]), N.dp(cells[1]), N.dp(v), N.dp(scores), N.dp(ga),
+                                                          N.dp(gb), N.dp(wa), N.dp(wb)))
+        return NativeGradient(scores, ga, gb, wa, wb) if strain else (scores, ga, gb)
 
     # ---- ... of dense rows in periodic cells (additive) ------------------------------------------------------
     # The minimum-image rows of from_coords(box_a= / cell_a= ...) (include/loco_hd_hip.h, lchd_sensitivity_coords_periodic).  A row

@@ -23,6 +23,9 @@ Forward is DeviceSession.sensitivity_coords_periodic, backward is side A of Devi
 
 The movable structure in a periodic box or cell: forward is DeviceSession.sensitivity_images on its image cloud, backward is side A of
 DeviceSession.gradient_images (side_gradient_images).
+
+The two periodic forms take `native=True` as well: forward and backward are then one DeviceSession.native_gradient_images /
+native_gradient_coords_periodic call each, backward with grad_output as the pair weights.  Boxes and cells stay non-differentiable.
 """
 from __future__ import annotations
 
@@ -128,6 +131,59 @@ class _LoCoHDScoresPeriodic(torch.autograd.Function):
         return grad_a.to(ctx.dtype), None, None, None, None, None, None, None, None
 
 
+def _native_periodic_call(ctx, x, weights):
+    """The movable structure uploaded (thresholded: with its image cloud), one native periodic gradient call, both dropped again."""
+    session = ctx.session
+    mine = []
+    try:
+        mine.append(session.upload(x.cpu().numpy(), ctx.cat, ctx.tag))
+        if ctx.anchors is None:
+            return session.native_gradient_coords_periodic(mine[0], ctx.cloud_b, pair_weights=weights, wf_index=ctx.wf_index, box_a=ctx.box,
+                                                           cell_a=ctx.cell, box_b=ctx.ref_box, cell_b=ctx.ref_cell)
+        mine.append(session.periodic_images(mine[0], ctx.box, ctx.thr, cell=ctx.cell))
+        return session.native_gradient_images(mine[1], ctx.cloud_b, ctx.anchors, ctx.thr, pair_weights=weights)
+    finally:
+        for cl in reversed(mine):
+            session._clouds.remove(cl)
+            N.lib().lchd_cloud_destroy(session._ctx, cl)
+
+
+class _LoCoHDScoresPeriodicNative(torch.autograd.Function):
+    """locohd_scores_periodic(native=True): as _LoCoHDScoresNative, on DeviceSession.native_gradient_images."""
+
+    @staticmethod
+    def forward(ctx, xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, threshold_distance, box, cell):
+        x = xyz_a.detach()
+        ctx.session, ctx.cloud_b, ctx.anchors, ctx.thr, ctx.box, ctx.cell = session, cloud_b_ref, anchors, threshold_distance, box, cell
+        ctx.cat = np.asarray(cat_a, dtype=np.int32)
+        ctx.tag = None if tag_a is None else np.asarray(tag_a, dtype=np.int32)
+        ctx.save_for_backward(x)
+        return _native_periodic_call(ctx, x, None)[0]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (x,) = ctx.saved_tensors
+        return (_native_periodic_call(ctx, x, grad_output)[1].to(x.dtype),) + (None,) * 8  # side A alone moves
+
+
+class _LoCoHDScoresDensePeriodicNative(torch.autograd.Function):
+    """locohd_scores_dense_periodic(native=True): as _LoCoHDScoresDenseNative, on DeviceSession.native_gradient_coords_periodic."""
+
+    @staticmethod
+    def forward(ctx, xyz_a, session, cloud_b_ref, cat_a, wf_index, box, cell, ref_box, ref_cell):
+        x = xyz_a.detach()
+        ctx.session, ctx.cloud_b, ctx.anchors, ctx.wf_index = session, cloud_b_ref, None, wf_index
+        ctx.box, ctx.cell, ctx.ref_box, ctx.ref_cell = box, cell, ref_box, ref_cell
+        ctx.cat, ctx.tag = np.asarray(cat_a, dtype=np.int32), None
+        ctx.save_for_backward(x)
+        return _native_periodic_call(ctx, x, None)[0]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (x,) = ctx.saved_tensors
+        return (_native_periodic_call(ctx, x, grad_output)[1].to(x.dtype),) + (None,) * 8
+
+
 class _LoCoHDScoresDense(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz_a, session, cloud_b_ref, cat_a, wf_index):
@@ -174,11 +230,15 @@ class _LoCoHDScoresDensePeriodic(torch.autograd.Function):
         return grad_a.to(ctx.dtype), None, None, None, None, None, None, None, None
 
 
-def locohd_scores_dense_periodic(session, cloud_b_ref, xyz_a, cat_a, wf_index=None, *, box=None, cell=None, ref_box=None, ref_cell=None):
+def locohd_scores_dense_periodic(session, cloud_b_ref, xyz_a, cat_a, wf_index=None, *, box=None, cell=None, ref_box=None, ref_cell=None,
+                                 native=False):
     """`locohd_scores_dense` under minimum-image periodic boundaries (DeviceSession.sensitivity_coords_periodic): `box` / `cell` is the
     periodic box (Lx, Ly, Lz) or cell (3 x 3) of the movable structure, `ref_box` / `ref_cell` that of the reference; a structure with
     neither is open.  Backward is side A of DeviceSession.gradient_coords_periodic with grad_output as the row weights; xyz_a need not be
-    wrapped: the gradient is the one with respect to xyz_a as given."""
+    wrapped: the gradient is the one with respect to xyz_a as given.  native=True: forward and backward are one
+    DeviceSession.native_gradient_coords_periodic call each (its bits); boxes and cells are not differentiable either way."""
+    if native:
+        return _LoCoHDScoresDensePeriodicNative.apply(xyz_a, session, cloud_b_ref, cat_a, wf_index, box, cell, ref_box, ref_cell)
     return _LoCoHDScoresDensePeriodic.apply(xyz_a, session, cloud_b_ref, cat_a, wf_index, box, cell, ref_box, ref_cell)
 
 
@@ -205,9 +265,12 @@ def locohd_scores(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, threshold_
     return _LoCoHDScores.apply(xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, float(threshold_distance))
 
 
-def locohd_scores_periodic(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, threshold_distance, *, box=None, cell=None):
+def locohd_scores_periodic(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, threshold_distance, *, box=None, cell=None, native=False):
     """`locohd_scores` for a movable structure in a periodic box (Lx, Ly, Lz) or triclinic cell (3 x 3, lattice vectors as rows): the
     structure is uploaded, its image cloud is built with reach = threshold_distance, and both leave the session again.  `cloud_b_ref` is
     any cloud of `session`, an image cloud (DeviceSession.periodic_images) included.  xyz_a need not be wrapped: a wrap is a translation
-    by a lattice vector, so the gradient is the one with respect to xyz_a as given."""
+    by a lattice vector, so the gradient is the one with respect to xyz_a as given.  native=True: forward and backward are one
+    DeviceSession.native_gradient_images call each (its bits); the box or cell is not differentiable either way."""
+    if native:
+        return _LoCoHDScoresPeriodicNative.apply(xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, float(threshold_distance), box, cell)
     return _LoCoHDScoresPeriodic.apply(xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, float(threshold_distance), box, cell)

@@ -23,6 +23,7 @@
 #include "lchd_device.h"
 #include "lchd_math.h"
 #include "lchd_radial_bins.h"
+#include "lchd_strain_sum.h"
 
 using namespace lchd;
 
@@ -4842,8 +4843,11 @@ extern "C" int lchd_nearest_primitives(lchd_ctx* c, const lchd_config* cfg, cons
 // the caller's array -- and k_grad_accumulate (lchd_gradient.hip) adds them into the exact accumulators of lchd_exact_sum.h.  A tile
 // is added only after its pass has succeeded: a pass that reports too small a width is repeated at lchd_sensitivity_needed_width first.
 // The dense form is one tile of lchd_sensitivity_coords_dev with the row's atom as the anchor.  k_grad_finish rounds once at the end.
-static int64_t grad_pair_bytes(int32_t width) { return 8 * (int64_t)sens_row(width, kSensPlain); }  // 40 width + 16
+static int64_t grad_pair_bytes(int32_t width, int resolve = kSensPlain) { return 8 * (int64_t)sens_row(width, resolve); }  // plain: 40 width + 16
 constexpr int64_t kGradMaxAdds = (int64_t)1 << 31;  // additions a limb takes without carry propagation (lchd_exact_sum.h)
+static int64_t grad_plan_tile(int64_t n_pairs, int32_t width, int resolve, int64_t budget_bytes) {
+    return std::max<int64_t>(1, std::min(budget_bytes / grad_pair_bytes(width, resolve), n_pairs));
+}
 
 extern "C" int lchd_gradient_plan(int64_t n_pairs, int32_t width, int64_t budget_bytes, int64_t* tile_pairs_out) {
     if (!tile_pairs_out) return fail(LCHD_EVALUE, "null output pointer");
@@ -4851,10 +4855,24 @@ extern "C" int lchd_gradient_plan(int64_t n_pairs, int32_t width, int64_t budget
     if (n_pairs < 1 || width < 1 || width > kRadialMaxPoints || budget_bytes < 0)
         return fail(LCHD_EVALUE, "a gradient plan takes n_pairs >= 1, a width in 1 .. %d and a budget >= 0 (got %lld, %d, %lld)", kRadialMaxPoints,
                     (long long)n_pairs, width, (long long)budget_bytes);
-    const int64_t fit = budget_bytes / grad_pair_bytes(width);
-    *tile_pairs_out = std::max<int64_t>(1, std::min(fit, n_pairs));
+    *tile_pairs_out = grad_plan_tile(n_pairs, width, kSensPlain, budget_bytes);
     return LCHD_OK;
 }
+// ... for the wider rows of the periodic forms (resolve: LCHD_GRAD_PLAIN / _IMAGES / _MIN_IMAGE), with the call's slot rule in front: what
+// a periodic call of these pairs at this width would refuse is refused here, with the same words.
+extern "C" int lchd_gradient_plan_periodic(int64_t n_pairs, int32_t width, int32_t resolve, int64_t budget_bytes, int64_t* tile_pairs_out) {
+    if (!tile_pairs_out) return fail(LCHD_EVALUE, "null output pointer");
+    *tile_pairs_out = 0;
+    if (n_pairs < 1 || width < 1 || width > kRadialMaxPoints || budget_bytes < 0 || resolve < kSensPlain || resolve > kSensMinImage)
+        return fail(LCHD_EVALUE, "a gradient plan takes n_pairs >= 1, a width in 1 .. %d, a resolve mode in 0 .. 2 and a budget >= 0 (got %lld, %d, %d, %lld)",
+                    kRadialMaxPoints, (long long)n_pairs, width, resolve, (long long)budget_bytes);
+    if (n_pairs >= (kGradMaxAdds + width - 1) / width)
+        return fail(LCHD_EUNSUPPORTED, "%lld pairs with rows of %d slots exceed the 2^31 additions an exact accumulator takes: split the list",
+                    (long long)n_pairs, width);
+    *tile_pairs_out = grad_plan_tile(n_pairs, width, resolve, budget_bytes);
+    return LCHD_OK;
+}
+extern "C" int64_t lchd_gradient_strain_waves(void) { return 4 * (int64_t)kStrainMaxBlocks; }
 
 struct GradRequest {
     lchd_cloud *a, *b;
@@ -4865,28 +4883,42 @@ struct GradRequest {
     const double* weights;    // DEVICE [n_pairs] or null
     int64_t tile_pairs;       // 0: lchd_gradient_plan
     double *scores, *grad_a, *grad_b;  // DEVICE
+    // the periodic forms: which sensitivity call fills a tile.  kSensPlain: the two open calls, coordinates read by the accumulation;
+    // kSensImages: lchd_sensitivity_images_dev (thresholded; any cloud may be an image cloud, gradients per source atom);
+    // kSensMinImage: lchd_sensitivity_coords_periodic_dev (dense) with `cell`.  The last two accumulate from the lists' disp.
+    int resolve = kSensPlain;
+    const double* cell[2] = {nullptr, nullptr};   // HOST [9] or null: an open side (kSensMinImage)
+    double* strain[2] = {nullptr, nullptr};       // DEVICE [9] each, both or neither (a resolving form)
 };
 static int grad_core(lchd_ctx* c, const GradRequest& R) {
     if (!c || !R.a || !R.b) return fail(LCHD_EVALUE, "null argument");
     const bool dense = R.anchors == nullptr;
+    const int resolve = R.resolve;
     if (R.tile_pairs < 0) return fail(LCHD_EVALUE, "tile_pairs = %lld is negative (0: planned from the free device memory)", (long long)R.tile_pairs);
     if (R.n_pairs < 0) return fail(LCHD_EVALUE, "negative pair count");
+    if (!R.strain[0] != !R.strain[1]) return fail(LCHD_EVALUE, "one strain pointer is null and the other is not: a call writes both tensors or neither");
+    const bool strain = R.strain[0] != nullptr;
     if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
     if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
-    if (R.a->images || R.b->images) return fail(LCHD_EUNSUPPORTED, "a native gradient call takes the structures themselves, not periodic image clouds");
+    if (resolve == kSensPlain && (R.a->images || R.b->images))
+        return fail(LCHD_EUNSUPPORTED, "a native gradient call takes the structures themselves, not periodic image clouds");
     if (dense && R.a->n != R.b->n)
         return fail(LCHD_EVALUE, "Expected matrices with the same length, got lengths %lld and %lld!", (long long)R.a->n, (long long)R.b->n);
     if (dense && (R.a->sid || R.b->sid)) return fail(LCHD_EVALUE, "from_coords takes single structures, not batches");
-    const int64_t n_at[2] = {R.a->n, R.b->n};
+    if (strain && (R.a->sid || R.b->sid))
+        return fail(LCHD_EUNSUPPORTED, "a strain derivative belongs to one box or cell: a batch of structures has many (ask for gradients alone, or score one structure per call)");
+    // (an image cloud's lists name source atoms: one gradient row per source atom)
+    const int64_t n_at[2] = {resolve == kSensImages ? lchd_cloud_home_size(R.a) : R.a->n, resolve == kSensImages ? lchd_cloud_home_size(R.b) : R.b->n};
     if ((n_at[0] > 0 && !R.grad_a) || (n_at[1] > 0 && !R.grad_b) || (R.n_pairs > 0 && !R.scores)) return fail(LCHD_EVALUE, "null output pointer");
     if (dense && R.n_pairs > kRadialMaxPoints)
         return fail(LCHD_EUNSUPPORTED, "a sensitivity call takes dense rows of at most %d points (got %lld / %lld)", kRadialMaxPoints, (long long)n_at[0],
                     (long long)n_at[1]);
     CTX_GUARD(c);
     hipStream_t s = c->stream;
-    // the accumulators: [status word, 256 bytes] | side A [n_a][3][limbs] | side B; zero between calls (k_grad_finish leaves them so)
+    // the accumulators: [status word, 256 bytes] | side A [n_a][3][limbs] | side B | strain [2][6][limbs]; zero between calls (the finish
+    // kernels leave them so)
     const size_t side_bytes[2] = {(size_t)n_at[0] * 3 * LCHD_GRAD_LIMBS * 8, (size_t)n_at[1] * 3 * LCHD_GRAD_LIMBS * 8};
-    const size_t acc_bytes = 256 + side_bytes[0] + side_bytes[1];
+    const size_t acc_bytes = 256 + side_bytes[0] + side_bytes[1] + 2 * LCHD_STRAIN_LIMBS * 8;
     const bool grown = acc_bytes > c->grad_acc_cap;
     if (grown) HIP_TRY(hipStreamSynchronize(s));
     if (int rc = grow_block(c->d_grad_acc, c->grad_acc_cap, acc_bytes)) return rc;
@@ -4894,6 +4926,7 @@ static int grad_core(lchd_ctx* c, const GradRequest& R) {
     c->grad_acc_dirty = true;
     uint32_t* const d_flag = reinterpret_cast<uint32_t*>(c->d_grad_acc);
     int64_t* const acc[2] = {reinterpret_cast<int64_t*>(c->d_grad_acc + 256), reinterpret_cast<int64_t*>(c->d_grad_acc + 256 + side_bytes[0])};
+    int64_t* const strain_acc = reinterpret_cast<int64_t*>(c->d_grad_acc + 256 + side_bytes[0] + side_bytes[1]);
 
     int32_t width = dense ? (int32_t)std::max<int64_t>(R.n_pairs, 1) : std::min(std::max(128, c->grad_width), kRadialMaxPoints);
     int64_t tile = dense ? R.n_pairs : std::min(R.tile_pairs, R.n_pairs);
@@ -4903,31 +4936,36 @@ static int grad_core(lchd_ctx* c, const GradRequest& R) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         budget = std::min<size_t>(free_b, (size_t)1 << 62) / 4;  // (the pass itself takes its stores and arena next to the lists)
-        if (int rc = lchd_gradient_plan(R.n_pairs, width, (int64_t)budget, &tile)) return rc;
+        tile = grad_plan_tile(R.n_pairs, width, resolve, (int64_t)budget);
     }
-    int64_t adds = 0;  // slots handed to k_grad_accumulate so far: what one atom's limbs can have received at the most
+    int64_t adds = 0;  // slots per side handed to the accumulation so far: what one accumulator's limbs can have received at the most
     for (int64_t p0 = 0; p0 < R.n_pairs;) {
         const int64_t tp = std::min(tile, R.n_pairs - p0);
-        if (!dense && adds + tp * (int64_t)width >= kGradMaxAdds)
+        // (a dense row adds to its atoms once per row, far below the limit; the strain sums take every slot of the call)
+        if ((!dense || strain) && adds + tp * (int64_t)width >= kGradMaxAdds)
             return fail(LCHD_EUNSUPPORTED, "%lld pairs with rows of %d slots exceed the 2^31 additions an exact accumulator takes: split the list",
                         (long long)R.n_pairs, width);
-        const size_t lists = (size_t)tp * (size_t)grad_pair_bytes(width);
+        const size_t lists = (size_t)tp * (size_t)grad_pair_bytes(width, resolve);
         if (lists > c->grad_cap) HIP_TRY(hipStreamSynchronize(s));  // (the block about to be freed may still be read)
         if (int rc = grow_block(c->d_grad, c->grad_cap, lists)) return rc;
-        SensitivityOut o = sens_carve(reinterpret_cast<double*>(c->d_grad), tp, width);
+        SensitivityOut o = sens_carve(reinterpret_cast<double*>(c->d_grad), tp, width, resolve);
         o.scores = R.scores + p0;
         const int32_t* wf = R.wf ? R.wf + p0 : nullptr;
-        const int rc = dense ? lchd_sensitivity_coords_dev(c, R.a, R.b, wf, width, o.scores, o.count_a, o.idx_a, o.dist_a, o.g_a, o.count_b, o.idx_b,
-                                                           o.dist_b, o.g_b)
-                             : lchd_sensitivity_primitives_dev(c, R.a, R.b, R.anchors + 2 * p0, wf, tp, R.thr, width, o.scores, o.count_a, o.idx_a,
-                                                               o.dist_a, o.g_a, o.count_b, o.idx_b, o.dist_b, o.g_b);
+        int rc;
+        if (resolve == kSensImages)
+            rc = lchd_sensitivity_images_dev(c, R.a, R.b, R.anchors + 2 * p0, wf, tp, R.thr, width, o.scores, o.count_a, o.idx_a, o.image_a, o.dist_a,
+                                             o.g_a, o.disp_a, o.count_b, o.idx_b, o.image_b, o.dist_b, o.g_b, o.disp_b);
+        else if (resolve == kSensMinImage)
+            rc = lchd_sensitivity_coords_periodic_dev(c, R.a, R.b, wf, R.cell[0], R.cell[1], width, o.scores, o.count_a, o.idx_a, o.dist_a, o.g_a,
+                                                      o.count_b, o.idx_b, o.dist_b, o.g_b, o.disp_a, o.disp_b);
+        else if (dense)
+            rc = lchd_sensitivity_coords_dev(c, R.a, R.b, wf, width, o.scores, o.count_a, o.idx_a, o.dist_a, o.g_a, o.count_b, o.idx_b, o.dist_b, o.g_b);
+        else
+            rc = lchd_sensitivity_primitives_dev(c, R.a, R.b, R.anchors + 2 * p0, wf, tp, R.thr, width, o.scores, o.count_a, o.idx_a, o.dist_a, o.g_a,
+                                                 o.count_b, o.idx_b, o.dist_b, o.g_b);
         if (rc == LCHD_EVALUE && !dense && c->sens_needed > width) {  // too narrow: nothing of this tile has been added; once more, wider
             width = (int32_t)c->sens_needed;
-            if (planned) {
-                int64_t fit = tile;
-                if (int rc2 = lchd_gradient_plan(R.n_pairs, width, (int64_t)budget, &fit)) return rc2;
-                tile = std::min(tile, fit);
-            }
+            if (planned) tile = std::min(tile, grad_plan_tile(R.n_pairs, width, resolve, (int64_t)budget));
             continue;
         }
         if (rc) return rc;
@@ -4936,7 +4974,7 @@ static int grad_core(lchd_ctx* c, const GradRequest& R) {
         for (int k = 0; k < 2; ++k) {
             GradSide& S = ga.s[k];
             S.idx = k ? o.idx_b : o.idx_a; S.dist = k ? o.dist_b : o.dist_a; S.g = k ? o.g_b : o.g_a;
-            S.disp = nullptr;
+            S.disp = k ? o.disp_b : o.disp_a;  // (null in the plain layout)
             S.x = cl[k]->x; S.y = cl[k]->y; S.z = cl[k]->z;
             S.n = n_at[k];
             S.acc = acc[k];
@@ -4947,12 +4985,15 @@ static int grad_core(lchd_ctx* c, const GradRequest& R) {
         ga.dense = dense ? 1 : 0;
         ga.flag = d_flag;
         if (!launch_grad_accumulate(s, ga)) return fail(LCHD_EDEVICE, "the gradient accumulation kernel rejected its launch configuration");
+        if (strain && !launch_strain_accumulate(s, ga, strain_acc))
+            return fail(LCHD_EDEVICE, "the strain accumulation kernel rejected its launch configuration");
         HIP_TRY(hipGetLastError());
         adds += tp * (int64_t)width;
         p0 += tp;
     }
     if (!dense) c->grad_width = width;
-    if (!launch_grad_finish(s, acc[0], n_at[0], R.grad_a) || !launch_grad_finish(s, acc[1], n_at[1], R.grad_b))
+    if (!launch_grad_finish(s, acc[0], n_at[0], R.grad_a) || !launch_grad_finish(s, acc[1], n_at[1], R.grad_b) ||
+        (strain && !launch_strain_finish(s, strain_acc, R.strain[0], R.strain[1])))
         return fail(LCHD_EDEVICE, "the gradient finish kernel rejected its launch configuration");
     HIP_TRY(hipGetLastError());
     uint32_t flag = 0;
@@ -4979,6 +5020,34 @@ extern "C" int lchd_gradient_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* 
     if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
     return grad_core(c, GradRequest{a, b, nullptr, d_wf_index, a->n, 0.0, d_pair_weights, 0, d_scores, d_grad_a, d_grad_b});
 }
+// ... under periodic boundaries: the same tile loop on the lists of lchd_sensitivity_images_dev / lchd_sensitivity_coords_periodic_dev,
+// accumulated from their displacements; with the strain tensors requested, k_strain_accumulate behind every tile's accumulation.
+extern "C" int lchd_gradient_images_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
+                                        int64_t n_pairs, double thr, const double* d_pair_weights, int64_t tile_pairs, double* d_scores,
+                                        double* d_grad_a, double* d_grad_b, double* d_strain_a, double* d_strain_b) {
+    CTX_LOCK(c);
+    if (tile_pairs < 0) return fail(LCHD_EVALUE, "tile_pairs = %lld is negative (0: planned from the free device memory)", (long long)tile_pairs);
+    if (!d_strain_a != !d_strain_b) return fail(LCHD_EVALUE, "one strain pointer is null and the other is not: a call writes both tensors or neither");
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (n_pairs > 0 && !d_anchors) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    static const int64_t no_pairs[2] = {0, 0};
+    GradRequest R{a, b, d_anchors ? d_anchors : no_pairs, d_wf_index, n_pairs, thr, d_pair_weights, tile_pairs, d_scores, d_grad_a, d_grad_b};
+    R.resolve = kSensImages;
+    R.strain[0] = d_strain_a; R.strain[1] = d_strain_b;
+    return grad_core(c, R);
+}
+extern "C" int lchd_gradient_coords_periodic_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
+                                                 const double* cell_b, const double* d_pair_weights, double* d_scores, double* d_grad_a,
+                                                 double* d_grad_b, double* d_strain_a, double* d_strain_b) {
+    CTX_LOCK(c);
+    if (!d_strain_a != !d_strain_b) return fail(LCHD_EVALUE, "one strain pointer is null and the other is not: a call writes both tensors or neither");
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    GradRequest R{a, b, nullptr, d_wf_index, a->n, 0.0, d_pair_weights, 0, d_scores, d_grad_a, d_grad_b};
+    R.resolve = kSensMinImage;
+    R.cell[0] = cell_a; R.cell[1] = cell_b;
+    R.strain[0] = d_strain_a; R.strain[1] = d_strain_b;
+    return grad_core(c, R);
+}
 
 // The host-array forms: both structures as temporary clouds; the list, the weights and the three outputs in one temporary device block.
 struct GradHostArrays {
@@ -4989,12 +5058,16 @@ struct GradHostArrays {
     double thr;
     int64_t tile_pairs;
     double *scores, *grad_a, *grad_b;
+    int resolve = kSensPlain;                    // as GradRequest
+    const double* cell[2] = {nullptr, nullptr};
+    double* strain[2] = {nullptr, nullptr};      // HOST [9] each, both or neither
 };
 static int grad_host(lchd_ctx* c, HostTemps& t, const GradHostArrays& H) {
     const size_t P = (size_t)H.n_pairs, na = (size_t)H.n_a, nb = (size_t)H.n_b;
     auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
     const size_t o_wf = up(H.anchors ? 16 * P : 0), o_w = up(o_wf + (H.wf ? 4 * P : 0)), o_sc = up(o_w + (H.weights ? 8 * P : 0)),
-                 o_ga = up(o_sc + 8 * P), o_gb = up(o_ga + 24 * na), total = o_gb + 24 * nb;
+                 o_ga = up(o_sc + 8 * P), o_gb = up(o_ga + 24 * na), o_st = up(o_gb + 24 * nb), total = o_st + 2 * 72;
+    if (!H.strain[0] != !H.strain[1]) return fail(LCHD_EVALUE, "one strain pointer is null and the other is not: a call writes both tensors or neither");
     if (hipMalloc(&t.d_blk, total ? total : 256) != hipSuccess) {
         (void)hipGetLastError();
         return fail(LCHD_EUNSUPPORTED, "no device memory for the %zu bytes of lists and outputs of this call", total);
@@ -5003,11 +5076,16 @@ static int grad_host(lchd_ctx* c, HostTemps& t, const GradHostArrays& H) {
     if (H.wf && P) HIP_TRY(hipMemcpy(t.d_blk + o_wf, H.wf, 4 * P, hipMemcpyHostToDevice));
     if (H.weights && P) HIP_TRY(hipMemcpy(t.d_blk + o_w, H.weights, 8 * P, hipMemcpyHostToDevice));
     static const int64_t no_pairs[2] = {0, 0};
-    const GradRequest R{t.clouds[0], t.clouds[1],
+    GradRequest R{t.clouds[0], t.clouds[1],
                         H.anchors ? (P ? reinterpret_cast<const int64_t*>(t.d_blk) : no_pairs) : nullptr,
                         H.wf ? reinterpret_cast<const int32_t*>(t.d_blk + o_wf) : nullptr, H.n_pairs, H.thr,
                         H.weights ? reinterpret_cast<const double*>(t.d_blk + o_w) : nullptr, H.tile_pairs,
                         reinterpret_cast<double*>(t.d_blk + o_sc), reinterpret_cast<double*>(t.d_blk + o_ga), reinterpret_cast<double*>(t.d_blk + o_gb)};
+    R.resolve = H.resolve;
+    for (int k = 0; k < 2; ++k) {
+        R.cell[k] = H.cell[k];
+        if (H.strain[k]) R.strain[k] = reinterpret_cast<double*>(t.d_blk + o_st + 72 * (size_t)k);
+    }
     const int rc = grad_core(c, R);
     // (an out-of-range contribution fails the call behind complete outputs: the scores are valid and go back)
     const bool range = rc == LCHD_EVALUE && strstr(g_err, "gradient contribution") != nullptr;
@@ -5016,6 +5094,8 @@ static int grad_host(lchd_ctx* c, HostTemps& t, const GradHostArrays& H) {
         if (P) HIP_TRY(hipMemcpy(H.scores, t.d_blk + o_sc, 8 * P, hipMemcpyDeviceToHost));
         if (na) HIP_TRY(hipMemcpy(H.grad_a, t.d_blk + o_ga, 24 * na, hipMemcpyDeviceToHost));
         if (nb) HIP_TRY(hipMemcpy(H.grad_b, t.d_blk + o_gb, 24 * nb, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 2; ++k)
+            if (H.strain[k]) HIP_TRY(hipMemcpy(H.strain[k], t.d_blk + o_st + 72 * (size_t)k, 72, hipMemcpyDeviceToHost));
         if (rc) snprintf(g_err, sizeof g_err, "%s", msg.c_str());
     }
     return rc;
@@ -5066,6 +5146,108 @@ extern "C" int lchd_gradient_coords(lchd_ctx* c, const lchd_config* cfg, const i
         if (int rc = lchd_cloud_create(c, xyz_a, seq_a, nullptr, n, &t.clouds[0])) return rc;
         if (int rc = lchd_cloud_create(c, xyz_b, seq_b, nullptr, n, &t.clouds[1])) return rc;
         return grad_host(c, t, GradHostArrays{nullptr, wf_index, pair_weights, n, n, n, 0.0, 0, scores, grad_a, grad_b});
+    };
+    t.rc = run();
+    c->last_valid = false;
+    c->pend.req.a = c->pend.req.b = nullptr;
+    return t.rc;
+}
+
+// ... under periodic boundaries.  The thresholded form: the structures as clouds of their own, a side with a box or cell replaced by its
+// image cloud (reach = the threshold) as lchd_sensitivity_primitives_periodic builds them, with that call's checks in its order.
+extern "C" int lchd_gradient_primitives_periodic(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a,
+                                                 const int32_t* tag_a, int64_t n_a, const double* xyz_b, const int32_t* cat_b,
+                                                 const int32_t* tag_b, int64_t n_b, const int64_t* anchors, const int32_t* wf_index,
+                                                 int64_t n_pairs, double thr, const double* box_a, const double* cell_a, const double* box_b,
+                                                 const double* cell_b, const double* pair_weights, int64_t tile_pairs, double* scores,
+                                                 double* grad_a, double* grad_b, double* strain_a, double* strain_b) {
+    CTX_LOCK(c);
+    // (what the arguments alone decide comes first: these need no context)
+    if (tile_pairs < 0) return fail(LCHD_EVALUE, "tile_pairs = %lld is negative (0: planned from the free device memory)", (long long)tile_pairs);
+    if (n_pairs < 0) return fail(LCHD_EVALUE, "negative pair count");
+    if (!strain_a != !strain_b) return fail(LCHD_EVALUE, "one strain pointer is null and the other is not: a call writes both tensors or neither");
+    const double* const box[2] = {box_a, box_b};
+    const double* const cell[2] = {cell_a, cell_b};
+    const int64_t n_at[2] = {n_a, n_b};
+    for (int k = 0; k < 2; ++k)
+        if (box[k] && cell[k])
+            return fail(LCHD_EVALUE, "a box and a cell were both given: a structure has one periodic box or one periodic cell");
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (int rc = check_wf_index(cfg, wf_index, n_pairs)) return rc;
+    if (n_a < 0 || n_b < 0 || n_a > ((int64_t)1 << 27) || n_b > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "structure size out of range");
+    for (int k = 0; k < 2; ++k)
+        if (box[k]) if (int rc = lchd_box_validate(box[k], 1, thr)) return rc;
+    for (int k = 0; k < 2; ++k)
+        if (cell[k]) if (int rc = lchd_cell_validate(cell[k], 1, thr)) return rc;
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if ((n_pairs > 0 && (!anchors || !scores)) || (n_a > 0 && !grad_a) || (n_b > 0 && !grad_b)) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    for (int64_t p = 0; p < n_pairs; ++p)  // (an index beyond the structure would name a ghost atom of an image cloud)
+        for (int k = 0; k < 2; ++k)
+            if (anchors[2 * p + k] < 0 || anchors[2 * p + k] >= n_at[k])
+                return fail(LCHD_EPANIC, "index out of bounds: an anchor index is outside its structure (src/locohd.rs:521)");
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    static const int64_t no_pairs[2] = {0, 0};
+    HostTemps t(c);  // clouds[0 .. 1]: what the call runs on; clouds[2 .. 3]: the structures behind image clouds (destroyed after them)
+    auto run = [&]() -> int {
+        lchd_cloud* own[2] = {nullptr, nullptr};
+        if (int rc = lchd_cloud_create(c, xyz_a, cat_a, tag_a, n_a, &own[0])) return rc;
+        t.clouds[0] = own[0];
+        if (int rc = lchd_cloud_create(c, xyz_b, cat_b, tag_b, n_b, &own[1])) return rc;
+        t.clouds[1] = own[1];
+        for (int k = 0; k < 2; ++k) {
+            if (!box[k] && !cell[k]) continue;
+            t.clouds[2 + k] = own[k];
+            t.clouds[k] = nullptr;
+            if (int rc = box[k] ? lchd_cloud_create_images(c, own[k], box[k], 1, thr, &t.clouds[k])
+                                : lchd_cloud_create_images_cell(c, own[k], cell[k], 1, thr, &t.clouds[k]))
+                return rc;
+        }
+        GradHostArrays H{anchors ? anchors : no_pairs, wf_index, pair_weights, n_pairs, n_a, n_b, thr, tile_pairs, scores, grad_a, grad_b};
+        H.resolve = kSensImages;
+        H.strain[0] = strain_a; H.strain[1] = strain_b;
+        return grad_host(c, t, H);
+    };
+    t.rc = run();
+    c->last_valid = false;  // the clouds of this call go away (`t` destroys them on return)
+    c->pend.req.a = c->pend.req.b = nullptr;
+    return t.rc;
+}
+// The dense form: lchd_gradient_coords with the cells of lchd_sensitivity_coords_periodic (row-major [9], NULL: an open side).
+extern "C" int lchd_gradient_coords_periodic(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                             int64_t len_seq_b, const double* xyz_a, const double* xyz_b, int64_t n, const int32_t* wf_index,
+                                             const double* cell_a, const double* cell_b, const double* pair_weights, double* scores,
+                                             double* grad_a, double* grad_b, double* strain_a, double* strain_b) {
+    CTX_LOCK(c);
+    if (n < 0) return fail(LCHD_EVALUE, "negative structure size");
+    if (int rc = coords_lengths(xyz_a, n, xyz_b, n)) return rc;
+    if (!strain_a != !strain_b) return fail(LCHD_EVALUE, "one strain pointer is null and the other is not: a call writes both tensors or neither");
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    {
+        const double* const cells[2] = {cell_a, cell_b};
+        MinImageCell rec[2];
+        const MinImageCell* cell[2];
+        if (int rc = reduce_cells(cells, 2, false, rec, cell)) return rc;
+    }
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    if (int rc = check_wf_index(cfg, wf_index, n)) return rc;
+    if (n == 0) {
+        if (strain_a) for (int k = 0; k < 9; ++k) strain_a[k] = strain_b[k] = 0.0;
+        return LCHD_OK;
+    }
+    if (n > len_seq_a || n > len_seq_b) return fail(LCHD_EPANIC, "index out of bounds: a distance row is longer than its seq");
+    if (!seq_a || !seq_b || !scores || !grad_a || !grad_b) return fail(LCHD_EVALUE, "null pointer");
+    HostTemps t(c);
+    auto run = [&]() -> int {
+        if (int rc = lchd_cloud_create(c, xyz_a, seq_a, nullptr, n, &t.clouds[0])) return rc;
+        if (int rc = lchd_cloud_create(c, xyz_b, seq_b, nullptr, n, &t.clouds[1])) return rc;
+        GradHostArrays H{nullptr, wf_index, pair_weights, n, n, n, 0.0, 0, scores, grad_a, grad_b};
+        H.resolve = kSensMinImage;
+        H.cell[0] = cell_a; H.cell[1] = cell_b;
+        H.strain[0] = strain_a; H.strain[1] = strain_b;
+        return grad_host(c, t, H);
     };
     t.rc = run();
     c->last_valid = false;

@@ -587,6 +587,12 @@ struct GradAccumArgs {
 };
 bool launch_grad_accumulate(hipStream_t s, const GradAccumArgs& a);  // false: nothing launched (a null array, a side shorter than its rows)
 bool launch_grad_finish(hipStream_t s, int64_t* acc, int64_t n_atoms, double* grad);  // grad [n_atoms][3]; zeroes acc
+// The strain derivative of the same lists (k_strain_accumulate; every side needs `disp`): six exact sums per side, acc [2][6][LCHD_GRAD_LIMBS]
+// with side A first.  The grid does not grow with the pair count: at most kStrainMaxBlocks workgroups of four wavefronts, each wavefront
+// on one side, so at most 2 kStrainMaxBlocks wavefronts per side add their 48 limb totals once.
+constexpr int kStrainMaxBlocks = 512;
+bool launch_strain_accumulate(hipStream_t s, const GradAccumArgs& a, int64_t* acc);  // false: nothing launched (a null array, no disp)
+bool launch_strain_finish(hipStream_t s, int64_t* acc, double* strain_a, double* strain_b);  // strain [9] row-major each; zeroes acc
 void launch_mark_overflow(hipStream_t s, const uint32_t* list_a, uint32_t na, const uint32_t* list_b, uint32_t nb, uint32_t* bits_a, uint32_t* bits_b);
 void launch_count_overflow(hipStream_t s, const OverflowSelect& a, unsigned long long* total);
 void launch_write_overflow(hipStream_t s, const OverflowSelect& a);

@@ -16,8 +16,17 @@
 //                       No floating-point atomics; an out-of-range step (lchd_exact_sum.h) adds nothing and raises the flag.
 //   k_grad_finish       one lane per (atom, component): the correctly rounded double of the accumulator into grad[N][3], limbs zeroed
 //                       for the next call.
+//   k_strain_accumulate the strain derivative W of both sides (lchd_strain_sum.h): W[i][j] += step_i * disp[p][k][j], i <= j, over the
+//                       slots k_grad_accumulate uses, from lists that carry `disp`.  Every slot of a call adds to the same 48 limbs of
+//                       its side, so nothing is added per slot: a grid of at most kStrainMaxBlocks workgroups, whatever the pair count;
+//                       a wavefront serves ONE side (its index's parity, which the grid stride keeps) and carries that side's 6 x 8
+//                       limb partial sums in each lane's registers across its whole loop over the pairs; at the end the sums go over
+//                       the wavefront with shuffles of the 64-bit limbs, and lanes 0 .. 47 issue one integer atomic each (zero sums
+//                       skipped).  A partial sum takes 2^31 terms like a limb: the host layer keeps a call's slots per side below that.
+//   k_strain_finish     one workgroup: both sides' six sums rounded once into the symmetric double[9] tensors, limbs zeroed.
 #include "lchd_device.h"
 #include "lchd_exact_sum.h"
+#include "lchd_strain_sum.h"
 
 namespace lchd {
 
@@ -98,6 +107,78 @@ __global__ __launch_bounds__(256) void k_grad_finish(int64_t* __restrict__ acc, 
 #pragma unroll
     for (int k = 0; k < LCHD_GRAD_LIMBS; ++k) { mine[k] = limbs[k]; limbs[k] = 0; }
     grad[i] = lchd_xs_finish(mine);
+}
+
+__global__ __launch_bounds__(256) void k_strain_accumulate(GradAccumArgs ga, int64_t* __restrict__ acc_a, int64_t* __restrict__ acc_b) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
+    const int side = (int)(wave0 & 1);  // (n_waves is a multiple of 4: every w of this wavefront's loop has this parity)
+    const GradSide& S = ga.s[side];
+    const int64_t K = ga.width;
+    int64_t part[LCHD_STRAIN_COMPONENTS][LCHD_GRAD_LIMBS] = {};
+    bool bad = false;
+    for (int64_t w = wave0; w < 2 * ga.n_pairs; w += n_waves) {
+        const int64_t p = w >> 1;
+        const int32_t* __restrict__ idx = S.idx + p * K;
+        const double* __restrict__ dist = S.dist + p * K;
+        const double* __restrict__ g = S.g + p * K;
+        const double* __restrict__ disp = S.disp + 3 * (p * K);
+        const int64_t a = ga.dense ? p : (int64_t)idx[0];
+        if (a < 0 || a >= S.n) continue;
+        const double v = ga.weights ? ga.weights[p] : 1.0;
+        for (int64_t k = 1 + lane; k < K; k += 64) {
+            const int64_t m = idx[k];
+            const double d = dist[k], gk = g[k];
+            if (m < 0 || m >= S.n || !(d > 0.0) || !isfinite(gk)) continue;
+            const double dp[3] = {disp[3 * k], disp[3 * k + 1], disp[3 * k + 2]};
+            if (!lchd_strain_slot(part, v, gk, d, dp)) bad = true;
+        }
+    }
+    if (__ballot(bad) && lane == 0) lchd_xs_flag_or(ga.flag, LCHD_XS_OUT_OF_RANGE);
+    // the side's 48 limbs: every lane ends with the wave's totals, lane i adds total i
+    int64_t out = 0;
+#pragma unroll
+    for (int c = 0; c < LCHD_STRAIN_COMPONENTS; ++c)
+#pragma unroll
+        for (int k = 0; k < LCHD_GRAD_LIMBS; ++k) {
+            long long t = part[c][k];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+            if (lane == c * LCHD_GRAD_LIMBS + k) out = t;
+        }
+    if (lane < LCHD_STRAIN_LIMBS && out != 0) lchd_xs_limb_add((side ? acc_b : acc_a) + lane, out);
+}
+
+// acc: [2][LCHD_STRAIN_LIMBS], side A then side B
+__global__ __launch_bounds__(128) void k_strain_finish(int64_t* __restrict__ acc, double* __restrict__ strain_a, double* __restrict__ strain_b) {
+    const int t = threadIdx.x, side = t / 9, e = t % 9, i = e / 3, j = e % 3;
+    double v = 0.0;
+    if (t < 18) {
+        const int64_t* const limbs = acc + side * LCHD_STRAIN_LIMBS + lchd_strain_component(i < j ? i : j, i < j ? j : i) * LCHD_GRAD_LIMBS;
+        int64_t mine[LCHD_GRAD_LIMBS];
+#pragma unroll
+        for (int k = 0; k < LCHD_GRAD_LIMBS; ++k) mine[k] = limbs[k];
+        v = lchd_xs_finish(mine);
+    }
+    __syncthreads();
+    if (t < 18) (side ? strain_b : strain_a)[e] = v;
+    if (t < 2 * LCHD_STRAIN_LIMBS) acc[t] = 0;
+}
+
+bool launch_strain_accumulate(hipStream_t s, const GradAccumArgs& a, int64_t* acc) {
+    if (a.n_pairs <= 0) return true;
+    if (a.width < 1 || !a.flag || !acc) return false;
+    for (int k = 0; k < 2; ++k)
+        if (!a.s[k].idx || !a.s[k].dist || !a.s[k].g || !a.s[k].disp || a.s[k].n < 1 || (a.dense && a.s[k].n < a.n_pairs)) return false;
+    const int64_t blocks = (2 * a.n_pairs + 3) / 4;
+    k_strain_accumulate<<<(unsigned)(blocks < kStrainMaxBlocks ? blocks : kStrainMaxBlocks), 256, 0, s>>>(a, acc, acc + LCHD_STRAIN_LIMBS);
+    return true;
+}
+
+bool launch_strain_finish(hipStream_t s, int64_t* acc, double* strain_a, double* strain_b) {
+    if (!acc || !strain_a || !strain_b) return false;
+    k_strain_finish<<<1, 128, 0, s>>>(acc, strain_a, strain_b);
+    return true;
 }
 
 bool launch_grad_accumulate(hipStream_t s, const GradAccumArgs& a) {

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .api import LoCoHD, MinImageSensitivity, Nearest, PeriodicSensitivity, Sensitivity, dense_cells, periodic_boxes, periodic_cells
+from .api import LoCoHD, MinImageSensitivity, NativeGradient, Nearest, PeriodicSensitivity, Sensitivity, dense_cells, periodic_boxes, periodic_cells
 
 
 def last_sweep_of(ctx):
@@ -594,6 +594,64 @@ class DeviceSession:
         w_ptr = None if w is None else C.c_void_p(w.data_ptr())
         N.check(N.lib().lchd_gradient_coords_dev(self._ctx, cloud_a, cloud_b, wf_ptr, w_ptr, *[C.c_void_p(t.data_ptr()) for t in out]))
         return out
+
+    def _native_periodic_buffers(self, cloud_a, cloud_b, p, pair_weights, wf_index, out, strain):
+        """`_native_gradient_buffers` with one gradient row per SOURCE atom and, with `strain`, the two [3][3] tensors behind them."""
+        torch = self.torch
+        na, nb = (int(N.lib().lchd_cloud_home_size(cl)) for cl in (cloud_a, cloud_b))
+        dev = torch.device("cuda", self.device)
+        w = wf_ptr = None
+        if pair_weights is not None:
+            if pair_weights.numel() != p:
+                raise ValueError(f"pair_weights has {pair_weights.numel()} entries for {p} pairs")
+            w = pair_weights.detach().to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+        if wf_index is not None:
+            assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= p
+            wf_ptr = C.c_void_p(wf_index.data_ptr())
+        shapes = ((p,), (na, 3), (nb, 3)) + (((3, 3), (3, 3)) if strain else ())
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=torch.float64, device=dev) for shape in shapes)
+        if len(out) != len(shapes):
+            raise ValueError(f"out holds {len(out)} tensors; this call fills {len(shapes)}")
+        for t, shape in zip(out, shapes):
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
+        return w, wf_ptr, tuple(out)
+
+    def native_gradient_images(self, cloud_a, cloud_b, anchors, threshold_distance: float, pair_weights=None, wf_index=None, *,
+                               tile_pairs=0, strain=False, out=None):
+        """`native_gradient` for clouds of which any may be an image cloud (periodic_images): `(scores, grad_a, grad_b)` with one gradient
+        row per SOURCE atom (lchd_cloud_home_size), the terms `gradient_images` sums with index_add_ reduced exactly on the device
+        (lchd_gradient_images_dev).  strain=True: a `NativeGradient` whose strain_a / strain_b [3][3] are the strain derivatives of
+        sum_p v_p S_p per side (LoCoHD.native_gradient_from_primitives_periodic); NotImplementedError with a batch cloud.  out: the three
+        (with strain: five) float64 CUDA tensors, filled and returned.  Other arguments and the bit guarantee as `native_gradient`."""
+        torch = self.torch
+        assert anchors.is_cuda and anchors.dtype == torch.int64 and anchors.is_contiguous()
+        if int(tile_pairs) < 0:
+            raise ValueError(f"tile_pairs = {int(tile_pairs)} is negative (0: planned from the free device memory)")
+        p = anchors.shape[0]
+        w, wf_ptr, out = self._native_periodic_buffers(cloud_a, cloud_b, p, pair_weights, wf_index, out, strain)
+        w_ptr = None if w is None else C.c_void_p(w.data_ptr())
+        ptrs = [C.c_void_p(t.data_ptr()) for t in out] + ([] if strain else [None, None])
+        N.check(N.lib().lchd_gradient_images_dev(self._ctx, cloud_a, cloud_b, C.c_void_p(anchors.data_ptr()), wf_ptr, p,
+                                                 float(threshold_distance), w_ptr, int(tile_pairs), *ptrs))
+        return NativeGradient(*out) if strain else out
+
+    def native_gradient_coords_periodic(self, cloud_a, cloud_b, pair_weights=None, wf_index=None, *, box_a=None, box_b=None, cell_a=None,
+                                        cell_b=None, strain=False, out=None):
+        """`native_gradient_coords` on minimum-image rows (LoCoHD.native_gradient_from_coords_periodic): boxes and cells (keyword-only,
+        host arrays) as `sensitivity_coords_periodic` takes them, a side with neither is open; strain and out as in
+        `native_gradient_images` (lchd_gradient_coords_periodic_dev)."""
+        for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+            if box is not None and cell is not None:
+                raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
+        pc_a = dense_cells(box_a, cell_a, 1, "box_a", "cell_a")
+        pc_b = dense_cells(box_b, cell_b, 1, "box_b", "cell_b")
+        n = int(N.lib().lchd_cloud_size(cloud_a))
+        w, wf_ptr, out = self._native_periodic_buffers(cloud_a, cloud_b, n, pair_weights, wf_index, out, strain)
+        w_ptr = None if w is None else C.c_void_p(w.data_ptr())
+        ptrs = [C.c_void_p(t.data_ptr()) for t in out] + ([] if strain else [None, None])
+        N.check(N.lib().lchd_gradient_coords_periodic_dev(self._ctx, cloud_a, cloud_b, wf_ptr, N.dp(pc_a), N.dp(pc_b), w_ptr, *ptrs))
+        return NativeGradient(*out) if strain else out
 
     def sensitivity_coords(self, cloud_a, cloud_b, out=None, wf_index=None, *, width=None):
         """Neighbour sensitivities of the dense row pairs of two uploaded structures of equal size (LoCoHD.sensitivity_from_coords; no
