@@ -509,6 +509,53 @@ int lchd_attribution_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *
                           int64_t len_seq_b, const double *dmx_a, const double *dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
                           const int32_t *wf_index, double *out);
 
+/* ---- category-weight gradients (additive, not in the reference) ----------------------------------------
+ * The derivative of a pair's score with respect to the category_weights of the configuration: G[p][c] = dS_p / dw_c.  Between two merged
+ * breakpoints u_j <= u_{j+1} (the notation of the radial profiles above; u_0 = 0, u_{J+1} = +inf), with nA_c / nB_c the category counts
+ * of the piece (anchors included), p_c = w_c nA_c / sum_k w_k nA_k and q_c likewise from nB, D(p, q) the statistical distance,
+ * x_c = p_c dD/dp_c and y_c = q_c dD/dq_c -- since w_c dp_k/dw_c = p_c (delta_kc - p_k):
+ *   w_c dD/dw_c = x_c + y_c - p_c sum_k x_k - q_c sum_k y_k
+ *   out[p][c]   = (1 / w_c) * sum_j (F(u_{j+1}) - F(u_j)) * (w_c dD/dw_c)_j
+ * Hellinger, exponent e: d_c = p_c^(1/e) - q_c^(1/e), T = sum_c |d_c|^e, D = (T / 2)^(1/e),
+ *   x_c = (D / (e T)) |d_c|^(e-1) sgn(d_c) p_c^(1/e)        y_c = -(D / (e T)) |d_c|^(e-1) sgn(d_c) q_c^(1/e)
+ *   (e = 2: w_c dH/dw_c = (sqrt p_c - sqrt q_c)^2 / (4 H) - (p_c + q_c) H / 4)
+ * Kullback-Leibler, epsilon (side A is the first argument, as in the scoring calls):
+ *   x_c = p_c [ln((p_c + eps) / (q_c + eps)) + p_c / (p_c + eps)]        y_c = -p_c q_c / (q_c + eps)
+ * Every term is finite at p_c = 0 or q_c = 0; nothing divides by a PMF entry.  Conventions:
+ *   - a Hellinger piece with T = 0 adds 0 to every column (the distance has a kink there; 0 is the subgradient the attribution implies)
+ *   - a category with d_c = 0 has x_c = y_c = 0 for every exponent (sgn 0 = 0)
+ *   - a piece with F(u_{j+1}) - F(u_j) <= 0 adds nothing
+ * so that
+ *   - a category neither environment of a pair holds has an exactly zero column
+ *   - two identical environments give a row of exact zeros under Hellinger; one category gives exact zeros
+ *   - sum_c w_c out[p][c] = 0 up to rounding: the score is homogeneous of degree 0 in the weights
+ * out is row-major [pairs][n_categories] f64, categories in the order of lchd_config.  Under Kolmogorov-Smirnov and Renyi configurations
+ * these calls fail with LCHD_EUNSUPPORTED (the message names the distance); the scoring calls are untouched.
+ * The calls are the attribution calls of the same name with another kernel (lchd_category_gradient.hip) behind the same pass: the same
+ * environments, store builds, record pass, capacity repeats, errors (a NaN row for a weight-function index outside the dictionary, ...),
+ * stream and lock rules, limits (64 categories, 65 535 points), and they too leave the hints of the scoring passes and
+ * lchd_ctx_last_sweep alone.  One accumulator per category and lane, reduced in lane order: no floating-point atomics, a row's bits
+ * depend on the stored pair and the configuration alone.  Device groups have no such call. */
+/* Thresholded, device-resident; d_out DEVICE f64 [n_pairs][n_categories]. */
+int lchd_category_gradient_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors, const int32_t *d_wf_index,
+                                          int64_t n_pairs, double threshold_distance, double *d_out);
+/* The same from host arrays, open or periodic per side (box_* / cell_* as lchd_attribution_primitives); out HOST [n_pairs][n_categories]. */
+int lchd_category_gradient_primitives(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a, const int32_t *tag_a,
+                                      int64_t n_a, const double *xyz_b, const int32_t *cat_b, const int32_t *tag_b, int64_t n_b,
+                                      const int64_t *anchors, const int32_t *wf_index, int64_t n_pairs, double threshold_distance,
+                                      const double *box_a, const double *cell_a, const double *box_b, const double *cell_b, double *out);
+/* Dense rows, device-resident single structures of equal size; d_out DEVICE [n][n_categories]. */
+int lchd_category_gradient_coords_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, const double *cell_a,
+                                      const double *cell_b, double *d_out);
+/* The same from host arrays, as lchd_from_coords takes them; out HOST [n][n_categories]. */
+int lchd_category_gradient_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                                  int64_t len_seq_b, const double *xyz_a, int64_t n_a, const double *xyz_b, int64_t n_b,
+                                  const int32_t *wf_index, const double *cell_a, const double *cell_b, double *out);
+/* Given distance rows; out HOST [rows][n_categories]. */
+int lchd_category_gradient_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                                int64_t len_seq_b, const double *dmx_a, const double *dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
+                                const int32_t *wf_index, double *out);
+
 /* ---- neighbour sensitivities (additive, not in the reference) ------------------------------------------
  * Which members of the two environments carry a pair's score, and how it changes when one of them moves: the derivative of the score
  * with respect to the distance d of every environment member.  On the piecewise-constant integrand the sweeps walk,

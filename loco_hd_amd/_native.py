@@ -168,6 +168,12 @@ _PROTOS = {
     "lchd_attribution_coords_dev": (C.c_int, [_VP, _VP, _VP, _VP, _DP, _DP, _VP]),
     "lchd_attribution_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _i64, _DP, _i64, _IP, _DP, _DP, _DP]),
     "lchd_attribution_dmxs": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _i64, _i64, _IP, _DP]),
+    "lchd_category_gradient_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _i64, _f64, _VP]),
+    "lchd_category_gradient_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _DP,
+                                                    _DP, _DP, _DP, _DP]),
+    "lchd_category_gradient_coords_dev": (C.c_int, [_VP, _VP, _VP, _VP, _DP, _DP, _VP]),
+    "lchd_category_gradient_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _i64, _DP, _i64, _IP, _DP, _DP, _DP]),
+    "lchd_category_gradient_dmxs": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _i64, _i64, _IP, _DP]),
     "lchd_sensitivity_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _i64, _f64, _i32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lchd_sensitivity_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _i32,
                                               _DP, _IP, _IP, _DP, _DP, _IP, _IP, _DP, _DP]),

@@ -45,6 +45,7 @@ except ImportError:  # pragma: no cover
 
 WF_KINDS = {"hyper_exp": 0, "dagum": 1, "uniform": 2, "kumaraswamy": 3}
 SD_KINDS = {"Hellinger": 0, "Kolmogorov-Smirnov": 1, "Kullback-Leibler": 2, "Renyi": 3}
+_CATEGORY_GRADIENT = "category gradient"  # the third selector of the _pair_rows_from_* helpers, next to None and an edge array
 
 
 def _f64(x) -> np.ndarray:
@@ -838,12 +839,25 @@ class LoCoHD:
         return ed
 
     def _no_device_group_for_pair_rows(self, ed) -> None:
+        if ed is _CATEGORY_GRADIENT:  # (and what else its kernel does not take, before any device is touched)
+            if self._devices is not None:
+                raise NotImplementedError("a category-weight gradient applies to one device (a device group has no such call): drop devices=[...]")
+            if self._sd._name not in ("Hellinger", "Kullback-Leibler"):
+                raise NotImplementedError("a category-weight gradient is implemented for the Hellinger and Kullback-Leibler distances; not for "
+                                          f"the {self._sd._name} distance")
+            if len(self._weights) > 64:
+                raise NotImplementedError(f"a category-weight gradient takes at most 64 categories (got {len(self._weights)})")
+            return
         if self._devices is not None:
             what, call = ("an attribution", "attribution") if ed is None else ("a radial profile", "radial")
             raise ValueError(f"{what} applies to one device (a device group has no {call} call): drop devices=[...]")
 
-    # The three radial methods and the three attribution methods differ in the kernel their pass ends in and in the row it writes:
-    # `ed` is the checked edge array of a radial call (rows of len(ed) - 1 bins) or None for an attribution (rows of C categories).
+    def _pair_rows_width(self, ed) -> int:
+        return len(self._weights) if ed is None or ed is _CATEGORY_GRADIENT else len(ed) - 1
+
+    # The three radial methods, the three attribution methods and the three category-gradient methods differ in the kernel their pass
+    # ends in and in the row it writes: `ed` is the checked edge array of a radial call (rows of len(ed) - 1 bins), None for an
+    # attribution or _CATEGORY_GRADIENT for a category-weight gradient (rows of C categories).
     def _pair_rows_from_primitives(self, ed, prim_a, prim_b, anchor_pairs, threshold_distance, box_a, box_b, cell_a, cell_b) -> np.ndarray:
         for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
             if box is not None and cell is not None:
@@ -858,13 +872,15 @@ class LoCoHD:
         pa, pb, interner = self._packed_lists(prim_a, prim_b)
         anchors = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
         cfg, keep = self._config(interner)
-        out = np.empty((len(anchors), len(self._weights) if ed is None else len(ed) - 1))
+        out = np.empty((len(anchors), self._pair_rows_width(ed)))
         if len(anchors) == 0:
             return out
         xa, xb = _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3)
         head = (self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa), N.dp(xb), N.ip(pb.cat), N.ip(pb.tag), len(xb),
                 N.lp(anchors), N.ip(idx), len(anchors), thr, N.dp(ba), N.dp(ca), N.dp(bb), N.dp(cb))
-        if ed is None:
+        if ed is _CATEGORY_GRADIENT:
+            N.check(N.lib().lchd_category_gradient_primitives(*head, N.dp(out)))
+        elif ed is None:
             N.check(N.lib().lchd_attribution_primitives(*head, N.dp(out)))
         else:
             N.check(N.lib().lchd_radial_primitives(*head, N.dp(ed), len(ed), N.dp(out)))
@@ -883,12 +899,14 @@ class LoCoHD:
         idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], len(xa))
         ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
         cfg, keep = self._config()
-        out = np.empty((len(xa), len(self._weights) if ed is None else len(ed) - 1))
+        out = np.empty((len(xa), self._pair_rows_width(ed)))
         if len(xa) == 0:
             return out
         head = (self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(xa), len(xa), N.dp(xb), len(xb), N.ip(idx), N.dp(pc_a),
                 N.dp(pc_b))
-        if ed is None:
+        if ed is _CATEGORY_GRADIENT:
+            N.check(N.lib().lchd_category_gradient_coords(*head, N.dp(out)))
+        elif ed is None:
             N.check(N.lib().lchd_attribution_coords(*head, N.dp(out)))
         else:
             N.check(N.lib().lchd_radial_coords(*head, N.dp(ed), len(ed), N.dp(out)))
@@ -898,19 +916,21 @@ class LoCoHD:
         self._no_device_group_for_pair_rows(ed)
         (ma, la), (mb, lb) = self._matrix(dmx_a), self._matrix(dmx_b)
         if la is not None or lb is not None:
-            name = "attribution_from_dmxs" if ed is None else "radial_from_dmxs"
+            name = "category_gradient_from_dmxs" if ed is _CATEGORY_GRADIENT else "attribution_from_dmxs" if ed is None else "radial_from_dmxs"
             raise ValueError(f"{name} takes rectangular distance matrices (rows of equal length)")
         if ma.shape[0] != mb.shape[0]:
             raise ValueError(f"Expected matrices with the same length, got lengths {ma.shape[0]} and {mb.shape[0]}!")
         idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], ma.shape[0])
         ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
         cfg, keep = self._config()
-        out = np.empty((ma.shape[0], len(self._weights) if ed is None else len(ed) - 1))
+        out = np.empty((ma.shape[0], self._pair_rows_width(ed)))
         if ma.shape[0] == 0:
             return out
         head = (self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(ma), N.dp(mb), ma.shape[0], ma.shape[1], mb.shape[1],
                 N.ip(idx))
-        if ed is None:
+        if ed is _CATEGORY_GRADIENT:
+            N.check(N.lib().lchd_category_gradient_dmxs(*head, N.dp(out)))
+        elif ed is None:
             N.check(N.lib().lchd_attribution_dmxs(*head, N.dp(out)))
         else:
             N.check(N.lib().lchd_radial_dmxs(*head, N.dp(ed), len(ed), N.dp(out)))
@@ -957,6 +977,29 @@ class LoCoHD:
     def attribution_from_dmxs(self, seq_a, seq_b, dmx_a, dmx_b, w_func_keys: Optional[Sequence[str]] = None) -> np.ndarray:
         """Additive: the score of every row pair `from_dmxs` would score, split over the categories, as a float64 array (rows, C)."""
         return self._pair_rows_from_dmxs(None, seq_a, seq_b, dmx_a, dmx_b, w_func_keys)
+
+    # ---- category-weight gradients (additive) -------------------------------------------------------------
+    # G[p][c] = dS_p / dw_c, the derivative of pair p's score with respect to `category_weights` (include/loco_hd_hip.h, "category-weight
+    # gradients"): with p_c = w_c n_c / sum_k w_k n_k per side, w_c dD/dw_c = x_c + y_c - p_c sum_k x_k - q_c sum_k y_k, integrated over
+    # the pieces of the pair as the score is.  Columns follow `categories`; sum_c w_c G[p][c] = 0.  Hellinger and Kullback-Leibler
+    # distances (NotImplementedError otherwise), at most 64 categories, no device groups.
+    def category_gradient_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                                          threshold_distance: float, *, box_a=None, box_b=None, cell_a=None, cell_b=None) -> np.ndarray:
+        """Additive: the derivative of the score of every anchor pair `from_primitives` would score with respect to every category
+        weight, as a float64 array (P, C) with columns in `categories` order.  `anchor_pairs`, `box_a` / `box_b` / `cell_a` / `cell_b`: as
+        `attribution_from_primitives` takes them."""
+        return self._pair_rows_from_primitives(_CATEGORY_GRADIENT, prim_a, prim_b, anchor_pairs, threshold_distance, box_a, box_b, cell_a, cell_b)
+
+    def category_gradient_from_coords(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None, *, box_a=None,
+                                      box_b=None, cell_a=None, cell_b=None) -> np.ndarray:
+        """Additive: the derivative of the score of every dense row pair `from_coords` would score with respect to every category
+        weight, as a float64 array (n, C).  `box_a` / `box_b` / `cell_a` / `cell_b` (keyword-only): minimum-image rows."""
+        return self._pair_rows_from_coords(_CATEGORY_GRADIENT, seq_a, seq_b, coords_a, coords_b, w_func_keys, box_a, box_b, cell_a, cell_b)
+
+    def category_gradient_from_dmxs(self, seq_a, seq_b, dmx_a, dmx_b, w_func_keys: Optional[Sequence[str]] = None) -> np.ndarray:
+        """Additive: the derivative of the score of every row pair `from_dmxs` would score with respect to every category weight, as a
+        float64 array (rows, C)."""
+        return self._pair_rows_from_dmxs(_CATEGORY_GRADIENT, seq_a, seq_b, dmx_a, dmx_b, w_func_keys)
 
     # ---- neighbour sensitivities and coordinate gradients (additive) ---------------------------------------
     # g = dS/dd = w(d) (H- - H+) for every member of the pair's two environments (include/loco_hd_hip.h, "neighbour sensitivities"): which

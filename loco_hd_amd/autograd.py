@@ -24,6 +24,11 @@ Forward is DeviceSession.sensitivity_coords_periodic, backward is side A of Devi
 The movable structure in a periodic box or cell: forward is DeviceSession.sensitivity_images on its image cloud, backward is side A of
 DeviceSession.gradient_images (side_gradient_images).
 
+    scores = locohd_scores_weighted(session, cloud_a, cloud_b, anchors, threshold_distance, category_weights)
+
+Two fixed uploaded clouds, differentiable with respect to the category weights: forward is DeviceSession.set_category_weights and
+DeviceSession.from_primitives, backward one DeviceSession.category_gradient call.  The session keeps the last weights set.
+
 The two periodic forms take `native=True` as well: forward and backward are then one DeviceSession.native_gradient_images /
 native_gradient_coords_periodic call each, backward with grad_output as the pair weights.  Boxes and cells stay non-differentiable.
 """
@@ -274,3 +279,32 @@ def locohd_scores_periodic(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, t
     if native:
         return _LoCoHDScoresPeriodicNative.apply(xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, float(threshold_distance), box, cell)
     return _LoCoHDScoresPeriodic.apply(xyz_a, session, cloud_b_ref, cat_a, tag_a, anchors, float(threshold_distance), box, cell)
+
+
+class _LoCoHDScoresWeighted(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, category_weights, session, cloud_a, cloud_b, anchors, threshold_distance, wf_index):
+        w = category_weights.detach()
+        session.set_category_weights(w)
+        ctx.session, ctx.clouds, ctx.anchors, ctx.thr, ctx.wf_index = session, (cloud_a, cloud_b), anchors, threshold_distance, wf_index
+        ctx.save_for_backward(w)
+        return session.from_primitives(cloud_a, cloud_b, anchors, threshold_distance, wf_index=wf_index)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (w,) = ctx.saved_tensors
+        session = ctx.session
+        session.set_category_weights(w)  # (a no-op unless the session's weights were set again since forward)
+        g = session.category_gradient(ctx.clouds[0], ctx.clouds[1], ctx.anchors, ctx.thr, wf_index=ctx.wf_index)
+        grad_w = (g * grad_output.to(g.dtype)[:, None]).sum(0)
+        return grad_w.to(device=w.device, dtype=w.dtype), None, None, None, None, None, None
+
+
+def locohd_scores_weighted(session, cloud_a, cloud_b, anchors, threshold_distance, category_weights, wf_index=None):
+    """The scores of the anchor pairs (torch int64 CUDA tensor [P][2]) of two clouds uploaded to `session`, differentiable with respect
+    to `category_weights`, a float64 tensor [C] of positive values (on any device) that may require grad.  Forward sets the session's
+    weights (DeviceSession.set_category_weights) and scores (DeviceSession.from_primitives); backward is one
+    DeviceSession.category_gradient call, returning (G * grad_output[:, None]).sum(0).  Hellinger and Kullback-Leibler distances.
+    Coordinates are not differentiated here.  The session keeps the last weights set: later calls of the session score with them, and a
+    backward call puts the weights of its forward call back first."""
+    return _LoCoHDScoresWeighted.apply(category_weights, session, cloud_a, cloud_b, anchors, float(threshold_distance), wf_index)

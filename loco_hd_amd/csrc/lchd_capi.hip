@@ -3766,12 +3766,13 @@ extern "C" int lchd_radial_validate(const double* edges, int32_t n_edges) {
     return LCHD_OK;
 }
 // The consumer of a profile pass's stores: the profile kernel on ONE store (sides == 1: composition, lchd_profile.hip), or, on two
-// stores and the pair records of k_pair_meta, the radial kernel (edges.n >= 2) or the attribution kernel (edges.n == 0).  Everything
+// stores and the pair records of k_pair_meta, the radial kernel (edges.n >= 2), the attribution kernel (edges.n == 0) or the
+// category-gradient kernel (weights).  Everything
 // up to the consumer's launch is one code path; it asks which consumer it serves in the three helpers below, in consumer_list_limit,
 // in consumer_drop_records and where consumer_prims_pass fills a one-sided query; what else differs is data of the descriptor.
 struct PairConsumer {
     RadialEdges edges;  // n >= 2: a radial profile
-    const char* what;   // in messages: "a composition profile" / "a radial profile" / "an attribution"
+    const char* what;   // in messages: "a composition profile" / "a radial profile" / "an attribution" / ...
     const char* call;   // "composition" / "radial" / "attribution"
     const char* items;  // what its list holds: "anchors" / "anchor pairs"
     int sides;          // structures (stores) of a call, columns of its list: 1 composition, 2 the others
@@ -3781,10 +3782,12 @@ struct PairConsumer {
     int resolve;        // ... and what runs behind its kernel: kSensPlain nothing; kSensImages launch_sens_resolve, which resolves members
                         // of image clouds to source atoms (image and disp outputs); kSensMinImage launch_sens_min_image_disp on dense rows
                         // from coordinates (disp outputs alone)
+    bool weights;       // a category-weight gradient: the attribution call's pass and row, the other kernel (lchd_category_gradient.hip)
 };
 enum { kSensPlain = 0, kSensImages = 1, kSensMinImage = 2 };
 static const PairConsumer kComposition{{}, "a composition profile", "composition", "anchors", 1, false};
 static const PairConsumer kAttribution{{}, "an attribution", "attribution", "anchor pairs", 2, true};
+static const PairConsumer kCategoryGradient{{}, "a category-weight gradient", "category gradient", "anchor pairs", 2, true, 0, {}, 0, true};
 static PairConsumer radial_consumer(const double* edges, int32_t n_edges) {
     PairConsumer use{{}, "a radial profile", "radial", "anchor pairs", 2, true};
     use.edges.n = n_edges;
@@ -3825,7 +3828,10 @@ static int consumer_limits(const lchd_ctx* c, const PairConsumer& use) {
     static const char* names[4] = {"Hellinger", "Kolmogorov-Smirnov", "Kullback-Leibler", "Renyi"};
     if (use.sides == 1) return LCHD_OK;  // a composition has no distance, and its kernel takes every category count
     const int most = use.width ? kSensitivityMaxCategories : (use.edges.n ? kWideCategories : kAttributionMaxCategories);
-    if (!use.edges.n && !use.width && c->h_cfg.sd_kind != SD_HELLINGER)
+    if (use.weights && c->h_cfg.sd_kind != SD_HELLINGER && c->h_cfg.sd_kind != SD_KL)
+        return fail(LCHD_EUNSUPPORTED, "a category-weight gradient is implemented for the Hellinger and Kullback-Leibler distances; not for the %s distance",
+                    names[c->h_cfg.sd_kind & 3]);
+    if (!use.edges.n && !use.width && !use.weights && c->h_cfg.sd_kind != SD_HELLINGER)
         return fail(LCHD_EUNSUPPORTED, "an attribution splits the Hellinger distance over the categories; the %s distance is no sum of per-category terms",
                     names[c->h_cfg.sd_kind & 3]);
     if (c->h_cfg.n_categories > most)
@@ -3902,6 +3908,12 @@ static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use,
         ra.n_categories = c->h_cfg.n_categories;
         ra.out = d_out;
         launched = launch_radial(s, c->hellinger2 && c->unit_weights && !c->tune.force_generic, ra);
+    } else if (use.weights) {
+        CategoryGradientArgs ga{};
+        ga.sw = sw;
+        ga.n_categories = c->h_cfg.n_categories;
+        ga.out = d_out;
+        launched = launch_category_gradient(s, c->h_cfg.sd_kind, c->hellinger2, ga);
     } else {
         AttributionArgs aa{};
         aa.sw = sw;
@@ -4499,6 +4511,46 @@ extern "C" int lchd_attribution_dmxs(lchd_ctx* c, const lchd_config* cfg, const 
     if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
     return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr, nullptr,
                            kAttribution, out);
+}
+
+// category-weight gradients: the attribution calls with the fourth consumer; the stores and records go to launch_category_gradient
+// (lchd_category_gradient.hip).  Hellinger and Kullback-Leibler distances.
+extern "C" int lchd_category_gradient_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
+                                                     int64_t n_pairs, double thr, double* d_out) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    lchd_cloud* const cl[2] = {a, b};
+    return consumer_primitives_dev(c, cl, d_anchors, d_wf_index, n_pairs, thr, kCategoryGradient, d_out);
+}
+extern "C" int lchd_category_gradient_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a,
+                                                 const int32_t* tag_a, int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b,
+                                                 int64_t n_b, const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr,
+                                                 const double* box_a, const double* cell_a, const double* box_b, const double* cell_b, double* out) {
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    return pair_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, box_a, cell_a, box_b,
+                                cell_b, kCategoryGradient, out);
+}
+extern "C" int lchd_category_gradient_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
+                                                 const double* cell_b, double* d_out) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    lchd_cloud* const cl[2] = {a, b};
+    const double* const cells[2] = {cell_a, cell_b};
+    return consumer_coords_dev(c, cl, d_wf_index, cells, kCategoryGradient, d_out);
+}
+extern "C" int lchd_category_gradient_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                             int64_t len_seq_b, const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b,
+                                             const int32_t* wf_index, const double* cell_a, const double* cell_b, double* out) {
+    if (int rc = coords_lengths(xyz_a, n_a, xyz_b, n_b)) return rc;
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n_a, n_a, n_b, wf_index, cell_a, cell_b,
+                           kCategoryGradient, out);
+}
+extern "C" int lchd_category_gradient_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                           int64_t len_seq_b, const double* dmx_a, const double* dmx_b, int64_t rows, int64_t cols_a,
+                                           int64_t cols_b, const int32_t* wf_index, double* out) {
+    if (rows > 0 && (!dmx_a || !dmx_b)) return fail(LCHD_EVALUE, "null pointer");
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr, nullptr,
+                           kCategoryGradient, out);
 }
 
 // neighbour sensitivities: every statistical distance.  The thresholded pass is the attribution call's with the indexed lists (built from

@@ -454,6 +454,16 @@ struct AttributionArgs {
 // false: nothing launched (more than kAttributionMaxCategories categories, 16-bit category stores)
 bool launch_attribution(hipStream_t s, bool exponent2, bool unit_weights, const AttributionArgs& a);
 void init_attribution_kernels();  // per device, as init_radial_kernels
+// Category-weight gradients (lchd_category_gradient.hip): dS/dw_c of a pair's score (Hellinger and Kullback-Leibler distances), one row
+// of n_categories doubles per pair, from the stores and records an attribution call reads; at most kAttributionMaxCategories categories.
+struct CategoryGradientArgs {
+    SweepArgs sw;          // as RadialArgs::sw
+    int32_t n_categories;  // DevConfig::n_categories (the launcher sizes the LDS with it)
+    double* out;           // [n_pairs][n_categories]
+};
+// false: nothing launched (another distance, more than kAttributionMaxCategories categories, 16-bit category stores)
+bool launch_category_gradient(hipStream_t s, int sd_kind, bool exponent2, const CategoryGradientArgs& a);
+void init_category_gradient_kernels();  // per device, as init_radial_kernels
 // Neighbour sensitivities (lchd_sensitivity.hip): dS/dd of every member of a pair's two environments, and the score, from INDEXED
 // environment lists -- (distance, atom index, category) per point, ascending by (distance bits, atom index), the anchor first -- built
 // next to the scoring stores of the pass from the same cell lists and anchor records.

@@ -363,6 +363,7 @@ void init_device_kernels() {
     init_sweep_wide_kernels();
     init_radial_kernels();
     init_attribution_kernels();
+    init_category_gradient_kernels();
     init_sensitivity_kernels();
 }
 // The record pass alone, for a consumer of the pair records that is not a sweep (lchd_radial.hip): no small-pair rule is in force, no

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .api import LoCoHD, MinImageSensitivity, NativeGradient, Nearest, PeriodicSensitivity, Sensitivity, dense_cells, periodic_boxes, periodic_cells
+from .api import _CATEGORY_GRADIENT, LoCoHD, MinImageSensitivity, NativeGradient, Nearest, PeriodicSensitivity, Sensitivity, dense_cells, periodic_boxes, periodic_cells
 
 
 def last_sweep_of(ctx):
@@ -298,11 +298,12 @@ class DeviceSession:
         N.check(N.lib().lchd_radial_validate(N.dp(ed), len(ed)))
         return ed
 
-    # `ed`: the checked edges of a radial call (rows of len(ed) - 1 bins), or None: an attribution (rows of C categories)
+    # `ed`: the checked edges of a radial call (rows of len(ed) - 1 bins), None: an attribution, or _CATEGORY_GRADIENT: a category-weight
+    # gradient (rows of C categories)
     def _pair_rows(self, ed, cloud_a, cloud_b, anchors, threshold_distance, out, wf_index):
         torch = self.torch
         assert anchors.is_cuda and anchors.dtype == torch.int64 and anchors.is_contiguous()
-        p, k = anchors.shape[0], int(self._cfg.n_categories) if ed is None else len(ed) - 1
+        p, k = anchors.shape[0], int(self._cfg.n_categories) if ed is None or ed is _CATEGORY_GRADIENT else len(ed) - 1
         if out is None:
             out = torch.empty((p, k), dtype=torch.float64, device=anchors.device)
         assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= p * k
@@ -311,7 +312,9 @@ class DeviceSession:
             assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= p
             wf_ptr = C.c_void_p(wf_index.data_ptr())
         head = (self._ctx, cloud_a, cloud_b, C.c_void_p(anchors.data_ptr()), wf_ptr, p, float(threshold_distance))
-        if ed is None:
+        if ed is _CATEGORY_GRADIENT:
+            N.check(N.lib().lchd_category_gradient_primitives_dev(*head, C.c_void_p(out.data_ptr())))
+        elif ed is None:
             N.check(N.lib().lchd_attribution_primitives_dev(*head, C.c_void_p(out.data_ptr())))
         else:
             N.check(N.lib().lchd_radial_primitives_dev(*head, N.dp(ed), len(ed), C.c_void_p(out.data_ptr())))
@@ -324,7 +327,7 @@ class DeviceSession:
         pc_a = dense_cells(box_a, cell_a, 1, "box_a", "cell_a")
         pc_b = dense_cells(box_b, cell_b, 1, "box_b", "cell_b")
         torch = self.torch
-        n, k = int(N.lib().lchd_cloud_size(cloud_a)), int(self._cfg.n_categories) if ed is None else len(ed) - 1
+        n, k = int(N.lib().lchd_cloud_size(cloud_a)), int(self._cfg.n_categories) if ed is None or ed is _CATEGORY_GRADIENT else len(ed) - 1
         if out is None:
             out = torch.empty((n, k), dtype=torch.float64, device=torch.device("cuda", self.device))
         assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= n * k
@@ -333,7 +336,9 @@ class DeviceSession:
             assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= n
             wf_ptr = C.c_void_p(wf_index.data_ptr())
         head = (self._ctx, cloud_a, cloud_b, wf_ptr, N.dp(pc_a), N.dp(pc_b))
-        if ed is None:
+        if ed is _CATEGORY_GRADIENT:
+            N.check(N.lib().lchd_category_gradient_coords_dev(*head, C.c_void_p(out.data_ptr())))
+        elif ed is None:
             N.check(N.lib().lchd_attribution_coords_dev(*head, C.c_void_p(out.data_ptr())))
         else:
             N.check(N.lib().lchd_radial_coords_dev(*head, N.dp(ed), len(ed), C.c_void_p(out.data_ptr())))
@@ -357,6 +362,33 @@ class DeviceSession:
         anchors: torch int64 CUDA tensor [P][2]; wf_index: torch int32 CUDA tensor [P] or None; returns (or fills) a torch float64
         CUDA tensor [P][C] (lchd_attribution_primitives_dev)."""
         return self._pair_rows(None, cloud_a, cloud_b, anchors, threshold_distance, out, wf_index)
+
+    def category_gradient(self, cloud_a, cloud_b, anchors, threshold_distance: float, out=None, wf_index=None):
+        """Category-weight gradients dS/dw_c (LoCoHD.category_gradient_from_primitives) of anchor pairs of two uploaded clouds of any
+        kind, at the session's current category weights (set_category_weights).  anchors: torch int64 CUDA tensor [P][2]; wf_index: torch
+        int32 CUDA tensor [P] or None; returns (or fills) a torch float64 CUDA tensor [P][C] (lchd_category_gradient_primitives_dev)."""
+        return self._pair_rows(_CATEGORY_GRADIENT, cloud_a, cloud_b, anchors, threshold_distance, out, wf_index)
+
+    def category_gradient_coords(self, cloud_a, cloud_b, out=None, wf_index=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None):
+        """Category-weight gradients of the dense row pairs of two uploaded structures of equal size
+        (LoCoHD.category_gradient_from_coords): returns (or fills) a torch float64 CUDA tensor [n][C]
+        (lchd_category_gradient_coords_dev)."""
+        return self._pair_rows_coords(_CATEGORY_GRADIENT, cloud_a, cloud_b, out, wf_index, box_a, box_b, cell_a, cell_b)
+
+    def set_category_weights(self, weights):
+        """Replace the category weights of the session's configuration (lchd_ctx_set_config with everything else unchanged): every later
+        call of the session scores and differentiates with them, until they are set again.  `weights`: C positive values (a sequence, an
+        array or a torch tensor), validated as the LoCoHD constructor validates them (ValueError); also ValueError while an asynchronous
+        pass is pending.  Uploaded clouds stay valid: they hold no weights.  The LoCoHD object the session was made from keeps its own."""
+        if hasattr(weights, "detach"):
+            weights = weights.detach().cpu().numpy()
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        n_cat = int(self._cfg.n_categories)
+        N.check(N.lib().lchd_config_validate(n_cat, n_cat, N.dp(w), w.size))
+        cfg = N.ConfigC.from_buffer_copy(self._cfg)  # (its other pointers stay alive in self._keep)
+        cfg.category_weights = N.dp(w)
+        N.check(N.lib().lchd_ctx_set_config(self._ctx, C.byref(cfg)))
+        self._cfg, self._weights = cfg, w
 
     def sensitivity(self, cloud_a, cloud_b, anchors, threshold_distance: float, out=None, wf_index=None, *, width=None):
         """Neighbour sensitivities (LoCoHD.sensitivity_from_primitives) of anchor pairs of two uploaded structures or batches (no image
