@@ -12,12 +12,9 @@
 // the CDF routine that wrote the keys (cdf_lean, + 0.0, running maximum: k_env_key_sets), so a point at distance exactly e_k has
 // key == E_k bit for bit.  No CDF is evaluated per event.
 //
-// Shape: the many-category sweep's (lchd_sweep_wide.hip).  One pair per wavefront; tiles of kSweepTile merged events; lane l owns
-// ceil(T / 64) consecutive events of a tile (merge path); the category counts at a lane's first event come from a wave scan of the
-// per-lane histograms (LDS columns, count_A | count_B << 16); the lane then walks its events.  Between two events H is constant: the
-// lane hands (F_lo, F_hi, H) to radial_split (lchd_radial_bins.h) with its running bin index.  A lane's intervals are: lane 0, the
-// interval the previous tile left open; then event to event; then from its last event to the FIRST event of the next lane (known
-// before the walk: the smaller head of its two runs) -- so the intervals of a tile ascend with the lane, and so do the bins they add to.
+// Shape: the column-tile skeleton of lchd_pair_columns.h (pair record, LDS, tile split, histogram scan) around an event loop of its
+// own.  Between two events H is constant: the lane hands (F_lo, F_hi, H) to radial_split (lchd_radial_bins.h) with its running bin
+// index.  The intervals of a tile ascend with the lane (the skeleton's interval rule), and so do the bins they add to.
 // Sums (no floating-point atomics, a fixed shape for a stored pair):
 //   a bin strictly between the first and the last bin a lane adds to in a tile is that lane's alone in the tile: plain adds to acc[k]
 //   the first and the last bin of a lane may be shared with its neighbours: kept in registers, and after the walk every bin that occurs
@@ -25,13 +22,12 @@
 //   the tail (F(inf) - F(u_J)) * H_J is split by lane 0 after the last tile
 // Hellinger-2 with unit weights keeps the running Bhattacharyya numerator (O(1) per event, the literal form below kExactH2Below:
 // lchd_team_tile.h); every other distance, and category weights, evaluate sd_eval on the lane's counts per event.
+#include "lchd_pair_columns.h"
 #include "lchd_radial_bins.h"
-#include "lchd_sweep_common.h"
 
 namespace lchd {
 
 constexpr int kRadTab = kSqrtTab + 8;  // LDS square-root tables: counts 0 .. kSqrtTab (stores of at most kSqrtTab points per slot)
-constexpr int kRadDynMax = 150 * 1024;  // dynamic LDS the instantiations are allowed (+ the static tables: below the 160 KB of a CU)
 
 // StatisticalDistance::run on one lane's count column (cnt[c * 64] = count_A | count_B << 16): pmf.rs:65-83 normalises the weighted
 // counts by their sums (one reciprocal per side, as the sweeps do).  Out of line: the library's pow / log stay out of the event loop's code.
@@ -41,18 +37,14 @@ static __device__ __noinline__ double radial_sd(int kind, double p0, double p1, 
                       [&](int c) { return (w[c] * (double)(cnt[c * 64] >> 16)) * ib; }, C);
 }
 
-// Per wavefront, in dynamic LDS: two key tiles | bounds [65] | bin accumulators [64] | count columns [C][64] | carry row [C] | two category tiles
-static size_t radial_wave_bytes(int C) {
-    return ((size_t)kSweepTile * 16 + (65 + 64) * 8 + (size_t)C * 260 + (size_t)kSweepTile * 4 + 15) & ~(size_t)15;
-}
+// In front of the count columns (lchd_pair_columns.h): bounds [65] | bin accumulators [64]
+constexpr size_t kRadFront = (65 + 64) * 8;
 
 // H2U: Hellinger-2 with unit weights.  CAT16: 16-bit category ids in the store (and the 16-bit-category pair record).  TAB: both
 // stores have slots of at most kSqrtTab points, the square-root tables are read from LDS.  WPB: pairs (wavefronts) per workgroup.
 template <bool H2U, bool CAT16, bool TAB, int WPB>
 __global__ __launch_bounds__(64 * WPB) void k_radial(RadialArgs ra, int wave_bytes) {
     using CT = typename std::conditional<CAT16, uint16_t, uint8_t>::type;
-    constexpr int TILE = kSweepTile;
-    constexpr uint32_t kOneA = 1u, kOneB = 1u << 16, kMaskA = 0xFFFFu;
     extern __shared__ __attribute__((aligned(16))) unsigned char rad_smem[];
     __shared__ double t_sqrt[TAB ? kRadTab : 1], t_rsqrt[TAB ? kRadTab : 1];
     const SweepArgs& args = ra.sw;
@@ -67,16 +59,12 @@ __global__ __launch_bounds__(64 * WPB) void k_radial(RadialArgs ra, int wave_byt
         for (int k = tid; k < kRadTab; k += 64 * WPB) { t_sqrt[k] = g_sqrt[k]; t_rsqrt[k] = g_rsqrt[k]; }
         __syncthreads();
     }
-    unsigned char* const base = rad_smem + (size_t)wv * wave_bytes;
-    uint64_t* const sA = reinterpret_cast<uint64_t*>(base);
-    uint64_t* const sB = sA + TILE;
-    double* const Eb = reinterpret_cast<double*>(sB + TILE);  // [K + 1] bounds of this pair's weight function
-    double* const acc = Eb + 65;                              // [K]
-    uint32_t* const cnt0 = reinterpret_cast<uint32_t*>(acc + 64);
-    uint32_t* const cnt = cnt0 + lane;                        // this lane's column: cnt[c * 64]
-    uint32_t* const carry = cnt0 + (size_t)C * 64;            // per category: counts before the current tile
-    uint16_t* const cA = reinterpret_cast<uint16_t*>(carry + C);
-    uint16_t* const cB = cA + TILE;
+    const ColumnLds l = column_carve(rad_smem + (size_t)wv * wave_bytes, C, kRadFront);
+    const uint64_t *const sA = l.sA, *const sB = l.sB;
+    const uint16_t *const cA = l.cA, *const cB = l.cB;
+    double* const Eb = reinterpret_cast<double*>(l.front);  // [K + 1] bounds of this pair's weight function
+    double* const acc = Eb + 65;                            // [K]
+    uint32_t* const cnt = l.cnt0 + lane;                    // this lane's column: cnt[c * 64]
     auto sqrt_cnt = [&](int k) -> double { if constexpr (TAB) return t_sqrt[k]; else return g_sqrt[k]; };
     auto rsqrt_cnt = [&](int k) -> double { if constexpr (TAB) return t_rsqrt[k]; else return g_rsqrt[k]; };
 
@@ -87,20 +75,13 @@ __global__ __launch_bounds__(64 * WPB) void k_radial(RadialArgs ra, int wave_byt
     const int64_t pstride = (int64_t)gridDim.x * WPB;
     for (int64_t p = (int64_t)blockIdx.x * WPB + wv; p < args.n_pairs; p += pstride) {
         double* const out = ra.out + p * (int64_t)K;
-        const int4 m = args.meta[p];
-        const int mx = __builtin_amdgcn_readfirstlane(m.x), my = __builtin_amdgcn_readfirstlane(m.y);
-        const int mz = __builtin_amdgcn_readfirstlane(m.z), mw = __builtin_amdgcn_readfirstlane(m.w);
-        const int nA = CAT16 ? (mz & 0xFFFF) : (mz & 0xFFFFFF), nB = CAT16 ? (mw & 0xFFFF) : (mw & 0xFFFFFF);
-        const int wfi = __builtin_amdgcn_readfirstlane(args.wf_index ? args.wf_index[p] : 0);
-        const bool bad_wf = wfi < 0 || wfi >= n_sets;
-        // anchor out of range / overflowed or empty environment (flagged where it happened), or an index outside the dictionary
-        if (nA <= 0 || nB <= 0 || nA > kRadialMaxPoints || nB > kRadialMaxPoints || bad_wf) {
-            if (bad_wf && lane == 0) sweep_report(args.hst, ST_BAD_WF);
+        const PairHead h = pair_head_load<CAT16>(args, p, n_sets, lane);
+        if (!h.usable) {
             for (int k = lane; k < K; k += 64) out[k] = nan("");
             continue;
         }
-        const int64_t ea = mx, eb = my;
-        const int c0a = CAT16 ? ((mz >> 16) & 0xFFFF) : ((mz >> 24) & 255), c0b = CAT16 ? ((mw >> 16) & 0xFFFF) : ((mw >> 24) & 255);
+        const int64_t ea = h.ea, eb = h.eb;
+        const int nA = h.nA, nB = h.nB, c0a = h.c0a, c0b = h.c0b, wfi = h.wfi;
         const uint64_t* __restrict__ kA = args.env_a.key + ea * args.env_a.stride + (int64_t)wfi * args.env_a.set_stride;
         const uint64_t* __restrict__ kB = args.env_b.key + eb * args.env_b.stride + (int64_t)wfi * args.env_b.set_stride;
         const CT* __restrict__ tA = reinterpret_cast<const CT*>(args.env_a.cat) + ea * args.env_a.stride;
@@ -141,8 +122,7 @@ __global__ __launch_bounds__(64 * WPB) void k_radial(RadialArgs ra, int wave_byt
         wave_sync_lds();
         for (int k = lane; k <= K; k += 64) Eb[k] = ra.bounds[(int64_t)wfi * (K + 1) + k];
         for (int k = lane; k < K; k += 64) acc[k] = 0.0;
-        for (int c = lane; c < C; c += 64) carry[c] = (c == c0a ? kOneA : 0u) | (c == c0b ? kOneB : 0u);
-        for (int c = 0; c < C; ++c) cnt[c * 64] = (c == c0a ? kOneA : 0u) | (c == c0b ? kOneB : 0u);
+        column_seed_anchors(l, cnt, C, c0a, c0b, lane);
         if (H2U && c0a == c0b && !bad_cat) D = 1.0;
         wave_sync_lds();
         double F_carry = u2d(kA[0]);  // F(0): both anchors sit at distance 0
@@ -150,44 +130,17 @@ __global__ __launch_bounds__(64 * WPB) void k_radial(RadialArgs ra, int wave_byt
 
         const int mA = nA - 1, mB = nB - 1, M = mA + mB;  // non-anchor events
         int ia = 0, ib = 0;
-        for (int k0 = 0; k0 < M; k0 += TILE) {
-            const int T = min(TILE, M - k0);
-            const int nAt = min(TILE, mA - ia), nBt = min(TILE, mB - ib);
-            wave_sync_lds();  // previous tile fully consumed
-            for (int t = lane; t < nAt; t += 64) { sA[t] = kA[1 + ia + t]; cA[t] = tA[1 + ia + t]; }
-            for (int t = lane; t < nBt; t += 64) { sB[t] = kB[1 + ib + t]; cB[t] = tB[1 + ib + t]; }
-            wave_sync_lds();
-            const int epl = (T + 63) >> 6;
-            const int d0 = min(lane * epl, T), d1 = min(d0 + epl, T);
-            const int i1 = merge_path(sA, nAt, sB, nBt, d1);
-            int i0 = __shfl_up(i1, 1);
-            if (lane == 0) i0 = 0;
-            const int iend = __builtin_amdgcn_readlane(i1, 63);
-            const int j0 = d0 - i0, j1 = d1 - i1;
-            const int last = (T - 1) / epl;  // the last lane with events (wave-uniform)
-            const bool has = d0 < d1;
-
-            // pass 1: histogram of this lane's chunk into its column, wave scan per category
-            for (int c = 0; c < C; ++c) cnt[c * 64] = 0u;
-            for (int i = i0; i < i1; ++i) {
-                const int ct = cA[i];
-                if (ct >= C) bad_cat = true; else cnt[ct * 64] += kOneA;
-            }
-            for (int j = j0; j < j1; ++j) {
-                const int ct = cB[j];
-                if (ct >= C) bad_cat = true; else cnt[ct * 64] += kOneB;
-            }
+        for (int k0 = 0; k0 < M; k0 += kSweepTile) {
+            const ColumnTile t = column_tile_stage(l, kA, kB, tA, tB, mA, mB, M, k0, ia, ib, lane);
+            const int T = t.T, d0 = t.d0, d1 = t.d1, i0 = t.i0, i1 = t.i1, j0 = t.j0, j1 = t.j1, iend = t.iend, last = t.last;
+            const bool has = t.has;
             totA = 1 + ia + i0;
             totB = 1 + ib + j0;
             if constexpr (H2U) D = 0.0;
-            for (int c = 0; c < C; ++c) {
-                const uint32_t own = cnt[c * 64];
-                const uint32_t incl = wave_incl_scan_u32(own + (lane == 0 ? carry[c] : 0u));
-                const uint32_t excl = incl - own;
-                cnt[c * 64] = excl;
-                if (lane == 63) carry[c] = incl;
+            const bool bad_chunk = column_histogram_scan(l, cnt, t, C, lane, [&](uint32_t excl) {
                 if constexpr (H2U) D += sqrt_cnt((int)(excl & kMaskA)) * sqrt_cnt((int)(excl >> 16));
-            }
+            });
+            if (bad_chunk) bad_cat = true;
             if constexpr (H2U) { ra_ = rsqrt_cnt(totA); rb_ = rsqrt_cnt(totB); }
 
             // pass 2: this lane's events, one after the other; every interval goes through radial_split with the running bin index
@@ -293,16 +246,17 @@ void launch_radial_bounds(hipStream_t s, const DevConfig* cfg, int n_wf, const R
     k_radial_bounds<<<(n_wf + 63) / 64, 64, 0, s>>>(cfg, edges, bounds);
 }
 
+// (not launch_most_waves' rule: the width follows the category type and count, 4 x (9 KB + 260 bytes per category) fit below 65 categories)
 template <bool H2U, bool CAT16, bool TAB, int WPB>
 static void launch_radial_k(hipStream_t s, const RadialArgs& a) {
-    const size_t wb = radial_wave_bytes(a.n_categories);
+    const size_t wb = column_wave_bytes(a.n_categories, kRadFront);
     const int64_t blocks = (a.sw.n_pairs + WPB - 1) / WPB;
     k_radial<H2U, CAT16, TAB, WPB><<<(unsigned)(blocks < 8192 ? blocks : 8192), 64 * WPB, wb * WPB, s>>>(a, (int)wb);
 }
 template <bool H2U, bool TAB>
 static void launch_radial_t(hipStream_t s, const RadialArgs& a) {
     if (a.sw.env_a.cat16) launch_radial_k<H2U, true, TAB, 1>(s, a);
-    else if (a.n_categories <= 64) launch_radial_k<H2U, false, TAB, 4>(s, a);  // (4 x (9 KB + 260 bytes per category) of LDS)
+    else if (a.n_categories <= 64) launch_radial_k<H2U, false, TAB, 4>(s, a);
     else launch_radial_k<H2U, false, TAB, 1>(s, a);
 }
 bool launch_radial(hipStream_t s, bool hellinger2_unit, const RadialArgs& a) {
@@ -318,9 +272,8 @@ bool launch_radial(hipStream_t s, bool hellinger2_unit, const RadialArgs& a) {
 
 template <bool H2U, bool TAB>
 static void raise_radial_lds() {
-    const void* list[] = {reinterpret_cast<const void*>(&k_radial<H2U, true, TAB, 1>), reinterpret_cast<const void*>(&k_radial<H2U, false, TAB, 4>),
-                          reinterpret_cast<const void*>(&k_radial<H2U, false, TAB, 1>)};
-    for (const void* fn : list) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kRadDynMax);
+    raise_dynamic_lds({kernel_ptr(&k_radial<H2U, true, TAB, 1>), kernel_ptr(&k_radial<H2U, false, TAB, 4>), kernel_ptr(&k_radial<H2U, false, TAB, 1>)},
+                      kColumnDynMax);
 }
 void init_radial_kernels() {
     raise_radial_lds<false, false>();

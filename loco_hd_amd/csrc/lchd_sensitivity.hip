@@ -17,9 +17,9 @@
 //                   k_env_cells (env_dist2 / env_accepts below are those lines; tag_pair_accepted and cell_coord are lchd_kcommon.h's).
 //   k_rows_indexed  the same lists for DENSE rows (from_coords / from_dmxs): every column of row r a member, sorted by (distance bits,
 //                   column index) with no forced anchor; a dense row has no threshold, so dS/dd is the whole derivative away from ties
-//   k_sensitivity   k_attribution's shape (lchd_attribution.hip): one pair per wavefront, tiles of kSweepTile merged events (merge path
-//                   on the distance bits, A first on ties), a wave scan of the per-lane category histograms for the counts at each
-//                   lane's first event, then every lane walks its events.  Per event it evaluates H on the counts behind the event
+//   k_sensitivity   the column-tile skeleton of lchd_pair_columns.h (LDS, tile split, histogram scan; the keys are the distance bits,
+//                   A first on ties) around an event loop and a pair head of its own: the lengths come from the lists, the anchors'
+//                   categories from their first slots.  Per event it evaluates H on the counts behind the event
 //                   (sd_eval on the weighted, normalised counts: every statistical distance), has H in front of it from the previous
 //                   event -- a lane's first event takes it from the previous lane, lane 0 from the previous tile, carried like F --
 //                   and writes g to the event's slot of the pair's row of side A or B.  The same walk sums dF * H: the call returns
@@ -30,12 +30,11 @@
 //   k_sens_min_image_disp   behind k_rows_indexed + k_sensitivity on dense rows from coordinates: per member slot the displacement from
 //                   the row's atom to the member's nearest periodic image, the vector behind the minimum-image distance (see the kernel)
 #include "lchd_min_image.h"
-#include "lchd_sweep_common.h"
+#include "lchd_pair_columns.h"
 
 namespace lchd {
 
 constexpr int kIdxLdsPoints = 2048;       // k_env_indexed sorts lists of at most this many (padded) points in LDS, longer ones in place
-constexpr int kSensDynMax = 150 * 1024;   // dynamic LDS the k_sensitivity instantiations are allowed
 
 // ---- indexed environment lists -------------------------------------------------------------------------------------------------------
 __global__ void k_atom_of_pos(const uint32_t* __restrict__ pos_a, int32_t n_a, uint32_t* __restrict__ inv_a, const uint32_t* __restrict__ pos_b,
@@ -324,16 +323,9 @@ static __device__ __noinline__ double sens_sd(int kind, double p0, double p1, co
 }
 static __device__ __noinline__ double sens_pdf(int kind, const double* p, int np, double x) { return pdf_eval(kind, p, np, x); }
 
-// Per wavefront, in dynamic LDS: two key tiles | count columns [C][64] | carry row [C] | two category tiles
-static size_t sensitivity_wave_bytes(int C) {
-    return ((size_t)kSweepTile * 16 + (size_t)C * 260 + (size_t)kSweepTile * 4 + 15) & ~(size_t)15;
-}
-
 // WPB: pairs (wavefronts) per workgroup.
 template <int WPB>
 __global__ __launch_bounds__(64 * WPB) void k_sensitivity(SensitivityArgs sa, int wave_bytes) {
-    constexpr int TILE = kSweepTile;
-    constexpr uint32_t kOneA = 1u, kOneB = 1u << 16, kMaskA = 0xFFFFu;
     extern __shared__ __attribute__((aligned(16))) unsigned char sens_smem[];
     const SweepArgs& args = sa.sw;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -341,14 +333,10 @@ __global__ __launch_bounds__(64 * WPB) void k_sensitivity(SensitivityArgs sa, in
     const DevConfig* __restrict__ cfgp = args.cfg;
     const int C = cfgp->n_categories, K = sa.width;
     const double* __restrict__ cat_w = cfgp->cat_w;
-    unsigned char* const base = sens_smem + (size_t)wv * wave_bytes;
-    uint64_t* const sA = reinterpret_cast<uint64_t*>(base);
-    uint64_t* const sB = sA + TILE;
-    uint32_t* const cnt0 = reinterpret_cast<uint32_t*>(sB + TILE);
-    uint32_t* const cnt = cnt0 + lane;                        // this lane's count column: cnt[c * 64]
-    uint32_t* const carry = cnt0 + (size_t)C * 64;            // per category: counts before the current tile
-    uint16_t* const cA = reinterpret_cast<uint16_t*>(carry + C);
-    uint16_t* const cB = cA + TILE;
+    const ColumnLds l = column_carve(sens_smem + (size_t)wv * wave_bytes, C, 0);  // (nothing in front of the count columns)
+    const uint64_t *const sA = l.sA, *const sB = l.sB;
+    const uint16_t *const cA = l.cA, *const cB = l.cB;
+    uint32_t* const cnt = l.cnt0 + lane;  // this lane's count column: cnt[c * 64]
 
     const int n_wf = cfgp->n_wf;
     const int sd_kind = cfgp->sd_kind;
@@ -412,8 +400,7 @@ __global__ __launch_bounds__(64 * WPB) void k_sensitivity(SensitivityArgs sa, in
 
         // the two anchors (src/locohd.rs:82-84) in the carry row and in every lane's column
         wave_sync_lds();
-        for (int c = lane; c < C; c += 64) carry[c] = (c == c0a ? kOneA : 0u) | (c == c0b ? kOneB : 0u);
-        for (int c = 0; c < C; ++c) cnt[c * 64] = (c == c0a ? kOneA : 0u) | (c == c0b ? kOneB : 0u);
+        column_seed_anchors(l, cnt, C, c0a, c0b, lane);
         wave_sync_lds();
         double F_carry = cdf_lean(wf.kind, prm, wf.n_params, winv, 0.0) + 0.0;  // F(0): both anchors sit at distance 0
         double H_carry = bad_cat ? 0.0 : distance();
@@ -421,39 +408,11 @@ __global__ __launch_bounds__(64 * WPB) void k_sensitivity(SensitivityArgs sa, in
 
         const int mA = nA - 1, mB = nB - 1, M = mA + mB;  // non-anchor events
         int ia = 0, ib = 0;
-        for (int k0 = 0; k0 < M; k0 += TILE) {
-            const int T = min(TILE, M - k0);
-            const int nAt = min(TILE, mA - ia), nBt = min(TILE, mB - ib);
-            wave_sync_lds();  // previous tile fully consumed
-            for (int t = lane; t < nAt; t += 64) { sA[t] = kA[1 + ia + t]; cA[t] = tA[1 + ia + t]; }
-            for (int t = lane; t < nBt; t += 64) { sB[t] = kB[1 + ib + t]; cB[t] = tB[1 + ib + t]; }
-            wave_sync_lds();
-            const int epl = (T + 63) >> 6;
-            const int d0 = min(lane * epl, T), d1 = min(d0 + epl, T);
-            const int i1 = merge_path(sA, nAt, sB, nBt, d1);
-            int i0 = __shfl_up(i1, 1);
-            if (lane == 0) i0 = 0;
-            const int iend = __builtin_amdgcn_readlane(i1, 63);
-            const int j0 = d0 - i0, j1 = d1 - i1;
-            const int last = (T - 1) / epl;  // the last lane with events (wave-uniform)
-            const bool has = d0 < d1;
-
-            // pass 1: histogram of this lane's chunk into its column, wave scan per category
-            for (int c = 0; c < C; ++c) cnt[c * 64] = 0u;
-            for (int i = i0; i < i1; ++i) {
-                const int ct = cA[i];
-                if (ct >= C) bad_cat = true; else cnt[ct * 64] += kOneA;
-            }
-            for (int j = j0; j < j1; ++j) {
-                const int ct = cB[j];
-                if (ct >= C) bad_cat = true; else cnt[ct * 64] += kOneB;
-            }
-            for (int c = 0; c < C; ++c) {
-                const uint32_t own = cnt[c * 64];
-                const uint32_t incl = wave_incl_scan_u32(own + (lane == 0 ? carry[c] : 0u));
-                cnt[c * 64] = incl - own;
-                if (lane == 63) carry[c] = incl;
-            }
+        for (int k0 = 0; k0 < M; k0 += kSweepTile) {
+            const ColumnTile t = column_tile_stage(l, kA, kB, tA, tB, mA, mB, M, k0, ia, ib, lane);
+            const int T = t.T, d0 = t.d0, d1 = t.d1, i0 = t.i0, i1 = t.i1, j0 = t.j0, j1 = t.j1, iend = t.iend, last = t.last;
+            const bool has = t.has;
+            if (column_histogram_scan(l, cnt, t, C, lane, [](uint32_t) {})) bad_cat = true;
 
             // pass 2: this lane's events, one after the other
             int i = i0, j = j0;
@@ -514,18 +473,11 @@ __global__ __launch_bounds__(64 * WPB) void k_sensitivity(SensitivityArgs sa, in
 bool launch_sensitivity(hipStream_t s, const SensitivityArgs& a) {
     if (a.sw.n_pairs <= 0) return true;
     if (a.n_categories < 1 || a.n_categories > kSensitivityMaxCategories || a.width < 1) return false;
-    const size_t wb = sensitivity_wave_bytes(a.n_categories);
-    auto go = [&](auto wpb) {
+    const size_t wb = column_wave_bytes(a.n_categories, 0);
+    return launch_most_waves(kColumnDynMax, wb, a.sw.n_pairs, [&](auto wpb, unsigned grid) {
         constexpr int WPB = decltype(wpb)::value;
-        const int64_t blocks = (a.sw.n_pairs + WPB - 1) / WPB;
-        k_sensitivity<WPB><<<(unsigned)(blocks < 8192 ? blocks : 8192), 64 * WPB, wb * WPB, s>>>(a, (int)wb);
-    };
-    // the most pairs per workgroup (4, 2 or 1) whose LDS fits
-    if (wb * 4 <= (size_t)kSensDynMax) go(std::integral_constant<int, 4>{});
-    else if (wb * 2 <= (size_t)kSensDynMax) go(std::integral_constant<int, 2>{});
-    else if (wb <= (size_t)kSensDynMax) go(std::integral_constant<int, 1>{});
-    else return false;
-    return true;
+        k_sensitivity<WPB><<<grid, 64 * WPB, wb * WPB, s>>>(a, (int)wb);
+    });
 }
 
 // ---- lists that index image clouds ---------------------------------------------------------------------------------------------------
@@ -694,10 +646,8 @@ bool launch_sens_min_image_disp(hipStream_t s, const SensDispArgs& a) {
 }
 
 void init_sensitivity_kernels() {
-    const void* list[] = {reinterpret_cast<const void*>(&k_sensitivity<4>), reinterpret_cast<const void*>(&k_sensitivity<2>),
-                          reinterpret_cast<const void*>(&k_sensitivity<1>)};
-    for (const void* fn : list) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kSensDynMax);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows_indexed), hipFuncAttributeMaxDynamicSharedMemorySize, kRowsIdxLdsPoints * 12);
+    raise_dynamic_lds({kernel_ptr(&k_sensitivity<4>), kernel_ptr(&k_sensitivity<2>), kernel_ptr(&k_sensitivity<1>)}, kColumnDynMax);
+    raise_dynamic_lds({kernel_ptr(&k_rows_indexed)}, kRowsIdxLdsPoints * 12);
     (void)hipGetLastError();
 }
 

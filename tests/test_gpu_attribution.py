@@ -196,6 +196,45 @@ def test_category_counts(oracle, n_cat, all_present):
             assert np.any(got > 0.0)
 
 
+# Pairs (wavefronts) per workgroup: the most of 4, 2, 1 whose dynamic LDS fits 150 KiB = 153 600 bytes.  A wavefront takes
+# 7680 + C * (260 + 512 * columns) bytes rounded up to 16 (loco_hd_amd/csrc/lchd_pair_columns.h; columns: the f64 columns [C][64] of the
+# mode), so 4 fit up to 38 400 bytes and 2 up to 76 800:
+#   1 column  (exponent 2):       7680 + 772 C   <= 38 400  <=>  C <= 39   (39: 37 788, 40: 38 560);  C = 64 is 57 088 <= 76 800: never 1
+#   2 columns (other exponents):  7680 + 1284 C  <= 38 400  <=>  C <= 23   (23: 37 212, 24: 38 496)
+#                                                <= 76 800  <=>  C <= 53   (53: 75 732, 54: 77 016)
+WAVE_SEAMS = [(2.0, False, 39), (2.0, False, 40), (2.0, True, 39), (2.0, True, 40), (3.5, False, 23), (3.5, False, 24), (3.5, False, 53), (3.5, False, 54)]
+
+
+@pytest.mark.parametrize("e,weighted,n_cat", WAVE_SEAMS)
+def test_both_sides_of_every_pairs_per_workgroup_switch(oracle, e, weighted, n_cat):
+    """9 pairs (more than one workgroup at any width) of environments of about 40 points."""
+    lh = _lh()
+    cats = [f"k{k}" for k in range(n_cat)]
+    a, b = Cloud(700 + n_cat, 120, 14.0, cats), Cloud(800 + n_cat, 120, 14.0, cats)
+    rng = np.random.default_rng(n_cat)
+    pairs = [(int(i), int(j)) for i, j in rng.integers(0, 120, (9, 2))]
+    w = rng.uniform(0.3, 3.0, n_cat) if weighted else None
+    l = lh.LoCoHD(cats, lh.WeightFunction(*UNI), category_weights=None if w is None else list(w), statistical_distance=lh.StatisticalDistance("Hellinger", [e]))
+    got = l.attribution_from_primitives(a.atoms, b.atoms, pairs, 6.0)
+    what = f"{n_cat} categories, exponent {e}, {'weighted' if weighted else 'unit weights'}"
+    _check(got, _restated(a, b, pairs, 6.0, UNI, e, w, n_cat=n_cat), what)
+    _check(got.sum(1), _oracle_scores(oracle, cats, a, b, pairs, 6.0, UNI, e, w), "row sums against the oracle, " + what)
+    assert np.any(got > 0.0)
+
+
+def test_second_trip_of_the_pair_loop_repeats_the_first():
+    """8192 workgroups of 4 pairs cover 32 768 pairs; with 5 more the first wavefronts take a second pair.  The list is 7 pairs repeated:
+    every repetition's rows are the bytes of the first occurrence's."""
+    lh = _lh()
+    a, b = Cloud(31, 20, 7.0, CATS7), Cloud(32, 20, 7.0, CATS7)
+    short = [(int(i), int(j)) for i, j in np.random.default_rng(33).integers(0, 20, (7, 2))]
+    n = 8192 * 4 + 5
+    got = lh.LoCoHD(CATS7, lh.WeightFunction(*UNI)).attribution_from_primitives(a.atoms, b.atoms, (short * (n // 7 + 1))[:n], 6.0)
+    assert got.shape == (n, 7) and np.isfinite(got).all() and np.any(got[:7] > 0.0)
+    first = np.tile(got[:7], (n // 7 + 1, 1))[:n]
+    assert np.array_equal(got.view(np.uint8), first.view(np.uint8))
+
+
 def test_65_categories_are_refused():
     lh = _lh()
     cats = [f"k{k}" for k in range(65)]

@@ -187,6 +187,40 @@ def test_category_counts_and_unused_categories(n_cat, n_used):
         assert np.all(got == 0.0) if n_cat == 1 else np.any(got != 0.0)
 
 
+# Pairs (wavefronts) per workgroup: the most of 4, 2, 1 whose dynamic LDS fits 150 KiB = 153 600 bytes.  A wavefront takes
+# 7680 + C * (260 + 512 * columns) bytes rounded up to 16 (loco_hd_amd/csrc/lchd_pair_columns.h; columns: the f64 columns [C][64] of the
+# mode), so 4 fit up to 38 400 bytes and 2 up to 76 800:
+#   1 column  (Hellinger 2):                   7680 + 772 C   <= 38 400  <=>  C <= 39   (39: 37 788, 40: 38 560);  C = 64 is 57 088: never 1
+#   3 columns (other exponents, Kullback-L.):  7680 + 1796 C  <= 38 400  <=>  C <= 17   (17: 38 212, 18: 40 008)
+#                                                             <= 76 800  <=>  C <= 38   (38: 75 928, 39: 77 724)
+WAVE_SEAMS = [("h2", 39), ("h2", 40)] + [(d, c) for d in ("h3.5", "kl") for c in (17, 18, 38, 39)]
+
+
+@pytest.mark.parametrize("dist,n_cat", WAVE_SEAMS)
+def test_both_sides_of_every_pairs_per_workgroup_switch(dist, n_cat):
+    """9 pairs (more than one workgroup at any width) of environments of about 40 points."""
+    cats = [f"k{k}" for k in range(n_cat)]
+    a, b = Cloud(700 + n_cat, 120, 14.0, cats), Cloud(800 + n_cat, 120, 14.0, cats)
+    rng = np.random.default_rng(n_cat)
+    pairs = [(int(i), int(j)) for i, j in rng.integers(0, 120, (9, 2))]
+    weights = rng.uniform(0.3, 3.0, n_cat)
+    got = _locohd(DISTANCES[dist], weights=weights, cats=cats).category_gradient_from_primitives(a.atoms, b.atoms, pairs, 6.0)
+    _check(got, _restated(a, b, pairs, 6.0, UNI, DISTANCES[dist], weights, n_cat=n_cat), weights, f"{n_cat} categories, {dist}")
+    assert np.any(got != 0.0)
+
+
+def test_second_trip_of_the_pair_loop_repeats_the_first():
+    """8192 workgroups of 4 pairs cover 32 768 pairs; with 5 more the first wavefronts take a second pair.  The list is 7 pairs repeated:
+    every repetition's rows are the bytes of the first occurrence's."""
+    a, b = Cloud(31, 20, 7.0, CATS7), Cloud(32, 20, 7.0, CATS7)
+    short = [(int(i), int(j)) for i, j in np.random.default_rng(33).integers(0, 20, (7, 2))]
+    n = 8192 * 4 + 5
+    got = _locohd(H2, weights=WEIGHTS).category_gradient_from_primitives(a.atoms, b.atoms, (short * (n // 7 + 1))[:n], 6.0)
+    assert got.shape == (n, 7) and np.isfinite(got).all() and np.any(got[:7] != 0.0)
+    first = np.tile(got[:7], (n // 7 + 1, 1))[:n]
+    assert np.array_equal(got.view(np.uint8), first.view(np.uint8))
+
+
 def test_a_category_on_one_side_only(two_clouds, pairs40):
     a, b = two_clouds
     only_a = Cloud(103, 300, 20.0, CATS7, n_used=6)  # category 6 occurs in cloud b alone
