@@ -83,6 +83,9 @@ int lchd_wf_validate(int32_t kind, const double *params, int32_t n_params);
 int lchd_wf_cdf(int32_t kind, const double *params, int32_t n_params, const double *x, int64_t n, double *out);
 /* The density F' of the same weight function (additive): out[i] = w(x[i]); 0 for x < 0 and outside a bounded support. */
 int lchd_wf_pdf(int32_t kind, const double *params, int32_t n_params, const double *x, int64_t n, double *out);
+/* The parameter derivatives of the same weight function (additive): out[i][k] = dF/dtheta_k at x[i], k in the order of params, out
+ * row-major [n][n_params]; x<0 -> LCHD_EVALUE.  Conventions: "weight-function gradients" below. */
+int lchd_wf_cdf_grad(int32_t kind, const double *params, int32_t n_params, const double *x, int64_t n, double *out);
 /* StatisticalDistance::build validation, statistical_distances.rs:96-121 */
 int lchd_sd_validate(int32_t kind, int32_t n_params);
 /* StatisticalDistance::run, statistical_distances.rs:123-142 */
@@ -693,6 +696,56 @@ int lchd_sensitivity_coords_periodic(lchd_ctx *ctx, const lchd_config *cfg, cons
                                      const double *cell_a, const double *cell_b, int32_t width, double *scores, int32_t *count_a,
                                      int32_t *idx_a, double *dist_a, double *g_a, int32_t *count_b, int32_t *idx_b, double *dist_b,
                                      double *g_b, double *disp_a, double *disp_b);
+
+/* ---- weight-function gradients (additive, not in the reference) ------------------------------------------
+ * The derivative of a pair's score with respect to the parameters theta of the pair's weight function: how the score changes with which
+ * radii count, and how much.  The environments do not depend on the weight function, so on the piecewise-constant integrand
+ *   S           = sum_j (F(u_{j+1}) - F(u_j)) * H_j
+ *   dS/dtheta_k = sum_j (G_k(u_{j+1}) - G_k(u_j)) * H_j                                            G_k = dF/dtheta_k
+ *               = sum_members G_k(d_m) * (H- - H+) + G_k(inf) * H_last - G_k(0) * H_first          (summation by parts)
+ * with H- / H+ the statistical distance on the piece that ends / starts at the member, as for the sensitivities.  This is the
+ * derivative of the score as the scoring call computes it: no threshold caveat applies (a member entering or leaving at the threshold
+ * does not move with theta).  G_k per family, parameters in the order of lchd_weight_function::params (lchd_wf_cdf_grad evaluates it):
+ *   uniform (a, b)                 on a <= x <= b: (x - b) / (b - a)^2 and -(x - a) / (b - a)^2; 0 elsewhere
+ *   kumaraswamy (x_min, x_max, alpha, beta)   0 outside [x_min, x_max]; inside, z = (x - x_min) / L, L = x_max - x_min:
+ *                                  dF/dz = alpha beta z^(alpha-1) (1 - z^alpha)^(beta-1), dz/dx_min = -(1 - z) / L, dz/dx_max = -z / L,
+ *                                  dF/dalpha = beta (1 - z^alpha)^(beta-1) z^alpha ln z, dF/dbeta = -(1 - z^alpha)^beta ln(1 - z^alpha)
+ *   dagum (A, B, P)                t = (x / B)^-A: dF/dP = -F ln(1 + t), dF/dt = -P (1 + t)^(-P-1), dt/dA = -t ln(x / B), dt/dB = A t / B
+ *   hyper_exp (a_1..a_n, b_1..b_n) N = sum a_i: dF/da_k = ((1 - F) - e^(-b_k x)) / N, dF/db_k = a_k x e^(-b_k x) / N
+ * Conventions: x = +inf gives 0 in every family (so the G(inf) term vanishes); x = 0 gives the formula's value, 0 for a dagum; a product
+ * of the form 0 * ln 0 is 0; where the limit is infinite (kumaraswamy's bounds with alpha < 1 at z = 0 or beta < 1 at z = 1, a set of
+ * distances of measure zero) the value is 0, so every output is finite; a member exactly on a support bound of uniform / kumaraswamy
+ * takes the inside branch as the CDF does -- the derivative is one-sided there, and only there.
+ * Output: ONE block of n * (1 + NP) doubles, scores[n] | grad[n][NP] row-major, NP = the most parameters of any weight function of the
+ * configuration (lchd_weight_gradient_width once the context holds the configuration; a host call sizes `out` from its cfg).  Row p
+ * holds the derivatives with respect to the parameters of ITS weight function (wf_index[p]) in their order; the columns behind that
+ * function's n_params are exact zeros.  scores[p] is the pair's score from the same walk, bit for bit the sensitivity call's.
+ * A row and its score are NaN where the sensitivity call's rows are: an unusable pair, a category outside the configuration, a zero
+ * norm, a weight-function index outside the dictionary -- with the same status and return code.
+ * The calls are the sensitivity calls of the same name without the list outputs and without a row width (the lists are as wide as the
+ * pass needs) and with another kernel (lchd_weight_gradient.hip) behind the same pass: arguments, errors, stream and lock rules, capacity
+ * repeats and the untouched hints / lchd_ctx_last_sweep are theirs; lchd_sensitivity_needed_width is left alone.  Every statistical
+ * distance; at most 64 categories, lists of at most 65 535 points, weight functions of at most 16 parameters (more: LCHD_EUNSUPPORTED);
+ * a weight function whose F(+inf) is not 1 (a dagum with A = 0) fails with LCHD_EVALUE.  Open structures only: no boxes, cells or image
+ * clouds (LCHD_EUNSUPPORTED), and device groups have no such call.  One register accumulator per parameter and lane, reduced once per
+ * pair in lane order: no floating-point atomics, a row's bits depend on the stored pair and the configuration alone. */
+int32_t lchd_weight_gradient_width(lchd_ctx *ctx);
+/* Thresholded, device-resident (clouds as lchd_sensitivity_primitives_dev takes them); d_out DEVICE f64 [n_pairs * (1 + NP)]. */
+int lchd_weight_gradient_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors, const int32_t *d_wf_index,
+                                        int64_t n_pairs, double threshold_distance, double *d_out);
+/* The same from host arrays; out HOST [n_pairs * (1 + NP)]. */
+int lchd_weight_gradient_primitives(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a, const int32_t *tag_a,
+                                    int64_t n_a, const double *xyz_b, const int32_t *cat_b, const int32_t *tag_b, int64_t n_b,
+                                    const int64_t *anchors, const int32_t *wf_index, int64_t n_pairs, double threshold_distance, double *out);
+/* Dense rows, device-resident single structures of equal size n; d_out DEVICE [n * (1 + NP)]. */
+int lchd_weight_gradient_coords_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, double *d_out);
+/* The same from host arrays, as lchd_sensitivity_coords takes them; out HOST [n * (1 + NP)]. */
+int lchd_weight_gradient_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                                int64_t len_seq_b, const double *xyz_a, const double *xyz_b, int64_t n, const int32_t *wf_index, double *out);
+/* Given distance rows, as lchd_sensitivity_dmxs takes them; out HOST [rows * (1 + NP)]. */
+int lchd_weight_gradient_dmxs(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                              int64_t len_seq_b, const double *dmx_a, const double *dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
+                              const int32_t *wf_index, double *out);
 
 /* ---- native coordinate gradients (additive, not in the reference) ---------------------------------------
  * grad = sum_p v_p dS_p/dx over the pairs of a call, v the pair weights: the backward pass of a loss built from LoCoHD scores.  The lists

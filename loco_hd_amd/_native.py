@@ -123,6 +123,7 @@ _PROTOS = {
     "lchd_wf_validate": (C.c_int, [_i32, _DP, _i32]),
     "lchd_wf_cdf": (C.c_int, [_i32, _DP, _i32, _DP, _i64, _DP]),
     "lchd_wf_pdf": (C.c_int, [_i32, _DP, _i32, _DP, _i64, _DP]),
+    "lchd_wf_cdf_grad": (C.c_int, [_i32, _DP, _i32, _DP, _i64, _DP]),
     "lchd_sd_validate": (C.c_int, [_i32, _i32]),
     "lchd_sd_run": (C.c_int, [_i32, _DP, _DP, _DP, _i32, _DP]),
     "lchd_config_validate": (C.c_int, [_i64, _i64, _DP, _i64]),
@@ -174,6 +175,12 @@ _PROTOS = {
     "lchd_category_gradient_coords_dev": (C.c_int, [_VP, _VP, _VP, _VP, _DP, _DP, _VP]),
     "lchd_category_gradient_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _i64, _DP, _i64, _IP, _DP, _DP, _DP]),
     "lchd_category_gradient_dmxs": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _i64, _i64, _IP, _DP]),
+    "lchd_weight_gradient_width": (_i32, [_VP]),
+    "lchd_weight_gradient_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _i64, _f64, _VP]),
+    "lchd_weight_gradient_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _DP]),
+    "lchd_weight_gradient_coords_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "lchd_weight_gradient_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _IP, _DP]),
+    "lchd_weight_gradient_dmxs": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _i64, _i64, _IP, _DP]),
     "lchd_sensitivity_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _i64, _f64, _i32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lchd_sensitivity_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64, _i32,
                                               _DP, _IP, _IP, _DP, _DP, _IP, _IP, _DP, _DP]),

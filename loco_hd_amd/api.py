@@ -35,6 +35,9 @@ MinImageSensitivity = namedtuple("MinImageSensitivity", "scores count_a idx_a di
 # what the native periodic gradient calls return with strain=True (DeviceSession: the same fields as torch tensors): strain_a / strain_b are
 # the (3, 3) strain derivatives of the weighted score sum, one per side (include/loco_hd_hip.h, "the strain derivative")
 NativeGradient = namedtuple("NativeGradient", "scores grad_a grad_b strain_a strain_b")
+# what the weight-function gradient calls return (DeviceSession.weight_gradient: the same fields as torch tensors): scores (P,) and
+# grad (P, NP), row p the derivatives of pair p's score with respect to the parameters of its weight function, zero-padded to NP columns
+WeightGradient = namedtuple("WeightGradient", "scores grad")
 # what LoCoHD.nearest_from_primitives returns (DeviceSession.nearest: the same fields as torch tensors)
 Nearest = namedtuple("Nearest", "scores cols")
 
@@ -213,6 +216,14 @@ class WeightFunction:
         N.check(N.lib().lchd_wf_pdf(self._kind, N.dp(self._p), len(self._p), N.dp(x), x.size, N.dp(out)))
         return out.tolist()
 
+    def cdf_param_grad_vec(self, points: Sequence[float]) -> np.ndarray:
+        """Additive: the derivatives of the CDF with respect to the parameters, dF/dtheta_k at every point, as an (n, n_params) array
+        with columns in `parameters` order (0 at +inf; finite everywhere: include/loco_hd_hip.h, "weight-function gradients")."""
+        x = _f64(points).reshape(-1)
+        out = np.empty((x.size, len(self._p)))
+        N.check(N.lib().lchd_wf_cdf_grad(self._kind, N.dp(self._p), len(self._p), N.dp(x), x.size, N.dp(out)))
+        return out
+
     def density_point(self, point: float) -> float:
         return self.density_vec([float(point)])[0]
 
@@ -228,6 +239,18 @@ class WeightFunction:
 
     def __repr__(self) -> str:
         return f"WeightFunction({self._name!r}, {self._params!r})"
+
+
+def weight_gradient_width(w_funcs: Sequence[WeightFunction]) -> int:
+    """NP of a weight-function gradient over these functions -- the most parameters of any of them -- after the refusals of the call that
+    need no device: more than 16 parameters (NotImplementedError), a function whose F(inf) is not 1 (a degenerate dagum: ValueError)."""
+    np_max = max(len(w._p) for w in w_funcs)
+    if np_max > 16:
+        raise NotImplementedError(f"a weight-function gradient takes weight functions of at most 16 parameters (got {np_max})")
+    for w in w_funcs:
+        if w.integral_point(float("inf")) != 1.0:
+            raise ValueError(f"a weight-function gradient needs F(+inf) = 1 whatever the parameters: {w!r} is degenerate")
+    return np_max
 
 
 # Bumped by every PrimitiveAtom SETTER (not by construction): LoCoHD caches the packed form of the lists it is given and a
@@ -1000,6 +1023,83 @@ class LoCoHD:
         """Additive: the derivative of the score of every row pair `from_dmxs` would score with respect to every category weight, as a
         float64 array (rows, C)."""
         return self._pair_rows_from_dmxs(_CATEGORY_GRADIENT, seq_a, seq_b, dmx_a, dmx_b, w_func_keys)
+
+    # ---- weight-function gradients (additive) ---------------------------------------------------------------
+    # grad[p][k] = dS_p / dtheta_k, the derivative of pair p's score with respect to parameter k of the pair's weight function
+    # (include/loco_hd_hip.h, "weight-function gradients"): sum over the members of G_k(d) (H- - H+) minus G_k(0) H_first with
+    # G_k = dF/dtheta_k (WeightFunction.cdf_param_grad_vec).  Every statistical distance; open structures, one device.
+    def _weight_gradient_width(self, what: str, boxes=()) -> int:
+        """NP, the columns of a weight-gradient row, after every refusal that needs no device."""
+        if any(b is not None for b in boxes):
+            raise NotImplementedError(f"{what} takes open structures: periodic boxes and cells are not supported")
+        if self._devices is not None:
+            raise NotImplementedError("a weight-function gradient applies to one device (a device group has no such call): drop devices=[...]")
+        if len(self._weights) > 64:
+            raise NotImplementedError(f"a weight-function gradient takes at most 64 categories (got {len(self._weights)})")
+        return weight_gradient_width(list(self._w_func.values()) if isinstance(self._w_func, dict) else [self._w_func])
+
+    def weight_gradient_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                                        threshold_distance: float, *, box_a=None, box_b=None, cell_a=None, cell_b=None) -> WeightGradient:
+        """Additive: for every anchor pair `from_primitives` would score, the derivative of its score with respect to every parameter of
+        its weight function.  Returns `WeightGradient(scores (P,), grad (P, NP))` of float64 arrays: NP is the most parameters of any
+        function of `w_func`, row p holds the derivatives in the `parameters` order of pair p's function, and the columns behind its
+        parameter count are exact zeros.  This is the exact derivative of the score as computed (no threshold caveat), one-sided only
+        for a member exactly on a support bound of uniform / kumaraswamy.  At most 16 parameters (NotImplementedError); a dagum with
+        F(inf) != 1 is a ValueError; periodic boxes and cells and device groups are not supported (NotImplementedError)."""
+        np_max = self._weight_gradient_width("weight_gradient_from_primitives", (box_a, box_b, cell_a, cell_b))
+        thr = float(threshold_distance)
+        pairs, idx = self._anchor_arrays(anchor_pairs)
+        pa, pb, interner = self._packed_lists(prim_a, prim_b)
+        anchors = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        cfg, keep = self._config(interner)
+        n = len(anchors)
+        out = np.empty(n * (1 + np_max))
+        if n:
+            xa, xb = _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3)
+            N.check(N.lib().lchd_weight_gradient_primitives(self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa), N.dp(xb),
+                                                            N.ip(pb.cat), N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx), n, thr, N.dp(out)))
+        return WeightGradient(out[:n].copy(), out[n:].reshape(n, np_max).copy())
+
+    def weight_gradient_from_coords(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None, *, box_a=None,
+                                    box_b=None, cell_a=None, cell_b=None) -> WeightGradient:
+        """Additive: `weight_gradient_from_primitives` for the dense row pairs `from_coords` scores (pair r: the two structures of equal
+        size seen from their atoms r): `WeightGradient(scores (n,), grad (n, NP))`.  Open structures only."""
+        np_max = self._weight_gradient_width("weight_gradient_from_coords", (box_a, box_b, cell_a, cell_b))
+        xa, xb = self._coords(coords_a), self._coords(coords_b)
+        if len(xa) != len(xb):
+            raise ValueError(f"Expected matrices with the same length, got lengths {len(xa)} and {len(xb)}!")
+        n = len(xa)
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], n)
+        if n > 65535:
+            raise NotImplementedError(f"a weight-function gradient takes dense rows of at most 65535 points (got {n} / {n})")
+        ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
+        cfg, keep = self._config()
+        out = np.empty(n * (1 + np_max))
+        if n:
+            N.check(N.lib().lchd_weight_gradient_coords(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(xa), N.dp(xb), n,
+                                                        N.ip(idx), N.dp(out)))
+        return WeightGradient(out[:n].copy(), out[n:].reshape(n, np_max).copy())
+
+    def weight_gradient_from_dmxs(self, seq_a, seq_b, dmx_a, dmx_b, w_func_keys: Optional[Sequence[str]] = None) -> WeightGradient:
+        """Additive: `weight_gradient_from_primitives` for the row pairs `from_dmxs` scores (rectangular matrices with the same number
+        of rows): `WeightGradient(scores (rows,), grad (rows, NP))`."""
+        np_max = self._weight_gradient_width("weight_gradient_from_dmxs")
+        (ma, la), (mb, lb) = self._matrix(dmx_a), self._matrix(dmx_b)
+        if la is not None or lb is not None:
+            raise ValueError("weight_gradient_from_dmxs takes rectangular distance matrices (rows of equal length)")
+        if ma.shape[0] != mb.shape[0]:
+            raise ValueError(f"Expected matrices with the same length, got lengths {ma.shape[0]} and {mb.shape[0]}!")
+        n = ma.shape[0]
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], n)
+        if max(ma.shape[1], mb.shape[1]) > 65535:
+            raise NotImplementedError(f"a weight-function gradient takes dense rows of at most 65535 points (got {ma.shape[1]} / {mb.shape[1]})")
+        ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
+        cfg, keep = self._config()
+        out = np.empty(n * (1 + np_max))
+        if n:
+            N.check(N.lib().lchd_weight_gradient_dmxs(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(ma), N.dp(mb), n,
+                                                      ma.shape[1], mb.shape[1], N.ip(idx), N.dp(out)))
+        return WeightGradient(out[:n].copy(), out[n:].reshape(n, np_max).copy())
 
     # ---- neighbour sensitivities and coordinate gradients (additive) ---------------------------------------
     # g = dS/dd = w(d) (H- - H+) for every member of the pair's two environments (include/loco_hd_hip.h, "neighbour sensitivities"): which

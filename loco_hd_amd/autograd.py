@@ -29,6 +29,12 @@ DeviceSession.gradient_images (side_gradient_images).
 Two fixed uploaded clouds, differentiable with respect to the category weights: forward is DeviceSession.set_category_weights and
 DeviceSession.from_primitives, backward one DeviceSession.category_gradient call.  The session keeps the last weights set.
 
+    scores = locohd_scores_wf(session, cloud_a, cloud_b, anchors, threshold_distance, wf_params)
+
+Two fixed uploaded clouds, differentiable with respect to the parameters of the session's single weight function: forward is
+DeviceSession.set_weight_function and DeviceSession.from_primitives, backward one DeviceSession.weight_gradient call.  The session keeps
+the last parameters set.
+
 The two periodic forms take `native=True` as well: forward and backward are then one DeviceSession.native_gradient_images /
 native_gradient_coords_periodic call each, backward with grad_output as the pair weights.  Boxes and cells stay non-differentiable.
 """
@@ -308,3 +314,33 @@ def locohd_scores_weighted(session, cloud_a, cloud_b, anchors, threshold_distanc
     Coordinates are not differentiated here.  The session keeps the last weights set: later calls of the session score with them, and a
     backward call puts the weights of its forward call back first."""
     return _LoCoHDScoresWeighted.apply(category_weights, session, cloud_a, cloud_b, anchors, float(threshold_distance), wf_index)
+
+
+class _LoCoHDScoresWf(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, wf_params, session, cloud_a, cloud_b, anchors, threshold_distance):
+        prm = wf_params.detach()
+        session.set_weight_function(prm)
+        ctx.session, ctx.clouds, ctx.anchors, ctx.thr = session, (cloud_a, cloud_b), anchors, threshold_distance
+        ctx.save_for_backward(prm)
+        return session.from_primitives(cloud_a, cloud_b, anchors, threshold_distance)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (prm,) = ctx.saved_tensors
+        session = ctx.session
+        session.set_weight_function(prm)  # (a no-op unless the session's parameters were set again since forward)
+        grad = session.weight_gradient(ctx.clouds[0], ctx.clouds[1], ctx.anchors, ctx.thr).grad
+        grad_prm = (grad * grad_output.to(grad.dtype)[:, None]).sum(0)
+        return grad_prm.to(device=prm.device, dtype=prm.dtype), None, None, None, None, None
+
+
+def locohd_scores_wf(session, cloud_a, cloud_b, anchors, threshold_distance, wf_params):
+    """The scores of the anchor pairs (torch int64 CUDA tensor [P][2]) of two clouds uploaded to `session`, differentiable with respect
+    to `wf_params`, a float64 tensor of the parameters of the session's single weight function (on any device) that may require grad.
+    Forward sets the parameters (DeviceSession.set_weight_function) and scores (DeviceSession.from_primitives); backward is one
+    DeviceSession.weight_gradient call, returning (grad * grad_output[:, None]).sum(0).  Every statistical distance; a single weight
+    function only (a dictionary is a ValueError).  Coordinates and category weights are not differentiated here.  The session keeps the
+    last parameters set: later calls of the session score with them, and a backward call puts the parameters of its forward call back
+    first."""
+    return _LoCoHDScoresWf.apply(wf_params, session, cloud_a, cloud_b, anchors, float(threshold_distance))

@@ -101,6 +101,17 @@ extern "C" int lchd_wf_pdf(int32_t kind, const double* p, int32_t np, const doub
     return LCHD_OK;
 }
 
+// the parameter derivatives dF/dtheta_k of the same function (additive: lchd_math.h, cdf_param_grad); out: [n][n_params]
+extern "C" int lchd_wf_cdf_grad(int32_t kind, const double* p, int32_t np, const double* x, int64_t n, double* out) {
+    if (int rc = lchd_wf_validate(kind, p, np)) return rc;
+    if (n > 0 && (!x || !out)) return fail(LCHD_EVALUE, "null pointer");
+    for (int64_t i = 0; i < n; ++i) {
+        if (x[i] < 0.0) return fail(LCHD_EVALUE, "Invalid input value: %g. All values must be non-negative!", x[i]);
+        cdf_param_grad(kind, p, np, x[i], out + i * (int64_t)np);
+    }
+    return LCHD_OK;
+}
+
 extern "C" int lchd_sd_validate(int32_t kind, int32_t np) {  // statistical_distances.rs:96-121
     static const int want[4] = {1, 0, 1, 2};
     static const char* names[4] = {"Hellinger", "Kolmogorov-Smirnov", "Kullback-Leibler", "Renyi"};
@@ -239,6 +250,8 @@ struct lchd_ctx {
     bool cfg_set = false;
     bool hellinger2 = false, unit_weights = false, wf_pow = false;  // which sweep kernel variant applies
     bool finf_differ = false;  // the weight functions of a dictionary do not share F(+inf) (degenerate parameters): no key sets
+    int wf_np_max = 0;         // the most parameters of any weight function of the configuration: the row width of a weight-function gradient
+    bool wf_finf_off = false;  // a weight function's F(+inf) is not 1 (a degenerate dagum): no weight-function gradient
     int sd_fast = 0;  // Kullback-Leibler (1) / Renyi (2) with parameters the O(1)-per-event sweep handles (lchd_sweep_inc.hip)
     DevConfig h_cfg{};
     DevConfig* d_cfg = nullptr;
@@ -771,6 +784,12 @@ extern "C" int lchd_ctx_set_config(lchd_ctx* c, const lchd_config* cfg) {
         }
         // Kolmogorov-Smirnov on unit weights: max_c |a_c N_b - b_c N_a| / (N_a N_b) on integer counts (the KSM team sweep)
         if (cfg->sd_kind == LCHD_SD_KOLMOGOROV_SMIRNOV) c->sd_fast = 3;
+    }
+    c->wf_np_max = 0;
+    c->wf_finf_off = false;
+    for (int i = 0; i < cfg->n_weight_functions; ++i) {
+        c->wf_np_max = std::max(c->wf_np_max, (int)cfg->weight_functions[i].n_params);
+        c->wf_finf_off = c->wf_finf_off || !(finf[i] == 1.0);
     }
     c->wf_pow = false;
     for (int i = 0; i < cfg->n_weight_functions; ++i)
@@ -3783,6 +3802,8 @@ struct PairConsumer {
                         // of image clouds to source atoms (image and disp outputs); kSensMinImage launch_sens_min_image_disp on dense rows
                         // from coordinates (disp outputs alone)
     bool weights;       // a category-weight gradient: the attribution call's pass and row, the other kernel (lchd_category_gradient.hip)
+    bool wgrad;         // a weight-function gradient: the sensitivity call's pass and lists (width = the longest list there is: none is too
+                        // long for it), the other kernel (lchd_weight_gradient.hip) and rows of 1 + lchd_ctx::wf_np_max doubles
 };
 enum { kSensPlain = 0, kSensImages = 1, kSensMinImage = 2 };
 static const PairConsumer kComposition{{}, "a composition profile", "composition", "anchors", 1, false};
@@ -3799,6 +3820,12 @@ static PairConsumer sensitivity_consumer(int32_t width, const SensitivityOut& ou
     use.width = width;
     use.sens = out;
     use.resolve = resolve;
+    return use;
+}
+static PairConsumer weight_gradient_consumer() {
+    PairConsumer use{{}, "a weight-function gradient", "weight gradient", "anchor pairs", 2, true};
+    use.width = kRadialMaxPoints;
+    use.wgrad = true;
     return use;
 }
 // doubles per pair of a sensitivity call's block: the nine arrays, behind them the two disp rows of a call that resolves, and behind
@@ -3821,6 +3848,7 @@ static SensitivityOut sens_carve(double* blk, int64_t n, int w, int resolve = kS
 }
 // doubles per entry in the consumer's output: the bins / the categories of the context's configuration / a sensitivity call's block
 static size_t consumer_row(const lchd_ctx* c, const PairConsumer& use) {
+    if (use.wgrad) return 1 + (size_t)c->wf_np_max;  // scores[P] | grad[P][NP]
     if (use.width) return sens_row(use.width, use.resolve);
     return use.edges.n ? (size_t)use.edges.n - 1 : (size_t)c->h_cfg.n_categories;
 }
@@ -3836,6 +3864,10 @@ static int consumer_limits(const lchd_ctx* c, const PairConsumer& use) {
                     names[c->h_cfg.sd_kind & 3]);
     if (c->h_cfg.n_categories > most)
         return fail(LCHD_EUNSUPPORTED, "%s takes at most %d categories (got %d)", use.what, most, c->h_cfg.n_categories);
+    if (use.wgrad && c->wf_np_max > kWeightGradientMaxParams)
+        return fail(LCHD_EUNSUPPORTED, "%s takes weight functions of at most %d parameters (got %d)", use.what, kWeightGradientMaxParams, c->wf_np_max);
+    if (use.wgrad && c->wf_finf_off)
+        return fail(LCHD_EVALUE, "%s needs F(+inf) = 1 whatever the parameters: a degenerate dagum (A = 0) is refused", use.what);
     return LCHD_OK;
 }
 // The consumer's kernel behind a finished store build (stream order), with what hands the status over: the record pass (k_pair_meta)
@@ -3863,7 +3895,17 @@ static int consumer_enqueue(lchd_ctx* c, SweepArgs& sw, const PairConsumer& use,
     fill_sweep_args(c, sw);
     launch_pair_meta(s, sw);
     bool launched;
-    if (use.width) {
+    if (use.wgrad) {
+        WeightGradientArgs wa{};
+        wa.sw = sw;
+        wa.env_a = lists->env[0];
+        wa.env_b = lists->env[1];
+        wa.n_categories = c->h_cfg.n_categories;
+        wa.width = c->wf_np_max;
+        wa.scores = d_out;
+        wa.grad = d_out + sw.n_pairs;
+        launched = (!lists->cells || launch_env_indexed(s, *lists->cells)) && launch_weight_gradient(s, wa);
+    } else if (use.width) {
         SensitivityArgs sa{};
         sa.sw = sw;
         sa.env_a = lists->env[0];
@@ -4068,7 +4110,7 @@ static int consumer_primitives_dev(lchd_ctx* c, lchd_cloud* const* cl, const int
             const HostStatus h = *c->h_status;
             if ((f & ST_BAD_ANCHOR) || !(f & ST_ENV_OVERFLOW)) {
                 if (int rc = status_to_rc(f & ~(uint32_t)ST_ENV_OVERFLOW, DRV_PRIMS)) return rc;
-                if (use.width) {  // (the record pass publishes the longest environment among the pairs: the row width the call takes)
+                if (use.width && !use.wgrad) {  // (the record pass publishes the longest environment among the pairs: the row width the call takes)
                     c->sens_needed = (int64_t)h.max_env;
                     if (h.max_env > (uint32_t)use.width)
                         return fail(LCHD_EVALUE, "row width %d is too small: the longest environment of these pairs holds %u points (lchd_sensitivity_needed_width)",
@@ -4248,7 +4290,7 @@ static int consumer_dense_check(lchd_ctx* c, const PairConsumer& use, const int6
     bool over = false;
     for (int k = 0; k < use.sides; ++k) over = over || cols[k] > kRadialMaxPoints;
     if (!over) {
-        if (!use.width) return LCHD_OK;
+        if (!use.width || use.wgrad) return LCHD_OK;
         // every column is a member: the rows of a dense sensitivity call are as long as the longer side's
         const int64_t longest = std::max(cols[0], cols[1]);
         c->sens_needed = longest;
@@ -4731,6 +4773,55 @@ extern "C" int lchd_sensitivity_dmxs(lchd_ctx* c, const lchd_config* cfg, const 
         return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr,
                                nullptr, sensitivity_consumer(width, SensitivityOut{}, resolve), blk);
     });
+}
+
+// weight-function gradients: the sensitivity calls of the same name with the sixth consumer -- the same plan, list builders and record
+// pass, no row width from the caller (the lists are as wide as the pass needs), k_weight_gradient (lchd_weight_gradient.hip) behind them.
+// out: ONE block, scores[P] | grad[P][NP], NP = the most parameters of any weight function of the configuration
+// (lchd_weight_gradient_width once the context holds it).  Open structures only.
+extern "C" int32_t lchd_weight_gradient_width(lchd_ctx* c) { return c && c->cfg_set ? c->wf_np_max : 0; }
+static const char* const kWgradOpen = "a weight-function gradient takes the structures themselves, not periodic image clouds";
+extern "C" int lchd_weight_gradient_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors, const int32_t* d_wf_index,
+                                                   int64_t n_pairs, double thr, double* d_out) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (n_pairs > 0 && !d_out) return fail(LCHD_EVALUE, "null output pointer");
+    if (a->images || b->images) return fail(LCHD_EUNSUPPORTED, "%s", kWgradOpen);
+    lchd_cloud* const cl[2] = {a, b};
+    return consumer_primitives_dev(c, cl, d_anchors, d_wf_index, n_pairs, thr, weight_gradient_consumer(), d_out);
+}
+extern "C" int lchd_weight_gradient_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a, const int32_t* tag_a,
+                                               int64_t n_a, const double* xyz_b, const int32_t* cat_b, const int32_t* tag_b, int64_t n_b,
+                                               const int64_t* anchors, const int32_t* wf_index, int64_t n_pairs, double thr, double* out) {
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (n_pairs > 0 && !out) return fail(LCHD_EVALUE, "null output pointer");
+    return pair_primitives_host(c, cfg, xyz_a, cat_a, tag_a, n_a, xyz_b, cat_b, tag_b, n_b, anchors, wf_index, n_pairs, thr, nullptr, nullptr,
+                                nullptr, nullptr, weight_gradient_consumer(), out);
+}
+extern "C" int lchd_weight_gradient_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, double* d_out) {
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    if (a->n > 0 && !d_out) return fail(LCHD_EVALUE, "null output pointer");
+    if (a->images || b->images) return fail(LCHD_EUNSUPPORTED, "%s", kWgradOpen);
+    lchd_cloud* const cl[2] = {a, b};
+    const double* const cells[2] = {nullptr, nullptr};
+    return consumer_coords_dev(c, cl, d_wf_index, cells, weight_gradient_consumer(), d_out);
+}
+extern "C" int lchd_weight_gradient_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                           int64_t len_seq_b, const double* xyz_a, const double* xyz_b, int64_t n, const int32_t* wf_index,
+                                           double* out) {
+    if (int rc = coords_lengths(xyz_a, n, xyz_b, n)) return rc;
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (n > 0 && !out) return fail(LCHD_EVALUE, "null output pointer");
+    return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, nullptr, nullptr, n, n, n, wf_index, nullptr, nullptr,
+                           weight_gradient_consumer(), out);
+}
+extern "C" int lchd_weight_gradient_dmxs(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                         int64_t len_seq_b, const double* dmx_a, const double* dmx_b, int64_t rows, int64_t cols_a, int64_t cols_b,
+                                         const int32_t* wf_index, double* out) {
+    if (rows > 0 && (!dmx_a || !dmx_b)) return fail(LCHD_EVALUE, "null pointer");
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (rows > 0 && !out) return fail(LCHD_EVALUE, "null output pointer");
+    return pair_dense_host(c, cfg, seq_a, len_seq_a, seq_b, len_seq_b, nullptr, nullptr, dmx_a, dmx_b, rows, cols_a, cols_b, wf_index, nullptr,
+                           nullptr, weight_gradient_consumer(), out);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -535,6 +535,21 @@ struct SensitivityArgs {
 };
 bool launch_sensitivity(hipStream_t s, const SensitivityArgs& a);  // false: nothing launched (more than kSensitivityMaxCategories categories)
 void init_sensitivity_kernels();  // per device, as init_radial_kernels
+// Weight-function gradients (lchd_weight_gradient.hip): dS/dtheta_k for every parameter of the pair's weight function, and the score, from
+// the indexed lists and pair records a sensitivity call reads.  Row p of grad holds the derivatives in the function's parameter order;
+// the columns behind its n_params are exact zeros.
+constexpr int kWeightGradientMaxParams = 16;  // (per-lane register accumulators: hyper_exp up to 8 components, and every other family)
+struct WeightGradientArgs {
+    SweepArgs sw;            // as SensitivityArgs::sw
+    IndexedStore env_a, env_b;
+    int32_t n_categories;    // DevConfig::n_categories (the launcher sizes the LDS with it)
+    int32_t width;           // NP: columns of a row, the most parameters of any function of the dictionary, 1 .. kWeightGradientMaxParams
+    double* scores;          // [P]
+    double* grad;            // [P][NP]
+};
+// false: nothing launched (more than kSensitivityMaxCategories categories, a width outside 1 .. kWeightGradientMaxParams)
+bool launch_weight_gradient(hipStream_t s, const WeightGradientArgs& a);
+void init_weight_gradient_kernels();  // per device, as init_radial_kernels
 // Behind launch_sensitivity on lists that index image clouds (k_sens_resolve_images): per member slot the displacement from the anchor in
 // the cloud the list indexes, the image code, and -- in place -- the source atom instead of the cloud index.
 struct SensResolveSide {

@@ -365,6 +365,7 @@ void init_device_kernels() {
     init_attribution_kernels();
     init_category_gradient_kernels();
     init_sensitivity_kernels();
+    init_weight_gradient_kernels();
 }
 // The record pass alone, for a consumer of the pair records that is not a sweep (lchd_radial.hip): no small-pair rule is in force, no
 // leftover list is kept; the counts it publishes are those of any pass.

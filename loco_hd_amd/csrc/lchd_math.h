@@ -96,6 +96,72 @@ LCHD_HD double pdf_eval(int kind, const double* p, int np, double x) {
     }
 }
 
+// The parameter derivatives G_k = dF/dtheta_k (additive, not in the reference): the analytic derivative of each CDF as written above with
+// respect to each of its parameters, in the order a WeightFunction takes them.  out[k * stride], k < np.  Conventions:
+//   x = +inf (and x < 0) gives 0 in every family: F(inf) = 1 whatever the parameters (a dagum with F(inf) != 1 is refused by the callers)
+//   x = 0 gives the formula's value; a dagum at x = 0 gives 0
+//   a product of the form 0 * ln 0 is 0
+//   where the limit is infinite -- kumaraswamy's dF/dx_min, dF/dx_max with alpha < 1 at z = 0 and with beta < 1 at z = 1, a set of
+//   distances of measure zero -- the value is 0; every other non-finite intermediate (a dagum with B = 0) gives 0 as well, so the output
+//   is finite for every parameter set lchd_wf_validate accepts
+//   a point exactly on a support bound of uniform / kumaraswamy takes the inside branch, as the CDF does: one-sided there
+LCHD_HD void cdf_param_grad_strided(int kind, const double* p, int np, double x, double* out, int stride) {
+    for (int k = 0; k < np; ++k) out[k * stride] = 0.0;
+    if (!(x >= 0.0) || x == (double)INFINITY) return;
+    switch (kind) {
+        case WF_HYPER_EXP: {  // N = sum a_i: dF/da_k = ((1 - F) - e^(-b_k x)) / N, dF/db_k = a_k x e^(-b_k x) / N
+            const int n = np / 2;
+            double norm = 0.0, sum = 0.0;
+            for (int i = 0; i < n; ++i) {
+                const double e = exp(-p[n + i] * x);
+                out[(n + i) * stride] = e;  // (kept in the slot it ends in)
+                sum += p[i] * e;
+                norm += p[i];
+            }
+            const double tail = sum / norm;  // 1 - F
+            for (int i = 0; i < n; ++i) {
+                const double e = out[(n + i) * stride];
+                out[i * stride] = (tail - e) / norm;
+                out[(n + i) * stride] = p[i] * x * e / norm;
+            }
+            break;
+        }
+        case WF_DAGUM: {  // t = (x/B)^-A: dF/dP = -F ln(1 + t), dF/dt = -P (1 + t)^(-P-1), dt/dA = -t ln(x/B), dt/dB = A t / B
+            if (x == 0.0) return;
+            const double r = x / p[1], t = pow(r, -p[0]);
+            if (!(t > 0.0) || t == (double)INFINITY) return;  // (F is 1 or 0 there and flat in every parameter)
+            const double dFdt = -p[2] * pow(1.0 + t, -p[2] - 1.0);
+            out[0] = dFdt * (-t * log(r));
+            out[stride] = dFdt * (p[0] * t / p[1]);
+            out[2 * stride] = -pow(1.0 + t, -p[2]) * log1p(t);
+            break;
+        }
+        case WF_UNIFORM: {  // on a <= x <= b: (x - b) / (b - a)^2, -(x - a) / (b - a)^2
+            if (x < p[0] || x > p[1]) return;
+            const double L = p[1] - p[0];
+            out[0] = (x - p[1]) / (L * L);
+            out[stride] = -(x - p[0]) / (L * L);
+            break;
+        }
+        default: {  // kumaraswamy, z = (x - x_min) / L: dF/dz = a b z^(a-1) (1 - z^a)^(b-1), dz/dx_min = -(1 - z) / L, dz/dx_max = -z / L,
+                    // dF/da = b (1 - z^a)^(b-1) z^a ln z, dF/db = -(1 - z^a)^b ln(1 - z^a)
+            if (x < p[0] || x > p[1]) return;
+            const double L = p[1] - p[0], z = (x - p[0]) / L, a = p[2], b = p[3];
+            const double za = pow(z, a), u = 1.0 - za;
+            const double dFdz = a * b * pow(z, a - 1.0) * pow(u, b - 1.0);
+            out[0] = dFdz * (-(1.0 - z) / L);
+            out[stride] = dFdz * (-z / L);
+            const double zlnz = (z > 0.0 && z < 1.0) ? za * log(z) : 0.0;
+            out[2 * stride] = zlnz != 0.0 ? b * pow(u, b - 1.0) * zlnz : 0.0;
+            out[3 * stride] = (u > 0.0 && u < 1.0) ? -pow(u, b) * log1p(-za) : 0.0;
+            break;
+        }
+    }
+    for (int k = 0; k < np; ++k)
+        if (!(fabs(out[k * stride]) < (double)INFINITY)) out[k * stride] = 0.0;
+}
+LCHD_HD void cdf_param_grad(int kind, const double* p, int np, double x, double* out) { cdf_param_grad_strided(kind, p, np, x, out, 1); }
+
 // statistical_distances.rs:4-10.  P1/P2 are callables c -> probability so that kernels can feed
 // register-resident state without materialising the normalised vectors (pmf.rs:78-81 does).
 template <int NMAX, class P1, class P2>

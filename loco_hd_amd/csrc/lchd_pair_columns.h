@@ -97,6 +97,14 @@ __device__ __forceinline__ void column_seed_anchors(const ColumnLds& l, uint32_t
     for (int c = 0; c < C; ++c) cnt[c * 64] = (c == c0a ? kOneA : 0u) | (c == c0b ? kOneB : 0u);
 }
 
+// StatisticalDistance::run on one lane's count column (cnt[c * 64] = count_A | count_B << 16), normalised like pmf.rs:65-83; out of line:
+// the library's pow / log stay out of the event loop's code (k_sensitivity, k_weight_gradient).
+static __device__ __noinline__ double sens_sd(int kind, double p0, double p1, const uint32_t* cnt, const double* __restrict__ w, int C, double ia,
+                                              double ib) {
+    return sd_eval<0>(kind, p0, p1, [&](int c) { return (w[c] * (double)(cnt[c * 64] & 0xFFFFu)) * ia; },
+                      [&](int c) { return (w[c] * (double)(cnt[c * 64] >> 16)) * ib; }, C);
+}
+
 // ---- one tile -----------------------------------------------------------------------------------------------------------------------------
 struct ColumnTile {
     int T;               // events of the tile

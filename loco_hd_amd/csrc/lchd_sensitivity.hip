@@ -314,13 +314,6 @@ bool launch_rows_indexed(hipStream_t s, const RowsIndexedArgs& a) {
 }
 
 // ---- the sweep -----------------------------------------------------------------------------------------------------------------------
-// StatisticalDistance::run on one lane's count column (cnt[c * 64] = count_A | count_B << 16), normalised like pmf.rs:65-83; out of line:
-// the library's pow / log stay out of the event loop's code.
-static __device__ __noinline__ double sens_sd(int kind, double p0, double p1, const uint32_t* cnt, const double* __restrict__ w, int C, double ia,
-                                              double ib) {
-    return sd_eval<0>(kind, p0, p1, [&](int c) { return (w[c] * (double)(cnt[c * 64] & 0xFFFFu)) * ia; },
-                      [&](int c) { return (w[c] * (double)(cnt[c * 64] >> 16)) * ib; }, C);
-}
 static __device__ __noinline__ double sens_pdf(int kind, const double* p, int np, double x) { return pdf_eval(kind, p, np, x); }
 
 // WPB: pairs (wavefronts) per workgroup.

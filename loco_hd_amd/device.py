@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .api import _CATEGORY_GRADIENT, LoCoHD, MinImageSensitivity, NativeGradient, Nearest, PeriodicSensitivity, Sensitivity, dense_cells, periodic_boxes, periodic_cells
+from .api import _CATEGORY_GRADIENT, LoCoHD, MinImageSensitivity, NativeGradient, Nearest, PeriodicSensitivity, Sensitivity, WeightGradient, dense_cells, periodic_boxes, periodic_cells
 
 
 def last_sweep_of(ctx):
@@ -389,6 +389,67 @@ class DeviceSession:
         cfg.category_weights = N.dp(w)
         N.check(N.lib().lchd_ctx_set_config(self._ctx, C.byref(cfg)))
         self._cfg, self._weights = cfg, w
+
+    def _weight_gradient_out(self, p, out, device):
+        """(WeightGradient of views into one block of p * (1 + NP) doubles, the block): the layout the C call writes."""
+        torch = self.torch
+        k = int(N.lib().lchd_weight_gradient_width(self._ctx))
+        if out is None:
+            out = torch.empty(p * (1 + k), dtype=torch.float64, device=device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= p * (1 + k)
+        flat = out.view(-1)
+        return WeightGradient(flat[:p], flat[p:p * (1 + k)].view(p, k)), flat
+
+    def weight_gradient(self, cloud_a, cloud_b, anchors, threshold_distance: float, out=None, wf_index=None):
+        """Weight-function gradients dS/dtheta_k (LoCoHD.weight_gradient_from_primitives) of anchor pairs of two uploaded structures or
+        batches (no image clouds), at the session's current parameters (set_weight_function).  anchors: torch int64 CUDA tensor [P][2];
+        wf_index: torch int32 CUDA tensor [P] or None; out: a float64 CUDA tensor of at least P * (1 + NP) elements or None.  Returns
+        `WeightGradient(scores [P], grad [P][NP])`, views into one block scores | grad (lchd_weight_gradient_primitives_dev)."""
+        torch = self.torch
+        assert anchors.is_cuda and anchors.dtype == torch.int64 and anchors.is_contiguous()
+        p = anchors.shape[0]
+        res, flat = self._weight_gradient_out(p, out, anchors.device)
+        wf_ptr = None
+        if wf_index is not None:
+            assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= p
+            wf_ptr = C.c_void_p(wf_index.data_ptr())
+        N.check(N.lib().lchd_weight_gradient_primitives_dev(self._ctx, cloud_a, cloud_b, C.c_void_p(anchors.data_ptr()), wf_ptr, p,
+                                                            float(threshold_distance), C.c_void_p(flat.data_ptr())))
+        return res
+
+    def weight_gradient_coords(self, cloud_a, cloud_b, out=None, wf_index=None):
+        """Weight-function gradients of the dense row pairs of two uploaded structures of equal size n
+        (LoCoHD.weight_gradient_from_coords): `WeightGradient(scores [n], grad [n][NP])` (lchd_weight_gradient_coords_dev)."""
+        torch = self.torch
+        n = int(N.lib().lchd_cloud_size(cloud_a))
+        res, flat = self._weight_gradient_out(n, out, torch.device("cuda", self.device))
+        wf_ptr = None
+        if wf_index is not None:
+            assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= n
+            wf_ptr = C.c_void_p(wf_index.data_ptr())
+        N.check(N.lib().lchd_weight_gradient_coords_dev(self._ctx, cloud_a, cloud_b, wf_ptr, C.c_void_p(flat.data_ptr())))
+        return res
+
+    def set_weight_function(self, params):
+        """Replace the parameters of the session's single weight function (lchd_ctx_set_config with everything else unchanged): every
+        later call of the session scores and differentiates with them, until they are set again.  The family and the parameter count stay;
+        `params` (a sequence, an array or a torch tensor) is validated as the WeightFunction constructor validates it (ValueError).  Also
+        ValueError for a session with a dictionary of weight functions and while an asynchronous pass is pending.  Uploaded clouds stay
+        valid: they hold no weight function.  The LoCoHD object the session was made from keeps its own."""
+        if int(self._cfg.n_weight_functions) != 1:
+            raise ValueError("set_weight_function applies to a session with a single weight function, not a dictionary")
+        if hasattr(params, "detach"):
+            params = params.detach().cpu().numpy()
+        prm = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1))
+        old = self._cfg.weight_functions[0]
+        if prm.size != int(old.n_params):
+            raise ValueError(f"set_weight_function keeps the parameter count: {int(old.n_params)} expected, got {prm.size}")
+        N.check(N.lib().lchd_wf_validate(int(old.kind), N.dp(prm), prm.size))
+        arr = (N.WeightFunctionC * 1)(N.WeightFunctionC(int(old.kind), prm.size, N.dp(prm)))
+        cfg = N.ConfigC.from_buffer_copy(self._cfg)  # (its other pointers stay alive in self._keep)
+        cfg.weight_functions = arr
+        N.check(N.lib().lchd_ctx_set_config(self._ctx, C.byref(cfg)))
+        self._cfg, self._wf = cfg, (arr, prm)
 
     def sensitivity(self, cloud_a, cloud_b, anchors, threshold_distance: float, out=None, wf_index=None, *, width=None):
         """Neighbour sensitivities (LoCoHD.sensitivity_from_primitives) of anchor pairs of two uploaded structures or batches (no image
