@@ -868,6 +868,81 @@ int lchd_gradient_coords_periodic(lchd_ctx *ctx, const lchd_config *cfg, const i
                                   const double *cell_a, const double *cell_b, const double *pair_weights, double *scores,
                                   double *grad_a, double *grad_b, double *strain_a, double *strain_b);
 
+/* ---- reduced parameter gradients (additive, not in the reference) ------------------------------------------
+ * out = sum_p v_p dS_p/dw_c and sum_p v_p dS_p/dtheta over the pairs of a call, v the pair weights: the backward pass of a loss over P
+ * pairs with respect to parameters every pair shares.  The per-pair call of the same inputs (lchd_category_gradient_* / lchd_weight_gradient_*
+ * above) produces rows row[p][0 .. W): W = n_categories for a category gradient, W = NP = lchd_weight_gradient_width for a weight gradient
+ * (next to scores[p]).  They never reach the caller; the rule that reduces them is fixed, in IEEE float64 with no contraction:
+ *
+ *     use      = !isnan(row[p][0])              (an unusable pair's row is NaN in every column)
+ *     term_k   = v_p * row[p][k]                (one multiplication; v_p = 1.0 without pair weights)
+ *     acc[b][k] += term_k                       exact: lchd_xs_add of lchd_exact_sum.h (64-bit integer atomics, order-free)
+ *     out[b][k] = lchd_xs_finish(acc[b][k])     THE correctly rounded double, once
+ *
+ *   category form   one bucket; out [n_categories].
+ *   weight form     b = wf_index[p], or 0 without an index; out [n_weight_functions][NP] row-major: row f holds sum v_p dS_p/dtheta over the
+ *                   pairs scored with function f, in that function's parameter order, exact zeros behind its n_params.  scores [n_pairs]
+ *                   as the per-pair call returns them, bit for bit.
+ *   out of range    a term that is not finite or >= 2^LCHD_GRAD_LIMIT_LOG2 in magnitude on a usable row (a NaN or infinite v_p is one such
+ *                   case) adds nothing; the call completes and then fails with LCHD_EVALUE ("parameter gradient contribution not finite or
+ *                   >= 2^63 (pair weights?)"): its scores are valid, its sums unspecified, the next call starts from clean accumulators --
+ *                   the behaviour of lchd_gradient_*.  Terms below 2^LCHD_GRAD_QUANTUM_LOG2 are cut off toward zero, as there.
+ *   pair_weights    [n_pairs] float64 or NULL (ones), for the thresholded and the dense forms.
+ * The outputs are a function of the rows and weights alone: the same bits for every tile_pairs, in default and deterministic mode, on
+ * every run -- given the same rows, which the per-pair passes produce bit-identically for every slot size.
+ * The thresholded forms walk the pair list in tiles exactly as lchd_gradient_primitives_dev does: per tile the unchanged per-pair pass
+ * into a grow-only block of the context, then the accumulation (lchd_param_sum.hip); a tile is added only after its pass has succeeded.
+ * tile_pairs: 0 = lchd_param_sum_plan on a quarter of the free device memory; > 0: that many pairs per tile, clamped to n_pairs; < 0:
+ * LCHD_EVALUE.  The dense forms are one tile.
+ * lchd_param_sum_plan: pure host arithmetic, the largest tile in 1 .. n_pairs with tile * (8 row_doubles + 20) <= budget_bytes (1 if not
+ * even one pair fits: the allocation then decides).  row_doubles is the per-pair call's row: n_categories for the category form, 1 + NP
+ * for the weight form (its score travels with the row).  The 20 bytes are what the thresholded pass holds per pair next to the row: its
+ * 16-byte pair record and a 4-byte list entry.  The formula is NOT the call's footprint: environment stores and indexed lists come on
+ * top.  They are sized by the distinct anchors of a tile, not by its pairs (these passes plan with neutral hints, so a side-B store with one
+ * slot per pair is taken only under the LCHD_PER_PAIR=1 test hook, where it adds a slot per pair below 2^22 pairs), and at 10^6 pairs of
+ * two 10 k-atom clouds they were measured at about 180 - 290 MB next to 23 - 76 MB of rows: budget for them.  n_pairs < 1, row_doubles outside 1 .. 65 or a negative budget: LCHD_EVALUE.
+ * A call of 2^31 pairs or more is LCHD_EUNSUPPORTED (the limbs' headroom): split it.
+ * Clouds, batches, boxes and cells are accepted where the per-pair form accepts them; limits, errors, status reports, stream and lock
+ * rules are those of the per-pair call of the same name (a weight-function index outside the dictionary fails the call as it fails that
+ * one); the context is held once for the whole call.  The host-array category form keeps the box_* / cell_* arguments of
+ * lchd_category_gradient_primitives; the weight forms are open structures only.  Given distance rows (dmxs) and device groups have no
+ * such call.  The calls return with their outputs complete. */
+int lchd_param_sum_plan(int64_t n_pairs, int32_t row_doubles, int64_t budget_bytes, int64_t *tile_pairs_out);
+/* Thresholded, device-resident; d_pair_weights DEVICE [n_pairs] or NULL, d_out DEVICE f64 [n_categories]. */
+int lchd_category_gradient_sum_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors,
+                                              const int32_t *d_wf_index, int64_t n_pairs, double threshold_distance,
+                                              const double *d_pair_weights, int64_t tile_pairs, double *d_out);
+/* The same from host arrays, open or periodic per side; out HOST [n_categories]. */
+int lchd_category_gradient_sum_primitives(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a,
+                                          const int32_t *tag_a, int64_t n_a, const double *xyz_b, const int32_t *cat_b, const int32_t *tag_b,
+                                          int64_t n_b, const int64_t *anchors, const int32_t *wf_index, int64_t n_pairs,
+                                          double threshold_distance, const double *box_a, const double *cell_a, const double *box_b,
+                                          const double *cell_b, const double *pair_weights, int64_t tile_pairs, double *out);
+/* Dense rows, device-resident single structures of equal size n; d_pair_weights DEVICE [n] or NULL, d_out DEVICE [n_categories]. */
+int lchd_category_gradient_sum_coords_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, const double *cell_a,
+                                          const double *cell_b, const double *d_pair_weights, double *d_out);
+/* The same from host arrays, as lchd_category_gradient_coords takes them; out HOST [n_categories]. */
+int lchd_category_gradient_sum_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                                      int64_t len_seq_b, const double *xyz_a, int64_t n_a, const double *xyz_b, int64_t n_b,
+                                      const int32_t *wf_index, const double *cell_a, const double *cell_b, const double *pair_weights,
+                                      double *out);
+/* Thresholded, device-resident; d_scores DEVICE [n_pairs], d_out DEVICE [n_weight_functions][NP]. */
+int lchd_weight_gradient_sum_primitives_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int64_t *d_anchors, const int32_t *d_wf_index,
+                                            int64_t n_pairs, double threshold_distance, const double *d_pair_weights, int64_t tile_pairs,
+                                            double *d_scores, double *d_out);
+/* The same from host arrays; scores HOST [n_pairs], out HOST [n_weight_functions][NP] (sized from cfg). */
+int lchd_weight_gradient_sum_primitives(lchd_ctx *ctx, const lchd_config *cfg, const double *xyz_a, const int32_t *cat_a, const int32_t *tag_a,
+                                        int64_t n_a, const double *xyz_b, const int32_t *cat_b, const int32_t *tag_b, int64_t n_b,
+                                        const int64_t *anchors, const int32_t *wf_index, int64_t n_pairs, double threshold_distance,
+                                        const double *pair_weights, int64_t tile_pairs, double *scores, double *out);
+/* Dense rows, device-resident single structures of equal size n; d_scores DEVICE [n]. */
+int lchd_weight_gradient_sum_coords_dev(lchd_ctx *ctx, lchd_cloud *a, lchd_cloud *b, const int32_t *d_wf_index, const double *d_pair_weights,
+                                        double *d_scores, double *d_out);
+/* The same from host arrays, as lchd_weight_gradient_coords takes them. */
+int lchd_weight_gradient_sum_coords(lchd_ctx *ctx, const lchd_config *cfg, const int32_t *seq_a, int64_t len_seq_a, const int32_t *seq_b,
+                                    int64_t len_seq_b, const double *xyz_a, const double *xyz_b, int64_t n, const int32_t *wf_index,
+                                    const double *pair_weights, double *scores, double *out);
+
 /* ---- cross-scoring (additive, not in the reference) ------------------------------------------------------
  * Every anchor of one list against every anchor of another: which environments of B look like this environment of A.
  *   cross:   out[i][j] = the score lchd_from_primitives_dev gives the pair (anchors_a[i], anchors_b[j]) -- same threshold, configuration

@@ -213,6 +213,17 @@ _PROTOS = {
     "lchd_gradient_coords_periodic_dev": (C.c_int, [_VP, _VP, _VP, _VP, _DP, _DP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "lchd_gradient_coords_periodic": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _IP, _DP, _DP, _DP, _DP, _DP,
                                                 _DP, _DP, _DP]),
+    "lchd_param_sum_plan": (C.c_int, [_i64, _i32, _i64, _LP]),
+    "lchd_category_gradient_sum_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _i64, _f64, _VP, _i64, _VP]),
+    "lchd_category_gradient_sum_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64,
+                                                        _DP, _DP, _DP, _DP, _DP, _i64, _DP]),
+    "lchd_category_gradient_sum_coords_dev": (C.c_int, [_VP, _VP, _VP, _VP, _DP, _DP, _VP, _VP]),
+    "lchd_category_gradient_sum_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _i64, _DP, _i64, _IP, _DP, _DP, _DP, _DP]),
+    "lchd_weight_gradient_sum_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _i64, _f64, _VP, _i64, _VP, _VP]),
+    "lchd_weight_gradient_sum_primitives": (C.c_int, [_VP, C.POINTER(ConfigC), _DP, _IP, _IP, _i64, _DP, _IP, _IP, _i64, _LP, _IP, _i64, _f64,
+                                                      _DP, _i64, _DP, _DP]),
+    "lchd_weight_gradient_sum_coords_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "lchd_weight_gradient_sum_coords": (C.c_int, [_VP, C.POINTER(ConfigC), _IP, _i64, _IP, _i64, _DP, _DP, _i64, _IP, _DP, _DP, _DP]),
     "lchd_cross_plan": (C.c_int, [_i64, _i64, _i64, _LP]),
     "lchd_cross_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _i64, _VP, _i64, _i32, _f64, _i64, _VP]),
     "lchd_nearest_primitives_dev": (C.c_int, [_VP, _VP, _VP, _VP, _i64, _VP, _i64, _i32, _f64, _i64, _i32, _VP, _VP]),

@@ -38,6 +38,9 @@ NativeGradient = namedtuple("NativeGradient", "scores grad_a grad_b strain_a str
 # what the weight-function gradient calls return (DeviceSession.weight_gradient: the same fields as torch tensors): scores (P,) and
 # grad (P, NP), row p the derivatives of pair p's score with respect to the parameters of its weight function, zero-padded to NP columns
 WeightGradient = namedtuple("WeightGradient", "scores grad")
+# what the reduced weight-function gradient calls return (DeviceSession.weight_gradient_sum: the same fields as torch tensors): scores (P,)
+# and grad (n_wf, NP), row f the exact sum of v_p dS_p/dtheta over the pairs scored with function f, zero-padded to NP columns
+WeightGradientSum = namedtuple("WeightGradientSum", "scores grad")
 # what LoCoHD.nearest_from_primitives returns (DeviceSession.nearest: the same fields as torch tensors)
 Nearest = namedtuple("Nearest", "scores cols")
 
@@ -1100,6 +1103,122 @@ class LoCoHD:
             N.check(N.lib().lchd_weight_gradient_dmxs(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(ma), N.dp(mb), n,
                                                       ma.shape[1], mb.shape[1], N.ip(idx), N.dp(out)))
         return WeightGradient(out[:n].copy(), out[n:].reshape(n, np_max).copy())
+
+    # ---- reduced parameter gradients (additive) --------------------------------------------------------------
+    # sum_p v_p dS_p/dw_c and sum_p v_p dS_p/dtheta in ONE native call (include/loco_hd_hip.h, "reduced parameter gradients"): the rows of
+    # the two families above never reach the host; every term v_p * row[p][k] is one float64 product, the terms of a column are summed
+    # EXACTLY (fixed point, quantum 2^-192) and rounded once.  The bits are the same for every `tile_pairs`, mode and run.
+    @staticmethod
+    def _param_sum_args(pair_weights, n: int, tile_pairs, what: str):
+        """(pair weights as a contiguous float64 array or None, tile_pairs as an int) after the refusals that need no device."""
+        if int(tile_pairs) < 0:
+            raise ValueError(f"tile_pairs = {int(tile_pairs)} is negative (0: planned from the free device memory)")
+        if pair_weights is None:
+            return None, int(tile_pairs)
+        v = np.asarray(pair_weights)
+        if v.dtype.kind not in "fiu":
+            raise ValueError(f"pair_weights must be real numbers (got dtype {v.dtype})")
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        if len(v) != n:
+            raise ValueError(f"pair_weights has {len(v)} entries for {n} {what}")
+        return v, int(tile_pairs)
+
+    def category_gradient_sum_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                                              threshold_distance: float, pair_weights=None, *, tile_pairs: int = 0, box_a=None, box_b=None,
+                                              cell_a=None, cell_b=None) -> np.ndarray:
+        """Additive: sum_p v_p dS_p/dw_c over the anchor pairs, v = `pair_weights` (default: ones), as a float64 array (C,): the rows of
+        `category_gradient_from_primitives` reduced on the device (lchd_category_gradient_sum_primitives) in tiles of `tile_pairs` pairs
+        (0: planned from the free device memory), every column the correctly rounded exact sum of its terms.  An unusable pair (a NaN row)
+        adds nothing.  ValueError if a term is not finite or reaches 2^63.  Boxes and cells as `category_gradient_from_primitives`."""
+        for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+            if box is not None and cell is not None:
+                raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
+        self._no_device_group_for_pair_rows(_CATEGORY_GRADIENT)
+        thr = float(threshold_distance)
+        ba = None if box_a is None else periodic_boxes(box_a, 1, thr, "box_a")
+        bb = None if box_b is None else periodic_boxes(box_b, 1, thr, "box_b")
+        ca = None if cell_a is None else periodic_cells(cell_a, 1, thr, "cell_a")
+        cb = None if cell_b is None else periodic_cells(cell_b, 1, thr, "cell_b")
+        pairs, idx = self._anchor_arrays(anchor_pairs)
+        anchors = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        v, tile = self._param_sum_args(pair_weights, len(anchors), tile_pairs, "anchor pairs")
+        pa, pb, interner = self._packed_lists(prim_a, prim_b)
+        cfg, keep = self._config(interner)
+        out = np.zeros(len(self._weights))
+        xa, xb = _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3)
+        N.check(N.lib().lchd_category_gradient_sum_primitives(self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa),
+                                                              N.dp(xb), N.ip(pb.cat), N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx),
+                                                              len(anchors), thr, N.dp(ba), N.dp(ca), N.dp(bb), N.dp(cb), N.dp(v), tile,
+                                                              N.dp(out)))
+        return out
+
+    def category_gradient_sum_from_coords(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None,
+                                          pair_weights=None, *, box_a=None, box_b=None, cell_a=None, cell_b=None) -> np.ndarray:
+        """Additive: `category_gradient_sum_from_primitives` for the dense row pairs `from_coords` scores: sum_r v_r dS_r/dw_c as a
+        float64 array (C,), one tile (lchd_category_gradient_sum_coords).  `box_a` / `box_b` / `cell_a` / `cell_b`: minimum-image rows."""
+        for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+            if box is not None and cell is not None:
+                raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
+        self._no_device_group_for_pair_rows(_CATEGORY_GRADIENT)
+        pc_a = dense_cells(box_a, cell_a, 1, "box_a", "cell_a")
+        pc_b = dense_cells(box_b, cell_b, 1, "box_b", "cell_b")
+        xa, xb = self._coords(coords_a), self._coords(coords_b)
+        if len(xa) != len(xb):
+            raise ValueError(f"Expected matrices with the same length, got lengths {len(xa)} and {len(xb)}!")
+        v, _ = self._param_sum_args(pair_weights, len(xa), 0, "rows")
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], len(xa))
+        ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
+        cfg, keep = self._config()
+        out = np.zeros(len(self._weights))
+        N.check(N.lib().lchd_category_gradient_sum_coords(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(xa), len(xa),
+                                                          N.dp(xb), len(xb), N.ip(idx), N.dp(pc_a), N.dp(pc_b), N.dp(v), N.dp(out)))
+        return out
+
+    def _n_weight_functions(self) -> int:
+        return len(self._w_func) if isinstance(self._w_func, dict) else 1
+
+    def weight_gradient_sum_from_primitives(self, prim_a: Sequence[PrimitiveAtom], prim_b: Sequence[PrimitiveAtom], anchor_pairs,
+                                            threshold_distance: float, pair_weights=None, *, tile_pairs: int = 0, box_a=None, box_b=None,
+                                            cell_a=None, cell_b=None) -> WeightGradientSum:
+        """Additive: `WeightGradientSum(scores (P,), grad (n_wf, NP))`: the scores of `weight_gradient_from_primitives`, bit for bit, and
+        per weight function f of `w_func` (in its order) the exact sum of v_p dS_p/dtheta over the pairs scored with f, rounded once, with
+        exact zeros behind f's parameter count (lchd_weight_gradient_sum_primitives).  v = `pair_weights` (default: ones); `tile_pairs`:
+        pairs per pass, 0 = planned from the free device memory.  ValueError if a term is not finite or reaches 2^63.  Open structures
+        on one device only; at most 16 parameters."""
+        np_max = self._weight_gradient_width("weight_gradient_sum_from_primitives", (box_a, box_b, cell_a, cell_b))
+        thr = float(threshold_distance)
+        pairs, idx = self._anchor_arrays(anchor_pairs)
+        anchors = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        n = len(anchors)
+        v, tile = self._param_sum_args(pair_weights, n, tile_pairs, "anchor pairs")
+        pa, pb, interner = self._packed_lists(prim_a, prim_b)
+        cfg, keep = self._config(interner)
+        scores, out = np.empty(n), np.zeros((self._n_weight_functions(), np_max))
+        xa, xb = _f64(pa.xyz).reshape(-1, 3), _f64(pb.xyz).reshape(-1, 3)
+        N.check(N.lib().lchd_weight_gradient_sum_primitives(self._context(), C.byref(cfg), N.dp(xa), N.ip(pa.cat), N.ip(pa.tag), len(xa), N.dp(xb),
+                                                            N.ip(pb.cat), N.ip(pb.tag), len(xb), N.lp(anchors), N.ip(idx), n, thr, N.dp(v), tile,
+                                                            N.dp(scores), N.dp(out)))
+        return WeightGradientSum(scores, out)
+
+    def weight_gradient_sum_from_coords(self, seq_a, seq_b, coords_a, coords_b, w_func_keys: Optional[Sequence[str]] = None, pair_weights=None, *,
+                                        box_a=None, box_b=None, cell_a=None, cell_b=None) -> WeightGradientSum:
+        """Additive: `weight_gradient_sum_from_primitives` for the dense row pairs `from_coords` scores:
+        `WeightGradientSum(scores (n,), grad (n_wf, NP))`, one tile (lchd_weight_gradient_sum_coords).  Open structures only."""
+        np_max = self._weight_gradient_width("weight_gradient_sum_from_coords", (box_a, box_b, cell_a, cell_b))
+        xa, xb = self._coords(coords_a), self._coords(coords_b)
+        if len(xa) != len(xb):
+            raise ValueError(f"Expected matrices with the same length, got lengths {len(xa)} and {len(xb)}!")
+        n = len(xa)
+        v, _ = self._param_sum_args(pair_weights, n, 0, "rows")
+        idx = self._wf_indices(None if w_func_keys is None else [str(k) for k in w_func_keys], n)
+        if n > 65535:
+            raise NotImplementedError(f"a weight-function gradient takes dense rows of at most 65535 points (got {n} / {n})")
+        ca, cb = self._cats(list(seq_a)), self._cats(list(seq_b))
+        cfg, keep = self._config()
+        scores, out = np.empty(n), np.zeros((self._n_weight_functions(), np_max))
+        N.check(N.lib().lchd_weight_gradient_sum_coords(self._context(), C.byref(cfg), N.ip(ca), ca.size, N.ip(cb), cb.size, N.dp(xa), N.dp(xb), n,
+                                                        N.ip(idx), N.dp(v), N.dp(scores), N.dp(out)))
+        return WeightGradientSum(scores, out)
 
     # ---- neighbour sensitivities and coordinate gradients (additive) ---------------------------------------
     # g = dS/dd = w(d) (H- - H+) for every member of the pair's two environments (include/loco_hd_hip.h, "neighbour sensitivities"): which

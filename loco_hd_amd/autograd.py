@@ -35,6 +35,9 @@ Two fixed uploaded clouds, differentiable with respect to the parameters of the 
 DeviceSession.set_weight_function and DeviceSession.from_primitives, backward one DeviceSession.weight_gradient call.  The session keeps
 the last parameters set.
 
+Both take `native=True`: backward is then one DeviceSession.category_gradient_sum / weight_gradient_sum call with grad_output as the pair
+weights, the exact sum of the terms rounded once, with no per-pair block in torch.
+
 The two periodic forms take `native=True` as well: forward and backward are then one DeviceSession.native_gradient_images /
 native_gradient_coords_periodic call each, backward with grad_output as the pair weights.  Boxes and cells stay non-differentiable.
 """
@@ -289,10 +292,11 @@ def locohd_scores_periodic(session, cloud_b_ref, xyz_a, cat_a, tag_a, anchors, t
 
 class _LoCoHDScoresWeighted(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, category_weights, session, cloud_a, cloud_b, anchors, threshold_distance, wf_index):
+    def forward(ctx, category_weights, session, cloud_a, cloud_b, anchors, threshold_distance, wf_index, native):
         w = category_weights.detach()
         session.set_category_weights(w)
         ctx.session, ctx.clouds, ctx.anchors, ctx.thr, ctx.wf_index = session, (cloud_a, cloud_b), anchors, threshold_distance, wf_index
+        ctx.native = bool(native)
         ctx.save_for_backward(w)
         return session.from_primitives(cloud_a, cloud_b, anchors, threshold_distance, wf_index=wf_index)
 
@@ -301,27 +305,33 @@ class _LoCoHDScoresWeighted(torch.autograd.Function):
         (w,) = ctx.saved_tensors
         session = ctx.session
         session.set_category_weights(w)  # (a no-op unless the session's weights were set again since forward)
-        g = session.category_gradient(ctx.clouds[0], ctx.clouds[1], ctx.anchors, ctx.thr, wf_index=ctx.wf_index)
-        grad_w = (g * grad_output.to(g.dtype)[:, None]).sum(0)
-        return grad_w.to(device=w.device, dtype=w.dtype), None, None, None, None, None, None
+        if ctx.native:  # (one call, grad_output as the pair weights: the rows never reach torch)
+            grad_w = session.category_gradient_sum(ctx.clouds[0], ctx.clouds[1], ctx.anchors, ctx.thr, grad_output, wf_index=ctx.wf_index)
+        else:
+            g = session.category_gradient(ctx.clouds[0], ctx.clouds[1], ctx.anchors, ctx.thr, wf_index=ctx.wf_index)
+            grad_w = (g * grad_output.to(g.dtype)[:, None]).sum(0)
+        return grad_w.to(device=w.device, dtype=w.dtype), None, None, None, None, None, None, None
 
 
-def locohd_scores_weighted(session, cloud_a, cloud_b, anchors, threshold_distance, category_weights, wf_index=None):
+def locohd_scores_weighted(session, cloud_a, cloud_b, anchors, threshold_distance, category_weights, wf_index=None, native=False):
     """The scores of the anchor pairs (torch int64 CUDA tensor [P][2]) of two clouds uploaded to `session`, differentiable with respect
     to `category_weights`, a float64 tensor [C] of positive values (on any device) that may require grad.  Forward sets the session's
     weights (DeviceSession.set_category_weights) and scores (DeviceSession.from_primitives); backward is one
     DeviceSession.category_gradient call, returning (G * grad_output[:, None]).sum(0).  Hellinger and Kullback-Leibler distances.
     Coordinates are not differentiated here.  The session keeps the last weights set: later calls of the session score with them, and a
-    backward call puts the weights of its forward call back first."""
-    return _LoCoHDScoresWeighted.apply(category_weights, session, cloud_a, cloud_b, anchors, float(threshold_distance), wf_index)
+    backward call puts the weights of its forward call back first.  native=True: backward is one DeviceSession.category_gradient_sum call
+    with grad_output as the pair weights -- no (P, C) block, every column the correctly rounded exact sum (its bits); forward is the same
+    either way."""
+    return _LoCoHDScoresWeighted.apply(category_weights, session, cloud_a, cloud_b, anchors, float(threshold_distance), wf_index, native)
 
 
 class _LoCoHDScoresWf(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, wf_params, session, cloud_a, cloud_b, anchors, threshold_distance):
+    def forward(ctx, wf_params, session, cloud_a, cloud_b, anchors, threshold_distance, native):
         prm = wf_params.detach()
         session.set_weight_function(prm)
         ctx.session, ctx.clouds, ctx.anchors, ctx.thr = session, (cloud_a, cloud_b), anchors, threshold_distance
+        ctx.native = bool(native)
         ctx.save_for_backward(prm)
         return session.from_primitives(cloud_a, cloud_b, anchors, threshold_distance)
 
@@ -330,17 +340,21 @@ class _LoCoHDScoresWf(torch.autograd.Function):
         (prm,) = ctx.saved_tensors
         session = ctx.session
         session.set_weight_function(prm)  # (a no-op unless the session's parameters were set again since forward)
-        grad = session.weight_gradient(ctx.clouds[0], ctx.clouds[1], ctx.anchors, ctx.thr).grad
-        grad_prm = (grad * grad_output.to(grad.dtype)[:, None]).sum(0)
-        return grad_prm.to(device=prm.device, dtype=prm.dtype), None, None, None, None, None
+        if ctx.native:  # (one call, grad_output as the pair weights; a single function: row 0 of [1][NP])
+            grad_prm = session.weight_gradient_sum(ctx.clouds[0], ctx.clouds[1], ctx.anchors, ctx.thr, grad_output).grad[0]
+        else:
+            grad = session.weight_gradient(ctx.clouds[0], ctx.clouds[1], ctx.anchors, ctx.thr).grad
+            grad_prm = (grad * grad_output.to(grad.dtype)[:, None]).sum(0)
+        return grad_prm.to(device=prm.device, dtype=prm.dtype), None, None, None, None, None, None
 
 
-def locohd_scores_wf(session, cloud_a, cloud_b, anchors, threshold_distance, wf_params):
+def locohd_scores_wf(session, cloud_a, cloud_b, anchors, threshold_distance, wf_params, native=False):
     """The scores of the anchor pairs (torch int64 CUDA tensor [P][2]) of two clouds uploaded to `session`, differentiable with respect
     to `wf_params`, a float64 tensor of the parameters of the session's single weight function (on any device) that may require grad.
     Forward sets the parameters (DeviceSession.set_weight_function) and scores (DeviceSession.from_primitives); backward is one
     DeviceSession.weight_gradient call, returning (grad * grad_output[:, None]).sum(0).  Every statistical distance; a single weight
     function only (a dictionary is a ValueError).  Coordinates and category weights are not differentiated here.  The session keeps the
     last parameters set: later calls of the session score with them, and a backward call puts the parameters of its forward call back
-    first."""
-    return _LoCoHDScoresWf.apply(wf_params, session, cloud_a, cloud_b, anchors, float(threshold_distance))
+    first.  native=True: backward is one DeviceSession.weight_gradient_sum call with grad_output as the pair weights (its bits); forward is
+    the same either way."""
+    return _LoCoHDScoresWf.apply(wf_params, session, cloud_a, cloud_b, anchors, float(threshold_distance), native)

@@ -443,6 +443,7 @@ static Tuning tuning_from_env() {  // the ONLY place that reads LCHD_* hooks (te
     t.team_batch = env_int("LCHD_TEAM_BATCH", 0);
     t.team_grid = env_int("LCHD_TEAM_GRID", 0);
     t.ensemble_block = env_int("LCHD_ENSEMBLE_BLOCK", 0);
+    t.param_sum_blocks = env_int("LCHD_PARAM_SUM_BLOCKS", 0);
     return t;
 }
 
@@ -5396,4 +5397,300 @@ extern "C" int lchd_gradient_coords_periodic(lchd_ctx* c, const lchd_config* cfg
     c->last_valid = false;
     c->pend.req.a = c->pend.req.b = nullptr;
     return t.rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// reduced parameter gradients: sum_p v_p dS_p/dw_c and sum_p v_p dS_p/dtheta (include/loco_hd_hip.h, "reduced parameter gradients")
+// ------------------------------------------------------------------------------------------------
+// The tile loop of grad_core on the rows of the category-gradient / weight-gradient calls: per tile the unchanged per-pair pass
+// (consumer_primitives_dev; dense: consumer_coords_dev, one tile) writes its rows into the context's gradient block, and
+// k_param_accumulate (lchd_param_sum.hip) adds them, times the pair weights, into exact accumulators that share the block of the
+// coordinate gradients' (status word in front, all zero between calls).  k_param_finish rounds once at the end.
+// Bytes per pair of a tile: the row block (8 row_doubles) and what the thresholded pass carves per pair next to its stores (carve_pass:
+// the 16-byte pair record and the 4-byte left-over list entry); the stores and indexed lists go with the anchors, not with the pairs.
+constexpr int64_t kParamSumPassPairBytes = 16 + 4;
+static int64_t param_sum_pair_bytes(int64_t row_doubles) { return 8 * row_doubles + kParamSumPassPairBytes; }
+static int64_t param_sum_plan_tile(int64_t n_pairs, int64_t row_doubles, int64_t budget_bytes) {
+    return std::max<int64_t>(1, std::min(budget_bytes / param_sum_pair_bytes(row_doubles), n_pairs));
+}
+extern "C" int lchd_param_sum_plan(int64_t n_pairs, int32_t row_doubles, int64_t budget_bytes, int64_t* tile_pairs_out) {
+    if (!tile_pairs_out) return fail(LCHD_EVALUE, "null output pointer");
+    *tile_pairs_out = 0;
+    if (n_pairs < 1 || row_doubles < 1 || row_doubles > kParamSumMaxWidth + 1 || budget_bytes < 0)
+        return fail(LCHD_EVALUE, "a parameter-sum plan takes n_pairs >= 1, rows of 1 .. %d doubles and a budget >= 0 (got %lld, %d, %lld)",
+                    kParamSumMaxWidth + 1, (long long)n_pairs, row_doubles, (long long)budget_bytes);
+    *tile_pairs_out = param_sum_plan_tile(n_pairs, row_doubles, budget_bytes);
+    return LCHD_OK;
+}
+
+struct ParamSumRequest {
+    bool wgrad;               // the weight form (rows scores | grad[NP], buckets = the weight functions); else the category form
+    lchd_cloud *a, *b;
+    const int64_t* anchors;   // DEVICE [n_pairs][2]; null: the dense form (pair r = row r, n_pairs = size(a))
+    const int32_t* wf;        // DEVICE or null
+    int64_t n_pairs;
+    double thr;
+    const double* cell[2];    // HOST [9] or null (the dense category form)
+    const double* weights;    // DEVICE [n_pairs] or null
+    int64_t tile_pairs;       // 0: lchd_param_sum_plan
+    double* scores;           // DEVICE [n_pairs] (the weight form)
+    double* out;              // DEVICE [C] / [n_wf][NP]
+};
+// *range (may be null): set when the call completed and then failed on an out-of-range term -- its scores are valid
+static int param_sum_core(lchd_ctx* c, const ParamSumRequest& R, bool* range = nullptr) {
+    if (range) *range = false;
+    if (!c || !R.a || !R.b) return fail(LCHD_EVALUE, "null argument");
+    const bool dense = R.anchors == nullptr;
+    if (R.tile_pairs < 0) return fail(LCHD_EVALUE, "tile_pairs = %lld is negative (0: planned from the free device memory)", (long long)R.tile_pairs);
+    if (R.n_pairs < 0) return fail(LCHD_EVALUE, "negative pair count");
+    if (!c->cfg_set) return fail(LCHD_EVALUE, "lchd_ctx_set_config has not been called");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (R.wgrad && (R.a->images || R.b->images)) return fail(LCHD_EUNSUPPORTED, "%s", kWgradOpen);
+    const PairConsumer use = R.wgrad ? weight_gradient_consumer() : kCategoryGradient;
+    if (int rc = consumer_limits(c, use)) return rc;
+    if (R.n_pairs >= kGradMaxAdds)
+        return fail(LCHD_EUNSUPPORTED, "%lld pairs exceed the 2^31 additions an exact accumulator takes: split the list", (long long)R.n_pairs);
+    const int32_t W = R.wgrad ? c->wf_np_max : c->h_cfg.n_categories, buckets = R.wgrad ? c->h_cfg.n_wf : 1;
+    const int64_t row = (int64_t)consumer_row(c, use), n_out = (int64_t)buckets * W;
+    if (!R.out || (R.wgrad && R.n_pairs > 0 && !R.scores)) return fail(LCHD_EVALUE, "null output pointer");
+    CTX_GUARD(c);
+    hipStream_t s = c->stream;
+    // the accumulators: [status word, 256 bytes] | [buckets][W][limbs]; zero between calls (the finish kernel leaves them so)
+    const size_t acc_bytes = 256 + (size_t)n_out * LCHD_GRAD_LIMBS * 8;
+    const bool grown = acc_bytes > c->grad_acc_cap;
+    if (grown) HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = grow_block(c->d_grad_acc, c->grad_acc_cap, acc_bytes)) return rc;
+    if (grown || c->grad_acc_dirty) HIP_TRY(hipMemsetAsync(c->d_grad_acc, 0, c->grad_acc_cap, s));
+    c->grad_acc_dirty = true;
+    uint32_t* const d_flag = reinterpret_cast<uint32_t*>(c->d_grad_acc);
+    int64_t* const acc = reinterpret_cast<int64_t*>(c->d_grad_acc + 256);
+
+    int64_t tile = dense ? R.n_pairs : std::min(R.tile_pairs, R.n_pairs);
+    if (!dense && R.tile_pairs == 0 && R.n_pairs > 0) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        tile = param_sum_plan_tile(R.n_pairs, row, (int64_t)(std::min<size_t>(free_b, (size_t)1 << 62) / 4));  // (the stores take theirs next to the rows)
+    }
+    lchd_cloud* const cl[2] = {R.a, R.b};
+    for (int64_t p0 = 0; p0 < R.n_pairs; p0 += tile) {
+        const int64_t tp = std::min(tile, R.n_pairs - p0);
+        const size_t rows_bytes = (size_t)tp * (size_t)row * 8;
+        if (rows_bytes > c->grad_cap) HIP_TRY(hipStreamSynchronize(s));  // (the block about to be freed may still be read)
+        if (int rc = grow_block(c->d_grad, c->grad_cap, rows_bytes)) return rc;
+        double* const blk = reinterpret_cast<double*>(c->d_grad);
+        const int32_t* const wf = R.wf ? R.wf + p0 : nullptr;
+        if (int rc = dense ? consumer_coords_dev(c, cl, wf, R.cell, use, blk)
+                           : consumer_primitives_dev(c, cl, R.anchors + 2 * p0, wf, tp, R.thr, use, blk))
+            return rc;  // (nothing of this tile has been added)
+        ParamSumArgs pa{};
+        pa.rows = R.wgrad ? blk + tp : blk;  // (the weight form's block: scores[tp] | grad[tp][NP])
+        pa.ld = W;
+        pa.weights = R.weights ? R.weights + p0 : nullptr;
+        pa.bucket = buckets > 1 ? wf : nullptr;  // (a dictionary without an index: every pair is scored with function 0, bucket 0)
+        if (R.wgrad) { pa.scores_in = blk; pa.scores_out = R.scores + p0; }
+        pa.acc = acc;
+        pa.flag = d_flag;
+        pa.n_pairs = tp;
+        pa.width = W;
+        pa.n_buckets = buckets;
+        if (!launch_param_accumulate(s, pa, c->tune.param_sum_blocks))
+            return fail(LCHD_EDEVICE, "the parameter-sum accumulation kernel rejected its launch configuration");
+        HIP_TRY(hipGetLastError());
+    }
+    if (!launch_param_finish(s, acc, n_out, R.out)) return fail(LCHD_EDEVICE, "the parameter-sum finish kernel rejected its launch configuration");
+    HIP_TRY(hipGetLastError());
+    uint32_t flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));  // the call returns with the outputs complete, as the per-pair call does
+    if (flag) HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof flag, s));
+    c->grad_acc_dirty = false;
+    if (flag && range) *range = true;
+    if (flag) return fail(LCHD_EVALUE, "parameter gradient contribution not finite or >= 2^63 (pair weights?)");
+    return LCHD_OK;
+}
+
+static const int64_t kNoPairs[2] = {0, 0};  // (a non-null list marks the thresholded form; with no pairs it is never read)
+extern "C" int lchd_category_gradient_sum_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors,
+                                                         const int32_t* d_wf_index, int64_t n_pairs, double thr, const double* d_pair_weights,
+                                                         int64_t tile_pairs, double* d_out) {
+    CTX_LOCK(c);
+    if (n_pairs > 0 && !d_anchors) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    return param_sum_core(c, ParamSumRequest{false, a, b, d_anchors ? d_anchors : kNoPairs, d_wf_index, n_pairs, thr, {nullptr, nullptr},
+                                             d_pair_weights, tile_pairs, nullptr, d_out});
+}
+extern "C" int lchd_category_gradient_sum_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index, const double* cell_a,
+                                                     const double* cell_b, const double* d_pair_weights, double* d_out) {
+    CTX_LOCK(c);
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    return param_sum_core(c, ParamSumRequest{false, a, b, nullptr, d_wf_index, a->n, 0.0, {cell_a, cell_b}, d_pair_weights, 0, nullptr, d_out});
+}
+extern "C" int lchd_weight_gradient_sum_primitives_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int64_t* d_anchors,
+                                                       const int32_t* d_wf_index, int64_t n_pairs, double thr, const double* d_pair_weights,
+                                                       int64_t tile_pairs, double* d_scores, double* d_out) {
+    CTX_LOCK(c);
+    if (n_pairs > 0 && !d_anchors) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    return param_sum_core(c, ParamSumRequest{true, a, b, d_anchors ? d_anchors : kNoPairs, d_wf_index, n_pairs, thr, {nullptr, nullptr},
+                                             d_pair_weights, tile_pairs, d_scores, d_out});
+}
+extern "C" int lchd_weight_gradient_sum_coords_dev(lchd_ctx* c, lchd_cloud* a, lchd_cloud* b, const int32_t* d_wf_index,
+                                                   const double* d_pair_weights, double* d_scores, double* d_out) {
+    CTX_LOCK(c);
+    if (!c || !a || !b) return fail(LCHD_EVALUE, "null argument");
+    return param_sum_core(c, ParamSumRequest{true, a, b, nullptr, d_wf_index, a->n, 0.0, {nullptr, nullptr}, d_pair_weights, 0, d_scores, d_out});
+}
+
+// The host-array forms: the structures as temporary clouds (a periodic side of the thresholded category form replaced by its image
+// cloud, as lchd_category_gradient_primitives does); the list, the weights and the outputs in one temporary device block.
+struct ParamSumHostArrays {
+    bool wgrad;
+    const int64_t* anchors;   // null: the dense form
+    const int32_t* wf;
+    const double* weights;
+    int64_t n_pairs;
+    double thr;
+    const double* cell[2];
+    int64_t tile_pairs;
+    double *scores, *out;     // HOST
+};
+static int param_sum_host(lchd_ctx* c, HostTemps& t, const ParamSumHostArrays& H) {
+    const size_t P = (size_t)H.n_pairs;
+    const size_t n_out = H.wgrad ? (size_t)c->h_cfg.n_wf * (size_t)c->wf_np_max : (size_t)c->h_cfg.n_categories;
+    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t o_wf = up(H.anchors ? 16 * P : 0), o_w = up(o_wf + (H.wf ? 4 * P : 0)), o_sc = up(o_w + (H.weights ? 8 * P : 0)),
+                 o_out = up(o_sc + (H.wgrad ? 8 * P : 0)), total = o_out + 8 * n_out;
+    if (hipMalloc(&t.d_blk, total ? total : 256) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(LCHD_EUNSUPPORTED, "no device memory for the %zu bytes of lists and outputs of this call", total);
+    }
+    if (H.anchors && P) HIP_TRY(hipMemcpy(t.d_blk, H.anchors, 16 * P, hipMemcpyHostToDevice));
+    if (H.wf && P) HIP_TRY(hipMemcpy(t.d_blk + o_wf, H.wf, 4 * P, hipMemcpyHostToDevice));
+    if (H.weights && P) HIP_TRY(hipMemcpy(t.d_blk + o_w, H.weights, 8 * P, hipMemcpyHostToDevice));
+    const ParamSumRequest R{H.wgrad, t.clouds[0], t.clouds[1],
+                            H.anchors ? (P ? reinterpret_cast<const int64_t*>(t.d_blk) : kNoPairs) : nullptr,
+                            H.wf ? reinterpret_cast<const int32_t*>(t.d_blk + o_wf) : nullptr, H.n_pairs, H.thr, {H.cell[0], H.cell[1]},
+                            H.weights ? reinterpret_cast<const double*>(t.d_blk + o_w) : nullptr, H.tile_pairs,
+                            reinterpret_cast<double*>(t.d_blk + o_sc), reinterpret_cast<double*>(t.d_blk + o_out)};
+    bool range = false;  // (an out-of-range term fails the call behind complete outputs: the scores are valid and go back)
+    const int rc = param_sum_core(c, R, &range);
+    if (rc == LCHD_OK || range) {
+        const std::string msg = g_err;
+        if (H.wgrad && P) HIP_TRY(hipMemcpy(H.scores, t.d_blk + o_sc, 8 * P, hipMemcpyDeviceToHost));
+        if (n_out) HIP_TRY(hipMemcpy(H.out, t.d_blk + o_out, 8 * n_out, hipMemcpyDeviceToHost));
+        if (rc) snprintf(g_err, sizeof g_err, "%s", msg.c_str());
+    }
+    return rc;
+}
+// the thresholded host forms, with the checks of consumer_primitives_host in its order
+static int param_sum_primitives_host(lchd_ctx* c, const lchd_config* cfg, bool wgrad, const ProfilePrimsSide* sd, const int64_t* anchors,
+                                     const int32_t* wf_index, int64_t n_pairs, double thr, const double* pair_weights, int64_t tile_pairs,
+                                     double* scores, double* out) {
+    CTX_LOCK(c);
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (tile_pairs < 0) return fail(LCHD_EVALUE, "tile_pairs = %lld is negative (0: planned from the free device memory)", (long long)tile_pairs);
+    if (n_pairs < 0) return fail(LCHD_EVALUE, "negative pair count");
+    for (int k = 0; k < 2; ++k)
+        if (sd[k].box && sd[k].cell)
+            return fail(LCHD_EVALUE, "a box and a cell were both given: a structure has one periodic box or one periodic cell");
+    if (int rc = check_wf_index(cfg, wf_index, n_pairs)) return rc;
+    for (int k = 0; k < 2; ++k)
+        if (sd[k].n < 0 || sd[k].n > ((int64_t)1 << 27)) return fail(LCHD_EUNSUPPORTED, "structure size out of range");
+    for (int k = 0; k < 2; ++k)
+        if (sd[k].box) if (int rc = lchd_box_validate(sd[k].box, 1, thr)) return rc;
+    for (int k = 0; k < 2; ++k)
+        if (sd[k].cell) if (int rc = lchd_cell_validate(sd[k].cell, 1, thr)) return rc;
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    if (!out || (n_pairs > 0 && (!anchors || (wgrad && !scores)))) return fail(LCHD_EVALUE, "null anchor / output pointer");
+    for (int64_t p = 0; p < n_pairs; ++p)  // (an index beyond the structure would name a ghost atom of an image cloud)
+        for (int k = 0; k < 2; ++k)
+            if (anchors[2 * p + k] < 0 || anchors[2 * p + k] >= sd[k].n)
+                return fail(LCHD_EPANIC, "index out of bounds: an anchor index is outside its structure (src/locohd.rs:521)");
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    HostTemps t(c);  // clouds[0 .. 1]: what the call runs on; clouds[2 .. 3]: the structures behind image clouds (destroyed after them)
+    auto run = [&]() -> int {
+        for (int k = 0; k < 2; ++k) {
+            lchd_cloud* own = nullptr;
+            if (int rc = lchd_cloud_create(c, sd[k].xyz, sd[k].cat, sd[k].tag, sd[k].n, &own)) return rc;
+            t.clouds[k] = own;
+            if (!sd[k].box && !sd[k].cell) continue;
+            t.clouds[2 + k] = own;
+            t.clouds[k] = nullptr;
+            if (int rc = sd[k].box ? lchd_cloud_create_images(c, own, sd[k].box, 1, thr, &t.clouds[k])
+                                   : lchd_cloud_create_images_cell(c, own, sd[k].cell, 1, thr, &t.clouds[k]))
+                return rc;
+        }
+        return param_sum_host(c, t, ParamSumHostArrays{wgrad, anchors ? anchors : kNoPairs, wf_index, pair_weights, n_pairs, thr, {nullptr, nullptr},
+                                                       tile_pairs, scores, out});
+    };
+    t.rc = run();
+    c->last_valid = false;  // the clouds of this call go away (`t` destroys them on return)
+    c->pend.req.a = c->pend.req.b = nullptr;
+    return t.rc;
+}
+// ... and the dense ones, with the checks of consumer_dense_host in its order
+static int param_sum_coords_host(lchd_ctx* c, const lchd_config* cfg, bool wgrad, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                 int64_t len_seq_b, const double* xyz_a, const double* xyz_b, int64_t n, const int32_t* wf_index,
+                                 const double* cell_a, const double* cell_b, const double* pair_weights, double* scores, double* out) {
+    CTX_LOCK(c);
+    if (n < 0) return fail(LCHD_EVALUE, "negative structure size");
+    if (!c || !cfg) return fail(LCHD_EVALUE, "null context / configuration");
+    if (c->pend.active) return fail(LCHD_EVALUE, "an asynchronous call has not been finished (lchd_ctx_finish)");
+    {
+        const double* const cells[2] = {cell_a, cell_b};
+        MinImageCell rec[2];
+        const MinImageCell* cell[2];
+        if (int rc = reduce_cells(cells, 2, false, rec, cell)) return rc;
+    }
+    CTX_GUARD(c);
+    if (int rc = lchd_ctx_set_config(c, cfg)) return rc;
+    if (int rc = check_wf_index(cfg, wf_index, n)) return rc;
+    if (n > len_seq_a || n > len_seq_b) return fail(LCHD_EPANIC, "index out of bounds: a distance row is longer than its seq");
+    if (!out || (n > 0 && (!seq_a || !seq_b || (wgrad && !scores)))) return fail(LCHD_EVALUE, "null pointer");
+    if (n == 0) {  // (no rows: every sum is +0.0)
+        const size_t n_out = wgrad ? (size_t)c->h_cfg.n_wf * (size_t)c->wf_np_max : (size_t)c->h_cfg.n_categories;
+        for (size_t k = 0; k < n_out; ++k) out[k] = 0.0;
+        return LCHD_OK;
+    }
+    HostTemps t(c);
+    auto run = [&]() -> int {
+        if (int rc = lchd_cloud_create(c, xyz_a, seq_a, nullptr, n, &t.clouds[0])) return rc;
+        if (int rc = lchd_cloud_create(c, xyz_b, seq_b, nullptr, n, &t.clouds[1])) return rc;
+        return param_sum_host(c, t, ParamSumHostArrays{wgrad, nullptr, wf_index, pair_weights, n, 0.0, {cell_a, cell_b}, 0, scores, out});
+    };
+    t.rc = run();
+    c->last_valid = false;
+    c->pend.req.a = c->pend.req.b = nullptr;
+    return t.rc;
+}
+
+extern "C" int lchd_category_gradient_sum_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a,
+                                                     const int32_t* tag_a, int64_t n_a, const double* xyz_b, const int32_t* cat_b,
+                                                     const int32_t* tag_b, int64_t n_b, const int64_t* anchors, const int32_t* wf_index,
+                                                     int64_t n_pairs, double thr, const double* box_a, const double* cell_a, const double* box_b,
+                                                     const double* cell_b, const double* pair_weights, int64_t tile_pairs, double* out) {
+    const ProfilePrimsSide sd[2] = {{xyz_a, cat_a, tag_a, n_a, box_a, cell_a}, {xyz_b, cat_b, tag_b, n_b, box_b, cell_b}};
+    return param_sum_primitives_host(c, cfg, false, sd, anchors, wf_index, n_pairs, thr, pair_weights, tile_pairs, nullptr, out);
+}
+extern "C" int lchd_category_gradient_sum_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                                 int64_t len_seq_b, const double* xyz_a, int64_t n_a, const double* xyz_b, int64_t n_b,
+                                                 const int32_t* wf_index, const double* cell_a, const double* cell_b, const double* pair_weights,
+                                                 double* out) {
+    if (int rc = coords_lengths(xyz_a, n_a, xyz_b, n_b)) return rc;
+    return param_sum_coords_host(c, cfg, false, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, n_a, wf_index, cell_a, cell_b, pair_weights,
+                                 nullptr, out);
+}
+extern "C" int lchd_weight_gradient_sum_primitives(lchd_ctx* c, const lchd_config* cfg, const double* xyz_a, const int32_t* cat_a,
+                                                   const int32_t* tag_a, int64_t n_a, const double* xyz_b, const int32_t* cat_b,
+                                                   const int32_t* tag_b, int64_t n_b, const int64_t* anchors, const int32_t* wf_index,
+                                                   int64_t n_pairs, double thr, const double* pair_weights, int64_t tile_pairs, double* scores,
+                                                   double* out) {
+    const ProfilePrimsSide sd[2] = {{xyz_a, cat_a, tag_a, n_a, nullptr, nullptr}, {xyz_b, cat_b, tag_b, n_b, nullptr, nullptr}};
+    return param_sum_primitives_host(c, cfg, true, sd, anchors, wf_index, n_pairs, thr, pair_weights, tile_pairs, scores, out);
+}
+extern "C" int lchd_weight_gradient_sum_coords(lchd_ctx* c, const lchd_config* cfg, const int32_t* seq_a, int64_t len_seq_a, const int32_t* seq_b,
+                                               int64_t len_seq_b, const double* xyz_a, const double* xyz_b, int64_t n, const int32_t* wf_index,
+                                               const double* pair_weights, double* scores, double* out) {
+    if (int rc = coords_lengths(xyz_a, n, xyz_b, n)) return rc;
+    return param_sum_coords_host(c, cfg, true, seq_a, len_seq_a, seq_b, len_seq_b, xyz_a, xyz_b, n, wf_index, nullptr, nullptr, pair_weights,
+                                 scores, out);
 }

@@ -618,6 +618,25 @@ bool launch_grad_finish(hipStream_t s, int64_t* acc, int64_t n_atoms, double* gr
 constexpr int kStrainMaxBlocks = 512;
 bool launch_strain_accumulate(hipStream_t s, const GradAccumArgs& a, int64_t* acc);  // false: nothing launched (a null array, no disp)
 bool launch_strain_finish(hipStream_t s, int64_t* acc, double* strain_a, double* strain_b);  // strain [9] row-major each; zeroes acc
+// Reduced parameter gradients (lchd_param_sum.hip): the rows of one tile of a per-pair parameter-gradient call times the pair weights,
+// added into exact accumulators acc [n_buckets][width][LCHD_GRAD_LIMBS].  The grid does not grow with the pair count: at most
+// kParamSumMaxBlocks workgroups of four wavefronts (max_blocks > 0: at most that many, the LCHD_PARAM_SUM_BLOCKS hook).
+constexpr int kParamSumMaxBlocks = 512;
+constexpr int kParamSumMaxWidth = 64;  // columns of a row: the categories of a category gradient, the parameters of a weight gradient
+struct ParamSumArgs {
+    const double* rows;        // [P][ld], the first `width` columns of a row are summed; a NaN in column 0: the pair adds nothing
+    const double* weights;     // [P] pair weights of the tile, or null: 1.0
+    const int32_t* bucket;     // [P] the pair's bucket (its weight-function index), or null: every pair adds to bucket 0
+    const double* scores_in;   // [P] the tile's scores, copied to scores_out [P]; both or neither
+    double* scores_out;
+    int64_t* acc;
+    uint32_t* flag;            // LCHD_XS_OUT_OF_RANGE is ORed into it
+    int64_t n_pairs, ld;       // P, the leading dimension of rows
+    int32_t width, n_buckets;
+    int32_t width_pow2;        // (set by the launcher)
+};
+bool launch_param_accumulate(hipStream_t s, const ParamSumArgs& a, int max_blocks);  // false: nothing launched (a null array, a bad shape)
+bool launch_param_finish(hipStream_t s, int64_t* acc, int64_t n, double* out);       // out [n]; zeroes acc
 void launch_mark_overflow(hipStream_t s, const uint32_t* list_a, uint32_t na, const uint32_t* list_b, uint32_t nb, uint32_t* bits_a, uint32_t* bits_b);
 void launch_count_overflow(hipStream_t s, const OverflowSelect& a, unsigned long long* total);
 void launch_write_overflow(hipStream_t s, const OverflowSelect& a);

@@ -8,6 +8,7 @@
  *                                 s, to their limbs -- one 64-bit integer add each (device: one atomic add without a return value).
  *                                 Integer addition is associative: the limbs after any number of adds do not depend on their order.
  *                                 A non-finite s or |s| >= 2^63 adds nothing and ORs LCHD_XS_OUT_OF_RANGE into *flag.
+ *   lchd_xs_add_parts(limbs, r)   the adds of lchd_xs_add for a value already split (lchd_xs_split, r.ok): for a caller that ORs the flag itself.
  *   lchd_xs_finish(limbs)         propagates the carries and returns THE correctly rounded (to nearest, ties to even) double of
  *                                 q * sum t; a sum of exactly 0 is +0.0.
  *
@@ -86,17 +87,22 @@ LCHD_XS_FN void lchd_xs_flag_or(uint32_t *flag, uint32_t v) {
 #endif
 }
 
-LCHD_XS_FN void lchd_xs_add(int64_t *limbs, double s, uint32_t *flag) {
-    const lchd_xs_parts r = lchd_xs_split(s);
+/* limbs += the chunks of one split value (r.ok): at most three limb adds, zero chunks skipped.  For a caller that raises the flag itself. */
+LCHD_XS_FN void lchd_xs_add_parts(int64_t *limbs, const lchd_xs_parts r) {
     int j;
-    if (!r.ok) {
-        lchd_xs_flag_or(flag, LCHD_XS_OUT_OF_RANGE);
-        return;
-    }
     for (j = 0; j < 3; ++j) {
         const int k = r.first + j;
         if (r.chunk[j] && k < LCHD_GRAD_LIMBS) lchd_xs_limb_add(limbs + k, r.negative ? -(int64_t)r.chunk[j] : (int64_t)r.chunk[j]);
     }
+}
+
+LCHD_XS_FN void lchd_xs_add(int64_t *limbs, double s, uint32_t *flag) {
+    const lchd_xs_parts r = lchd_xs_split(s);
+    if (!r.ok) {
+        lchd_xs_flag_or(flag, LCHD_XS_OUT_OF_RANGE);
+        return;
+    }
+    lchd_xs_add_parts(limbs, r);
 }
 
 /* The correctly rounded double of q * (sum of the limbs' chunks); the limbs are read, not changed. */

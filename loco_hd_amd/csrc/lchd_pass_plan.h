@@ -77,6 +77,7 @@ struct Tuning {
     int team_batch = 0;             // LCHD_TEAM_BATCH: pairs per wavefront and batch of the team sweeps (0: team_batch() of lchd_kernels.hip; else rounded to a multiple of the teams, at most 64)
     int team_grid = 0;              // LCHD_TEAM_GRID: at most this many workgroups per team-sweep launch (0: the measured caps of launch_sweep)
     int ensemble_block = 0;         // LCHD_ENSEMBLE_BLOCK: at most this many structures resident in the dense ensemble call's environment store (0: as many as the free HBM holds)
+    int param_sum_blocks = 0;       // LCHD_PARAM_SUM_BLOCKS: at most this many workgroups of k_param_accumulate (0: kParamSumMaxBlocks)
 };
 
 inline int next_pow2_host(int64_t n) {

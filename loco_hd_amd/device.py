@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .api import _CATEGORY_GRADIENT, LoCoHD, MinImageSensitivity, NativeGradient, Nearest, PeriodicSensitivity, Sensitivity, WeightGradient, dense_cells, periodic_boxes, periodic_cells
+from .api import _CATEGORY_GRADIENT, LoCoHD, MinImageSensitivity, NativeGradient, Nearest, PeriodicSensitivity, Sensitivity, WeightGradient, WeightGradientSum, dense_cells, periodic_boxes, periodic_cells
 
 
 def last_sweep_of(ctx):
@@ -428,6 +428,104 @@ class DeviceSession:
             assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= n
             wf_ptr = C.c_void_p(wf_index.data_ptr())
         N.check(N.lib().lchd_weight_gradient_coords_dev(self._ctx, cloud_a, cloud_b, wf_ptr, C.c_void_p(flat.data_ptr())))
+        return res
+
+    # ---- reduced parameter gradients: sum_p v_p dS_p/dw_c and sum_p v_p dS_p/dtheta in one native call ----
+    def _param_sum_args(self, p, pair_weights, wf_index, tile_pairs):
+        """Checked arguments of the four reduced calls: (weights tensor or None, its pointer, wf pointer, tile_pairs)."""
+        torch = self.torch
+        if int(tile_pairs) < 0:
+            raise ValueError(f"tile_pairs = {int(tile_pairs)} is negative (0: planned from the free device memory)")
+        w = wf_ptr = None
+        if pair_weights is not None:
+            if not (pair_weights.dtype.is_floating_point or pair_weights.dtype in (torch.int32, torch.int64)):
+                raise ValueError(f"pair_weights must be real numbers (got dtype {pair_weights.dtype})")
+            if pair_weights.numel() != p:
+                raise ValueError(f"pair_weights has {pair_weights.numel()} entries for {p} pairs")
+            w = pair_weights.detach().to(device=torch.device("cuda", self.device), dtype=torch.float64).reshape(-1).contiguous()
+        if wf_index is not None:
+            assert wf_index.is_cuda and wf_index.dtype == torch.int32 and wf_index.is_contiguous() and wf_index.numel() >= p
+            wf_ptr = C.c_void_p(wf_index.data_ptr())
+        # (`w` lives until the call, which returns with its outputs complete, is over)
+        return w, (None if w is None else C.c_void_p(w.data_ptr())), wf_ptr, int(tile_pairs)
+
+    def _category_sum_out(self, out):
+        torch = self.torch
+        n_cat = int(self._cfg.n_categories)
+        if out is None:
+            out = torch.empty(n_cat, dtype=torch.float64, device=torch.device("cuda", self.device))
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (n_cat,)
+        return out
+
+    def _weight_sum_out(self, p, out):
+        torch = self.torch
+        dev = torch.device("cuda", self.device)
+        shapes = ((p,), (int(self._cfg.n_weight_functions), int(N.lib().lchd_weight_gradient_width(self._ctx))))
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=torch.float64, device=dev) for shape in shapes)
+        for t, shape in zip(out, shapes):
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape
+        return WeightGradientSum(*out)
+
+    def category_gradient_sum(self, cloud_a, cloud_b, anchors, threshold_distance: float, pair_weights=None, wf_index=None, *, tile_pairs=0,
+                              out=None):
+        """sum_p v_p dS_p/dw_c (LoCoHD.category_gradient_sum_from_primitives) over the anchor pairs of two uploaded clouds of any kind, as
+        a torch float64 CUDA tensor [C], in ONE native call (lchd_category_gradient_sum_primitives_dev): the rows of `category_gradient`
+        are reduced on the device, tile by tile, into exact fixed-point accumulators and never reach torch.  anchors: torch int64 CUDA
+        tensor [P][2]; pair_weights: v, a tensor [P] (default: ones); wf_index: torch int32 CUDA tensor [P] or None; tile_pairs: pairs per
+        pass, 0 = planned from the free device memory; out: a float64 CUDA tensor [C], filled and returned.  The bits are a function of
+        the rows and weights alone: the same for every tile size, mode and run.  ValueError if a term is not finite or reaches 2^63."""
+        torch = self.torch
+        assert anchors.is_cuda and anchors.dtype == torch.int64 and anchors.is_contiguous()
+        p = anchors.shape[0]
+        w, w_ptr, wf_ptr, tile = self._param_sum_args(p, pair_weights, wf_index, tile_pairs)
+        out = self._category_sum_out(out)
+        N.check(N.lib().lchd_category_gradient_sum_primitives_dev(self._ctx, cloud_a, cloud_b, C.c_void_p(anchors.data_ptr()), wf_ptr, p,
+                                                                  float(threshold_distance), w_ptr, tile, C.c_void_p(out.data_ptr())))
+        return out
+
+    def category_gradient_sum_coords(self, cloud_a, cloud_b, pair_weights=None, wf_index=None, *, tile_pairs=0, out=None, box_a=None,
+                                     box_b=None, cell_a=None, cell_b=None):
+        """`category_gradient_sum` for the dense row pairs of two uploaded structures of equal size n
+        (LoCoHD.category_gradient_sum_from_coords): pair_weights / wf_index [n] or None; one tile, whatever `tile_pairs` (>= 0) says
+        (lchd_category_gradient_sum_coords_dev)."""
+        for side, box, cell in (("a", box_a, cell_a), ("b", box_b, cell_b)):
+            if box is not None and cell is not None:
+                raise ValueError(f"box_{side} and cell_{side} were both given: a structure has one periodic box or one periodic cell")
+        pc_a = dense_cells(box_a, cell_a, 1, "box_a", "cell_a")
+        pc_b = dense_cells(box_b, cell_b, 1, "box_b", "cell_b")
+        n = int(N.lib().lchd_cloud_size(cloud_a))
+        w, w_ptr, wf_ptr, _ = self._param_sum_args(n, pair_weights, wf_index, tile_pairs)
+        out = self._category_sum_out(out)
+        N.check(N.lib().lchd_category_gradient_sum_coords_dev(self._ctx, cloud_a, cloud_b, wf_ptr, N.dp(pc_a), N.dp(pc_b), w_ptr,
+                                                              C.c_void_p(out.data_ptr())))
+        return out
+
+    def weight_gradient_sum(self, cloud_a, cloud_b, anchors, threshold_distance: float, pair_weights=None, wf_index=None, *, tile_pairs=0,
+                            out=None):
+        """`WeightGradientSum(scores [P], grad [n_wf][NP])` (LoCoHD.weight_gradient_sum_from_primitives) of the anchor pairs of two
+        uploaded structures or batches (no image clouds) in ONE native call (lchd_weight_gradient_sum_primitives_dev): the scores of
+        `weight_gradient`, bit for bit, and per weight function f the exact sum of v_p dS_p/dtheta over the pairs with wf_index[p] = f
+        (all pairs without an index), rounded once, zeros behind f's parameters.  Arguments as `category_gradient_sum`; out: two float64
+        CUDA tensors [P] and [n_wf][NP].  ValueError if a term is not finite or reaches 2^63 (the scores in `out` are then valid)."""
+        torch = self.torch
+        assert anchors.is_cuda and anchors.dtype == torch.int64 and anchors.is_contiguous()
+        p = anchors.shape[0]
+        w, w_ptr, wf_ptr, tile = self._param_sum_args(p, pair_weights, wf_index, tile_pairs)
+        res = self._weight_sum_out(p, out)
+        N.check(N.lib().lchd_weight_gradient_sum_primitives_dev(self._ctx, cloud_a, cloud_b, C.c_void_p(anchors.data_ptr()), wf_ptr, p,
+                                                                float(threshold_distance), w_ptr, tile, C.c_void_p(res.scores.data_ptr()),
+                                                                C.c_void_p(res.grad.data_ptr())))
+        return res
+
+    def weight_gradient_sum_coords(self, cloud_a, cloud_b, pair_weights=None, wf_index=None, *, tile_pairs=0, out=None):
+        """`weight_gradient_sum` for the dense row pairs of two uploaded structures of equal size n
+        (LoCoHD.weight_gradient_sum_from_coords): one tile (lchd_weight_gradient_sum_coords_dev)."""
+        n = int(N.lib().lchd_cloud_size(cloud_a))
+        w, w_ptr, wf_ptr, _ = self._param_sum_args(n, pair_weights, wf_index, tile_pairs)
+        res = self._weight_sum_out(n, out)
+        N.check(N.lib().lchd_weight_gradient_sum_coords_dev(self._ctx, cloud_a, cloud_b, wf_ptr, w_ptr, C.c_void_p(res.scores.data_ptr()),
+                                                            C.c_void_p(res.grad.data_ptr())))
         return res
 
     def set_weight_function(self, params):
